@@ -19,16 +19,26 @@ torch.distributed.run, before this process has touched a GPU); under an external
 rank.  Positions are dealt block-cyclic (nanomod_amd/sharding.py: `chunks` rounds of N equal blocks, each block with
 a +-nb halo of recomputed neighbours), so the all-gather of round c lands as one contiguous piece of the full track
 and runs on RCCL's stream beside the kernels of round c+1.  Two figures are timed: `value` = kernels + all-gather
-(for N=1 there is nothing to gather), and `compute_only` = the kernels alone.
+(for N=1 there is nothing to gather), and with `--full` `compute_only` = the kernels alone.
 
-Before the warm-up one untimed pass is checked against the CPU oracle (the C restatement) on a bounded sample of the
-same input; the result goes into `verify`, and a failed verification makes the exit code non-zero.  The oracle is
-also the `cpu_baseline` (C port on all usable cores and on one; the reference-shaped Python loop on all cores, one spawn
-child per core started before this process touches a GPU).  `value` is the library default (D bit for bit).  The default
-N = 1 run also times — each checked against the oracle first — all three tests + Fisher and int16 rows on the same buffers,
-the rational-D flag, 3-decimal input, one GPU's share of chr20, the ragged preset with KS and with all tests, and the
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last timed step's outputs if
+`--dump-outputs DIR` is given, and prints its record.  `value` is the library default (D bit for bit); `ms_per_step` is
+the wall time of one timed step.
+
+`--full` adds everything else.  Before the warm-up one untimed pass is checked against the CPU oracle (the C restatement)
+on a bounded sample of the same input; the result goes into `verify`, and a failed verification makes the exit code
+non-zero.  The oracle is also the `cpu_baseline` (C port on all usable cores and on one; the reference-shaped Python loop
+on all cores, one spawn child per core started before this process touches a GPU).  N > 1 also times the kernels
+without the all-gather (`compute_only`), and the device copy rate is measured for the roofline.  The N = 1 run also
+times — each checked against the oracle first — all three tests + Fisher and int16 rows on the same buffers, the
+rational-D flag, 3-decimal input, one GPU's share of chr20, the ragged preset with KS and with all tests, and the
 host-resident entry (NMOD_MEM_HOST) on the same rows against the pinned-copy rate measured in the same run (`host_path`).
 Prints ONE JSON line (the last line of stdout) on rank 0.
+
+`--dump-outputs DIR`: the arrays a caller of the timed path receives from its last timed step, as DIR/<name>.npy
+(float64; `status` as float32), on a fixed seeded sample of DUMP_SAMPLE positions (`position.npy` holds their global
+indices) when the genome is larger.  The nb positions at either end of the genome are left out: their window is padded with
+p = 1, which makes their Stouffer statistic -inf by definition.  With the same arguments the inputs are the same from run to run.
 """
 import argparse
 import hashlib
@@ -64,6 +74,7 @@ PRESETS = {
                    name='BASELINE.json configs[4]: skewed ragged coverage, 10 Mb'),
 }
 RAGGED_CLIP0, RAGGED_CLIP1 = (5, 4000), (5, 400)
+DUMP_SAMPLE = 1 << 19           # positions written by --dump-outputs: <= 8 float64 tracks + status + index, < 64 MB
 
 
 def algorithmic_bytes(n0, n1, sample_bytes, k_out, csr):
@@ -615,7 +626,7 @@ def _leg_values(side):
     return out, ok
 
 
-def compact_record(full, side, host_path, drop_in, side_file):
+def compact_record(full, side, host_path, drop_in, side_file, with_side_file=True):
     """The LAST stdout line: the contract's keys + roofline + cpu_baseline + verify, short enough for the driver's 8 KB tail
     (tests/test_bench_launcher.py pins < 8 000 bytes on a canned full record).  Everything verbose — notes, definitions, every
     side leg with its own verification — is in `side_legs_file` and on earlier stdout lines of its own."""
@@ -632,7 +643,7 @@ def compact_record(full, side, host_path, drop_in, side_file):
                                        'spread_milli', 'outlier_permille', 'rccl_ranks') if k in c}
     rec['config']['ks_d'] = 'rational (NMOD_FLAG_KS_RATIONAL_D)' if 'RATIONAL' in c['ks_d'] else 'float form, bit for bit'
     rec['config']['parallelism'] = c['parallelism_short']
-    rec['compute_only'] = full['compute_only']['value']
+    rec['compute_only'] = full['compute_only']['value'] if full['compute_only'] else None
     if full.get('allgather_exposed_ms'):
         rec['allgather_exposed_ms_max'] = full['allgather_exposed_ms']['max']
     rec['roofline'] = {'bound': 'hbm', 'achieved': r['achieved'], 'peak': r['peak'], 'unit': r['unit'], 'frac': r['frac'],
@@ -645,12 +656,13 @@ def compact_record(full, side, host_path, drop_in, side_file):
                    'attached_from': full['valu']['source']}
     if full.get('form_share') is not None:
         rec['form_share'] = full['form_share']
-    rec['verify'] = {'ok': bool(v.get('ok')), 'positions': v.get('positions'), 'against': 'oracle/nanomod_oracle.c, same input',
-                     'max_rel_err_p': max(errs_p) if errs_p else None, 'max_abs_err_p': max(errs_abs_p) if errs_abs_p else None,
-                     'max_abs_err_ks_d': v.get('max_abs_err_ks_d'), 'max_abs_err_mwu_u': v.get('max_abs_err_mwu_u')}
-    for k in ('gathered_track_equals_local', 'block_boundaries_checked', 'block_boundary_positions_differing'):
-        if k in v:
-            rec['verify'][k] = v[k]
+    if full['verify'] is not None:                                   # (--full only: a plain run checks nothing)
+        rec['verify'] = {'ok': bool(v.get('ok')), 'positions': v.get('positions'), 'against': 'oracle/nanomod_oracle.c, same input',
+                         'max_rel_err_p': max(errs_p) if errs_p else None, 'max_abs_err_p': max(errs_abs_p) if errs_abs_p else None,
+                         'max_abs_err_ks_d': v.get('max_abs_err_ks_d'), 'max_abs_err_mwu_u': v.get('max_abs_err_mwu_u')}
+        for k in ('gathered_track_equals_local', 'block_boundaries_checked', 'block_boundary_positions_differing'):
+            if k in v:
+                rec['verify'][k] = v[k]
     if cb is not None:
         rec['cpu_baseline'] = {'value': cb['value'], 'unit': cb['unit'], 'cores': cb['cores'], 'kind': cb['kind'],
                                'cpu_model': cb.get('cpu_model'), 'sample': cb['sample_short'],
@@ -669,8 +681,9 @@ def compact_record(full, side, host_path, drop_in, side_file):
         big = drop_in.get('at_200v200', {}).get('arrays')
         if big:
             rec['drop_in_mtest2']['at_200v200'] = big['positions_per_s']
-    rec['side_legs_file'] = side_file
-    rec['leg_seconds'] = full.get('leg_seconds')
+    if with_side_file:
+        rec['side_legs_file'] = side_file
+        rec['leg_seconds'] = full.get('leg_seconds')
     rec['build_info'] = full['build_info_short']
     rec['lib_sha16'] = full.get('lib_sha16')
     rec = _sig(rec)
@@ -788,7 +801,15 @@ def main():
     ap.add_argument('--rational-d', action='store_true', help='KS-only configurations: time NMOD_FLAG_KS_RATIONAL_D (D as the exact rational, <= 2 ulp '
                     'from ks_2samp\'s float form) instead of the library default (D bit for bit); the default run reports this rate as a side figure')
     ap.add_argument('--launch-only', action='store_true', help='ranks print RANK / WORLD_SIZE and exit before any GPU call (launcher test)')
+    ap.add_argument('--full', action='store_true', help='also verify against the oracle, time the CPU baseline, the side legs, the host-resident '
+                    'and drop-in legs and the other presets, and write the side file; a plain run only times the K steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s outputs as DIR/<name>.npy '
+                    '(a fixed seeded sample of %d positions when there are more)' % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -806,7 +827,7 @@ def main():
     # the reference-shaped CPU leg: one fresh process per usable core, started BEFORE this process touches a GPU (they idle
     # until the CPU-baseline leg and never load the HIP library)
     refpy = None
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu:
         pz = PRESETS[args.config]
         at = bool(args.all_tests or pz['all_tests'])
         refpy = start_refpy_workers({'seed': SEED, 'n0': args.n0 or pz['n0'], 'n1': args.n1 or pz['n1'], 'csr': pz['layout'] == 'csr',
@@ -1019,15 +1040,46 @@ def main():
         out['counting_rejected'] = round(st['count_rejected'] / n, 6)
         return out
 
-    # ---- one untimed pass, checked on rank 0 against the CPU oracle on a bounded sample of the same input
-    step(gather)
-    state.wait()
-    torch.cuda.synchronize()
-    headline_share = form_share(det.dispatch_stats())          # (of the pass's last block)
+    def dump_outputs(dirname):
+        """the last timed step's outputs as a caller receives them: the gathered tracks (N > 1 or a forced collective), else every
+        track of this rank's blocks without their halos, on a fixed seeded sample of the genome's positions.  The sample leaves out
+        the nb positions at either end of the genome: their window reaches past it and is padded with p = 1 (myDetect.py:373-414),
+        so their Stouffer statistic is -inf in every build and compares nothing"""
+        if gather:
+            state.wait()
+            tracks = state.result()
+        inner = total - 2 * NB
+        k = min(inner, DUMP_SAMPLE)
+        pos = NB + (np.arange(inner, dtype=np.int64) if k == inner else np.sort(np.random.default_rng(SEED).choice(inner, k, replace=False)))
+        out = {'position': pos.astype(np.float64)}
+        if gather:
+            sel = torch.from_numpy(pos).to(dev)
+            for name, v in tracks.items():
+                out[name] = v.index_select(0, sel).cpu().numpy()
+        else:
+            parts = {}
+            for c, b in enumerate(blocks):
+                lo, hi = sharding.cyclic_block(total, world, rank, chunks, c)
+                a0, a1 = np.searchsorted(pos, (lo, hi))
+                sel = torch.from_numpy(pos[a0:a1] - b['lo_h']).to(dev)
+                for name, v in b['out'].items():
+                    parts.setdefault(name, []).append(v.index_select(0, sel).cpu().numpy())
+            for name, v in parts.items():
+                out[name] = np.concatenate(v)
+        os.makedirs(dirname, exist_ok=True)
+        for name, v in out.items():
+            np.save(os.path.join(dirname, name + '.npy'), v.astype(np.float32 if v.dtype.itemsize < 4 else np.float64))
+
     verify = None
     cpu_rows = None
-    mean_n = samples_local / max(n_local, 1)
-    if rank == 0:
+    headline_share = None
+    # ---- (--full) one untimed pass, checked on rank 0 against the CPU oracle on a bounded sample of the same input
+    if args.full:
+        step(gather)
+        state.wait()
+        torch.cuda.synchronize()
+        headline_share = form_share(det.dispatch_stats())          # (of the pass's last block)
+    if args.full and rank == 0:
         cap_default = 1_000_000 if not csr else 200_000
         cap = min(args.cpu_sample or cap_default, blocks[0]['n'])
         cpu_rows = host_rows(cap)
@@ -1091,17 +1143,21 @@ def main():
     det.timer = timer
     elapsed = timed(gather, args.steps)
     det.timer = None
-    compute_elapsed = elapsed
-    if gather:                                       # second figure: the kernels alone, same K
+    if headline_share is None:
+        headline_share = form_share(det.dispatch_stats())      # (of the last timed step's last block)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
+    compute_elapsed = None if gather else elapsed
+    if gather and args.full:                         # second figure: the kernels alone, same K
         compute_elapsed = timed(False, args.steps)
 
     k1_ms, k1_n = timer.read(L.KERNEL_RANK_STATS)
     k2_ms, _ = timer.read(L.KERNEL_FINALIZE)
     k3_ms, _ = timer.read(L.KERNEL_COMBINE)
 
-    # measured device copy bandwidth (read + write bytes over the time of dst.copy_(src), 1 GiB each way)
+    # (--full) measured device copy bandwidth (read + write bytes over the time of dst.copy_(src), 1 GiB each way)
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         dst = torch.empty_like(src)
         for _ in range(3):
@@ -1173,7 +1229,7 @@ def main():
         t_leg[0] = now
 
     leg_done('headline')
-    simple = world == 1 and not csr and not args.force_collective and not args.no_side and chunks == 1
+    simple = args.full and world == 1 and not csr and not args.force_collective and not args.no_side and chunks == 1
     headline_default = simple and args.config == 'ecoli' and args.dtype == 'f32' and args.ties == 'few' and not all_tests and args.spread == 0
     if headline_default and 'all_tests' in legs:
         # (a) all three tests + Fisher on the same buffers: what every real getKStest call computes (myDetect.py:331-343), BASELINE configs[2]
@@ -1340,7 +1396,7 @@ def main():
 
     # ---- the host-resident entry on the same rows (NMOD_MEM_HOST): PCIe-bound, its own roofline
     host_path = None
-    if world == 1 and not csr and not args.no_host_path and chunks == 1 and not args.force_collective and ('host_path' in legs or not headline_default):
+    if args.full and world == 1 and not csr and not args.no_host_path and chunks == 1 and not args.force_collective and ('host_path' in legs or not headline_default):
         host_path = host_path_leg(nm, torch, local_rank, blocks, n0, n1, NB, WDIF, method, tests,
                                   want_i16=(args.dtype == 'f32'), ref_out=blocks[0]['out'], flags=det.flags)
         bad = [k for k, v in host_path.items() if isinstance(v, dict) and (v.get('equals_device_resident_pass') is False or v.get('equals_int16_pass') is False)]
@@ -1459,7 +1515,8 @@ def main():
                                     {'per_rank': exposed['per_rank_ms'], 'max': max(exposed['per_rank_ms']), 'steps': args.steps,
                                      'note': 'HIP-event time between the last round\'s kernels and the end of the last outstanding all-gather on each '
                                              'rank\'s compute stream, after the K timed steps: the part of the gather that no kernel hides'},
-            'compute_only': {'value': total * args.steps / compute_elapsed, 'unit': 'positions/s',
+            'compute_only': None if compute_elapsed is None else
+                            {'value': total * args.steps / compute_elapsed, 'unit': 'positions/s',
                              'ms_per_step': compute_elapsed / args.steps * 1e3,
                              'note': 'the same K steps without the all-gather (tracks stay sharded)' if gather else
                                      'identical to value: one rank has nothing to gather'},
@@ -1496,11 +1553,12 @@ def main():
             line['lib_sha16'] = hashlib.sha256(open(L.LIB_PATH, 'rb').read()).hexdigest()[:16]
         except OSError:
             line['lib_sha16'] = None
-        if not args.no_cpu and world == 1:           # the CPU baseline is an N=1 figure
+        if args.full and not args.no_cpu and world == 1:           # the CPU baseline is an N=1 figure
             line['cpu_baseline'] = cpu_baseline(cpu_rows, '%s, %s' % (reads_txt, tests_txt), method, 7 if all_tests else 1, usable_cpus(), refpy=refpy)
             leg_done('cpu_baseline')
-        line['leg_seconds'] = leg_seconds
-    ok = torch.tensor([1 if (rank != 0 or verify['ok']) else 0], device=dev)
+        if args.full:
+            line['leg_seconds'] = leg_seconds
+    ok = torch.tensor([1 if (rank != 0 or verify is None or verify['ok']) else 0], device=dev)
     if dist is not None:
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         dist.barrier()
@@ -1513,23 +1571,25 @@ def main():
         except Exception:
             pass
         sys.stdout.flush()
-        # the verbose record and every side leg go to the side file (each leg was a stdout line of its own when it finished); the LAST
-        # stdout line is the compact record the driver parses
-        full = dict(line)
-        full['side_legs'] = dict(side)
-        if host_path is not None:
-            full['host_path'] = host_path
-        if drop_in is not None:
-            full['drop_in_mtest2'] = drop_in
-        side_file = args.side_file
-        try:
-            with open(side_file, 'w') as f:
-                json.dump(full, f, indent=1)
-        except OSError as e:
-            print('bench.py: could not write %s: %s' % (side_file, e), file=sys.stderr)
-            side_file = None
-        rel = os.path.relpath(side_file, ROOT) if side_file else None
-        rec_, text = compact_record(line, side, host_path, drop_in, rel)
+        # (--full) the verbose record and every side leg go to the side file (each leg was a stdout line of its own when it finished);
+        # the LAST stdout line is the compact record the driver parses
+        rel = None
+        if args.full:
+            full = dict(line)
+            full['side_legs'] = dict(side)
+            if host_path is not None:
+                full['host_path'] = host_path
+            if drop_in is not None:
+                full['drop_in_mtest2'] = drop_in
+            side_file = args.side_file
+            try:
+                with open(side_file, 'w') as f:
+                    json.dump(full, f, indent=1)
+            except OSError as e:
+                print('bench.py: could not write %s: %s' % (side_file, e), file=sys.stderr)
+                side_file = None
+            rel = os.path.relpath(side_file, ROOT) if side_file else None
+        rec_, text = compact_record(line, side, host_path, drop_in, rel, with_side_file=args.full)
         emit_line(text)
     if int(ok.item()) == 0:
         sys.exit(3)                                  # a numerically wrong build must not look like a benchmark record

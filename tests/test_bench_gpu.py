@@ -1,6 +1,7 @@
 """-m gpu: bench.py end to end at small sizes — flag combinations whose legs interact (the rational-D flag through the side legs
 and the host-resident leg, the ragged preset with all tests on 3-decimal input, the forced collective with the boundary check):
-the line parses, every verification in it holds, the exit code is 0."""
+the line parses, every verification in it holds, the exit code is 0 (all with `--full`); and the plain run, which only times
+its steps, with the outputs it dumps."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _bench(args):
         env.pop(k, None)
     with tempfile.TemporaryDirectory() as tmp:
         side = os.path.join(tmp, 'side.json')
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args + ['--steps', '2', '--warmup', '1', '--no-cpu', '--side-file', side],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full'] + args + ['--steps', '2', '--warmup', '1', '--no-cpu', '--side-file', side],
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = r.stdout.strip().splitlines()
@@ -109,3 +110,53 @@ def test_drop_in_leg_on_the_reference_dict_shape():
     assert big['reads_per_group'] == 200 and big['arrays']['verify_ok'] and big['arrays']['table_lines'] == 460000
     st = big['arrays']['stages']
     assert st['h2d_bytes'] >= 460000 * 400 * 2 and all(st[k] > 0 for k in ('build_csr_s', 'detect_host_s', 'rank_order_s', 'write_table_s'))      # (float64 rows on the 0.001 grid: narrowed to int16 on the way)
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one():
+    """a plain run (no `--full`): exactly --steps timed steps, no verification or side legs in the line, no side file; the
+    --dump-outputs arrays are the last step's tracks of every position but the nb at either end of the genome (fewer than
+    DUMP_SAMPLE here), finite, equal to the oracle on the same rows and identical from run to run"""
+    import tempfile
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, 'oracle'))
+    import bench
+    import oracle_c
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'NMOD_NO_COUNTING', 'NMOD_NO_COUNT_WIDE'):
+        env.pop(k, None)
+    P, n = 100_000, 200
+    dumps = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for i in range(2):
+            d = os.path.join(tmp, 'out%d' % i)
+            r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--positions', str(P),
+                                '--dump-outputs', d, '--side-file', os.path.join(tmp, 'side.json')],
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            c = json.loads(r.stdout.strip().splitlines()[-1])
+            assert c['steps'] == 3 and c['warmup'] == 1 and c['ms_per_step'] > 0 and c['value'] > 0 and c['unit'] == 'positions/s'
+            assert c['higher_is_better'] is True and c['metric'] == 'genomic positions/sec (KS + Stouffer)' and c['dtype'].startswith('f32')
+            assert c['roofline']['launches_timed'] == 3 and c['roofline']['kernel_avg_ms'] > 0
+            for k in ('verify', 'cpu_baseline', 'side', 'host_path', 'drop_in_mtest2', 'side_legs_file'):
+                assert k not in c, k
+            assert not os.path.exists(os.path.join(tmp, 'side.json'))
+            names = sorted(f[:-4] for f in os.listdir(d))
+            assert names == ['comb_p', 'comb_st', 'ks_d', 'ks_p', 'position', 'status'], names
+            arrs = {k: np.load(os.path.join(d, k + '.npy')) for k in names}
+            assert all(a.dtype in (np.float32, np.float64) and a.shape == (P - 2 * bench.NB,) and np.isfinite(a).all() for a in arrs.values())
+            dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True) for k in dumps[0])
+    got = dumps[0]
+    assert np.array_equal(got['position'], np.arange(bench.NB, P - bench.NB, dtype=np.float64))
+    vn = 2000
+    a = bench.synth_rows(bench.SEED, 0, vn, 0, n, bench.PLANT_PERIOD, bench.PLANT_SHIFT, False).reshape(-1)
+    b = bench.synth_rows(bench.SEED, 0, vn, 1, n, bench.PLANT_PERIOD, bench.PLANT_SHIFT, False).reshape(-1)
+    off = np.arange(0, (vn + 1) * n, n, dtype=np.int64)
+    exp = oracle_c.detect_batch(a, off, b, off, np.zeros(vn, np.int32), bench.NB, bench.WDIF, 'stouffer', tests=1)
+    # dumped index j is position j + nb; the oracle's last nb positions have neighbours beyond its rows
+    g_, e_ = slice(0, vn - 2 * bench.NB), slice(bench.NB, vn - bench.NB)
+    assert np.array_equal(got['ks_d'][g_], exp['ks_d'][e_]) and np.array_equal(got['status'][g_], exp['status'][e_])
+    for k in ('ks_p', 'comb_st', 'comb_p'):
+        e = exp[k][e_]
+        assert np.all(np.abs(got[k][g_] - e) <= 1e-9 * np.abs(e) + (1e-12 if k == 'comb_st' else 1e-300)), k

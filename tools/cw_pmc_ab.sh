@@ -10,7 +10,7 @@ for LIB in $LIBS; do
   echo "== $(basename $LIB) outliers $O"
   for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES" "SQC_ICACHE_REQ SQC_ICACHE_MISSES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT"; do
     D=/tmp/cwpmc; rm -rf $D
-    rocprofv3 --pmc $grp --output-format csv -d $D -- python3 $R/bench.py --config ragged --all-tests --positions 2000000 --dtype i16 --spread 200 --outliers $O --steps 2 --warmup 1 --no-cpu --no-side --no-host-path --side-file /tmp/pmc_side.json > /dev/null 2> $D.err
+    rocprofv3 --pmc $grp --output-format csv -d $D -- python3 $R/bench.py --full --config ragged --all-tests --positions 2000000 --dtype i16 --spread 200 --outliers $O --steps 2 --warmup 1 --no-cpu --no-side --no-host-path --side-file /tmp/pmc_side.json > /dev/null 2> $D.err
     python3 - "$D" <<'PY'
 import csv,glob,collections,sys
 d=collections.defaultdict(float); n=collections.defaultdict(int)

@@ -78,7 +78,7 @@ SIDE = '/tmp/prof_side.json'
 
 def bench_line(extra, steps=20, warmup=5, keep_side=None):
     """the LAST stdout line (the compact record); the verbose record + side legs (bench.py --side-file) go to `keep_side`"""
-    r = run(['python3', BENCH, '--steps', str(steps), '--warmup', str(warmup), '--side-file', SIDE] + extra)      # (a later --steps in `extra` wins)
+    r = run(['python3', BENCH, '--full', '--steps', str(steps), '--warmup', str(warmup), '--side-file', SIDE] + extra)      # (a later --steps in `extra` wins)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     if keep_side and os.path.exists(SIDE):
         shutil.copy(SIDE, keep_side)
@@ -104,7 +104,7 @@ for cfg, extra in CONFIGS:
     # kernel trace + stats
     d = '/tmp/prof_%s_trace' % cfg
     shutil.rmtree(d, ignore_errors=True)
-    r = run(['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', 'python3', BENCH, '--steps', '10', '--warmup', '3', '--no-cpu', '--no-side', '--no-host-path', '--side-file', SIDE] + extra)
+    r = run(['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', 'python3', BENCH, '--full', '--steps', '10', '--warmup', '3', '--no-cpu', '--no-side', '--no-host-path', '--side-file', SIDE] + extra)
     under = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     for f in glob.glob(d + '/*/*kernel_stats.csv'):
         shutil.copy(f, os.path.join(OUT, '%s_%s_kernel_stats.csv' % (TAG, cfg)))
@@ -117,7 +117,7 @@ for cfg, extra in CONFIGS:
     for gi, group in enumerate(PMC_GROUPS):
         d = '/tmp/prof_%s_pmc%d' % (cfg, gi)
         shutil.rmtree(d, ignore_errors=True)
-        run(['rocprofv3', '--pmc'] + group + ['--output-format', 'csv', '-d', d, '--', 'python3', BENCH] + extra + ['--steps', '2', '--warmup', '1', '--no-cpu', '--no-side', '--no-host-path', '--side-file', SIDE])
+        run(['rocprofv3', '--pmc'] + group + ['--output-format', 'csv', '-d', d, '--', 'python3', BENCH, '--full'] + extra + ['--steps', '2', '--warmup', '1', '--no-cpu', '--no-side', '--no-host-path', '--side-file', SIDE])
         vals, meta = k1_rows(d + '/*/*counter_collection.csv', 'Counter_Name')
         # per bench step: 4 passes of the hot path run under the profiler (verify, warm-up, 2 timed); a ragged pass is
         # many size-class launches, so the counters are summed over the K1 kernels and divided by the passes

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/quick_bench.sh "<bench args>" ... : one short line per configuration (GPU box)
 for a in "$@"; do
-  python bench.py $a --steps 20 --warmup 5 --no-cpu 2>/dev/null | python -c "
+  python bench.py --full $a --steps 20 --warmup 5 --no-cpu 2>/dev/null | python -c "
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 try:

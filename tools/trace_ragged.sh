@@ -3,7 +3,7 @@
 cd /tmp; export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/p5
-rocprofv3 --kernel-trace --output-format csv -d /tmp/p5 -- python3 $R/bench.py --config ragged --all-tests --steps 2 --warmup 1 --no-cpu "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/p5 -- python3 $R/bench.py --full --config ragged --all-tests --steps 2 --warmup 1 --no-cpu "$@" > /dev/null 2>&1
 python3 - <<PY
 import csv,glob,re
 rows=[]
