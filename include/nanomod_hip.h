@@ -79,7 +79,8 @@ enum {
   NMOD_STATUS_MWU_ALL_IDENTICAL = 1, /* scipy 1.2.1 mannwhitneyu raises ValueError (T == 0), uncaught at myDetect.py:331 */
   NMOD_STATUS_T_NAN = 2,             /* zero variance in both groups: ttest_ind returns (nan, nan), myDetect.py:335 */
   NMOD_STATUS_EMPTY = 4,             /* n0 == 0 or n1 == 0 (cannot occur after mfilter_coverage, myDetect.py:301-314) */
-  NMOD_STATUS_TOO_LARGE = 8,         /* more samples in a group than the max_n0 / max_n1 the caller promised, or than NMOD_MAX_RANKED:
+  NMOD_STATUS_TOO_LARGE = 8,         /* more samples in a group than the max_n0 / max_n1 the caller promised, or than NMOD_MAX_RANKED
+                                        (NMOD_MAX_DEEP with NMOD_FLAG_DEEP):
                                         the position is skipped, its outputs are NaN, the rest of the batch is computed */
   NMOD_STATUS_NONFINITE = 16         /* a NaN or infinite sample (see the header comment): the position's statistics are unspecified */
 };
@@ -99,7 +100,10 @@ enum {
                                  smaller one in KS-only mode); positions beyond it take the workgroup-per-position
                                  pass (big_rank.hpp), slower but unlimited up to NMOD_MAX_RANKED */
 #define NMOD_MAX_RANKED 65535 /* max samples per group per position in any mode (16-bit ranks, 32-bit KS numerator); a position
-                                 beyond it gets NMOD_STATUS_TOO_LARGE */
+                                 beyond it gets NMOD_STATUS_TOO_LARGE — unless NMOD_FLAG_DEEP is set */
+#define NMOD_MAX_DEEP 16777215 /* 2^24 - 1: max samples per group with NMOD_FLAG_DEEP (deep_rank.hpp: n0 n1 < 2^48, so the KS
+                                  numerator is exact in uint64 / fp64; twice the rank sum < 2^51, exact in fp64; the tie term
+                                  sum (t^3 - t) < 2^75 is summed in 128 bits and rounded once) */
 #define NMOD_MAX_NB 64        /* max --neighborPvalues */
 
 typedef struct nmod_params {
@@ -145,6 +149,14 @@ typedef struct nmod_params {
  * statistics are the same bit for bit, the Welch moments come from exact integer sums instead of the two-pass float64 sums
  * (both within 1e-11 of the reference's t).  This flag sends every chunk as float64 (A/B, parity tests). */
 #define NMOD_FLAG_NO_HOST_NARROW 16
+/* Deep coverage (amplicon / plasmid runs: NanoMod's own examples put more than 65 535 reads on a base, and the reference tests
+ * whatever it is given): a position with a group beyond NMOD_MAX_RANKED, both groups within NMOD_MAX_DEEP, is computed in every
+ * mode (all tests, KS-only, NMOD_FLAG_KS_RATIONAL_D, want_mstd; every dtype — float64 samples are sorted as 64-bit keys; CSR or
+ * fixed stride; both memspaces; nmod_downsample_ks) by the multi-workgroup deep form (deep_rank.hpp) instead
+ * of being skipped with NMOD_STATUS_TOO_LARGE.  Its scratch comes from the library's pool (rounds of at most 2^27 keys; the
+ * workspace size does not change); the host round trip is the one the large-position pass makes.  Without the flag a position
+ * beyond NMOD_MAX_RANKED is NMOD_STATUS_TOO_LARGE as before; beyond NMOD_MAX_DEEP it is with the flag too. */
+#define NMOD_FLAG_DEEP 32
 
 /* Caller-allocated SoA outputs, npos elements each; a NULL member is skipped.
  * One (stat, p) pair per test = the tuples getKStest returns
@@ -233,7 +245,8 @@ typedef struct nmod_dispatch_stats {
   int64_t count_tried;      /* positions of the classes whose probe let a counting form run */
   int64_t count_rejected;   /* ... that the counting form handed on to the class's sorting form (counted there above) */
   int64_t f64_redo;         /* NMOD_DTYPE_F64: positions done again on 64-bit keys (their first form counts them as well) */
-  int64_t reserved[4];
+  int64_t deep;             /* the deep form (NMOD_FLAG_DEEP): a group beyond NMOD_MAX_RANKED */
+  int64_t reserved[3];
 } nmod_dispatch_stats;
 int nmod_last_dispatch_stats(nmod_dispatch_stats* st);
 
@@ -248,7 +261,8 @@ const char* nmod_build_info(void);
 
 /* Name of the K1 kernel instance a position with n0 / n1 samples is dispatched to under prm's dtype / tests / method
  * (e.g. "ks_rank_kernel<16,16,f32>"), from the same size-class functions the dispatcher uses: what bench.py prints as
- * roofline.kernel and what the rocprofv3 kernel trace shows.  No device work. */
+ * roofline.kernel and what the rocprofv3 kernel trace shows.  No device work.  A group beyond NMOD_MAX_RANKED:
+ * NMOD_ERR_TOO_LARGE, or with NMOD_FLAG_DEEP and both groups within NMOD_MAX_DEEP "deep_rank_kernel<f32|i16|f64>". */
 int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char* buf, int32_t buflen);
 
 /* Returns the slabs cached in the library's scratch pool of `device` to the driver (see the header comment), and frees the
@@ -268,7 +282,8 @@ int nmod_combine_track(const nmod_params* prm, int64_t npos,
  * (--downsampling_quantile, 0.25) of the p-sorted resamples is written to ks_d[i] / ks_p[i].  The reference draws from numpy's
  * unseeded global generator; here the draws are a counter-based function of (seed, i, iteration, group, draw) on the device —
  * reproducible, statistically equivalent, not bit-comparable (SURVEY.md 8a row A3').  The resampled rows are materialised in
- * HBM chunk by chunk (2^27 samples) and go through the same KS kernel as everything else.  Synchronises. */
+ * HBM chunk by chunk (2^27 samples) and go through the same KS kernel as everything else.  Groups (and cov) beyond
+ * NMOD_MAX_RANKED need NMOD_FLAG_DEEP in prm->flags (NMOD_ERR_TOO_LARGE otherwise); the flag is passed on to the KS batch.  Synchronises. */
 int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, const int64_t* off0, const void* sig1, const int64_t* off1,
                        const int64_t* positions, const int64_t* cov, int32_t iters, double quantile, uint64_t seed,
                        double* ks_d, double* ks_p);

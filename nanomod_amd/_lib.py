@@ -18,10 +18,12 @@ MEM_HOST, MEM_DEVICE = 0, 1
 METHOD_KS, METHOD_STOUFFER, METHOD_FISHER = 0, 1, 2
 TEST_KS, TEST_MWU, TEST_WELCH, TEST_ALL = 1, 2, 4, 7
 FLAG_KS_RATIONAL_D, FLAG_CHECK_FINITE, FLAG_NO_COUNTING, FLAG_NO_COUNT_WIDE, FLAG_NO_HOST_NARROW = 1, 2, 4, 8, 16
+FLAG_DEEP = 32            # groups beyond MAX_RANKED (up to MAX_DEEP) take the deep form instead of STATUS_TOO_LARGE
 STATUS_MWU_ALL_IDENTICAL, STATUS_T_NAN, STATUS_EMPTY, STATUS_TOO_LARGE, STATUS_NONFINITE = 1, 2, 4, 8, 16
 KERNEL_RANK_STATS, KERNEL_FINALIZE, KERNEL_COMBINE, KERNEL_SYNTH = 0, 1, 2, 3
 MAX_GROUP = 2048          # largest group of the wave-resident kernels; larger ones (<= MAX_RANKED) take big_rank_kernel
 MAX_RANKED = 65535
+MAX_DEEP = 2 ** 24 - 1    # largest group with FLAG_DEEP
 MAX_NB = 64
 COMM_ID_BYTES = 128
 ERR_NO_RCCL, ERR_RCCL = -6, -7
@@ -51,7 +53,7 @@ class NmodHostStats(C.Structure):
 
 class NmodDispatchStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ('positions', 'ks_rank', 'rank_hist', 'rank_hist_wide', 'rank_pair', 'rank_count', 'rank_count_wide',
-                                         'big', 'skipped', 'count_tried', 'count_rejected', 'f64_redo')] + [('reserved', C.c_int64 * 4)]
+                                         'big', 'skipped', 'count_tried', 'count_rejected', 'f64_redo', 'deep')] + [('reserved', C.c_int64 * 3)]
 
 
 def last_dispatch_stats():

@@ -51,6 +51,9 @@ def build_parser():
     d.add_argument('--coverages', type=str, default='0-0')                             # NanoMod.py:392
     d.add_argument('--seed', type=int, default=0, help='seed of the down-sampling draws (the reference is unseeded)')
     d.add_argument('--device', type=int, default=0)
+    d.add_argument('--deepCoverage', type=int, default=0, choices=[0, 1],
+                   help='1: test positions with a group beyond 65 535 samples (amplicon / plasmid runs) on the deep form '
+                   'instead of reporting NaN for them (moptions[\'nmod_deep\'])')
     d.add_argument('--fast5Reader', default='', help="module:function used to read one resquiggled read file, path -> "
                    "(mapped_chrom, mapped_start, mapped_strand, norm_mean[], base[]) | None; default: the h5py reader of "
                    "nanomod_amd.fast5_ingest (Events table + Alignment attributes, myFast5.py:92-126)")
@@ -178,7 +181,13 @@ def load_input(path, a, log=print):
     return g
 
 
+def nmod_options(a):
+    """The moptions keys of this build (detect.mtest2) that the command line sets."""
+    return {'nmod_device': a.device, 'nmod_seed': a.seed, 'nmod_deep': int(a.deepCoverage)}
+
+
 def run_detect(a, log=print):
+    deep = bool(nmod_options(a)['nmod_deep'])
     engine.warm_up(a.device)                                    # HIP start-up beside the loading of the inputs
     g0, g1 = load_input(a.wrkBase1, a, log), load_input(a.wrkBase2, a, log)
     t0 = time.time()
@@ -188,14 +197,14 @@ def run_detect(a, log=print):
     method, nb = a.testMethod, a.neighborPvalues
     dev_method = method if (method in ('stouffer', 'fisher') and nb > 0) else 'ks'
     res = engine.detect_host(sig0, off0, sig1, off1, rid, nb=nb, weights_dif=a.WeightsDif, method=dev_method,
-                             want_mstd=a.mstd != 0, device=a.device)
+                             want_mstd=a.mstd != 0, device=a.device, deep=deep)
     if npos and np.any(res['status'] & L.STATUS_MWU_ALL_IDENTICAL):
         raise ValueError('All numbers are identical in mannwhitneyu')                  # scipy 1.2.1, uncaught in the reference
     cov = [int(x) for x in a.coverages.split('-')]                                     # NanoMod.py:174-176
     if npos:
         detect.downsample_update(res, sig0, off0, sig1, off1, rid, strand, cov * 2 if len(cov) == 1 else cov,
                                  iters=a.downsampling, quantile=a.downsampling_quantile, seed=a.seed, nb=nb,
-                                 weights_dif=a.WeightsDif, method=dev_method, device=a.device)
+                                 weights_dif=a.WeightsDif, method=dev_method, device=a.device, deep=deep)
     if a.outLevel <= detect.OUTPUT_INFO:
         log('Producing pvalues: consuming time %d' % (time.time() - t0))
     if method != 'ks' and nb == 0:                                                     # myDetect.py:413

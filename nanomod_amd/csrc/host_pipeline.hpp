@@ -277,8 +277,10 @@ static int detect_host_pipelined(const nmod_params* prm, int64_t npos, const voi
   int64_t m0 = csr0 ? 0 : prm->stride0, m1 = csr1 ? 0 : prm->stride1;
   if (csr0) for (int64_t i = 0; i < npos; ++i) { const int64_t n = off0[i + 1] - off0[i]; if (n < 0) return NMOD_ERR_INVALID_ARG; m0 = std::max(m0, n); }
   if (csr1) for (int64_t i = 0; i < npos; ++i) { const int64_t n = off1[i + 1] - off1[i]; if (n < 0) return NMOD_ERR_INVALID_ARG; m1 = std::max(m1, n); }
-  // (a group beyond NMOD_MAX_RANKED: the device skips that position and flags it NMOD_STATUS_TOO_LARGE; its rows still cross the bus)
-  const int64_t lim0 = std::min<int64_t>(m0, NMOD_MAX_RANKED), lim1 = std::min<int64_t>(m1, NMOD_MAX_RANKED);
+  // (a group beyond NMOD_MAX_RANKED — NMOD_MAX_DEEP with NMOD_FLAG_DEEP: the device skips that position and flags it NMOD_STATUS_TOO_LARGE;
+  // its rows still cross the bus.  A chunk always holds whole positions, at least one, and the slots are sized for the largest chunk)
+  const int64_t group_cap = (prm->flags & NMOD_FLAG_DEEP) ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;
+  const int64_t lim0 = std::min<int64_t>(m0, group_cap), lim1 = std::min<int64_t>(m1, group_cap);
   auto row0 = [&](int64_t i) { return csr0 ? off0[i] : i * prm->stride0; };     // first sample of position i (element index)
   auto row1 = [&](int64_t i) { return csr1 ? off1[i] : i * prm->stride1; };
   const int64_t total_bytes = (row0(npos) - row0(0) + row1(npos) - row1(0)) * (int64_t)esz;

@@ -21,6 +21,7 @@
 #include "rank_stats_launch.hpp"
 #include "pvalue_kernels.hpp"
 #include "big_rank.hpp"
+#include "deep_rank.hpp"
 #include "rank_all.hpp"
 #include "build_info.hpp"
 
@@ -79,10 +80,11 @@ constexpr int kMetaBigTotal = kMetaMax + 2;     // [170..171] u64: scratch float
 constexpr int kMetaBigCursor = kMetaMax + 4;    // [172..173] u64: bump allocator of big_rank_kernel
 constexpr int kMetaWideRedo = kMetaMax + 8;     // [176] positions on the WIDE form's redo list (wide_redo_kernel)
 constexpr int kMetaCntGate = kMetaMax + 10;     // [178] the counting form's gate (cnt_probe_kernel: 1 = the batch is event-like)
+constexpr int kMetaDeepTiles = kMetaMax + 12;   // [180..181] u64: tiles of the deep positions (NMOD_FLAG_DEEP, deep_rank.hpp)
 constexpr int kMetaRedo = 184;                  // float64 front end: [184] count of positions to redo, [184 + kClassStride] = 0 (their
                                                 // offset in the list), [242..243] u64 scratch keys they need, [244..245] u64 bump allocator
 constexpr int kMetaRedoTotal = 242, kMetaRedoCursor = 244;
-static_assert(kMetaRedo + kClassStride < kMetaRedoTotal && kMetaRedoCursor + 2 <= kMetaInts && kMetaBigCursor + 2 <= kMetaWideRedo && kMetaWideRedo < kMetaCntGate && kMetaCntGate < kMetaRedo, "meta layout");
+static_assert(kMetaRedo + kClassStride < kMetaRedoTotal && kMetaRedoCursor + 2 <= kMetaInts && kMetaBigCursor + 2 <= kMetaWideRedo && kMetaWideRedo < kMetaCntGate && kMetaCntGate < kMetaDeepTiles && kMetaDeepTiles + 2 <= kMetaRedo, "meta layout");
 // (kBigClass, kBigHistClass, kWideBigBase .., kNumPairs: rank_stats_launch.hpp)
 static_assert(kNumPairs <= kClassStride && kStatsClass + kClassStride <= kStatsGate && kStatsGate + kClassStride <= kStatsLeft && kStatsLeft + kClassStride <= kStatsTried && kStatsTried + kClassStride <= kStatsWords, "class tables");
 
@@ -119,6 +121,7 @@ static Workspace carve(void* base, int64_t npos) {
 struct BinArgs {
   int64_t npos; const int64_t* off0; const int64_t* off1; int64_t stride0, stride1;
   int cmax0, cmax1; int ks_only; int allow_big; int force_big; int64_t lim0, lim1; uint8_t* cls; int32_t* meta; int32_t* order;
+  int deep;                                     // NMOD_FLAG_DEEP: a group beyond NMOD_MAX_RANKED within lim0 / lim1 takes kDeepClass
 };
 
 
@@ -145,12 +148,14 @@ __global__ __launch_bounds__(256) void classify_kernel(BinArgs a) {
     int64_t n1 = a.stride1 > 0 ? a.stride1 : a.off1[p + 1] - a.off1[p];
     int c0 = size_class_of(n0), c1 = size_class_of(n1);
     // beyond what the caller promised (or the format allows): skipped, NMOD_STATUS_TOO_LARGE
-    const bool over = n0 > a.lim0 || n1 > a.lim1 || n0 > NMOD_MAX_RANKED || n1 > NMOD_MAX_RANKED;
+    const bool beyond = n0 > NMOD_MAX_RANKED || n1 > NMOD_MAX_RANKED;
+    const bool over = n0 > a.lim0 || n1 > a.lim1 || (beyond && !a.deep);
     // beyond the wave-resident kernels: KS-only sorts the smaller group only, all-tests mode sorts both
     const bool big = a.force_big ||                                   // fp64 keys: every position takes big_rank_kernel
                      (a.ks_only ? (c0 < c1 ? c0 : c1) >= kNumSizeClasses : (c0 >= kNumSizeClasses || c1 >= kNumSizeClasses));
     int cid;
     if (over || n0 <= 0 || n1 <= 0 || (big && !a.allow_big)) cid = 255;
+    else if (beyond) cid = kDeepClass;                                // (a.deep: the multi-workgroup form, deep_rank.hpp)
     else if (big && !a.ks_only && !a.force_big && (n0 < n1 ? n0 : n1) <= 256 && (n0 < n1 ? n1 : n0) <= kWideBigMaxQ)
       cid = kWideBigBase + (c0 < c1 ? c0 : c1);
     else if (big && !a.ks_only && !a.force_big && (n0 < n1 ? n0 : n1) <= kBigHistMaxS && (n0 < n1 ? n1 : n0) <= kBigHistMaxQ) cid = kBigHistClass;
@@ -160,6 +165,8 @@ __global__ __launch_bounds__(256) void classify_kernel(BinArgs a) {
     if (cid == kBigClass)
       atomicAdd(reinterpret_cast<unsigned long long*>(a.meta + kMetaBigTotal),
                 (unsigned long long)(big_pow2_ceil(n0) + big_pow2_ceil(n1)));
+    if (cid == kDeepClass)
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.meta + kMetaDeepTiles), (unsigned long long)(deep_tiles(n0) + deep_tiles(n1)));
     a.cls[p] = (uint8_t)cid;
     if (cid != 255) atomicAdd(&hist[cid], 1);
   }
@@ -255,6 +262,7 @@ struct F64Args {
   const uint8_t* tied; const uint8_t* cls;     // K1's tie flags; the size-class byte of the binning (null: no binning ran)
   int32_t* order; int32_t* meta;               // redo list (ws.order) and its counters (ws.meta + kMetaRedo ...)
   double* moments;
+  int32_t deep;                                // NMOD_FLAG_DEEP: positions with a group beyond NMOD_MAX_RANKED belong to deep_rank.hpp (fp64 keys, own moments)
 };
 
 __device__ __forceinline__ void f64_rows(const F64Args& a, int64_t p, int64_t& o0, int& n0, int64_t& o1, int& n1) {
@@ -303,6 +311,7 @@ __global__ __launch_bounds__(256) void f64_moments_kernel(F64Args a) {
   for (int64_t p = w0; p < a.npos; p += ws) {
     int64_t o0, o1; int n0, n1;
     f64_rows(a, p, o0, n0, o1, n1);
+    if (a.deep && (n0 > NMOD_MAX_RANKED || n1 > NMOD_MAX_RANKED)) continue;
     for (int g = 0; g < 2; ++g) {
       const double* src = (g ? a.d1 + o1 : a.d0 + o0);
       const int n = g ? n1 : n0;
@@ -323,7 +332,7 @@ __global__ __launch_bounds__(256) void f64_redo_list_kernel(F64Args a) {
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < a.npos; p += (int64_t)gridDim.x * 256) {
     if (!a.cls3[p]) continue;
     const bool big = a.cls && (a.cls[p] == (uint8_t)kBigClass || a.cls[p] == (uint8_t)kBigHistClass);
-    const bool skipped = a.cls && a.cls[p] == 255;
+    const bool skipped = a.cls && (a.cls[p] == 255 || a.cls[p] == (uint8_t)kDeepClass);
     if (skipped || !(a.tied[p] || big)) continue;
     int64_t o0, o1; int n0, n1;
     f64_rows(a, p, o0, n0, o1, n1);
@@ -391,7 +400,7 @@ static int check_params(const nmod_params* prm) {
   if (prm->method < NMOD_METHOD_KS || prm->method > NMOD_METHOD_FISHER) return NMOD_ERR_INVALID_ARG;
   if (prm->nb < 0 || prm->nb > NMOD_MAX_NB) return NMOD_ERR_INVALID_ARG;
   if ((prm->tests & ~NMOD_TEST_ALL) != 0) return NMOD_ERR_INVALID_ARG;
-  if ((prm->flags & ~(NMOD_FLAG_KS_RATIONAL_D | NMOD_FLAG_CHECK_FINITE | NMOD_FLAG_NO_COUNTING | NMOD_FLAG_NO_COUNT_WIDE | NMOD_FLAG_NO_HOST_NARROW)) != 0 || prm->reserved != 0) return NMOD_ERR_INVALID_ARG;
+  if ((prm->flags & ~(NMOD_FLAG_KS_RATIONAL_D | NMOD_FLAG_CHECK_FINITE | NMOD_FLAG_NO_COUNTING | NMOD_FLAG_NO_COUNT_WIDE | NMOD_FLAG_NO_HOST_NARROW | NMOD_FLAG_DEEP)) != 0 || prm->reserved != 0) return NMOD_ERR_INVALID_ARG;
   return NMOD_OK;
 }
 
@@ -473,6 +482,71 @@ struct DevScratch {
   ~DevScratch() { if (p) { if (async) hipFreeAsync(p, owner); else { hipStreamSynchronize(owner); hipFree(p); } } }
 };
 
+// ---------------------------------------------------------------- the deep form (NMOD_FLAG_DEEP, deep_rank.hpp)
+// Enqueues K1 of the ndeep positions of class kDeepClass (`tiles` tiles in all, from the classifier) on `stream`: the tile
+// table, then round by round the tile sort, the moments, the merge passes and the ranking.  Leaves `da` describing the slab
+// (in `scratch`) for deep_finalize_kernel; no host round trip of its own.
+template <int DT>
+static int enqueue_deep_rounds(DeepArgs& da, int64_t round_tiles, int64_t max_group, bool all, int num_cus, hipStream_t stream,
+                               void* keys_a, void* keys_b) {
+  typedef typename BigKey<DT>::type K;
+  const size_t tile_lds = (size_t)kDeepTile * sizeof(K);
+  NMOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(deep_tile_kernel<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+  int passes = 0;
+  for (int64_t w = kDeepTile; w < deep_tiles(max_group) * kDeepTile; w <<= 1) ++passes;     // the longest group's runs -> one
+  const unsigned tb = (unsigned)std::min<int64_t>(round_tiles, (int64_t)num_cus * 8);
+  const unsigned mb = (unsigned)std::min<int64_t>(round_tiles * (kDeepTile / kDeepChunk), (int64_t)num_cus * 16);
+  const unsigned pb = (unsigned)std::min<int64_t>(da.ndeep, (int64_t)num_cus * 4);
+  for (int r = 0; r < da.nrounds; ++r) {
+    da.round = r;
+    da.src = nullptr; da.dst = keys_a;
+    hipLaunchKernelGGL(deep_tile_kernel<DT>, dim3(tb), dim3(kDeepThreads), tile_lds, stream, da);
+    if (all) {
+      hipLaunchKernelGGL(deep_mean_kernel, dim3(pb), dim3(kDeepThreads), 0, stream, da);
+      da.src = keys_a;
+      hipLaunchKernelGGL(deep_q_kernel<DT>, dim3(tb), dim3(kDeepThreads), 0, stream, da);
+    }
+    void* bufs[2] = {keys_a, keys_b};
+    for (int p = 0; p < passes; ++p) {
+      da.src = bufs[p & 1]; da.dst = bufs[(p + 1) & 1]; da.width = (int64_t)kDeepTile << p;
+      hipLaunchKernelGGL(deep_merge_kernel<DT>, dim3(mb), dim3(kDeepThreads), 0, stream, da);
+    }
+    da.src = bufs[passes & 1]; da.dst = nullptr;
+    hipLaunchKernelGGL(deep_rank_kernel<DT>, dim3(tb), dim3(kDeepThreads), 0, stream, da);
+    NMOD_HIP(hipGetLastError());
+  }
+  da.src = nullptr; da.dst = nullptr;
+  return NMOD_OK;
+}
+
+static int enqueue_deep(const nmod_params* prm, DeepArgs& da, DevScratch& scratch, int dtype, const void* sig0, const void* sig1,
+                        const int64_t* off0, const int64_t* off1, int64_t stride0, int64_t stride1, const Workspace& ws,
+                        int64_t ndeep, int64_t tiles, int64_t max_group, bool all, int num_cus, hipStream_t stream) {
+  if (ndeep <= 0 || tiles < 2 * ndeep) return NMOD_ERR_INVALID_ARG;
+  const int64_t nrounds = (tiles + kDeepRoundStride - 1) / kDeepRoundStride;
+  const int64_t round_tiles = std::min<int64_t>(tiles, kDeepRoundTiles);
+  const int64_t ksz = dtype == NMOD_DTYPE_F64 ? 8 : 4;
+  int64_t o = 0;
+  auto take = [&](int64_t bytes) { const int64_t r = o; o += align256(bytes); return r; };
+  const int64_t o_ptile = take((ndeep + 1) * 8), o_round = take((nrounds + 1) * 8), o_acc = take(ndeep * (int64_t)sizeof(DeepAcc));
+  const int64_t o_sum = take(tiles * 8), o_q = take(tiles * 8);
+  const int64_t o_ka = take(round_tiles * kDeepTile * ksz), o_kb = take(round_tiles * kDeepTile * ksz);
+  NMOD_HIP(scratch.alloc((size_t)o, stream, prm->device));
+  char* base = (char*)scratch.p;
+  NMOD_HIP(hipMemsetAsync(base + o_acc, 0, (size_t)ndeep * sizeof(DeepAcc), stream));
+  da.sig0 = sig0; da.sig1 = sig1; da.off0 = off0; da.off1 = off1; da.stride0 = stride0; da.stride1 = stride1;
+  da.pos_list = ws.order; da.class_meta = ws.meta; da.deep_class = kDeepClass;
+  da.ndeep = ndeep; da.nrounds = (int32_t)nrounds;
+  da.ptile = (int64_t*)(base + o_ptile); da.roundtab = (int64_t*)(base + o_round); da.acc = (DeepAcc*)(base + o_acc);
+  da.tile_sum = (double*)(base + o_sum); da.tile_q = (double*)(base + o_q); da.all = all ? 1 : 0;
+  hipLaunchKernelGGL(deep_plan_kernel, dim3(1), dim3(kDeepPlanThreads), 0, stream, da);
+  NMOD_HIP(hipGetLastError());
+  ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_RANK_STATS, stream);
+  if (dtype == NMOD_DTYPE_F64) return enqueue_deep_rounds<2>(da, round_tiles, max_group, all, num_cus, stream, base + o_ka, base + o_kb);
+  if (dtype == NMOD_DTYPE_I16_MILLI) return enqueue_deep_rounds<1>(da, round_tiles, max_group, all, num_cus, stream, base + o_ka, base + o_kb);
+  return enqueue_deep_rounds<0>(da, round_tiles, max_group, all, num_cus, stream, base + o_ka, base + o_kb);
+}
+
 // the float64 samples behind float32 keys (detect_f64): device pointers in the index space of the offsets
 struct F64Src { const double* d0; const double* d1; uint8_t* cls3; };
 
@@ -523,15 +597,20 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
     if (max1 <= 0) max1 = mx[1];
   }
   // a group beyond NMOD_MAX_RANKED: that position is skipped by the classifier and flagged NMOD_STATUS_TOO_LARGE by K2, the rest
-  // of the batch is computed (the reference has no limit: myDetect.py:327-343)
-  max0 = std::min<int64_t>(max0, NMOD_MAX_RANKED); max1 = std::min<int64_t>(max1, NMOD_MAX_RANKED);
+  // of the batch is computed (the reference has no limit: myDetect.py:327-343) — unless NMOD_FLAG_DEEP sends it to the deep form
+  // (deep_rank.hpp), which takes groups up to NMOD_MAX_DEEP
+  const bool deep_flag = (prm->flags & NMOD_FLAG_DEEP) != 0;
+  const int64_t group_cap = deep_flag ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;
+  max0 = std::min<int64_t>(max0, group_cap); max1 = std::min<int64_t>(max1, group_cap);
+  const bool deep_possible = deep_flag && std::max(max0, max1) > NMOD_MAX_RANKED;
   int cmax0 = size_class_of(std::max<int64_t>(max0, 1)), cmax1 = size_class_of(std::max<int64_t>(max1, 1));
   // positions beyond the wave-resident kernels (both groups sorted in all-tests mode, the smaller one in KS-only
   // mode) go to big_rank_kernel; the maxima tell whether any can exist
   const bool big_possible = all ? (cmax0 >= kNumSizeClasses || cmax1 >= kNumSizeClasses)
                                 : (std::min(cmax0, cmax1) >= kNumSizeClasses);
   cmax0 = std::min(cmax0, kNumSizeClasses - 1); cmax1 = std::min(cmax1, kNumSizeClasses - 1);
-  if (!meta_cleared && (!(uniform && !big_possible) || f64)) NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
+  const bool binned = !(uniform && !big_possible && !deep_possible);
+  if (!meta_cleared && (binned || f64)) NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
 
   RankStatsArgs ra;
   memset(&ra, 0, sizeof(ra));
@@ -601,10 +680,13 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
     return e;
   };
 
-  DevScratch big_scratch;
+  DevScratch big_scratch, deep_scratch;
+  DeepArgs da;                                                // the deep form's state between K1 and its finalize
+  memset(&da, 0, sizeof(da));
+  const int deep_dtype = f64 ? 2 : prm->dtype;                // (float64 samples: the deep form sorts them as 64-bit keys)
   int st_uniform_cls = -1, st_cnt256 = 0, st_cw = 0;          // for nmod_last_dispatch_stats
   constexpr int kCls256 = kNumGeneralClasses + 2;
-  if (uniform && !big_possible) {
+  if (!binned) {
     const int ucls = all ? launch_class_of(cmax0, cmax1) : kKsClassBase + std::min(cmax0, cmax1);
     st_uniform_cls = ucls; st_cnt256 = (ucls == kCls256 && ra.cnt_gate) ? 1 : 0;
     const bool uwide = wide_f32 && wide_class(ucls);
@@ -619,6 +701,7 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
     BinArgs ba;
     ba.npos = npos; ba.off0 = off0; ba.off1 = off1; ba.stride0 = ra.stride0; ba.stride1 = ra.stride1;
     ba.cmax0 = cmax0; ba.cmax1 = cmax1; ba.ks_only = all ? 0 : 1; ba.allow_big = 1; ba.force_big = 0; ba.lim0 = std::max<int64_t>(max0, 1); ba.lim1 = std::max<int64_t>(max1, 1);
+    ba.deep = deep_flag ? 1 : 0;
     ba.cls = ws.cls; ba.meta = ws.meta; ba.order = ws.order;
     unsigned blocks = (unsigned)std::min<int64_t>((npos + 255) / 256, 4096);
     hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(256), 0, stream, ba);
@@ -655,12 +738,25 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
       for (int cls = 0; cls < kNumClasses && !any_wide; ++cls) any_wide = wanted[cls] && wide_class(cls);
       if (any_wide) { const int rr = launch_wide_redo(); if (rr != NMOD_OK) return rr; }
     }
-    if (big_possible) {
-      // the only host round trip of this path: how many large positions, how much scratch
-      int32_t head[4];
+    if (big_possible || deep_possible) {
+      // the only host round trip of this path: how many large (and deep) positions, how much scratch
+      int32_t head[8];
       NMOD_HIP(hipMemcpyAsync(&head[0], ws.meta + kBigClass, 8, hipMemcpyDeviceToHost, stream));     // kBigClass, kBigHistClass
       NMOD_HIP(hipMemcpyAsync(&head[2], ws.meta + kMetaBigTotal, 8, hipMemcpyDeviceToHost, stream));
+      if (deep_possible) {
+        NMOD_HIP(hipMemcpyAsync(&head[4], ws.meta + kDeepClass, 4, hipMemcpyDeviceToHost, stream));
+        NMOD_HIP(hipMemcpyAsync(&head[6], ws.meta + kMetaDeepTiles, 8, hipMemcpyDeviceToHost, stream));
+      } else {
+        head[4] = 0; head[6] = 0; head[7] = 0;
+      }
       NMOD_HIP(hipStreamSynchronize(stream));
+      if (head[4] > 0) {
+        unsigned long long tiles;
+        memcpy(&tiles, &head[6], 8);
+        const int rc = enqueue_deep(prm, da, deep_scratch, deep_dtype, f64 ? (const void*)f64->d0 : sig0, f64 ? (const void*)f64->d1 : sig1,
+                                    off0, off1, ra.stride0, ra.stride1, ws, head[4], (int64_t)tiles, std::max(max0, max1), all, num_cus, stream);
+        if (rc != NMOD_OK) return rc;
+      }
       const int64_t nbig = head[0], nbig_hist = head[1];
       unsigned long long total;
       memcpy(&total, &head[2], 8);
@@ -700,7 +796,7 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
     F64Args fx;
     memset(&fx, 0, sizeof(fx));
     fx.d0 = f64->d0; fx.d1 = f64->d1; fx.off0 = off0; fx.off1 = off1; fx.stride0 = ra.stride0; fx.stride1 = ra.stride1;
-    fx.npos = npos; fx.cls3 = f64->cls3; fx.tied = ws.tied; fx.cls = (uniform && !big_possible) ? nullptr : ws.cls;
+    fx.npos = npos; fx.cls3 = f64->cls3; fx.tied = ws.tied; fx.cls = binned ? ws.cls : nullptr; fx.deep = deep_flag ? 1 : 0;
     fx.order = ws.order; fx.meta = ws.meta; fx.moments = ws.moments;
     const unsigned gb = (unsigned)std::min<int64_t>((npos + 255) / 256, 4096);
     hipLaunchKernelGGL(f64_redo_list_kernel, dim3(gb), dim3(256), 0, stream, fx);
@@ -739,9 +835,10 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
   fa.tests = tests; fa.want_mstd = prm->want_mstd; fa.out = *out;
   // what K1 covered: exactly the limits the classifier used (the promised / measured maxima), in every mode —
   // a position beyond them was skipped by K1 and must be flagged TOO_LARGE here, never read from the workspace
-  fa.max_n0 = std::max<int64_t>(max0, 1);
-  fa.max_n1 = std::max<int64_t>(max1, 1);
+  fa.max_n0 = std::max<int64_t>(std::min<int64_t>(max0, NMOD_MAX_RANKED), 1);
+  fa.max_n1 = std::max<int64_t>(std::min<int64_t>(max1, NMOD_MAX_RANKED), 1);
   fa.min_cap = 0;
+  if (deep_possible) { fa.deep_lim0 = std::max<int64_t>(max0, 1); fa.deep_lim1 = std::max<int64_t>(max1, 1); }   // (K2 leaves them to the deep form)
   if ((prm->flags & NMOD_FLAG_CHECK_FINITE) && prm->dtype != NMOD_DTYPE_I16_MILLI) {
     // one pass over the samples: the float64 samples themselves where the keys are their float32 images
     NonfiniteArgs na;
@@ -760,6 +857,15 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
   }
   {
     ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_FINALIZE, stream);
+    if (da.ndeep > 0) {                  // the deep positions' outputs (K2 skips them), then the slab goes back to the pool
+      const unsigned db = (unsigned)((da.ndeep + 255) / 256);
+      const int32_t rat = ra.ks_rational_d, chk = (prm->flags & NMOD_FLAG_CHECK_FINITE) ? 1 : 0;
+      if (deep_dtype == NMOD_DTYPE_I16_MILLI) hipLaunchKernelGGL(deep_finalize_kernel<1>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
+      else if (deep_dtype == NMOD_DTYPE_F64) hipLaunchKernelGGL(deep_finalize_kernel<2>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
+      else hipLaunchKernelGGL(deep_finalize_kernel<0>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
+      NMOD_HIP(hipGetLastError());
+      NMOD_HIP(deep_scratch.release(stream));
+    }
     hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, fa);
     NMOD_HIP(hipGetLastError());
   }
@@ -1027,7 +1133,7 @@ const char* nmod_strerror(int rc) {
     case NMOD_ERR_HIP:
       snprintf(g_errbuf, sizeof(g_errbuf), "HIP runtime error: %s", hipGetErrorString(g_last_hip));
       return g_errbuf;
-    case NMOD_ERR_TOO_LARGE: return "a position has more samples in a group than NMOD_MAX_RANKED (65535)";
+    case NMOD_ERR_TOO_LARGE: return "a position has more samples in a group than NMOD_MAX_RANKED (65535; NMOD_MAX_DEEP with NMOD_FLAG_DEEP)";
     case NMOD_ERR_WORKSPACE: return "workspace missing or smaller than nmod_workspace_bytes()";
     case NMOD_ERR_NO_DEVICE: return "no HIP device";
     case NMOD_ERR_NO_RCCL: return "librccl.so could not be bound (neither loaded in this process nor on the loader path)";
@@ -1150,7 +1256,12 @@ int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char*
   int rc = check_params(prm);
   if (rc != NMOD_OK) return rc;
   if (!buf || buflen < 8 || n0 <= 0 || n1 <= 0) return NMOD_ERR_INVALID_ARG;
-  if (std::max(n0, n1) > NMOD_MAX_RANKED) return NMOD_ERR_TOO_LARGE;
+  if (std::max(n0, n1) > NMOD_MAX_RANKED) {
+    // NMOD_FLAG_DEEP: the multi-workgroup form (deep_rank.hpp; float64 samples as 64-bit keys) up to NMOD_MAX_DEEP
+    if (!(prm->flags & NMOD_FLAG_DEEP) || std::max(n0, n1) > NMOD_MAX_DEEP) return NMOD_ERR_TOO_LARGE;
+    snprintf(buf, buflen, "deep_rank_kernel<%s>", prm->dtype == NMOD_DTYPE_I16_MILLI ? "i16" : (prm->dtype == NMOD_DTYPE_F64 ? "f64" : "f32"));
+    return NMOD_OK;
+  }
   const bool want_comb = prm->method != NMOD_METHOD_KS;
   int tests = prm->tests | (want_comb ? NMOD_TEST_KS : 0);
   const bool all = (tests & (NMOD_TEST_MWU | NMOD_TEST_WELCH)) != 0 || prm->want_mstd;
@@ -1225,7 +1336,8 @@ static void assemble_dispatch_stats(const unsigned long long* raw, int64_t npos,
     const int64_t n = (int64_t)raw[kStatsClass + c];
     if (n == 0) continue;
     placed += n;
-    int64_t* sorting = c >= kWideBigBase ? &st->rank_hist_wide
+    int64_t* sorting = c == kDeepClass ? &st->deep
+                     : c >= kWideBigBase ? &st->rank_hist_wide
                      : (c == kBigClass || c == kBigHistClass) ? &st->big
                      : c >= kKsClassBase ? &st->ks_rank
                      : c >= kNumGeneralClasses ? &st->rank_hist
@@ -1289,6 +1401,7 @@ int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, 
   int num_cus = 0;
   NMOD_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
   const int64_t max_elements = env_i64("NMOD_DOWNSAMPLE_ELEMENTS", (int64_t)1 << 27);
+  const int64_t group_cap = (prm->flags & NMOD_FLAG_DEEP) ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;   // (NMOD_FLAG_DEEP: deep groups and resamples too)
   std::vector<int32_t> rn[2], rsz[2];
   std::vector<int64_t> roff[2], vbase[2];
   std::vector<char> rows[2];
@@ -1305,7 +1418,7 @@ int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, 
       int64_t n[2], z[2];
       for (int g = 0; g < 2; ++g) {
         n[g] = off[g][p + 1] - off[g][p];
-        if (n[g] <= 0 || n[g] > NMOD_MAX_RANKED) return n[g] > NMOD_MAX_RANKED ? NMOD_ERR_TOO_LARGE : NMOD_ERR_INVALID_ARG;
+        if (n[g] <= 0 || n[g] > group_cap) return n[g] > group_cap ? NMOD_ERR_TOO_LARGE : NMOD_ERR_INVALID_ARG;
         z[g] = (cov[hi] > 0 && n[g] > cov[hi]) ? cov[hi] : n[g];
       }
       const int64_t add = (z[0] + z[1]) * (int64_t)iters;
@@ -1326,7 +1439,7 @@ int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, 
     struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } } drain{stream};
     // ---- device buffers of the chunk (stream-ordered, from the library's pool)
     nmod_params dp = *prm;
-    dp.memspace = NMOD_MEM_DEVICE; dp.tests = NMOD_TEST_KS; dp.method = NMOD_METHOD_KS; dp.want_mstd = 0; dp.flags = 0;
+    dp.memspace = NMOD_MEM_DEVICE; dp.tests = NMOD_TEST_KS; dp.method = NMOD_METHOD_KS; dp.want_mstd = 0; dp.flags = prm->flags & NMOD_FLAG_DEEP;
     dp.stride0 = 0; dp.stride1 = 0; dp.max_n0 = (int32_t)maxsz[0]; dp.max_n1 = (int32_t)maxsz[1];
     const int64_t wsb = nmod_workspace_bytes(&dp, nv);
     DevScratch d_rows[2], d_meta[2], d_virt[2], d_voff[2], d_ws, d_res;

@@ -22,17 +22,26 @@ struct FinalizeArgs {
   int64_t max_n0, max_n1;               // per-group limits of this launch
   int64_t min_cap;                      // KS-only: capacity limit of the smaller (sorted) group, else 0
   const uint8_t* nonfinite;             // [npos] or null: 1 where nonfinite_scan_kernel found a NaN / infinite sample (NMOD_FLAG_CHECK_FINITE)
+  int64_t deep_lim0, deep_lim1;         // NMOD_FLAG_DEEP: a position with a group beyond NMOD_MAX_RANKED and both within these limits is
+                                        // the deep form's (deep_rank.hpp writes its outputs): skipped here.  0: no deep form in this batch
   nmod_out out;
 };
 
-__global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.npos) return;
-  const int64_t n0 = a.stride0 > 0 ? a.stride0 : a.off0[p + 1] - a.off0[p];
-  const int64_t n1 = a.stride1 > 0 ? a.stride1 : a.off1[p + 1] - a.off1[p];
+// K1's facts of position p in the workspace (the wave-resident, counting and large-position forms)
+struct K1Facts {
+  const FinalizeArgs& a; int64_t p;
+  __device__ __forceinline__ double ks_d(double prod) const { return a.ks_d_ref ? a.ks_d_ref[p] : (double)a.ks_num[p] / prod; }
+  __device__ __forceinline__ double mwu_s() const { return (double)a.mwu_s[p]; }
+  __device__ __forceinline__ double tie() const { return (double)a.tie[p]; }
+  __device__ __forceinline__ const double* moments() const { return a.moments + p * 4; }
+  __device__ __forceinline__ bool nonfinite() const { return a.nonfinite && a.nonfinite[p]; }
+};
+
+// The outputs and status of one position from K1's facts (src: K1Facts, or the deep form's DeepFacts)
+template <class Src>
+__device__ __forceinline__ void finalize_position(const FinalizeArgs& a, int64_t p, int64_t n0, int64_t n1, bool too_large, const Src& src) {
   const double nan = __builtin_nan("");
   unsigned status = 0;
-  const bool too_large = (n0 > a.max_n0 || n1 > a.max_n1) || (a.min_cap > 0 && (n0 < n1 ? n0 : n1) > a.min_cap);
   const bool empty = (n0 <= 0 || n1 <= 0) || too_large;    // "empty": nothing was computed by K1
   if (n0 <= 0 || n1 <= 0) status |= NMOD_STATUS_EMPTY;
   if (too_large) status |= NMOD_STATUS_TOO_LARGE;
@@ -45,7 +54,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
       // ks_2samp (scipy 1.2.1): d = max|cdf1 - cdf2|; en = sqrt(n1*n2/float(n1+n2));
       // prob = kstwobign.sf((en + 0.12 + 0.11/en) * d)
       // KS-only mode: the exact rational, correctly rounded (<= 1 ulp from the float-CDF form)
-      d = a.ks_d_ref ? a.ks_d_ref[p] : (double)a.ks_num[p] / prod;
+      d = src.ks_d(prod);
       double en = sqrt(prod / (double)(n0 + n1));
       pv = kolmogorov_sf((en + 0.12 + 0.11 / en) * d);
     }
@@ -57,10 +66,10 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
     double u = nan, pv = nan;
     if (!empty) {
       // mannwhitneyu(x, y, use_continuity=True, alternative=None) of scipy 1.2.1
-      double u1 = prod - 0.5 * (double)a.mwu_s[p];      // n1*n2 + n1(n1+1)/2 - sum(rank x)
+      double u1 = prod - 0.5 * src.mwu_s();      // n1*n2 + n1(n1+1)/2 - sum(rank x)
       double u2 = prod - u1;
       double size = (double)(n0 + n1);
-      double T = (size < 2.0) ? 1.0 : 1.0 - (double)a.tie[p] / (size * size * size - size);
+      double T = (size < 2.0) ? 1.0 : 1.0 - src.tie() / (size * size * size - size);
       if (T == 0.0) {
         status |= NMOD_STATUS_MWU_ALL_IDENTICAL;          // the reference raises here
       } else {
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
   }
 
   if ((a.tests & NMOD_TEST_WELCH) || a.want_mstd) {
-    const double* mo = a.moments + p * 4;
+    const double* mo = src.moments();
     double mean0 = nan, m20 = nan, mean1 = nan, m21 = nan;
     if (!empty) { mean0 = mo[0]; m20 = mo[1]; mean1 = mo[2]; m21 = mo[3]; }
     // finite samples have finite moments: a NaN or an infinity here is one in the position's samples (NMOD_STATUS_NONFINITE)
@@ -107,8 +116,18 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
       if (a.out.std1) a.out.std1[p] = sqrt(m21 / dn1);
     }
   }
-  if (a.nonfinite && !empty && a.nonfinite[p]) status |= NMOD_STATUS_NONFINITE;
+  if (!empty && src.nonfinite()) status |= NMOD_STATUS_NONFINITE;
   if (a.out.status) a.out.status[p] = (uint8_t)status;
+}
+
+__global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.npos) return;
+  const int64_t n0 = a.stride0 > 0 ? a.stride0 : a.off0[p + 1] - a.off0[p];
+  const int64_t n1 = a.stride1 > 0 ? a.stride1 : a.off1[p + 1] - a.off1[p];
+  if (a.deep_lim0 > 0 && n0 > 0 && n1 > 0 && (n0 > NMOD_MAX_RANKED || n1 > NMOD_MAX_RANKED) && n0 <= a.deep_lim0 && n1 <= a.deep_lim1) return;
+  const bool too_large = (n0 > a.max_n0 || n1 > a.max_n1) || (a.min_cap > 0 && (n0 < n1 ? n0 : n1) > a.min_cap);
+  finalize_position(a, p, n0, n1, too_large, K1Facts{a, p});
 }
 
 // NMOD_FLAG_CHECK_FINITE: one wave per position reads both rows and flags a NaN / infinite sample (float32 or float64 rows)

@@ -28,7 +28,8 @@ constexpr int kBigHistClass = kNumClasses + 1;     // 48: all tests, big_hist_ke
 constexpr int kWideBigBase = kNumClasses + 2;      // 49 + cs: all tests, smaller group in class cs <= 2 (<= 256), larger 2 049 .. 4 096:
 constexpr int kNumWideBig = 3;                     //          rank_hist_kernel WIDE with two hash passes (rank_hist.hpp)
 constexpr int kWideBigMaxQ = 4096;
-constexpr int kNumPairs = kWideBigBase + kNumWideBig;                   // 52 class lists
+constexpr int kDeepClass = kWideBigBase + kNumWideBig;                  // 52: NMOD_FLAG_DEEP, a group beyond NMOD_MAX_RANKED (deep_rank.hpp)
+constexpr int kNumPairs = kDeepClass + 1;                               // 53 class lists
 
 __host__ __device__ inline int size_class_of(int64_t n) {   // smallest class with 64 << c >= n; 6 if too large
   int c = 0;

@@ -10,7 +10,8 @@ Same names, argument meaning and error behaviour as
 `moptions` keys read (as the reference): 'ds2', <dataset>['norm_mean'|'base'|
 'basedict'][(chrom,strand)][pos], 'MinCoverage', 'neighborPvalues',
 'WeightsDif', 'testMethod', 'rankUse', 'SaveTest', 'outFolder', 'FileID',
-'mstd', 'coverages', 'RegionRankbyST' (+ 'window', 'WindOvlp', 'percentile', 'NA'), 'outLevel'.
+'mstd', 'coverages', 'RegionRankbyST' (+ 'window', 'WindOvlp', 'percentile', 'NA'), 'outLevel';
+of this build: 'nmod_device', 'nmod_seed', 'nmod_strict', 'nmod_quiet', 'nmod_deep' (1: groups beyond 65 535 samples on the deep form).
 Keys written: 'sign_test', 'sorted_sign_test', optionally 'sign_test_mstd', 'nmod_flagged' (positions flagged TOO_LARGE / NONFINITE; 'nmod_strict' raises),
 plus 'sign_test_arrays' (the same numbers as numpy arrays, an addition).
 """
@@ -529,7 +530,7 @@ def region_rank(moptions, sorted_ind, use_pind):
 
 # myDetect.py:416-462
 def downsample_update(res, sig0, off0, sig1, off1, rid, strands, coverages, *, iters=100, quantile=0.25, seed=0,
-                      nb=2, weights_dif=2.0, method='stouffer', device=0):
+                      nb=2, weights_dif=2.0, method='stouffer', device=0, deep=False):
     """Down-sampling branch (myDetect.py:339-361) on a finished batch: positions where a group exceeds its
     strand's coverage threshold get the KS pair of the `quantile`-th of `iters` resamples (seeded here,
     unseeded in the reference) and the combined track is recomputed; MWU / Welch keep the full data.
@@ -542,7 +543,7 @@ def downsample_update(res, sig0, off0, sig1, off1, rid, strands, coverages, *, i
     flag = np.nonzero((cov_pos > 0) & ((n0a > cov_pos) | (n1a > cov_pos)))[0]
     if len(flag):
         dsd, dsp = engine.downsample_ks(sig0, off0, sig1, off1, flag, cov_pos[flag], iters=iters, quantile=quantile,
-                                        seed=seed, device=device)
+                                        seed=seed, device=device, deep=deep)
         res['ks_d'][flag] = dsd
         res['ks_p'][flag] = dsp
         if method != 'ks':
@@ -560,13 +561,16 @@ def mtest2(moptions):
     nb = moptions['neighborPvalues']
     want_mstd = not moptions.get('mstd', 0) == 0
     dev = moptions.get('nmod_device', 0)
+    # moptions['nmod_deep']: positions with a group beyond 65 535 samples (amplicon / plasmid data) are tested by the deep form
+    # (NMOD_FLAG_DEEP) in the batch and in the down-sampling branch instead of being flagged with NaN statistics; off by default
+    deep = bool(moptions.get('nmod_deep', 0))
     start_time = time.time()
     # the combine is skipped for 'ks' (myDetect.py:443); for nb == 0 it returns the KS tuple (:413)
     dev_method = method if (method in ('stouffer', 'fisher') and nb > 0) else 'ks'
     if method not in ('ks', 'stouffer', 'fisher') and nb > 0 and npos > 0:
         raise UnboundLocalError("local variable 'comb_p_p' referenced before assignment")       # as the reference
     res = engine.detect_host(sig0, off0, sig1, off1, rid, nb=max(nb, 0), weights_dif=moptions.get('WeightsDif', 2.0),
-                             method=dev_method, want_mstd=want_mstd, device=dev)
+                             method=dev_method, want_mstd=want_mstd, device=dev, deep=deep)
     if npos and np.any(res['status'] & L.STATUS_MWU_ALL_IDENTICAL):
         raise ValueError('All numbers are identical in mannwhitneyu')                             # scipy 1.2.1, uncaught in the reference
     # positions the device could not take (a group beyond 65 535 samples: NaN outputs) or whose samples are not finite
@@ -586,7 +590,7 @@ def mtest2(moptions):
         downsample_update(res, sig0, off0, sig1, off1, rid, meta['strand'], moptions.get('coverages', (0, 0)),
                           iters=int(moptions.get('downsampling', 100)), quantile=float(moptions.get('downsampling_quantile', 0.25)),
                           seed=int(moptions.get('nmod_seed', 0)), nb=nb, weights_dif=moptions.get('WeightsDif', 2.0),
-                          method=dev_method, device=dev)
+                          method=dev_method, device=dev, deep=deep)
     with_comb = not method == "ks" and nb >= 0
     if with_comb and nb == 0:                                                                     # myDetect.py:413: the KS tuple itself
         res['comb_st'], res['comb_p'] = res['ks_d'], res['ks_p']

@@ -57,7 +57,7 @@ def _join_warm_up(device):
 
 
 def detect_host(sig0, off0, sig1, off1, run_id, *, nb=2, weights_dif=2.0, method='stouffer',
-                tests=L.TEST_ALL, want_mstd=False, device=0, stride0=0, stride1=0, flags=0, out=None):
+                tests=L.TEST_ALL, want_mstd=False, device=0, stride0=0, stride1=0, flags=0, deep=False, out=None):
     """Run the hot path on host-resident CSR inputs; returns a dict of numpy arrays.
 
     sig0/sig1: float32 (canonical), int16 (milli-units) or float64 1-D arrays; off0/off1:
@@ -89,6 +89,8 @@ def detect_host(sig0, off0, sig1, off1, run_id, *, nb=2, weights_dif=2.0, method
         run = np.ascontiguousarray(run_id, dtype=np.int32)
         if run.shape[0] != npos:
             raise ValueError('run_id must be int32[npos]')
+    if deep:
+        flags = int(flags) | L.FLAG_DEEP
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, tests=tests, method=method_id,
                         nb=nb, weights_dif=weights_dif, want_mstd=int(bool(want_mstd)),
                         stride0=stride0 if off0 is None else 0, stride1=stride1 if off1 is None else 0, flags=flags)
@@ -257,7 +259,7 @@ class DeviceDetector:
     and nothing synchronises unless max_n0/max_n1 are unknown for CSR inputs or allow groups beyond MAX_GROUP
     (one round trip sizes the scratch of the large-position pass)."""
 
-    def __init__(self, device=0, nb=2, weights_dif=2.0, method='stouffer', tests=L.TEST_ALL, want_mstd=False, flags=0):
+    def __init__(self, device=0, nb=2, weights_dif=2.0, method='stouffer', tests=L.TEST_ALL, want_mstd=False, flags=0, deep=False):
         import torch
         self.torch = torch
         self.lib = L.load()
@@ -267,7 +269,7 @@ class DeviceDetector:
         self.method = L.METHOD_BY_NAME[method] if isinstance(method, str) else method
         self.tests = tests
         self.want_mstd = bool(want_mstd)
-        self.flags = int(flags)          # L.FLAG_* (include/nanomod_hip.h: NMOD_FLAG_*)
+        self.flags = int(flags) | (L.FLAG_DEEP if deep else 0)          # L.FLAG_* (include/nanomod_hip.h: NMOD_FLAG_*); deep: FLAG_DEEP
         self._ws = None
         self.timer = None
 
@@ -369,7 +371,7 @@ class DeviceDetector:
         return out
 
 
-def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile=0.25, seed=0, device=0):
+def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile=0.25, seed=0, device=0, deep=False):
     """The down-sampling branch of getKStest (myDetect.py:345-361) for the positions `positions` (indices into
     the CSR arrays) through nmod_downsample_ks: `iters` times, a group with more than cov[i] samples is resampled WITH
     replacement to cov[i] samples (np.random.choice semantics), KS is run on each resample, and the (D, p) pair at index
@@ -378,6 +380,7 @@ def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile
     statistically equivalent, not bit-comparable (SURVEY.md §8a row A3', §8f row 4).  The resampled rows are
     materialised chunk by chunk in HBM and go through the same KS kernel as everything else; resampling, KS and the
     quantile selection all run in the library (round 3 assembled the rows with torch indexing).
+    deep: L.FLAG_DEEP, for groups and thresholds beyond L.MAX_RANKED (up to L.MAX_DEEP); without it such a group is an error.
     Returns (ks_d, ks_p) numpy arrays aligned with `positions`."""
     lib = L.load()
     _join_warm_up(device)
@@ -391,7 +394,8 @@ def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile
     if positions.shape != cov.shape or (len(positions) and (positions.min() < 0 or positions.max() >= len(off0) - 1)):
         raise ValueError('positions / cov must be aligned and index the CSR rows')
     out_d = np.empty(len(positions)); out_p = np.empty(len(positions))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, tests=L.TEST_KS, method=L.METHOD_KS)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, tests=L.TEST_KS, method=L.METHOD_KS,
+                        flags=L.FLAG_DEEP if deep else 0)
     rc = lib.nmod_downsample_ks(C.byref(prm), len(positions), _np_ptr(sig0), _np_ptr(off0), _np_ptr(sig1), _np_ptr(off1),
                                 _np_ptr(positions), _np_ptr(cov), int(iters), float(quantile), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                 _np_ptr(out_d), _np_ptr(out_p))
