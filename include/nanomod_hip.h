@@ -226,12 +226,13 @@ typedef struct nmod_host_stats {
 } nmod_host_stats;
 int nmod_last_host_stats(nmod_host_stats* st);
 
-/* Which K1 form computed the positions of the calling thread's last nmod_detect_batch.  The forms produce the same numbers
+/* Which K1 form computed the positions of the last successful nmod_detect_batch of the calling thread; a failed call clears
+ * it (nmod_downsample_ks leaves it alone, an empty batch reports no positions).  The forms produce the same numbers
  * (tests/test_gpu_parity.py runs batches through both and compares); which one runs is decided on the device — size classes,
  * and for the counting forms a probe per class plus a per-position check — so the split is a property of the data the caller
  * can only learn here.  NMOD_MEM_DEVICE: the counters are reduced on request from facts the call left in `workspace` (one
  * small kernel on the call's stream, one synchronisation): ask before the workspace is reused or freed.  NMOD_MEM_HOST: they
- * were read back with the results.  NMOD_ERR_INVALID_ARG when the thread has made no such call. */
+ * were read back with the results.  NMOD_ERR_INVALID_ARG when there is no such call. */
 typedef struct nmod_dispatch_stats {
   int64_t positions;        /* positions of the batch */
   int64_t ks_rank;          /* ks_rank_kernel: KS only, the smaller group sorted */

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rank_stats.hpp"
+#include "rank_stats_launch.hpp"   // kBigHistMaxS / kBigHistMaxQ
 
 namespace nmod {
 
@@ -212,8 +213,6 @@ void big_rank_kernel(BigArgs a) {
 // the ties INSIDE Q, the one thing that would need Q sorted, are counted by an open-addressing hash table in LDS:
 // an arrival that finds its key present gets the number of earlier arrivals from the slot's counter and adds
 // p (p - 1).  One pass over Q, no scratch slab, no copy of Q anywhere.
-constexpr int kBigHistMaxS = 1024;              // keys of S in LDS, a power of two (the sort pads to one); two blocks per CU
-constexpr int kBigHistMaxQ = 4096;              // samples of Q: half the slots of the hash table
 constexpr int kBigHistSlots = 8192;
 constexpr unsigned kBigHistEmpty = 0xffffffffu;  // (a NaN pattern no arithmetic produces)
 constexpr int kBigHistAux = 24;                  // words of block-wide accumulators behind the tables

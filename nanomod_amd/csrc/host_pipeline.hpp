@@ -259,7 +259,8 @@ struct HpCall {
 
 // ---------------------------------------------------------------- the pipeline
 static int detect_host_pipelined(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
-                                 const void* sig1, const int64_t* off1, const int32_t* run_id, nmod_out* out) {
+                                 const void* sig1, const int64_t* off1, const int32_t* run_id, nmod_out* out,
+                                 unsigned long long* stats_totals) {
   memset(&g_host_stats, 0, sizeof(g_host_stats));
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1 || !out) return NMOD_ERR_INVALID_ARG;
@@ -371,7 +372,6 @@ static int detect_host_pipelined(const nmod_params* prm, int64_t npos, const voi
   char* dbase = (char*)dmem.p;
   unsigned long long* d_stats = (unsigned long long*)(dbase + (int64_t)slots * dev_slot);
   NMOD_HIP(hipMemsetAsync(d_stats, 0, kStatsWords * 8, res.s_k));
-  g_dispatch.valid = false;
   char* dfull = dbase + (int64_t)slots * dev_slot + stats_bytes;
   double* f_ksd = (double*)dfull; double* f_ksp = (double*)(dfull + align256(npos * 8));
   double* f_cst = (double*)(dfull + 2 * align256(npos * 8)); double* f_cp = (double*)(dfull + 3 * align256(npos * 8));
@@ -459,26 +459,24 @@ static int detect_host_pipelined(const nmod_params* prm, int64_t npos, const voi
     dout.status = (uint8_t*)(slab + (int64_t)ntr * n * 8);
     const char* di = in_dev(s);
     int r;
+    StatsArgs sa;                                 // which K1 form took the chunk's positions (nmod_last_dispatch_stats)
     if (narrowed[c]) {                              // the chunk arrived as int16 milli-units
       nmod_params dp16 = dp;
       dp16.dtype = NMOD_DTYPE_I16_MILLI;
       r = detect_device(&dp16, n, di + o_sig0, csr0 ? (const int64_t*)(di + o_off0) : nullptr, di + o_sig1,
-                        csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout);
+                        csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout, &sa);
     } else if (prm->dtype == NMOD_DTYPE_F64) {
       const int64_t t0 = row0(cut[c + 1]) - row0(lo), t1 = row1(cut[c + 1]) - row1(lo);
       const int64_t bounds[4] = {0, t0, 0, t1};
       r = detect_f64(&dp, n, di + o_sig0, csr0 ? (const int64_t*)(di + o_off0) : nullptr, di + o_sig1,
-                     csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout, bounds);
+                     csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout, &sa, bounds);
     } else {
       r = detect_device(&dp, n, di + o_sig0, csr0 ? (const int64_t*)(di + o_off0) : nullptr, di + o_sig1,
-                        csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout);
+                        csr1 ? (const int64_t*)(di + o_off1) : nullptr, nullptr, ws_dev(s), wsb, &dout, &sa);
     }
     if (r != NMOD_OK) return r;
-    {                                             // which K1 form took the chunk's positions (nmod_last_dispatch_stats)
-      StatsArgs sa = g_dispatch.args;
-      sa.acc = d_stats;
-      NMOD_HIP(enqueue_dispatch_stats(sa, res.s_k));
-    }
+    sa.acc = d_stats;
+    NMOD_HIP(enqueue_dispatch_stats(sa, res.s_k));
     if (want_comb) {                              // the KS track of the whole batch stays on the device for K3
       NMOD_HIP(hipMemcpyAsync(f_ksd + lo, dv[4], (size_t)n * 8, hipMemcpyDeviceToDevice, res.s_k));
       NMOD_HIP(hipMemcpyAsync(f_ksp + lo, dv[5], (size_t)n * 8, hipMemcpyDeviceToDevice, res.s_k));
@@ -510,10 +508,9 @@ static int detect_host_pipelined(const nmod_params* prm, int64_t npos, const voi
     NMOD_HIP(hipMemcpyAsync(out->comb_p, f_cp, (size_t)npos * 8, hipMemcpyDeviceToHost, res.s_k));
     g_host_stats.d2h_bytes += npos * 16;
   }
-  NMOD_HIP(hipMemcpyAsync(g_dispatch.host_totals, d_stats, kStatsWords * 8, hipMemcpyDeviceToHost, res.s_k));
+  NMOD_HIP(hipMemcpyAsync(stats_totals, d_stats, kStatsWords * 8, hipMemcpyDeviceToHost, res.s_k));
   for (int c = std::max(0, nchunks - slots); c < nchunks; ++c) { rc = retire(c); if (rc != NMOD_OK) return rc; }
   NMOD_HIP(hipStreamSynchronize(res.s_k));
-  g_dispatch.valid = true; g_dispatch.host = true; g_dispatch.npos = npos;
   g_host_stats.chunks = nchunks; g_host_stats.slots = slots; g_host_stats.copy_threads = threads;
   g_host_stats.pinned_input = pinned_in ? 1 : 0;
   g_host_stats.chunk_positions = cap_pos;

@@ -120,8 +120,7 @@ static Workspace carve(void* base, int64_t npos) {
 // ---------------------------------------------------------------- binning kernels
 struct BinArgs {
   int64_t npos; const int64_t* off0; const int64_t* off1; int64_t stride0, stride1;
-  int cmax0, cmax1; int ks_only; int allow_big; int force_big; int64_t lim0, lim1; uint8_t* cls; int32_t* meta; int32_t* order;
-  int deep;                                     // NMOD_FLAG_DEEP: a group beyond NMOD_MAX_RANKED within lim0 / lim1 takes kDeepClass
+  ClassRule rule; uint8_t* cls; int32_t* meta; int32_t* order;
 };
 
 
@@ -146,22 +145,7 @@ __global__ __launch_bounds__(256) void classify_kernel(BinArgs a) {
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < a.npos; p += (int64_t)gridDim.x * 256) {
     int64_t n0 = a.stride0 > 0 ? a.stride0 : a.off0[p + 1] - a.off0[p];
     int64_t n1 = a.stride1 > 0 ? a.stride1 : a.off1[p + 1] - a.off1[p];
-    int c0 = size_class_of(n0), c1 = size_class_of(n1);
-    // beyond what the caller promised (or the format allows): skipped, NMOD_STATUS_TOO_LARGE
-    const bool beyond = n0 > NMOD_MAX_RANKED || n1 > NMOD_MAX_RANKED;
-    const bool over = n0 > a.lim0 || n1 > a.lim1 || (beyond && !a.deep);
-    // beyond the wave-resident kernels: KS-only sorts the smaller group only, all-tests mode sorts both
-    const bool big = a.force_big ||                                   // fp64 keys: every position takes big_rank_kernel
-                     (a.ks_only ? (c0 < c1 ? c0 : c1) >= kNumSizeClasses : (c0 >= kNumSizeClasses || c1 >= kNumSizeClasses));
-    int cid;
-    if (over || n0 <= 0 || n1 <= 0 || (big && !a.allow_big)) cid = 255;
-    else if (beyond) cid = kDeepClass;                                // (a.deep: the multi-workgroup form, deep_rank.hpp)
-    else if (big && !a.ks_only && !a.force_big && (n0 < n1 ? n0 : n1) <= 256 && (n0 < n1 ? n1 : n0) <= kWideBigMaxQ)
-      cid = kWideBigBase + (c0 < c1 ? c0 : c1);
-    else if (big && !a.ks_only && !a.force_big && (n0 < n1 ? n0 : n1) <= kBigHistMaxS && (n0 < n1 ? n1 : n0) <= kBigHistMaxQ) cid = kBigHistClass;
-    else if (big) cid = kBigClass;
-    else if (a.ks_only) cid = kKsClassBase + (c0 < c1 ? c0 : c1);
-    else cid = (c0 > a.cmax0 || c1 > a.cmax1) ? 255 : launch_class_of(c0, c1);
+    const int cid = classify_position(n0, n1, a.rule);     // (255: beyond what the caller promised or the format allows, TOO_LARGE)
     if (cid == kBigClass)
       atomicAdd(reinterpret_cast<unsigned long long*>(a.meta + kMetaBigTotal),
                 (unsigned long long)(big_pow2_ceil(n0) + big_pow2_ceil(n1)));
@@ -345,8 +329,8 @@ __global__ __launch_bounds__(256) void f64_redo_list_kernel(F64Args a) {
 
 // ---------------------------------------------------------------- dispatch statistics (nmod_last_dispatch_stats)
 // Which K1 form took how many positions of a batch is decided on the device (class lists, the probes' gates, the counting forms'
-// per-position flags) and never leaves it on the hot path.  detect_device remembers where those facts sit in the caller's
-// workspace; dispatch_stats_kernel reduces them to kStatsWords counters when somebody asks (device-resident batches: on request,
+// per-position flags) and never leaves it on the hot path.  detect_device returns where those facts sit in the caller's
+// workspace (StatsArgs); dispatch_stats_kernel reduces them to kStatsWords counters when somebody asks (device-resident batches: on request,
 // nothing is launched otherwise; host-resident batches: once per chunk into a per-call accumulator, the path is PCIe-bound).
 struct StatsArgs {
   int64_t npos; int32_t uniform_cls;             // >= 0: one class holds all npos positions (no class lists were built)
@@ -379,11 +363,12 @@ __global__ __launch_bounds__(256) void dispatch_stats_kernel(StatsArgs a) {
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&a.acc[1], (unsigned long long)mine);
   }
 }
+// the last successful nmod_detect_batch of the thread (written there and nowhere else)
 struct DispatchRec {
   bool valid = false; bool host = false; int device = 0; hipStream_t stream = nullptr;
-  StatsArgs args;                                // (acc = the workspace's own block for a device-resident batch)
-  unsigned long long host_totals[kStatsWords];   // a host-resident batch: read back before the call returned
-  int64_t npos = 0; int32_t ks_only = 0;
+  StatsArgs args = {};                                // (acc = the workspace's own block for a device-resident batch)
+  unsigned long long host_totals[kStatsWords] = {};   // a host-resident (or empty) batch: read back before the call returned
+  int64_t npos = 0;
 };
 thread_local DispatchRec g_dispatch;
 static hipError_t enqueue_dispatch_stats(const StatsArgs& a, hipStream_t stream) {
@@ -459,6 +444,21 @@ static hipMemPool_t scratch_pool(int dev) {
     g_pool[dev] = pool;
   }
   return g_pool[dev];
+}
+
+// CU count per device, looked up once (the attribute query is not cheap and this runs every batch); an atomic per device:
+// concurrent first calls both query and store the same value
+static hipError_t device_cus(int dev, int* num_cus) {
+  static std::atomic<int> cache[kMaxDevices];
+  const bool cacheable = dev >= 0 && dev < kMaxDevices;
+  int n = cacheable ? cache[dev].load(std::memory_order_relaxed) : 0;
+  if (n <= 0) {
+    const hipError_t e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    if (cacheable) cache[dev].store(n, std::memory_order_relaxed);
+  }
+  *num_cus = n;
+  return hipSuccess;
 }
 
 struct DevScratch {
@@ -550,10 +550,312 @@ static int enqueue_deep(const nmod_params* prm, DeepArgs& da, DevScratch& scratc
 // the float64 samples behind float32 keys (detect_f64): device pointers in the index space of the offsets
 struct F64Src { const double* d0; const double* d1; uint8_t* cls3; };
 
+// ---------------------------------------------------------------- one device-resident batch, stage by stage (detect_device)
+// plan_batch decides what runs; enqueue_bins, enqueue_k1, enqueue_large, enqueue_f64_fixups and enqueue_outputs put it on the
+// stream in that order.  Each stage reads and extends this record.
+struct Batch {
+  const nmod_params* prm; hipStream_t stream; int num_cus;
+  int64_t npos; const void* sig0; const void* sig1; const int64_t* off0; const int64_t* off1;
+  int64_t stride0, stride1;                    // (0: the group's offsets)
+  const int32_t* run_id; nmod_out* out; const F64Src* f64; Workspace ws;
+  // plan_batch
+  int tests; bool all, want_comb, deep_flag, binned, big_possible, deep_possible, cw_on, wide_redo;
+  int deep_dtype;                              // (float64 samples: the deep form sorts them as 64-bit keys)
+  int64_t max0, max1;                          // the limits K1 covers: the promised or measured maxima, capped
+  ClassRule rule;
+  int uniform_cls;                             // an unbinned batch: the one class of all its positions
+  bool wanted[kNumClasses];                    // the class lists K1 launches (and, with big_possible in all-tests mode, the WIDE large classes)
+  // enqueue_k1 on
+  RankStatsArgs ra;
+  bool cw_ran;                                 // the counting form for any coverage was tried on some class
+  DeepArgs da; DevScratch deep_scratch;        // the deep form's state between K1 and its finalize
+};
+
+// The maxima (their one host round trip when the caller promised none), the test mode, unbinned or binned, whether large or deep
+// positions can exist, the counting forms on or off, the classes K1 launches; the workspace's counters are cleared here.
+static int plan_batch(Batch& b) {
+  const nmod_params* prm = b.prm;
+  hipStream_t stream = b.stream;
+  const Workspace& ws = b.ws;
+  b.tests = prm->tests | (b.want_comb ? NMOD_TEST_KS : 0);
+  b.all = (b.tests & (NMOD_TEST_MWU | NMOD_TEST_WELCH)) != 0 || prm->want_mstd;
+  const bool uniform = prm->stride0 > 0 && prm->stride1 > 0;
+  b.max0 = prm->stride0 > 0 ? prm->stride0 : prm->max_n0;
+  b.max1 = prm->stride1 > 0 ? prm->stride1 : prm->max_n1;
+  // the class counters / cursors / maxima in ws.meta: cleared once per batch, and not at all for a fixed-stride batch of
+  // wave-resident positions (one launch, no lists: the common benchmark shape pays no memset per step)
+  bool meta_cleared = false;
+  if (b.max0 <= 0 || b.max1 <= 0) {
+    NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
+    meta_cleared = true;
+    hipLaunchKernelGGL(max_n_kernel, dim3(1024), dim3(256), 0, stream, b.npos,
+                       prm->stride0 > 0 ? nullptr : b.off0, prm->stride1 > 0 ? nullptr : b.off1, ws.meta);
+    NMOD_HIP(hipGetLastError());
+    int32_t mx[2];
+    NMOD_HIP(hipMemcpyAsync(mx, ws.meta + kMetaMax, 8, hipMemcpyDeviceToHost, stream));
+    NMOD_HIP(hipStreamSynchronize(stream));
+    if (b.max0 <= 0) b.max0 = mx[0];
+    if (b.max1 <= 0) b.max1 = mx[1];
+  }
+  // a group beyond NMOD_MAX_RANKED: that position is skipped by the classifier and flagged NMOD_STATUS_TOO_LARGE by K2, the rest
+  // of the batch is computed (the reference has no limit: myDetect.py:327-343) — unless NMOD_FLAG_DEEP sends it to the deep form
+  // (deep_rank.hpp), which takes groups up to NMOD_MAX_DEEP
+  b.deep_flag = (prm->flags & NMOD_FLAG_DEEP) != 0;
+  const int64_t group_cap = b.deep_flag ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;
+  b.max0 = std::min<int64_t>(b.max0, group_cap); b.max1 = std::min<int64_t>(b.max1, group_cap);
+  b.deep_possible = b.deep_flag && std::max(b.max0, b.max1) > NMOD_MAX_RANKED;
+  b.deep_dtype = b.f64 ? NMOD_DTYPE_F64 : prm->dtype;
+  int cmax0 = size_class_of(std::max<int64_t>(b.max0, 1)), cmax1 = size_class_of(std::max<int64_t>(b.max1, 1));
+  // positions beyond the wave-resident kernels (both groups sorted in all-tests mode, the smaller one in KS-only
+  // mode) go to big_rank_kernel; the maxima tell whether any can exist
+  b.big_possible = b.all ? (cmax0 >= kNumSizeClasses || cmax1 >= kNumSizeClasses) : (std::min(cmax0, cmax1) >= kNumSizeClasses);
+  cmax0 = std::min(cmax0, kNumSizeClasses - 1); cmax1 = std::min(cmax1, kNumSizeClasses - 1);
+  b.binned = !(uniform && !b.big_possible && !b.deep_possible);
+  if (!meta_cleared && (b.binned || b.f64)) {
+    NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
+    meta_cleared = true;
+  }
+  b.rule.lim0 = std::max<int64_t>(b.max0, 1); b.rule.lim1 = std::max<int64_t>(b.max1, 1);
+  b.rule.ks_only = b.all ? 0 : 1; b.rule.deep = b.deep_flag ? 1 : 0;
+  b.uniform_cls = -1;
+  if (!b.binned) {
+    b.uniform_cls = classify_position(b.max0, b.max1, b.rule);
+    if (b.uniform_cls != 255) b.wanted[b.uniform_cls] = true;
+  } else {
+    for (int c0 = 0; c0 <= cmax0; ++c0)
+      for (int c1 = 0; c1 <= cmax1; ++c1) b.wanted[small_class_of(c0, c1, !b.all)] = true;
+  }
+  // all tests, classes other than the 256-capacity one: the counting form for any coverage (rank_count_wide.hpp) is tried per class
+  // when its probe finds the class event-like; the sorting form of the class then runs over the work list that is left
+  // (NMOD_FLAG_NO_COUNT_WIDE turns it off; KS-only batches too — the form without the tie term and the moments — when a group of
+  // the batch can reach the size it takes)
+  const bool counting_off = (prm->flags & NMOD_FLAG_NO_COUNTING) != 0, cw_off = (prm->flags & NMOD_FLAG_NO_COUNT_WIDE) != 0;
+  b.cw_on = !counting_off && !cw_off && (b.all || std::max(b.max0, b.max1) >= kCwKsMinQ);
+  // the WIDE float32 form may put positions on its redo list: wide_redo_kernel finishes them (count read on the device)
+  const bool wide_f32 = b.all && prm->dtype == NMOD_DTYPE_F32;
+  b.wide_redo = wide_f32 && b.big_possible;
+  for (int cls = 0; cls < kNumClasses; ++cls) b.wide_redo = b.wide_redo || (wide_f32 && b.wanted[cls] && wide_class(cls));
+  if (b.wide_redo && !meta_cleared) NMOD_HIP(hipMemsetAsync(ws.meta + kMetaWideRedo, 0, 4, stream));   // (the redo counter alone)
+  return NMOD_OK;
+}
+
+// binned batches: every position's class (and the large positions' scratch), then the class lists in ws.order
+static int enqueue_bins(Batch& b) {
+  BinArgs ba;
+  ba.npos = b.npos; ba.off0 = b.off0; ba.off1 = b.off1; ba.stride0 = b.stride0; ba.stride1 = b.stride1;
+  ba.rule = b.rule; ba.cls = b.ws.cls; ba.meta = b.ws.meta; ba.order = b.ws.order;
+  const unsigned blocks = (unsigned)std::min<int64_t>((b.npos + 255) / 256, 4096);
+  hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(256), 0, b.stream, ba);
+  hipLaunchKernelGGL(class_offsets_kernel, dim3(1), dim3(64), 0, b.stream, b.ws.meta);
+  hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((b.npos + kScatterSpan - 1) / kScatterSpan)), dim3(256), 0, b.stream, ba);
+  NMOD_HIP(hipGetLastError());
+  return NMOD_OK;
+}
+
+// K1 of the wave-resident classes: the counting forms for any coverage (probe, then one run over every class), each class's
+// sorting form, the WIDE classes of large positions, the WIDE float32 form's redo
+static int enqueue_k1(Batch& b) {
+  const nmod_params* prm = b.prm;
+  const Workspace& ws = b.ws;
+  RankStatsArgs& ra = b.ra;
+  memset(&ra, 0, sizeof(ra));
+  ra.sig0 = b.sig0; ra.sig1 = b.sig1; ra.off0 = b.off0; ra.off1 = b.off1; ra.stride0 = b.stride0; ra.stride1 = b.stride1;
+  ra.npos = b.npos; ra.ks_num = ws.ks_num; ra.mwu_s = ws.mwu_s; ra.tie = ws.tie; ra.moments = ws.moments; ra.ks_d_ref = ws.ks_d_ref;
+  ra.ks_rational_d = (!b.all && (prm->flags & NMOD_FLAG_KS_RATIONAL_D)) ? 1 : 0;
+  ra.tied = b.f64 ? ws.tied : nullptr;          // float32 keys of float64 samples: K1 reports the positions whose keys tie
+  ra.redo_list = ws.redo; ra.redo_count = ws.meta + kMetaWideRedo;
+  if (b.binned) { ra.pos_list = ws.order; ra.class_meta = ws.meta; }
+  // all tests on capacity-256 positions: the counting form is tried first (rank_count.hpp; a device-side probe decides whether
+  // the batch is event-like, positions it cannot take fall through to rank_hist_kernel).  The float32 images of float64 samples
+  // qualify where they are whole numbers (positions on the 0.001 grid carry k as keys).  NMOD_FLAG_NO_COUNTING turns it off (A/B, parity tests).
+  if (b.all && !(prm->flags & NMOD_FLAG_NO_COUNTING)) { ra.cnt_gate = ws.meta + kMetaCntGate; ra.cnt_done = ws.cnt_done; }
+  const K1Launcher& k1 = k1_launcher(prm->dtype, b.all);
+  CountWideWs cww;
+  cww.gates = ws.work_meta + 2 * kClassStride; cww.work_list = ws.work_list; cww.work_meta = ws.work_meta;
+  std::vector<int> counted;
+  if (b.cw_on) {
+    for (int cls = 0; cls < kNumClasses; ++cls) if (b.wanted[cls] && count_wide_class(cls)) counted.push_back(cls);
+    if (b.big_possible && b.all) for (int cs = 0; cs < kNumWideBig; ++cs) counted.push_back(kWideBigBase + cs);
+  }
+  b.cw_ran = !counted.empty();
+  if (b.cw_ran) {
+    bool vc = false;                                          // (both groups above 1 024 samples: the value-domain form, all tests)
+    for (int c : counted) vc = vc || class_forms(c).count == kCountValue;
+    NMOD_HIP(k1.count_wide_prepare(counted.data(), (int)counted.size(), b.stream, ra, cww));
+    NMOD_HIP(k1.count_wide_run(b.num_cus, b.npos, b.stream, ra, cww, vc));
+  }
+  // a class's sorting form; where the counting form was in play (its gate is set, on the device) it walks the work list
+  auto launch_class = [&](int cls, bool cw) -> hipError_t {
+    ra.class_id = cls; ra.alt_gates = cw ? cww.gates : nullptr; ra.alt_list = ws.work_list; ra.alt_meta = ws.work_meta;
+    const hipError_t e = k1.rank_stats(cls, b.num_cus, b.npos, b.stream, ra);
+    ra.alt_gates = nullptr;
+    return e;
+  };
+  for (int cls = 0; cls < kNumClasses; ++cls) if (b.wanted[cls]) NMOD_HIP(launch_class(cls, b.cw_on && count_wide_class(cls)));
+  // larger group of 2 049 .. 4 096 samples against at most 256: rank_hist_kernel WIDE as well
+  if (b.big_possible && b.all) for (int cs = 0; cs < kNumWideBig; ++cs) NMOD_HIP(launch_class(kWideBigBase + cs, b.cw_on));
+  if (b.wide_redo) {
+    WideRedoArgs wr;
+    wr.sig0 = b.sig0; wr.sig1 = b.sig1; wr.off0 = b.off0; wr.off1 = b.off1; wr.stride0 = b.stride0; wr.stride1 = b.stride1;
+    wr.list = ws.redo; wr.count = ws.meta + kMetaWideRedo; wr.tie = ws.tie;
+    hipLaunchKernelGGL(wide_redo_kernel, dim3((unsigned)std::min<int64_t>(b.npos, (int64_t)b.num_cus * 2)), dim3(kBigThreads), 0, b.stream, wr);
+    NMOD_HIP(hipGetLastError());
+  }
+  return NMOD_OK;
+}
+
+// the arguments of a large-position launch over the list of class `big_class` (counts and offsets in `class_meta`, positions in
+// ws.order), writing K1's outputs; scratch / cursor: the key slab and its bump allocator, where the form sorts in one
+static BigArgs big_args(const Batch& b, const void* sig0, const void* sig1, const int32_t* class_meta, int big_class, bool all,
+                        void* scratch, int32_t* cursor) {
+  BigArgs bg;
+  memset(&bg, 0, sizeof(bg));
+  bg.sig0 = sig0; bg.sig1 = sig1; bg.off0 = b.off0; bg.off1 = b.off1; bg.stride0 = b.stride0; bg.stride1 = b.stride1;
+  bg.pos_list = b.ws.order; bg.class_meta = class_meta; bg.big_class = big_class; bg.all = all ? 1 : 0;
+  bg.scratch = scratch; bg.cursor = reinterpret_cast<unsigned long long*>(cursor);
+  bg.ks_num = b.ws.ks_num; bg.mwu_s = b.ws.mwu_s; bg.tie = b.ws.tie; bg.moments = b.ws.moments; bg.ks_d_ref = b.ws.ks_d_ref;
+  return bg;
+}
+
+// the large positions of a binned batch: the deep form, big_rank_kernel, big_hist_kernel
+static int enqueue_large(Batch& b) {
+  if (!b.big_possible && !b.deep_possible) return NMOD_OK;
+  const nmod_params* prm = b.prm;
+  hipStream_t stream = b.stream;
+  const Workspace& ws = b.ws;
+  // the only host round trip of this path: how many large (and deep) positions, how much scratch
+  int32_t head[8];
+  NMOD_HIP(hipMemcpyAsync(&head[0], ws.meta + kBigClass, 8, hipMemcpyDeviceToHost, stream));     // kBigClass, kBigHistClass
+  NMOD_HIP(hipMemcpyAsync(&head[2], ws.meta + kMetaBigTotal, 8, hipMemcpyDeviceToHost, stream));
+  if (b.deep_possible) {
+    NMOD_HIP(hipMemcpyAsync(&head[4], ws.meta + kDeepClass, 4, hipMemcpyDeviceToHost, stream));
+    NMOD_HIP(hipMemcpyAsync(&head[6], ws.meta + kMetaDeepTiles, 8, hipMemcpyDeviceToHost, stream));
+  } else {
+    head[4] = 0; head[6] = 0; head[7] = 0;
+  }
+  NMOD_HIP(hipStreamSynchronize(stream));
+  if (head[4] > 0) {
+    unsigned long long tiles;
+    memcpy(&tiles, &head[6], 8);
+    const int rc = enqueue_deep(prm, b.da, b.deep_scratch, b.deep_dtype, b.f64 ? (const void*)b.f64->d0 : b.sig0,
+                                b.f64 ? (const void*)b.f64->d1 : b.sig1, b.off0, b.off1, b.stride0, b.stride1, ws, head[4], (int64_t)tiles,
+                                std::max(b.max0, b.max1), b.all, b.num_cus, stream);
+    if (rc != NMOD_OK) return rc;
+  }
+  const int64_t nbig = head[0], nbig_hist = head[1];
+  unsigned long long total;
+  memcpy(&total, &head[2], 8);
+  if (nbig > 0) {
+    DevScratch big_scratch;
+    NMOD_HIP(big_scratch.alloc((size_t)total * 4, stream, prm->device));
+    const BigArgs bg = big_args(b, b.sig0, b.sig1, ws.meta, kBigClass, b.all, big_scratch.p, ws.meta + kMetaBigCursor);
+    const unsigned blocks = (unsigned)std::min<int64_t>(nbig, (int64_t)b.num_cus * 4);   // 4 x 33 KB of LDS per CU
+    if (prm->dtype == NMOD_DTYPE_F32) hipLaunchKernelGGL(big_rank_kernel<0>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
+    else hipLaunchKernelGGL(big_rank_kernel<1>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
+    NMOD_HIP(hipGetLastError());
+    NMOD_HIP(big_scratch.release(stream));
+  }
+  if (nbig_hist > 0) {
+    const BigArgs bg = big_args(b, b.sig0, b.sig1, ws.meta, kBigHistClass, true, nullptr, nullptr);
+    const unsigned blocks = (unsigned)std::min<int64_t>(nbig_hist, (int64_t)b.num_cus * 2);        // 80 KB of LDS per block
+    auto kfn = prm->dtype == NMOD_DTYPE_F32 ? big_hist_kernel<0> : big_hist_kernel<1>;
+    NMOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigHistLds));
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBigThreads), kBigHistLds, stream, bg);
+    NMOD_HIP(hipGetLastError());
+  }
+  return NMOD_OK;
+}
+
+// float64 samples behind the keys: redo the positions whose keys tied with 64-bit keys, moments from the samples
+static int enqueue_f64_fixups(Batch& b) {
+  const F64Src* f64 = b.f64;
+  const Workspace& ws = b.ws;
+  hipStream_t stream = b.stream;
+  F64Args fx;
+  memset(&fx, 0, sizeof(fx));
+  fx.d0 = f64->d0; fx.d1 = f64->d1; fx.off0 = b.off0; fx.off1 = b.off1; fx.stride0 = b.stride0; fx.stride1 = b.stride1;
+  fx.npos = b.npos; fx.cls3 = f64->cls3; fx.tied = ws.tied; fx.cls = b.binned ? ws.cls : nullptr; fx.deep = b.deep_flag ? 1 : 0;
+  fx.order = ws.order; fx.meta = ws.meta; fx.moments = ws.moments;
+  const unsigned gb = (unsigned)std::min<int64_t>((b.npos + 255) / 256, 4096);
+  hipLaunchKernelGGL(f64_redo_list_kernel, dim3(gb), dim3(256), 0, stream, fx);
+  NMOD_HIP(hipGetLastError());
+  int32_t nredo = 0; unsigned long long total = 0;
+  NMOD_HIP(hipMemcpyAsync(&nredo, ws.meta + kMetaRedo, 4, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipMemcpyAsync(&total, ws.meta + kMetaRedoTotal, 8, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipStreamSynchronize(stream));
+  if (nredo > 0) {
+    DevScratch redo_scratch;
+    NMOD_HIP(redo_scratch.alloc((size_t)total * 8, stream, b.prm->device));
+    const BigArgs bg = big_args(b, f64->d0, f64->d1, ws.meta + kMetaRedo, 0, b.all, redo_scratch.p, ws.meta + kMetaRedoCursor);
+    const unsigned blocks = (unsigned)std::min<int64_t>(nredo, (int64_t)b.num_cus * 4);
+    ScopedKernelTimer tm(b.prm->timer, NMOD_KERNEL_RANK_STATS, stream);
+    hipLaunchKernelGGL(big_rank_kernel<2>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
+    NMOD_HIP(hipGetLastError());
+    NMOD_HIP(redo_scratch.release(stream));
+  }
+  if (b.all) {
+    const unsigned mb = (unsigned)std::min<int64_t>((b.npos + 3) / 4, (int64_t)b.num_cus * 16);
+    hipLaunchKernelGGL(f64_moments_kernel, dim3(mb), dim3(256), 0, stream, fx);
+    NMOD_HIP(hipGetLastError());
+  }
+  return NMOD_OK;
+}
+
+// the non-finite scan, the deep positions' outputs, K2 (p-values) and K3 (the combined track)
+static int enqueue_outputs(Batch& b) {
+  const nmod_params* prm = b.prm;
+  const Workspace& ws = b.ws;
+  const F64Src* f64 = b.f64;
+  hipStream_t stream = b.stream;
+  FinalizeArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.npos = b.npos; fa.off0 = b.off0; fa.off1 = b.off1; fa.stride0 = b.stride0; fa.stride1 = b.stride1;
+  fa.ks_num = ws.ks_num; fa.mwu_s = ws.mwu_s; fa.tie = ws.tie; fa.moments = ws.moments; fa.ks_d_ref = b.ra.ks_rational_d ? nullptr : ws.ks_d_ref;   // every K1 form writes ks_2samp's float form of D (unless the caller opted out)
+  fa.tests = b.tests; fa.want_mstd = prm->want_mstd; fa.out = *b.out;
+  // what K1 covered: exactly the limits the classifier used (the promised / measured maxima), in every mode —
+  // a position beyond them was skipped by K1 and must be flagged TOO_LARGE here, never read from the workspace
+  fa.max_n0 = std::max<int64_t>(std::min<int64_t>(b.max0, NMOD_MAX_RANKED), 1);
+  fa.max_n1 = std::max<int64_t>(std::min<int64_t>(b.max1, NMOD_MAX_RANKED), 1);
+  fa.min_cap = 0;
+  if (b.deep_possible) { fa.deep_lim0 = std::max<int64_t>(b.max0, 1); fa.deep_lim1 = std::max<int64_t>(b.max1, 1); }   // (K2 leaves them to the deep form)
+  if ((prm->flags & NMOD_FLAG_CHECK_FINITE) && prm->dtype != NMOD_DTYPE_I16_MILLI) {
+    // one pass over the samples: the float64 samples themselves where the keys are their float32 images
+    NonfiniteArgs na;
+    memset(&na, 0, sizeof(na));
+    na.sig0 = f64 ? (const void*)f64->d0 : b.sig0; na.sig1 = f64 ? (const void*)f64->d1 : b.sig1; na.f64 = f64 ? 1 : 0;
+    na.off0 = b.off0; na.off1 = b.off1; na.stride0 = b.stride0; na.stride1 = b.stride1; na.npos = b.npos;
+    na.lim0 = fa.max_n0; na.lim1 = fa.max_n1; na.flag = ws.nonfinite;
+    const unsigned nb_ = (unsigned)std::min<int64_t>((b.npos + 3) / 4, (int64_t)b.num_cus * 32);
+    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(nb_), dim3(256), 0, stream, na);
+    NMOD_HIP(hipGetLastError());
+    fa.nonfinite = ws.nonfinite;
+  }
+  if (b.want_comb) {                     // the combine needs the KS track even if the caller does not
+    if (!fa.out.ks_d) fa.out.ks_d = ws.tmp_ks_d;
+    if (!fa.out.ks_p) fa.out.ks_p = ws.tmp_ks_p;
+  }
+  {
+    ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_FINALIZE, stream);
+    if (b.da.ndeep > 0) {                // the deep positions' outputs (K2 skips them), then the slab goes back to the pool
+      const unsigned db = (unsigned)((b.da.ndeep + 255) / 256);
+      const int32_t rat = b.ra.ks_rational_d, chk = (prm->flags & NMOD_FLAG_CHECK_FINITE) ? 1 : 0;
+      if (b.deep_dtype == NMOD_DTYPE_I16_MILLI) hipLaunchKernelGGL(deep_finalize_kernel<1>, dim3(db), dim3(256), 0, stream, b.da, fa, rat, chk);
+      else if (b.deep_dtype == NMOD_DTYPE_F64) hipLaunchKernelGGL(deep_finalize_kernel<2>, dim3(db), dim3(256), 0, stream, b.da, fa, rat, chk);
+      else hipLaunchKernelGGL(deep_finalize_kernel<0>, dim3(db), dim3(256), 0, stream, b.da, fa, rat, chk);
+      NMOD_HIP(hipGetLastError());
+      NMOD_HIP(b.deep_scratch.release(stream));
+    }
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((b.npos + 255) / 256)), dim3(256), 0, stream, fa);
+    NMOD_HIP(hipGetLastError());
+  }
+  if (b.want_comb) return launch_combine(prm, stream, b.npos, fa.out.ks_d, fa.out.ks_p, b.run_id, b.out->comb_st, b.out->comb_p);
+  return NMOD_OK;
+}
+
+// One batch in device memory on prm->stream.  stats (may be null): where the facts of nmod_last_dispatch_stats sit in `workspace`.
 static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
                          const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
-                         int64_t workspace_bytes, nmod_out* out, const F64Src* f64 = nullptr) {
-  hipStream_t stream = (hipStream_t)prm->stream;
+                         int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const F64Src* f64 = nullptr) {
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1 || !out) return NMOD_ERR_INVALID_ARG;
   if ((prm->stride0 <= 0 && !off0) || (prm->stride1 <= 0 && !off1)) return NMOD_ERR_INVALID_ARG;
@@ -561,325 +863,29 @@ static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0,
   const bool want_comb = prm->method != NMOD_METHOD_KS && (out->comb_st || out->comb_p);
   if (want_comb && (!out->comb_st || !out->comb_p)) return NMOD_ERR_INVALID_ARG;
   if (want_comb && prm->nb > 0 && !run_id) return NMOD_ERR_INVALID_ARG;
-  Workspace ws = carve(workspace, npos);
-  if (!workspace || workspace_bytes < ws.bytes) return NMOD_ERR_WORKSPACE;
-
-  // CU count per device, looked up once (the attribute query is not cheap and this runs every batch); an atomic
-  // per device: concurrent first calls both query and store the same value
-  static std::atomic<int> cu_cache[kMaxDevices];
-  int num_cus = (prm->device >= 0 && prm->device < kMaxDevices) ? cu_cache[prm->device].load(std::memory_order_relaxed) : 0;
-  if (num_cus <= 0) {
-    NMOD_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
-    if (prm->device >= 0 && prm->device < kMaxDevices) cu_cache[prm->device].store(num_cus, std::memory_order_relaxed);
-  }
-
-  int tests = prm->tests;
-  if (want_comb) tests |= NMOD_TEST_KS;
-  const bool all = (tests & (NMOD_TEST_MWU | NMOD_TEST_WELCH)) != 0 || prm->want_mstd;
-
-  // ---- size classes
-  const bool uniform = prm->stride0 > 0 && prm->stride1 > 0;
-  int64_t max0 = prm->stride0 > 0 ? prm->stride0 : prm->max_n0;
-  int64_t max1 = prm->stride1 > 0 ? prm->stride1 : prm->max_n1;
-  // the class counters / cursors / maxima in ws.meta: cleared once per batch, and not at all for a fixed-stride batch of
-  // wave-resident positions (one launch, no lists: the common benchmark shape pays no memset per step)
-  bool meta_cleared = false;
-  if (max0 <= 0 || max1 <= 0) {
-    NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
-    meta_cleared = true;
-    hipLaunchKernelGGL(max_n_kernel, dim3(1024), dim3(256), 0, stream, npos,
-                       prm->stride0 > 0 ? nullptr : off0, prm->stride1 > 0 ? nullptr : off1, ws.meta);
-    NMOD_HIP(hipGetLastError());
-    int32_t mx[2];
-    NMOD_HIP(hipMemcpyAsync(mx, ws.meta + kMetaMax, 8, hipMemcpyDeviceToHost, stream));
-    NMOD_HIP(hipStreamSynchronize(stream));
-    if (max0 <= 0) max0 = mx[0];
-    if (max1 <= 0) max1 = mx[1];
-  }
-  // a group beyond NMOD_MAX_RANKED: that position is skipped by the classifier and flagged NMOD_STATUS_TOO_LARGE by K2, the rest
-  // of the batch is computed (the reference has no limit: myDetect.py:327-343) — unless NMOD_FLAG_DEEP sends it to the deep form
-  // (deep_rank.hpp), which takes groups up to NMOD_MAX_DEEP
-  const bool deep_flag = (prm->flags & NMOD_FLAG_DEEP) != 0;
-  const int64_t group_cap = deep_flag ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;
-  max0 = std::min<int64_t>(max0, group_cap); max1 = std::min<int64_t>(max1, group_cap);
-  const bool deep_possible = deep_flag && std::max(max0, max1) > NMOD_MAX_RANKED;
-  int cmax0 = size_class_of(std::max<int64_t>(max0, 1)), cmax1 = size_class_of(std::max<int64_t>(max1, 1));
-  // positions beyond the wave-resident kernels (both groups sorted in all-tests mode, the smaller one in KS-only
-  // mode) go to big_rank_kernel; the maxima tell whether any can exist
-  const bool big_possible = all ? (cmax0 >= kNumSizeClasses || cmax1 >= kNumSizeClasses)
-                                : (std::min(cmax0, cmax1) >= kNumSizeClasses);
-  cmax0 = std::min(cmax0, kNumSizeClasses - 1); cmax1 = std::min(cmax1, kNumSizeClasses - 1);
-  const bool binned = !(uniform && !big_possible && !deep_possible);
-  if (!meta_cleared && (binned || f64)) NMOD_HIP(hipMemsetAsync(ws.meta, 0, kMetaInts * 4, stream));
-
-  RankStatsArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  ra.sig0 = sig0; ra.sig1 = sig1; ra.off0 = off0; ra.off1 = off1;
-  ra.stride0 = prm->stride0 > 0 ? prm->stride0 : 0; ra.stride1 = prm->stride1 > 0 ? prm->stride1 : 0;
-  ra.npos = npos; ra.ks_num = ws.ks_num; ra.mwu_s = ws.mwu_s; ra.tie = ws.tie; ra.moments = ws.moments; ra.ks_d_ref = ws.ks_d_ref;
-  ra.ks_rational_d = (!all && (prm->flags & NMOD_FLAG_KS_RATIONAL_D)) ? 1 : 0;
-  ra.tied = f64 ? ws.tied : nullptr;            // float32 keys of float64 samples: K1 reports the positions whose keys tie
-  ra.redo_list = ws.redo; ra.redo_count = ws.meta + kMetaWideRedo;
-  // the WIDE float32 form may put positions on its redo list: wide_redo_kernel finishes them (count read on the device)
-  auto launch_wide_redo = [&]() -> int {
-    WideRedoArgs wr;
-    wr.sig0 = sig0; wr.sig1 = sig1; wr.off0 = off0; wr.off1 = off1; wr.stride0 = ra.stride0; wr.stride1 = ra.stride1;
-    wr.list = ws.redo; wr.count = ws.meta + kMetaWideRedo; wr.tie = ws.tie;
-    hipLaunchKernelGGL(wide_redo_kernel, dim3((unsigned)std::min<int64_t>(npos, (int64_t)num_cus * 2)), dim3(kBigThreads), 0, stream, wr);
-    NMOD_HIP(hipGetLastError());
-    return NMOD_OK;
-  };
-  const bool wide_f32 = all && prm->dtype == NMOD_DTYPE_F32;
-  // all tests on capacity-256 positions: the counting form is tried first (rank_count.hpp; a device-side probe decides whether
-  // the batch is event-like, positions it cannot take fall through to rank_hist_kernel).  The float32 images of float64 samples
-  // qualify where they are whole numbers (positions on the 0.001 grid carry k as keys).  NMOD_FLAG_NO_COUNTING turns it off (A/B, parity tests).
-  const bool counting_off = (prm->flags & NMOD_FLAG_NO_COUNTING) != 0;
-  if (all && !counting_off) { ra.cnt_gate = ws.meta + kMetaCntGate; ra.cnt_done = ws.cnt_done; }
-
-  auto launch = [&](int cls, int64_t work) -> hipError_t {
-    ra.class_id = cls;
-    if (prm->dtype == NMOD_DTYPE_F32)
-      return all ? launch_rank_stats_d0_a1(cls, num_cus, work, stream, ra)
-                 : launch_rank_stats_d0_a0(cls, num_cus, work, stream, ra);
-    return all ? launch_rank_stats_d1_a1(cls, num_cus, work, stream, ra)
-               : launch_rank_stats_d1_a0(cls, num_cus, work, stream, ra);
-  };
-
-  // all tests, classes other than the 256-capacity one: the counting form for any coverage (rank_count_wide.hpp) is tried per class
-  // when its probe finds the class event-like; the sorting form of the class then runs over the work list that is left
-  // (NMOD_FLAG_NO_COUNT_WIDE turns it off)
-  const bool cw_off = (prm->flags & NMOD_FLAG_NO_COUNT_WIDE) != 0;
-  // (KS-only batches too — the form without the tie term and the moments — when a group of the batch can reach the size it takes)
-  const bool cw_on = !counting_off && !cw_off && (all || std::max(max0, max1) >= kCwKsMinQ);
-  CountWideWs cww;
-  cww.gates = ws.work_meta + 2 * kClassStride; cww.work_list = ws.work_list; cww.work_meta = ws.work_meta;
-  auto cw_prepare = [&](const std::vector<int>& classes) -> hipError_t {
-    if (classes.empty()) return hipSuccess;
-    if (prm->dtype == NMOD_DTYPE_F32)
-      return all ? launch_count_wide_prepare_d0_a1(classes.data(), (int)classes.size(), stream, ra, cww)
-                 : launch_count_wide_prepare_d0_a0(classes.data(), (int)classes.size(), stream, ra, cww);
-    return all ? launch_count_wide_prepare_d1_a1(classes.data(), (int)classes.size(), stream, ra, cww)
-               : launch_count_wide_prepare_d1_a0(classes.data(), (int)classes.size(), stream, ra, cww);
-  };
-  // ... then the counting form over every class the probe accepted and the compaction of what it left, in one launch each
-  auto cw_run = [&](const std::vector<int>& classes) -> hipError_t {
-    if (classes.empty()) return hipSuccess;
-    hipError_t e = cw_prepare(classes);
-    if (e != hipSuccess) return e;
-    bool vc = false;                                          // (both groups above 1 024 samples: the value-domain form, all tests)
-    for (int c : classes) vc = vc || count_wide_rs_index(c) == 5;
-    if (prm->dtype == NMOD_DTYPE_F32)
-      return all ? launch_count_wide_run_d0_a1(num_cus, npos, stream, ra, cww, vc) : launch_count_wide_run_d0_a0(num_cus, npos, stream, ra, cww, vc);
-    return all ? launch_count_wide_run_d1_a1(num_cus, npos, stream, ra, cww, vc) : launch_count_wide_run_d1_a0(num_cus, npos, stream, ra, cww, vc);
-  };
-  // a class's sorting form; where the counting form was in play (its gate is set, on the device) it walks the work list
-  auto launch_class = [&](int cls, int64_t work, bool counted) -> hipError_t {
-    ra.alt_gates = counted ? cww.gates : nullptr; ra.alt_list = ws.work_list; ra.alt_meta = ws.work_meta;
-    const hipError_t e = launch(cls, work);
-    ra.alt_gates = nullptr;
-    return e;
-  };
-
-  DevScratch big_scratch, deep_scratch;
-  DeepArgs da;                                                // the deep form's state between K1 and its finalize
-  memset(&da, 0, sizeof(da));
-  const int deep_dtype = f64 ? 2 : prm->dtype;                // (float64 samples: the deep form sorts them as 64-bit keys)
-  int st_uniform_cls = -1, st_cnt256 = 0, st_cw = 0;          // for nmod_last_dispatch_stats
-  constexpr int kCls256 = kNumGeneralClasses + 2;
-  if (!binned) {
-    const int ucls = all ? launch_class_of(cmax0, cmax1) : kKsClassBase + std::min(cmax0, cmax1);
-    st_uniform_cls = ucls; st_cnt256 = (ucls == kCls256 && ra.cnt_gate) ? 1 : 0;
-    const bool uwide = wide_f32 && wide_class(ucls);
-    if (uwide && !meta_cleared && !f64) NMOD_HIP(hipMemsetAsync(ws.meta + kMetaWideRedo, 0, 4, stream));   // (the meta block is not cleared for uniform batches)
-    ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_RANK_STATS, stream);
-    const bool counted = cw_on && count_wide_rs_index(ucls) >= 0;
-    st_cw = counted ? 1 : 0;
-    if (counted) NMOD_HIP(cw_run(std::vector<int>{ucls}));
-    NMOD_HIP(launch_class(ucls, npos, counted));
-    if (uwide) { const int rr = launch_wide_redo(); if (rr != NMOD_OK) return rr; }
-  } else {
-    BinArgs ba;
-    ba.npos = npos; ba.off0 = off0; ba.off1 = off1; ba.stride0 = ra.stride0; ba.stride1 = ra.stride1;
-    ba.cmax0 = cmax0; ba.cmax1 = cmax1; ba.ks_only = all ? 0 : 1; ba.allow_big = 1; ba.force_big = 0; ba.lim0 = std::max<int64_t>(max0, 1); ba.lim1 = std::max<int64_t>(max1, 1);
-    ba.deep = deep_flag ? 1 : 0;
-    ba.cls = ws.cls; ba.meta = ws.meta; ba.order = ws.order;
-    unsigned blocks = (unsigned)std::min<int64_t>((npos + 255) / 256, 4096);
-    hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(256), 0, stream, ba);
-    hipLaunchKernelGGL(class_offsets_kernel, dim3(1), dim3(64), 0, stream, ws.meta);
-    hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)((npos + kScatterSpan - 1) / kScatterSpan)), dim3(256), 0, stream, ba);
-    NMOD_HIP(hipGetLastError());
-    ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_RANK_STATS, stream);
-    bool wanted[kNumClasses] = {false};
-    for (int c0 = 0; c0 <= cmax0; ++c0)
-      for (int c1 = 0; c1 <= cmax1; ++c1) wanted[all ? launch_class_of(c0, c1) : kKsClassBase + std::min(c0, c1)] = true;
-    ra.pos_list = ws.order; ra.class_meta = ws.meta;
-    std::vector<int> counted_classes;
-    if (cw_on) {
-      for (int cls = 0; cls < kNumClasses; ++cls) if (wanted[cls] && count_wide_rs_index(cls) >= 0) counted_classes.push_back(cls);
-      if (big_possible && all) for (int cs = 0; cs < kNumWideBig; ++cs) counted_classes.push_back(kWideBigBase + cs);
-      NMOD_HIP(cw_run(counted_classes));
-      st_cw = counted_classes.empty() ? 0 : 1;
-    }
-    st_cnt256 = (all && wanted[kCls256] && ra.cnt_gate) ? 1 : 0;
-    for (int cls = 0; cls < kNumClasses; ++cls) {
-      if (!wanted[cls]) continue;
-      ra.pos_list = ws.order; ra.class_meta = ws.meta; ra.class_id = cls;
-      NMOD_HIP(launch_class(cls, npos, cw_on && count_wide_rs_index(cls) >= 0));
-    }
-    if (big_possible && all) {
-      // larger group of 2 049 .. 4 096 samples against at most 256: rank_hist_kernel WIDE as well
-      for (int cs = 0; cs < kNumWideBig; ++cs) {
-        ra.pos_list = ws.order; ra.class_meta = ws.meta;
-        NMOD_HIP(launch_class(kWideBigBase + cs, npos, cw_on));
-      }
-    }
-    if (wide_f32) {
-      bool any_wide = big_possible;
-      for (int cls = 0; cls < kNumClasses && !any_wide; ++cls) any_wide = wanted[cls] && wide_class(cls);
-      if (any_wide) { const int rr = launch_wide_redo(); if (rr != NMOD_OK) return rr; }
-    }
-    if (big_possible || deep_possible) {
-      // the only host round trip of this path: how many large (and deep) positions, how much scratch
-      int32_t head[8];
-      NMOD_HIP(hipMemcpyAsync(&head[0], ws.meta + kBigClass, 8, hipMemcpyDeviceToHost, stream));     // kBigClass, kBigHistClass
-      NMOD_HIP(hipMemcpyAsync(&head[2], ws.meta + kMetaBigTotal, 8, hipMemcpyDeviceToHost, stream));
-      if (deep_possible) {
-        NMOD_HIP(hipMemcpyAsync(&head[4], ws.meta + kDeepClass, 4, hipMemcpyDeviceToHost, stream));
-        NMOD_HIP(hipMemcpyAsync(&head[6], ws.meta + kMetaDeepTiles, 8, hipMemcpyDeviceToHost, stream));
-      } else {
-        head[4] = 0; head[6] = 0; head[7] = 0;
-      }
-      NMOD_HIP(hipStreamSynchronize(stream));
-      if (head[4] > 0) {
-        unsigned long long tiles;
-        memcpy(&tiles, &head[6], 8);
-        const int rc = enqueue_deep(prm, da, deep_scratch, deep_dtype, f64 ? (const void*)f64->d0 : sig0, f64 ? (const void*)f64->d1 : sig1,
-                                    off0, off1, ra.stride0, ra.stride1, ws, head[4], (int64_t)tiles, std::max(max0, max1), all, num_cus, stream);
-        if (rc != NMOD_OK) return rc;
-      }
-      const int64_t nbig = head[0], nbig_hist = head[1];
-      unsigned long long total;
-      memcpy(&total, &head[2], 8);
-      if (nbig > 0) {
-        NMOD_HIP(big_scratch.alloc((size_t)total * 4, stream, prm->device));
-        BigArgs bg;
-        memset(&bg, 0, sizeof(bg));
-        bg.sig0 = sig0; bg.sig1 = sig1; bg.off0 = off0; bg.off1 = off1; bg.stride0 = ra.stride0; bg.stride1 = ra.stride1;
-        bg.pos_list = ws.order; bg.class_meta = ws.meta; bg.big_class = kBigClass; bg.all = all ? 1 : 0;
-        bg.scratch = big_scratch.p;
-        bg.cursor = reinterpret_cast<unsigned long long*>(ws.meta + kMetaBigCursor);
-        bg.ks_num = ws.ks_num; bg.mwu_s = ws.mwu_s; bg.tie = ws.tie; bg.moments = ws.moments; bg.ks_d_ref = ws.ks_d_ref;
-        const unsigned blocks = (unsigned)std::min<int64_t>(nbig, (int64_t)num_cus * 4);   // 4 x 33 KB of LDS per CU
-        if (prm->dtype == NMOD_DTYPE_F32) hipLaunchKernelGGL(big_rank_kernel<0>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
-        else hipLaunchKernelGGL(big_rank_kernel<1>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
-        NMOD_HIP(hipGetLastError());
-        NMOD_HIP(big_scratch.release(stream));
-      }
-      if (nbig_hist > 0) {
-        BigArgs bg;
-        memset(&bg, 0, sizeof(bg));
-        bg.sig0 = sig0; bg.sig1 = sig1; bg.off0 = off0; bg.off1 = off1; bg.stride0 = ra.stride0; bg.stride1 = ra.stride1;
-        bg.pos_list = ws.order; bg.class_meta = ws.meta; bg.big_class = kBigHistClass; bg.all = 1;
-        bg.ks_num = ws.ks_num; bg.mwu_s = ws.mwu_s; bg.tie = ws.tie; bg.moments = ws.moments; bg.ks_d_ref = ws.ks_d_ref;
-        const unsigned blocks = (unsigned)std::min<int64_t>(nbig_hist, (int64_t)num_cus * 2);        // 80 KB of LDS per block
-        auto kfn = prm->dtype == NMOD_DTYPE_F32 ? big_hist_kernel<0> : big_hist_kernel<1>;
-        NMOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigHistLds));
-        hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBigThreads), kBigHistLds, stream, bg);
-        NMOD_HIP(hipGetLastError());
-      }
-    }
-  }
-
-  // ---- float64 samples behind the keys: redo the positions whose keys tied with 64-bit keys, moments from the samples
-  DevScratch redo_scratch;
-  if (f64) {
-    F64Args fx;
-    memset(&fx, 0, sizeof(fx));
-    fx.d0 = f64->d0; fx.d1 = f64->d1; fx.off0 = off0; fx.off1 = off1; fx.stride0 = ra.stride0; fx.stride1 = ra.stride1;
-    fx.npos = npos; fx.cls3 = f64->cls3; fx.tied = ws.tied; fx.cls = binned ? ws.cls : nullptr; fx.deep = deep_flag ? 1 : 0;
-    fx.order = ws.order; fx.meta = ws.meta; fx.moments = ws.moments;
-    const unsigned gb = (unsigned)std::min<int64_t>((npos + 255) / 256, 4096);
-    hipLaunchKernelGGL(f64_redo_list_kernel, dim3(gb), dim3(256), 0, stream, fx);
-    NMOD_HIP(hipGetLastError());
-    int32_t nredo = 0; unsigned long long total = 0;
-    NMOD_HIP(hipMemcpyAsync(&nredo, ws.meta + kMetaRedo, 4, hipMemcpyDeviceToHost, stream));
-    NMOD_HIP(hipMemcpyAsync(&total, ws.meta + kMetaRedoTotal, 8, hipMemcpyDeviceToHost, stream));
-    NMOD_HIP(hipStreamSynchronize(stream));
-    if (nredo > 0) {
-      NMOD_HIP(redo_scratch.alloc((size_t)total * 8, stream, prm->device));
-      BigArgs bg;
-      memset(&bg, 0, sizeof(bg));
-      bg.sig0 = f64->d0; bg.sig1 = f64->d1; bg.off0 = off0; bg.off1 = off1; bg.stride0 = ra.stride0; bg.stride1 = ra.stride1;
-      bg.pos_list = ws.order; bg.class_meta = ws.meta + kMetaRedo; bg.big_class = 0; bg.all = all ? 1 : 0;
-      bg.scratch = redo_scratch.p;
-      bg.cursor = reinterpret_cast<unsigned long long*>(ws.meta + kMetaRedoCursor);
-      bg.ks_num = ws.ks_num; bg.mwu_s = ws.mwu_s; bg.tie = ws.tie; bg.moments = ws.moments; bg.ks_d_ref = ws.ks_d_ref;
-      const unsigned blocks = (unsigned)std::min<int64_t>(nredo, (int64_t)num_cus * 4);
-      ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_RANK_STATS, stream);
-      hipLaunchKernelGGL(big_rank_kernel<2>, dim3(blocks), dim3(kBigThreads), 0, stream, bg);
-      NMOD_HIP(hipGetLastError());
-      NMOD_HIP(redo_scratch.release(stream));
-    }
-    if (all) {
-      const unsigned mb = (unsigned)std::min<int64_t>((npos + 3) / 4, (int64_t)num_cus * 16);
-      hipLaunchKernelGGL(f64_moments_kernel, dim3(mb), dim3(256), 0, stream, fx);
-      NMOD_HIP(hipGetLastError());
-    }
-  }
-
-  // ---- p-values
-  FinalizeArgs fa;
-  memset(&fa, 0, sizeof(fa));
-  fa.npos = npos; fa.off0 = off0; fa.off1 = off1; fa.stride0 = ra.stride0; fa.stride1 = ra.stride1;
-  fa.ks_num = ws.ks_num; fa.mwu_s = ws.mwu_s; fa.tie = ws.tie; fa.moments = ws.moments; fa.ks_d_ref = ra.ks_rational_d ? nullptr : ws.ks_d_ref;   // every K1 form writes ks_2samp's float form of D (unless the caller opted out)
-  fa.tests = tests; fa.want_mstd = prm->want_mstd; fa.out = *out;
-  // what K1 covered: exactly the limits the classifier used (the promised / measured maxima), in every mode —
-  // a position beyond them was skipped by K1 and must be flagged TOO_LARGE here, never read from the workspace
-  fa.max_n0 = std::max<int64_t>(std::min<int64_t>(max0, NMOD_MAX_RANKED), 1);
-  fa.max_n1 = std::max<int64_t>(std::min<int64_t>(max1, NMOD_MAX_RANKED), 1);
-  fa.min_cap = 0;
-  if (deep_possible) { fa.deep_lim0 = std::max<int64_t>(max0, 1); fa.deep_lim1 = std::max<int64_t>(max1, 1); }   // (K2 leaves them to the deep form)
-  if ((prm->flags & NMOD_FLAG_CHECK_FINITE) && prm->dtype != NMOD_DTYPE_I16_MILLI) {
-    // one pass over the samples: the float64 samples themselves where the keys are their float32 images
-    NonfiniteArgs na;
-    memset(&na, 0, sizeof(na));
-    na.sig0 = f64 ? (const void*)f64->d0 : sig0; na.sig1 = f64 ? (const void*)f64->d1 : sig1; na.f64 = f64 ? 1 : 0;
-    na.off0 = off0; na.off1 = off1; na.stride0 = ra.stride0; na.stride1 = ra.stride1; na.npos = npos;
-    na.lim0 = fa.max_n0; na.lim1 = fa.max_n1; na.flag = ws.nonfinite;
-    const unsigned nb_ = (unsigned)std::min<int64_t>((npos + 3) / 4, (int64_t)num_cus * 32);
-    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(nb_), dim3(256), 0, stream, na);
-    NMOD_HIP(hipGetLastError());
-    fa.nonfinite = ws.nonfinite;
-  }
-  if (want_comb) {                       // the combine needs the KS track even if the caller does not
-    if (!fa.out.ks_d) fa.out.ks_d = ws.tmp_ks_d;
-    if (!fa.out.ks_p) fa.out.ks_p = ws.tmp_ks_p;
-  }
+  Batch b{};
+  b.ws = carve(workspace, npos);
+  if (!workspace || workspace_bytes < b.ws.bytes) return NMOD_ERR_WORKSPACE;
+  NMOD_HIP(device_cus(prm->device, &b.num_cus));
+  b.prm = prm; b.stream = (hipStream_t)prm->stream; b.npos = npos; b.sig0 = sig0; b.sig1 = sig1; b.off0 = off0; b.off1 = off1;
+  b.stride0 = prm->stride0 > 0 ? prm->stride0 : 0; b.stride1 = prm->stride1 > 0 ? prm->stride1 : 0;
+  b.run_id = run_id; b.out = out; b.f64 = f64; b.want_comb = want_comb;
+  int rc = plan_batch(b);
+  if (rc == NMOD_OK && b.binned) rc = enqueue_bins(b);
+  if (rc != NMOD_OK) return rc;
   {
-    ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_FINALIZE, stream);
-    if (da.ndeep > 0) {                  // the deep positions' outputs (K2 skips them), then the slab goes back to the pool
-      const unsigned db = (unsigned)((da.ndeep + 255) / 256);
-      const int32_t rat = ra.ks_rational_d, chk = (prm->flags & NMOD_FLAG_CHECK_FINITE) ? 1 : 0;
-      if (deep_dtype == NMOD_DTYPE_I16_MILLI) hipLaunchKernelGGL(deep_finalize_kernel<1>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
-      else if (deep_dtype == NMOD_DTYPE_F64) hipLaunchKernelGGL(deep_finalize_kernel<2>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
-      else hipLaunchKernelGGL(deep_finalize_kernel<0>, dim3(db), dim3(256), 0, stream, da, fa, rat, chk);
-      NMOD_HIP(hipGetLastError());
-      NMOD_HIP(deep_scratch.release(stream));
-    }
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, stream, fa);
-    NMOD_HIP(hipGetLastError());
+    ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_RANK_STATS, b.stream);
+    rc = enqueue_k1(b);
+    if (rc == NMOD_OK) rc = enqueue_large(b);
   }
-  if (want_comb) {
-    int rc = launch_combine(prm, stream, npos, fa.out.ks_d, fa.out.ks_p, run_id, out->comb_st, out->comb_p);
-    if (rc != NMOD_OK) return rc;
-  }
-  {
-    DispatchRec& d = g_dispatch;
-    d.valid = true; d.host = false; d.device = prm->device; d.stream = stream; d.npos = npos; d.ks_only = all ? 0 : 1;
-    d.args.npos = npos; d.args.uniform_cls = st_uniform_cls; d.args.meta = ws.meta; d.args.work_meta = ws.work_meta;
-    d.args.gates = ws.work_meta + 2 * kClassStride; d.args.cnt_done = ws.cnt_done; d.args.cnt256_ran = st_cnt256; d.args.cw_ran = st_cw;
-    d.args.f64 = f64 ? 1 : 0; d.args.acc = ws.stats;
-  }
+  if (rc == NMOD_OK && f64) rc = enqueue_f64_fixups(b);
+  if (rc == NMOD_OK) rc = enqueue_outputs(b);
+  if (rc != NMOD_OK || !stats) return rc;
+  memset(stats, 0, sizeof(*stats));
+  stats->npos = npos; stats->uniform_cls = b.binned ? -1 : b.uniform_cls;
+  stats->meta = b.ws.meta; stats->work_meta = b.ws.work_meta; stats->gates = b.ws.work_meta + 2 * kClassStride; stats->cnt_done = b.ws.cnt_done;
+  stats->cnt256_ran = (b.wanted[kNumGeneralClasses + 2] && b.ra.cnt_gate) ? 1 : 0; stats->cw_ran = b.cw_ran ? 1 : 0;
+  stats->f64 = f64 ? 1 : 0; stats->acc = b.ws.stats;
   return NMOD_OK;
 }
 
@@ -896,7 +902,7 @@ struct DevBuf {
 // one-past-last element of each array in use, {b0, e0, b1, e1}, when the caller knows them (no round trip for the offsets).
 static int detect_f64(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
                       const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
-                      int64_t workspace_bytes, nmod_out* out, const int64_t* bounds = nullptr) {
+                      int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const int64_t* bounds = nullptr) {
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1 || !out) return NMOD_ERR_INVALID_ARG;
   if ((prm->stride0 <= 0 && !off0) || (prm->stride1 <= 0 && !off1)) return NMOD_ERR_INVALID_ARG;
@@ -928,13 +934,13 @@ static int detect_f64(const nmod_params* prm, int64_t npos, const void* sig0, co
   fx.stride0 = prm->stride0 > 0 ? prm->stride0 : 0; fx.stride1 = prm->stride1 > 0 ? prm->stride1 : 0;
   fx.npos = npos; fx.k0 = (float*)enc0.p - b0; fx.k1 = (float*)enc1.p - b1; fx.cls3 = src.cls3;
   int num_cus = 0;
-  NMOD_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
+  NMOD_HIP(device_cus(prm->device, &num_cus));
   const unsigned eb = (unsigned)std::min<int64_t>((npos + 3) / 4, (int64_t)num_cus * 16);
   hipLaunchKernelGGL(f64_encode_kernel, dim3(eb), dim3(256), 0, stream, fx);
   NMOD_HIP(hipGetLastError());
   nmod_params ep = *prm;
   ep.dtype = NMOD_DTYPE_F32;
-  int rc = detect_device(&ep, npos, fx.k0, off0, fx.k1, off1, run_id, workspace, workspace_bytes, out, &src);
+  int rc = detect_device(&ep, npos, fx.k0, off0, fx.k1, off1, run_id, workspace, workspace_bytes, out, stats, &src);
   // the key buffers go back to the pool in stream order
   const hipError_t r0 = enc0.release(stream), r1 = enc1.release(stream), r2 = d_cls3.release(stream);
   if (rc == NMOD_OK && (r0 != hipSuccess || r1 != hipSuccess || r2 != hipSuccess)) { g_last_hip = r0 != hipSuccess ? r0 : (r1 != hipSuccess ? r1 : r2); rc = NMOD_ERR_HIP; }
@@ -1153,14 +1159,25 @@ int64_t nmod_workspace_bytes(const nmod_params* prm, int64_t npos) {
 int nmod_detect_batch(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
                       const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
                       int64_t workspace_bytes, nmod_out* out) {
+  g_dispatch.valid = false;                      // (a failed call leaves no record: it could point into memory handed back)
   int rc = check_params(prm);
   if (rc != NMOD_OK) return rc;
   if (npos < 0) return NMOD_ERR_INVALID_ARG;
   if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
   NMOD_HIP(hipSetDevice(prm->device));
-  if (prm->memspace == NMOD_MEM_HOST) return detect_host_pipelined(prm, npos, sig0, off0, sig1, off1, run_id, out);
-  if (prm->dtype == NMOD_DTYPE_F64) return detect_f64(prm, npos, sig0, off0, sig1, off1, run_id, workspace, workspace_bytes, out);
-  return detect_device(prm, npos, sig0, off0, sig1, off1, run_id, workspace, workspace_bytes, out);
+  DispatchRec rec;                               // an empty batch: the totals of a host record, all zero
+  rec.host = true; rec.npos = npos;
+  if (prm->memspace == NMOD_MEM_HOST) {
+    rc = detect_host_pipelined(prm, npos, sig0, off0, sig1, off1, run_id, out, rec.host_totals);
+  } else {
+    rc = prm->dtype == NMOD_DTYPE_F64 ? detect_f64(prm, npos, sig0, off0, sig1, off1, run_id, workspace, workspace_bytes, out, &rec.args)
+                                      : detect_device(prm, npos, sig0, off0, sig1, off1, run_id, workspace, workspace_bytes, out, &rec.args);
+    if (npos > 0) { rec.host = false; rec.device = prm->device; rec.stream = (hipStream_t)prm->stream; }
+  }
+  if (rc != NMOD_OK) return rc;
+  rec.valid = true;
+  g_dispatch = rec;
+  return NMOD_OK;
 }
 
 int nmod_combine_track(const nmod_params* prm, int64_t npos, const double* ks_d, const double* ks_p,
@@ -1256,56 +1273,34 @@ int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char*
   int rc = check_params(prm);
   if (rc != NMOD_OK) return rc;
   if (!buf || buflen < 8 || n0 <= 0 || n1 <= 0) return NMOD_ERR_INVALID_ARG;
-  if (std::max(n0, n1) > NMOD_MAX_RANKED) {
-    // NMOD_FLAG_DEEP: the multi-workgroup form (deep_rank.hpp; float64 samples as 64-bit keys) up to NMOD_MAX_DEEP
-    if (!(prm->flags & NMOD_FLAG_DEEP) || std::max(n0, n1) > NMOD_MAX_DEEP) return NMOD_ERR_TOO_LARGE;
-    snprintf(buf, buflen, "deep_rank_kernel<%s>", prm->dtype == NMOD_DTYPE_I16_MILLI ? "i16" : (prm->dtype == NMOD_DTYPE_F64 ? "f64" : "f32"));
-    return NMOD_OK;
-  }
   const bool want_comb = prm->method != NMOD_METHOD_KS;
-  int tests = prm->tests | (want_comb ? NMOD_TEST_KS : 0);
+  const int tests = prm->tests | (want_comb ? NMOD_TEST_KS : 0);
   const bool all = (tests & (NMOD_TEST_MWU | NMOD_TEST_WELCH)) != 0 || prm->want_mstd;
-  // (NMOD_DTYPE_F64 runs on per-position float32 keys: the float32 instances)
+  // the classifier of the device (NMOD_DTYPE_F64: the narrower dtype is a property of the data), under the format's limits
+  const bool deep = (prm->flags & NMOD_FLAG_DEEP) != 0;
+  const int64_t cap = deep ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;
+  const int cls = classify_position(n0, n1, ClassRule{cap, cap, all ? 0 : 1, deep ? 1 : 0});
+  if (cls == 255) return NMOD_ERR_TOO_LARGE;
+  // (NMOD_DTYPE_F64 runs on per-position float32 keys: the float32 instances; the deep form sorts the samples as 64-bit keys)
   const char* dt = prm->dtype == NMOD_DTYPE_I16_MILLI ? "i16" : "f32";
-  const int c0 = size_class_of(n0), c1 = size_class_of(n1);
-  // the same decisions classify_kernel / detect_device take (NMOD_DTYPE_F64: the narrower dtype is a property of the data)
-  const bool big = all ? (c0 >= kNumSizeClasses || c1 >= kNumSizeClasses) : (std::min(c0, c1) >= kNumSizeClasses);
-  // (all tests, smaller group <= 1 024, larger <= 4 095, not the classes of eight or four positions per wave: the counting form for
-  // any coverage when the device-side probe finds the class event-like — a property of the data; the sorting form takes the rest)
-  const char* kd = prm->dtype == NMOD_DTYPE_F64 ? "f32 keys" : dt;
-  if (big && all && std::min(n0, n1) <= 256 && std::max(n0, n1) <= kWideBigMaxQ) {
-    snprintf(buf, buflen, "rank_count_wide_kernel<%s> (event-like rows) | rank_hist_kernel<%d,64,%s,wide>", kd, 1 << std::min(c0, c1), dt); return NMOD_OK;
+  const ClassForms f = class_forms(cls);
+  char form[64];
+  if (f.sort == kSortDeep) snprintf(form, sizeof(form), "deep_rank_kernel<%s>", prm->dtype == NMOD_DTYPE_F64 ? "f64" : dt);
+  else if (f.sort == kSortBig) snprintf(form, sizeof(form), cls == kBigHistClass ? "big_hist_kernel<%s>" : "big_rank_kernel<%s>", dt);
+  else if (f.sort == kSortHistWide) snprintf(form, sizeof(form), "rank_hist_kernel<%d,64,%s,wide>", 1 << wide_class_of_s(cls), dt);
+  else if (f.sort == kSortPair) snprintf(form, sizeof(form), "rank_pair_kernel<%d,%d,%s>", 1 << (cls / kNumSizeClasses), 1 << (cls % kNumSizeClasses), dt);
+  else {
+    const bool ks = f.sort == kSortKs;
+    const int c = ks ? cls - kKsClassBase : cls - kNumGeneralClasses;
+    const int LG = ks ? ksonly_lanes_per_group(c) : packed_lanes_per_group(c), R = (64 << c) / LG;
+    snprintf(form, sizeof(form), ks ? "ks_rank_kernel<%d,%d,%s>" : "rank_hist_kernel<%d,%d,%s>", R, LG, dt);
   }
-  if (big && all && std::min(n0, n1) <= kBigHistMaxS && std::max(n0, n1) <= kBigHistMaxQ) { snprintf(buf, buflen, "big_hist_kernel<%s>", dt); return NMOD_OK; }
-  if (big) { snprintf(buf, buflen, "big_rank_kernel<%s>", dt); return NMOD_OK; }
-  if (!all) {
-    const int cs = std::min(c0, c1);
-    const int LG = ksonly_lanes_per_group(cs), R = (64 << cs) / LG;
-    // (the larger group of at least kCwKsMinQ samples, the smaller one of at most 1 024: the counting form when the probe finds the class event-like)
-    if (cs == 5 && std::max(n0, n1) <= 4095)
-      snprintf(buf, buflen, "rank_count_value_kernel<%s,ks> (event-like rows) | ks_rank_kernel<%d,%d,%s>", prm->dtype == NMOD_DTYPE_F64 ? "f32 keys" : dt, R, LG, dt);
-    else if (cs <= 4 && std::max(n0, n1) >= kCwKsMinQ && std::max(n0, n1) <= 4095)
-      snprintf(buf, buflen, "rank_count_wide_kernel<%s,ks> (event-like rows) | ks_rank_kernel<%d,%d,%s>", prm->dtype == NMOD_DTYPE_F64 ? "f32 keys" : dt, R, LG, dt);
-    else snprintf(buf, buflen, "ks_rank_kernel<%d,%d,%s>", R, LG, dt);
-    return NMOD_OK;
-  }
-  const int cls = launch_class_of(c0, c1);
-  if (cls >= kNumGeneralClasses) {
-    const int cm = cls - kNumGeneralClasses;
-    const int LG = packed_lanes_per_group(cm), R = (64 << cm) / LG;
-    // capacity-256 positions: the counting form when the device-side probe finds the batch event-like (a property of the data)
-    if (cm == 2 && prm->dtype != NMOD_DTYPE_F64) snprintf(buf, buflen, "rank_count_kernel<%s> (event-like rows) | rank_hist_kernel<%d,%d,%s>", dt, R, LG, dt);
-    else if (cm == 2) snprintf(buf, buflen, "rank_count_kernel<f32 keys> (event-like rows) | rank_hist_kernel<%d,%d,%s>", R, LG, dt);
-    else if (count_wide_rs_index(cls) >= 0) snprintf(buf, buflen, "rank_count_wide_kernel<%s> (event-like rows) | rank_hist_kernel<%d,%d,%s>", kd, R, LG, dt);
-    else snprintf(buf, buflen, "rank_hist_kernel<%d,%d,%s>", R, LG, dt);
-  } else if (wide_class(cls)) {
-    if (count_wide_rs_index(cls) >= 0) snprintf(buf, buflen, "rank_count_wide_kernel<%s> (event-like rows) | rank_hist_kernel<%d,64,%s,wide>", kd, 1 << std::min(c0, c1), dt);
-    else snprintf(buf, buflen, "rank_hist_kernel<%d,64,%s,wide>", 1 << std::min(c0, c1), dt);
-  } else {
-    if (count_wide_rs_index(cls) == 5) snprintf(buf, buflen, "rank_count_value_kernel<%s> (event-like rows) | rank_pair_kernel<%d,%d,%s>", kd, 1 << c0, 1 << c1, dt);
-    else if (count_wide_rs_index(cls) >= 0) snprintf(buf, buflen, "rank_count_wide_kernel<%s> (event-like rows) | rank_pair_kernel<%d,%d,%s>", kd, 1 << c0, 1 << c1, dt);
-    else snprintf(buf, buflen, "rank_pair_kernel<%d,%d,%s>", 1 << c0, 1 << c1, dt);
-  }
+  // the counting form first when the device-side probe finds the class (the batch, for the 256-capacity class) event-like — a
+  // property of the data; in KS-only mode for a larger group of kCwKsMinQ .. kCwMaxQ samples
+  const int64_t q = std::max(n0, n1);
+  if (f.count == kCountNone || (!all && (q < kCwKsMinQ || q > kCwMaxQ))) { snprintf(buf, buflen, "%s", form); return NMOD_OK; }
+  static const char* const counting[] = {"", "rank_count_kernel", "rank_count_wide_kernel", "rank_count_value_kernel"};
+  snprintf(buf, buflen, "%s<%s%s> (event-like rows) | %s", counting[f.count], prm->dtype == NMOD_DTYPE_F64 ? "f32 keys" : dt, all ? "" : ",ks", form);
   return NMOD_OK;
 }
 
@@ -1330,22 +1325,20 @@ int nmod_last_host_stats(nmod_host_stats* st) {
 static void assemble_dispatch_stats(const unsigned long long* raw, int64_t npos, nmod_dispatch_stats* st) {
   memset(st, 0, sizeof(*st));
   st->positions = npos;
-  constexpr int c256 = kNumGeneralClasses + 2;
+  // the counter of each sorting form (K1Sort order)
+  static int64_t nmod_dispatch_stats::* const sorting[] = {&nmod_dispatch_stats::ks_rank, &nmod_dispatch_stats::rank_hist,
+      &nmod_dispatch_stats::rank_hist_wide, &nmod_dispatch_stats::rank_pair, &nmod_dispatch_stats::big, &nmod_dispatch_stats::deep};
   int64_t placed = 0;
   for (int c = 0; c < kNumPairs; ++c) {
     const int64_t n = (int64_t)raw[kStatsClass + c];
     if (n == 0) continue;
     placed += n;
-    int64_t* sorting = c == kDeepClass ? &st->deep
-                     : c >= kWideBigBase ? &st->rank_hist_wide
-                     : (c == kBigClass || c == kBigHistClass) ? &st->big
-                     : c >= kKsClassBase ? &st->ks_rank
-                     : c >= kNumGeneralClasses ? &st->rank_hist
-                     : wide_class(c) ? &st->rank_hist_wide : &st->rank_pair;
+    const ClassForms f = class_forms(c);
+    const bool c256 = f.count == kCount256;
     const int64_t tried = (int64_t)raw[kStatsTried + c];
-    const int64_t counted = c == c256 ? (int64_t)raw[1] : tried - (int64_t)raw[kStatsLeft + c];
-    if (c == c256) st->rank_count += counted; else st->rank_count_wide += counted;
-    *sorting += n - counted;
+    const int64_t counted = c256 ? (int64_t)raw[1] : tried - (int64_t)raw[kStatsLeft + c];
+    if (c256) st->rank_count += counted; else st->rank_count_wide += counted;
+    st->*sorting[f.sort] += n - counted;
     st->count_tried += tried;
     st->count_rejected += tried - counted;
   }
@@ -1376,10 +1369,10 @@ const char* nmod_build_info(void) {
     snprintf(head, sizeof(head), "arch=gfx950 abi=%d hip=%d.%d", NMOD_ABI_VERSION, HIP_VERSION_MAJOR, HIP_VERSION_MINOR);
     info = head;
     info += " | abi_tu: " NMOD_BUILD_FLAGS;
-    info += std::string(" | k1_f32_ks: ") + rank_stats_build_flags_d0_a0();
-    info += std::string(" | k1_f32_all: ") + rank_stats_build_flags_d0_a1();
-    info += std::string(" | k1_i16_ks: ") + rank_stats_build_flags_d1_a0();
-    info += std::string(" | k1_i16_all: ") + rank_stats_build_flags_d1_a1();
+    info += std::string(" | k1_f32_ks: ") + k1_d0_a0().build_flags;
+    info += std::string(" | k1_f32_all: ") + k1_d0_a1().build_flags;
+    info += std::string(" | k1_i16_ks: ") + k1_d1_a0().build_flags;
+    info += std::string(" | k1_i16_all: ") + k1_d1_a1().build_flags;
   });
   return info.c_str();
 }
@@ -1399,7 +1392,7 @@ int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, 
   const int esz = prm->dtype == NMOD_DTYPE_F32 ? 4 : (prm->dtype == NMOD_DTYPE_F64 ? 8 : 2);
   const int kth = (int)((double)iters * quantile);
   int num_cus = 0;
-  NMOD_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
+  NMOD_HIP(device_cus(prm->device, &num_cus));
   const int64_t max_elements = env_i64("NMOD_DOWNSAMPLE_ELEMENTS", (int64_t)1 << 27);
   const int64_t group_cap = (prm->flags & NMOD_FLAG_DEEP) ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;   // (NMOD_FLAG_DEEP: deep groups and resamples too)
   std::vector<int32_t> rn[2], rsz[2];
@@ -1471,9 +1464,9 @@ int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, 
     // the 100 resamples of every flagged position through the same KS kernel as everything else
     if (prm->dtype == NMOD_DTYPE_F64) {
       const int64_t bounds[4] = {0, vat[0], 0, vat[1]};
-      rc = detect_f64(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout, bounds);
+      rc = detect_f64(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout, nullptr, bounds);
     } else {
-      rc = detect_device(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout);
+      rc = detect_device(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout, nullptr);
     }
     if (rc != NMOD_OK) { hipStreamSynchronize(stream); return rc; }
     hipLaunchKernelGGL(select_quantile_kernel, dim3((unsigned)std::min<int64_t>((nrows + 3) / 4, (int64_t)num_cus * 32)), dim3(256), 0, stream,

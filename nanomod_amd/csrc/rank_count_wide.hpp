@@ -41,7 +41,6 @@
 
 namespace nmod {
 
-constexpr int kCwMaxQ = 4095;                                  // Q's half of a word, and |A nQ - B nS| through 16-bit dot products
 constexpr int kCwWindow = 2048;                                // values the table covers: 64 lane blocks of 32 entries
 constexpr int kCwTail = 64;                                    // tail samples (outside the window) a position may have: one per lane
 constexpr int kCwTableWords = 64 * 36 + 8;                     // a lane's block: 4 pad words + up to 32 entries; + the dump entry

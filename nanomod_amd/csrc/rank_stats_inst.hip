@@ -93,18 +93,32 @@ KernelFn pick_ks(int cs, bool flags) {
   }
 }
 #endif
-}  // namespace
 
-#define NMOD_CAT2(a, b) a##b
-#define NMOD_CAT(a, b) NMOD_CAT2(a, b)
-#define NMOD_LAUNCH_NAME NMOD_CAT(NMOD_CAT(launch_rank_stats_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
-#define NMOD_FLAGS_NAME NMOD_CAT(NMOD_CAT(rank_stats_build_flags_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
+// The dynamic-LDS attribute (lds_limit, else lds) and the occupancy of a kernel at `lds`, looked up once per device and kept in
+// `slot` (atomics: concurrent first launches both run the queries and store the same number); slot null: looked up every time
+hipError_t blocks_per_cu(std::atomic<int>* slot, const void* fn, size_t lds, int* per_cu, size_t lds_limit = 0) {
+  int pc = slot ? slot->load(std::memory_order_relaxed) : 0;
+  if (pc <= 0) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_limit ? lds_limit : lds));
+    if (e != hipSuccess) return e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, fn, 64 * kWavesPerBlock, lds);
+    if (e != hipSuccess) return e;
+    if (pc < 1) return hipErrorLaunchOutOfResources;     // (never launch a block that cannot get its LDS: its table walks would not end)
+    if (slot) slot->store(pc, std::memory_order_relaxed);
+  }
+  *per_cu = pc;
+  return hipSuccess;
+}
+constexpr int kCacheDevices = 64;
+int cache_device() {                                     // index of the per-device caches, -1: not cacheable
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kCacheDevices ? dev : -1;
+}
+int64_t grid_of(int64_t work_items, int num_cus, int per_cu) {
+  return std::max<int64_t>(1, std::min<int64_t>((work_items + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)num_cus * per_cu));
+}
 
-// the experiment macros THIS translation unit's kernels were compiled with (nmod_build_info)
-const char* NMOD_FLAGS_NAME() { return NMOD_BUILD_FLAGS; }
-
-hipError_t NMOD_LAUNCH_NAME(int cls, int num_cus, int64_t work_items, hipStream_t stream,
-                            const RankStatsArgs& args) {
+hipError_t launch_rank_stats(int cls, int num_cus, int64_t work_items, hipStream_t stream, const RankStatsArgs& args) {
   const bool ks = cls >= kKsClassBase && cls < kNumClasses;
   const bool packed = cls >= kNumGeneralClasses && cls < kKsClassBase;
   KernelFn fn = nullptr;
@@ -125,31 +139,19 @@ hipError_t NMOD_LAUNCH_NAME(int cls, int num_cus, int64_t work_items, hipStream_
     const int pw = ks ? ksonly_positions_per_wave(cls - kKsClassBase) : packed_positions_per_wave(cls - kNumGeneralClasses);
     work_items = (work_items + pw - 1) / pw;
   }
-  // the dynamic-LDS attribute and the occupancy of a kernel are looked up once per (device, class), not on every launch
-  // (atomics: concurrent first launches of a class both run the queries and store the same number)
-  static std::atomic<int> per_cu_cache[64][2 * kClassStride];     // [class] and [kClassStride + class] for the FLAGS instances
-  int dev = 0;
-  const bool cacheable = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+  static std::atomic<int> per_cu_cache[kCacheDevices][2 * kClassStride];     // [class] and [kClassStride + class] for the FLAGS instances
+  const int dev = cache_device();
 #if NMOD_INST_ALL
   const int slot_id = cls + (counting ? kClassStride : 0);
+  // (one WIDE instance serves every class of the larger group: its limit is that of the largest)
+  const size_t lds_limit = wide ? rank_stats_lds_bytes(kWideBigBase + wide_class_of_s(cls), ALL, DT) : lds;
 #else
   const int slot_id = cls + ((ks && args.tied) ? kClassStride : 0);
+  const size_t lds_limit = lds;
 #endif
-  int per_cu = cacheable ? per_cu_cache[dev][slot_id].load(std::memory_order_relaxed) : 0;
-  if (per_cu <= 0) {
-    // (one WIDE instance serves every class of the larger group: its limit is that of the largest)
-    size_t lds_limit = lds;
-#if NMOD_INST_ALL
-    if (wide) lds_limit = rank_stats_lds_bytes(kWideBigBase + wide_class_of_s(cls), ALL, DT);
-#endif
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit);
-    if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * kWavesPerBlock, lds);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) return hipErrorLaunchOutOfResources;     // (never launch a block that cannot get its LDS: its table walks would not end)
-    if (cacheable) per_cu_cache[dev][slot_id].store(per_cu, std::memory_order_relaxed);
-  }
+  int per_cu = 0;
+  hipError_t e = blocks_per_cu(dev >= 0 ? &per_cu_cache[dev][slot_id] : nullptr, reinterpret_cast<const void*>(fn), lds, &per_cu, lds_limit);
+  if (e != hipSuccess) return e;
 #if NMOD_INST_ALL
   if (counting) {
     // probe (one block: is the batch event-like?) -> rank_count_kernel (exits at once when it is not) -> the AFTER instance below
@@ -161,48 +163,35 @@ hipError_t NMOD_LAUNCH_NAME(int cls, int num_cus, int64_t work_items, hipStream_
     const bool int_keys = args.tied != nullptr;
     if (int_keys) hipLaunchKernelGGL(cnt_probe_kernel<2>, dim3(1), dim3(1024), 0, stream, pa);
     else hipLaunchKernelGGL(cnt_probe_kernel<0>, dim3(1), dim3(1024), 0, stream, pa);
-    static std::atomic<int> cnt_per_cu[64][2];
+    static std::atomic<int> cnt_per_cu[kCacheDevices][2];
     KernelFn cfn = int_keys ? (KernelFn)rank_count_kernel<2> : (KernelFn)rank_count_kernel<0>;
-    std::atomic<int>& cpc_slot = cnt_per_cu[cacheable ? dev : 0][int_keys ? 1 : 0];
+    std::atomic<int>* cslot = dev >= 0 ? &cnt_per_cu[dev][int_keys ? 1 : 0] : nullptr;
 #else
     hipLaunchKernelGGL(cnt_probe_kernel<DT>, dim3(1), dim3(1024), 0, stream, pa);
-    static std::atomic<int> cnt_per_cu[64][1];
+    static std::atomic<int> cnt_per_cu[kCacheDevices][1];
     KernelFn cfn = rank_count_kernel<DT>;
-    std::atomic<int>& cpc_slot = cnt_per_cu[cacheable ? dev : 0][0];
+    std::atomic<int>* cslot = dev >= 0 ? &cnt_per_cu[dev][0] : nullptr;
 #endif
     const size_t clds = rank_count_lds_bytes();
-    int cpc = cacheable ? cpc_slot.load(std::memory_order_relaxed) : 0;
-    if (cpc <= 0) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
-      if (e != hipSuccess) return e;
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&cpc, cfn, 64 * kWavesPerBlock, clds);
-      if (e != hipSuccess) return e;
-      if (cpc < 1) return hipErrorLaunchOutOfResources;
-      if (cacheable) cpc_slot.store(cpc, std::memory_order_relaxed);
-    }
-    int64_t cblocks = std::min<int64_t>((work_items + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)num_cus * cpc);
-    if (cblocks < 1) cblocks = 1;
-    hipLaunchKernelGGL(cfn, dim3((unsigned)cblocks), dim3(64 * kWavesPerBlock), clds, stream, args);
-    const hipError_t e = hipGetLastError();
+    int cpc = 0;
+    e = blocks_per_cu(cslot, reinterpret_cast<const void*>(cfn), clds, &cpc);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cfn, dim3((unsigned)grid_of(work_items, num_cus, cpc)), dim3(64 * kWavesPerBlock), clds, stream, args);
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
 #endif
-  int64_t blocks = (work_items + kWavesPerBlock - 1) / kWavesPerBlock;
-  int64_t cap = (int64_t)num_cus * per_cu;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  const int64_t blocks = grid_of(work_items, num_cus, per_cu);
 #if NMOD_INST_ALL
   if (counting) {
     // gate clear: the plain instance over the whole list; gate set: the AFTER instance over what the counting form left
     RankStatsArgs a2 = args;
     a2.cnt_mode = 1;
     KernelFn plain = pick_packed(cls - kNumGeneralClasses, false);
-    static std::atomic<int> plain_ready[64];
-    if (!cacheable || plain_ready[dev].load(std::memory_order_relaxed) == 0) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(plain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      if (cacheable) plain_ready[dev].store(1, std::memory_order_relaxed);
-    }
+    static std::atomic<int> plain_per_cu[kCacheDevices];
+    int ppc = 0;                                         // (the plain instance runs on the AFTER instance's grid)
+    e = blocks_per_cu(dev >= 0 ? &plain_per_cu[dev] : nullptr, reinterpret_cast<const void*>(plain), lds, &ppc);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(plain, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), lds, stream, a2);
     a2.cnt_mode = 2;
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), lds, stream, a2);
@@ -213,13 +202,7 @@ hipError_t NMOD_LAUNCH_NAME(int cls, int num_cus, int64_t work_items, hipStream_
   return hipGetLastError();
 }
 
-}  // namespace nmod
-
-#define NMOD_CW_PREP_NAME NMOD_CAT(NMOD_CAT(launch_count_wide_prepare_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
-#define NMOD_CW_RUN_NAME NMOD_CAT(NMOD_CAT(launch_count_wide_run_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
-namespace nmod {
-
-hipError_t NMOD_CW_PREP_NAME(const int* classes, int nclasses, hipStream_t stream, const RankStatsArgs& a, const CountWideWs& w) {
+hipError_t count_wide_prepare(const int* classes, int nclasses, hipStream_t stream, const RankStatsArgs& a, const CountWideWs& w) {
   if (nclasses <= 0) return hipSuccess;
   if (nclasses > kClassStride) return hipErrorInvalidValue;        // (cls[] / max_s[] / the segs area hold one entry per class)
   CntWideProbeArgs pa;
@@ -237,58 +220,45 @@ hipError_t NMOD_CW_PREP_NAME(const int* classes, int nclasses, hipStream_t strea
   return hipGetLastError();
 }
 
-hipError_t NMOD_CW_RUN_NAME(int num_cus, int64_t work_items, hipStream_t stream, const RankStatsArgs& a, const CountWideWs& w, bool value_class) {
+hipError_t count_wide_run(int num_cus, int64_t work_items, hipStream_t stream, const RankStatsArgs& a, const CountWideWs& w, bool value_class) {
   typedef void (*CwFn)(CntWideArgs);
 #if NMOD_INST_DTYPE == 0
   const bool int_keys = a.tied != nullptr;
   CwFn fn = int_keys ? (CwFn)rank_count_wide_kernel<2, NMOD_INST_ALL == 0> : (CwFn)rank_count_wide_kernel<0, NMOD_INST_ALL == 0>;
+  CwFn vfn = int_keys ? (CwFn)rank_count_value_kernel<2, NMOD_INST_ALL == 0> : (CwFn)rank_count_value_kernel<0, NMOD_INST_ALL == 0>;
   const int slot = int_keys ? 1 : 0;
 #else
   CwFn fn = (CwFn)rank_count_wide_kernel<1, NMOD_INST_ALL == 0>;
+  CwFn vfn = (CwFn)rank_count_value_kernel<1, NMOD_INST_ALL == 0>;
   const int slot = 0;
 #endif
-  static std::atomic<int> per_cu[64][2];
-  int dev = 0;
-  const bool cacheable = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+  static std::atomic<int> per_cu[kCacheDevices][2], vper_cu[kCacheDevices][2];
+  const int dev = cache_device();
   const size_t lds = rank_count_wide_lds_bytes();
-  int pc = cacheable ? per_cu[dev][slot].load(std::memory_order_relaxed) : 0;
-  if (pc <= 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, fn, 64 * kWavesPerBlock, lds);
-    if (e != hipSuccess) return e;
-    if (pc < 1) return hipErrorLaunchOutOfResources;
-    if (cacheable) per_cu[dev][slot].store(pc, std::memory_order_relaxed);
-  }
+  int pc = 0;
+  hipError_t e = blocks_per_cu(dev >= 0 ? &per_cu[dev][slot] : nullptr, reinterpret_cast<const void*>(fn), lds, &pc);
+  if (e != hipSuccess) return e;
   CntWideArgs ca;
   ca.rs = a; ca.gates = w.gates; ca.segs = w.gates + kClassStride; ca.work_list = w.work_list; ca.work_meta = w.work_meta;
-  int64_t blocks = std::min<int64_t>((work_items + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)num_cus * pc);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), lds, stream, ca);
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid_of(work_items, num_cus, pc)), dim3(64 * kWavesPerBlock), lds, stream, ca);
   if (value_class) {
     // the class whose groups both hold more than 1 024 samples: the value-domain form (rank_count_value.hpp), a launch of its own
-#if NMOD_INST_DTYPE == 0
-    CwFn vfn = int_keys ? (CwFn)rank_count_value_kernel<2, NMOD_INST_ALL == 0> : (CwFn)rank_count_value_kernel<0, NMOD_INST_ALL == 0>;
-#else
-    CwFn vfn = (CwFn)rank_count_value_kernel<1, NMOD_INST_ALL == 0>;
-#endif
-    static std::atomic<int> vper_cu[64][2];
     const size_t vlds = rank_count_value_lds_bytes();
-    int vpc = cacheable ? vper_cu[dev][slot].load(std::memory_order_relaxed) : 0;
-    if (vpc <= 0) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(vfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds);
-      if (e != hipSuccess) return e;
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&vpc, vfn, 64 * kWavesPerBlock, vlds);
-      if (e != hipSuccess) return e;
-      if (vpc < 1) return hipErrorLaunchOutOfResources;
-      if (cacheable) vper_cu[dev][slot].store(vpc, std::memory_order_relaxed);
-    }
-    int64_t vblocks = std::min<int64_t>((work_items + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)num_cus * vpc);
-    if (vblocks < 1) vblocks = 1;
-    hipLaunchKernelGGL(vfn, dim3((unsigned)vblocks), dim3(64 * kWavesPerBlock), vlds, stream, ca);
+    int vpc = 0;
+    e = blocks_per_cu(dev >= 0 ? &vper_cu[dev][slot] : nullptr, reinterpret_cast<const void*>(vfn), vlds, &vpc);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vfn, dim3((unsigned)grid_of(work_items, num_cus, vpc)), dim3(64 * kWavesPerBlock), vlds, stream, ca);
   }
   return hipGetLastError();
 }
+}  // namespace
+
+#define NMOD_CAT2(a, b) a##b
+#define NMOD_CAT(a, b) NMOD_CAT2(a, b)
+#define NMOD_K1_NAME NMOD_CAT(NMOD_CAT(k1_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
+const K1Launcher& NMOD_K1_NAME() {
+  static const K1Launcher k1 = {launch_rank_stats, count_wide_prepare, count_wide_run, NMOD_BUILD_FLAGS};
+  return k1;
+}
 
 }  // namespace nmod
-

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/nanomod_hip.h"
 
 namespace nmod {
 
@@ -28,6 +29,8 @@ constexpr int kBigHistClass = kNumClasses + 1;     // 48: all tests, big_hist_ke
 constexpr int kWideBigBase = kNumClasses + 2;      // 49 + cs: all tests, smaller group in class cs <= 2 (<= 256), larger 2 049 .. 4 096:
 constexpr int kNumWideBig = 3;                     //          rank_hist_kernel WIDE with two hash passes (rank_hist.hpp)
 constexpr int kWideBigMaxQ = 4096;
+constexpr int kBigHistMaxS = 1024;              // kBigHistClass: keys of S in LDS, a power of two (the sort pads to one); two blocks per CU
+constexpr int kBigHistMaxQ = 4096;              //                samples of Q: half the slots of the hash table (big_rank.hpp)
 constexpr int kDeepClass = kWideBigBase + kNumWideBig;                  // 52: NMOD_FLAG_DEEP, a group beyond NMOD_MAX_RANKED (deep_rank.hpp)
 constexpr int kNumPairs = kDeepClass + 1;                               // 53 class lists
 
@@ -40,6 +43,27 @@ __host__ __device__ inline int launch_class_of(int c0, int c1) {
   int cm = c0 > c1 ? c0 : c1, cl = c0 > c1 ? c1 : c0;
   if (cm <= 4 && cl >= cm - 1) return kNumGeneralClasses + cm;
   return c0 * kNumSizeClasses + c1;
+}
+// The batch's rule of the classifier: the group limits K1 covers (the promised or measured maxima), KS-only mode (the smaller
+// group sorted) or all tests (both), NMOD_FLAG_DEEP
+struct ClassRule { int64_t lim0, lim1; int32_t ks_only, deep; };
+__host__ __device__ inline int small_class_of(int c0, int c1, bool ks_only) {   // a position within the wave-resident kernels
+  return ks_only ? kKsClassBase + (c0 < c1 ? c0 : c1) : launch_class_of(c0, c1);
+}
+// The launch class of a position with n0 / n1 samples: classify_kernel, the uniform path of detect_device and
+// nmod_describe_dispatch all take it from here.  255: no K1 form (an empty group, or one beyond the rule's limits: TOO_LARGE)
+__host__ __device__ inline int classify_position(int64_t n0, int64_t n1, const ClassRule& r) {
+  const int c0 = size_class_of(n0), c1 = size_class_of(n1), cs = c0 < c1 ? c0 : c1;
+  const int64_t s = n0 < n1 ? n0 : n1, q = n0 < n1 ? n1 : n0;
+  const bool beyond = q > NMOD_MAX_RANKED;
+  if (n0 <= 0 || n1 <= 0 || n0 > r.lim0 || n1 > r.lim1 || (beyond && !r.deep)) return 255;
+  if (beyond) return kDeepClass;                                    // the multi-workgroup form (deep_rank.hpp)
+  // beyond the wave-resident kernels: KS-only sorts the smaller group only, all-tests mode sorts both
+  const bool big = r.ks_only ? cs >= kNumSizeClasses : (c0 >= kNumSizeClasses || c1 >= kNumSizeClasses);
+  if (!big) return small_class_of(c0, c1, r.ks_only);
+  if (!r.ks_only && s <= 256 && q <= kWideBigMaxQ) return kWideBigBase + cs;
+  if (!r.ks_only && s <= kBigHistMaxS && q <= kBigHistMaxQ) return kBigHistClass;
+  return kBigClass;
 }
 // general classes served by the WIDE form of rank_hist_kernel: the smaller group fits 256 sorted samples
 inline bool wide_class(int cls) {
@@ -130,27 +154,37 @@ __host__ __device__ inline int count_wide_rs_index(int cls) {
 // KS-only mode: a class holds every position whose SMALLER group has the class's capacity; the form takes those whose larger group has at
 // least this many samples (200 v 200 and below stay with ks_rank_kernel, four or eight positions per wave)
 constexpr int kCwKsMinQ = 320;
+constexpr int kCwMaxQ = 4095;                   // Q's half of a word, and |A nQ - B nS| through 16-bit dot products (rank_count_wide.hpp)
+// What serves a class: the sorting form (the counter of nmod_dispatch_stats it adds to) and the counting form tried first, if any
+enum K1Sort { kSortKs, kSortHist, kSortHistWide, kSortPair, kSortBig, kSortDeep };
+enum K1Count { kCountNone, kCount256, kCountWide, kCountValue };
+struct ClassForms { K1Sort sort; K1Count count; };
+inline ClassForms class_forms(int cls) {
+  ClassForms f;
+  f.sort = cls == kDeepClass ? kSortDeep : cls >= kWideBigBase ? kSortHistWide : cls >= kBigClass ? kSortBig : cls >= kKsClassBase ? kSortKs
+         : cls >= kNumGeneralClasses ? kSortHist : wide_class(cls) ? kSortHistWide : kSortPair;
+  // the 256-capacity packed class has its own counting form (rank_count.hpp); the rest through count_wide_rs_index
+  const int rs = count_wide_rs_index(cls);
+  f.count = cls == kNumGeneralClasses + 2 ? kCount256 : rs == 5 ? kCountValue : rs >= 0 ? kCountWide : kCountNone;
+  return f;
+}
+// the count-wide forms of the class lists (not the 256-capacity one), tried per class when the batch has them on
+inline bool count_wide_class(int cls) { return class_forms(cls).count >= kCountWide; }
 struct CountWideWs { int32_t* gates; int32_t* work_list; int32_t* work_meta; };
-// once per batch: one probe block per class in `classes` (gates[class]), then the work lists as copies of the class lists
-hipError_t launch_count_wide_prepare_d0_a1(const int* classes, int nclasses, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w);
-hipError_t launch_count_wide_prepare_d1_a1(const int* classes, int nclasses, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w);
-hipError_t launch_count_wide_prepare_d0_a0(const int* classes, int nclasses, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w);   // (KS-only)
-hipError_t launch_count_wide_prepare_d1_a0(const int* classes, int nclasses, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w);
-// then, before the classes' sorting launches: rank_count_wide_kernel over every class whose gate is set; it appends what it hands on
-// to the work lists itself (value_class: a class of index 5 is among them, rank_count_value_kernel follows in a launch of its own)
-hipError_t launch_count_wide_run_d0_a1(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
-hipError_t launch_count_wide_run_d1_a1(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
-hipError_t launch_count_wide_run_d0_a0(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
-hipError_t launch_count_wide_run_d1_a0(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
-
-hipError_t launch_rank_stats_d0_a0(int cls, int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a);
-hipError_t launch_rank_stats_d0_a1(int cls, int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a);
-hipError_t launch_rank_stats_d1_a0(int cls, int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a);
-hipError_t launch_rank_stats_d1_a1(int cls, int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a);
-// the experiment macros each of the four translation units was compiled with (build_info.hpp)
-const char* rank_stats_build_flags_d0_a0();
-const char* rank_stats_build_flags_d0_a1();
-const char* rank_stats_build_flags_d1_a0();
-const char* rank_stats_build_flags_d1_a1();
+// K1 of one (dtype, tests) translation unit (rank_stats_inst.hip, built four times): its launchers and its build flags
+struct K1Launcher {
+  // a class's sorting form (the 256-capacity class with all tests: behind its counting form when args.cnt_gate is set)
+  hipError_t (*rank_stats)(int cls, int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a);
+  // once per batch: one probe block per class in `classes` (gates[class]), then the work lists as copies of the class lists
+  hipError_t (*count_wide_prepare)(const int* classes, int nclasses, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w);
+  // then, before the classes' sorting launches: rank_count_wide_kernel over every class whose gate is set; it appends what it hands
+  // on to the work lists itself (value_class: a class of index 5 is among them, rank_count_value_kernel follows in a launch of its own)
+  hipError_t (*count_wide_run)(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
+  const char* build_flags;                     // the experiment macros the unit was compiled with (build_info.hpp)
+};
+const K1Launcher& k1_d0_a0(); const K1Launcher& k1_d0_a1(); const K1Launcher& k1_d1_a0(); const K1Launcher& k1_d1_a1();   // f32 / i16 x KS-only / all
+inline const K1Launcher& k1_launcher(int dtype, bool all) {
+  return dtype == NMOD_DTYPE_F32 ? (all ? k1_d0_a1() : k1_d0_a0()) : (all ? k1_d1_a1() : k1_d1_a0());
+}
 
 }  // namespace nmod

@@ -652,6 +652,37 @@ def test_dispatch_forms_keep_16_keys_per_lane():
         assert buf.value == name, (tests, a, b, buf.value)
 
 
+def test_describe_dispatch_table_is_pinned():
+    """nmod_describe_dispatch over every size-class edge, both test modes, the three dtypes, with and without NMOD_FLAG_DEEP:
+    return codes and names are pinned by a digest of the whole table (recorded before the classifier was shared between the
+    binning kernel, the dispatcher and this description).  On a mismatch the table is printed, to be diffed against that build's"""
+    import ctypes as C
+    import hashlib
+    from nanomod_amd import _lib as L
+    lib = L.load()
+    sizes = [1, 63, 64, 65, 128, 129, 256, 257, 319, 320, 512, 513, 1024, 1025, 2048, 2049, 4095, 4096, 4097, 65535, 65536,
+             2 ** 24 - 1, 2 ** 24]
+    buf = C.create_string_buffer(256)
+    rows = []
+    for tests, method in ((L.TEST_KS, L.METHOD_KS), (L.TEST_ALL, L.METHOD_STOUFFER)):
+        for dtype in (L.DTYPE_F32, L.DTYPE_I16_MILLI, L.DTYPE_F64):
+            for flags in (0, L.FLAG_DEEP):
+                prm = L.make_params(tests=tests, method=method, dtype=dtype, flags=flags)
+                for n0 in sizes:
+                    for n1 in sizes:
+                        buf.value = b''
+                        rc = lib.nmod_describe_dispatch(C.byref(prm), n0, n1, buf, 256)
+                        rows.append('%d %d %d %d %d %d %s' % (tests, dtype, flags, n0, n1, rc, buf.value.decode() if rc == 0 else ''))
+    table = '\n'.join(rows) + '\n'
+    digest = hashlib.sha256(table.encode()).hexdigest()
+    if digest != DESCRIBE_TABLE_SHA256:
+        print(table)
+    assert digest == DESCRIBE_TABLE_SHA256
+
+
+DESCRIBE_TABLE_SHA256 = '934e25f2038532d31d54ff684e3ca3f4cf807537c5250dd01ac2d6fb35ebc00b'
+
+
 def test_mfilter_coverage_fast_path_keeps_the_reference_semantics():
     """a non-integer MinCoverage is not truncated (len 4 < 4.5 is deleted, as `len(row) < MinCoverage` does), and a
     strand missing from 'base' raises only when something is actually deleted (myDetect.py:304-309)"""

@@ -1,4 +1,5 @@
 """-m gpu: the HIP path (through the C ABI) against the oracle and the golden fixtures."""
+import ctypes as C
 import json
 import os
 import zlib
@@ -2019,3 +2020,47 @@ def test_int16_packed_sort_edges(nm, all_tests):
         if all_tests:
             ident = (exp['status'] & 1) != 0
             assert np.array_equal(got['mwu_u'][~ident], exp['mwu_u'][~ident]), n
+
+
+def test_dispatch_record_is_that_of_the_last_successful_batch(nm):
+    """nmod_last_dispatch_stats reports the thread's last successful nmod_detect_batch: a failed call clears the record (a
+    device-resident record points into the workspace of its call), nmod_downsample_ks leaves it alone, and an empty batch
+    reports no positions"""
+    import torch
+    import nanomod_amd._lib as L
+    import nanomod_amd.engine as E
+    lib = L.load()
+    rng = np.random.default_rng(11)
+    npos, n = 1000, 40
+    a = torch.from_numpy(rng.standard_normal(npos * n).astype(np.float32)).cuda()
+    b = torch.from_numpy(rng.standard_normal(npos * n).astype(np.float32)).cuda()
+    rid = torch.zeros(npos, dtype=torch.int32, device='cuda:0')
+    det = nm.DeviceDetector(0, nb=2, method='stouffer')
+    det.run(a, b, rid, stride0=n, stride1=n, npos=npos)
+    st = L.last_dispatch_stats()
+    assert st['positions'] == npos and st['rank_hist'] == npos and st['skipped'] == 0, st
+    # the same batch with a workspace one byte short: refused, and no record is left behind
+    prm = det._params(L.DTYPE_F32, n, n, 0, 0)
+    ws, need = det.workspace(prm, npos)
+    res = det.alloc_outputs(npos)
+    o = L.NmodOut()
+    for name in L.OUT_FIELDS:
+        if name in res:
+            setattr(o, name, res[name].data_ptr())
+    o.status = res['status'].data_ptr()
+    rc = lib.nmod_detect_batch(C.byref(prm), npos, a.data_ptr(), None, b.data_ptr(), None, rid.data_ptr(), ws.data_ptr(), need - 1, C.byref(o))
+    assert rc == -4
+    torch.cuda.synchronize()
+    assert lib.nmod_last_dispatch_stats(C.byref(L.NmodDispatchStats())) == -1
+    # a successful batch, then the down-sampling branch (its own KS batches on the library's scratch): the batch's counts stay
+    det.run(a, b, rid, stride0=n, stride1=n, npos=npos)
+    torch.cuda.synchronize()
+    off = np.arange(0, 6 * 300, 300, dtype=np.int64)
+    x = rng.standard_normal(5 * 300).astype(np.float32)
+    y = rng.standard_normal(5 * 300).astype(np.float32)
+    d, p = E.downsample_ks(x, off, y, off, np.arange(5), np.full(5, 100), iters=20)
+    assert np.isfinite(d).all() and np.isfinite(p).all()
+    assert L.last_dispatch_stats() == st
+    # an empty batch: a record of no positions
+    det.run(a, b, rid, stride0=n, stride1=n, npos=0)
+    assert L.last_dispatch_stats() == {k: 0 for k in st}
