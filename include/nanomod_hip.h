@@ -399,6 +399,59 @@ int nmod_allgather_tracks(nmod_comm* comm, void* stream, int64_t block_len, int3
                           const double* const* local, double* const* full);
 int nmod_comm_destroy(nmod_comm* comm);
 
+/* ---- read-level input: per-read event tables -> the tested CSR rows, on the device (nanomod_amd/csrc/read_pivot.hip).
+ * The reference appends every event of every aligned read to its position's list (mReadSignalBase, myDetect.py:104-124),
+ * filters thin positions (mfilter_coverage, myDetect.py:301-314) and tests the positions both groups share, in sorted order
+ * (myDetect.py:421,427-431).  These three calls do the same for flat read sets: prm->memspace must be NMOD_MEM_DEVICE (every
+ * array pointer is device memory; sizes and counts marked "host" are host pointers), prm->dtype is the value type of the
+ * samples, prm->device / prm->stream as everywhere.  Each call synchronises its stream once or a few times to learn its
+ * data-dependent sizes; outputs are identical bytes on every run.  Scratch comes from the library's per-device pool
+ * (nmod_trim_scratch returns it).
+ *
+ * nmod_pivot_reads — myDetect.py:104-124 for a whole read set.  Read r has (chrom, strand) id cs[r] = 2 * chrom index +
+ * (strand == '-') (ids ascend in mtest2's order, '+' before '-'; 0 <= cs < ncs), 0-based start[r] (mapped_start) and events
+ * roff[r] .. roff[r+1] (roff[0] == 0, non-decreasing; at most 2^32 - 1 events in all) of val (prm->dtype) and base (one byte
+ * each).  Event i of a read of n events lies at position start + i on '+', start + n - 1 - i on '-'; events outside the
+ * inclusive clip [pos_lo, pos_hi] (either bound -1 = none; the event-level window of myDetect.py:112-114) are dropped.
+ * Output: *npos_out rows, key_out[i] = cs << 40 | pos strictly ascending, off_out[0 .. npos] CSR offsets into sig_out /
+ * the samples of a row in read order (the order GroupBuilder.finish gives), base_out[i] = the base of the row's LAST read
+ * (myDetect.py:122).  Capacities: key_out / base_out cap_pos rows, off_out cap_pos + 1, sig_out roff[nreads] samples.
+ * NMOD_ERR_INVALID_ARG (nothing written) for bad offsets, cs outside [0, ncs), a negative start, a position at or past 2^40,
+ * or cap_pos below the row count; also when the rows beyond 1 024 samples hold 2^31 - 1 or more samples in all (they are
+ * ordered by one radix sort, whose index range that is; key_out / off_out are written by then, sig_out / base_out are not).
+ * Scratch: 28 B per position of the dense range of every cs (its last covered position minus its first, plus one, summed
+ * over cs) + 4 B per event, and 24 B per sample of rows beyond 1 024 samples (so at most 24 B x (2^31 - 1)). */
+int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t ncs, const int32_t* cs, const int64_t* start,
+                     const int64_t* roff, const void* val, const uint8_t* base, int64_t pos_lo, int64_t pos_hi,
+                     int64_t cap_pos, int64_t* key_out, int64_t* off_out, void* sig_out, uint8_t* base_out,
+                     int64_t* npos_out /* host */, int64_t* nsamples_out /* host */);
+
+/* nmod_select_tested — myDetect.py:301-314 per group + :421,427-431: the rows of both pivoted groups (keys strictly ascending,
+ * offsets off*[0 .. npos*] over nsig* samples of prm->dtype) whose key both groups hold with at least min_coverage samples,
+ * in key order: rows0 / rows1 (cap entries each), the CSR offsets of the tested rows off0_out / off1_out (cap + 1 each),
+ * *ntested_out, the samples per group and *dtype_out, the one dtype detect.encode_pair picks for the tested samples of both
+ * groups (a device reduction): float32 input stays float32; otherwise float32 if every value is float32-exact, else int16
+ * milli-units if every value is k/1000.0 with |k| <= 32767, else float64; float64 input beyond 4 000 000 tested samples
+ * passes through, int16 input is never widened to float64 (its values are k/1000.0).  NMOD_ERR_INVALID_ARG for bad offsets
+ * or cap below the tested row count.  Scratch: 24 B per row of group 1. */
+int nmod_select_tested(const nmod_params* prm, int64_t min_coverage,
+                       int64_t npos0, const int64_t* key0, const int64_t* off0, const void* sig0, int64_t nsig0,
+                       int64_t npos1, const int64_t* key1, const int64_t* off1, const void* sig1, int64_t nsig1,
+                       int64_t cap, int64_t* rows0, int64_t* rows1, int64_t* off0_out, int64_t* off1_out,
+                       int64_t* ntested_out /* host */, int64_t* nsamples0_out /* host */, int64_t* nsamples1_out /* host */,
+                       int32_t* dtype_out /* host */);
+
+/* nmod_gather_tested — the tested rows (from nmod_select_tested) as the inputs of nmod_detect_batch: sig0_out / sig1_out in
+ * out_dtype at off0_out / off1_out, run_out[t] (detect.run_ids / pos_check, myDetect.py:366-371: a new run at every change of
+ * cs or gap in pos, from the keys), key_out[t] = key1[rows1[t]], base0_out / base1_out the bases of both groups (the table
+ * uses group 2's; myDetect.py:432-434 reports mismatches).  int16 input means k/1000.0 in every conversion.  Enqueued only:
+ * no synchronisation.  Scratch: 8 B per tested row. */
+int nmod_gather_tested(const nmod_params* prm, int64_t ntested, const int64_t* rows0, const int64_t* rows1,
+                       const int64_t* off0, const void* sig0, const uint8_t* base0,
+                       const int64_t* off1, const void* sig1, const uint8_t* base1, const int64_t* key1,
+                       int32_t out_dtype, const int64_t* off0_out, const int64_t* off1_out, void* sig0_out, void* sig1_out,
+                       int32_t* run_out, int64_t* key_out, uint8_t* base0_out, uint8_t* base1_out);
+
 /* Lane-permutation self test of the wave primitives the sort is built from
  * (runs tiny kernels; returns NMOD_OK or the number of the first failing primitive). */
 int nmod_selftest(int32_t device);

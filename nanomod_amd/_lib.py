@@ -110,6 +110,12 @@ _SIGNATURES = {
     'nmod_rank_order': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'nmod_region_rank': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_char, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
+                         + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4
+                           + [C.POINTER(C.c_int64)] * 3 + [C.POINTER(C.c_int32)]),
+    'nmod_gather_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 9 + [C.c_int32] + [C.c_void_p] * 8),
 }
 
 

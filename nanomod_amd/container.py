@@ -9,9 +9,17 @@ the CLI reads one `.npz` per read group holding what ReadAllFast5 accumulates in
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 FIELDS = ('chrom', 'strand', 'pos', 'base', 'off', 'sig')
+# A read-level container holds the reads themselves (what --fast5Reader returns, one read after the other): per read
+#     chrom (U)   strand (U1, '+' / '-')   start (int64, 0-based mapped_start)   off (int64[nreads+1], CSR event offsets)
+# per event
+#     norm_mean (float64 | float32 | int16 milli-units)   base (S1)
+# Read order is the order that decides sample order inside a position.  `detect` groups it on the device.
+READ_FIELDS = ('chrom', 'strand', 'start', 'off', 'norm_mean', 'base')
 
 
 def save_group(path, chrom, strand, pos, base, off, sig):
@@ -27,6 +35,49 @@ def load_group(path):
             and g['off'][-1] == len(g['sig'])):
         raise ValueError('%s: inconsistent container' % path)
     return g
+
+
+def milli_or_same(values):
+    """int16 milli-units when every value is k/1000.0 with |k| <= 32767 (NanoMod's 3-dp Events), else the values as given"""
+    v = np.asarray(values)
+    if v.dtype == np.int16 or v.dtype.kind != 'f':
+        return v
+    k = np.rint(v.astype(np.float64) * 1000.0)
+    if np.all(np.abs(k) <= 32767) and np.array_equal(k / 1000.0, v.astype(np.float64)):
+        return k.astype(np.int16)
+    return v
+
+
+def save_reads(path, chrom, strand, start, off, norm_mean, base):
+    """A read-level container, uncompressed (a multi-GB load is bounded by I/O, not zlib); values go in as int16 milli-units
+    when that is exact."""
+    np.savez(path, chrom=np.asarray(chrom).astype(str), strand=np.asarray(strand).astype(str), start=np.asarray(start, dtype=np.int64),
+             off=np.asarray(off, dtype=np.int64), norm_mean=milli_or_same(norm_mean), base=np.asarray(base).astype('S1'))
+
+
+def check_reads(r, what='read set'):
+    n = len(r['start'])
+    off = r['off']
+    if not (len(r['chrom']) == len(r['strand']) == n and len(off) == n + 1 and off[0] == 0 and bool(np.all(np.diff(off) >= 0))
+            and off[-1] == len(r['norm_mean']) == len(r['base']) and bool(np.all(np.isin(r['strand'], ('+', '-'))))
+            and r['norm_mean'].dtype in (np.float64, np.float32, np.int16)):
+        raise ValueError('%s: inconsistent read-level container' % what)
+    return r
+
+
+def load_reads(path):
+    z = np.load(path)
+    r = {k: z[k] for k in READ_FIELDS}
+    r['base'] = r['base'].astype('S1')
+    return check_reads(r, path)
+
+
+def is_read_level(path):
+    """a read-level container is told from a per-position one by its fields (start + norm_mean instead of pos + sig)"""
+    if not (isinstance(path, str) and path.endswith('.npz')) or not os.path.isfile(path):
+        return False
+    with np.load(path) as z:
+        return 'start' in z.files and 'norm_mean' in z.files
 
 
 def from_moptions_dataset(ds):

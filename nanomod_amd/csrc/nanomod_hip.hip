@@ -24,6 +24,7 @@
 #include "deep_rank.hpp"
 #include "rank_all.hpp"
 #include "build_info.hpp"
+#include "scratch_pool.hpp"
 
 namespace nmod {
 
@@ -427,7 +428,7 @@ constexpr int kMaxDevices = 64;
 static std::mutex g_pool_mutex;
 static hipMemPool_t g_pool[kMaxDevices] = {nullptr};        // guarded by g_pool_mutex
 
-static hipMemPool_t scratch_pool(int dev) {
+hipMemPool_t scratch_pool(int dev) {            // (declared in scratch_pool.hpp: read_pivot.hip takes its scratch here too)
   if (dev < 0 || dev >= kMaxDevices) return nullptr;
   std::lock_guard<std::mutex> lock(g_pool_mutex);
   if (!g_pool[dev]) {
@@ -461,26 +462,6 @@ static hipError_t device_cus(int dev, int* num_cus) {
   return hipSuccess;
 }
 
-struct DevScratch {
-  void* p = nullptr; bool async = false; hipStream_t owner = nullptr;
-  hipError_t alloc(size_t bytes, hipStream_t s, int dev) {
-    owner = s;
-    hipMemPool_t pool = scratch_pool(dev);
-    if (pool && hipMallocFromPoolAsync(&p, bytes ? bytes : 4, pool, s) == hipSuccess) { async = true; return hipSuccess; }
-    (void)hipGetLastError();
-    p = nullptr;
-    return hipMalloc(&p, bytes ? bytes : 4);
-  }
-  hipError_t release(hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (p) e = async ? hipFreeAsync(p, s) : (hipStreamSynchronize(s), hipFree(p));
-    p = nullptr;
-    return e;
-  }
-  // an early return (error path) with kernels of the allocation stream still queued: the slab goes back to the pool
-  // ordered behind them on THAT stream — freeing on the null stream does not order against a non-blocking stream
-  ~DevScratch() { if (p) { if (async) hipFreeAsync(p, owner); else { hipStreamSynchronize(owner); hipFree(p); } } }
-};
 
 // ---------------------------------------------------------------- the deep form (NMOD_FLAG_DEEP, deep_rank.hpp)
 // Enqueues K1 of the ndeep positions of class kDeepClass (`tiles` tiles in all, from the classifier) on `stream`: the tile

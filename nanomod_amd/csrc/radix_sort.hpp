@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 namespace nmod {
+namespace {        // internal linkage: each translation unit that sorts (rank_order.hip, read_pivot.hip) has its own copy
 
 constexpr int kRsThreads = 256;
 constexpr int kRsItems = 8;
@@ -152,4 +153,5 @@ inline hipError_t rs_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_t
   return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace nmod

@@ -401,3 +401,183 @@ def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile
                                 _np_ptr(out_d), _np_ptr(out_p))
     L.check(rc, 'nmod_downsample_ks')
     return out_d, out_p
+
+
+# ---------------------------------------------------------------------------------------------------- read-level input
+_TORCH_OF_DTYPE = {L.DTYPE_F32: 'float32', L.DTYPE_I16_MILLI: 'int16', L.DTYPE_F64: 'float64'}
+
+
+def _dtype_code(a):
+    try:
+        return {np.dtype(np.float32): L.DTYPE_F32, np.dtype(np.int16): L.DTYPE_I16_MILLI, np.dtype(np.float64): L.DTYPE_F64}[np.dtype(a)]
+    except KeyError:
+        raise ValueError('values must be float32, int16 (milli-units) or float64')
+
+
+def _torch_dtype_code(t):
+    import torch
+    return {torch.float32: L.DTYPE_F32, torch.int16: L.DTYPE_I16_MILLI, torch.float64: L.DTYPE_F64}[t.dtype]
+
+
+def chrom_names(*read_sets):
+    """the sorted chromosome names over read sets: the index space of the (chrom, strand) ids both groups must share"""
+    heads = [np.unique(np.asarray(r['chrom']).astype(str)) for r in read_sets]
+    return [str(n) for n in np.unique(np.concatenate(heads) if heads else np.zeros(0, str)).tolist()]
+
+
+class _CallTimer:
+    """HIP events around one library call on the current stream; adds its device time (s) to timer[name] when timer is a dict"""
+
+    def __init__(self, timer, name, dev):
+        self.timer, self.name, self.dev = timer, name, dev
+
+    def __enter__(self):
+        if self.timer is not None:
+            import torch
+            self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.a.record(torch.cuda.current_stream(self.dev))
+        return self
+
+    def __exit__(self, *exc):
+        if self.timer is not None and exc[0] is None:
+            import torch
+            self.b.record(torch.cuda.current_stream(self.dev))
+            self.b.synchronize()
+            self.timer[self.name] = self.timer.get(self.name, 0.0) + self.a.elapsed_time(self.b) / 1e3
+        return False
+
+
+def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=None):
+    """nmod_pivot_reads (myDetect.py:104-124) on a read-level set (container.READ_FIELDS): returns device tensors key
+    (cs << 40 | pos, ascending), off, sig (the input dtype), base (uint8) and the host list `names` the chrom ids index.
+    Inside a position the samples come in read order; the base is the last read's.  pos_lo / pos_hi: the inclusive
+    event-level window (myDetect.py:112-114).  timer: a dict that collects the device time (s) of the copy ('h2d') and of
+    nmod_pivot_reads ('pivot'), measured with HIP events."""
+    import torch
+    lib = L.load()
+    _join_warm_up(device)
+    names = chrom_names(reads) if names is None else list(names)
+    chrom = np.asarray(reads['chrom']).astype(str)
+    strand = np.asarray(reads['strand']).astype(str)
+    start = np.ascontiguousarray(reads['start'], dtype=np.int64)
+    off = np.ascontiguousarray(reads['off'], dtype=np.int64)
+    val = np.ascontiguousarray(reads['norm_mean'])
+    dtype = _dtype_code(val.dtype)
+    nreads = len(start)
+    if len(off) != nreads + 1 or len(chrom) != nreads or len(strand) != nreads:
+        raise ValueError('reads: chrom / strand / start need one entry per read and off nreads + 1')
+    if not np.all(np.isin(strand, ('+', '-'))):
+        raise ValueError("reads: strand must be '+' or '-'")
+    cid = np.searchsorted(np.array(names, dtype=str), chrom) if nreads else np.zeros(0, np.int64)
+    if nreads and (np.any(cid >= len(names)) or np.any(np.array(names, dtype=str)[np.minimum(cid, len(names) - 1)] != chrom)):
+        raise ValueError('reads: a chromosome is missing from names')
+    cs = (2 * cid + (strand == '-')).astype(np.int32)
+    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
+    lo = -1 if pos_lo is None else int(pos_lo)
+    hi = -1 if pos_hi is None else int(pos_hi)
+    nev = int(off[-1]) if len(off) else 0
+    # row capacity: no more rows than events, nor than positions of the covered range of every (chrom, strand)
+    cap = nev
+    if nreads:
+        n = np.diff(off)
+        a = np.maximum(start, lo) if lo >= 0 else start
+        b = np.minimum(start + n - 1, hi) if hi >= 0 else start + n - 1
+        ok = (n > 0) & (a <= b)
+        if ok.any():
+            spans = 0
+            for c in np.unique(cs[ok]):
+                m = ok & (cs == c)
+                spans += int(b[m].max()) - int(a[m].min()) + 1
+            cap = min(cap, spans)
+        else:
+            cap = 0
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    with _CallTimer(timer, 'h2d', dev):
+        d_cs, d_start, d_off, d_val, d_base = t(cs), t(start), t(off), t(val), t(base)
+    key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+    roff = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    sig = torch.empty(max(nev, 1), dtype=d_val.dtype, device=dev)
+    rbase = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    npos, nsamp = C.c_int64(0), C.c_int64(0)
+    prm = L.make_params(device=device, memspace=L.MEM_DEVICE, dtype=dtype, stream=torch.cuda.current_stream(dev).cuda_stream)
+    with _CallTimer(timer, 'pivot', dev):
+        rc = lib.nmod_pivot_reads(C.byref(prm), nreads, 2 * len(names), d_cs.data_ptr(), d_start.data_ptr(), d_off.data_ptr(),
+                                  d_val.data_ptr(), d_base.data_ptr(), lo, hi, cap, key.data_ptr(), roff.data_ptr(), sig.data_ptr(),
+                                  rbase.data_ptr(), C.byref(npos), C.byref(nsamp))
+    L.check(rc, 'nmod_pivot_reads')
+    p, ns = npos.value, nsamp.value
+    return dict(key=key[:p], off=roff[:p + 1], sig=sig[:ns], base=rbase[:p], names=names)
+
+
+def group_to_device(g, names, device=0):
+    """a per-position container (container.FIELDS) in the layout pivot_reads returns, rows sorted by key"""
+    import torch
+    chrom = np.asarray(g['chrom']).astype(str)
+    cid = np.searchsorted(np.array(names, dtype=str), chrom)
+    key = (cid.astype(np.int64) << 41) | ((np.asarray(g['strand']) == '-').astype(np.int64) << 40) | np.asarray(g['pos'], dtype=np.int64)
+    order = np.argsort(key, kind='stable')
+    from . import container
+    sig, off = container.gather_rows(np.asarray(g['sig']), np.asarray(g['off'], dtype=np.int64), order)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    base = np.asarray(g['base']).astype('S1').view(np.uint8)[order]
+    return dict(key=t(key[order]), off=t(off), sig=t(sig), base=t(base), names=list(names))
+
+
+def select_tested(g0, g1, min_coverage, device=0, out_level=3, log=print, timer=None):
+    """nmod_select_tested + nmod_gather_tested on two pivoted groups (pivot_reads, same `names`): the tested rows as
+    (meta, sig0, off0, sig1, off1, run_id) like cli.select_positions, the CSR arrays and run ids on the device (the inputs of
+    DeviceDetector.run), meta on the host.  timer: a dict that collects the device time (s) of nmod_select_tested ('select')
+    and nmod_gather_tested ('gather'), measured with HIP events."""
+    import torch
+    lib = L.load()
+    if list(g0['names']) != list(g1['names']):
+        raise ValueError('both groups must be pivoted with the same chromosome names')
+    names = list(g1['names'])
+    dev = torch.device('cuda', device)
+    s0, s1 = g0['sig'], g1['sig']
+    if s0.dtype != s1.dtype:                       # one dtype for both: the exact float64 values (int16 means k / 1000)
+        f = lambda s: s.double() / 1000.0 if s.dtype == torch.int16 else s.double()
+        s0, s1 = f(s0), f(s1)
+    dtype = _torch_dtype_code(s0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    prm = L.make_params(device=device, memspace=L.MEM_DEVICE, dtype=dtype, stream=stream)
+    n0, n1 = g0['key'].numel(), g1['key'].numel()
+    cap = min(n0, n1)
+    rows0 = torch.empty(max(cap, 1), dtype=torch.int64, device=dev); rows1 = torch.empty_like(rows0)
+    off0 = torch.empty(cap + 1, dtype=torch.int64, device=dev); off1 = torch.empty_like(off0)
+    nt, ns0, ns1, odt = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    ptr = lambda x: x.data_ptr() if x.numel() else None
+    with _CallTimer(timer, 'select', dev):
+        rc = lib.nmod_select_tested(C.byref(prm), int(min_coverage), n0, ptr(g0['key']), g0['off'].data_ptr(), ptr(s0), s0.numel(),
+                                    n1, ptr(g1['key']), g1['off'].data_ptr(), ptr(s1), s1.numel(), cap, rows0.data_ptr(),
+                                    rows1.data_ptr(), off0.data_ptr(), off1.data_ptr(), C.byref(nt), C.byref(ns0), C.byref(ns1),
+                                    C.byref(odt))
+    L.check(rc, 'nmod_select_tested')
+    npos = nt.value
+    tdt = getattr(torch, _TORCH_OF_DTYPE[odt.value])
+    sig0 = torch.empty(ns0.value, dtype=tdt, device=dev); sig1 = torch.empty(ns1.value, dtype=tdt, device=dev)
+    run = torch.empty(npos, dtype=torch.int32, device=dev)
+    key = torch.empty(npos, dtype=torch.int64, device=dev)
+    b0 = torch.empty(npos, dtype=torch.uint8, device=dev); b1 = torch.empty_like(b0)
+    off0, off1 = off0[:npos + 1], off1[:npos + 1]
+    with _CallTimer(timer, 'gather', dev):
+        rc = lib.nmod_gather_tested(C.byref(prm), npos, rows0.data_ptr(), rows1.data_ptr(), g0['off'].data_ptr(), ptr(s0),
+                                    ptr(g0['base']), g1['off'].data_ptr(), ptr(s1), ptr(g1['base']), ptr(g1['key']), odt.value,
+                                    off0.data_ptr(), off1.data_ptr(), ptr(sig0), ptr(sig1), ptr(run), ptr(key), ptr(b0), ptr(b1))
+    L.check(rc, 'nmod_gather_tested')
+    hkey = key.cpu().numpy()
+    cid = (hkey >> 41).astype(np.int64)
+    chrom = np.array(names, dtype=str)[cid] if npos else np.zeros(0, dtype=str)
+    strand = np.where((hkey >> 40) & 1, '-', '+').astype('U1')
+    pos = hkey & ((1 << 40) - 1)
+    base = b1.cpu().numpy().view('S1').astype('U1')
+    base0 = b0.cpu().numpy().view('S1').astype('U1')
+    if out_level <= 3:                                                                 # myDetect.py:432-434
+        for i in np.nonzero(base0 != base)[0][:20]:
+            log('Error not equal', (chrom[i], strand[i]), int(pos[i]), base[i], base0[i])
+    h0, h1 = off0.cpu().numpy(), off1.cpu().numpy()
+    meta = dict(chrom=chrom, strand=strand, pos=pos, base=base, n0=np.diff(h0).astype(np.int32), n1=np.diff(h1).astype(np.int32),
+                names=names, chrom_id=cid.astype(np.int32))
+    return meta, sig0, off0, sig1, off1, run

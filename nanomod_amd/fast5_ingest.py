@@ -63,6 +63,47 @@ def read_passes_filters(n_events, mapped_chrom, mapped_start, mapped_strand, opt
     return True
 
 
+def filter_reads(n_events, chrom, start, opts, log=print, names=None):
+    """read_passes_filters over a whole read set at once: a bool mask, and the same log lines in read order"""
+    n = np.asarray(n_events, dtype=np.int64); start = np.asarray(start, dtype=np.int64)
+    keep = np.ones(len(n), dtype=bool)
+    if 'Chr' in opts:
+        keep &= np.asarray(chrom) == opts['Chr']
+    if 'Pos2' in opts:
+        keep &= ~((start > opts['Pos2']) | (start + n < opts['Pos']))
+    if 'start_pos' in opts and 'end_pos' in opts:
+        keep &= ~((start > opts['start_pos']) | (start + n < opts['end_pos']))
+    min_lr, nbw = opts.get('min_lr', 500), opts.get('min_lr_nb', 0)
+    if nbw < 1:
+        short = keep & (n < min_lr)                                                    # myDetect.py:90-93
+        for i in np.flatnonzero(short):
+            log('CheckReadMappedLength={} {}'.format('' if names is None else names[i], int(n[i])))
+        keep &= ~short
+    else:
+        keep &= (min_lr - nbw < n) & (n < min_lr + nbw)
+        near = lambda v: (v < nbw) | ((8000 - nbw < v) & (v < 8000 + nbw)) | ((16000 - nbw < v) & (v < 16000 + nbw))
+        keep &= near(start) & near(start + n)                                          # myDetect.py:99-103
+    return keep
+
+
+def select_reads(reads, opts, log=print):
+    """the reads of a read-level set that pass filter_reads, as a new read-level set (order kept)"""
+    off = reads['off']
+    keep = filter_reads(np.diff(off), reads['chrom'], reads['start'], opts, log, reads.get('name'))
+    if bool(keep.all()):
+        return reads
+    idx = np.flatnonzero(keep)
+    lens = np.diff(off)[idx]
+    new_off = np.zeros(len(idx) + 1, dtype=np.int64)
+    new_off[1:] = np.cumsum(lens)
+    ev = np.repeat(off[idx] - new_off[:-1], lens) + np.arange(new_off[-1], dtype=np.int64)
+    out = {k: reads[k][idx] for k in ('chrom', 'strand', 'start')}
+    if 'name' in reads:
+        out['name'] = [reads['name'][i] for i in idx]
+    out.update(off=new_off, norm_mean=reads['norm_mean'][ev], base=reads['base'][ev])
+    return out
+
+
 class GroupBuilder:
     """Accumulates reads of one group; `finish()` returns the container arrays."""
 
@@ -131,3 +172,39 @@ def ingest_folder(folder, opts=None, reader=None, suffix='.fast5', log=print):
         level = nxt
     log('Number of files in ' + str(folder) + 'is ' + str(n_files))
     return gb.finish()
+
+
+def ingest_folder_reads(folder, opts=None, reader=None, suffix='.fast5', log=print):
+    """The walk of ingest_folder, kept as a read-level set (container.READ_FIELDS + 'name', the file path of each read): one
+    chrom / strand / start per read, the events as they come.  Reads without alignment never enter it; `opts` applies the
+    per-read filters (filter_reads), not the event-level window, which the device pivot applies."""
+    reader = reader or h5py_reader
+    chrom, strand, start, lens, vals, bases, names = [], [], [], [], [], [], []
+    level = [folder.rstrip('/')]
+    n_files = 0
+    while level:
+        nxt = []
+        for cur in level:
+            for name in os.listdir(cur):
+                path = cur + '/' + name
+                if name.endswith(suffix):
+                    n_files += 1
+                    if not os.path.isfile(path):
+                        continue
+                    rec = reader(path)
+                    if rec is not None:
+                        c, st, sd, nm, b = rec
+                        chrom.append(c); start.append(int(st)); strand.append(sd); names.append(path)
+                        lens.append(len(nm)); vals.append(np.asarray(nm)); bases.append(np.asarray(b).astype('S1'))
+                elif os.path.isdir(path) and name != 'mall':
+                    nxt.append(path)
+        level = nxt
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    reads = dict(chrom=np.array(chrom, dtype=str), strand=np.array(strand, dtype=str), start=np.array(start, dtype=np.int64), off=off,
+                 norm_mean=np.concatenate(vals) if vals else np.zeros(0), base=np.concatenate(bases) if bases else np.zeros(0, 'S1'),
+                 name=names)
+    if opts:
+        reads = select_reads(reads, opts, log)
+    log('Number of files in ' + str(folder) + 'is ' + str(n_files))
+    return reads
