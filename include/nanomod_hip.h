@@ -251,9 +251,7 @@ typedef struct nmod_dispatch_stats {
 } nmod_dispatch_stats;
 int nmod_last_dispatch_stats(nmod_dispatch_stats* st);
 
-/* "arch=gfx950 abi=3 ... | <translation unit>: NMOD_SKIP=0 NMOD_EXP=0 ..." — the value of every experiment macro
- * (phase-skip and variant switches of the kernel headers) in each translation unit of THIS binary.  A product build
- * reports NMOD_SKIP=0 NMOD_EXP=0 everywhere (tests/test_abi_and_host.py). */
+/* "arch=gfx950 abi=4 hip=M.m": the target, the ABI version and the HIP version (major.minor) this binary was built with. */
 const char* nmod_build_info(void);
 
 /* KS statistic: ks_d is ks_2samp's own float form max|fl(c0/n0) - fl(c1/n1)| bit for bit in every mode (myDetect.py:341 ->

@@ -247,11 +247,8 @@ __device__ __forceinline__ const float* ks_search(const float* base, float x) {
 
 // Cooperative schedule (all 64 lanes rank one position): S is wave-uniform, so the probes of the first two search levels are
 // scalars — read once per position, the two levels compare against them and take no LDS round trip (VERDICT r4 item 4:
-// configs[4] KS-only 15.89 -> 15.39 ms, LDS instructions -15 %, issue utilisation 0.66 -> 0.68; -DNMOD_KS_TOPS=0 is the old loop;
-// profiles/r5_ks_tops_ab.txt)
-#ifndef NMOD_KS_TOPS
-#define NMOD_KS_TOPS 1
-#endif
+// configs[4] KS-only 15.89 -> 15.39 ms, LDS instructions -15 %, issue utilisation 0.66 -> 0.68 against the loop of LDS probes
+// it replaced; profiles/r5_ks_tops_ab.txt)
 struct KsTops { float hi, lo0, lo1, last; };
 template <int R, int LG>
 __device__ __forceinline__ KsTops ks_tops(const float* base) {
@@ -537,7 +534,6 @@ void ks_rank_kernel(RankStatsArgs args) {
     Q4Raw ra = load_q4(sig_c, off_c, idx_a, have_a);                          // the round being ranked next (raw)
     Q1Raw rt = load_q1(sig_c, off_c, idx_t, have_t);                          // first one-per-lane round
 
-#if !(defined(NMOD_EXP) && (NMOD_EXP & 1))
     if constexpr (PACKED) {
       // two keys per register through the network, then the sorted keys as floats; the top C - m keys of the position
       // are its pads (a sample may equal the pad value 32767: only the key INDEX tells them apart)
@@ -546,7 +542,6 @@ void ks_rank_kernel(RankStatsArgs args) {
     } else {
       seg_sort_any<R, LG>(x, sel, lane);
     }
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) keys[r * ROW + gl] = x[r];
     if constexpr (PACKED) {                        // (the pads go to LDS as +inf: predicated stores, one compare per key)
@@ -600,12 +595,8 @@ void ks_rank_kernel(RankStatsArgs args) {
         const Q4Raw rb = load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
         float xa[4];
         q4_values(xa, ra, c < full);
-#if !(defined(NMOD_EXP) && (NMOD_EXP & 2))
         if (s_full) rank_and_count(std::integral_constant<int, 4>{}, std::true_type{}, keys, xa);
         else rank_and_count(std::integral_constant<int, 4>{}, std::false_type{}, keys, xa);
-#else
-        if (xa[0] + xa[1] + xa[2] + xa[3] == 12345.f) atomicAdd(hist, 1u);
-#endif
         ra = rb;
       }
 #pragma unroll 1
@@ -632,20 +623,14 @@ void ks_rank_kernel(RankStatsArgs args) {
         const Q1Raw nt = load_q1(sig_n, off_n, nfs * 256 + lane, nfs * 256 + lane < q_n);
         const float* kb = lds_all + (wave * PW + sl) * POS_WORDS;
         const int fs = q_c / 256, ts = (q_c - fs * 256 + 63) / 64;
-#if NMOD_KS_TOPS
         const KsTops tops = ks_tops<R, LG>(kb);
-#endif
 #pragma unroll 2
         for (int c = 0; c < fs; ++c) {
           // (past the last round: the last round again — a load that is never used, from an address that exists)
           const Q4Raw rb = load_q4(sig_c, off_c, min(c + 1, fs - 1) * 256 + 4 * lane, true);
           float xq[4];
           q4_values(xq, ra, true);
-#if NMOD_KS_TOPS
           rank_and_count_tops(std::integral_constant<int, 4>{}, kb, tops, xq);
-#else
-          rank_and_count(std::integral_constant<int, 4>{}, std::true_type{}, kb, xq);
-#endif
           ra = rb;
         }
 #pragma unroll 1
@@ -653,11 +638,7 @@ void ks_rank_kernel(RankStatsArgs args) {
           const int idx_now = fs * 256 + c * 64 + lane;
           const Q1Raw r1 = load_q1(sig_c, off_c, idx_now + 64, idx_now + 64 < q_c);
           float xq[1] = {q1_value(rt, idx_now < q_c)};
-#if NMOD_KS_TOPS
           rank_and_count_tops(std::integral_constant<int, 1>{}, kb, tops, xq);
-#else
-          rank_and_count(std::integral_constant<int, 1>{}, std::true_type{}, kb, xq);
-#endif
           rt = r1;
         }
         sig_c = sig_n; off_c = off_n; q_c = q_n; ra = na; rt = nt;
@@ -801,9 +782,6 @@ void ks_rank_kernel(RankStatsArgs args) {
       using Mine = typename std::conditional<LG == 64, unsigned long long, unsigned>::type;
       Mine mine = (Mine)(hits >> seg_base);
       if constexpr (LG < 32) mine &= (Mine)((1u << LG) - 1u);
-#if defined(NMOD_EXP) && (NMOD_EXP & 4)
-      mine = 0;
-#endif
       // the candidate (cumU(0), 0) belongs to lane 0 of the position
       if (gl == 0 && (mine & (Mine)1)) {
         const int cu0 = (int)(h0 >> 16) - (int)(h0 & 0xffffu);

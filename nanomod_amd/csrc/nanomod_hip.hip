@@ -23,7 +23,6 @@
 #include "big_rank.hpp"
 #include "deep_rank.hpp"
 #include "rank_all.hpp"
-#include "build_info.hpp"
 #include "scratch_pool.hpp"
 
 namespace nmod {
@@ -1343,18 +1342,8 @@ int nmod_last_dispatch_stats(nmod_dispatch_stats* st) {
 }
 
 const char* nmod_build_info(void) {
-  static std::once_flag once;
-  static std::string info;
-  std::call_once(once, [] {
-    char head[96];
-    snprintf(head, sizeof(head), "arch=gfx950 abi=%d hip=%d.%d", NMOD_ABI_VERSION, HIP_VERSION_MAJOR, HIP_VERSION_MINOR);
-    info = head;
-    info += " | abi_tu: " NMOD_BUILD_FLAGS;
-    info += std::string(" | k1_f32_ks: ") + k1_d0_a0().build_flags;
-    info += std::string(" | k1_f32_all: ") + k1_d0_a1().build_flags;
-    info += std::string(" | k1_i16_ks: ") + k1_d1_a0().build_flags;
-    info += std::string(" | k1_i16_all: ") + k1_d1_a1().build_flags;
-  });
+  static const std::string info = "arch=gfx950 abi=" + std::to_string(NMOD_ABI_VERSION) + " hip=" + std::to_string(HIP_VERSION_MAJOR) + "." +
+                                  std::to_string(HIP_VERSION_MINOR);
   return info.c_str();
 }
 

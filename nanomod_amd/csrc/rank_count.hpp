@@ -66,16 +66,6 @@ __device__ __forceinline__ void cnt_lookup_chunk(unsigned ap0, unsigned ap1, uns
   for (int h = 0; h < 2; ++h) { lo[h] = b[4 * h] | (b[4 * h + 2] << 16); hi[h] = b[4 * h + 1] | (b[4 * h + 3] << 16); }
 }
 
-#ifndef NMOD_CNT_SKIP
-#define NMOD_CNT_SKIP 0
-#endif
-#ifndef NMOD_CNT_WAVES
-#define NMOD_CNT_WAVES 4
-#endif
-#ifndef NMOD_CNT_TAILS
-#define NMOD_CNT_TAILS 1     // 1: the probe lets batches with a few outliers per position through (the kernel's tail path); 0: round 5's probe
-#endif
-
 // min / max over the 16 lanes of a position, in every lane
 __device__ __forceinline__ int cnt_allmin_i32(int v) {
   v = min(v, dpp_i<NMOD_QP(1, 0, 3, 2), 0xf, 0xf, true>(0, v));
@@ -150,7 +140,6 @@ __global__ __launch_bounds__(1024) void cnt_probe_kernel(CntProbeArgs a) {
     const int vmax = (int)(wave_max_u32((unsigned)hi ^ 0x80000000u) ^ 0x80000000u);
     const int vmin = (int)(~wave_max_u32(~((unsigned)lo ^ 0x80000000u)) ^ 0x80000000u);
     bool fit = __ballot(!ok) == 0ull && (unsigned)(vmax - vmin) < (unsigned)kCntWindow;
-#if NMOD_CNT_TAILS
     if (!fit && __ballot(!ok) == 0ull) {
       // a few outliers: the kernel keeps the position when at most kCntTail samples lie further than 1 024 from the mean of its keys
       // (half of that here: the batch should mostly take the kernel's path without them).  The probe counts against a NARROWER
@@ -166,7 +155,6 @@ __global__ __launch_bounds__(1024) void cnt_probe_kernel(CntProbeArgs a) {
       fit = nfar <= kCntTail / 2;
       if (fit && lane == 0) atomicAdd(&far, nfar);
     }
-#endif
     if (lane == 0) { atomicAdd(&seen, 1); if (fit) atomicAdd(&fits, 1); }
   }
   __syncthreads();
@@ -176,7 +164,7 @@ __global__ __launch_bounds__(1024) void cnt_probe_kernel(CntProbeArgs a) {
 }
 
 template <int DTYPE>
-__global__ __launch_bounds__(64 * kWavesPerBlock, NMOD_CNT_WAVES)
+__global__ __launch_bounds__(64 * kWavesPerBlock, 4)
 void rank_count_kernel(RankStatsArgs args) {
   constexpr int LG = kCntLanes, PW = 4, NS = 16;        // NS: sample slots per lane and group (4 chunks of 4)
   extern __shared__ __attribute__((aligned(16))) unsigned lds_cnt[];
@@ -717,7 +705,6 @@ void rank_count_kernel(RankStatsArgs args) {
       const double dn0 = (double)n0, dn1 = (double)n1;
       double r0, r1;
       if (uniform) { r0 = recip[0]; r1 = recip[1]; } else { r0 = 1.0 / dn0; r1 = 1.0 / dn1; }
-#if !(NMOD_CNT_SKIP & 1)
 #pragma unroll
       for (int s = 0; s < 2 * NS; ++s) {                                          // candidate s: slot s >> 1 of group 1, at its value (even) / just below it (odd)
         const int sl = s >> 1, p = sl >> 1;
@@ -748,7 +735,6 @@ void rank_count_kernel(RankStatsArgs args) {
           }
         }
       }
-#endif
       dmax = seg_allmax_f64<LG>(dmax);
       const unsigned MWS = pos_allsum_u32<LG>(mws);
       // sum_v (a + b)^3 (< 2^28): group 1's samples give a^3 + 3 a^2 b + 3 a b^2, group 2's arrival numbers b^3

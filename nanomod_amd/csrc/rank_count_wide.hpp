@@ -35,10 +35,6 @@
 #include "rank_count.hpp"
 #include "rank_stats_launch.hpp"
 
-#ifndef NMOD_CW_OR3
-#define NMOD_CW_OR3 1        // 1: one v_or3_b32 per two pairs of int16 samples keeps watch for samples outside the window
-#endif
-
 namespace nmod {
 
 constexpr int kCwWindow = 2048;                                // values the table covers: 64 lane blocks of 32 entries
@@ -474,9 +470,6 @@ __device__ __forceinline__ void cw_segment(const RankStatsArgs& args, int32_t* w
           iq2 = (unsigned)__builtin_amdgcn_sdot2(d2, d2, (int)iq2, false);
         }
         const unsigned uu = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(CntU2, d2) + __builtin_bit_cast(CntU2, hw2), __builtin_bit_cast(CntU2, w2)));
-#if !NMOD_CW_OR3
-        watch |= uu;
-#endif
         const unsigned x0 = ((uu & 0xffffu) >> lgE << 4) + tbE, x1 = ((uu >> 16) >> lgE << 4) + tbE;
         unsigned a0, a1;
         asm("v_mad_u32_u16 %0, %1, 4, %2" : "=v"(a0) : "v"(uu), "v"(x0));
@@ -507,11 +500,7 @@ __device__ __forceinline__ void cw_segment(const RankStatsArgs& args, int32_t* w
             } else {
               const CntWU2 two = __builtin_bit_cast(CntWU2, qb[j]);
               const unsigned ua = q_pair16(two.x), ub = q_pair16(two.y);
-#if NMOD_CW_OR3
-              asm("v_or3_b32 %0, %1, %2, %3" : "=v"(watch) : "v"(watch), "v"(ua), "v"(ub));
-#else
-              (void)ua; (void)ub;
-#endif
+              asm("v_or3_b32 %0, %1, %2, %3" : "=v"(watch) : "v"(watch), "v"(ua), "v"(ub));   // one OR per two pairs
             }
           }
         }

@@ -165,12 +165,6 @@ __device__ __forceinline__ unsigned pos_allsum_u32(unsigned v) {     // sum over
   return v;
 }
 
-#ifndef NMOD_SKIP
-#define NMOD_SKIP 0
-#endif
-#ifndef NMOD_HIST_WAVES
-#define NMOD_HIST_WAVES 4
-#endif
 // WIDE (LG = 64, R = 1, 2 or 4; one position per wave): positions whose groups fall in DIFFERENT capacity classes, the
 // smaller one S of at most 256 samples, the other Q of up to 4 096 (config 5: ~1000 v ~50 reads).  S is sorted and
 // ranked into exactly as above; Q streams through the ranking rounds in a loop (nothing of it is kept), and the ties
@@ -184,16 +178,13 @@ __device__ __forceinline__ unsigned pos_allsum_u32(unsigned v) {     // sum over
 constexpr unsigned kWideEmpty = 0xffffffffu;
 constexpr int kWideList = 128;                     // words of the list in front of the exact table: < 64 waiting + <= 64 of one flush
 constexpr int kWideTail = 64;                      // counters: samples of Q outside the window wait here for an all-pairs tie count (round 6)
-#ifndef NMOD_WIDE_TAILS
-#define NMOD_WIDE_TAILS 1                          // 0: round 5's form — any sample outside the window sends the position to recount16
-#endif
 
 // AFTER (R = LG = 16 only): the launch follows rank_count_kernel (rank_count.hpp) over the same work list.  When the probe's
 // gate is set, that kernel has left one flag byte per position, four per work item (cnt_done as dwords): a wave reads the
 // dwords of its next 64 items with one load and walks only the items that still hold a position (a 64-bit mask), and
 // inside such an item only those positions are valid.  Gate clear: every item, as without AFTER.
 template <int R, int LG, int DTYPE, bool WIDE = false, bool AFTER = false>
-__global__ __launch_bounds__(64 * kWavesPerBlock, (WIDE ? 2 : (R <= 16 ? NMOD_HIST_WAVES : 2)))
+__global__ __launch_bounds__(64 * kWavesPerBlock, (WIDE ? 2 : (R <= 16 ? 4 : 2)))
 void rank_hist_kernel(RankStatsArgs args) {
   static_assert(!AFTER || (!WIDE && 64 / LG == 4), "the counting form works on items of four positions");
   // around the counting form two instances are launched and the probe's gate picks one: continuous rows run the plain instance
@@ -357,7 +348,6 @@ void rank_hist_kernel(RankStatsArgs args) {
     const Q1Raw rk = load_q1(sig_q, off_q, 0, q > 0);                       // the shift of Q's moments
 
     // ---- S: moments, sort, keys to LDS, ties inside S
-#if !(NMOD_SKIP & 4)
     // WIDE: fl(1/m) and fl(1/q) once per position, for both groups' moments and the float form of D (this form has the
     // registers to keep them; the packed form re-derives them where needed)
     double rm_w = 0.0, rq_w = 0.0;
@@ -375,7 +365,6 @@ void rank_hist_kernel(RankStatsArgs args) {
         mo[0] = mean; mo[1] = m2;
       }
     }
-#endif
     // WIDE, float32: are S's samples on the milli-unit grid?  Then Q's ties are counted by value (direct-address counters, as
     // for int16 input) instead of through the multiset hash, as long as Q's samples are on the grid too (checked as they stream)
     bool s_grid = false;
@@ -384,11 +373,7 @@ void rank_hist_kernel(RankStatsArgs args) {
 #pragma unroll
       for (int r = 0; r < R; ++r) { int k; const bool ok = grid_key(x[r], k); okl = okl && (ok || r * 64 + lane >= m); }
       s_grid = __ballot(!okl) == 0ull && m > 0;
-#if defined(NMOD_NO_GRID)
-      s_grid = false;
-#endif
     }
-#if !(NMOD_SKIP & 16)
     if constexpr (PACKED) {
       // (packed_sort_i16.hpp; the top C - m keys of the position are its pads: a sample may equal the pad value 32767,
       // only the key index tells them apart)
@@ -402,15 +387,10 @@ void rank_hist_kernel(RankStatsArgs args) {
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) keys[r * ROW + gl] = x[r];
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) hist[r * ROW + gl] = 0u;
     if (gl == LG - 1) hist[Lay::END] = 0u;                               // bin C
-#if (NMOD_SKIP & 8)
-    unsigned pp = 0;
-#else
     unsigned pp = seg_tie_pp<R, LG>(x, gl, lane);
-#endif
     asm volatile("" : "+v"(pp));                  // (done here, while S is in registers: not sunk below the ranking rounds)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -429,32 +409,18 @@ void rank_hist_kernel(RankStatsArgs args) {
     // rank NV samples: all the searches first (independent chains of LDS reads that the scheduler interleaves), then
     // the histogram updates: bin L(x) += 1 << 16, + 1 when x equals the key it landed on (ks_rank.hpp) — no second
     // search and no branch on ties
-#ifndef NMOD_WIDE_TOPS
-#define NMOD_WIDE_TOPS 0
-#endif
-    // WIDE: one position per wave, so S is wave-uniform: the probes of the first two search levels as scalars (ks_rank.hpp)
-    [[maybe_unused]] KsTops tops;
-    if constexpr (WIDE && NMOD_WIDE_TOPS) tops = ks_tops<R, LG>(keys);
     auto rank_many = [&](auto nv_tag, const float* xq, bool have, unsigned* ad) {
       constexpr int NV = decltype(nv_tag)::value;
       const float* lp[NV];
 #pragma unroll
-      for (int e = 0; e < NV; ++e) {
-        if constexpr (WIDE && NMOD_WIDE_TOPS) lp[e] = ks_search_tops<R, LG>(keys, xq[e], tops);
-        else lp[e] = ks_search<R, LG, false, true>(keys, xq[e]);
-      }
+      for (int e = 0; e < NV; ++e) lp[e] = ks_search<R, LG, false, true>(keys, xq[e]);
       unsigned inc[NV];
 #pragma unroll
       for (int e = 0; e < NV; ++e) inc[e] = (*lp[e] == xq[e]) ? 0x10001u : 0x10000u;
 #pragma unroll
       for (int e = 0; e < NV; ++e) {
         unsigned* bin = reinterpret_cast<unsigned*>(const_cast<float*>(lp[e])) + HIST_OFF;
-#if !(NMOD_SKIP & 1024)
         if (have) atomicAdd(bin, inc[e]);
-#else
-        asm volatile("" :: "v"(bin), "v"(inc[e]));
-        if (have) atomicAdd(hist + (threadIdx.x & 63), inc[e]);          // (timing experiment: a conflict-free address)
-#endif
         ad[e] = (unsigned)(uintptr_t)bin - (unsigned)(uintptr_t)keys;      // byte offset inside the position's LDS (< 64 KB)
       }
     };
@@ -472,7 +438,7 @@ void rank_hist_kernel(RankStatsArgs args) {
     // on the grid: the deferred list's words, unused on this path) and tail_ties() counts the ties among the listed samples by
     // all pairs after the pass.  More than kWideTail of them: recount16 as before.
     int wtails = 0;                                                          // (wave-uniform) samples put on the tail list
-    const int wcount = WIDE ? wslots - ((NMOD_WIDE_TAILS && DTYPE == 1) ? kWideTail : 0) : 0;   // words of 8-bit counters
+    const int wcount = WIDE ? wslots - (DTYPE == 1 ? kWideTail : 0) : 0;   // words of 8-bit counters
     [[maybe_unused]] unsigned* const wtail = reinterpret_cast<unsigned*>(keys) + BIN_WORDS + wcount;   // (float32: wcount = wslots, the deferred list)
     [[maybe_unused]] auto count_many = [&](auto cb_tag, auto nv_tag, const int* iv, const bool* have, int base) {
       constexpr int BITS = decltype(cb_tag)::value, NV = decltype(nv_tag)::value;
@@ -485,20 +451,14 @@ void rank_hist_kernel(RankStatsArgs args) {
         const bool in = u < ((unsigned)((BITS == 8) ? wcount : wslots) << PW_LOG);
         sh[e] = (u & ((1u << PW_LOG) - 1u)) * (unsigned)BITS;
         old[e] = 0u;
-#if !(NMOD_SKIP & 128)
         if (have[e] && in) old[e] = atomicAdd(&ht[u >> PW_LOG], 1u << sh[e]);
-#endif
         if constexpr (BITS == 8) {
-#if NMOD_WIDE_TAILS
           const unsigned long long mk = __ballot(have[e] && !in);
           if (mk != 0ull) {                                                  // (wave-uniform; never on rows without outliers)
             const int idx = wtails + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
             if (have[e] && !in && idx < kWideTail) wtail[idx] = (unsigned)iv[e];
             wtails += (int)__popcll(mk);
           }
-#else
-          redo |= __ballot(have[e] && !in);
-#endif
         }
       }
 #pragma unroll
@@ -578,9 +538,7 @@ void rank_hist_kernel(RankStatsArgs args) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) xa[e] = (float)iv[e];
         unsigned ad[4];
-#if !(NMOD_SKIP & 512)
         rank_many(std::integral_constant<int, 4>{}, xa, true, ad);
-#endif
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const int d = iv[e] - kq; s1i += d; s2i += (long long)d * (long long)d; }
         count_many(std::integral_constant<int, 8>{}, std::integral_constant<int, 4>{}, iv, hv, wb);
@@ -596,9 +554,7 @@ void rank_hist_kernel(RankStatsArgs args) {
         const bool hv[1] = {have};
         const float xq1[1] = {have ? (float)iv1[0] : big};
         unsigned a1[1];
-#if !(NMOD_SKIP & 512)
         rank_many(std::integral_constant<int, 1>{}, xq1, have, a1);
-#endif
         const int d = have ? iv1[0] - kq : 0;
         s1i += d; s2i += (long long)d * (long long)d;
         count_many(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{}, iv1, hv, wb);
@@ -673,13 +629,8 @@ void rank_hist_kernel(RankStatsArgs args) {
             idx[e] = hsh >> SH;
             bit[e] = 1u << (idx[e] & 31u);
           }
-#if !(NMOD_SKIP & 4096)
 #pragma unroll
           for (int e = 0; e < NV; ++e) { old[e] = 0u; if (have[e]) old[e] = atomicOr(&ht[idx[e] >> 5], bit[e]); }
-#else
-#pragma unroll
-          for (int e = 0; e < NV; ++e) old[e] = 0u;               // (timing experiment: no bitmap atomics)
-#endif
           bool hit[NV], any = false;
 #pragma unroll
           for (int e = 0; e < NV; ++e) { hit[e] = (old[e] & bit[e]) != 0u; any = any || hit[e]; hits += hit[e] ? 1u : 0u; }
@@ -694,9 +645,7 @@ void rank_hist_kernel(RankStatsArgs args) {
           const float xa[4] = {ra.x, ra.y, ra.z, ra.w};
           if (rank) {
             unsigned ad[4];
-#if !(NMOD_SKIP & 512)
             rank_many(std::integral_constant<int, 4>{}, xa, true, ad);
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const double d = (double)xa[e] - KQ; s1w += d; s2w = __fma_rn(d, d, s2w); }
           }
@@ -718,18 +667,13 @@ void rank_hist_kernel(RankStatsArgs args) {
           rt = load_q1(sig_q, off_q, idx, idx < q);
           if (rank) {
             unsigned a1[1];
-#if !(NMOD_SKIP & 512)
             rank_many(std::integral_constant<int, 1>{}, xq1, have, a1);
-#endif
             const double d = (double)(have ? xq1[0] : kqf) - KQ;
             s1w += d; s2w = __fma_rn(d, d, s2w);
           }
           { const bool hv[1] = {have}; mark_many(std::integral_constant<int, 1>{}, xq1, hv); }
         }
         const unsigned total_hits = pos_allsum_u32<64>(hits);
-#if (NMOD_SKIP & 2048)
-        return;                                                    // (timing experiment: no second pass)
-#endif
         if (total_hits == 0u) return;                              // no two samples on one bit: no ties inside Q
         if (2u * total_hits + 64u > (3u * tslots) / 4u) {          // (a bit shared by c samples: c - 1 hits, c <= 2 (c - 1) samples to walk)
           if (valid && lane == 0) args.redo_list[atomicAdd(args.redo_count, 1)] = (int32_t)pos;
@@ -762,19 +706,11 @@ void rank_hist_kernel(RankStatsArgs args) {
           unsigned bits[NV], idx[NV], w[NV];
 #pragma unroll
           for (int e = 0; e < NV; ++e) { bits[e] = __float_as_uint(xv[e] + 0.0f); idx[e] = (bits[e] * 2654435761u) >> SH; }
-#if (NMOD_SKIP & 16384)
-#pragma unroll
-          for (int e = 0; e < NV; ++e) w[e] = idx[e];                // (timing experiment: no bitmap reads)
-#else
 #pragma unroll
           for (int e = 0; e < NV; ++e) w[e] = B2[idx[e] >> 5];
-#endif
 #pragma unroll
           for (int e = 0; e < NV; ++e) {
             bool sus = have[e] && ((w[e] >> (idx[e] & 31u)) & 1u) != 0u;
-#if (NMOD_SKIP & 8192)
-            ppq += sus ? 1u : 0u; sus = false;                        // (timing experiment: no list, no walks)
-#endif
             if (__ballot(sus && full_l) != 0ull) flush();
             pend = sus ? bits[e] : pend;
             full_l = full_l || sus;
@@ -823,9 +759,7 @@ void rank_hist_kernel(RankStatsArgs args) {
           const Q4Raw rb = load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
           const float xa[4] = {ra.x, ra.y, ra.z, ra.w};
           unsigned ad[4];
-#if !(NMOD_SKIP & 512)
           rank_many(std::integral_constant<int, 4>{}, xa, true, ad);
-#endif
           int iv[4]; bool hv[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -844,9 +778,7 @@ void rank_hist_kernel(RankStatsArgs args) {
           const int idx = full * (4 * LG) + (c + 1) * LG + gl;
           rt = load_q1(sig_q, off_q, idx, idx < q);
           unsigned a1[1];
-#if !(NMOD_SKIP & 512)
           rank_many(std::integral_constant<int, 1>{}, xq1, have, a1);
-#endif
           const double d = (double)(have ? xq1[0] : kqf) - KQ;
           s1w += d; s2w = __fma_rn(d, d, s2w);
           int iv1[1];
@@ -867,9 +799,6 @@ void rank_hist_kernel(RankStatsArgs args) {
       }
     } else {
     __builtin_amdgcn_s_waitcnt(0x0F70);            // everything requested before the sort has arrived
-#if (NMOD_SKIP & 32)
-    full_w = 0; tail_w = 0;
-#endif
 #pragma unroll
     for (int c = 0; c < R / 4; ++c) {
       if (c < full_w) {
@@ -1026,7 +955,6 @@ void rank_hist_kernel(RankStatsArgs args) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
-#if !(NMOD_SKIP & 64)
     if constexpr (WIDE) {
       // Q's moments from the sums of the ranking rounds (shifted by its first sample)
       const float kqf = (q > 0) ? (float)rk : 0.0f;
@@ -1086,7 +1014,6 @@ void rank_hist_kernel(RankStatsArgs args) {
     }   // !WIDE
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#endif
     // ---- the float form of D, only for the candidates that reach the integer maximum: the lanes of a position
     // take the bins of one such lane at a time from the table
     double dmax = 0.0;
@@ -1103,9 +1030,6 @@ void rank_hist_kernel(RankStatsArgs args) {
       using Mine = typename std::conditional<LG == 64, unsigned long long, unsigned>::type;
       Mine mine = (Mine)(hits >> seg_base);
       if constexpr (LG < 32) mine &= (Mine)((1u << LG) - 1u);
-#if (NMOD_SKIP & 2)
-      mine = 0;
-#endif
       // the candidate (cumU(0), 0) belongs to lane 0 of the position: bin 0's table word was cleared, its counts are
       // what `cum` of lane 0 started from
       if (gl2 == 0 && (mine & (Mine)1)) {
@@ -1172,10 +1096,8 @@ void rank_hist_kernel(RankStatsArgs args) {
     // (a bin is unordered inside and ordered against its neighbours: maxc phases sort every bin.  Groups far apart
     // put many samples into one end bin — up to q phases of 2 instructions per key, against the register footprint
     // that a second copy of the full network would add to every item)
-#if !(NMOD_SKIP & 1)
     if (maxc > 1) seg_oddeven_phases<R, LG>(y, gl2, maxc);
     pp += seg_tie_pp<R, LG>(y, gl2, lane);
-#endif
     }
 
     // ---- totals of the position

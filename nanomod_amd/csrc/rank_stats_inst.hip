@@ -11,7 +11,6 @@
 #include "rank_count_wide.hpp"
 #include "rank_count_value.hpp"
 #include "rank_stats_launch.hpp"
-#include "build_info.hpp"
 
 #ifndef NMOD_INST_DTYPE
 #error "define NMOD_INST_DTYPE and NMOD_INST_ALL"
@@ -257,7 +256,7 @@ hipError_t count_wide_run(int num_cus, int64_t work_items, hipStream_t stream, c
 #define NMOD_CAT(a, b) NMOD_CAT2(a, b)
 #define NMOD_K1_NAME NMOD_CAT(NMOD_CAT(k1_d, NMOD_INST_DTYPE), NMOD_CAT(_a, NMOD_INST_ALL))
 const K1Launcher& NMOD_K1_NAME() {
-  static const K1Launcher k1 = {launch_rank_stats, count_wide_prepare, count_wide_run, NMOD_BUILD_FLAGS};
+  static const K1Launcher k1 = {launch_rank_stats, count_wide_prepare, count_wide_run};
   return k1;
 }
 

@@ -71,17 +71,15 @@ inline bool wide_class(int cls) {
   return cls < kNumGeneralClasses && (cls / kNumSizeClasses <= 2 || cls % kNumSizeClasses <= 2);
 }
 // 32-bit words of a wave's tie table in the WIDE form (rank_hist.hpp): see wide_table_words.
-#ifndef NMOD_WIDE_I16_WORDS
-#define NMOD_WIDE_I16_WORDS 2048                   // 8 192 values, four blocks per CU (1 912 words = five blocks: measured 10 % slower)
-#endif
+constexpr int kWideI16Words = 2048;                // 8 192 values, four blocks per CU (1 912 words = five blocks: measured 10 % slower)
 __host__ __device__ constexpr int wide_table_words(int cls, int dtype) {
-  // int16: NMOD_WIDE_I16_WORDS (counters over 8 192 values).  float32 (round 4): 2 048 words for every class — the two bitmaps of
+  // int16: kWideI16Words (counters over 8 192 values).  float32 (round 4): 2 048 words for every class — the two bitmaps of
   // the bitmap form (B1's words double as the exact table of the few samples on shared bits), the counters of the grid form
   // (8 192 values); the multiset hash that sized the table by the class of the larger group (up to 4 100 words: two blocks per
   // CU for groups beyond 2 048 samples) is gone — a position with more shared bits than the exact table takes is finished by
   // wide_redo_kernel.  Every class of R = 1, 2 fits four blocks per CU (+6.5 % on configs[4] over 3 068 / 4 100 words).
   (void)cls;
-  return dtype == 1 ? NMOD_WIDE_I16_WORDS : 2048;
+  return dtype == 1 ? kWideI16Words : 2048;
 }
 __host__ __device__ constexpr int wide_table_slots(int words) {
   switch (words) {
@@ -180,7 +178,6 @@ struct K1Launcher {
   // then, before the classes' sorting launches: rank_count_wide_kernel over every class whose gate is set; it appends what it hands
   // on to the work lists itself (value_class: a class of index 5 is among them, rank_count_value_kernel follows in a launch of its own)
   hipError_t (*count_wide_run)(int num_cus, int64_t work_items, hipStream_t s, const RankStatsArgs& a, const CountWideWs& w, bool value_class);
-  const char* build_flags;                     // the experiment macros the unit was compiled with (build_info.hpp)
 };
 const K1Launcher& k1_d0_a0(); const K1Launcher& k1_d0_a1(); const K1Launcher& k1_d1_a0(); const K1Launcher& k1_d1_a1();   // f32 / i16 x KS-only / all
 inline const K1Launcher& k1_launcher(int dtype, bool all) {

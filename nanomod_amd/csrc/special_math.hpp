@@ -129,9 +129,6 @@ __device__ inline double betacf(double a, double b, double x) {
       const double sc = __builtin_amdgcn_rcp(fmax(mag, 1e-300));
       A0 *= sc; B0 *= sc; A1 *= sc; B1 *= sc;
     }
-#if defined(NMOD_EXP) && (NMOD_EXP & 8)
-    break;
-#endif
   }
   const double tiny = 1e-300;
   if (fabs(B1) < tiny) B1 = tiny;

@@ -24,37 +24,22 @@ __device__ __forceinline__ float dpp_f(float old, float src) {
   return __int_as_float(dpp_i<CTRL, ROW_MASK, BANK_MASK, BOUND_CTRL>(__float_as_int(old), __float_as_int(src)));
 }
 
-// Which exchanges go through the LDS crossbar (ds_swizzle, bit mode: lane ^ mask inside 32 lanes) instead of
-// a DPP move.  A DPP move is a VALU instruction (~6 cycles of the SIMD with the v_med3 that consumes it,
-// tools/valu_rate.hip); ds_swizzle issues on the LDS pipe, which K1's sort leaves mostly idle.
-// bits: 1 xor1, 2 xor2, 4 xor4, 8 xor8, 16 mirror2, 32 mirror4, 64 mirror8, 128 mirror16
-#ifndef NMOD_SWZ_MASK
-#define NMOD_SWZ_MASK 0
-#endif
-template <int XORMASK>
-__device__ __forceinline__ float lane_swizzle_xor(float x) {
-  return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x1F | (XORMASK << 10)));
-}
+// Exchanges inside a 16-lane row are DPP moves, VALU instructions (~6 cycles of the SIMD with the v_med3 that consumes
+// them, tools/valu_rate.hip).  ds_swizzle in their place, on the LDS pipe that K1's sort leaves mostly idle, was measured:
+// the xor-4 stage alone -1 %, all 176 moves per item +3.5 % (profiles/HISTORY.md).
 
 // value of lane (l ^ M) for M in {1,2,4,8,16}
 template <int M>
 __device__ __forceinline__ float lane_xor(float x) {
-  if constexpr (M <= 8 && (NMOD_SWZ_MASK & M) != 0) return lane_swizzle_xor<M>(x);
-  else
   // every lane has a valid source in these patterns, so bound_ctrl:1 with old = 0 lets the
   // compiler emit the bare v_mov_b32_dpp (a tied `old` costs an extra v_mov per move)
   if constexpr (M == 1) return dpp_f<NMOD_QP(1, 0, 3, 2), 0xf, 0xf, true>(0.0f, x);
   else if constexpr (M == 2) return dpp_f<NMOD_QP(2, 3, 0, 1), 0xf, 0xf, true>(0.0f, x);
   else if constexpr (M == 8) return dpp_f<0x120 + 8, 0xf, 0xf, true>(0.0f, x);   // row_ror:8 == xor 8 inside a row
   else if constexpr (M == 4) {
-#if defined(NMOD_XOR4_BANKS)
-    float y = dpp_f<kDppRowShl + 4, 0xf, 0x5>(x, x);   // banks 0,2 read lane+4
-    return dpp_f<kDppRowShr + 4, 0xf, 0xA>(y, x);      // banks 1,3 read lane-4
-#else
-    // l ^ 4 = (l ^ 7) ^ 3: a mirror of the 8-lane half, then of the quad — two full moves (the bank-masked pair above
-    // needs a copy of x first and writes one register twice: three dependent instructions)
+    // l ^ 4 = (l ^ 7) ^ 3: a mirror of the 8-lane half, then of the quad — two full moves (a bank-masked row_shl:4 / row_shr:4
+    // pair needs a copy of x first and writes one register twice: three dependent instructions)
     return dpp_f<NMOD_QP(3, 2, 1, 0), 0xf, 0xf, true>(0.0f, dpp_f<kDppRowHalfMirror, 0xf, 0xf, true>(0.0f, x));
-#endif
   } else {
     static_assert(M == 16, "lane_xor: unsupported distance");
     return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), 0x401F));  // bit mode: xor 0x10
@@ -64,8 +49,7 @@ __device__ __forceinline__ float lane_xor(float x) {
 // value of lane (l ^ (G-1)): reversal inside aligned groups of G lanes
 template <int G>
 __device__ __forceinline__ float lane_mirror(float x, int lane) {
-  if constexpr (G <= 16 && (NMOD_SWZ_MASK & (G * 8)) != 0) return lane_swizzle_xor<G - 1>(x);
-  else if constexpr (G == 2) return dpp_f<NMOD_QP(1, 0, 3, 2), 0xf, 0xf, true>(0.0f, x);
+  if constexpr (G == 2) return dpp_f<NMOD_QP(1, 0, 3, 2), 0xf, 0xf, true>(0.0f, x);
   else if constexpr (G == 4) return dpp_f<NMOD_QP(3, 2, 1, 0), 0xf, 0xf, true>(0.0f, x);
   else if constexpr (G == 8) return dpp_f<kDppRowHalfMirror, 0xf, 0xf, true>(0.0f, x);
   else if constexpr (G == 16) return dpp_f<kDppRowMirror, 0xf, 0xf, true>(0.0f, x);

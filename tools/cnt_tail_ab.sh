@@ -1,10 +1,10 @@
 #!/bin/bash
 # tools/cnt_tail_ab.sh: the counting form of the 256-capacity class with its outlier path, on one box: configs[2] (4.6 M x 200 v 200, all
-# tests) on event-like rows with 0 / 1 / 10 per mille outliers, int16 and float32, for every library in LIBS (default: the build +
-# nanomod_amd/exp/*.so).  One line per run.
+# tests) on event-like rows with 0 / 1 / 10 per mille outliers, int16 and float32, for every library in LIBS (default: the build).
+# One line per run.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
-LIBS=${LIBS:-"$R/nanomod_amd/libnanomod_hip.so $(ls $R/nanomod_amd/exp/*.so 2>/dev/null)"}
+LIBS=${LIBS:-$R/nanomod_amd/libnanomod_hip.so}
 for DT in ${DTYPES:-i16 f32}; do
   for O in ${OUTLIERS:-0 1 10}; do
     for LIB in $LIBS; do

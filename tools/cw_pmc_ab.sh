@@ -1,9 +1,10 @@
 #!/bin/bash
-# tools/cw_pmc_ab.sh: counters of rank_count_wide_kernel for every library in LIBS on one box (ragged preset, all tests, int16 event-like
-# rows, OUTLIERS per mille): VALU / SALU / LDS instructions, wave cycles, instruction-cache misses — per pass of 2 M positions
+# tools/cw_pmc_ab.sh: counters of rank_count_wide_kernel for every library in LIBS (default: the build) on one box (ragged preset, all
+# tests, int16 event-like rows, OUTLIERS per mille): VALU / SALU / LDS instructions, wave cycles, instruction-cache misses — per pass
+# of 2 M positions
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
-LIBS=${LIBS:-"$R/nanomod_amd/libnanomod_hip.so $(ls $R/nanomod_amd/exp/*.so 2>/dev/null)"}
+LIBS=${LIBS:-$R/nanomod_amd/libnanomod_hip.so}
 for O in ${OUTLIERS:-0}; do
 for LIB in $LIBS; do
   export NMOD_HIP_LIB=$LIB

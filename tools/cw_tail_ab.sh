@@ -1,10 +1,10 @@
 #!/bin/bash
 # tools/cw_tail_ab.sh: the counting form for any coverage with its tail list, on one box: the ragged preset (configs[4]) and the chr20
-# shape, all tests, int16 / float32 event-like rows with 0 / 1 / 10 per mille outliers, for every library in LIBS (default: the build +
-# nanomod_amd/exp/*.so, made by tools/build_variant.sh).  One line per run: positions/s, K1 ms, form share.
+# shape, all tests, int16 / float32 event-like rows with 0 / 1 / 10 per mille outliers, for every library in LIBS (default: the build).
+# One line per run: positions/s, K1 ms, form share.
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp; export TMPDIR=/tmp
-LIBS=${LIBS:-"$R/nanomod_amd/libnanomod_hip.so $(ls $R/nanomod_amd/exp/*.so 2>/dev/null)"}
+LIBS=${LIBS:-$R/nanomod_amd/libnanomod_hip.so}
 for CFG in ${CONFIGS:-ragged}; do
   for DT in ${DTYPES:-i16}; do
     for O in ${OUTLIERS:-0 1 10}; do

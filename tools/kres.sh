@@ -1,7 +1,7 @@
 #!/bin/bash
-# registers / scratch of the K1 instances: tools/kres.sh <dtype 0|1> <all 0|1> [name filter] [extra -D flags]
+# registers / scratch of the K1 instances: tools/kres.sh <dtype 0|1> <all 0|1> [name filter]
 cd "$(dirname "$0")/../nanomod_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DNMOD_INST_DTYPE=$1 -DNMOD_INST_ALL=$2 $4 -Rpass-analysis=kernel-resource-usage -c rank_stats_inst.hip -o /tmp/kres_$1_$2.o 2>&1 \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DNMOD_INST_DTYPE=$1 -DNMOD_INST_ALL=$2 -Rpass-analysis=kernel-resource-usage -c rank_stats_inst.hip -o /tmp/kres_$1_$2.o 2>&1 \
  | python3 -c "
 import re,sys
 name=None; rec={}

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/time_libs.sh "<bench args>" lib1.so lib2.so ...: timed run only (phase-skip variants give wrong numbers: no verify gate)
+# tools/time_libs.sh "<bench args>" lib1.so lib2.so ...: timed run only, one line per library (verify is printed, not gated on)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 ARGS="$1"; shift
 for lib in "$@"; do
