@@ -376,6 +376,26 @@ int nmod_region_rank(const nmod_params* prm, int64_t npos, const int32_t* strand
                      const int64_t* pos, const char* base, const double* value, int32_t w, int32_t movesize,
                      char na, double percentile, int32_t wind_ovlp, int32_t* ranked_out, int64_t* n_ranked);
 
+/* Multiple-testing correction of whole p-value tracks on the device: Benjamini-Hochberg or Benjamini-Yekutieli adjusted
+ * p-values (q-values), one family per track, each of the `ntracks` (1..8) tracks on its own.  The reference has no such step;
+ * the definition is that of scipy.stats.false_discovery_control on the VALID elements of a track, where an element is valid iff
+ * 0 <= p <= 1 (so NaN — the p-values of positions flagged TOO_LARGE / T_NAN / NONFINITE — is not): with m valid elements
+ * p_(1) <= ... <= p_(m), a_i = fl(p_(i) * fl(m / i)), for BY a_i = fl(a_i * c_m) with c_m = sum_{k<=m} 1/k, and
+ * q_(i) = min(1, min_{j>=i} a_j), written at the element's own index; an invalid element gets q = NaN and takes no part.
+ * BH is bit-equal to scipy 1.15; BY is within 1e-14 relative (c_m is summed differently).  summary[t] (may be NULL): tested = m,
+ * excluded = n - m, rejected = #{q <= alpha}, p_crit = the largest valid p whose q <= alpha (NaN when nothing is rejected).
+ * Reads struct_size, device, stream and memspace of prm and nothing else.  The arrays `p` and `q_out` themselves are host
+ * memory; the tracks they point to and `summary` live where prm->memspace says; q_out[t] == p[t] (in place) is allowed.
+ * NMOD_MEM_DEVICE: everything is enqueued on prm->stream and the call returns WITHOUT synchronising (m, c_m and the summary
+ * stay on the device), so it can follow a detect call in a pipeline; scratch (about 24 bytes per element, tracks one after
+ * another) comes stream-ordered from the library's pool.  NMOD_MEM_HOST: copy in, run, copy back, synchronise.  n == 0 is
+ * NMOD_OK (summaries: zero counts, p_crit NaN).  NMOD_ERR_INVALID_ARG before any device work: n < 0 or n > 2^31 - 2, ntracks
+ * outside 1..8, a NULL track, an unknown method, alpha outside (0, 1]. */
+enum { NMOD_FDR_BH = 0, NMOD_FDR_BY = 1 };
+typedef struct nmod_fdr_summary { int64_t tested, excluded, rejected; double p_crit; } nmod_fdr_summary;
+int nmod_fdr_adjust(const nmod_params* prm, int64_t n, int32_t ntracks, const double* const* p,
+                    int32_t method, double alpha, double* const* q_out, nmod_fdr_summary* summary /* ntracks, may be NULL */);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -63,6 +63,14 @@ def last_dispatch_stats():
     return {n: int(getattr(st, n)) for n, _ in NmodDispatchStats._fields_ if n != 'reserved'}
 
 
+FDR_BH, FDR_BY = 0, 1
+FDR_BY_NAME = {'bh': FDR_BH, 'by': FDR_BY}
+
+
+class NmodFdrSummary(C.Structure):
+    _fields_ = [('tested', C.c_int64), ('excluded', C.c_int64), ('rejected', C.c_int64), ('p_crit', C.c_double)]
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -110,6 +118,8 @@ _SIGNATURES = {
     'nmod_rank_order': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     'nmod_region_rank': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_char, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    'nmod_fdr_adjust': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_double,
+                                  C.POINTER(C.c_void_p), C.c_void_p]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -54,6 +54,11 @@ def build_parser():
     d.add_argument('--deepCoverage', type=int, default=0, choices=[0, 1],
                    help='1: test positions with a group beyond 65 535 samples (amplicon / plasmid runs) on the deep form '
                    'instead of reporting NaN for them (moptions[\'nmod_deep\'])')
+    d.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'],
+                   help='bh / by: Benjamini-Hochberg / Benjamini-Yekutieli q-values of the p-value tracks, one family per track over '
+                   'all tested positions, written to <FileID>_sign_test_fdr.txt (moptions[\'nmod_fdr\'])')
+    d.add_argument('--fdrAlpha', type=float, default=0.05, help='level of the rejected count and p_crit that --fdr reports '
+                   '(moptions[\'nmod_fdr_alpha\'])')
     d.add_argument('--fast5Reader', default='', help="module:function used to read one resquiggled read file, path -> "
                    "(mapped_chrom, mapped_start, mapped_strand, norm_mean[], base[]) | None; default: the h5py reader of "
                    "nanomod_amd.fast5_ingest (Events table + Alignment attributes, myFast5.py:92-126)")
@@ -230,7 +235,8 @@ def select_positions_device(a, log=print):
 
 def nmod_options(a):
     """The moptions keys of this build (detect.mtest2) that the command line sets."""
-    return {'nmod_device': a.device, 'nmod_seed': a.seed, 'nmod_deep': int(a.deepCoverage)}
+    return {'nmod_device': a.device, 'nmod_seed': a.seed, 'nmod_deep': int(a.deepCoverage),
+            'nmod_fdr': '' if getattr(a, 'fdr', 'none') == 'none' else a.fdr, 'nmod_fdr_alpha': float(getattr(a, 'fdrAlpha', 0.05))}
 
 
 def run_detect(a, log=print):
@@ -273,10 +279,20 @@ def run_detect(a, log=print):
     if method != 'ks' and nb == 0:                                                     # myDetect.py:413
         res['comb_st'], res['comb_p'] = res['ks_d'].copy(), res['ks_p'].copy()
     os.makedirs(a.outFolder, exist_ok=True)
+    opts = nmod_options(a)
+    fdr = None
+    if opts['nmod_fdr']:                                                               # q-values of the table's p-value tracks
+        fdr, fdr_summary = detect.fdr_tracks(res, method != 'ks' and nb >= 0, opts['nmod_fdr'], opts['nmod_fdr_alpha'], a.device)
+        if a.outLevel <= detect.OUTPUT_INFO:
+            for name, s in fdr_summary.items():
+                log('FDR %s %s alpha=%g: tested %d excluded %d rejected %d p_crit %.3E'
+                    % (opts['nmod_fdr'], name, opts['nmod_fdr_alpha'], s['tested'], s['excluded'], s['rejected'], s['p_crit']))
     if a.SaveTest:
         with_comb = nb > 0 and method != 'ks'                                          # myDetect.py:533
         path = os.path.join(a.outFolder, a.FileID + '_sign_test.txt')
         write_sign_test(path, meta, res, with_comb)
+        if fdr is not None:
+            detect.write_sign_test_fdr(os.path.join(a.outFolder, a.FileID + '_sign_test_fdr.txt'), meta, fdr)
         if a.outLevel <= detect.OUTPUT_ERROR:
             log('Test data is saved in', path)
         if a.mstd != 0:

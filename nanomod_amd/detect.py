@@ -14,6 +14,8 @@ Same names, argument meaning and error behaviour as
 of this build: 'nmod_device', 'nmod_seed', 'nmod_strict', 'nmod_quiet', 'nmod_deep' (1: groups beyond 65 535 samples on the deep form).
 Keys written: 'sign_test', 'sorted_sign_test', optionally 'sign_test_mstd', 'nmod_flagged' (positions flagged TOO_LARGE / NONFINITE; 'nmod_strict' raises),
 plus 'sign_test_arrays' (the same numbers as numpy arrays, an addition).
+'nmod_fdr' ('bh' / 'by', with 'nmod_fdr_alpha', 0.05): q-values of the table's p-value tracks in 'sign_test_fdr' ('mwu_q', 't_q',
+'ks_q', 'comb_q'), their summaries in 'nmod_fdr_summary', and save_test also writes <FileID>_sign_test_fdr.txt.
 """
 from __future__ import annotations
 
@@ -552,6 +554,37 @@ def downsample_update(res, sig0, off0, sig1, off1, rid, strands, coverages, *, i
     return flag
 
 
+FDR_TRACKS = (('mwu_p', 'mwu_q'), ('t_p', 't_q'), ('ks_p', 'ks_q'), ('comb_p', 'comb_q'))
+
+
+def _fdr_option(moptions):
+    m = moptions.get('nmod_fdr', '') or ''
+    if m not in ('', 'bh', 'by'):
+        raise ValueError("moptions['nmod_fdr'] must be '', 'bh' or 'by', not %r" % (m,))
+    return m
+
+
+def fdr_tracks(res, with_comb, method, alpha=0.05, device=0):
+    """q-values of the table's p-value tracks (mwu_p, t_p, ks_p, and comb_p iff with_comb) in one nmod_fdr_adjust call.
+    Returns ({'mwu_q': ..., 't_q': ..., 'ks_q': ...[, 'comb_q': ...]} float64 arrays in record order, {track name: summary dict})."""
+    pairs = [pq for pq in FDR_TRACKS if pq[0] != 'comb_p' or with_comb]
+    qs, summ = engine.fdr_adjust_host([res[p] for p, _ in pairs], method=method, alpha=alpha, device=device)
+    return {q: a for (_, q), a in zip(pairs, qs)}, {p: s for (p, _), s in zip(pairs, summ)}
+
+
+def write_sign_test_fdr(path, meta, fdr):
+    """<FileID>_sign_test_fdr.txt: per position the first four fields of its _sign_test.txt line (chromosome, strand, 1-based
+    position, base), then ' %.3E' per q in the order mwu, t, ks, comb (Python's spelling of nan)."""
+    cols = [np.asarray(fdr[q], dtype=np.float64).tolist() for _, q in FDR_TRACKS if q in fdr]
+    fmt = '%s %s %d %s' + ' %.3E' * len(cols) + '\n'
+    names = [str(n) for n in meta['names']]
+    chrom = [names[i] for i in np.asarray(meta['chrom_id']).tolist()]
+    strand, base = (list(engine._first_chars(meta[k]).decode()) for k in ('strand', 'base'))      # as the table prints them
+    pos = (np.asarray(meta['pos'], dtype=np.int64) + 1).tolist()
+    with open(path, 'w') as f:
+        f.writelines(fmt % ((c, s, p, b) + qs) for c, s, p, b, qs in zip(chrom, strand, pos, base, zip(*cols)))
+
+
 def mtest2(moptions):
     print("Start sorting")
     engine.warm_up(moptions.get('nmod_device', 0))          # the HIP start-up runs beside the host-side preparation
@@ -594,6 +627,11 @@ def mtest2(moptions):
     with_comb = not method == "ks" and nb >= 0
     if with_comb and nb == 0:                                                                     # myDetect.py:413: the KS tuple itself
         res['comb_st'], res['comb_p'] = res['ks_d'], res['ks_p']
+    # moptions['nmod_fdr'] ('bh' / 'by'; '' = off, the default): Benjamini-Hochberg / -Yekutieli q-values of the p-value tracks the
+    # table prints, one family per track over all tested positions (nmod_fdr_adjust); the reference has no such step
+    fdr_method = _fdr_option(moptions)
+    if fdr_method:
+        moptions['sign_test_fdr'], moptions['nmod_fdr_summary'] = fdr_tracks(res, with_comb, fdr_method, float(moptions.get('nmod_fdr_alpha', 0.05)), dev)
     sign_test = SignTestRecords(meta, res, with_comb)
     moptions['sign_test'] = sign_test
     moptions['sign_test_arrays'] = res
@@ -644,6 +682,8 @@ def save_test(moptions):
     else:
         meta, res = _arrays_from_records(recs, with_comb)
     engine.write_sign_test_host(txtfile, meta, res, with_comb)
+    if _fdr_option(moptions) and 'sign_test_fdr' in moptions:
+        write_sign_test_fdr(moptions['outFolder'] + '/' + moptions["FileID"] + '_sign_test_fdr.txt', meta, moptions['sign_test_fdr'])
     if not moptions.get('mstd', 0) == 0:
         with open(moptions['outFolder'] + '/' + moptions["FileID"] + '_meanstd.cvs', 'w') as mw:
             for c, st, p, b in zip(meta['chrom'].tolist(), meta['strand'].tolist(), meta['pos'].tolist(), meta['base'].tolist()):

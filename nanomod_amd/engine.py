@@ -169,6 +169,47 @@ def argsort_device(key):
     return order.to(torch.int64)
 
 
+FDR_SUMMARY_FIELDS = ('tested', 'excluded', 'rejected', 'p_crit')
+
+
+def _fdr_method(method):
+    if isinstance(method, str):
+        if method not in L.FDR_BY_NAME:
+            raise ValueError("fdr method must be 'bh' or 'by', not %r" % (method,))
+        return L.FDR_BY_NAME[method]
+    return int(method)
+
+
+def fdr_adjust_host(tracks, method='bh', alpha=0.05, device=0):
+    """Benjamini-Hochberg ('bh') or Benjamini-Yekutieli ('by') q-values of whole p-value tracks (nmod_fdr_adjust), one family per
+    track: a float64 array or a list of up to eight of equal length.  An element outside [0, 1] (NaN included) gets q = NaN and
+    is left out of the family.  Returns (list of q arrays, list of summary dicts: tested, excluded, rejected, p_crit)."""
+    lib = L.load()
+    if isinstance(tracks, np.ndarray) and tracks.ndim == 1:
+        tracks = [tracks]
+    ps = [np.ascontiguousarray(t, dtype=np.float64) for t in tracks]
+    n = ps[0].shape[0] if ps else 0
+    if any(t.ndim != 1 or t.shape[0] != n for t in ps):
+        raise ValueError('fdr_adjust_host: the tracks must be one-dimensional and of one length')
+    qs = [np.empty(n, dtype=np.float64) for _ in ps]
+    nt = len(ps)
+    parr = (C.c_void_p * max(nt, 1))(*[t.ctypes.data for t in ps])
+    qarr = (C.c_void_p * max(nt, 1))(*[t.ctypes.data for t in qs])
+    summ = (L.NmodFdrSummary * max(nt, 1))()
+    prm = L.make_params(device=device, memspace=L.MEM_HOST)
+    rc = lib.nmod_fdr_adjust(C.byref(prm), n, nt, parr, _fdr_method(method), float(alpha), qarr, C.cast(summ, C.c_void_p))
+    L.check(rc, 'nmod_fdr_adjust')
+    return qs, [{f: getattr(summ[t], f) for f in FDR_SUMMARY_FIELDS} for t in range(nt)]
+
+
+def fdr_summary_dicts(summary):
+    """the device tensor of DeviceDetector.fdr (ntracks x 4 float64 words) as summary dicts; synchronises"""
+    raw = summary.cpu().numpy()
+    counts = raw.view(np.int64)
+    return [dict(tested=int(counts[t, 0]), excluded=int(counts[t, 1]), rejected=int(counts[t, 2]), p_crit=float(raw[t, 3]))
+            for t in range(raw.shape[0])]
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -341,6 +382,29 @@ class DeviceDetector:
                                         ptr(run_id), ws.data_ptr(), need, C.byref(o))
         L.check(rc, 'nmod_detect_batch')
         return res
+
+    def fdr(self, res, tracks=('comb_p',), method='bh', alpha=0.05, out=None):
+        """q-values of p-value tracks of a run() result (or of any dict of float64 CUDA tensors of one length), enqueued on the
+        current stream without synchronising (nmod_fdr_adjust, NMOD_MEM_DEVICE).  Returns (list of q tensors in `tracks` order, a
+        float64 CUDA tensor of ntracks x 4 words holding each track's nmod_fdr_summary: tested, excluded, rejected as int64 bit
+        images and p_crit; engine.fdr_summary_dicts reads it).  A track that `res` lacks raises KeyError.  out: a dict of
+        tensors to write q into (a track's own tensor for in place)."""
+        torch = self.torch
+        ps = [res[name] for name in tracks]                         # KeyError for a track the run did not produce
+        for t in ps:
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and t.numel() == ps[0].numel()):
+                raise ValueError('fdr: tracks must be contiguous float64 CUDA vectors of one length')
+        n = ps[0].numel() if ps else 0
+        dev = 'cuda:%d' % self.device
+        qs = [out[name] if out is not None else torch.empty(n, dtype=torch.float64, device=dev) for name in tracks]
+        nt = len(ps)
+        summary = torch.empty((max(nt, 1), 4), dtype=torch.float64, device=dev)
+        parr = (C.c_void_p * max(nt, 1))(*[t.data_ptr() for t in ps])
+        qarr = (C.c_void_p * max(nt, 1))(*[t.data_ptr() for t in qs])
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        rc = self.lib.nmod_fdr_adjust(C.byref(prm), n, nt, parr, _fdr_method(method), float(alpha), qarr, summary.data_ptr())
+        L.check(rc, 'nmod_fdr_adjust')
+        return qs, summary
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
