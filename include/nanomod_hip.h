@@ -396,6 +396,42 @@ typedef struct nmod_fdr_summary { int64_t tested, excluded, rejected; double p_c
 int nmod_fdr_adjust(const nmod_params* prm, int64_t n, int32_t ntracks, const double* const* p,
                     int32_t method, double alpha, double* const* q_out, nmod_fdr_summary* summary /* ntracks, may be NULL */);
 
+/* Per-position modified fraction: a two-component normal mixture fitted by EM on the device (K8; the reference has no such step —
+ * its simulations mix modified and unmodified reads at known shares, mySimulate.py --Percentages).  One group is the reference
+ * ("unmodified") group R, the other the mixed group Y: mix_group 0 = sig0 is mixed, 1 = sig1 is.  Samples as doubles (float32
+ * up-cast, int16 k / 1000.0, float64 as is).  Per position mu = mean(R), s2 = var(R) (ddof = 0), s = sqrt(s2), n = |Y|,
+ * d = mean(Y) - mu, and the model y ~ (1 - pi) N(mu, s2) + pi N(m, v) with v == s2 (NMOD_MIX_EQUAL_VAR) or v free and floored at
+ * s2 / 16 (NMOD_MIX_FREE_VAR).  Start pi = 0.5, m = mu + 2 d, v = s2; iteration k = 1, 2, ...:
+ *   t_i = ln((1 - pi) / pi) + 1/2 ln(v / s2) + (y_i - m)^2 / (2 v) - (y_i - mu)^2 / (2 s2)        r_i = 1 / (1 + exp(t_i))
+ *   W = sum r_i,  pi' = W / n,  m' = sum r_i y_i / W,  free model: v' = max(sum r_i (y_i - m')^2 / W, s2 / 16)
+ *   delta = max(|pi' - pi|, |m' - m| / s [, |sqrt(v') - sqrt(v)| / s]);  take the primed values
+ * and stop when delta <= tol (tol > 0) or k == max_iter (1 .. 10 000); tol == 0 never stops early.  With the final parameters and
+ * one more evaluation of t_i: llr = 2 sum_i [ln(1 - pi) + softplus(-t_i)], twice the log-likelihood gain over "all of Y is
+ * unmodified", and resp = r_i per read.  llr is a SCORE: the null pi = 0 lies on the boundary of the parameter space with m
+ * unidentified, so no chi-square law applies and no p-value is attached.
+ * Outputs, npos elements each, a NULL member skipped: pi, mu_mod (= m), sd_mod (= sqrt v), llr, iters (iterations run), status
+ * (NMOD_MIX_* bits below); resp (optional): float32 in the mixed group's own sample layout (its CSR offsets or stride).
+ *   NMOD_MIX_NOT_CONVERGED  max_iter iterations ran and the last delta was above tol; the estimates are written
+ *   NMOD_MIX_DEGENERATE     |R| < 2, |Y| < 2, s2 == 0 (every sample of R equal), a non-finite sample, or W underflowed to 0: NaN outputs, iters 0, NaN resp
+ *   NMOD_MIX_SKIPPED        the gate left the position out: NaN outputs and resp
+ *   NMOD_MIX_VAR_FLOORED    the variance floor was active in the last iteration
+ *   NMOD_MIX_TOO_LARGE      a group beyond NMOD_MAX_DEEP: NaN outputs and resp
+ * Gate: gate (npos doubles, may be NULL = every position) and gate_max: position i is computed iff gate[i] <= gate_max (NaN
+ * compares false) — typically gate = the q track of nmod_fdr_adjust and gate_max = alpha, on the same stream, no host round trip.
+ * Reads struct_size, device, stream, memspace, dtype, stride0 / stride1 of prm and nothing else; a group is CSR when its offsets
+ * are given, else fixed stride.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream and the call returns WITHOUT
+ * synchronising; scratch (12 bytes per position) comes stream-ordered from the library's pool.  NMOD_MEM_HOST: copy in, run, copy
+ * back, synchronise (one staged copy, not the pipelined host entry).  npos == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG before any
+ * device work: mix_group not 0 / 1, an unknown model, max_iter outside 1 .. 10 000, tol negative or not finite, npos < 0 or
+ * beyond 2^32 - 2, out NULL, a NULL signal array with npos > 0, a group with neither offsets nor a stride, an unknown dtype,
+ * host offsets that decrease.  A position's results are the same bits whatever else is in the batch, in CSR or stride form. */
+enum { NMOD_MIX_EQUAL_VAR = 0, NMOD_MIX_FREE_VAR = 1 };
+enum { NMOD_MIX_NOT_CONVERGED = 1, NMOD_MIX_DEGENERATE = 2, NMOD_MIX_SKIPPED = 4, NMOD_MIX_VAR_FLOORED = 8, NMOD_MIX_TOO_LARGE = 16 };
+typedef struct nmod_mix_out { double *pi, *mu_mod, *sd_mod, *llr; int32_t* iters; uint8_t* status; float* resp; } nmod_mix_out;
+int nmod_mix_fraction(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0, const void* sig1, const int64_t* off1,
+                      int32_t mix_group, int32_t model, int32_t max_iter, double tol,
+                      const double* gate, double gate_max, const nmod_mix_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -71,6 +71,16 @@ class NmodFdrSummary(C.Structure):
     _fields_ = [('tested', C.c_int64), ('excluded', C.c_int64), ('rejected', C.c_int64), ('p_crit', C.c_double)]
 
 
+MIX_EQUAL_VAR, MIX_FREE_VAR = 0, 1
+MIX_BY_NAME = {'equal': MIX_EQUAL_VAR, 'free': MIX_FREE_VAR}
+MIX_NOT_CONVERGED, MIX_DEGENERATE, MIX_SKIPPED, MIX_VAR_FLOORED, MIX_TOO_LARGE = 1, 2, 4, 8, 16
+MIX_FIELDS = ('pi', 'mu_mod', 'sd_mod', 'llr')
+
+
+class NmodMixOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in MIX_FIELDS] + [('iters', C.c_void_p), ('status', C.c_void_p), ('resp', C.c_void_p)]
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -120,6 +130,8 @@ _SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_char, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
     'nmod_fdr_adjust': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_double,
                                   C.POINTER(C.c_void_p), C.c_void_p]),
+    'nmod_mix_fraction': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_double, C.c_void_p, C.c_double, C.POINTER(NmodMixOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -59,6 +59,16 @@ def build_parser():
                    'all tested positions, written to <FileID>_sign_test_fdr.txt (moptions[\'nmod_fdr\'])')
     d.add_argument('--fdrAlpha', type=float, default=0.05, help='level of the rejected count and p_crit that --fdr reports '
                    '(moptions[\'nmod_fdr_alpha\'])')
+    d.add_argument('--mixFraction', default='none', choices=['none', 'equal', 'free'],
+                   help='equal / free: the modified fraction of the mixed group per position by a two-component EM (the modified reads '
+                   'share the variance of the unmodified ones, or have their own), written to <FileID>_sign_test_mix.txt; with --fdr only '
+                   'for the positions it rejects at --fdrAlpha (moptions[\'nmod_mix\']).  The llr column is a score without a p-value')
+    d.add_argument('--mixGroup', type=int, default=2, choices=[1, 2],
+                   help='which group is the mixture: 1 = --wrkBase1, 2 = --wrkBase2; the other is the unmodified reference '
+                   '(moptions[\'nmod_mix_group\'])')
+    d.add_argument('--mixMaxIter', type=int, default=200, help='EM iterations at most, 1 .. 10000 (moptions[\'nmod_mix_max_iter\'])')
+    d.add_argument('--mixTol', type=float, default=1e-6, help='EM stops when no parameter moved by more than this; 0 = always run '
+                   '--mixMaxIter (moptions[\'nmod_mix_tol\'])')
     d.add_argument('--fast5Reader', default='', help="module:function used to read one resquiggled read file, path -> "
                    "(mapped_chrom, mapped_start, mapped_strand, norm_mean[], base[]) | None; default: the h5py reader of "
                    "nanomod_amd.fast5_ingest (Events table + Alignment attributes, myFast5.py:92-126)")
@@ -102,6 +112,10 @@ def validate(a):
             neighbors = (a.window - 1) // 2
             a.roi['start_pos'] = max(a.roi['Pos'] - neighbors, 0)
             a.roi['end_pos'] = a.roi['Pos'] + neighbors
+    if not 1 <= getattr(a, 'mixMaxIter', 200) <= 10000:
+        errs.append('Error: --mixMaxIter should be in 1 .. 10000')
+    if not 0.0 <= getattr(a, 'mixTol', 1e-6) < float('inf'):
+        errs.append('Error: --mixTol should be finite and not negative')
     for f in (a.wrkBase1, a.wrkBase2):
         if not (os.path.isfile(f) or os.path.isdir(f)):
             errs.append('Error: input %s does not exist' % f)
@@ -236,7 +250,9 @@ def select_positions_device(a, log=print):
 def nmod_options(a):
     """The moptions keys of this build (detect.mtest2) that the command line sets."""
     return {'nmod_device': a.device, 'nmod_seed': a.seed, 'nmod_deep': int(a.deepCoverage),
-            'nmod_fdr': '' if getattr(a, 'fdr', 'none') == 'none' else a.fdr, 'nmod_fdr_alpha': float(getattr(a, 'fdrAlpha', 0.05))}
+            'nmod_fdr': '' if getattr(a, 'fdr', 'none') == 'none' else a.fdr, 'nmod_fdr_alpha': float(getattr(a, 'fdrAlpha', 0.05)),
+            'nmod_mix': '' if getattr(a, 'mixFraction', 'none') == 'none' else a.mixFraction, 'nmod_mix_group': int(getattr(a, 'mixGroup', 2)),
+            'nmod_mix_max_iter': int(getattr(a, 'mixMaxIter', 200)), 'nmod_mix_tol': float(getattr(a, 'mixTol', 1e-6))}
 
 
 def run_detect(a, log=print):
@@ -287,12 +303,26 @@ def run_detect(a, log=print):
             for name, s in fdr_summary.items():
                 log('FDR %s %s alpha=%g: tested %d excluded %d rejected %d p_crit %.3E'
                     % (opts['nmod_fdr'], name, opts['nmod_fdr_alpha'], s['tested'], s['excluded'], s['rejected'], s['p_crit']))
+    mix = None
+    if opts['nmod_mix']:                                                               # modified fraction per (rejected) position
+        if not isinstance(sig0, np.ndarray):                                  # (the device route's tensors: this step reads host rows)
+            sig0, off0, sig1, off1 = (x.cpu().numpy() for x in (sig0, off0, sig1, off1))
+        gate = None if fdr is None else fdr['comb_q' if (method != 'ks' and nb >= 0) else 'ks_q']
+        mix = detect.mix_tracks(sig0, off0, sig1, off1, opts['nmod_mix'], group=opts['nmod_mix_group'], max_iter=opts['nmod_mix_max_iter'],
+                                tol=opts['nmod_mix_tol'], gate=gate, gate_max=opts['nmod_fdr_alpha'], device=a.device)
+        if a.outLevel <= detect.OUTPUT_INFO:
+            done = ~((mix['status'] & L.MIX_SKIPPED) != 0)
+            log('MIX %s group %d: computed %d of %d positions, not converged %d, degenerate %d'
+                % (opts['nmod_mix'], opts['nmod_mix_group'], int(done.sum()), npos, int(((mix['status'] & L.MIX_NOT_CONVERGED) != 0).sum()),
+                   int(((mix['status'] & L.MIX_DEGENERATE) != 0).sum())))
     if a.SaveTest:
         with_comb = nb > 0 and method != 'ks'                                          # myDetect.py:533
         path = os.path.join(a.outFolder, a.FileID + '_sign_test.txt')
         write_sign_test(path, meta, res, with_comb)
         if fdr is not None:
             detect.write_sign_test_fdr(os.path.join(a.outFolder, a.FileID + '_sign_test_fdr.txt'), meta, fdr)
+        if mix is not None:
+            detect.write_sign_test_mix(os.path.join(a.outFolder, a.FileID + '_sign_test_mix.txt'), meta, mix)
         if a.outLevel <= detect.OUTPUT_ERROR:
             log('Test data is saved in', path)
         if a.mstd != 0:

@@ -585,6 +585,39 @@ def write_sign_test_fdr(path, meta, fdr):
         f.writelines(fmt % ((c, s, p, b) + qs) for c, s, p, b, qs in zip(chrom, strand, pos, base, zip(*cols)))
 
 
+MIX_COLUMNS = ('pi', 'mu_mod', 'sd_mod', 'llr', 'iters', 'status')
+
+
+def _mix_option(moptions):
+    m = moptions.get('nmod_mix', '') or ''
+    if m not in ('', 'equal', 'free'):
+        raise ValueError("moptions['nmod_mix'] must be '', 'equal' or 'free', not %r" % (m,))
+    return m
+
+
+def mix_tracks(sig0, off0, sig1, off1, model, *, group=2, max_iter=200, tol=1e-6, gate=None, gate_max=0.05, device=0):
+    """The per-position modified fraction of the tested rows (nmod_mix_fraction): `group` 1 / 2 names the mixed group the way
+    --wrkBase1 / --wrkBase2 do, the other one is the unmodified reference.  Returns the dict of engine.mix_fraction_host."""
+    if group not in (1, 2):
+        raise ValueError("moptions['nmod_mix_group'] must be 1 or 2, not %r" % (group,))
+    return engine.mix_fraction_host(sig0, off0, sig1, off1, mix_group=group - 1, model=model, max_iter=max_iter, tol=tol, gate=gate,
+                                    gate_max=gate_max, device=device)
+
+
+def write_sign_test_mix(path, meta, mix):
+    """<FileID>_sign_test_mix.txt: per computed position the first four fields of its _sign_test.txt line (chromosome, strand,
+    1-based position, base), then ' %.6f %.6f %.6f %.3f %d %d' = pi mu_mod sd_mod llr iters status; positions the gate left out
+    (NMOD_MIX_SKIPPED) are omitted.  llr is a score, not a test statistic with a p-value."""
+    names = [str(n) for n in meta['names']]
+    chrom = [names[i] for i in np.asarray(meta['chrom_id']).tolist()]
+    strand, base = (list(engine._first_chars(meta[k]).decode()) for k in ('strand', 'base'))      # as the table prints them
+    pos = (np.asarray(meta['pos'], dtype=np.int64) + 1).tolist()
+    cols = [np.asarray(mix[k]).tolist() for k in MIX_COLUMNS]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %s %.6f %.6f %.6f %.3f %d %d\n' % ((c, s, p, b) + row)
+                     for c, s, p, b, row in zip(chrom, strand, pos, base, zip(*cols)) if not row[5] & L.MIX_SKIPPED)
+
+
 def mtest2(moptions):
     print("Start sorting")
     engine.warm_up(moptions.get('nmod_device', 0))          # the HIP start-up runs beside the host-side preparation
@@ -632,6 +665,17 @@ def mtest2(moptions):
     fdr_method = _fdr_option(moptions)
     if fdr_method:
         moptions['sign_test_fdr'], moptions['nmod_fdr_summary'] = fdr_tracks(res, with_comb, fdr_method, float(moptions.get('nmod_fdr_alpha', 0.05)), dev)
+    # moptions['nmod_mix'] ('equal' / 'free'; '' = off, the default): the modified fraction of the mixed group (nmod_mix_group, 1 or 2,
+    # default 2) per position by a two-component EM (nmod_mix_fraction); with nmod_fdr also set only the positions whose combined q
+    # (KS q without a combined track) is at most nmod_fdr_alpha are computed.  The reference has no such step
+    mix_model = _mix_option(moptions)
+    if mix_model:
+        gate = None
+        if fdr_method:
+            gate = moptions['sign_test_fdr']['comb_q' if with_comb else 'ks_q']
+        moptions['sign_test_mix'] = mix_tracks(sig0, off0, sig1, off1, mix_model, group=moptions.get('nmod_mix_group', 2),
+                                               max_iter=moptions.get('nmod_mix_max_iter', 200), tol=moptions.get('nmod_mix_tol', 1e-6),
+                                               gate=gate, gate_max=float(moptions.get('nmod_fdr_alpha', 0.05)), device=dev)
     sign_test = SignTestRecords(meta, res, with_comb)
     moptions['sign_test'] = sign_test
     moptions['sign_test_arrays'] = res
@@ -684,6 +728,8 @@ def save_test(moptions):
     engine.write_sign_test_host(txtfile, meta, res, with_comb)
     if _fdr_option(moptions) and 'sign_test_fdr' in moptions:
         write_sign_test_fdr(moptions['outFolder'] + '/' + moptions["FileID"] + '_sign_test_fdr.txt', meta, moptions['sign_test_fdr'])
+    if _mix_option(moptions) and 'sign_test_mix' in moptions:
+        write_sign_test_mix(moptions['outFolder'] + '/' + moptions["FileID"] + '_sign_test_mix.txt', meta, moptions['sign_test_mix'])
     if not moptions.get('mstd', 0) == 0:
         with open(moptions['outFolder'] + '/' + moptions["FileID"] + '_meanstd.cvs', 'w') as mw:
             for c, st, p, b in zip(meta['chrom'].tolist(), meta['strand'].tolist(), meta['pos'].tolist(), meta['base'].tolist()):

@@ -210,6 +210,74 @@ def fdr_summary_dicts(summary):
             for t in range(raw.shape[0])]
 
 
+def _mix_args(mix_group, model, max_iter, tol):
+    """the checked (mix_group, model id, max_iter, tol) of a mix call: ValueError for what the library would refuse"""
+    if isinstance(model, str):
+        if model not in L.MIX_BY_NAME:
+            raise ValueError("mix model must be 'equal' or 'free', not %r" % (model,))
+        model = L.MIX_BY_NAME[model]
+    if model not in (L.MIX_EQUAL_VAR, L.MIX_FREE_VAR):
+        raise ValueError('mix model must be 0 (equal variance) or 1 (free variance), not %r' % (model,))
+    if mix_group not in (0, 1):
+        raise ValueError('mix_group must be 0 (sig0 is the mixed group) or 1 (sig1 is), not %r' % (mix_group,))
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= 10000:
+        raise ValueError('max_iter must be an integer in 1 .. 10000, not %r' % (max_iter,))
+    tol = float(tol)
+    if not (tol >= 0.0) or tol == float('inf'):
+        raise ValueError('tol must be finite and >= 0, not %r' % (tol,))
+    return int(mix_group), int(model), int(max_iter), tol
+
+
+def mix_fraction_host(sig0, off0, sig1, off1, *, mix_group=1, model='equal', max_iter=200, tol=1e-6, gate=None, gate_max=0.05,
+                      want_resp=False, device=0, stride0=0, stride1=0):
+    """Per-position modified fraction by a two-component EM (nmod_mix_fraction, include/nanomod_hip.h) on host-resident rows:
+    one group is the reference ("unmodified") group, the other (mix_group: 0 = sig0, 1 = sig1) a mixture of unmodified reads and
+    reads at another level.  model 'equal' / 'free': the modified component shares the reference variance or has its own.
+    gate: a float64 track, position i is computed iff gate[i] <= gate_max (NaN: not), e.g. the q-values of fdr_adjust_host.
+    Returns a dict of numpy arrays: pi, mu_mod, sd_mod, llr (float64; llr is a score without a p-value), iters (int32), status
+    (uint8, L.MIX_* bits) and with want_resp `resp` (float32, the posterior of every read of the mixed group, in its layout)."""
+    lib = L.load()
+    mix_group, model, max_iter, tol = _mix_args(mix_group, model, max_iter, tol)
+    _join_warm_up(device)
+    sig0 = np.ascontiguousarray(sig0)
+    sig1 = np.ascontiguousarray(sig1)
+    if sig0.dtype != sig1.dtype or sig0.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('sig0/sig1 must both be float32, both int16 (milli-units) or both float64')
+    dtype = _dtype_code(sig0.dtype)
+    if off0 is not None:
+        npos = len(off0) - 1
+    elif off1 is not None:
+        npos = len(off1) - 1
+    else:
+        npos = sig0.shape[0] // stride0
+    off0 = None if off0 is None else np.ascontiguousarray(off0, dtype=np.int64)
+    off1 = None if off1 is None else np.ascontiguousarray(off1, dtype=np.int64)
+    _check_csr(off0, npos, 'off0')
+    _check_csr(off1, npos, 'off1')
+    for sig, off, stride, name in ((sig0, off0, stride0, 'sig0'), (sig1, off1, stride1, 'sig1')):
+        if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
+            raise ValueError('%s is shorter than its offsets / stride say' % name)
+    if gate is not None:
+        gate = np.ascontiguousarray(gate, dtype=np.float64)
+        if gate.shape != (npos,):
+            raise ValueError('gate must be float64[npos]')
+    res = {k: np.empty(npos, dtype=np.float64) for k in L.MIX_FIELDS}
+    res['iters'] = np.empty(npos, dtype=np.int32)
+    res['status'] = np.empty(npos, dtype=np.uint8)
+    if want_resp:
+        ysig, yoff, ystride = (sig1, off1, stride1) if mix_group == 1 else (sig0, off0, stride0)
+        res['resp'] = np.empty((int(yoff[-1]) if yoff is not None else npos * ystride) if npos else 0, dtype=np.float32)
+    out = L.NmodMixOut()
+    for k, a in res.items():
+        setattr(out, k, _np_ptr(a))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride0 if off0 is None else 0,
+                        stride1=stride1 if off1 is None else 0)
+    rc = lib.nmod_mix_fraction(C.byref(prm), npos, _np_ptr(sig0), _np_ptr(off0), _np_ptr(sig1), _np_ptr(off1), mix_group, model,
+                               max_iter, tol, _np_ptr(gate), float(gate_max), C.byref(out))
+    L.check(rc, 'nmod_mix_fraction')
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -405,6 +473,46 @@ class DeviceDetector:
         rc = self.lib.nmod_fdr_adjust(C.byref(prm), n, nt, parr, _fdr_method(method), float(alpha), qarr, summary.data_ptr())
         L.check(rc, 'nmod_fdr_adjust')
         return qs, summary
+
+    def mix(self, sig0, sig1, *, off0=None, off1=None, stride0=0, stride1=0, npos=None, mix_group=1, model='equal', max_iter=200,
+            tol=1e-6, gate=None, gate_max=0.05, want_resp=False, out=None):
+        """Per-position modified fraction (nmod_mix_fraction, NMOD_MEM_DEVICE) of rows described as in run(), enqueued on the
+        current stream without synchronising.  gate: a float64 CUDA track, position i is computed iff gate[i] <= gate_max.  Returns
+        a dict of CUDA tensors: pi, mu_mod, sd_mod, llr (float64), iters (int32), status (uint8, L.MIX_* bits), and with want_resp
+        `resp` (float32, one posterior per read of the mixed group, in its layout).  llr is a score: it has no p-value.
+
+        Tests, q-values and fractions of the rejected positions as one stream, nothing read on the host in between:
+
+            res = det.run(sig0, sig1, run_id, stride0=n, stride1=n, npos=npos)
+            (q,), summary = det.fdr(res, tracks=('comb_p',), method='bh', alpha=0.05)
+            mix = det.mix(sig0, sig1, stride0=n, stride1=n, npos=npos, gate=q, gate_max=0.05)
+        """
+        torch = self.torch
+        mix_group, model, max_iter, tol = _mix_args(mix_group, model, max_iter, tol)
+        dtype = self._dtype_of(sig0)
+        if self._dtype_of(sig1) != dtype:
+            raise ValueError('sig0 and sig1 must share a dtype')
+        if npos is None:
+            npos = (off0.numel() - 1) if off0 is not None else ((off1.numel() - 1) if off1 is not None else sig0.numel() // stride0)
+        dev = 'cuda:%d' % self.device
+        if gate is not None and not (gate.is_cuda and gate.dtype == torch.float64 and gate.is_contiguous() and gate.numel() == npos):
+            raise ValueError('mix: gate must be a contiguous float64 CUDA vector of npos elements')
+        res = out
+        if res is None:
+            res = {k: torch.empty(npos, dtype=torch.float64, device=dev) for k in L.MIX_FIELDS}
+            res['iters'] = torch.empty(npos, dtype=torch.int32, device=dev)
+            res['status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
+            if want_resp:
+                res['resp'] = torch.empty((sig1 if mix_group == 1 else sig0).numel(), dtype=torch.float32, device=dev)
+        o = L.NmodMixOut()
+        for k, t in res.items():
+            setattr(o, k, t.data_ptr())
+        prm = self._params(dtype, stride0 if off0 is None else 0, stride1 if off1 is None else 0, 0, 0)
+        ptr = lambda t: (t.data_ptr() if t is not None else None)
+        rc = self.lib.nmod_mix_fraction(C.byref(prm), npos, ptr(sig0), ptr(off0), ptr(sig1), ptr(off1), mix_group, model, max_iter,
+                                        tol, ptr(gate), float(gate_max), C.byref(o))
+        L.check(rc, 'nmod_mix_fraction')
+        return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
