@@ -283,10 +283,20 @@ __device__ __forceinline__ const float* ks_search_tops(const float* base, float 
   return all ? base + Lay::END : p;
 }
 
+// Maximum of two doubles that are known to be numbers (the callers' values are finite and >= 0): the bare instruction.
+// fmax() first quiets every operand whose origin the compiler cannot see — a lane exchange, a loop-carried value — with a
+// v_max_f64 v, v of its own, two instructions out of three in the reductions below.  The s_nop covers the two wait
+// states a DPP move needs after a VALU write of its source: the compiler does not count them across inline assembly.
+__device__ __forceinline__ double fmax_numbers(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 template <int LG>
-__device__ __forceinline__ double seg_allmax_f64(double v) {
-  v = fmax(v, dpp_f64_row(v, 0)); v = fmax(v, dpp_f64_row(v, 1)); v = fmax(v, dpp_f64_row(v, 2));
-  if constexpr (LG >= 16) v = fmax(v, dpp_f64_row(v, 3));
+__device__ __forceinline__ double seg_allmax_f64(double v) {      // v finite, >= 0
+  v = fmax_numbers(v, dpp_f64_row(v, 0)); v = fmax_numbers(v, dpp_f64_row(v, 1)); v = fmax_numbers(v, dpp_f64_row(v, 2));
+  if constexpr (LG >= 16) v = fmax_numbers(v, dpp_f64_row(v, 3));
   if constexpr (LG >= 32) v = fmax(v, xor16_f64(v));
   if constexpr (LG == 64) v = wave_max_f64(v);
   return v;
@@ -736,18 +746,34 @@ void ks_rank_kernel(RankStatsArgs args) {
       }
       best = (unsigned)max(max(hi, q - lo), 0);
     } else {
-      // general form with the run ends of S as masks
-      // Pads are +inf, so "s_{k-1} != s_k" alone marks the run ends: it holds at k = m and fails for k > m.
+      // general form.  Per bin k the two candidates are b_k = cumL(k-1)*m - k*q and a_k = cumU(k)*m - k*q, valid at
+      // the run ends of S.  Pads are +inf, so "s_{k-1} != s_k" alone marks the run ends: it holds at k = m and fails
+      // for k > m.  Three facts (any capacity, any key type: only the order of the keys and the counts enter) keep the
+      // masking to one select per bin:
+      //   * a_k >= b_k: cumU(k) = cumL(k-1) + cnt[k] - eq[k] and eq[k] <= cnt[k].  So the maximum over the valid
+      //     candidates needs only a_k, the minimum only b_k;
+      //   * b_k needs no mask for k <= m.  Inside a run (s_k = s_{k+1}) bin k is empty — no x has s_k < x <= s_{k+1} —
+      //     so cumL(k) = cumL(k-1) and b_{k+1} = b_k - q: along a run b falls strictly to its valid value at the run's
+      //     end.  An unmasked b_k is never the minimum and never equals -best.  For the pads (k > m) k*q is clamped
+      //     at m*q; cumL(k-1) = q there (every sample ranks at or below m), so their b_k is 0, the neutral value;
+      //   * a_k keeps its mask: where samples of Q sit on a run of S (eq > 0 at the run's start) the count cumU(k)
+      //     inside the run already holds them while k is still short of the run's end, and a_k can exceed every valid
+      //     candidate.  A masked a_k counts as 0 (the pads too: they are no run ends).
+      //   hi = max(0, a_0, max_k run_end_k ? a_k : 0),  lo = min(0, min_k b_k),  best = max(hi, -lo).
+      // A lane whose own max(hi, -lo) equals the position's best therefore holds a valid candidate that attains it,
+      // which is what the float-form pass below relies on.
       int cl = (int)(cum >> 16);                                    // cumL(k-1) entering bin k = e0 + 1
       // k = 0: (cumU(0), 0), cumU(0) = the samples below key 0 = cntL[0] - eq[0]
       int hi = (gl == 0) ? __mul24((int)(h0 >> 16) - (int)(h0 & 0xffffu), m) : 0, lo = 0;
-      int nkq = -__mul24(e0, q);
+      const int nkq_min = -__mul24(m, q);                           // (24-bit operands: m <= 2 048, q <= 65 535)
+      int nkq = -__mul24(e0, q);                                    // (clamped from the first bin on)
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const float up = (r == R - 1) ? s_next : s_own[r + 1];
         const bool run_end = s_own[r] != up;
-        nkq -= q;
+        nkq = max(nkq - q, nkq_min);
         const int cand_b = __mul24(cl, m) + nkq;                   // v = the S value with upper rank k: cumL(k-1)*m - k*q
+        lo = min(lo, cand_b);
         const int clp = cl;
         cl += (int)(h[r] >> 16);                                   // cumL(k)
         const int cu = cl - (int)(h[r] & 0xffffu);                 // cumU(k) = cumL(k) - #{x = s_{k+1}}
@@ -757,9 +783,7 @@ void ks_rank_kernel(RankStatsArgs args) {
           w16[0] = (unsigned short)cu; w16[1] = (unsigned short)clp;
         }
         const int cand_a = __mul24(cu, m) + nkq;                   // v = the largest sample below s_{k+1}: cumU(k)*m - k*q
-        const int ca = run_end ? cand_a : 0, cb = run_end ? cand_b : 0;
-        hi = max(hi, max(ca, cb));
-        lo = min(lo, min(ca, cb));
+        hi = max(hi, run_end ? cand_a : 0);
       }
       best = (unsigned)max(hi, -lo);
     }
@@ -789,35 +813,77 @@ void ks_rank_kernel(RankStatsArgs args) {
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
+      // Per trip only the integer filter runs: which of the examined bins hold a candidate that reaches `best`.  A lane
+      // parks such a candidate as one word, k << 16 | c (c <= 65 535, 1 <= k <= 2 048: never 0), and the fp64 form
+      // |fl(k/m) - fl(c/q)| is evaluated once, after the last trip — all lanes paid for it on every trip before, while one
+      // or two lanes of a position hold such a candidate.  A lane that finds a second candidate while one is parked
+      // (another trip's, or both candidates of one bin) makes the wave evaluate the parked ones first.  The candidates
+      // evaluated are the same set as trip by trip, and a maximum does not depend on the order.
+      // The lanes' findings are kept as wave masks built from ballots of plain compares, so that the tests for the
+      // (almost always empty) collisions are scalar instructions: `parked` = the lanes whose word is not 0.
+      unsigned pw = 0u;
+      unsigned long long parked = 0ull;
+      auto flush = [&]() {
+        const double d = fabs(hist_exact_quot((int)(pw >> 16), dm, rm) - hist_exact_quot((int)(pw & 0xffffu), dq, rq));
+        dmax = (d > dmax) ? d : dmax;          // (numbers: the compare is the maximum; a lane with nothing parked has d = 0)
+        pw = 0u; parked = 0ull;
+      };
+      const int ibest = (int)best;
+      const int nq = -q;
+      // the table word of bin k: cumL(k-1) << 16 | cumU(k) from the general evaluation, cumL(k) from the short one, whose
+      // cumL(k-1) is word k - 1.  `slow` is wave-uniform: the shift and the mask are scalars
+      const int t_shift = slow ? 16 : 0;
+      const unsigned t_mask = slow ? 0xffffu : 0xffffffffu;
 #pragma unroll 1
-      while (__ballot(mine != (Mine)0) != 0ull) {
+      for (;;) {
+        const unsigned long long m_act = __ballot(mine != (Mine)0);
+        if (m_act == 0ull) break;
         const bool act = mine != (Mine)0;
-        const int hl = act ? (__ffsll((long long)mine) - 1) : 0;              // the lane of this position whose bins are examined
+        int hl = act ? (__ffsll((long long)mine) - 1) : 0;                    // the lane of this position whose bins are examined
+        asm volatile("" : "+v"(hl));                                         // (one select here, not one per use)
         mine &= mine - (Mine)1;
-#pragma unroll
+#pragma unroll 1
         for (int j = 0; j < BPL; ++j) {
           const int rr = gl * BPL + j;                                        // bin k = hl * R + rr + 1
-          const bool in = act && rr < R;
+          // (an idle lane of the trip has hl = 0: its addresses are those of column 0, its findings are masked by m_act)
+          const bool in = rr < R;
           const int k = hl * R + rr + 1;
           // key k - 1 / word k - 1 = row rr of column hl; key / word k = row rr + 1 of column hl, or row 0 of column hl + 1
           const int wp = in ? rr * ROW + hl : 0;
           const int wk = in ? ((rr + 1 < R) ? (rr + 1) * ROW + hl : hl + 1) : 0;
           const unsigned tp = hist[wp], tk = hist[wk];
-          const bool run_end = keys[wp] != keys[wk];
-          const int clp = slow ? (int)(tk >> 16) : (int)tp;                   // cumL(k-1)
-          const int cu = slow ? (int)(tk & 0xffffu) : (int)tk;                // cumU(k)
-          const int nkq = -__mul24(k, q);
+          const float key_p = keys[wp], key_k = keys[wk];
+          const int clp = (int)((slow ? tk : tp) >> t_shift);                 // cumL(k-1)
+          const int cu = (int)(tk & t_mask);                                  // cumU(k)
+          const int nkq = __mul24(k, nq);
           const int cand_b = __mul24(clp, m) + nkq;                           // (cumL(k-1), k)
           const int cand_a = __mul24(cu, m) + nkq;                            // (cumU(k), k)
-          const bool hb = in && run_end && (unsigned)abs(cand_b) == best;
-          const bool ha = in && run_end && (unsigned)abs(cand_a) == best;
-          const double fk = hist_exact_quot(k, dm, rm);
-          const double db = fabs(fk - hist_exact_quot(clp, dq, rq));
-          const double da = fabs(fk - hist_exact_quot(cu, dq, rq));
-          dmax = hb ? fmax(dmax, db) : dmax;
-          dmax = ha ? fmax(dmax, da) : dmax;
+          // (the same as per-lane conditions for the selects)
+          const bool ok = act && in && key_p != key_k;                        // a run of S ends at k
+          const bool hb = ok && (cand_b == ibest || cand_b == -ibest);
+          // (an empty bin makes the two the same point, cumU(k) = cumL(k-1): parked once)
+          const bool ha = ok && (cand_a == ibest || cand_a == -ibest) && !(hb && cu == clp);
+          const unsigned kw = (unsigned)k << 16;
+          if constexpr (LG < 64) {
+            unsigned long long m_ok = m_act & __ballot(key_p != key_k);
+            if constexpr (BPL * LG != R) m_ok &= __ballot(rr < R);
+            const unsigned long long m_b = m_ok & (__ballot(cand_b == ibest) | __ballot(cand_b == -ibest));
+            const unsigned long long m_a = m_ok & (__ballot(cand_a == ibest) | __ballot(cand_a == -ibest)) & (~m_b | __ballot(cu != clp));
+            if ((m_b & parked) != 0ull) flush();
+            pw = hb ? (kw | (unsigned)clp) : pw; parked |= m_b;
+            if ((m_a & parked) != 0ull) flush();
+            pw = ha ? (kw | (unsigned)cu) : pw; parked |= m_a;
+          } else {
+            // (one position per wave: its sizes and `best` are scalars already, and the masks above would not fit the
+            // scalar registers next to them; the ballot of a combined condition costs two vector instructions here)
+            if (__ballot(hb && pw != 0u) != 0ull) flush();
+            pw = hb ? (kw | (unsigned)clp) : pw;
+            if (__ballot(ha && pw != 0u) != 0ull) flush();
+            pw = ha ? (kw | (unsigned)cu) : pw;
+          }
         }
       }
+      if ((LG < 64) ? (parked != 0ull) : (__ballot(pw != 0u) != 0ull)) flush();
       dmax = seg_allmax_f64<LG>(dmax);
     }
     if (valid && gl == 0) {

@@ -891,6 +891,10 @@ void rank_hist_kernel(RankStatsArgs args) {
       int cl = (int)(cum >> 16);                                             // cumL(k-1) entering bin k = e02 + 1
       // k = 0: (cumU(0), 0), cumU(0) = the samples below key 0 = cntL[0] - eq[0]
       int hi = (gl2 == 0) ? __mul24((int)(h0 >> 16) - (int)(h0 & 0xffffu), m) : 0, lo = 0;
+      // (the candidates as in ks_rank.hpp's general form, see the derivation there: (cumU(k), k) >= (cumL(k-1), k), so the
+      // maximum takes only the first — masked by the run end — and the minimum only the second, which needs no mask
+      // once k*q is clamped at m*q for the pads)
+      const int nkq_min = -__mul24(m, q);
       int nkq = -__mul24(e02, q);
       float kprev = keys[gl2];                                               // key e02
       constexpr int CH = (R >= 4) ? 4 : R;                                    // bins per chunk
@@ -914,9 +918,10 @@ void rank_hist_kernel(RankStatsArgs args) {
           const bool run_end = kprev != knext;
           kprev = knext;
           const int k = e02 + r + 1;
-          nkq -= q;
+          nkq = max(nkq - q, nkq_min);
           acc_l += (unsigned)cl;
           const int cand_b = __mul24(cl, m) + nkq;                           // (cumL(k-1), k)
+          lo = min(lo, cand_b);
           const unsigned wl = (unsigned)cl << 16;
           const int eqk = (int)(hr & 0xffffu);                               // samples of Q equal to key k (a run start, or 0)
           cl += (int)(hr >> 16);                                             // cumL(k)
@@ -924,9 +929,7 @@ void rank_hist_kernel(RankStatsArgs args) {
           const unsigned w = wl | (run_end ? 0x8000u : 0u) | (unsigned)cu;
           if (r < R - 1) hist[(r + 1) * ROW + gl2] = w; else hist[gl2 + 1] = w;
           const int cand_a = __mul24(cu, m) + nkq;                           // (cumU(k), k)
-          const int ca = run_end ? cand_a : 0, cb = run_end ? cand_b : 0;
-          hi = max(hi, max(ca, cb));
-          lo = min(lo, min(ca, cb));
+          hi = max(hi, run_end ? cand_a : 0);
           // the ties of the run of S that ends at k with the `brun` samples of Q equal to it: a wave-uniform branch,
           // taken for the few boundaries where some lane closes a tied run
           if (wave_ties && __ballot(run_end && brun != 0) != 0ull) {
