@@ -269,7 +269,14 @@ int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char*
 int nmod_trim_scratch(int32_t device);
 
 /* Replaces combin_pvalues / get_combin_pvalue on a whole KS track
- * (myDetect.py:373-414).  ks_d is only read when nb == 0 (:413). */
+ * (myDetect.py:373-414).  ks_d is only read when nb == 0 (:413).
+ * Conventions (the reference's, through numpy's IEEE arithmetic; pinned by tests/test_tails_gpu.py):
+ *   - a neighbour outside the track or in another run (run_id differs) is a pad, p = 1: a Stouffer window that touches a pad is
+ *     (Z, p) = (-inf, 1.0) exactly; to a Fisher window a pad contributes nothing;
+ *   - a NaN p makes (NaN, NaN) of exactly the windows of its own run that contain it;
+ *   - p = 0 gives (DBL_MAX, DBL_MIN) (m_max_float / m_min_float of (+inf, 0)); in a Stouffer window that also holds a pad or a
+ *     p = 1 the sum is (+inf) + (-inf): (NaN, NaN);
+ *   - comb_p is clamped to DBL_MIN from below, comb_st to DBL_MAX from above. */
 int nmod_combine_track(const nmod_params* prm, int64_t npos,
                        const double* ks_d, const double* ks_p, const int32_t* run_id,
                        double* comb_st, double* comb_p);
