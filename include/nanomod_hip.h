@@ -157,6 +157,11 @@ typedef struct nmod_params {
  * workspace size does not change); the host round trip is the one the large-position pass makes.  Without the flag a position
  * beyond NMOD_MAX_RANKED is NMOD_STATUS_TOO_LARGE as before; beyond NMOD_MAX_DEEP it is with the flag too. */
 #define NMOD_FLAG_DEEP 32
+/* Kernel-form switch for A/B measurements and parity tests; the numbers are the same bit for bit with and without it.  The
+ * persistent waves of the KS-only K1 kernel take a fixed, strided part of their items and draw the rest in small chunks from a
+ * per-launch counter, so that the waves of a launch end together (DESIGN_NOTES.md A.10).  With this flag every wave walks its
+ * equal, strided share as before (no counter, no atomic). */
+#define NMOD_FLAG_K1_STATIC_ITEMS 128
 
 /* Caller-allocated SoA outputs, npos elements each; a NULL member is skipped.
  * One (stat, p) pair per test = the tuples getKStest returns
@@ -175,6 +180,13 @@ typedef struct nmod_out {
 int nmod_abi_version(void);
 int nmod_device_count(void);                 /* number of HIP devices (0 if none) */
 const char* nmod_strerror(int rc);
+
+/* How a K1 launch of `items` work items on `waves` resident waves hands its items out (host arithmetic only, no device needed):
+ * plan[0] = strided rounds r — wave w takes items w + k * waves, k < r; plan[1] = first item handed out by chunk (r * waves);
+ * plan[2] = items per chunk c — chunk j holds items plan[1] + j * c .. + c - 1 (those below `items`), chunk w belongs to wave
+ * w and chunk waves + t to the wave that draws ticket t from the launch's counter; plan[3] = 1 when such tickets are drawn at
+ * all.  flags: NMOD_FLAG_K1_STATIC_ITEMS gives the plan of the strided walk (r = ceil(items / waves), nothing left to claim). */
+int nmod_item_claim_plan(int64_t items, int64_t waves, int32_t flags, int64_t* plan);
 
 /* Device scratch needed by nmod_detect_batch for `npos` positions (bytes). */
 int64_t nmod_workspace_bytes(const nmod_params* prm, int64_t npos);

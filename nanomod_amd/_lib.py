@@ -19,6 +19,7 @@ METHOD_KS, METHOD_STOUFFER, METHOD_FISHER = 0, 1, 2
 TEST_KS, TEST_MWU, TEST_WELCH, TEST_ALL = 1, 2, 4, 7
 FLAG_KS_RATIONAL_D, FLAG_CHECK_FINITE, FLAG_NO_COUNTING, FLAG_NO_COUNT_WIDE, FLAG_NO_HOST_NARROW = 1, 2, 4, 8, 16
 FLAG_DEEP = 32            # groups beyond MAX_RANKED (up to MAX_DEEP) take the deep form instead of STATUS_TOO_LARGE
+FLAG_K1_STATIC_ITEMS = 128   # the KS-only K1 kernel walks equal strided shares instead of claiming chunks of items (A/B, parity tests)
 STATUS_MWU_ALL_IDENTICAL, STATUS_T_NAN, STATUS_EMPTY, STATUS_TOO_LARGE, STATUS_NONFINITE = 1, 2, 4, 8, 16
 KERNEL_RANK_STATS, KERNEL_FINALIZE, KERNEL_COMBINE, KERNEL_SYNTH = 0, 1, 2, 3
 MAX_GROUP = 2048          # largest group of the wave-resident kernels; larger ones (<= MAX_RANKED) take big_rank_kernel
@@ -93,6 +94,7 @@ _SIGNATURES = {
     'nmod_device_count': (C.c_int, []),
     'nmod_strerror': (C.c_char_p, [C.c_int]),
     'nmod_workspace_bytes': (C.c_int64, [C.POINTER(NmodParams), C.c_int64]),
+    'nmod_item_claim_plan': (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     'nmod_detect_batch': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(NmodOut)]),
     'nmod_combine_track': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

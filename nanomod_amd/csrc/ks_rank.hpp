@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "rank_stats_packed.hpp"
 #include "packed_sort_i16.hpp"
+#include "item_claim.hpp"
 
 namespace nmod {
 
@@ -408,11 +409,14 @@ void ks_rank_kernel(RankStatsArgs args) {
 
   // One work item = the PW positions of a wave.  S = the smaller group (D is symmetric in the groups).
   struct Item { bool valid, swap; int m, q; int64_t pos, off_s, off_q; };
-  auto describe = [&](int64_t it) {
+  // (32-bit: count <= npos < 2^31; an item past the end — the strided walk's last step, a chunk claimed beyond it — counts as
+  // item `items`, whose entries li >= count are invalid and still fit)
+  const uint32_t items32 = (uint32_t)items;
+  auto describe = [&](uint32_t it) {
     Item d;
-    const int64_t li = it * PW + slot;
-    d.valid = it < items && li < count;
-    d.pos = d.valid ? (list ? (int64_t)list[li] : li) : 0;
+    const uint32_t li = min(it, items32) * PW + slot;
+    d.valid = li < (uint32_t)count;
+    d.pos = d.valid ? (list ? (int64_t)list[li] : (int64_t)li) : 0;
     // (positions are < 2^31 and strides <= 65 535: one 32 x 32 -> 64-bit multiply each)
     int64_t o0 = 0, o1 = 0; int n0 = 0, n1 = 0;
     if (d.valid) {
@@ -459,7 +463,12 @@ void ks_rank_kernel(RankStatsArgs args) {
   // Software pipeline: the S rows of the NEXT item are requested while this item's Q is ranked, and every
   // round of Q samples is requested before the previous round is ranked — otherwise each item pays five
   // dependent HBM round trips (measured: the load-only skeleton of this kernel ran at 3.9 TB/s).
-  Item cur = describe(wave_global);
+  // Which items: a fixed, strided part, then chunks of consecutive items drawn from the launch's counter (item_claim.hpp) — waves
+  // with equal shares end far apart (the SIMD issues its oldest wave first), and the launch would end on one or two waves per SIMD.
+  ItemWalk walk;
+  const uint32_t it_first = walk.begin(item_claim_plan<uint32_t>((uint32_t)items, (uint32_t)wave_stride, args.strided_items != 0),
+                                      (uint32_t)wave_global, (uint32_t)wave_stride, args.claim + args.class_id, lane);
+  Item cur = describe(it_first);
   constexpr bool PACKED = ks_packed_sort(R, LG, DTYPE);
   float x[R];
   unsigned pk[8];                                  // PACKED: the item's S rows as packed int16 keys (x is filled by the sort)
@@ -473,8 +482,9 @@ void ks_rank_kernel(RankStatsArgs args) {
   // have long arrived — vmcnt retires in order, so a wait placed at the sort would also wait for the Q round
   // requested just before it
   __builtin_amdgcn_s_waitcnt(0x0F70);
+  walk.collect();
 
-  for (int64_t it = wave_global; it < items; it += wave_stride) {
+  for (uint32_t it = it_first, it_next; it < items32; it = it_next) {
     const bool valid = cur.valid;
     const int64_t pos = cur.pos;
     const int m = cur.m, q = cur.q;
@@ -515,7 +525,10 @@ void ks_rank_kernel(RankStatsArgs args) {
       coop = coop_cost < full_w * 4 + tail_w;
     }
     // requests that the sort hides: the next item's S rows, then this item's first rounds of Q
-    const Item nxt = describe(it + wave_stride);
+    // (a claim, when this call issues one, is the first vector memory operation of the item: every load of the previous one
+    // was waited for at its bottom, and its result is taken behind the next vmcnt(0), after the sort)
+    it_next = walk.next(it, lane);
+    const Item nxt = describe(it_next);
     KsRows<R, LG, DTYPE> rows_next;
     rows_next.request(nxt.swap ? args.sig1 : args.sig0, nxt.off_s, nxt.m, gl);
     // (PIPE_COOP: in the coop schedule these are the first rounds of the wave's FIRST position, 64 lanes wide)
@@ -599,6 +612,7 @@ void ks_rank_kernel(RankStatsArgs args) {
 
     // everything requested before the sort has arrived; from here the number of outstanding loads is known
     __builtin_amdgcn_s_waitcnt(0x0F70);
+    walk.collect();
     if (!coop) {
 #pragma unroll 1
       for (int c = 0; c < full_w; ++c) {

@@ -19,6 +19,7 @@
 #include "../../include/nanomod_hip.h"
 #include "rank_stats.hpp"
 #include "rank_stats_launch.hpp"
+#include "item_claim.hpp"
 #include "pvalue_kernels.hpp"
 #include "big_rank.hpp"
 #include "deep_rank.hpp"
@@ -74,7 +75,7 @@ struct Workspace {
 // [kStatsClass + c] positions of launch class c, [kStatsGate + c] the any-coverage counting form's gate of class c (summed over the
 // chunks of a host-resident batch), [kStatsLeft + c] positions it left to the class's sorting form
 constexpr int kStatsClass = 8, kStatsGate = 64, kStatsLeft = 128, kStatsTried = 192, kStatsWords = 256;
-constexpr int kMetaInts = 256;
+constexpr int kMetaInts = 320;
 constexpr int kMetaMax = 3 * kClassStride;      // [168..169] max n0 / n1
 constexpr int kMetaBigTotal = kMetaMax + 2;     // [170..171] u64: scratch floats the large positions need
 constexpr int kMetaBigCursor = kMetaMax + 4;    // [172..173] u64: bump allocator of big_rank_kernel
@@ -84,6 +85,8 @@ constexpr int kMetaDeepTiles = kMetaMax + 12;   // [180..181] u64: tiles of the 
 constexpr int kMetaRedo = 184;                  // float64 front end: [184] count of positions to redo, [184 + kClassStride] = 0 (their
                                                 // offset in the list), [242..243] u64 scratch keys they need, [244..245] u64 bump allocator
 constexpr int kMetaRedoTotal = 242, kMetaRedoCursor = 244;
+constexpr int kMetaClaim = 256;                 // [256 + c] ticket counter of class c's ks_rank_kernel launch (item_claim.hpp): 0 when it starts
+static_assert(kMetaRedoCursor + 2 <= kMetaClaim && kMetaClaim + kClassStride <= kMetaInts, "meta layout: claim counters");
 static_assert(kMetaRedo + kClassStride < kMetaRedoTotal && kMetaRedoCursor + 2 <= kMetaInts && kMetaBigCursor + 2 <= kMetaWideRedo && kMetaWideRedo < kMetaCntGate && kMetaCntGate < kMetaDeepTiles && kMetaDeepTiles + 2 <= kMetaRedo, "meta layout");
 // (kBigClass, kBigHistClass, kWideBigBase .., kNumPairs: rank_stats_launch.hpp)
 static_assert(kNumPairs <= kClassStride && kStatsClass + kClassStride <= kStatsGate && kStatsGate + kClassStride <= kStatsLeft && kStatsLeft + kClassStride <= kStatsTried && kStatsTried + kClassStride <= kStatsWords, "class tables");
@@ -385,7 +388,7 @@ static int check_params(const nmod_params* prm) {
   if (prm->method < NMOD_METHOD_KS || prm->method > NMOD_METHOD_FISHER) return NMOD_ERR_INVALID_ARG;
   if (prm->nb < 0 || prm->nb > NMOD_MAX_NB) return NMOD_ERR_INVALID_ARG;
   if ((prm->tests & ~NMOD_TEST_ALL) != 0) return NMOD_ERR_INVALID_ARG;
-  if ((prm->flags & ~(NMOD_FLAG_KS_RATIONAL_D | NMOD_FLAG_CHECK_FINITE | NMOD_FLAG_NO_COUNTING | NMOD_FLAG_NO_COUNT_WIDE | NMOD_FLAG_NO_HOST_NARROW | NMOD_FLAG_DEEP)) != 0 || prm->reserved != 0) return NMOD_ERR_INVALID_ARG;
+  if ((prm->flags & ~(NMOD_FLAG_KS_RATIONAL_D | NMOD_FLAG_CHECK_FINITE | NMOD_FLAG_NO_COUNTING | NMOD_FLAG_NO_COUNT_WIDE | NMOD_FLAG_NO_HOST_NARROW | NMOD_FLAG_DEEP | NMOD_FLAG_K1_STATIC_ITEMS)) != 0 || prm->reserved != 0) return NMOD_ERR_INVALID_ARG;
   return NMOD_OK;
 }
 
@@ -616,6 +619,8 @@ static int plan_batch(Batch& b) {
   b.wide_redo = wide_f32 && b.big_possible;
   for (int cls = 0; cls < kNumClasses; ++cls) b.wide_redo = b.wide_redo || (wide_f32 && b.wanted[cls] && wide_class(cls));
   if (b.wide_redo && !meta_cleared) NMOD_HIP(hipMemsetAsync(ws.meta + kMetaWideRedo, 0, 4, stream));   // (the redo counter alone)
+  // KS-only: ks_rank_kernel draws tickets from its class's counter unless the call asks for the strided walk (the counters alone)
+  if (!b.all && !meta_cleared && !(prm->flags & NMOD_FLAG_K1_STATIC_ITEMS)) NMOD_HIP(hipMemsetAsync(ws.meta + kMetaClaim, 0, kClassStride * 4, stream));
   return NMOD_OK;
 }
 
@@ -644,6 +649,7 @@ static int enqueue_k1(Batch& b) {
   ra.ks_rational_d = (!b.all && (prm->flags & NMOD_FLAG_KS_RATIONAL_D)) ? 1 : 0;
   ra.tied = b.f64 ? ws.tied : nullptr;          // float32 keys of float64 samples: K1 reports the positions whose keys tie
   ra.redo_list = ws.redo; ra.redo_count = ws.meta + kMetaWideRedo;
+  ra.claim = reinterpret_cast<uint32_t*>(ws.meta + kMetaClaim); ra.strided_items = (prm->flags & NMOD_FLAG_K1_STATIC_ITEMS) ? 1 : 0;
   if (b.binned) { ra.pos_list = ws.order; ra.class_meta = ws.meta; }
   // all tests on capacity-256 positions: the counting form is tried first (rank_count.hpp; a device-side probe decides whether
   // the batch is event-like, positions it cannot take fall through to rank_hist_kernel).  The float32 images of float64 samples
@@ -1128,6 +1134,13 @@ const char* nmod_strerror(int rc) {
       return g_errbuf;
     default: return "unknown error code";
   }
+}
+
+int nmod_item_claim_plan(int64_t items, int64_t waves, int32_t flags, int64_t* plan) {
+  if (items < 0 || waves < 1 || !plan) return NMOD_ERR_INVALID_ARG;
+  const ItemClaimPlan p = item_claim_plan<int64_t>(items, waves, (flags & NMOD_FLAG_K1_STATIC_ITEMS) != 0);
+  plan[0] = p.rounds; plan[1] = p.first; plan[2] = p.chunk; plan[3] = p.dynamic;
+  return NMOD_OK;
 }
 
 int64_t nmod_workspace_bytes(const nmod_params* prm, int64_t npos) {

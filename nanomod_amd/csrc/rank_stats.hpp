@@ -52,6 +52,9 @@ struct RankStatsArgs {
   const int32_t* alt_gates; const int32_t* alt_list; const int32_t* alt_meta;
   int32_t cnt_mode;                            // rank_hist_kernel launches around the counting form: 1 = run only when the gate is clear (the plain
                                                // instance takes the whole list), 2 = only when it is set (the AFTER instance takes what is left); 0 = always
+  // ks_rank_kernel hands a part of its items out by chunk (item_claim.hpp): claim[class_id] is the launch's ticket counter, 0 when
+  // the launch starts; strided_items != 0 (NMOD_FLAG_K1_STATIC_ITEMS): the strided walk for every item, the counter is not touched
+  uint32_t* claim; int32_t strided_items;
 };
 
 // compare-exchange of two registers.  (fminf / fmaxf put a canonicalising v_max x, x in front of every value of unknown
