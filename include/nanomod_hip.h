@@ -82,7 +82,9 @@ enum {
   NMOD_STATUS_TOO_LARGE = 8,         /* more samples in a group than the max_n0 / max_n1 the caller promised, or than NMOD_MAX_RANKED
                                         (NMOD_MAX_DEEP with NMOD_FLAG_DEEP):
                                         the position is skipped, its outputs are NaN, the rest of the batch is computed */
-  NMOD_STATUS_NONFINITE = 16         /* a NaN or infinite sample (see the header comment): the position's statistics are unspecified */
+  NMOD_STATUS_NONFINITE = 16,        /* a NaN or infinite sample (see the header comment): the position's statistics are unspecified */
+  NMOD_STATUS_BAD_REFERENCE = 32     /* nmod_one_sample only: the position's reference is unusable (mean or sd not finite, sd <= 0, ref_n < 2);
+                                        no other entry point sets it */
 };
 
 /* return codes */
@@ -450,6 +452,46 @@ typedef struct nmod_mix_out { double *pi, *mu_mod, *sd_mod, *llr; int32_t* iters
 int nmod_mix_fraction(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0, const void* sig1, const int64_t* off1,
                       int32_t mix_group, int32_t model, int32_t max_iter, double tol,
                       const double* gate, double gate_max, const nmod_mix_out* out);
+
+/* One-sample detection against a stored per-position reference (K9; the reference project has no such step — it always needs two
+ * read groups).  Position i has the samples x_1..x_n of ONE group (as doubles: float32 up-cast, int16 k / 1000.0, float64 as is), a
+ * reference level mu = ref_mean[i] and spread sd = ref_sd[i] (the ddof = 0 standard deviation, what want_mstd reports) and
+ * optionally the reference's coverage nr = ref_n[i].
+ *   Moments: m = mean(x), s2 = var(x) with ddof = 0 (two-pass fp64 about the mean; int16: in milli-units, the first sum exact),
+ *     shift = (m - mu) / sd; outputs mean = m, std = sqrt(s2).
+ *   KS against N(mu, sd^2): x_(1) <= ... <= x_(n) sorted, F_k = 0.5 erfc(-(x_(k) - mu) / (sd sqrt 2)),
+ *     D = max_k max(k/n - F_k, F_k - (k-1)/n)  (ties need no special case: the largest k of a tie group attains the upper term,
+ *     the smallest the lower one), ks_p = kolmogorov((sqrt n + 0.12 + 0.11 / sqrt n) D): the Stephens-corrected asymptotic tail,
+ *     the one-sample form of what ks_2samp does with en = sqrt(n0 n1 / (n0 + n1)), by the same device function.  D within 1e-13
+ *     absolute of the definition in exact arithmetic, ks_p within 1e-9 relative; both clamped as nmod_detect_batch clamps its pair.
+ *   t, sign sample minus reference, clamped as the two-sample pair:
+ *     ref_n given (a stored control): Welch from the statistics, vx = s2 n / (n - 1), vr = sd^2 nr / (nr - 1),
+ *       se2 = vx / n + vr / nr, t = (m - mu) / sqrt(se2), df = se2^2 / ((vx/n)^2 / (n - 1) + (vr/nr)^2 / (nr - 1)) —
+ *       scipy.stats.ttest_ind_from_stats(equal_var=False), so the t of the two-sample Welch test on the full data (1e-11 relative);
+ *     ref_n == NULL (a model: the reference is taken as known): t = (m - mu) / sqrt(vx / n), df = n - 1 — scipy.stats.ttest_1samp;
+ *     se2 == 0 (vx == 0 for a model) or n == 1: t and t_p are NaN with NMOD_STATUS_T_NAN (KS is computed).
+ *   Combine: comb_st / comb_p are the window combine of this KS track under prm->nb / method / weights_dif and run_id — the code
+ *     behind nmod_combine_track with all its pad / NaN / p = 0 conventions; not written when method == NMOD_METHOD_KS.
+ *   Status per position: NMOD_STATUS_EMPTY (n == 0), NMOD_STATUS_TOO_LARGE (n beyond NMOD_MAX_ONE, NMOD_MAX_ONE_F64 for float64),
+ *     NMOD_STATUS_BAD_REFERENCE, NMOD_STATUS_NONFINITE (a NaN or infinite sample; exact here: the kernels see every sample) — each
+ *     of these four gives NaN in every output of the position, and its combine windows follow K3's NaN rule — and NMOD_STATUS_T_NAN.
+ *     Deeper positions (the NMOD_FLAG_DEEP range) are not computed by this entry.
+ * A NULL output member is skipped; out->struct_size = sizeof(nmod_one_out).  Rows: CSR when `off` is given, else the fixed stride
+ * prm->stride0.  Reads struct_size, device, stream, memspace, dtype, stride0, nb, method, weights_dif of prm and nothing else.
+ * NMOD_MEM_DEVICE: everything is enqueued on prm->stream and the call returns WITHOUT synchronising and without a host round trip;
+ * scratch (16 bytes per position, 16 more when the combined pair is wanted without the KS pair) comes stream-ordered from the
+ * library's pool.  NMOD_MEM_HOST: copy in, run, copy back, synchronise (one staged copy, not the pipelined host entry).  npos == 0
+ * is NMOD_OK.  NMOD_ERR_INVALID_ARG before any device work: npos < 0 or beyond 2^32 - 2, out NULL (or of another struct_size), a
+ * NULL sig / ref_mean / ref_sd with npos > 0, neither offsets nor a stride, an unknown dtype, nb outside 0 .. NMOD_MAX_NB, an
+ * unknown method, host offsets that decrease, a NULL run_id (or a Stouffer weights_dif <= 0) when a combined track is requested.
+ * A position's results are the same bits whatever else is in the batch, in CSR or stride form, from host or device memory. */
+#define NMOD_MAX_ONE 16384      /* samples per position, float32 / int16: 64 KiB of keys in one workgroup's LDS */
+#define NMOD_MAX_ONE_F64 8192   /* samples per position, float64 (64-bit keys) */
+typedef struct nmod_one_out { int32_t struct_size; int32_t reserved;
+  double *ks_d, *ks_p, *t_t, *t_p, *shift, *mean, *std, *comb_st, *comb_p; uint8_t* status; } nmod_one_out;
+int nmod_one_sample(const nmod_params* prm, int64_t npos, const void* sig, const int64_t* off /* or prm->stride0 */,
+                    const double* ref_mean, const double* ref_sd, const int32_t* ref_n /* may be NULL */,
+                    const int32_t* run_id, const nmod_one_out* out);
 
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One

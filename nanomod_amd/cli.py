@@ -75,7 +75,82 @@ def build_parser():
     d.add_argument('--devicePivot', type=int, default=0, choices=[0, 1],
                    help='1: read FAST5 folders as read-level sets and group their events by position on the GPU '
                    '(nmod_pivot_reads), as read-level .npz containers always are')
+    pr = sub.add_parser('profile', help='reduce one read group to a per-position control profile (coverage, mean, sd) for detect1')
+    pr.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    pr.add_argument('--wrkBase1', required=True, help='the control read group: a per-position .npz container')
+    pr.add_argument('--MinCoverage', type=int, default=5)
+    pr.add_argument('--outFolder', default='mRes')
+    pr.add_argument('--FileID', default='mod', help='the profile is written to <outFolder>/<FileID>_profile.npz')
+    pr.add_argument('--device', type=int, default=0)
+    o = sub.add_parser('detect1', help='one read group against a stored profile: KS against N(mean, sd^2), t, window combine')
+    o.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    o.add_argument('--wrkBase1', required=True, help='the sample read group: a per-position .npz container')
+    o.add_argument('--refProfile', required=True, help="a profile written by 'profile' (a control) or by onesample.save_profile (a model)")
+    o.add_argument('--FileID', default='mod')
+    o.add_argument('--outFolder', default='mRes')
+    o.add_argument('--MinCoverage', type=int, default=5)
+    o.add_argument('--topN', type=int, default=30)
+    o.add_argument('--neighborPvalues', type=int, default=2)
+    o.add_argument('--WeightsDif', type=float, default=2.0)
+    o.add_argument('--testMethod', default='stouffer', choices=['fisher', 'stouffer', 'ks'])
+    o.add_argument('--rankUse', default='pv', choices=['st', 'pv'])
+    o.add_argument('--SaveTest', type=int, default=1, choices=[0, 1])
+    o.add_argument('--Pos', default='', help="region of interest chr:pos[:pos2] (1-based)")
+    o.add_argument('--window', type=int, default=21, help='with --Pos chr:pos: the region is pos +- (window - 1) / 2')
+    o.add_argument('--device', type=int, default=0)
+    o.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'],
+                   help='bh / by: q-values of the t, KS and combined p-value tracks, written to <FileID>_one_sample_fdr.txt')
+    o.add_argument('--fdrAlpha', type=float, default=0.05)
     return p
+
+
+def validate1(a):
+    """the checks of validate() that concern profile / detect1"""
+    errs = []
+    if a.MinCoverage < 3:
+        errs.append('Error: --MinCoverage should be not less than 3')
+    inputs = [a.wrkBase1]
+    if a.cmd == 'detect1':
+        inputs.append(a.refProfile)
+        if a.topN < 1:
+            errs.append('Error: --topN should be larger than 0')
+        if not 0 <= a.neighborPvalues <= L.MAX_NB:
+            errs.append('Error: --neighborPvalues should be in 0 .. %d' % L.MAX_NB)
+        if a.WeightsDif < 1.0:
+            a.WeightsDif = 1.0
+        if not 0.0 < a.fdrAlpha <= 1.0:
+            errs.append('Error: --fdrAlpha should be in (0, 1]')
+        a.wrkBase2, a.mixMaxIter, a.mixTol, a.percentile = a.wrkBase1, 200, 1e-6, 0.1           # (validate() reads them)
+        errs += [e for e in validate(a) if e not in errs]
+    for f in inputs:
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    return errs
+
+
+def run_profile(a, log=print):
+    from . import onesample
+    prof = onesample.build_profile(container.load_group(a.wrkBase1), a.MinCoverage, a.device, log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_profile.npz')
+    onesample.save_profile(path, prof)
+    if a.outLevel <= detect.OUTPUT_ERROR:
+        log('Profile of %d positions is saved in %s' % (len(prof['pos']), path))
+    return prof
+
+
+def run_detect1(a, log=print):
+    from . import onesample
+    mo = {'ds2': ['sample'], 'sample': {'nmod_container': load_input(a.wrkBase1, a, log)}, 'nmod_profile': a.refProfile,
+          'MinCoverage': a.MinCoverage, 'neighborPvalues': a.neighborPvalues, 'WeightsDif': a.WeightsDif, 'testMethod': a.testMethod,
+          'rankUse': a.rankUse, 'SaveTest': a.SaveTest, 'outFolder': a.outFolder, 'FileID': a.FileID, 'outLevel': a.outLevel,
+          'nmod_device': a.device, 'nmod_fdr': '' if a.fdr == 'none' else a.fdr, 'nmod_fdr_alpha': a.fdrAlpha}
+    order = onesample.mtest1(mo)
+    if a.fdr != 'none' and a.outLevel <= detect.OUTPUT_INFO:
+        for name, s in mo['nmod_fdr_summary'].items():
+            log('FDR %s %s alpha=%g: tested %d excluded %d rejected %d p_crit %.3E'
+                % (a.fdr, name, a.fdrAlpha, s['tested'], s['excluded'], s['rejected'], s['p_crit']))
+    return mo['one_sample_meta'], mo['one_sample_arrays'], order
 
 
 def validate(a):
@@ -360,6 +435,19 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd in ('profile', 'detect1'):
+        errs = validate1(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        if a.cmd == 'profile':
+            run_profile(a)
+            return 0
+        meta, res, order = run_detect1(a)
+        first = ('comb_p' if a.testMethod != 'ks' else 'ks_p')
+        for r, i in enumerate(order[:a.topN]):
+            print('%d %s %s %d %s %.3E' % (r + 1, meta['chrom'][i], meta['strand'][i], meta['pos'][i] + 1, meta['base'][i], res[first][i]))
+        return 0
     if a.cmd != 'detect':
         parser.print_help()
         return 1

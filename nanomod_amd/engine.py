@@ -278,6 +278,48 @@ def mix_fraction_host(sig0, off0, sig1, off1, *, mix_group=1, model='equal', max
     return res
 
 
+def one_sample_host(sig, off, ref_mean, ref_sd, ref_n=None, run_id=None, *, stride=0, nb=2, weights_dif=2.0, method='stouffer', device=0):
+    """One read group against a stored per-position reference (nmod_one_sample, include/nanomod_hip.h) on host-resident rows:
+    sig float32, int16 (milli-units) or float64, rows by `off` (int64[npos + 1]) or a fixed `stride`; ref_mean / ref_sd float64[npos]
+    (sd with ddof = 0), ref_n int32[npos] for a stored control (Welch t from the statistics) or None for a model (one-sample t).
+    Returns a dict of numpy arrays: ks_d, ks_p, t_t, t_p, shift, mean, std (float64), status (uint8, L.STATUS_* bits) and, when
+    method is not 'ks' (run_id is then required), comb_st / comb_p: the window combine of the KS track."""
+    lib = L.load()
+    _join_warm_up(device)
+    sig = np.ascontiguousarray(sig)
+    if sig.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('sig must be float32, int16 (milli-units) or float64')
+    ref_mean = np.ascontiguousarray(ref_mean, dtype=np.float64)
+    ref_sd = np.ascontiguousarray(ref_sd, dtype=np.float64)
+    npos = ref_mean.shape[0]
+    off = None if off is None else np.ascontiguousarray(off, dtype=np.int64)
+    _check_csr(off, npos, 'off')
+    if ref_sd.shape != (npos,):
+        raise ValueError('ref_sd must be float64[npos]')
+    if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
+        raise ValueError('sig is shorter than its offsets / stride say')
+    if ref_n is not None:
+        ref_n = np.ascontiguousarray(ref_n, dtype=np.int32)
+        if ref_n.shape != (npos,):
+            raise ValueError('ref_n must be int32[npos]')
+    method_id = L.METHOD_BY_NAME[method] if isinstance(method, str) else method
+    run = None
+    if run_id is not None:
+        run = np.ascontiguousarray(run_id, dtype=np.int32)
+        if run.shape != (npos,):
+            raise ValueError('run_id must be int32[npos]')
+    names = [k for k in L.ONE_FIELDS if method_id != L.METHOD_KS or not k.startswith('comb_')]
+    res = {k: np.empty(npos, dtype=np.float64) for k in names}
+    res['status'] = np.empty(npos, dtype=np.uint8)
+    out = L.make_one_out(**{k: _np_ptr(a) for k, a in res.items()})
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(sig.dtype), method=method_id, nb=nb,
+                        weights_dif=weights_dif, stride0=stride if off is None else 0)
+    rc = lib.nmod_one_sample(C.byref(prm), npos, _np_ptr(sig), _np_ptr(off), _np_ptr(ref_mean), _np_ptr(ref_sd), _np_ptr(ref_n),
+                             _np_ptr(run), C.byref(out))
+    L.check(rc, 'nmod_one_sample')
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -512,6 +554,39 @@ class DeviceDetector:
         rc = self.lib.nmod_mix_fraction(C.byref(prm), npos, ptr(sig0), ptr(off0), ptr(sig1), ptr(off1), mix_group, model, max_iter,
                                         tol, ptr(gate), float(gate_max), C.byref(o))
         L.check(rc, 'nmod_mix_fraction')
+        return res
+
+    def one_sample(self, sig, ref_mean, ref_sd, ref_n=None, run_id=None, *, off=None, stride=0, npos=None, out=None):
+        """One read group against a stored per-position reference (nmod_one_sample, NMOD_MEM_DEVICE) under the detector's nb /
+        method / weights_dif, enqueued on the current stream without synchronising.  sig: float32, int16 or float64 CUDA rows by
+        `off` (int64 CUDA tensor) or a fixed `stride`; ref_mean / ref_sd: float64 CUDA vectors; ref_n: int32 (a stored control) or
+        None (a model); run_id: int32, required unless the method is 'ks'.  Returns a dict of CUDA tensors: ks_d, ks_p, t_t, t_p,
+        shift, mean, std (float64), status (uint8) and, unless the method is 'ks', comb_st / comb_p — which fdr() accepts:
+
+            res = det.one_sample(sig, mu, sd, n_ref, run_id, stride=n)
+            qs, summary = det.fdr(res, tracks=('ks_p', 't_p', 'comb_p'))
+        """
+        torch = self.torch
+        dtype = self._dtype_of(sig)
+        if npos is None:
+            npos = ref_mean.numel()
+        dev = 'cuda:%d' % self.device
+        for t, dt, name in ((ref_mean, torch.float64, 'ref_mean'), (ref_sd, torch.float64, 'ref_sd'), (ref_n, torch.int32, 'ref_n'),
+                            (run_id, torch.int32, 'run_id'), (off, torch.int64, 'off')):
+            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == npos + (name == 'off')):
+                raise ValueError('one_sample: %s must be a contiguous %s CUDA vector of npos%s elements' % (name, dt, ' + 1' if name == 'off' else ''))
+        if self.method != L.METHOD_KS and run_id is None:
+            raise ValueError('one_sample: run_id is needed for the combined track')
+        res = out
+        if res is None:
+            names = [k for k in L.ONE_FIELDS if self.method != L.METHOD_KS or not k.startswith('comb_')]
+            res = {k: torch.empty(npos, dtype=torch.float64, device=dev) for k in names}
+            res['status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
+        o = L.make_one_out(**{k: t.data_ptr() for k, t in res.items()})
+        prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
+        ptr = lambda t: (t.data_ptr() if t is not None else None)
+        rc = self.lib.nmod_one_sample(C.byref(prm), npos, ptr(sig), ptr(off), ptr(ref_mean), ptr(ref_sd), ptr(ref_n), ptr(run_id), C.byref(o))
+        L.check(rc, 'nmod_one_sample')
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
