@@ -121,16 +121,63 @@ struct KsRows {
     }
   }
 
+  // Fixed-stride batches (ks_rank_kernel<..., UNIFORM>): every row has the same n, so which samples a lane takes is the
+  // same for every item.  plan() works out, once per launch, the byte offset of each chunk inside a row (boff) and whether
+  // the lane has a chunk there at all (live); per item request_uniform() is then one 64-bit add and one load per chunk —
+  // the same addresses, issued as unconditionally, as request() computes.
+  // Chunk k covers samples k*4*LG .. (k+1)*4*LG - 1, so only the chunk `last` that holds sample n - 1 has lanes with and
+  // lanes without a share (last_live); the chunks before it are live in every lane, the ones behind it in none (rows
+  // shorter than four samples: no chunk is live).  One lane mask and one number instead of a mask per chunk.
+  struct Plan { unsigned boff[NK]; int last; bool last_live; };
+  __device__ static __forceinline__ Plan plan(int n, int gl) {
+    Plan pl;
+    pl.last = (n >= 4) ? (n - 1) / (4 * LG) : -1;
+    pl.last_live = n >= 4 && n - (pl.last * (4 * LG) + 4 * gl) > 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int idx = k * (4 * LG) + 4 * gl;
+      const int t = n - idx;
+      pl.boff[k] = (n >= 4 && t > 0) ? (unsigned)((t >= 4) ? idx : n - 4) * (unsigned)sizeof(T) : 0u;
+    }
+    return pl;
+  }
+  __device__ __forceinline__ void request_uniform(const void* sig, int64_t off, int n, int gl, const Plan& pl) {
+    const char* row = reinterpret_cast<const char*>(reinterpret_cast<const T*>(sig) + off);
+    const char* dummy = ks_packed_sort(R, LG, DTYPE) ? reinterpret_cast<const char*>(kKsPad16) : reinterpret_cast<const char*>(kKsInf4);
+    int last = pl.last;
+    asm volatile("" : "+s"(last));                    // (the chunks' masks are scalar selects per item, not NK register pairs held across the loop)
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const bool live = k < last || (k == last && pl.last_live);
+      v[k] = ks_global_load<V4>(live ? row + pl.boff[k] : dummy);
+    }
+    s[0] = s[1] = s[2] = T(0);
+    asm volatile("" : "+v"(gl), "+s"(n));             // (the tests stay here: hoisted, they are scalar registers every item pays for)
+    if (n < 4) {                                      // (n is a launch constant: a scalar branch)
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+        if (gl == 0 && e < n) s[e] = ks_global_load<T>(reinterpret_cast<const T*>(row) + e);
+    }
+  }
+
+  // UNI: n is a launch constant (fixed-stride batches) — whether a chunk holds the end of a row (n is no multiple of four)
+  // and whether the rows are shorter than four samples are scalar tests instead of ballots
+  template <bool UNI = false>
   __device__ __forceinline__ void finish(float (&x)[R], int n, int gl) const {
     const float inf = __builtin_inff();
+    // (the lane's share of a row end is the same for every item, and the compiler would keep a mask per component and every
+    // test of n in scalar registers, which run out: spills into the lanes of a vector register, read back per item.  Hide
+    // the lane number and n: the scalar tests are taken per item, the lane's share only where a branch needs it.)
+    if constexpr (UNI) asm volatile("" : "+v"(gl), "+s"(n));
     const bool long_row = n >= 4;
+    const bool row_end = long_row && (n & 3) != 0;   // UNI: a chunk of the (every) row holds its end
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       const int idx = k * (4 * LG) + 4 * gl;
       const int t = long_row ? n - idx : 0;          // samples of this chunk: component j is one of them iff j >= 4 - t
       if constexpr (DTYPE == 0) {
         x[4 * k + 0] = v[k].x; x[4 * k + 1] = v[k].y; x[4 * k + 2] = v[k].z; x[4 * k + 3] = v[k].w;   // empty chunks read +inf
-        if (__ballot(t > 0 && t < 4) != 0ull) {      // a chunk that holds the end of a row: drop the overlap
+        if (UNI ? row_end : (__ballot(t > 0 && t < 4) != 0ull)) {      // a chunk that holds the end of a row: drop the overlap
           x[4 * k + 0] = (t >= 4 || t <= 0) ? x[4 * k + 0] : inf;
           x[4 * k + 1] = (t >= 3 || t <= 0) ? x[4 * k + 1] : inf;
           x[4 * k + 2] = (t >= 2 || t <= 0) ? x[4 * k + 2] : inf;
@@ -142,7 +189,7 @@ struct KsRows {
         x[4 * k + 3] = (t >= 1) ? (float)v[k].w : inf;
       }
     }
-    if (__ballot(!long_row && n > 0) != 0ull) {
+    if (UNI ? !long_row : (__ballot(!long_row && n > 0) != 0ull)) {
 #pragma unroll
       for (int e = 0; e < 3; ++e) x[e] = (!long_row && gl == 0 && e < n) ? (float)s[e] : x[e];
     }
@@ -150,22 +197,25 @@ struct KsRows {
 
   // the same rows as packed int16 keys for seg_sort_packed16: two samples per register in load order (the sort does not
   // care which), 32767 pads — empty chunks already read a block of them
+  template <bool UNI = false>
   __device__ __forceinline__ void finish_packed(unsigned (&p)[8], int n, int gl) const {
     static_assert(R == 16, "packed rows: 16 keys per lane");
+    if constexpr (UNI) asm volatile("" : "+v"(gl), "+s"(n));   // (see finish())
     const bool long_row = n >= 4;
+    const bool row_end = long_row && (n & 3) != 0;
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       p[2 * k] = ((unsigned)(unsigned short)v[k].y << 16) | (unsigned)(unsigned short)v[k].x;
       p[2 * k + 1] = ((unsigned)(unsigned short)v[k].w << 16) | (unsigned)(unsigned short)v[k].z;
       const int idx = k * (4 * LG) + 4 * gl;
       const int t = long_row ? n - idx : 0;          // samples of this chunk: component j is one of them iff j >= 4 - t
-      if (__ballot(t > 0 && t < 4) != 0ull) {        // a chunk that holds the end of a row: drop the overlap
+      if (UNI ? row_end : (__ballot(t > 0 && t < 4) != 0ull)) {        // a chunk that holds the end of a row: drop the overlap
         if (t == 3) p[2 * k] = (p[2 * k] & 0xffff0000u) | 0x7fffu;           // component 0 belongs to the previous lane
         if (t == 2 || t == 1) p[2 * k] = 0x7fff7fffu;                        // components 0 and 1 do
         if (t == 1) p[2 * k + 1] = (p[2 * k + 1] & 0xffff0000u) | 0x7fffu;   // only component 3 is ours
       }
     }
-    if (__ballot(!long_row && n > 0) != 0ull) {      // rows shorter than four samples: lane 0 holds them in s[]
+    if (UNI ? !long_row : (__ballot(!long_row && n > 0) != 0ull)) {      // rows shorter than four samples: lane 0 holds them in s[]
       if (!long_row && gl == 0) {
         const unsigned s0 = (0 < n) ? (unsigned)(unsigned short)s[0] : 0x7fffu;
         const unsigned s1 = (1 < n) ? (unsigned)(unsigned short)s[1] : 0x7fffu;
@@ -358,9 +408,16 @@ __device__ __forceinline__ void seg_moments_packed16(const unsigned (&p)[8], int
 // samples themselves, and the flagged positions are redone with 64-bit keys (nanomod_hip.hip: detect_f64).  For the KS
 // statistic only ties BETWEEN the groups matter: two keys of S with equal images and no sample of Q on them bound a
 // pooled point that lies between its neighbours' values of |F0 - F1|.
-template <int R, int LG, int DTYPE, bool FLAGS = false>
+// UNIFORM: the instance for fixed-stride batches without a position list (stride0 > 0, stride1 > 0, pos_list and alt_gates
+// null: launch_rank_stats picks it exactly then).  Every position has the same two sizes, so what the loop head of the
+// generic instance works out per item in vector registers — which group is S, the ranking schedule, the chunk layout of
+// the row loads, the clamps of the bin evaluation, fl(1/m) and fl(1/q) — is a launch constant here, taken once before
+// the loop and held in scalar registers.  Per item there remain the position, two row offsets and the loads themselves.
+// Slots past the end of the batch rank position 0 again (and store nothing) instead of an empty position.
+template <int R, int LG, int DTYPE, bool FLAGS = false, bool UNIFORM = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock, (R <= 16 ? 4 : 2))
 void ks_rank_kernel(RankStatsArgs args) {
+  static_assert(!(UNIFORM && FLAGS), "the float64 front end keeps the generic instance");
   static_assert(LG == 8 || LG == 16 || LG == 32 || LG == 64, "lanes per sorted group");
   static_assert(R >= 8 && R <= 32 && (R & (R - 1)) == 0, "registers per lane");
   constexpr int PW = 64 / LG;                  // positions per wave
@@ -396,6 +453,9 @@ void ks_rank_kernel(RankStatsArgs args) {
 
   int64_t count = args.npos;
   const int32_t* list = nullptr;
+  if constexpr (UNIFORM) {
+    if (count <= 0) return;                        // (slots past the end read position 0: there has to be one)
+  } else
   if (args.alt_gates != nullptr && args.alt_gates[args.class_id] != 0) {     // what rank_count_wide_kernel left of the class
     count = args.alt_meta[args.class_id];
     list = args.alt_list + args.alt_meta[kClassStride + args.class_id];
@@ -412,10 +472,23 @@ void ks_rank_kernel(RankStatsArgs args) {
   // (32-bit: count <= npos < 2^31; an item past the end — the strided walk's last step, a chunk claimed beyond it — counts as
   // item `items`, whose entries li >= count are invalid and still fit)
   const uint32_t items32 = (uint32_t)items;
+  // UNIFORM: the launch constants (kernel arguments: scalar registers)
+  const bool u_swap = args.stride1 < args.stride0;
+  const int u_m = (int)(u_swap ? args.stride1 : args.stride0), u_q = (int)(u_swap ? args.stride0 : args.stride1);
+  const void* const u_sig_s = u_swap ? args.sig1 : args.sig0;
+  const void* const u_sig_q = u_swap ? args.sig0 : args.sig1;
   auto describe = [&](uint32_t it) {
     Item d;
     const uint32_t li = min(it, items32) * PW + slot;
     d.valid = li < (uint32_t)count;
+    if constexpr (UNIFORM) {
+      // (positions are < 2^31 and strides <= 65 535: one 32 x 32 -> 64-bit multiply per group)
+      d.pos = d.valid ? (int64_t)li : 0;
+      d.swap = u_swap; d.m = u_m; d.q = u_q;
+      d.off_s = (int64_t)((uint64_t)(uint32_t)d.pos * (uint64_t)(uint32_t)u_m);
+      d.off_q = (int64_t)((uint64_t)(uint32_t)d.pos * (uint64_t)(uint32_t)u_q);
+      return d;
+    }
     d.pos = d.valid ? (list ? (int64_t)list[li] : (int64_t)li) : 0;
     // (positions are < 2^31 and strides <= 65 535: one 32 x 32 -> 64-bit multiply each)
     int64_t o0 = 0, o1 = 0; int n0 = 0, n1 = 0;
@@ -472,11 +545,28 @@ void ks_rank_kernel(RankStatsArgs args) {
   constexpr bool PACKED = ks_packed_sort(R, LG, DTYPE);
   float x[R];
   unsigned pk[8];                                  // PACKED: the item's S rows as packed int16 keys (x is filled by the sort)
+  [[maybe_unused]] typename KsRows<R, LG, DTYPE>::Plan row_plan;
+  if constexpr (UNIFORM) row_plan = KsRows<R, LG, DTYPE>::plan(u_m, gl);
+  // UNIFORM: fl(m), fl(q), fl(1/m), fl(1/q) as scalar register pairs, the reciprocals read once from the block's recip[]
+  [[maybe_unused]] double u_dm = 0.0, u_dq = 0.0, u_rm = 0.0, u_rq = 0.0;
+  if constexpr (UNIFORM) {
+    // (inline assembly: the builtin is folded away where the compiler can see that the value is uniform, and the value
+    // then stays in a vector register pair)
+    auto uni64 = [](double v) {
+      const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+      unsigned lo, hi;
+      asm("v_readfirstlane_b32 %0, %1" : "=s"(lo) : "v"((unsigned)b));
+      asm("v_readfirstlane_b32 %0, %1" : "=s"(hi) : "v"((unsigned)(b >> 32)));
+      return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    };
+    u_dm = uni64((double)u_m); u_dq = uni64((double)u_q); u_rm = uni64(recip[0]); u_rq = uni64(recip[1]);
+  }
   {
     KsRows<R, LG, DTYPE> first;
-    first.request(cur.swap ? args.sig1 : args.sig0, cur.off_s, cur.m, gl);
-    if constexpr (PACKED) first.finish_packed(pk, cur.m, gl);
-    else first.finish(x, cur.m, gl);
+    if constexpr (UNIFORM) first.request_uniform(u_sig_s, cur.off_s, u_m, gl, row_plan);
+    else first.request(cur.swap ? args.sig1 : args.sig0, cur.off_s, cur.m, gl);
+    if constexpr (PACKED) first.template finish_packed<UNIFORM>(pk, cur.m, gl);
+    else first.template finish<UNIFORM>(x, cur.m, gl);
   }
   // vmcnt(0) (expcnt / lgkmcnt untouched): S rows are waited for here and at the bottom of the loop, where they
   // have long arrived — vmcnt retires in order, so a wait placed at the sort would also wait for the Q round
@@ -487,8 +577,8 @@ void ks_rank_kernel(RankStatsArgs args) {
   for (uint32_t it = it_first, it_next; it < items32; it = it_next) {
     const bool valid = cur.valid;
     const int64_t pos = cur.pos;
-    const int m = cur.m, q = cur.q;
-    const void* sig_q = cur.swap ? args.sig0 : args.sig1;
+    const int m = UNIFORM ? u_m : cur.m, q = UNIFORM ? u_q : cur.q;
+    const void* sig_q = UNIFORM ? u_sig_q : (cur.swap ? args.sig0 : args.sig1);
     const int64_t off_q = cur.off_q;
 
     // ---- the ranking schedule (needs only q) and the first round of Q, requested before the sort.
@@ -498,7 +588,9 @@ void ks_rank_kernel(RankStatsArgs args) {
     const int full = q / (4 * LG);
     const int tail = (q - full * (4 * LG) + LG - 1) / LG;
     int full_w = full, tail_w = tail;
-    if constexpr (PW > 1) {
+    if constexpr (UNIFORM) {
+      // every position of the wave has this schedule
+    } else if constexpr (PW > 1) {
       full_w = 0; tail_w = 0;
 #pragma unroll
       for (int s = 0; s < PW; ++s) {
@@ -514,7 +606,10 @@ void ks_rank_kernel(RankStatsArgs args) {
     // after the other — balanced when the Q sizes of the wave's positions differ (ragged coverage).
     int slots = (full_w * 4 + tail_w) * LG;
     bool coop = false;
-    if constexpr (PW > 1) {
+    if constexpr (UNIFORM) {
+      // equal sizes never take the cooperative schedule: own costs full * 4 + tail = ceil(q / LG) rounds, coop
+      // PW * ceil(q / 64) >= PW * q / 64 = q / LG — an integer, so >= ceil(q / LG).  The whole coop path drops out of the instance.
+    } else if constexpr (PW > 1) {
       int coop_cost = 0;
 #pragma unroll
       for (int sl = 0; sl < PW; ++sl) {
@@ -530,7 +625,8 @@ void ks_rank_kernel(RankStatsArgs args) {
     it_next = walk.next(it, lane);
     const Item nxt = describe(it_next);
     KsRows<R, LG, DTYPE> rows_next;
-    rows_next.request(nxt.swap ? args.sig1 : args.sig0, nxt.off_s, nxt.m, gl);
+    if constexpr (UNIFORM) rows_next.request_uniform(u_sig_s, nxt.off_s, u_m, gl, row_plan);
+    else rows_next.request(nxt.swap ? args.sig1 : args.sig0, nxt.off_s, nxt.m, gl);
     // (PIPE_COOP: in the coop schedule these are the first rounds of the wave's FIRST position, 64 lanes wide)
     constexpr bool PIPE_COOP = LG == 8;             // the forms ragged coverage lands in; the others keep the plain coop loop
     auto row_of_slot = [&](int sl, const void*& sg, int64_t& of, int& qn) {
@@ -568,7 +664,8 @@ void ks_rank_kernel(RankStatsArgs args) {
 #pragma unroll
     for (int r = 0; r < R; ++r) keys[r * ROW + gl] = x[r];
     if constexpr (PACKED) {                        // (the pads go to LDS as +inf: predicated stores, one compare per key)
-      const int real = m - e0;                     // keys of this lane that are samples
+      int real = m - e0;                           // keys of this lane that are samples
+      if constexpr (UNIFORM) asm volatile("" : "+v"(real));   // (per item, or the compiler keeps R lane masks in scalar registers)
 #pragma unroll
       for (int r = 0; r < R; ++r)
         if (r >= real) keys[r * ROW + gl] = inf;
@@ -582,7 +679,9 @@ void ks_rank_kernel(RankStatsArgs args) {
 
     // ---- rank every Q sample into S
     // a sorted group that fills its capacity exactly has no +inf pad: only then can a sample rank above every key
-    const bool s_full = __ballot(m == Lay::C) != 0ull;
+    int m_full = m;
+    if constexpr (UNIFORM) asm volatile("" : "+s"(m_full));       // (a scalar compare per item rather than a register pair across the loop)
+    const bool s_full = UNIFORM ? (m_full == Lay::C) : (__ballot(m == Lay::C) != 0ull);
 
     // rank NV samples (xq) and count them: bin L(x) += 1 << 16, + 1 when x equals the key it landed on (key C is +inf)
     auto rank_and_count = [&](auto nv_tag, auto full_tag, const float* kbase, const float* xq) {
@@ -616,7 +715,9 @@ void ks_rank_kernel(RankStatsArgs args) {
     if (!coop) {
 #pragma unroll 1
       for (int c = 0; c < full_w; ++c) {
-        const Q4Raw rb = load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
+        // (UNIFORM: past the last round the last round again — a load that is never used, from an address that exists)
+        const Q4Raw rb = UNIFORM ? load_q4(sig_q, off_q, min(c + 1, full - 1) * (4 * LG) + 4 * gl, true)
+                                 : load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
         float xa[4];
         q4_values(xa, ra, c < full);
         if (s_full) rank_and_count(std::integral_constant<int, 4>{}, std::true_type{}, keys, xa);
@@ -740,8 +841,14 @@ void ks_rank_kernel(RankStatsArgs args) {
       // its maximum runs over a_{e0+1} .. a_{e0+R} and its minimum over a_{e0} .. a_{e0+R-1} (lane 0 also owns
       // (cumL(0), 0) = a_0): no candidate is seen by two lanes, and the lanes that reach the position's maximum are
       // exactly the ones whose bins the float-form pass has to look at.
-      const int kq_max = __mul24(m - 1, q);                              // (24-bit operands: m <= 2 048, q <= 65 535)
+      // (UNIFORM: a scalar product per item rather than one more scalar register held across the loop — they run out)
+      int m_ev = m;
+      if constexpr (UNIFORM) asm volatile("" : "+s"(m_ev));
+      const int kq_max = __mul24(m_ev - 1, q);                           // (24-bit operands: m <= 2 048, q <= 65 535)
       int kq = min(__mul24(e0, q), kq_max);
+      // (UNIFORM: k*q clamped is the same for every item, and the compiler would keep all R of them in registers — past the
+      // 128 the four waves per SIMD allow.  The running value is recomputed per item, as in the generic instance.)
+      if constexpr (UNIFORM) asm volatile("" : "+v"(kq));
       const int cmax = q - (int)(hist[Lay::word(m)] >> 16);              // cumL(m-1)
       int c = min((int)(cum >> 16), cmax);
       int a = __mul24(c, m) - kq;                                        // a_{e0}
@@ -779,8 +886,11 @@ void ks_rank_kernel(RankStatsArgs args) {
       int cl = (int)(cum >> 16);                                    // cumL(k-1) entering bin k = e0 + 1
       // k = 0: (cumU(0), 0), cumU(0) = the samples below key 0 = cntL[0] - eq[0]
       int hi = (gl == 0) ? __mul24((int)(h0 >> 16) - (int)(h0 & 0xffffu), m) : 0, lo = 0;
-      const int nkq_min = -__mul24(m, q);                           // (24-bit operands: m <= 2 048, q <= 65 535)
+      int m_ev = m;
+      if constexpr (UNIFORM) asm volatile("" : "+s"(m_ev));         // (a scalar product per item: see kq_max above)
+      const int nkq_min = -__mul24(m_ev, q);                        // (24-bit operands: m <= 2 048, q <= 65 535)
       int nkq = -__mul24(e0, q);                                    // (clamped from the first bin on)
+      if constexpr (UNIFORM) asm volatile("" : "+v"(nkq));          // (recomputed per item: see kq above)
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const float up = (r == R - 1) ? s_next : s_own[r + 1];
@@ -811,9 +921,10 @@ void ks_rank_kernel(RankStatsArgs args) {
     double dmax = 0.0;
     if (!args.ks_rational_d) {
       constexpr int BPL = (R + LG - 1) / LG;
-      const double dm = (double)m, dq = (double)q;
+      const double dm = UNIFORM ? u_dm : (double)m, dq = UNIFORM ? u_dq : (double)q;
       double rm, rq;
-      if (uniform) { rm = recip[0]; rq = recip[1]; }
+      if constexpr (UNIFORM) { rm = u_rm; rq = u_rq; }
+      else if (uniform) { rm = recip[0]; rq = recip[1]; }
       else { rm = 1.0 / dm; rq = 1.0 / dq; }
       const int seg_base = lane & ~(LG - 1);
       const unsigned long long hits = __ballot(lbest == best && best != 0u);
@@ -901,8 +1012,8 @@ void ks_rank_kernel(RankStatsArgs args) {
       dmax = seg_allmax_f64<LG>(dmax);
     }
     if (valid && gl == 0) {
-      args.ks_num[pos] = (m > 0 && q > 0) ? best : 0u;
-      args.ks_d_ref[pos] = (m > 0 && q > 0) ? dmax : 0.0;
+      args.ks_num[pos] = (UNIFORM || (m > 0 && q > 0)) ? best : 0u;
+      args.ks_d_ref[pos] = (UNIFORM || (m > 0 && q > 0)) ? dmax : 0.0;
     }
     if constexpr (FLAGS) {
       const unsigned t = seg_allmax_u32<LG>(tie_lane ? 1u : 0u);   // a sample of Q tied with a key of S anywhere in the position
@@ -910,8 +1021,8 @@ void ks_rank_kernel(RankStatsArgs args) {
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0x0F70);
-    if constexpr (PACKED) rows_next.finish_packed(pk, nxt.m, gl);
-    else rows_next.finish(x, nxt.m, gl);
+    if constexpr (PACKED) rows_next.template finish_packed<UNIFORM>(pk, nxt.m, gl);
+    else rows_next.template finish<UNIFORM>(x, nxt.m, gl);
     cur = nxt;
   }
 }

@@ -68,7 +68,8 @@ KernelFn pick_packed(int cm, bool after_count) {
 }
 #else
 // KS-only builds carry only the ks_rank kernels
-KernelFn pick_ks(int cs, bool flags) {
+// uniform: a fixed-stride batch without a position list — the instance that holds the sizes and the schedule as launch constants
+KernelFn pick_ks(int cs, bool flags, bool uniform) {
 #if NMOD_INST_DTYPE == 0
   if (flags) {                 // float32 images of float64 samples: report ties (ks_rank.hpp)
     switch (cs) {
@@ -82,6 +83,16 @@ KernelFn pick_ks(int cs, bool flags) {
   }
 #endif
   (void)flags;
+  if (uniform) {
+    switch (cs) {
+      case 0: return ks_rank_kernel<8, 8, DT, false, true>;
+      case 1: return ks_rank_kernel<16, 8, DT, false, true>;
+      case 2: return ks_rank_kernel<16, 16, DT, false, true>;
+      case 3: return ks_rank_kernel<16, 32, DT, false, true>;
+      case 4: return ks_rank_kernel<16, 64, DT, false, true>;
+      default: return ks_rank_kernel<32, 64, DT, false, true>;
+    }
+  }
   switch (cs) {
     case 0: return ks_rank_kernel<8, 8, DT>;
     case 1: return ks_rank_kernel<16, 8, DT>;
@@ -131,21 +142,23 @@ hipError_t launch_rank_stats(int cls, int num_cus, int64_t work_items, hipStream
               : pick(cls / kNumSizeClasses, cls % kNumSizeClasses);
 #else
   if (!ks) return hipErrorInvalidValue;
-  fn = pick_ks(cls - kKsClassBase, args.tied != nullptr);
+  const bool ks_uniform = args.tied == nullptr && args.stride0 > 0 && args.stride1 > 0 && args.pos_list == nullptr && args.alt_gates == nullptr;
+  fn = pick_ks(cls - kKsClassBase, args.tied != nullptr, ks_uniform);
 #endif
   const size_t lds = rank_stats_lds_bytes(cls, ALL, DT);
   if (ks || packed) {
     const int pw = ks ? ksonly_positions_per_wave(cls - kKsClassBase) : packed_positions_per_wave(cls - kNumGeneralClasses);
     work_items = (work_items + pw - 1) / pw;
   }
-  static std::atomic<int> per_cu_cache[kCacheDevices][2 * kClassStride];     // [class] and [kClassStride + class] for the FLAGS instances
+  // [class], [kClassStride + class] for the FLAGS instances, [2 * kClassStride + class] for the fixed-stride KS instances
+  static std::atomic<int> per_cu_cache[kCacheDevices][3 * kClassStride];
   const int dev = cache_device();
 #if NMOD_INST_ALL
   const int slot_id = cls + (counting ? kClassStride : 0);
   // (one WIDE instance serves every class of the larger group: its limit is that of the largest)
   const size_t lds_limit = wide ? rank_stats_lds_bytes(kWideBigBase + wide_class_of_s(cls), ALL, DT) : lds;
 #else
-  const int slot_id = cls + ((ks && args.tied) ? kClassStride : 0);
+  const int slot_id = cls + ((ks && args.tied) ? kClassStride : ks_uniform ? 2 * kClassStride : 0);
   const size_t lds_limit = lds;
 #endif
   int per_cu = 0;
