@@ -394,10 +394,8 @@ __device__ __forceinline__ void seg_moments_packed16(const unsigned (&p)[8], int
   const double S1 = (double)(int)v;                                           // |S1| <= 256 * 32 768
   const double S2 = seg_allsum_f64<LG>(s2);                                   // <= 256 * 2^30
   const double dn = (double)n;
-  const double num = __fma_rn(dn, S2, -S1 * S1);                              // n * M2 in milli-units^2: every term an integer < 2^53
   const double rn = (rcp_n != 0.0) ? rcp_n : 1.0 / dn;
-  mean = S1 * rn * 1e-3;
-  m2 = num * rn * 1e-6;
+  milli_moments(0.0, S1, S2, dn, rn, mean, m2);                               // (about c = 0; n S2 - S1^2: every term an integer < 2^53)
 }
 
 // second launch-bound argument = minimum waves per SIMD: keeps every form whose LDS footprint allows

@@ -465,8 +465,7 @@ void rank_count_kernel(RankStatsArgs args) {
         } else {
           double S1 = (double)cnt_allsum_i32(i1[g] + xd[g]), S2 = (double)cnt_allsum_i32(i2[g]);   // exact: |S1| < 2^21, S2 < 2^31 (fitting positions)
           if (have_x) S2 += seg_allsum_f64<LG>(xdd[g]);                                          // (wave-uniform) + the tail samples' squares
-          mean[g] = ((double)kfirst[g] + S1 * rn) * 1e-3;
-          m2[g] = __fma_rn(dn, S2, -S1 * S1) * rn * 1e-6;                                       // (n S2 - S1^2: exact integers)
+          milli_moments((double)kfirst[g], S1, S2, dn, rn, mean[g], m2[g]);                      // (the bits rank_hist_kernel writes)
         }
       }
       if (fit && gl == 0) {

@@ -274,7 +274,7 @@ __device__ __forceinline__ void cv_segment(const RankStatsArgs& args, int32_t* w
         } else if constexpr (DTYPE == 1) {
           // exact integers: |S1| <= 4 095 * 1 024 + 128 * 2^16, S2 <= 4 095 * 2^20 + 128 * 2^32; n S2 and S1^2 below 2^53
           const double S1 = (double)(int)cw_wave_sum_u32((unsigned)is1[g]), S2 = (double)wave_sum_u64(is2[g]);
-          mean[g] = ((double)c + S1 * rn) * 1e-3; m2[g] = __fma_rn(dn, S2, -S1 * S1) * rn * 1e-6;
+          milli_moments((double)c, S1, S2, dn, rn, mean[g], m2[g]);
         }
       }
       if (lane == 0) {

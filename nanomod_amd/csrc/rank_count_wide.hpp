@@ -710,8 +710,8 @@ __device__ __forceinline__ void cw_segment(const RankStatsArgs& args, int32_t* w
             t2x = (double)tq_dd;
           }
           const double t1 = (double)(int)t1u, t2 = (double)t2u + t2x;
-          mean_s = ((double)c + s1 * rm) * 1e-3; m2_s = __fma_rn(dm, s2, -s1 * s1) * rm * 1e-6;
-          mean_q = ((double)c + t1 * rq) * 1e-3; m2_q = __fma_rn(dq, t2, -t1 * t1) * rq * 1e-6;
+          milli_moments((double)c, s1, s2, dm, rm, mean_s, m2_s);
+          milli_moments((double)c, t1, t2, dq, rq, mean_q, m2_q);
         }
         if (lane == 0) {
           args.ks_num[pos] = best;

@@ -127,6 +127,11 @@ __device__ __forceinline__ bool grid_key(float x, int& k) {
   else return q == x;
 }
 
+// What a lane without a sample loads in the packed (not WIDE) forms: +inf marks "no sample" from the ranking rounds to the
+// scatter.  (FLT_MAX, the filler of the KS-only kernel, is a value a float32 sample may have: such samples of Q were left out
+// of the scatter and of Q's moments.)  Samples are finite — NMOD_STATUS_NONFINITE otherwise — so +inf is never one.
+static __device__ const float kHistInf4[4] = {__builtin_inff(), __builtin_inff(), __builtin_inff(), __builtin_inff()};
+
 // `phases` odd-even transposition phases over the R x LG keys of every group of the wave (blocked layout): enough to
 // sort a sequence whose elements are at most phases - 1 places from home
 template <int R, int LG>
@@ -212,7 +217,7 @@ void rank_hist_kernel(RankStatsArgs args) {
   unsigned* hist = reinterpret_cast<unsigned*>(keys + HIST_OFF);    // bin j: cntL[j] << 16 | eq[j]; later the prefix table
 
   const float inf = __builtin_inff();
-  const float big = 3.4028234663852886e38f;
+  const float big = WIDE ? 3.4028234663852886e38f : inf;      // "no sample" (packed forms: never a sample's value, see kHistInf4)
   LaneSel sel;
 #pragma unroll
   for (int b = 0; b < 6; ++b) sel.s[b] = ((lane >> b) & 1) ? inf : -inf;
@@ -279,13 +284,14 @@ void rank_hist_kernel(RankStatsArgs args) {
   };
   using Q4Raw = typename std::conditional<DTYPE == 0, KsF4, KsS4>::type;
   using Q1Raw = typename std::conditional<DTYPE == 0, float, int16_t>::type;
-  // unconditional loads (see ks_rank_kernel): lanes without samples read a block of FLT_MAX
+  // unconditional loads (see ks_rank_kernel): lanes without samples read a block of `big` (WIDE: FLT_MAX, never used as a sample)
+  const Q1Raw* const filler = reinterpret_cast<const Q1Raw*>(WIDE ? kKsBig4 : kHistInf4);
   auto load_q4 = [&](const void* sig, int64_t off, int idx, bool have) -> Q4Raw {
-    const Q1Raw* src = have ? reinterpret_cast<const Q1Raw*>(sig) + off + idx : reinterpret_cast<const Q1Raw*>(kKsBig4);
+    const Q1Raw* src = have ? reinterpret_cast<const Q1Raw*>(sig) + off + idx : filler;
     return ks_global_load<Q4Raw>(src);
   };
   auto load_q1 = [&](const void* sig, int64_t off, int idx, bool have) -> Q1Raw {
-    return ks_global_load<Q1Raw>(have ? reinterpret_cast<const Q1Raw*>(sig) + off + idx : reinterpret_cast<const Q1Raw*>(kKsBig4));
+    return ks_global_load<Q1Raw>(have ? reinterpret_cast<const Q1Raw*>(sig) + off + idx : filler);
   };
 
   // fixed-stride batches: every position has the same sizes; fl(1/m) and fl(1/q) are taken once per block and parked
@@ -399,7 +405,7 @@ void rank_hist_kernel(RankStatsArgs args) {
     // ---- rank every Q sample into S and count it in the histograms; keep the sample and the LDS byte offset of its
     // L-bin inside the position's words (16 bits, two per register) for the scatter
     constexpr int NXS = WIDE ? 1 : R, NLA = WIDE ? 1 : R / 2;
-    float xs[NXS];                                 // the samples this lane ranked (FLT_MAX where it had none)
+    float xs[NXS];                                 // the samples this lane ranked (`big` where it had none)
     unsigned la[NLA];                              // byte offsets of their L-bins from `keys`
 #pragma unroll
     for (int r = 0; r < NXS; ++r) xs[r] = big;
@@ -964,9 +970,9 @@ void rank_hist_kernel(RankStatsArgs args) {
       const double KQ = (double)kqf;
       const double s1 = seg_allsum_f64<LG>(s1w), s2 = seg_allsum_f64<LG>(s2w);
       const double rn = rq_w;
-      double mu = KQ + s1 * rn;
-      double qq = s2 - s1 * s1 * rn;
-      if constexpr (DTYPE != 0) { mu = mu * 1e-3; qq = qq * 1e-6; }
+      double mu, qq;
+      if constexpr (DTYPE == 0) { mu = KQ + s1 * rn; qq = s2 - s1 * s1 * rn; }
+      else milli_moments(KQ, s1, s2, (double)q, rn, mu, qq);
       if (valid && gl2 == 0) {
         double* mo = args.moments + pos * 4 + (swap ? 0 : 2);
         mo[0] = mu; mo[1] = qq;
@@ -1006,9 +1012,9 @@ void rank_hist_kernel(RankStatsArgs args) {
       s2 = seg_allsum_f64<LG>(s2);
       const double dn = (double)q;
       const double rn = uniform ? recip[1] : 1.0 / dn;             // one division for mean and M2, none for a fixed-stride batch
-      double mu = KQ + s1 * rn;
-      double qq = s2 - s1 * s1 * rn;
-      if constexpr (DTYPE != 0) { mu = mu * 1e-3; qq = qq * 1e-6; }
+      double mu, qq;
+      if constexpr (DTYPE == 0) { mu = KQ + s1 * rn; qq = s2 - s1 * s1 * rn; }
+      else milli_moments(KQ, s1, s2, dn, rn, mu, qq);
       if (valid && gl2 == 0) {
         double* mo = args.moments + pos * 4 + (swap ? 0 : 2);
         mo[0] = mu; mo[1] = qq;

@@ -166,21 +166,49 @@ __device__ __forceinline__ void load_group(float (&x)[R], const void* sig, int64
   }
 }
 
-// mean and sum of squared deviations in fp64 (two-pass, as np.mean / np.var do)
+// int16 rows: mean and M2 of a group of n keys from its sums about a reference key c, S1 = sum (k - c) and S2 = sum (k - c)^2
+// (exact integers held in doubles; rn = fl(1/n)).  The sum of the keys n c + S1 and n S2 - S1^2 do not depend on c, and each is
+// rounded the same way from there on, so wherever both are exact every K1 form writes the same bits for a position, whichever
+// key it summed about, and the Welch outputs do not depend on which form the probes hand a position to.  Exact means n S2 and
+// S1^2 at most 2^53:
+//   about a sample of the group (rank_hist_kernel, rank_count_kernel; |k - c| < 2^16): n <= 1 024, all these forms hold;
+//   about 0 (rank_pair_kernel, the KS-only packed moments; |k| <= 2^15): n S2 <= n^2 2^30, n <= 2 048;
+//   about the centre of a counting window (rank_count_wide_kernel, rank_count_value_kernel): at most 4 095 samples within
+//   2^11 of c and 128 anywhere, n S2 < 2^12 (2^34 + 2^39).
+// The mean's quotient takes one correction step (q + (x - q n) fl(1/n), the correctly rounded x / n): a constant group of any size
+// then has exactly its value for a mean, so two constant groups of one value have equal means and Welch's t is 0 / 0 = NaN as in
+// the reference, not the quotient of two rounding errors.
+__device__ __forceinline__ void milli_moments(double c, double S1, double S2, double dn, double rn, double& mean, double& m2) {
+  const double x = __fma_rn(dn, c, S1);
+  const double q = __dmul_rn(x, rn);
+  mean = __dmul_rn(__fma_rn(__fma_rn(-q, dn, x), rn, q), 1e-3);
+  m2 = __dmul_rn(__dmul_rn(__fma_rn(dn, S2, -S1 * S1), rn), 1e-6);
+}
+
+// mean and sum of squared deviations in fp64.  float32: two-pass, as np.mean / np.var do.  int16 keys: one pass of exact integer
+// sums about 0, finished by milli_moments — the bits the counting forms write for the same position.
 template <int R, int DTYPE>
 __device__ __forceinline__ void group_moments(const float (&x)[R], int n, int lane, double& mean, double& m2) {
-  const double scale = (DTYPE == 0) ? 1.0 : 1e-3;
   double s = 0.0;
+  if constexpr (DTYPE != 0) {
+    double s2 = 0.0;
 #pragma unroll
-  for (int r = 0; r < R; ++r) if (r * 64 + lane < n) s += (double)x[r];
-  s = wave_sum_f64(s);
-  double mu = s / (double)n;                 // in sample units
-  double q = 0.0;
+    for (int r = 0; r < R; ++r) if (r * 64 + lane < n) { const double k = (double)x[r]; s += k; s2 = __fma_rn(k, k, s2); }
+    s = wave_sum_f64(s);                        // (integers below 2^53 at every step: exact in any order)
+    s2 = wave_sum_f64(s2);
+    const double dn = (double)n;
+    milli_moments(0.0, s, s2, dn, 1.0 / dn, mean, m2);
+  } else {
 #pragma unroll
-  for (int r = 0; r < R; ++r) if (r * 64 + lane < n) { double d = (double)x[r] - mu; q += d * d; }
-  q = wave_sum_f64(q);
-  if constexpr (DTYPE == 0) { mean = mu; m2 = q; }
-  else { mean = s / 1000.0 / (double)n; m2 = q * (scale * scale); }
+    for (int r = 0; r < R; ++r) if (r * 64 + lane < n) s += (double)x[r];
+    s = wave_sum_f64(s);
+    const double mu = s / (double)n;
+    double q = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) if (r * 64 + lane < n) { double d = (double)x[r] - mu; q += d * d; }
+    q = wave_sum_f64(q);
+    mean = mu; m2 = q;
+  }
 }
 
 // store the sorted registers (blocked layout) to LDS: element lane*R + r

@@ -121,7 +121,8 @@ __device__ __forceinline__ void load_packed(float (&x)[R], const void* sig, int6
 // mean and sum of squared deviations of one group in fp64; pads are +inf.  One pass over the keys, shifted by the
 // group's first sample K:  mean = K + S1/n,  M2 = S2 - S1^2/n  with S1 = sum (x - K), S2 = sum (x - K)^2.
 // The shift keeps the cancellation in M2 at ~(1 + (mean - K)^2 / var) ulps of fp64 — np.var's two-pass result to
-// ~1e-14 — for half the instructions of two masked passes (a pad becomes K: it adds 0 to both sums).
+// ~1e-14 — for half the instructions of two masked passes (a pad becomes K: it adds 0 to both sums).  int16 keys: S1 and S2
+// are exact, and milli_moments (rank_stats.hpp) finishes them.
 template <int R, int LG, int DTYPE>
 __device__ __forceinline__ void seg_moments(const float (&x)[R], int n, double& mean, double& m2, double rcp_n = 0.0) {
   const float inf = __builtin_inff();
@@ -142,10 +143,8 @@ __device__ __forceinline__ void seg_moments(const float (&x)[R], int n, double& 
   s2 = seg_allsum_f64<LG>(s2);
   const double dn = (double)n;
   const double rn = (rcp_n != 0.0) ? rcp_n : 1.0 / dn;                // one division for mean and M2 (none when the caller has fl(1/n))
-  const double mu = K + s1 * rn;
-  const double q = s2 - s1 * s1 * rn;
-  if constexpr (DTYPE == 0) { mean = mu; m2 = q; }
-  else { mean = mu * 1e-3; m2 = q * 1e-6; }
+  if constexpr (DTYPE == 0) { mean = K + s1 * rn; m2 = s2 - s1 * s1 * rn; }
+  else milli_moments(K, s1, s2, dn, rn, mean, m2);                    // (int16 keys: both sums are exact integers)
 }
 
 }  // namespace nmod
