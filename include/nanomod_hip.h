@@ -493,6 +493,52 @@ int nmod_one_sample(const nmod_params* prm, int64_t npos, const void* sig, const
                     const double* ref_mean, const double* ref_sd, const int32_t* ref_n /* may be NULL */,
                     const int32_t* run_id, const nmod_one_out* out);
 
+/* K-mer level models from a control run (K10; the reference project has no such step).  The table nmod_one_sample's "model" kind of
+ * reference comes from: every position of a read group carries the code of the k-mer it sits in (nanomod_amd.kmermodel.kmer_codes),
+ * and the samples of all positions of a code are pooled into that code's level and spread.
+ *   Position i belongs to code c = code[i].  Its samples are taken as doubles: float32 up-cast, int16 as k / 1000.0 (a division,
+ *     as K9 does), float64 as is.
+ *   A sample x of a position of code c is KEPT iff keep_lo[c] <= x && x <= keep_hi[c].  The bounds are inclusive; a NaN bound keeps
+ *     nothing; without bounds (both NULL) everything is kept.
+ *   A position is dropped whole, and flagged in pos_status, when it has
+ *     NMOD_STATUS_NO_CODE     code[i] < 0 (device memory: outside [0, ncodes) — never an out-of-range write),
+ *     NMOD_STATUS_EMPTY       n == 0,
+ *     NMOD_STATUS_TOO_LARGE   n > NMOD_MAX_DEEP,
+ *     NMOD_STATUS_NONFINITE   a NaN or infinite sample (exact: every sample is seen; kept or not makes no difference).
+ *     The first three are set together where they apply together; the samples of a position they drop are not looked at, so it never
+ *     carries NMOD_STATUS_NONFINITE.  A position that is not dropped has status 0.
+ *   Per code, over the kept samples of its remaining positions: n_samples = N, n_clipped = the samples not kept, n_positions = the
+ *     positions with at least one kept sample, mean, and sd with ddof = 0 over the POOLED SAMPLES — the total spread around the
+ *     k-mer's level (within and between positions), which is what a per-position prediction from the table has to carry.  N == 0
+ *     gives mean = sd = NaN.
+ *   int16 is exact: S1 = sum k in int64, S2 = sum k^2 in uint64 (a row of 2^24 - 1 samples of +-32 767 fits), V = N S2 - S1^2 in 128
+ *     bits, mean = ((double)S1 / (double)N) / 1000.0, sd = sqrt((double)V) / (double)N / 1000.0 with (double)V correctly rounded.
+ *     Limit: fewer than 2^32 samples (kept plus clipped) per code.  Integer sums are order-free: the int16 result is bit-identical
+ *     under any permutation of the positions.
+ *   float32 / float64: per position (n, mean, M2) over its kept samples in fp64 (two passes about the mean, with the correction
+ *     term), combined per code with the pairwise update of Chan, Golub and LeVeque in a fixed order: the code's positions in index
+ *     order, rank r on lane r mod 64 chained over r, then a fixed tree over the lanes.  No float atomics: the bits of a code's
+ *     outputs depend on that code's positions only (their samples and their relative order), not on the other positions of the
+ *     batch, CSR versus stride, the memspace or the CU count.
+ * A NULL member of `out` is skipped; out->struct_size = sizeof(nmod_kmer_out).  Rows: CSR when `off` is given, else the fixed stride
+ * prm->stride0.  Reads struct_size, device, stream, memspace, dtype, stride0 of prm and nothing else.  NMOD_MEM_DEVICE: everything
+ * is enqueued on prm->stream, the scratch (40 bytes per code for int16; 48 bytes per position for floats) comes stream-ordered from
+ * the library's pool, and the call returns WITHOUT synchronising.  NMOD_MEM_HOST: copy in, run, copy back, synchronise (one staged
+ * copy, like K8 / K9).  npos == 0 is NMOD_OK with zero counts and NaN mean / sd.  NMOD_ERR_INVALID_ARG before any device work: npos
+ * < 0 or beyond 2^31 - 2, ncodes outside 1 .. NMOD_MAX_KMER_CODES, out NULL (or of another struct_size), a NULL sig / code with npos
+ * > 0, neither offsets nor a stride, an unknown dtype, exactly one of keep_lo / keep_hi, host offsets that decrease, and (host memory
+ * only) a code outside [-1, ncodes).  int16 is the streaming form (every sample byte read once); the float forms are not tuned. */
+#define NMOD_MAX_KMER_CODES 65536          /* 4^8 */
+#define NMOD_STATUS_NO_CODE 64             /* nmod_kmer_model only: code[i] < 0 (or, device memory, outside [-1, ncodes)): the position takes no part */
+typedef struct nmod_kmer_out { int32_t struct_size; int32_t reserved;
+  int64_t *n_positions, *n_samples, *n_clipped;   /* ncodes each; a NULL member is skipped */
+  double  *mean, *sd;                              /* ncodes each */
+  uint8_t *pos_status;                             /* npos, optional */ } nmod_kmer_out;
+int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void* sig, const int64_t* off /* or prm->stride0 */,
+                    const int32_t* code, int32_t ncodes,
+                    const double* keep_lo, const double* keep_hi /* ncodes each, both NULL = keep everything */,
+                    const nmod_kmer_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -22,12 +22,14 @@ FLAG_DEEP = 32            # groups beyond MAX_RANKED (up to MAX_DEEP) take the d
 FLAG_K1_STATIC_ITEMS = 128   # the KS-only K1 kernel walks equal strided shares instead of claiming chunks of items (A/B, parity tests)
 STATUS_MWU_ALL_IDENTICAL, STATUS_T_NAN, STATUS_EMPTY, STATUS_TOO_LARGE, STATUS_NONFINITE = 1, 2, 4, 8, 16
 STATUS_BAD_REFERENCE = 32   # nmod_one_sample only: an unusable reference (mean / sd not finite, sd <= 0, ref_n < 2)
+STATUS_NO_CODE = 64         # nmod_kmer_model only: the position has no k-mer code and takes no part
 KERNEL_RANK_STATS, KERNEL_FINALIZE, KERNEL_COMBINE, KERNEL_SYNTH = 0, 1, 2, 3
 MAX_GROUP = 2048          # largest group of the wave-resident kernels; larger ones (<= MAX_RANKED) take big_rank_kernel
 MAX_RANKED = 65535
 MAX_DEEP = 2 ** 24 - 1    # largest group with FLAG_DEEP
 MAX_NB = 64
 MAX_ONE, MAX_ONE_F64 = 16384, 8192   # nmod_one_sample: samples per position (float32 / int16, float64)
+MAX_KMER_CODES = 65536    # nmod_kmer_model: 4^8
 COMM_ID_BYTES = 128
 ERR_NO_RCCL, ERR_RCCL = -6, -7
 
@@ -99,6 +101,22 @@ def make_one_out(**members):
     return o
 
 
+KMER_COUNT_FIELDS = ('n_positions', 'n_samples', 'n_clipped')
+KMER_FIELDS = KMER_COUNT_FIELDS + ('mean', 'sd')
+
+
+class NmodKmerOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(name, C.c_void_p) for name in KMER_FIELDS] + [('pos_status', C.c_void_p)]
+
+
+def make_kmer_out(**members):
+    o = NmodKmerOut()
+    o.struct_size = C.sizeof(NmodKmerOut)
+    for k, v in members.items():
+        setattr(o, k, v)
+    return o
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -152,6 +170,8 @@ _SIGNATURES = {
     'nmod_mix_fraction': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_double, C.c_void_p, C.c_double, C.POINTER(NmodMixOut)]),
     'nmod_one_sample': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(NmodOneOut)]),
+    'nmod_kmer_model': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.POINTER(NmodKmerOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -101,7 +101,75 @@ def build_parser():
     o.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'],
                    help='bh / by: q-values of the t, KS and combined p-value tracks, written to <FileID>_one_sample_fdr.txt')
     o.add_argument('--fdrAlpha', type=float, default=0.05)
+    km = sub.add_parser('kmermodel', help='pool a control read group into a k-mer level model (level and spread per k-mer) on the device')
+    km.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    km.add_argument('--wrkBase1', required=True, help='the control read group: a per-position .npz container')
+    km.add_argument('--kmer', type=int, default=5, help='k, 1 .. 8')
+    km.add_argument('--kmerCenter', type=int, default=2, help='offset of the position inside its k-mer in read direction, 0 .. k - 1')
+    km.add_argument('--MinCoverage', type=int, default=5)
+    km.add_argument('--clipSigma', type=float, default=0.0, help='> 0: re-estimate from the samples within mean +- clipSigma * sd per k-mer')
+    km.add_argument('--clipRounds', type=int, default=2, help='clipping passes after the plain one (with --clipSigma > 0)')
+    km.add_argument('--outFolder', default='mRes')
+    km.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_kmer_model.npz and <FileID>_kmer_model.txt')
+    km.add_argument('--device', type=int, default=0)
+    kp = sub.add_parser('kmerprofile', help="the 'model' profile a k-mer model predicts for the positions of a read group, for detect1")
+    kp.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    kp.add_argument('--kmerModel', required=True, help="a k-mer model written by 'kmermodel'")
+    kp.add_argument('--wrkBase1', required=True, help='the sample read group: a per-position .npz container')
+    kp.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    kp.add_argument('--outFolder', default='mRes')
+    kp.add_argument('--FileID', default='mod', help='the profile is written to <outFolder>/<FileID>_profile.npz')
     return p
+
+
+def validate_kmer(a):
+    """the checks of kmermodel / kmerprofile"""
+    errs = []
+    inputs = [a.wrkBase1]
+    if a.cmd == 'kmermodel':
+        if a.MinCoverage < 3:
+            errs.append('Error: --MinCoverage should be not less than 3')
+        if not 1 <= a.kmer <= 8:
+            errs.append('Error: --kmer should be in 1 .. 8')
+        elif not 0 <= a.kmerCenter < a.kmer:
+            errs.append('Error: --kmerCenter should be in 0 .. kmer - 1')
+        if not 0.0 <= a.clipSigma < float('inf'):
+            errs.append('Error: --clipSigma should be finite and not negative')
+        if a.clipRounds < 0:
+            errs.append('Error: --clipRounds should not be negative')
+    else:
+        inputs.append(a.kmerModel)
+        if a.minPositions < 1:
+            errs.append('Error: --minPositions should be larger than 0')
+    for f in inputs:
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    return errs
+
+
+def run_kmermodel(a, log=print):
+    from . import kmermodel
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    model = kmermodel.build_kmer_model(container.load_group(a.wrkBase1), a.kmer, a.kmerCenter, a.MinCoverage, a.clipSigma, a.clipRounds,
+                                       a.device, (lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_kmer_model.npz')
+    kmermodel.save_kmer_model(path, model)
+    kmermodel.write_kmer_table(os.path.join(a.outFolder, a.FileID + '_kmer_model.txt'), model)
+    if not quiet:
+        log('K-mer model is saved in %s' % path)
+    return model
+
+
+def run_kmerprofile(a, log=print):
+    from . import kmermodel, onesample
+    prof = kmermodel.model_profile(kmermodel.load_kmer_model(a.kmerModel), container.load_group(a.wrkBase1), a.minPositions)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_profile.npz')
+    onesample.save_profile(path, prof)
+    if a.outLevel <= detect.OUTPUT_ERROR:
+        log('Profile of %d positions is saved in %s' % (len(prof['pos']), path))
+    return prof
 
 
 def validate1(a):
@@ -435,6 +503,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd in ('kmermodel', 'kmerprofile'):
+        errs = validate_kmer(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_kmermodel(a) if a.cmd == 'kmermodel' else run_kmerprofile(a)
+        return 0
     if a.cmd in ('profile', 'detect1'):
         errs = validate1(a)
         if errs:

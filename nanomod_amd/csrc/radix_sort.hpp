@@ -135,12 +135,15 @@ inline size_t rs_scratch_bytes(int64_t n) {
   return (size_t)(m + (m + kRsScanChunk - 1) / kRsScanChunk + 1) * 4;
 }
 // keys / vals: the pairs, sorted in place (ascending keys, stable); keys_tmp / vals_tmp: as large.  n < 2^31.
-inline hipError_t rs_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint32_t* vals_tmp, int64_t n, void* scratch, hipStream_t stream) {
+// passes < 8: only the low `passes` bytes of the keys are sorted by (the others must be equal); after an odd number of passes
+// the result is in keys_tmp / vals_tmp.
+inline hipError_t rs_sort_pairs(uint64_t* keys, uint32_t* vals, uint64_t* keys_tmp, uint32_t* vals_tmp, int64_t n, void* scratch, hipStream_t stream,
+                                int passes = 8) {
   if (n <= 0) return hipSuccess;
   const int64_t ntiles = rs_tiles(n), m = 256 * ntiles, nb = (m + kRsScanChunk - 1) / kRsScanChunk;
   uint32_t* hist = static_cast<uint32_t*>(scratch);
   uint32_t* bsum = hist + m;
-  for (int pass = 0; pass < 8; ++pass) {
+  for (int pass = 0; pass < passes; ++pass) {
     const uint64_t* ksrc = (pass & 1) ? keys_tmp : keys; const uint32_t* vsrc = (pass & 1) ? vals_tmp : vals;
     uint64_t* kdst = (pass & 1) ? keys : keys_tmp; uint32_t* vdst = (pass & 1) ? vals : vals_tmp;
     hipLaunchKernelGGL(rs_hist_kernel, dim3((unsigned)ntiles), dim3(kRsThreads), 0, stream, ksrc, n, 8 * pass, ntiles, hist);

@@ -320,6 +320,46 @@ def one_sample_host(sig, off, ref_mean, ref_sd, ref_n=None, run_id=None, *, stri
     return res
 
 
+def kmer_model_host(sig, off, code, ncodes, keep_lo=None, keep_hi=None, *, stride=0, device=0):
+    """Per-code level models of host-resident rows (nmod_kmer_model, include/nanomod_hip.h): sig float32, int16 (milli-units) or
+    float64, rows by `off` (int64[npos + 1]) or a fixed `stride`; code int32[npos] in [-1, ncodes) (-1: the position takes no part);
+    keep_lo / keep_hi float64[ncodes] (inclusive bounds of the kept samples per code) or both None.  Returns a dict of numpy arrays:
+    n_positions, n_samples, n_clipped (int64[ncodes]), mean, sd (float64[ncodes], NaN for a code without kept samples) and
+    pos_status (uint8[npos], L.STATUS_* bits of the positions dropped whole)."""
+    lib = L.load()
+    _join_warm_up(device)
+    sig = np.ascontiguousarray(sig)
+    if sig.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('sig must be float32, int16 (milli-units) or float64')
+    code = np.ascontiguousarray(code, dtype=np.int32)
+    npos = code.shape[0]
+    off = None if off is None else np.ascontiguousarray(off, dtype=np.int64)
+    _check_csr(off, npos, 'off')
+    if code.ndim != 1:
+        raise ValueError('code must be int32[npos]')
+    if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
+        raise ValueError('sig is shorter than its offsets / stride say')
+    ncodes = int(ncodes)
+    if (keep_lo is None) != (keep_hi is None):
+        raise ValueError('keep_lo and keep_hi come together')
+    if keep_lo is not None:
+        keep_lo = np.ascontiguousarray(keep_lo, dtype=np.float64)
+        keep_hi = np.ascontiguousarray(keep_hi, dtype=np.float64)
+        if keep_lo.shape != (ncodes,) or keep_hi.shape != (ncodes,):
+            raise ValueError('keep_lo / keep_hi must be float64[ncodes]')
+    m = max(ncodes, 0)
+    res = {k: np.empty(m, dtype=np.int64) for k in L.KMER_COUNT_FIELDS}
+    res['mean'] = np.empty(m, dtype=np.float64)
+    res['sd'] = np.empty(m, dtype=np.float64)
+    res['pos_status'] = np.empty(npos, dtype=np.uint8)
+    out = L.make_kmer_out(**{k: _np_ptr(a) for k, a in res.items()})
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(sig.dtype), stride0=stride if off is None else 0)
+    rc = lib.nmod_kmer_model(C.byref(prm), npos, _np_ptr(sig), _np_ptr(off), _np_ptr(code), ncodes, _np_ptr(keep_lo), _np_ptr(keep_hi),
+                             C.byref(out))
+    L.check(rc, 'nmod_kmer_model')
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -587,6 +627,35 @@ class DeviceDetector:
         ptr = lambda t: (t.data_ptr() if t is not None else None)
         rc = self.lib.nmod_one_sample(C.byref(prm), npos, ptr(sig), ptr(off), ptr(ref_mean), ptr(ref_sd), ptr(ref_n), ptr(run_id), C.byref(o))
         L.check(rc, 'nmod_one_sample')
+        return res
+
+    def kmer_model(self, sig, code, ncodes, keep_lo=None, keep_hi=None, *, off=None, stride=0, npos=None, out=None):
+        """Per-code level models (nmod_kmer_model, NMOD_MEM_DEVICE), enqueued on the current stream without synchronising.  sig:
+        float32, int16 or float64 CUDA rows by `off` (int64 CUDA tensor) or a fixed `stride`; code: int32 CUDA vector (a value outside
+        [0, ncodes): the position takes no part, L.STATUS_NO_CODE); keep_lo / keep_hi: float64 CUDA vectors of ncodes inclusive bounds,
+        or both None.  Returns a dict of CUDA tensors: n_positions, n_samples, n_clipped (int64), mean, sd (float64), each of ncodes,
+        and pos_status (uint8, npos).  int16 is the streaming form; the float dtypes are not tuned."""
+        torch = self.torch
+        dtype = self._dtype_of(sig)
+        if npos is None:
+            npos = code.numel()
+        ncodes = int(ncodes)
+        dev = 'cuda:%d' % self.device
+        for t, dt, name, m in ((code, torch.int32, 'code', npos), (off, torch.int64, 'off', npos + 1),
+                               (keep_lo, torch.float64, 'keep_lo', ncodes), (keep_hi, torch.float64, 'keep_hi', ncodes)):
+            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == m):
+                raise ValueError('kmer_model: %s must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
+        res = out
+        if res is None:
+            res = {k: torch.empty(max(ncodes, 0), dtype=torch.int64, device=dev) for k in L.KMER_COUNT_FIELDS}
+            res['mean'] = torch.empty(max(ncodes, 0), dtype=torch.float64, device=dev)
+            res['sd'] = torch.empty(max(ncodes, 0), dtype=torch.float64, device=dev)
+            res['pos_status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
+        o = L.make_kmer_out(**{k: t.data_ptr() for k, t in res.items()})
+        prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
+        ptr = lambda t: (t.data_ptr() if t is not None else None)
+        rc = self.lib.nmod_kmer_model(C.byref(prm), npos, ptr(sig), ptr(off), ptr(code), ncodes, ptr(keep_lo), ptr(keep_hi), C.byref(o))
+        L.check(rc, 'nmod_kmer_model')
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
