@@ -19,11 +19,25 @@ def runs(lengths, first=0, step=1):
     return np.repeat(first + step * np.arange(len(lengths), dtype=np.int64), lengths)
 
 
+F64_UNIT = 2.0 ** -40
+
+
 def values(case, dtype):
-    """the two groups as the library's input arrays"""
+    """the two groups as the library's input arrays.  Further dtypes of big_cases.py: 'g32' — float32 on the milli-unit grid,
+    units / 1000 in float32 arithmetic (what grid_key of rank_hist.hpp accepts for |units| <= 32 767); 'f64' — float64; a case with
+    'kind' set says which doubles: 'redo' 1.0 + units * 2^-40 (every float32 image is 1.0, the doubles order and tie as the units
+    do: neither float32-exact nor on the grid unless every unit is 0), 'exact' units * 2^-11 (float32-exact), 'grid' units / 1000"""
+    if dtype == 'f64':
+        kind = case['kind']
+        f = lambda u: 1.0 + u * F64_UNIT if kind == 'redo' else (u * F32_UNIT if kind == 'exact' else u / 1000.0)
+        assert kind in ('redo', 'exact', 'grid') and max(np.abs(case['a']).max(), np.abs(case['b']).max()) < 2 ** 12
+        return f(case['a'].astype(np.float64)), f(case['b'].astype(np.float64))
     if case.get('f32'):
         assert dtype == 'f32'
         return case['a'], case['b']
+    if dtype == 'g32':
+        assert max(np.abs(case['a']).max(), np.abs(case['b']).max()) <= 32767
+        return case['a'].astype(np.float32) / np.float32(1000.0), case['b'].astype(np.float32) / np.float32(1000.0)
     if dtype == 'f32':
         return (case['a'] * F32_UNIT).astype(np.float32), (case['b'] * F32_UNIT).astype(np.float32)
     assert min(case['a'].min(), case['b'].min()) >= -32768 and max(case['a'].max(), case['b'].max()) <= 32767
