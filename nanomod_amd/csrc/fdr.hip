@@ -21,9 +21,9 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
+#include "entry_common.hpp"
+#include "entry_device.hpp"
 #include "radix_sort.hpp"
-#include "scratch_pool.hpp"
-#include "wave_ops.hpp"
 
 namespace nmod {
 
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kFdrThreads) void fdr_apply_kernel(const uint64_t* 
         qv = fmin(1.0, __longlong_as_double((long long)run));
         if (qv <= alpha) { ++rej; maxkey = key[e] > maxkey ? key[e] : maxkey; }
       } else {
-        qv = __longlong_as_double(0x7FF8000000000000ll);
+        qv = nan_f64();
       }
       q[idx[r]] = qv;
     }
@@ -223,12 +223,8 @@ __global__ void fdr_summary_kernel(const FdrState* st, int64_t n, nmod_fdr_summa
   out->tested = (int64_t)st->m;
   out->excluded = n - (int64_t)st->m;
   out->rejected = (int64_t)st->rejected;
-  out->p_crit = __longlong_as_double(st->rejected ? (long long)st->maxkey : 0x7FF8000000000000ll);
+  out->p_crit = st->rejected ? __longlong_as_double((long long)st->maxkey) : nan_f64();
 }
-
-#define NMOD_FDR_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
-
-static inline size_t fdr_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace nmod
 
@@ -236,42 +232,39 @@ using namespace nmod;
 
 extern "C" int nmod_fdr_adjust(const nmod_params* prm, int64_t n, int32_t ntracks, const double* const* p, int32_t method, double alpha,
                                double* const* q_out, nmod_fdr_summary* summary) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params)) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;       // (a p-value track is fp64)
   if (n < 0 || n > (int64_t)INT32_MAX - 1 || ntracks < 1 || ntracks > 8 || !p || !q_out) return NMOD_ERR_INVALID_ARG;
   if (method != NMOD_FDR_BH && method != NMOD_FDR_BY) return NMOD_ERR_INVALID_ARG;
   if (!(alpha > 0.0 && alpha <= 1.0)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_HOST && prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
   for (int t = 0; n > 0 && t < ntracks; ++t) if (!p[t] || !q_out[t]) return NMOD_ERR_INVALID_ARG;      // (an empty track has no address)
   const bool host = prm->memspace == NMOD_MEM_HOST;
   if (n == 0 && (host || !summary)) {
     for (int t = 0; summary && t < ntracks; ++t) { memset(&summary[t], 0, sizeof(summary[t])); summary[t].p_crit = NAN; }
     return NMOD_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) { (void)hipGetLastError(); return NMOD_ERR_NO_DEVICE; }
-  NMOD_FDR_HIP(hipSetDevice(prm->device));
+  const int rc = select_device(prm, nullptr);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const size_t cnt = (size_t)n;
   const int64_t ntiles = (n + kFdrTile - 1) / kFdrTile;
 
-  // one slab: keys, keys_tmp, tile minima, per-track state, summaries (host entry), the track (host entry), idx, idx_tmp, histogram
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t at = off; off += fdr_up(bytes); return at; };
-  const size_t o_keys = take(cnt * 8), o_keys_tmp = take(cnt * 8), o_tmin = take((size_t)(ntiles + 1) * 8);
-  const size_t o_state = take(sizeof(FdrState) * 8), o_sum = take(sizeof(nmod_fdr_summary) * 8);
-  const size_t o_track = take(host ? cnt * 8 : 0), o_idx = take(cnt * 4), o_idx_tmp = take(cnt * 4);
-  const size_t o_hist = take(n ? rs_scratch_bytes(n) : 0);
-  DevScratch slab;
-  NMOD_FDR_HIP(slab.alloc(off, stream, prm->device));
-  char* base = static_cast<char*>(slab.p);
-  uint64_t* keys = (uint64_t*)(base + o_keys); uint64_t* keys_tmp = (uint64_t*)(base + o_keys_tmp); uint64_t* tmin = (uint64_t*)(base + o_tmin);
-  FdrState* state = (FdrState*)(base + o_state);
-  nmod_fdr_summary* dsum = host ? (nmod_fdr_summary*)(base + o_sum) : summary;
-  double* dtrack = (double*)(base + o_track);
-  uint32_t* idx = (uint32_t*)(base + o_idx); uint32_t* idx_tmp = (uint32_t*)(base + o_idx_tmp);
-  void* hist = base + o_hist;
+  // one slab: keys, keys_tmp, tile minima, per-track state, idx, idx_tmp, histogram; for the host entry one track (the tracks
+  // go through it one after another) and the summaries
+  Slab slab(host);
+  const size_t o_keys = slab.take(cnt * 8), o_keys_tmp = slab.take(cnt * 8), o_tmin = slab.take((size_t)(ntiles + 1) * 8);
+  const size_t o_state = slab.take(sizeof(FdrState) * 8);
+  const size_t o_track = slab.take(host ? cnt * 8 : 0), o_idx = slab.take(cnt * 4), o_idx_tmp = slab.take(cnt * 4);
+  const size_t o_hist = slab.take(n ? rs_scratch_bytes(n) : 0);
+  nmod_fdr_summary* dsum = summary;
+  slab.out(dsum, sizeof(nmod_fdr_summary) * (size_t)ntracks);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  uint64_t* keys = slab.at<uint64_t>(o_keys); uint64_t* keys_tmp = slab.at<uint64_t>(o_keys_tmp); uint64_t* tmin = slab.at<uint64_t>(o_tmin);
+  FdrState* state = slab.at<FdrState>(o_state);
+  double* dtrack = slab.at<double>(o_track);
+  uint32_t* idx = slab.at<uint32_t>(o_idx); uint32_t* idx_tmp = slab.at<uint32_t>(o_idx_tmp);
+  void* hist = slab.at<char>(o_hist);
 
-  NMOD_FDR_HIP(hipMemsetAsync(state, 0, sizeof(FdrState) * 8, stream));
+  NMOD_HIP(hipMemsetAsync(state, 0, sizeof(FdrState) * 8, stream));
   const unsigned kblocks = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   for (int t = 0; t < ntracks; ++t) {             // one after another through the same scratch
     FdrState* st = state + t;
@@ -279,26 +272,22 @@ extern "C" int nmod_fdr_adjust(const nmod_params* prm, int64_t n, int32_t ntrack
     double* dst = q_out[t];
     if (n > 0) {
       if (host) {
-        NMOD_FDR_HIP(hipMemcpyAsync(dtrack, p[t], cnt * 8, hipMemcpyHostToDevice, stream));
+        NMOD_HIP(hipMemcpyAsync(dtrack, p[t], cnt * 8, hipMemcpyHostToDevice, stream));
         src = dtrack; dst = dtrack;
       }
       hipLaunchKernelGGL(fdr_key_kernel, dim3(kblocks), dim3(256), 0, stream, src, n, keys, idx, st);
-      NMOD_FDR_HIP(rs_sort_pairs(keys, idx, keys_tmp, idx_tmp, n, hist, stream));
+      NMOD_HIP(rs_sort_pairs(keys, idx, keys_tmp, idx_tmp, n, hist, stream));
       if (method == NMOD_FDR_BY) hipLaunchKernelGGL(fdr_cm_kernel, dim3(1), dim3(64), 0, stream, st);
       hipLaunchKernelGGL(fdr_tile_min_kernel, dim3((unsigned)ntiles), dim3(kFdrThreads), 0, stream, (const uint64_t*)keys, n,
                          (const FdrState*)st, (int)method, tmin);
       hipLaunchKernelGGL(fdr_tile_suffix_kernel, dim3(1), dim3(kFdrThreads), 0, stream, tmin, ntiles);
       hipLaunchKernelGGL(fdr_apply_kernel, dim3((unsigned)ntiles), dim3(kFdrThreads), 0, stream, (const uint64_t*)keys, (const uint32_t*)idx, n,
                          st, (int)method, alpha, (const uint64_t*)tmin, dst);
-      if (host) NMOD_FDR_HIP(hipMemcpyAsync(q_out[t], dtrack, cnt * 8, hipMemcpyDeviceToHost, stream));
+      if (host) NMOD_HIP(hipMemcpyAsync(q_out[t], dtrack, cnt * 8, hipMemcpyDeviceToHost, stream));
     }
     if (dsum) hipLaunchKernelGGL(fdr_summary_kernel, dim3(1), dim3(64), 0, stream, (const FdrState*)st, n, dsum + t);
   }
-  NMOD_FDR_HIP(hipGetLastError());
-  if (host) {
-    if (summary) NMOD_FDR_HIP(hipMemcpyAsync(summary, dsum, sizeof(nmod_fdr_summary) * (size_t)ntracks, hipMemcpyDeviceToHost, stream));
-    NMOD_FDR_HIP(hipStreamSynchronize(stream));
-  }
-  NMOD_FDR_HIP(slab.release(stream));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(slab.finish(stream));
   return NMOD_OK;
 }

@@ -29,9 +29,9 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
+#include "entry_common.hpp"
+#include "entry_device.hpp"
 #include "radix_sort.hpp"
-#include "scratch_pool.hpp"
-#include "wave_ops.hpp"
 
 namespace nmod {
 
@@ -55,8 +55,6 @@ struct KmArgs {
   double* pmean; double* pm2; int32_t* pn; int32_t* pcl; uint64_t* key; uint32_t* val;
   nmod_kmer_out out;
 };
-
-__device__ __forceinline__ double km_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 __device__ __forceinline__ void km_row(const KmArgs& a, int64_t i, int64_t& begin, int64_t& end) {
   if (a.off) { begin = a.off[i]; end = a.off[i + 1]; } else { begin = i * a.stride; end = begin + a.stride; }
@@ -344,7 +342,7 @@ __global__ __launch_bounds__(256) void km_finish_i16_kernel(KmArgs a) {
   const unsigned long long n = a.acc[c], s2 = a.acc[2 * (size_t)nc + c];
   const long long s1 = (long long)a.acc[(size_t)nc + c];
   km_write_counts(a.out, c, (long long)n, (long long)a.acc[3 * (size_t)nc + c], (long long)a.acc[4 * (size_t)nc + c]);
-  double mean = km_nan(), sd = km_nan();
+  double mean = nan_f64(), sd = nan_f64();
   if (n) {
     const unsigned long long m1 = (unsigned long long)(s1 < 0 ? -s1 : s1);
     const unsigned __int128 v = (unsigned __int128)n * s2 - (unsigned __int128)m1 * m1;   // >= 0 (Cauchy-Schwarz)
@@ -463,21 +461,16 @@ __global__ __launch_bounds__(256) void km_combine_kernel(KmArgs a, const uint64_
     ns = wave_sum_u64(ns); ncl = wave_sum_u64(ncl); npo = wave_sum_u64(npo);
     if (lane == 0) {
       km_write_counts(a.out, c, (long long)ns, (long long)npo, (long long)ncl);
-      if (a.out.mean) a.out.mean[c] = ns ? m.mean : km_nan();
-      if (a.out.sd) a.out.sd[c] = ns ? sqrt(m.m2 / m.n) : km_nan();
+      if (a.out.mean) a.out.mean[c] = ns ? m.mean : nan_f64();
+      if (a.out.sd) a.out.sd[c] = ns ? sqrt(m.m2 / m.n) : nan_f64();
     }
   }
 }
 
-#define NMOD_KM_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
-
-static inline size_t km_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <bool LDS_TABLE>
 static void km_launch_i16(const KmArgs& a, int num_cus, hipStream_t stream) {
-  const int64_t ntiles = (a.npos + kKmTile - 1) / kKmTile, need = (ntiles + kKmWaves - 1) / kKmWaves;
-  const int64_t cap = (int64_t)num_cus * (LDS_TABLE ? 1 : 2);
-  const dim3 grid((unsigned)(need < 1 ? 1 : (need < cap ? need : cap)));
+  const int64_t ntiles = (a.npos + kKmTile - 1) / kKmTile;
+  const dim3 grid(persistent_grid(ntiles, kKmWaves, (int64_t)num_cus * (LDS_TABLE ? 1 : 2)));
   const size_t lds = LDS_TABLE ? (size_t)a.ncodes * kKmLdsBytesPerCode : 0;
   // (above 64 KiB of dynamic LDS some runtimes want to be told; where there is no such limit the call is a no-op or an error to drop)
   const void* fn = a.kbound ? (const void*)km_i16_kernel<LDS_TABLE, true> : (const void*)km_i16_kernel<LDS_TABLE, false>;
@@ -492,20 +485,15 @@ using namespace nmod;
 
 extern "C" int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void* sig, const int64_t* off, const int32_t* code,
                                int32_t ncodes, const double* keep_lo, const double* keep_hi, const nmod_kmer_out* out) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params)) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
   if (npos < 0 || npos > (int64_t)INT32_MAX - 1 || ncodes < 1 || ncodes > NMOD_MAX_KMER_CODES) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_kmer_out)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_HOST && prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
-  if (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI && prm->dtype != NMOD_DTYPE_F64) return NMOD_ERR_INVALID_ARG;
   if ((keep_lo == nullptr) != (keep_hi == nullptr)) return NMOD_ERR_INVALID_ARG;
   if (npos > 0 && (!sig || !code)) return NMOD_ERR_INVALID_ARG;
   if (npos > 0 && !off && prm->stride0 <= 0) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
   if (host && npos > 0) {
-    if (off) {
-      if (off[0] < 0) return NMOD_ERR_INVALID_ARG;
-      for (int64_t i = 0; i < npos; ++i) if (off[i + 1] < off[i]) return NMOD_ERR_INVALID_ARG;
-    }
+    if (off && !csr_offsets_ok(off, npos)) return NMOD_ERR_INVALID_ARG;
     for (int64_t i = 0; i < npos; ++i) if (code[i] < -1 || code[i] >= ncodes) return NMOD_ERR_INVALID_ARG;
   }
   const size_t nc = (size_t)ncodes, np = (size_t)npos;
@@ -519,73 +507,49 @@ extern "C" int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void*
     }
     return NMOD_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) { (void)hipGetLastError(); return NMOD_ERR_NO_DEVICE; }
-  NMOD_KM_HIP(hipSetDevice(prm->device));
   int num_cus = 0;
-  NMOD_KM_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
+  const int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const bool i16 = prm->dtype == NMOD_DTYPE_I16_MILLI, clip = keep_lo != nullptr;
-  const size_t esz = prm->dtype == NMOD_DTYPE_F32 ? 4 : (i16 ? 2 : 8);
+  const size_t esz = elem_bytes(prm->dtype);
   const size_t tot = host ? (size_t)(off ? off[npos] : npos * prm->stride0) : 0;
-
-  // one slab: the table (int16) or the per-position moments and the sort's buffers (floats); for the host entry the inputs and
-  // outputs as well
-  size_t at = 0;
-  auto take = [&at](size_t bytes) { const size_t o = at; at += km_up(bytes); return o; };
-  const size_t o_acc = take(i16 ? nc * 8 * 5 : 0), o_kb = take(i16 && clip ? nc * 8 : 0);
-  const size_t o_pm = take(i16 ? 0 : np * 16), o_pn = take(i16 ? 0 : np * 8);
-  const size_t o_key = take(i16 ? 0 : np * 16), o_val = take(i16 ? 0 : np * 8), o_rs = take(i16 ? 0 : rs_scratch_bytes(npos));
-  const size_t o_sig = take(host ? tot * esz + 16 : 0), o_off = take(host && off ? (np + 1) * 8 : 0), o_code = take(host ? np * 4 : 0);
-  const size_t o_keep = take(host && clip ? nc * 16 : 0);
-  const size_t o_cnt = take(host ? nc * 8 * 3 : 0), o_ms = take(host ? nc * 16 : 0), o_st = take(host ? np : 0);
-  DevScratch slab;
-  NMOD_KM_HIP(slab.alloc(at, stream, prm->device));
-  char* base = static_cast<char*>(slab.p);
 
   KmArgs a;
   memset(&a, 0, sizeof(a));
   a.sig = sig; a.off = off; a.stride = off ? 0 : prm->stride0; a.code = code;
   a.npos = npos; a.ncodes = ncodes;
   a.keep_lo = keep_lo; a.keep_hi = keep_hi;
-  a.pos_status = out->pos_status;
   a.out = *out;
-  if (host) {
-    if (tot) NMOD_KM_HIP(hipMemcpyAsync(base + o_sig, sig, tot * esz, hipMemcpyHostToDevice, stream));
-    a.sig = base + o_sig;
-    if (off) { NMOD_KM_HIP(hipMemcpyAsync(base + o_off, off, (np + 1) * 8, hipMemcpyHostToDevice, stream)); a.off = (const int64_t*)(base + o_off); }
-    if (np) NMOD_KM_HIP(hipMemcpyAsync(base + o_code, code, np * 4, hipMemcpyHostToDevice, stream));
-    a.code = (const int32_t*)(base + o_code);
-    if (clip) {
-      NMOD_KM_HIP(hipMemcpyAsync(base + o_keep, keep_lo, nc * 8, hipMemcpyHostToDevice, stream));
-      NMOD_KM_HIP(hipMemcpyAsync(base + o_keep + nc * 8, keep_hi, nc * 8, hipMemcpyHostToDevice, stream));
-      a.keep_lo = (const double*)(base + o_keep); a.keep_hi = a.keep_lo + nc;
-    }
-    int64_t* cnt = (int64_t*)(base + o_cnt);
-    a.out.n_positions = out->n_positions ? cnt : nullptr;
-    a.out.n_samples = out->n_samples ? cnt + nc : nullptr;
-    a.out.n_clipped = out->n_clipped ? cnt + 2 * nc : nullptr;
-    a.out.mean = out->mean ? (double*)(base + o_ms) : nullptr;
-    a.out.sd = out->sd ? (double*)(base + o_ms) + nc : nullptr;
-    a.out.pos_status = out->pos_status ? (uint8_t*)(base + o_st) : nullptr;
-    a.pos_status = a.out.pos_status;
-  }
+
+  // one slab: the table (int16) or the per-position moments and the sort's buffers (floats); for the host entry the inputs
+  // (the samples with 16 spare bytes: km_i16_kernel reads whole aligned pieces) and outputs as well
+  Slab slab(host);
+  const size_t o_acc = slab.take(i16 ? nc * 8 * 5 : 0), o_kb = slab.take(i16 && clip ? nc * 8 : 0);
+  const size_t o_pm = slab.take(i16 ? 0 : np * 16), o_pn = slab.take(i16 ? 0 : np * 8);
+  const size_t o_key = slab.take(i16 ? 0 : np * 16), o_val = slab.take(i16 ? 0 : np * 8), o_rs = slab.take(i16 ? 0 : rs_scratch_bytes(npos));
+  slab.in(a.sig, tot * esz, 16); slab.in(a.off, (np + 1) * 8); slab.in(a.code, np * 4);
+  slab.in(a.keep_lo, nc * 8); slab.in(a.keep_hi, nc * 8);
+  slab.out(a.out.n_positions, nc * 8); slab.out(a.out.n_samples, nc * 8); slab.out(a.out.n_clipped, nc * 8);
+  slab.out(a.out.mean, nc * 8); slab.out(a.out.sd, nc * 8); slab.out(a.out.pos_status, np);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  a.pos_status = a.out.pos_status;
   const unsigned code_blocks = (unsigned)((nc + 255) / 256);
   if (i16) {
-    a.acc = (unsigned long long*)(base + o_acc);
-    NMOD_KM_HIP(hipMemsetAsync(a.acc, 0, nc * 8 * 5, stream));
+    a.acc = slab.at<unsigned long long>(o_acc);
+    NMOD_HIP(hipMemsetAsync(a.acc, 0, nc * 8 * 5, stream));
     if (clip) {
-      hipLaunchKernelGGL(km_bounds_kernel, dim3(code_blocks), dim3(256), 0, stream, a.keep_lo, a.keep_hi, ncodes, (int2*)(base + o_kb));
-      a.kbound = (const int2*)(base + o_kb);
+      hipLaunchKernelGGL(km_bounds_kernel, dim3(code_blocks), dim3(256), 0, stream, a.keep_lo, a.keep_hi, ncodes, slab.at<int2>(o_kb));
+      a.kbound = slab.at<int2>(o_kb);
     }
     if (npos > 0) {
       if (ncodes <= kKmLdsCodes) km_launch_i16<true>(a, num_cus, stream); else km_launch_i16<false>(a, num_cus, stream);
     }
     hipLaunchKernelGGL(km_finish_i16_kernel, dim3(code_blocks), dim3(256), 0, stream, a);
   } else {
-    a.pmean = (double*)(base + o_pm); a.pm2 = a.pmean + np;
-    a.pn = (int32_t*)(base + o_pn); a.pcl = a.pn + np;
-    a.key = (uint64_t*)(base + o_key); a.val = (uint32_t*)(base + o_val);
+    a.pmean = slab.at<double>(o_pm); a.pm2 = a.pmean + np;
+    a.pn = slab.at<int32_t>(o_pn); a.pcl = a.pn + np;
+    a.key = slab.at<uint64_t>(o_key); a.val = slab.at<uint32_t>(o_val);
     uint64_t* key_tmp = a.key + np; uint32_t* val_tmp = a.val + np;
     const int passes = ncodes < 256 ? 1 : (ncodes < 65536 ? 2 : 3);         // the largest key is ncodes
     if (npos > 0) {
@@ -593,24 +557,14 @@ extern "C" int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void*
       const dim3 mgrid((unsigned)(mb < mcap ? mb : mcap));
       if (prm->dtype == NMOD_DTYPE_F32) hipLaunchKernelGGL(km_moments_kernel<NMOD_DTYPE_F32>, mgrid, dim3(256), 0, stream, a);
       else hipLaunchKernelGGL(km_moments_kernel<NMOD_DTYPE_F64>, mgrid, dim3(256), 0, stream, a);
-      NMOD_KM_HIP(rs_sort_pairs(a.key, a.val, key_tmp, val_tmp, npos, base + o_rs, stream, passes));
+      NMOD_HIP(rs_sort_pairs(a.key, a.val, key_tmp, val_tmp, npos, slab.at<char>(o_rs), stream, passes));
     }
     const bool in_tmp = (passes & 1) != 0;
     const int64_t cb = ((int64_t)ncodes + 3) / 4, ccap = (int64_t)num_cus * 8;
     hipLaunchKernelGGL(km_combine_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, a,
                        (const uint64_t*)(in_tmp ? key_tmp : a.key), (const uint32_t*)(in_tmp ? val_tmp : a.val));
   }
-  NMOD_KM_HIP(hipGetLastError());
-  if (host) {
-    const int64_t* cnt = (const int64_t*)(base + o_cnt);
-    if (out->n_positions) NMOD_KM_HIP(hipMemcpyAsync(out->n_positions, cnt, nc * 8, hipMemcpyDeviceToHost, stream));
-    if (out->n_samples) NMOD_KM_HIP(hipMemcpyAsync(out->n_samples, cnt + nc, nc * 8, hipMemcpyDeviceToHost, stream));
-    if (out->n_clipped) NMOD_KM_HIP(hipMemcpyAsync(out->n_clipped, cnt + 2 * nc, nc * 8, hipMemcpyDeviceToHost, stream));
-    if (out->mean) NMOD_KM_HIP(hipMemcpyAsync(out->mean, base + o_ms, nc * 8, hipMemcpyDeviceToHost, stream));
-    if (out->sd) NMOD_KM_HIP(hipMemcpyAsync(out->sd, base + o_ms + nc * 8, nc * 8, hipMemcpyDeviceToHost, stream));
-    if (out->pos_status && np) NMOD_KM_HIP(hipMemcpyAsync(out->pos_status, base + o_st, np, hipMemcpyDeviceToHost, stream));
-    NMOD_KM_HIP(hipStreamSynchronize(stream));
-  }
-  NMOD_KM_HIP(slab.release(stream));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(slab.finish(stream));
   return NMOD_OK;
 }

@@ -19,8 +19,8 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
-#include "scratch_pool.hpp"
-#include "wave_ops.hpp"
+#include "entry_common.hpp"
+#include "entry_device.hpp"
 
 namespace nmod {
 
@@ -41,13 +41,6 @@ struct MixArgs {
   uint32_t* list[3]; uint32_t* count;                        // per class: indices of the positions to compute, their number
 };
 
-__device__ __forceinline__ double mix_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-__device__ __forceinline__ void mix_row(const int64_t* off, int64_t stride, int64_t i, int64_t& begin, int64_t& n) {
-  if (off) { begin = off[i]; n = off[i + 1] - begin; } else { begin = i * stride; n = stride; }
-  if (n < 0) n = 0;
-}
-
 template <int DT>
 __device__ __forceinline__ double mix_load(const void* p, int64_t i) {
   if constexpr (DT == NMOD_DTYPE_F32) return (double)static_cast<const float*>(p)[i];
@@ -56,7 +49,7 @@ __device__ __forceinline__ double mix_load(const void* p, int64_t i) {
 }
 
 __device__ __forceinline__ void mix_write_nan(const nmod_mix_out& o, int64_t i, unsigned status) {
-  const double nan = mix_nan();
+  const double nan = nan_f64();
   if (o.pi) o.pi[i] = nan;
   if (o.mu_mod) o.mu_mod[i] = nan;
   if (o.sd_mod) o.sd_mod[i] = nan;
@@ -74,8 +67,8 @@ __global__ __launch_bounds__(256) void mix_classify_kernel(MixArgs a) {
     int64_t yb = 0, yn = 0;
     if (in) {
       int64_t rb, rn;
-      mix_row(a.roff, a.rstride, i, rb, rn);
-      mix_row(a.yoff, a.ystride, i, yb, yn);
+      csr_row(a.roff, a.rstride, i, rb, rn);
+      csr_row(a.yoff, a.ystride, i, yb, yn);
       unsigned st = 0;
       if (a.gate && !(a.gate[i] <= a.gate_max)) st = NMOD_MIX_SKIPPED;                 // NaN compares false: skipped
       else if (rn > NMOD_MAX_DEEP || yn > NMOD_MAX_DEEP) st = NMOD_MIX_TOO_LARGE;
@@ -83,16 +76,7 @@ __global__ __launch_bounds__(256) void mix_classify_kernel(MixArgs a) {
       else cls = yn <= kMixSmall ? 0 : (yn <= kMixWave ? 1 : 2);
       if (cls < 0) mix_write_nan(a.out, i, st);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const unsigned long long mask = __ballot(cls == c);
-      if (mask) {
-        unsigned at = 0;
-        if (lane == 0) at = atomicAdd(&a.count[c], (unsigned)__popcll(mask));
-        at = __builtin_amdgcn_readfirstlane(at);
-        if (cls == c) a.list[c][at + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)i;
-      }
-    }
+    compact_to_lists<3>(cls, lane, a.list, a.count, i);
     if (a.out.resp) {                                       // the reads of the positions left out: NaN, a wave per row
       unsigned long long mask = __ballot(in && cls < 0);
       while (mask) {
@@ -127,13 +111,6 @@ __device__ __forceinline__ double mix_group_sum(double v) {
   }
 }
 
-template <int G>
-__device__ __forceinline__ bool mix_group_any(bool f, int lane) {
-  const unsigned long long b = __ballot(f);
-  if constexpr (G == 64) return b != 0ull;
-  else return ((b >> (lane & 48)) & 0xFFFFull) != 0ull;
-}
-
 // softplus(x) = ln(1 + e^x) without overflow
 __device__ __forceinline__ double mix_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
@@ -152,8 +129,8 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
     int64_t pos = 0, yb = 0, yn = 0, rb = 0, rn = 0;
     if (have) {
       pos = (int64_t)a.list[CLS][w];
-      mix_row(a.yoff, a.ystride, pos, yb, yn);
-      mix_row(a.roff, a.rstride, pos, rb, rn);
+      csr_row(a.yoff, a.ystride, pos, yb, yn);
+      csr_row(a.roff, a.rstride, pos, rb, rn);
     }
     // R: two passes, mean then the squares about it
     bool bad = false, varies = false;
@@ -184,8 +161,8 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
       acc += y[j];
     }
     const double d = mix_group_sum<G>(acc) / (double)yn - mu;
-    bad = mix_group_any<G>(bad, lane);
-    varies = mix_group_any<G>(varies, lane);                 // a constant reference group has s2 == 0 whatever its sums round to
+    bad = group_any<G>(bad, lane);
+    varies = group_any<G>(varies, lane);                 // a constant reference group has s2 == 0 whatever its sums round to
     bool degenerate = !have || bad || !varies || !(s2 > 0.0);
 
     const double sd = sqrt(s2), hs = 1.0 / (2.0 * s2), vfloor = s2 / 16.0, dn = (double)yn;
@@ -267,18 +244,6 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
   }
 }
 
-// sum over the workgroup, the same bits in every thread: wave sums, then the waves' words in index order
-__device__ __forceinline__ double mix_block_sum(double v, double* sh) {
-  const double w = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < kMixStreamWaves; ++i) t += sh[i];
-  __syncthreads();
-  return t;
-}
-
 // The streaming form: a workgroup per position, Y re-read every iteration.  The free-variance model makes two passes per
 // iteration (the second, about the new mean, evaluates the responsibilities again instead of storing them).
 template <int DT, int MODEL>
@@ -289,8 +254,8 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
   for (int64_t w = blockIdx.x; w < cnt; w += gridDim.x) {
     const int64_t pos = (int64_t)a.list[2][w];
     int64_t yb, yn, rb, rn;
-    mix_row(a.yoff, a.ystride, pos, yb, yn);
-    mix_row(a.roff, a.rstride, pos, rb, rn);
+    csr_row(a.yoff, a.ystride, pos, yb, yn);
+    csr_row(a.roff, a.rstride, pos, rb, rn);
     int bad = 0, varies = 0;
     const double x0 = mix_load<DT>(a.r, rb);
     double acc = 0.0;
@@ -300,20 +265,20 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
       varies |= x != x0;
       acc += x;
     }
-    const double mu = mix_block_sum(acc, sh) / (double)rn;
+    const double mu = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)rn;
     acc = 0.0;
     for (int64_t k = tid; k < rn; k += kMixStreamThreads) {
       const double dx = mix_load<DT>(a.r, rb + k) - mu;
       acc += dx * dx;
     }
-    const double s2 = mix_block_sum(acc, sh) / (double)rn;
+    const double s2 = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)rn;
     acc = 0.0;
     for (int64_t k = tid; k < yn; k += kMixStreamThreads) {
       const double x = mix_load<DT>(a.y, yb + k);
       bad |= !isfinite(x);
       acc += x;
     }
-    const double d = mix_block_sum(acc, sh) / (double)yn - mu;
+    const double d = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)yn - mu;
     bool degenerate = __syncthreads_or(bad) != 0;
     degenerate = __syncthreads_or(varies) == 0 || degenerate || !(s2 > 0.0);   // (a constant reference group: s2 == 0 exactly)
 
@@ -333,8 +298,8 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
         sr += r;
         sy += r * yv;
       }
-      sr = mix_block_sum(sr, sh);
-      sy = mix_block_sum(sy, sh);
+      sr = block_sum_f64<kMixStreamWaves>(sr, sh);
+      sy = block_sum_f64<kMixStreamWaves>(sy, sh);
       if (!(sr > 0.0)) { degenerate = true; active = false; break; }
       const double pn = sr / dn, mn = sy / sr;
       double vn = v;
@@ -347,7 +312,7 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
           const double r = 1.0 / (1.0 + exp(c0 + dy * dy * hv - dm * dm * hs));
           sq += r * (e * e);
         }
-        vn = mix_block_sum(sq, sh) / sr;
+        vn = block_sum_f64<kMixStreamWaves>(sq, sh) / sr;
         fl = vn < vfloor;
         if (fl) vn = vfloor;
       }
@@ -370,7 +335,7 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
       ll += l1 + mix_softplus(-t);
       if (resp) resp[yb + i] = degenerate ? __int_as_float(0x7FC00000) : (float)(1.0 / (1.0 + exp(t)));
     }
-    ll = 2.0 * mix_block_sum(ll, sh);
+    ll = 2.0 * block_sum_f64<kMixStreamWaves>(ll, sh);
     if (tid == 0) {
       if (degenerate) {
         mix_write_nan(a.out, pos, NMOD_MIX_DEGENERATE);
@@ -389,12 +354,8 @@ __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a
 template <int DT, int MODEL>
 static void mix_launch(const MixArgs& a, int num_cus, hipStream_t stream) {
   const int64_t cap = (int64_t)num_cus * 8;
-  const auto grid = [cap](int64_t work, int64_t per_block) {
-    const int64_t b = (work + per_block - 1) / per_block;
-    return dim3((unsigned)(b < 1 ? 1 : (b < cap ? b : cap)));
-  };
-  hipLaunchKernelGGL((mix_em_kernel<16, DT, MODEL>), grid(a.npos, kMixThreads / 16), dim3(kMixThreads), 0, stream, a);
-  hipLaunchKernelGGL((mix_em_kernel<64, DT, MODEL>), grid(a.npos, kMixThreads / 64), dim3(kMixThreads), 0, stream, a);
+  hipLaunchKernelGGL((mix_em_kernel<16, DT, MODEL>), dim3(persistent_grid(a.npos, kMixThreads / 16, cap)), dim3(kMixThreads), 0, stream, a);
+  hipLaunchKernelGGL((mix_em_kernel<64, DT, MODEL>), dim3(persistent_grid(a.npos, kMixThreads / 64, cap)), dim3(kMixThreads), 0, stream, a);
   const int64_t sb = a.npos < (int64_t)num_cus * 2 ? a.npos : (int64_t)num_cus * 2;
   hipLaunchKernelGGL((mix_stream_kernel<DT, MODEL>), dim3((unsigned)sb), dim3(kMixStreamThreads), 0, stream, a);
 }
@@ -405,17 +366,6 @@ static void mix_launch_model(const MixArgs& a, int model, int num_cus, hipStream
   else mix_launch<DT, NMOD_MIX_EQUAL_VAR>(a, num_cus, stream);
 }
 
-#define NMOD_MIX_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
-
-static inline size_t mix_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// a host-resident CSR offset array: starts at or above 0 and never decreases
-static bool mix_offsets_ok(const int64_t* off, int64_t npos) {
-  if (off[0] < 0) return false;
-  for (int64_t i = 0; i < npos; ++i) if (off[i + 1] < off[i]) return false;
-  return true;
-}
-
 }  // namespace nmod
 
 using namespace nmod;
@@ -423,87 +373,53 @@ using namespace nmod;
 extern "C" int nmod_mix_fraction(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0, const void* sig1,
                                  const int64_t* off1, int32_t mix_group, int32_t model, int32_t max_iter, double tol,
                                  const double* gate, double gate_max, const nmod_mix_out* out) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params)) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
   if (npos < 0 || npos > (int64_t)UINT32_MAX - 1 || !out) return NMOD_ERR_INVALID_ARG;
   if (mix_group != 0 && mix_group != 1) return NMOD_ERR_INVALID_ARG;
   if (model != NMOD_MIX_EQUAL_VAR && model != NMOD_MIX_FREE_VAR) return NMOD_ERR_INVALID_ARG;
   if (max_iter < 1 || max_iter > 10000 || !(tol >= 0.0) || isinf(tol)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_HOST && prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
-  if (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI && prm->dtype != NMOD_DTYPE_F64) return NMOD_ERR_INVALID_ARG;
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1) return NMOD_ERR_INVALID_ARG;
   if ((!off0 && prm->stride0 <= 0) || (!off1 && prm->stride1 <= 0)) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && ((off0 && !mix_offsets_ok(off0, npos)) || (off1 && !mix_offsets_ok(off1, npos)))) return NMOD_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) { (void)hipGetLastError(); return NMOD_ERR_NO_DEVICE; }
-  NMOD_MIX_HIP(hipSetDevice(prm->device));
+  if (host && ((off0 && !csr_offsets_ok(off0, npos)) || (off1 && !csr_offsets_ok(off1, npos)))) return NMOD_ERR_INVALID_ARG;
   int num_cus = 0;
-  NMOD_MIX_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
+  const int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t np = (size_t)npos, esz = prm->dtype == NMOD_DTYPE_F32 ? 4 : (prm->dtype == NMOD_DTYPE_I16_MILLI ? 2 : 8);
-
-  // one slab: the three work lists and their count words; for the host entry the inputs and outputs as well
+  const size_t np = (size_t)npos, esz = elem_bytes(prm->dtype);
   const size_t tot0 = host ? (size_t)(off0 ? off0[npos] : npos * prm->stride0) : 0;
   const size_t tot1 = host ? (size_t)(off1 ? off1[npos] : npos * prm->stride1) : 0;
-  const size_t toty = mix_group == 1 ? tot1 : tot0;
-  size_t at = 0;
-  auto take = [&at](size_t bytes) { const size_t o = at; at += mix_up(bytes); return o; };
-  const size_t o_list = take(np * 4 * 3), o_count = take(16);
-  const size_t o_sig0 = take(tot0 * esz), o_sig1 = take(tot1 * esz);
-  const size_t o_off0 = take(host && off0 ? (np + 1) * 8 : 0), o_off1 = take(host && off1 ? (np + 1) * 8 : 0);
-  const size_t o_gate = take(host && gate ? np * 8 : 0);
-  const size_t o_f64 = take(host ? np * 8 * 4 : 0), o_iters = take(host ? np * 4 : 0), o_status = take(host ? np : 0);
-  const size_t o_resp = take(host && out->resp ? toty * 4 : 0);
-  DevScratch slab;
-  NMOD_MIX_HIP(slab.alloc(at, stream, prm->device));
-  char* base = static_cast<char*>(slab.p);
+  const bool y1 = mix_group == 1;
 
   MixArgs a;
   memset(&a, 0, sizeof(a));
-  const void* s0 = sig0; const void* s1 = sig1;
-  const int64_t* f0 = off0; const int64_t* f1 = off1;
-  a.gate = gate;
+  a.y = y1 ? sig1 : sig0; a.yoff = y1 ? off1 : off0; a.ystride = y1 ? prm->stride1 : prm->stride0;
+  a.r = y1 ? sig0 : sig1; a.roff = y1 ? off0 : off1; a.rstride = y1 ? prm->stride0 : prm->stride1;
+  a.npos = npos; a.max_iter = max_iter; a.tol = tol;
+  a.gate = gate; a.gate_max = gate_max;
   a.out = *out;
-  if (host) {
-    if (tot0) NMOD_MIX_HIP(hipMemcpyAsync(base + o_sig0, sig0, tot0 * esz, hipMemcpyHostToDevice, stream));
-    if (tot1) NMOD_MIX_HIP(hipMemcpyAsync(base + o_sig1, sig1, tot1 * esz, hipMemcpyHostToDevice, stream));
-    s0 = base + o_sig0; s1 = base + o_sig1;
-    if (off0) { NMOD_MIX_HIP(hipMemcpyAsync(base + o_off0, off0, (np + 1) * 8, hipMemcpyHostToDevice, stream)); f0 = (const int64_t*)(base + o_off0); }
-    if (off1) { NMOD_MIX_HIP(hipMemcpyAsync(base + o_off1, off1, (np + 1) * 8, hipMemcpyHostToDevice, stream)); f1 = (const int64_t*)(base + o_off1); }
-    if (gate) { NMOD_MIX_HIP(hipMemcpyAsync(base + o_gate, gate, np * 8, hipMemcpyHostToDevice, stream)); a.gate = (const double*)(base + o_gate); }
-    double* f = (double*)(base + o_f64);
-    a.out.pi = out->pi ? f : nullptr; a.out.mu_mod = out->mu_mod ? f + np : nullptr;
-    a.out.sd_mod = out->sd_mod ? f + 2 * np : nullptr; a.out.llr = out->llr ? f + 3 * np : nullptr;
-    a.out.iters = out->iters ? (int32_t*)(base + o_iters) : nullptr;
-    a.out.status = out->status ? (uint8_t*)(base + o_status) : nullptr;
-    a.out.resp = out->resp ? (float*)(base + o_resp) : nullptr;
-  }
-  const bool y1 = mix_group == 1;
-  a.y = y1 ? s1 : s0; a.yoff = y1 ? f1 : f0; a.ystride = y1 ? prm->stride1 : prm->stride0;
-  a.r = y1 ? s0 : s1; a.roff = y1 ? f0 : f1; a.rstride = y1 ? prm->stride0 : prm->stride1;
-  a.npos = npos; a.max_iter = max_iter; a.tol = tol; a.gate_max = gate_max;
-  for (int c = 0; c < 3; ++c) a.list[c] = (uint32_t*)(base + o_list) + (size_t)c * np;
-  a.count = (uint32_t*)(base + o_count);
 
-  NMOD_MIX_HIP(hipMemsetAsync(a.count, 0, 16, stream));
+  // one slab: the three work lists and their count words; for the host entry the inputs and outputs as well
+  Slab slab(host);
+  const size_t o_list = slab.take(np * 4 * 3), o_count = slab.take(16);
+  const size_t toty = y1 ? tot1 : tot0, totr = y1 ? tot0 : tot1;
+  slab.in(a.y, toty * esz); slab.in(a.yoff, (np + 1) * 8);
+  slab.in(a.r, totr * esz); slab.in(a.roff, (np + 1) * 8);
+  slab.in(a.gate, np * 8);
+  slab.out(a.out.pi, np * 8); slab.out(a.out.mu_mod, np * 8); slab.out(a.out.sd_mod, np * 8); slab.out(a.out.llr, np * 8);
+  slab.out(a.out.iters, np * 4); slab.out(a.out.status, np); slab.out(a.out.resp, toty * 4);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  for (int c = 0; c < 3; ++c) a.list[c] = slab.at<uint32_t>(o_list) + (size_t)c * np;
+  a.count = slab.at<uint32_t>(o_count);
+
+  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
   const int64_t cb = (npos + 255) / 256;
   hipLaunchKernelGGL(mix_classify_kernel, dim3((unsigned)(cb < (int64_t)num_cus * 16 ? cb : (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
   if (prm->dtype == NMOD_DTYPE_F32) mix_launch_model<NMOD_DTYPE_F32>(a, model, num_cus, stream);
   else if (prm->dtype == NMOD_DTYPE_I16_MILLI) mix_launch_model<NMOD_DTYPE_I16_MILLI>(a, model, num_cus, stream);
   else mix_launch_model<NMOD_DTYPE_F64>(a, model, num_cus, stream);
-  NMOD_MIX_HIP(hipGetLastError());
-  if (host) {
-    const double* f = (const double*)(base + o_f64);
-    if (out->pi) NMOD_MIX_HIP(hipMemcpyAsync(out->pi, f, np * 8, hipMemcpyDeviceToHost, stream));
-    if (out->mu_mod) NMOD_MIX_HIP(hipMemcpyAsync(out->mu_mod, f + np, np * 8, hipMemcpyDeviceToHost, stream));
-    if (out->sd_mod) NMOD_MIX_HIP(hipMemcpyAsync(out->sd_mod, f + 2 * np, np * 8, hipMemcpyDeviceToHost, stream));
-    if (out->llr) NMOD_MIX_HIP(hipMemcpyAsync(out->llr, f + 3 * np, np * 8, hipMemcpyDeviceToHost, stream));
-    if (out->iters) NMOD_MIX_HIP(hipMemcpyAsync(out->iters, base + o_iters, np * 4, hipMemcpyDeviceToHost, stream));
-    if (out->status) NMOD_MIX_HIP(hipMemcpyAsync(out->status, base + o_status, np, hipMemcpyDeviceToHost, stream));
-    if (out->resp && toty) NMOD_MIX_HIP(hipMemcpyAsync(out->resp, base + o_resp, toty * 4, hipMemcpyDeviceToHost, stream));
-    NMOD_MIX_HIP(hipStreamSynchronize(stream));
-  }
-  NMOD_MIX_HIP(slab.release(stream));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(slab.finish(stream));
   return NMOD_OK;
 }

@@ -17,6 +17,7 @@
 #include <dlfcn.h>
 
 #include "../../include/nanomod_hip.h"
+#include "entry_common.hpp"
 #include "rank_stats.hpp"
 #include "rank_stats_launch.hpp"
 #include "item_claim.hpp"
@@ -28,14 +29,8 @@
 
 namespace nmod {
 
-thread_local hipError_t g_last_hip = hipSuccess;   // only feeds nmod_strerror's text
+thread_local hipError_t g_last_hip = hipSuccess;   // only feeds nmod_strerror's text; NMOD_HIP (entry_common.hpp) sets it
 thread_local char g_errbuf[256];
-
-#define NMOD_HIP(call)                                   \
-  do {                                                   \
-    hipError_t e_ = (call);                              \
-    if (e_ != hipSuccess) { g_last_hip = e_; return NMOD_ERR_HIP; } \
-  } while (0)
 
 // ---------------------------------------------------------------- event timer
 struct EvTimer {
@@ -90,8 +85,6 @@ static_assert(kMetaRedoCursor + 2 <= kMetaClaim && kMetaClaim + kClassStride <= 
 static_assert(kMetaRedo + kClassStride < kMetaRedoTotal && kMetaRedoCursor + 2 <= kMetaInts && kMetaBigCursor + 2 <= kMetaWideRedo && kMetaWideRedo < kMetaCntGate && kMetaCntGate < kMetaDeepTiles && kMetaDeepTiles + 2 <= kMetaRedo, "meta layout");
 // (kBigClass, kBigHistClass, kWideBigBase .., kNumPairs: rank_stats_launch.hpp)
 static_assert(kNumPairs <= kClassStride && kStatsClass + kClassStride <= kStatsGate && kStatsGate + kClassStride <= kStatsLeft && kStatsLeft + kClassStride <= kStatsTried && kStatsTried + kClassStride <= kStatsWords, "class tables");
-
-static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 static Workspace carve(void* base, int64_t npos) {
   Workspace w;
@@ -426,7 +419,6 @@ static int launch_combine(const nmod_params* prm, hipStream_t stream, int64_t np
 // threshold every batch would return its slab to the OS at the next synchronisation and map it again — measured
 // 20 ms per 1.3 GB); the device's default pool, which the caller's own hipMallocAsync traffic uses, is never
 // touched.  nmod_trim_scratch() returns the cached slabs to the driver.
-constexpr int kMaxDevices = 64;
 static std::mutex g_pool_mutex;
 static hipMemPool_t g_pool[kMaxDevices] = {nullptr};        // guarded by g_pool_mutex
 
@@ -447,21 +439,6 @@ hipMemPool_t scratch_pool(int dev) {            // (declared in scratch_pool.hpp
     g_pool[dev] = pool;
   }
   return g_pool[dev];
-}
-
-// CU count per device, looked up once (the attribute query is not cheap and this runs every batch); an atomic per device:
-// concurrent first calls both query and store the same value
-static hipError_t device_cus(int dev, int* num_cus) {
-  static std::atomic<int> cache[kMaxDevices];
-  const bool cacheable = dev >= 0 && dev < kMaxDevices;
-  int n = cacheable ? cache[dev].load(std::memory_order_relaxed) : 0;
-  if (n <= 0) {
-    const hipError_t e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    if (cacheable) cache[dev].store(n, std::memory_order_relaxed);
-  }
-  *num_cus = n;
-  return hipSuccess;
 }
 
 
@@ -1156,8 +1133,8 @@ int nmod_detect_batch(const nmod_params* prm, int64_t npos, const void* sig0, co
   int rc = check_params(prm);
   if (rc != NMOD_OK) return rc;
   if (npos < 0) return NMOD_ERR_INVALID_ARG;
-  if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(prm->device));
+  rc = select_device(prm, nullptr);
+  if (rc != NMOD_OK) return rc;
   DispatchRec rec;                               // an empty batch: the totals of a host record, all zero
   rec.host = true; rec.npos = npos;
   if (prm->memspace == NMOD_MEM_HOST) {

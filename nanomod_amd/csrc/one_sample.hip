@@ -20,8 +20,9 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
+#include "entry_common.hpp"
+#include "entry_device.hpp"
 #include "rank_stats_packed.hpp"
-#include "scratch_pool.hpp"
 #include "special_math.hpp"
 #include "wave_ops.hpp"
 
@@ -41,15 +42,8 @@ struct OneArgs {
   uint32_t* list[kOneClasses]; uint32_t* count;               // per class: indices of the positions to compute, their number
 };
 
-__device__ __forceinline__ double one_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-
-__device__ __forceinline__ void one_row(const OneArgs& a, int64_t i, int64_t& begin, int64_t& n) {
-  if (a.off) { begin = a.off[i]; n = a.off[i + 1] - begin; } else { begin = i * a.stride; n = a.stride; }
-  if (n < 0) n = 0;
-}
-
 __device__ __forceinline__ void one_write_nan(const nmod_one_out& o, int64_t i, unsigned status) {
-  const double nan = one_nan();
+  const double nan = nan_f64();
   if (o.ks_d) o.ks_d[i] = nan;
   if (o.ks_p) o.ks_p[i] = nan;
   if (o.t_t) o.t_t[i] = nan;
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(256) void one_classify_kernel(OneArgs a) {
     int cls = -1;
     if (i < a.npos) {
       int64_t b, n;
-      one_row(a, i, b, n);
+      csr_row(a.off, a.stride, i, b, n);
       const double mu = a.ref_mean[i], sd = a.ref_sd[i];
       unsigned st = 0;
       if (n == 0) st |= NMOD_STATUS_EMPTY;
@@ -79,16 +73,7 @@ __global__ __launch_bounds__(256) void one_classify_kernel(OneArgs a) {
       else if constexpr (DT == NMOD_DTYPE_F64) cls = 3;
       else cls = n <= kOneSmall ? 0 : (n <= kOneWave ? 1 : (n <= kOneWave2 ? 2 : 3));
     }
-#pragma unroll
-    for (int c = 0; c < kOneClasses; ++c) {
-      const unsigned long long mask = __ballot(cls == c);
-      if (mask) {
-        unsigned at = 0;
-        if (lane == 0) at = atomicAdd(&a.count[c], (unsigned)__popcll(mask));
-        at = __builtin_amdgcn_readfirstlane(at);
-        if (cls == c) a.list[c][at + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)i;
-      }
-    }
+    compact_to_lists<kOneClasses>(cls, lane, a.list, a.count, i);
   }
 }
 
@@ -110,7 +95,7 @@ __device__ __forceinline__ void one_finish(const OneArgs& a, int64_t pos, int64_
   const double mu = a.ref_mean[pos], sd = a.ref_sd[pos], dn = (double)n;
   const double en = sqrt(dn);
   const double ks_p = kolmogorov_sf((en + 0.12 + 0.11 / en) * d);
-  const double nan = one_nan();
+  const double nan = nan_f64();
   const double vx = s2 * dn / (dn - 1.0);                      // n == 1: 0 / 0
   double t = nan, t_p = nan;
   if (n >= 2) {
@@ -150,13 +135,6 @@ __device__ __forceinline__ double one_group_max(double v) {
   }
 }
 
-template <int LG>
-__device__ __forceinline__ bool one_group_any(bool f, int lane) {
-  const unsigned long long b = __ballot(f);
-  if constexpr (LG == 64) return b != 0ull;
-  else return ((b >> (lane & 48)) & 0xFFFFull) != 0ull;
-}
-
 // The register-resident form: LG lanes x R float32 keys per position (the samples, or k of an int16 sample: exact and
 // order-preserving), 64 / LG positions per wave.  Everything between the loads and the stores runs with all lanes on.
 template <int LG, int R, int DT>
@@ -180,7 +158,7 @@ __global__ __launch_bounds__(kOneThreads) void one_wave_kernel(OneArgs a) {
     int64_t pos = 0, begin = 0, n64 = 0;
     if (have) {
       pos = (int64_t)a.list[CLS][w];
-      one_row(a, pos, begin, n64);
+      csr_row(a.off, a.stride, pos, begin, n64);
     }
     const int n = (int)n64;                                   // <= CAP by the class
     // keys, and the moments from them: two passes in fp64 (int16: in milli-units, the sum of the k is exact)
@@ -207,7 +185,7 @@ __global__ __launch_bounds__(kOneThreads) void one_wave_kernel(OneArgs a) {
     const double m2 = seg_allsum_f64<LG>(acc);
     const double mean = DT == NMOD_DTYPE_F32 ? mk : sum / 1000.0 / dn;
     const double s2 = DT == NMOD_DTYPE_F32 ? m2 / dn : m2 / dn * 1e-6;
-    bad = one_group_any<LG>(bad, lane);
+    bad = group_any<LG>(bad, lane);
 
     if constexpr (LG == 64) wave_sort<R>(x, sel, lane); else seg_sort<R, LG>(x, sel, lane);
     store_sorted<R>(wkeys, x, lane);
@@ -249,18 +227,6 @@ __device__ __forceinline__ double one_load(const void* p, int64_t i) {
   else return static_cast<const double*>(p)[i];
 }
 
-// sum over the workgroup, the same bits in every thread: wave sums, then the waves' words in index order
-__device__ __forceinline__ double one_block_sum(double v, double* sh) {
-  const double w = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < kOneBlockWaves; ++i) t += sh[i];
-  return t;
-}
-
 // The workgroup form: a position's keys in LDS (64 KiB: NMOD_MAX_ONE float32 keys or NMOD_MAX_ONE_F64 64-bit images), padded
 // with the largest key to a power of two and sorted by a bitonic network.  The reduction words share the LDS with the keys:
 // they are used before the keys are loaded and after the last key was read.
@@ -275,7 +241,7 @@ __global__ __launch_bounds__(kOneBlockThreads) void one_block_kernel(OneArgs a) 
   for (int64_t w = blockIdx.x; w < cnt; w += gridDim.x) {
     const int64_t pos = (int64_t)a.list[3][w];
     int64_t begin, n64;
-    one_row(a, pos, begin, n64);
+    csr_row(a.off, a.stride, pos, begin, n64);
     const int n = (int)n64;                                   // <= the cap by the classifier
     const double dn = (double)n;
     int bad = 0;
@@ -285,17 +251,17 @@ __global__ __launch_bounds__(kOneBlockThreads) void one_block_kernel(OneArgs a) 
       bad |= !(fabs(v) <= kDblMax);
       acc += v;
     }
-    const double sum = one_block_sum(acc, sh);
+    const double sum = block_sum_f64<kOneBlockWaves>(acc, sh);
     const double mk = sum / dn;
     acc = 0.0;
     for (int k = tid; k < n; k += kOneBlockThreads) {
       const double dx = one_load<DT>(a.sig, begin + k) - mk;
       acc += dx * dx;
     }
-    const double m2 = one_block_sum(acc, sh);
+    const double m2 = block_sum_f64<kOneBlockWaves>(acc, sh);
     const double mean = DT == NMOD_DTYPE_I16_MILLI ? sum / 1000.0 / dn : mk;
     const double s2 = DT == NMOD_DTYPE_I16_MILLI ? m2 / dn * 1e-6 : m2 / dn;
-    const bool nonfinite = one_block_sum(bad ? 1.0 : 0.0, sh) != 0.0;
+    const bool nonfinite = block_sum_f64<kOneBlockWaves>(bad ? 1.0 : 0.0, sh) != 0.0;
     __syncthreads();                                          // every thread has read sh: the keys may come
 
     double d = 0.0;
@@ -347,28 +313,13 @@ static void one_launch(const OneArgs& a, int num_cus, hipStream_t stream) {
   const int64_t cb = (a.npos + 255) / 256;
   hipLaunchKernelGGL(one_classify_kernel<DT>, dim3((unsigned)(cb < (int64_t)num_cus * 16 ? cb : (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
   const int64_t cap = (int64_t)num_cus * 8;
-  const auto grid = [cap](int64_t work, int64_t per_block) {
-    const int64_t b = (work + per_block - 1) / per_block;
-    return dim3((unsigned)(b < 1 ? 1 : (b < cap ? b : cap)));
-  };
   if constexpr (DT != NMOD_DTYPE_F64) {
-    hipLaunchKernelGGL((one_wave_kernel<16, 16, DT>), grid(a.npos, kOneThreads / 16), dim3(kOneThreads), 0, stream, a);
-    hipLaunchKernelGGL((one_wave_kernel<64, 16, DT>), grid(a.npos, kOneThreads / 64), dim3(kOneThreads), 0, stream, a);
-    hipLaunchKernelGGL((one_wave_kernel<64, 32, DT>), grid(a.npos, kOneThreads / 64), dim3(kOneThreads), 0, stream, a);
+    hipLaunchKernelGGL((one_wave_kernel<16, 16, DT>), dim3(persistent_grid(a.npos, kOneThreads / 16, cap)), dim3(kOneThreads), 0, stream, a);
+    hipLaunchKernelGGL((one_wave_kernel<64, 16, DT>), dim3(persistent_grid(a.npos, kOneThreads / 64, cap)), dim3(kOneThreads), 0, stream, a);
+    hipLaunchKernelGGL((one_wave_kernel<64, 32, DT>), dim3(persistent_grid(a.npos, kOneThreads / 64, cap)), dim3(kOneThreads), 0, stream, a);
   }
   const int64_t sb = a.npos < (int64_t)num_cus * 2 ? a.npos : (int64_t)num_cus * 2;
   hipLaunchKernelGGL(one_block_kernel<DT>, dim3((unsigned)sb), dim3(kOneBlockThreads), 0, stream, a);
-}
-
-#define NMOD_ONE_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
-
-static inline size_t one_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// a host-resident CSR offset array: starts at or above 0 and never decreases
-static bool one_offsets_ok(const int64_t* off, int64_t npos) {
-  if (off[0] < 0) return false;
-  for (int64_t i = 0; i < npos; ++i) if (off[i + 1] < off[i]) return false;
-  return true;
 }
 
 }  // namespace nmod
@@ -377,10 +328,8 @@ using namespace nmod;
 
 extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void* sig, const int64_t* off, const double* ref_mean,
                                const double* ref_sd, const int32_t* ref_n, const int32_t* run_id, const nmod_one_out* out) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params)) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
   if (npos < 0 || npos > (int64_t)UINT32_MAX - 1 || !out || out->struct_size != (int32_t)sizeof(nmod_one_out)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_HOST && prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
-  if (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI && prm->dtype != NMOD_DTYPE_F64) return NMOD_ERR_INVALID_ARG;
   if (prm->nb < 0 || prm->nb > NMOD_MAX_NB) return NMOD_ERR_INVALID_ARG;
   if (prm->method != NMOD_METHOD_KS && prm->method != NMOD_METHOD_STOUFFER && prm->method != NMOD_METHOD_FISHER) return NMOD_ERR_INVALID_ARG;
   const bool want_comb = prm->method != NMOD_METHOD_KS && (out->comb_st || out->comb_p);
@@ -390,29 +339,13 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   if (!off && prm->stride0 <= 0) return NMOD_ERR_INVALID_ARG;
   if (want_comb && !run_id) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && off && !one_offsets_ok(off, npos)) return NMOD_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) { (void)hipGetLastError(); return NMOD_ERR_NO_DEVICE; }
-  NMOD_ONE_HIP(hipSetDevice(prm->device));
+  if (host && off && !csr_offsets_ok(off, npos)) return NMOD_ERR_INVALID_ARG;
   int num_cus = 0;
-  NMOD_ONE_HIP(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, prm->device));
+  int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t np = (size_t)npos, esz = prm->dtype == NMOD_DTYPE_F32 ? 4 : (prm->dtype == NMOD_DTYPE_I16_MILLI ? 2 : 8);
-
-  // one slab: the work lists and their count words, the KS track where the caller wants the combined pair without it; for the
-  // host entry the inputs and outputs as well
+  const size_t np = (size_t)npos, esz = elem_bytes(prm->dtype);
   const size_t tot = host ? (size_t)(off ? off[npos] : npos * prm->stride0) : 0;
-  const bool own_d = want_comb && (host || !out->ks_d), own_p = want_comb && (host || !out->ks_p);
-  size_t at = 0;
-  auto take = [&at](size_t bytes) { const size_t o = at; at += one_up(bytes); return o; };
-  const size_t o_list = take(np * 4 * kOneClasses), o_count = take(16);
-  const size_t o_sig = take(tot * esz), o_off = take(host && off ? (np + 1) * 8 : 0);
-  const size_t o_ref = take(host ? np * 16 : 0), o_refn = take(host && ref_n ? np * 4 : 0), o_run = take(host && want_comb ? np * 4 : 0);
-  const size_t o_f64 = take(host ? np * 8 * 9 : 0), o_status = take(host ? np : 0);
-  const size_t o_ksd = take(!host && own_d ? np * 8 : 0), o_ksp = take(!host && own_p ? np * 8 : 0);
-  DevScratch slab;
-  NMOD_ONE_HIP(slab.alloc(at, stream, prm->device));
-  char* base = static_cast<char*>(slab.p);
 
   OneArgs a;
   memset(&a, 0, sizeof(a));
@@ -421,34 +354,31 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   a.npos = npos;
   a.out = *out;
   const int32_t* d_run = run_id;
-  double* f = (double*)(base + o_f64);
-  double** const members[9] = {&a.out.ks_d, &a.out.ks_p, &a.out.t_t, &a.out.t_p, &a.out.shift, &a.out.mean, &a.out.std, &a.out.comb_st, &a.out.comb_p};
-  double* const theirs[9] = {out->ks_d, out->ks_p, out->t_t, out->t_p, out->shift, out->mean, out->std, out->comb_st, out->comb_p};
-  if (host) {
-    if (tot) NMOD_ONE_HIP(hipMemcpyAsync(base + o_sig, sig, tot * esz, hipMemcpyHostToDevice, stream));
-    a.sig = base + o_sig;
-    if (off) { NMOD_ONE_HIP(hipMemcpyAsync(base + o_off, off, (np + 1) * 8, hipMemcpyHostToDevice, stream)); a.off = (const int64_t*)(base + o_off); }
-    NMOD_ONE_HIP(hipMemcpyAsync(base + o_ref, ref_mean, np * 8, hipMemcpyHostToDevice, stream));
-    NMOD_ONE_HIP(hipMemcpyAsync(base + o_ref + np * 8, ref_sd, np * 8, hipMemcpyHostToDevice, stream));
-    a.ref_mean = (const double*)(base + o_ref); a.ref_sd = a.ref_mean + np;
-    if (ref_n) { NMOD_ONE_HIP(hipMemcpyAsync(base + o_refn, ref_n, np * 4, hipMemcpyHostToDevice, stream)); a.ref_n = (const int32_t*)(base + o_refn); }
-    if (want_comb) { NMOD_ONE_HIP(hipMemcpyAsync(base + o_run, run_id, np * 4, hipMemcpyHostToDevice, stream)); d_run = (const int32_t*)(base + o_run); }
-    for (int k = 0; k < 9; ++k) *members[k] = theirs[k] ? f + (size_t)k * np : nullptr;
-    if (own_d) a.out.ks_d = f;
-    if (own_p) a.out.ks_p = f + np;
-    a.out.status = out->status ? (uint8_t*)(base + o_status) : nullptr;
-  } else {
-    if (own_d) a.out.ks_d = (double*)(base + o_ksd);
-    if (own_p) a.out.ks_p = (double*)(base + o_ksp);
-  }
-  for (int c = 0; c < kOneClasses; ++c) a.list[c] = (uint32_t*)(base + o_list) + (size_t)c * np;
-  a.count = (uint32_t*)(base + o_count);
 
-  NMOD_ONE_HIP(hipMemsetAsync(a.count, 0, 16, stream));
+  // one slab: the work lists and their count words, the KS track where the caller wants the combined pair without it; for the
+  // host entry the inputs and outputs as well
+  Slab slab(host);
+  const size_t o_list = slab.take(np * 4 * kOneClasses), o_count = slab.take(16);
+  const bool own_d = want_comb && !out->ks_d, own_p = want_comb && !out->ks_p;
+  const size_t o_ksd = slab.take(own_d ? np * 8 : 0), o_ksp = slab.take(own_p ? np * 8 : 0);
+  slab.in(a.sig, tot * esz); slab.in(a.off, (np + 1) * 8);
+  slab.in(a.ref_mean, np * 8); slab.in(a.ref_sd, np * 8); slab.in(a.ref_n, np * 4);
+  if (want_comb) slab.in(d_run, np * 4);
+  double** const tracks[7] = {&a.out.ks_d, &a.out.ks_p, &a.out.t_t, &a.out.t_p, &a.out.shift, &a.out.mean, &a.out.std};
+  for (double** t : tracks) slab.out(*t, np * 8);
+  if (want_comb) { slab.out(a.out.comb_st, np * 8); slab.out(a.out.comb_p, np * 8); }
+  slab.out(a.out.status, np);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  if (own_d) a.out.ks_d = slab.at<double>(o_ksd);
+  if (own_p) a.out.ks_p = slab.at<double>(o_ksp);
+  for (int c = 0; c < kOneClasses; ++c) a.list[c] = slab.at<uint32_t>(o_list) + (size_t)c * np;
+  a.count = slab.at<uint32_t>(o_count);
+
+  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
   if (prm->dtype == NMOD_DTYPE_F32) one_launch<NMOD_DTYPE_F32>(a, num_cus, stream);
   else if (prm->dtype == NMOD_DTYPE_I16_MILLI) one_launch<NMOD_DTYPE_I16_MILLI>(a, num_cus, stream);
   else one_launch<NMOD_DTYPE_F64>(a, num_cus, stream);
-  NMOD_ONE_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   if (want_comb) {
     // the window combine of the KS track (K3): the code behind nmod_combine_track, on the same stream.  A member of the pair the
     // caller left out goes to a spare word of the slab
@@ -459,22 +389,14 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
     double* cst = a.out.comb_st; double* cpv = a.out.comb_p;
     DevScratch spare;
     if (!cst || !cpv) {
-      NMOD_ONE_HIP(spare.alloc(np * 8, stream, prm->device));
+      NMOD_HIP(spare.alloc(np * 8, stream, prm->device));
       if (!cst) cst = (double*)spare.p;
       if (!cpv) cpv = (double*)spare.p;
     }
-    const int rc = nmod_combine_track(&cp, npos, a.out.ks_d, a.out.ks_p, d_run, cst, cpv);
+    rc = nmod_combine_track(&cp, npos, a.out.ks_d, a.out.ks_p, d_run, cst, cpv);
     if (rc != NMOD_OK) return rc;
-    NMOD_ONE_HIP(spare.release(stream));
+    NMOD_HIP(spare.release(stream));
   }
-  if (host) {
-    for (int k = 0; k < 9; ++k) {
-      if (!theirs[k] || (k >= 7 && !want_comb)) continue;
-      NMOD_ONE_HIP(hipMemcpyAsync(theirs[k], f + (size_t)k * np, np * 8, hipMemcpyDeviceToHost, stream));
-    }
-    if (out->status) NMOD_ONE_HIP(hipMemcpyAsync(out->status, base + o_status, np, hipMemcpyDeviceToHost, stream));
-    NMOD_ONE_HIP(hipStreamSynchronize(stream));
-  }
-  NMOD_ONE_HIP(slab.release(stream));
+  NMOD_HIP(slab.finish(stream));
   return NMOD_OK;
 }

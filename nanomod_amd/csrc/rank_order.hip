@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/nanomod_hip.h"
+#include "entry_common.hpp"
 #include "radix_sort.hpp"
 
 namespace nmod {
@@ -39,7 +40,8 @@ struct Buf {
   hipError_t alloc(size_t b) { return hipMalloc(&p, b ? b : 1); }
 };
 
-#define NMOD_RO_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
+// (the keys are fp64 or int64 whatever prm->dtype says, and any memspace but NMOD_MEM_HOST means the device)
+constexpr unsigned kRankPrm = kPrmAnyDtype | kPrmAnyMemspace;
 
 }  // namespace nmod
 
@@ -47,12 +49,11 @@ using namespace nmod;
 
 extern "C" int nmod_rank_order(const nmod_params* prm, int64_t npos, const double* key_primary, const double* key_second,
                                const double* key_third, int32_t descending, int32_t* order_out) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params) || npos < 0 || npos > INT32_MAX) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm, kRankPrm) != NMOD_OK || npos < 0 || npos > INT32_MAX) return NMOD_ERR_INVALID_ARG;
   if (npos == 0) return NMOD_OK;
   if (!key_primary || !key_second || !key_third || !order_out) return NMOD_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) return NMOD_ERR_NO_DEVICE;
-  NMOD_RO_HIP(hipSetDevice(prm->device));
+  const int rc = select_device(prm, nullptr);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const bool host = prm->memspace == NMOD_MEM_HOST;
   const size_t n = (size_t)npos;
@@ -60,26 +61,26 @@ extern "C" int nmod_rank_order(const nmod_params* prm, int64_t npos, const doubl
   const double* keys[3] = {key_third, key_second, key_primary};          // least significant first
   if (host) {
     for (int k = 0; k < 3; ++k) {
-      NMOD_RO_HIP(dk[k].alloc(n * 8));
-      NMOD_RO_HIP(hipMemcpyAsync(dk[k].p, keys[k], n * 8, hipMemcpyHostToDevice, stream));
+      NMOD_HIP(dk[k].alloc(n * 8));
+      NMOD_HIP(hipMemcpyAsync(dk[k].p, keys[k], n * 8, hipMemcpyHostToDevice, stream));
       keys[k] = (const double*)dk[k].p;
     }
-    NMOD_RO_HIP(dout.alloc(n * 4));
+    NMOD_HIP(dout.alloc(n * 4));
   }
-  NMOD_RO_HIP(ka.alloc(n * 8)); NMOD_RO_HIP(kb.alloc(n * 8)); NMOD_RO_HIP(ia.alloc(n * 4)); NMOD_RO_HIP(ib.alloc(n * 4));
-  NMOD_RO_HIP(tmp.alloc(rs_scratch_bytes((int64_t)n)));
+  NMOD_HIP(ka.alloc(n * 8)); NMOD_HIP(kb.alloc(n * 8)); NMOD_HIP(ia.alloc(n * 4)); NMOD_HIP(ib.alloc(n * 4));
+  NMOD_HIP(tmp.alloc(rs_scratch_bytes((int64_t)n)));
   const unsigned blocks = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   hipLaunchKernelGGL(rank_iota_kernel, dim3(blocks), dim3(256), 0, stream, (uint32_t*)ia.p, (int64_t)n);
   uint32_t* cur = (uint32_t*)ia.p;
   for (int k = 0; k < 3; ++k) {
     hipLaunchKernelGGL(rank_keys_kernel, dim3(blocks), dim3(256), 0, stream, keys[k], cur, (int64_t)n, (uint64_t*)ka.p);
-    NMOD_RO_HIP(rs_sort_pairs((uint64_t*)ka.p, cur, (uint64_t*)kb.p, (uint32_t*)ib.p, (int64_t)n, tmp.p, stream));   // (in place: eight passes)
+    NMOD_HIP(rs_sort_pairs((uint64_t*)ka.p, cur, (uint64_t*)kb.p, (uint32_t*)ib.p, (int64_t)n, tmp.p, stream));   // (in place: eight passes)
   }
   int32_t* dst = host ? (int32_t*)dout.p : order_out;
   hipLaunchKernelGGL(rank_emit_kernel, dim3(blocks), dim3(256), 0, stream, cur, (int64_t)n, (int)(descending != 0), dst);
-  NMOD_RO_HIP(hipGetLastError());
-  if (host) NMOD_RO_HIP(hipMemcpyAsync(order_out, dst, n * 4, hipMemcpyDeviceToHost, stream));
-  NMOD_RO_HIP(hipStreamSynchronize(stream));          // the temporaries are freed on return
+  NMOD_HIP(hipGetLastError());
+  if (host) NMOD_HIP(hipMemcpyAsync(order_out, dst, n * 4, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipStreamSynchronize(stream));          // the temporaries are freed on return
   return NMOD_OK;
 }
 
@@ -96,29 +97,28 @@ __global__ __launch_bounds__(256) void argsort_keys_kernel(const int64_t* key, i
 }  // namespace nmod
 
 extern "C" int nmod_argsort_keys(const nmod_params* prm, int64_t n, const int64_t* keys, int32_t* order_out) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params) || n < 0 || n > INT32_MAX) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm, kRankPrm) != NMOD_OK || n < 0 || n > INT32_MAX) return NMOD_ERR_INVALID_ARG;
   if (n == 0) return NMOD_OK;
   if (!keys || !order_out) return NMOD_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) return NMOD_ERR_NO_DEVICE;
-  NMOD_RO_HIP(hipSetDevice(prm->device));
+  const int rc = select_device(prm, nullptr);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const bool host = prm->memspace == NMOD_MEM_HOST;
   const size_t cnt = (size_t)n;
   Buf dk, ka, kb, ia, ib, tmp;
   const int64_t* src = keys;
   if (host) {
-    NMOD_RO_HIP(dk.alloc(cnt * 8));
-    NMOD_RO_HIP(hipMemcpyAsync(dk.p, keys, cnt * 8, hipMemcpyHostToDevice, stream));
+    NMOD_HIP(dk.alloc(cnt * 8));
+    NMOD_HIP(hipMemcpyAsync(dk.p, keys, cnt * 8, hipMemcpyHostToDevice, stream));
     src = (const int64_t*)dk.p;
   }
-  NMOD_RO_HIP(ka.alloc(cnt * 8)); NMOD_RO_HIP(kb.alloc(cnt * 8)); NMOD_RO_HIP(ia.alloc(cnt * 4)); NMOD_RO_HIP(ib.alloc(cnt * 4));
-  NMOD_RO_HIP(tmp.alloc(rs_scratch_bytes(n)));
+  NMOD_HIP(ka.alloc(cnt * 8)); NMOD_HIP(kb.alloc(cnt * 8)); NMOD_HIP(ia.alloc(cnt * 4)); NMOD_HIP(ib.alloc(cnt * 4));
+  NMOD_HIP(tmp.alloc(rs_scratch_bytes(n)));
   const unsigned blocks = (unsigned)((cnt + 255) / 256 < 8192 ? (cnt + 255) / 256 : 8192);
   hipLaunchKernelGGL(argsort_keys_kernel, dim3(blocks), dim3(256), 0, stream, src, n, (uint64_t*)ka.p, (uint32_t*)ia.p);
-  NMOD_RO_HIP(rs_sort_pairs((uint64_t*)ka.p, (uint32_t*)ia.p, (uint64_t*)kb.p, (uint32_t*)ib.p, n, tmp.p, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(order_out, ia.p, cnt * 4, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
-  NMOD_RO_HIP(hipStreamSynchronize(stream));          // the temporaries are freed on return
+  NMOD_HIP(rs_sort_pairs((uint64_t*)ka.p, (uint32_t*)ia.p, (uint64_t*)kb.p, (uint32_t*)ib.p, n, tmp.p, stream));
+  NMOD_HIP(hipMemcpyAsync(order_out, ia.p, cnt * 4, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+  NMOD_HIP(hipStreamSynchronize(stream));          // the temporaries are freed on return
   return NMOD_OK;
 }
 
@@ -183,36 +183,35 @@ __global__ __launch_bounds__(256) void region_keys_kernel(RegionArgs a) {
 extern "C" int nmod_region_rank(const nmod_params* prm, int64_t npos, const int32_t* strand_lo, const int32_t* strand_hi,
                                 const int64_t* pos, const char* base, const double* value, int32_t w, int32_t movesize,
                                 char na, double percentile, int32_t wind_ovlp, int32_t* ranked_out, int64_t* n_ranked) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params) || npos < 0 || npos > INT32_MAX || !n_ranked) return NMOD_ERR_INVALID_ARG;
+  if (check_prm_common(prm, kRankPrm) != NMOD_OK || npos < 0 || npos > INT32_MAX || !n_ranked) return NMOD_ERR_INVALID_ARG;
   *n_ranked = 0;
   if (npos == 0) return NMOD_OK;
   if (!strand_lo || !strand_hi || !pos || !base || !value || !ranked_out || w < 0 || movesize < 1) return NMOD_ERR_INVALID_ARG;
   if (prm->memspace != NMOD_MEM_HOST) return NMOD_ERR_INVALID_ARG;              // post-processing of host-side records
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) return NMOD_ERR_NO_DEVICE;
-  NMOD_RO_HIP(hipSetDevice(prm->device));
+  int rc = select_device(prm, nullptr);
+  if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const size_t n = (size_t)npos;
   Buf d_lo, d_hi, d_pos, d_base, d_val, d_key, d_tb, d_ok;
-  NMOD_RO_HIP(d_lo.alloc(n * 4)); NMOD_RO_HIP(d_hi.alloc(n * 4)); NMOD_RO_HIP(d_pos.alloc(n * 8)); NMOD_RO_HIP(d_base.alloc(n));
-  NMOD_RO_HIP(d_val.alloc(n * 8)); NMOD_RO_HIP(d_key.alloc(n * 8)); NMOD_RO_HIP(d_tb.alloc(n * 8)); NMOD_RO_HIP(d_ok.alloc(n));
-  NMOD_RO_HIP(hipMemcpyAsync(d_lo.p, strand_lo, n * 4, hipMemcpyHostToDevice, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(d_hi.p, strand_hi, n * 4, hipMemcpyHostToDevice, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(d_pos.p, pos, n * 8, hipMemcpyHostToDevice, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(d_base.p, base, n, hipMemcpyHostToDevice, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(d_val.p, value, n * 8, hipMemcpyHostToDevice, stream));
+  NMOD_HIP(d_lo.alloc(n * 4)); NMOD_HIP(d_hi.alloc(n * 4)); NMOD_HIP(d_pos.alloc(n * 8)); NMOD_HIP(d_base.alloc(n));
+  NMOD_HIP(d_val.alloc(n * 8)); NMOD_HIP(d_key.alloc(n * 8)); NMOD_HIP(d_tb.alloc(n * 8)); NMOD_HIP(d_ok.alloc(n));
+  NMOD_HIP(hipMemcpyAsync(d_lo.p, strand_lo, n * 4, hipMemcpyHostToDevice, stream));
+  NMOD_HIP(hipMemcpyAsync(d_hi.p, strand_hi, n * 4, hipMemcpyHostToDevice, stream));
+  NMOD_HIP(hipMemcpyAsync(d_pos.p, pos, n * 8, hipMemcpyHostToDevice, stream));
+  NMOD_HIP(hipMemcpyAsync(d_base.p, base, n, hipMemcpyHostToDevice, stream));
+  NMOD_HIP(hipMemcpyAsync(d_val.p, value, n * 8, hipMemcpyHostToDevice, stream));
   RegionArgs ra;
   ra.npos = npos; ra.s_lo = (const int32_t*)d_lo.p; ra.s_hi = (const int32_t*)d_hi.p; ra.pos = (const int64_t*)d_pos.p;
   ra.base = (const char*)d_base.p; ra.value = (const double*)d_val.p; ra.w = w; ra.movesize = movesize; ra.na = na; ra.pct = percentile;
   ra.key = (double*)d_key.p; ra.tb = (double*)d_tb.p; ra.valid = (uint8_t*)d_ok.p;
   hipLaunchKernelGGL(region_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ra);
-  NMOD_RO_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   std::vector<double> key(n), tb(n);
   std::vector<uint8_t> ok(n);
-  NMOD_RO_HIP(hipMemcpyAsync(key.data(), d_key.p, n * 8, hipMemcpyDeviceToHost, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(tb.data(), d_tb.p, n * 8, hipMemcpyDeviceToHost, stream));
-  NMOD_RO_HIP(hipMemcpyAsync(ok.data(), d_ok.p, n, hipMemcpyDeviceToHost, stream));
-  NMOD_RO_HIP(hipStreamSynchronize(stream));
+  NMOD_HIP(hipMemcpyAsync(key.data(), d_key.p, n * 8, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipMemcpyAsync(tb.data(), d_tb.p, n * 8, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipMemcpyAsync(ok.data(), d_ok.p, n, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipStreamSynchronize(stream));
   // the windows, in generation order (= position order), then ranked by (key, tie-break), stable
   std::vector<int32_t> cand;
   std::vector<double> ck, ct;
@@ -221,7 +220,7 @@ extern "C" int nmod_region_rank(const nmod_params* prm, int64_t npos, const int3
   if (nc == 0) return NMOD_OK;
   std::vector<double> zeros((size_t)nc, 0.0);
   std::vector<int32_t> order((size_t)nc);
-  int rc = nmod_rank_order(prm, nc, ck.data(), ct.data(), zeros.data(), 0, order.data());
+  rc = nmod_rank_order(prm, nc, ck.data(), ct.data(), zeros.data(), 0, order.data());
   if (rc != NMOD_OK) return rc;
   int64_t out = 0;
   if (wind_ovlp == 1) {

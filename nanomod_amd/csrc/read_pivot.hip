@@ -30,13 +30,11 @@
 #include <type_traits>
 
 #include "../../include/nanomod_hip.h"
-#include "scratch_pool.hpp"
+#include "entry_common.hpp"
 #include "radix_sort.hpp"
 
 namespace nmod {
 namespace {
-
-#define NMOD_RP_HIP(call) do { if ((call) != hipSuccess) return NMOD_ERR_HIP; } while (0)
 
 constexpr int kPosBits = 40;
 constexpr int64_t kPosLimit = (int64_t)1 << kPosBits;
@@ -45,11 +43,7 @@ constexpr int kWaves = 4;                     // waves per block of the per-read
 constexpr int kScanPer = 16, kScanChunk = 256 * kScanPer;
 constexpr int64_t kDeviceEncodeAbove = 4000000;   // detect.DEVICE_ENCODE_ABOVE: float64 batches above it pass through
 
-inline unsigned grid_for(int64_t n, int64_t per_block) {
-  const int64_t b = (n + per_block - 1) / per_block;
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+inline unsigned grid_for(int64_t n, int64_t per_block) { return persistent_grid(n, per_block, 65536); }
 
 // ---------------------------------------------------------------------------------------------------- int64 scans
 enum { kScanId = 0, kScanNonzero = 1 };
@@ -286,41 +280,34 @@ int order_rows(int64_t npos, const int64_t* off, const uint32_t* eidx, const voi
                uint8_t* base_out, unsigned long long* large, int64_t* lrow, int64_t* loff, int dev, hipStream_t s) {
   hipLaunchKernelGGL(rp_order_kernel<T>, dim3(grid_for(npos, kWaves * 16)), dim3(64 * kWaves), 0, s, npos, off, eidx,
                      (const T*)val, base, (T*)sig_out, base_out, large, lrow, loff);
-  NMOD_RP_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   unsigned long long h = 0;
-  NMOD_RP_HIP(hipMemcpyAsync(&h, large, sizeof(h), hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(hipMemcpyAsync(&h, large, sizeof(h), hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipStreamSynchronize(s));
   const int64_t nlarge = (int64_t)(h >> 32), total = (int64_t)(h & 0xFFFFFFFFull);
   if (nlarge == 0) return NMOD_OK;
   if (total >= INT32_MAX) return NMOD_ERR_INVALID_ARG;                        // the radix sort's index range (documented in the header)
   const size_t kb = (size_t)align256(total * 8), vb = (size_t)align256(total * 4);
   DevScratch ls;
-  NMOD_RP_HIP(ls.alloc(2 * kb + 2 * vb + rs_scratch_bytes(total), s, dev));
+  NMOD_HIP(ls.alloc(2 * kb + 2 * vb + rs_scratch_bytes(total), s, dev));
   char* p = static_cast<char*>(ls.p);
   uint64_t* ka = (uint64_t*)p; uint64_t* kb2 = (uint64_t*)(p + kb);
   uint32_t* va = (uint32_t*)(p + 2 * kb); uint32_t* vb2 = (uint32_t*)(p + 2 * kb + vb);
   hipLaunchKernelGGL(rp_large_keys_kernel, dim3(grid_for(nlarge, kWaves)), dim3(64 * kWaves), 0, s, nlarge, (const int64_t*)lrow,
                      (const int64_t*)loff, off, eidx, ka, va);
-  NMOD_RP_HIP(hipGetLastError());
-  NMOD_RP_HIP(rs_sort_pairs(ka, va, kb2, vb2, total, p + 2 * kb + 2 * vb, s));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(rs_sort_pairs(ka, va, kb2, vb2, total, p + 2 * kb + 2 * vb, s));
   hipLaunchKernelGGL(rp_large_place_kernel<T>, dim3(grid_for(total, 256 * 8)), dim3(256), 0, s, total, (const uint64_t*)ka,
                      (const int64_t*)lrow, (const int64_t*)loff, off, (const T*)val, base, (T*)sig_out, base_out);
-  NMOD_RP_HIP(hipGetLastError());
-  NMOD_RP_HIP(ls.release(s));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(ls.release(s));
   return NMOD_OK;
 }
 
-int elem_size(int32_t dtype) {
-  return dtype == NMOD_DTYPE_F32 ? 4 : dtype == NMOD_DTYPE_I16_MILLI ? 2 : dtype == NMOD_DTYPE_F64 ? 8 : 0;
-}
-
+// the pivot works on device-resident tables only
 int begin_call(const nmod_params* prm) {
-  if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params) || prm->memspace != NMOD_MEM_DEVICE || !elem_size(prm->dtype))
-    return NMOD_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || prm->device < 0 || prm->device >= ndev) return NMOD_ERR_NO_DEVICE;
-  NMOD_RP_HIP(hipSetDevice(prm->device));
-  return NMOD_OK;
+  if (check_prm_common(prm) != NMOD_OK || prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
+  return select_device(prm, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------- select / gather
@@ -435,7 +422,7 @@ int launch_gather(int32_t out_dtype, int64_t ntested, const int64_t* rows, const
     hipLaunchKernelGGL((rp_gather_kernel<TI, int16_t>), g, b, 0, s, ntested, rows, off, (const TI*)sig, off_out, (int16_t*)sig_out);
   else
     hipLaunchKernelGGL((rp_gather_kernel<TI, double>), g, b, 0, s, ntested, rows, off, (const TI*)sig, off_out, (double*)sig_out);
-  NMOD_RP_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   return NMOD_OK;
 }
 
@@ -465,15 +452,15 @@ extern "C" int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t 
     return NMOD_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)prm->stream;
   int64_t nevents = 0;
-  NMOD_RP_HIP(hipMemcpyAsync(&nevents, roff + nreads, 8, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(hipMemcpyAsync(&nevents, roff + nreads, 8, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipStreamSynchronize(s));
   if (nevents < 0 || nevents > (int64_t)UINT32_MAX) return NMOD_ERR_INVALID_ARG;   // event indices are 32-bit
   if (nevents > 0 && (!val || !base || !sig_out)) return NMOD_ERR_INVALID_ARG;
   // ---- per-cs covered range
   const int64_t nc = ncs > 0 ? ncs : 1;
   DevScratch head;
   const size_t head_bytes = 256 + (size_t)align256(nc * 8) * 2 + (size_t)align256((nc + 1) * 8);
-  NMOD_RP_HIP(head.alloc(head_bytes, s, prm->device));
+  NMOD_HIP(head.alloc(head_bytes, s, prm->device));
   char* hp = static_cast<char*>(head.p);
   int* err = (int*)hp;
   int64_t* totals = (int64_t*)(hp + 64);                        // [npos, nsamples]
@@ -481,20 +468,20 @@ extern "C" int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t 
   int64_t* cmin = (int64_t*)(hp + 256);
   int64_t* cmax = (int64_t*)(hp + 256 + align256(nc * 8));
   int64_t* cbase = (int64_t*)(hp + 256 + 2 * align256(nc * 8));
-  NMOD_RP_HIP(hipMemsetAsync(hp, 0, 256, s));
-  NMOD_RP_HIP(hipMemsetAsync(cmin, 0xFF, nc * 8, s));
-  NMOD_RP_HIP(hipMemsetAsync(cmax, 0, nc * 8, s));
+  NMOD_HIP(hipMemsetAsync(hp, 0, 256, s));
+  NMOD_HIP(hipMemsetAsync(cmin, 0xFF, nc * 8, s));
+  NMOD_HIP(hipMemsetAsync(cmax, 0, nc * 8, s));
   if (nreads > 0) {
     hipLaunchKernelGGL(rp_check_kernel, dim3(grid_for(nreads, 256)), dim3(256), 0, s, nreads, ncs, cs, start, roff, nevents, pos_lo, pos_hi,
                        err, (unsigned long long*)cmin, (unsigned long long*)cmax);
-    NMOD_RP_HIP(hipGetLastError());
+    NMOD_HIP(hipGetLastError());
   }
   std::vector<int64_t> hmin(nc), hmax(nc), hbase(nc + 1);
   int herr = 0;
-  NMOD_RP_HIP(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipMemcpyAsync(hmin.data(), cmin, nc * 8, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipMemcpyAsync(hmax.data(), cmax, nc * 8, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipMemcpyAsync(hmin.data(), cmin, nc * 8, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipMemcpyAsync(hmax.data(), cmax, nc * 8, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipStreamSynchronize(s));
   if (herr) return NMOD_ERR_INVALID_ARG;
   int64_t S = 0;
   for (int64_t c = 0; c < nc; ++c) {
@@ -504,18 +491,18 @@ extern "C" int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t 
   }
   hbase[nc] = S;
   if (S == 0) {
-    NMOD_RP_HIP(hipMemsetAsync(off_out, 0, 8, s));
-    NMOD_RP_HIP(hipStreamSynchronize(s));
+    NMOD_HIP(hipMemsetAsync(off_out, 0, 8, s));
+    NMOD_HIP(hipStreamSynchronize(s));
     return NMOD_OK;
   }
-  NMOD_RP_HIP(hipMemcpyAsync(cmin, hmin.data(), nc * 8, hipMemcpyHostToDevice, s));
-  NMOD_RP_HIP(hipMemcpyAsync(cbase, hbase.data(), (nc + 1) * 8, hipMemcpyHostToDevice, s));
+  NMOD_HIP(hipMemcpyAsync(cmin, hmin.data(), nc * 8, hipMemcpyHostToDevice, s));
+  NMOD_HIP(hipMemcpyAsync(cbase, hbase.data(), (nc + 1) * 8, hipMemcpyHostToDevice, s));
   // ---- samples per dense position, rows, offsets.  Scratch: 28 B per dense position + 4 B per event (+ 16 B per large row)
   const int64_t nlcap = nevents / (kSmallRow + 1) + 1;
   const size_t b_cnt = align256((S + 1) * 8), b_row = align256(S * 8), b_cur = align256(S * 4), b_eidx = align256(nevents * 4),
                b_l = align256(nlcap * 8), b_bs = align256(scan_blocks(S + 1) * 8);
   DevScratch body;
-  NMOD_RP_HIP(body.alloc(b_cnt + 2 * b_row + b_cur + b_eidx + 2 * b_l + b_bs, s, prm->device));
+  NMOD_HIP(body.alloc(b_cnt + 2 * b_row + b_cur + b_eidx + 2 * b_l + b_bs, s, prm->device));
   char* p = static_cast<char*>(body.p);
   int64_t* cnt = (int64_t*)p; p += b_cnt;
   int64_t* rowid = (int64_t*)p; p += b_row;
@@ -525,24 +512,24 @@ extern "C" int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t 
   int64_t* lrow = (int64_t*)p; p += b_l;
   int64_t* loff = (int64_t*)p; p += b_l;
   int64_t* bsum = (int64_t*)p;
-  NMOD_RP_HIP(hipMemsetAsync(cnt, 0, (S + 1) * 8, s));
-  NMOD_RP_HIP(hipMemsetAsync(cur, 0, S * 4, s));
+  NMOD_HIP(hipMemsetAsync(cnt, 0, (S + 1) * 8, s));
+  NMOD_HIP(hipMemsetAsync(cur, 0, S * 4, s));
   hipLaunchKernelGGL(rp_diff_kernel, dim3(grid_for(nreads, 256)), dim3(256), 0, s, nreads, cs, start, roff, pos_lo, pos_hi,
                      (const int64_t*)cmin, (const int64_t*)cbase, (unsigned long long*)cnt);
-  NMOD_RP_HIP(hipGetLastError());
-  NMOD_RP_HIP((scan_i64<kScanId, true>(cnt, cnt, S, bsum, nullptr, s)));
-  NMOD_RP_HIP((scan_i64<kScanNonzero, false>(cnt, rowid, S, bsum, totals, s)));
-  NMOD_RP_HIP((scan_i64<kScanId, false>(cnt, soff, S, bsum, totals + 1, s)));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP((scan_i64<kScanId, true>(cnt, cnt, S, bsum, nullptr, s)));
+  NMOD_HIP((scan_i64<kScanNonzero, false>(cnt, rowid, S, bsum, totals, s)));
+  NMOD_HIP((scan_i64<kScanId, false>(cnt, soff, S, bsum, totals + 1, s)));
   int64_t ht[2];
-  NMOD_RP_HIP(hipMemcpyAsync(ht, totals, 16, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(hipMemcpyAsync(ht, totals, 16, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipStreamSynchronize(s));
   if (ht[0] > cap_pos || (ht[0] > 0 && !key_out) || (ht[0] > 0 && !base_out)) return NMOD_ERR_INVALID_ARG;
   hipLaunchKernelGGL(rp_rows_kernel, dim3(grid_for(S, 256 * 8)), dim3(256), 0, s, S, ncs, (const int64_t*)cnt, (const int64_t*)rowid,
                      (const int64_t*)soff, (const int64_t*)cmin, (const int64_t*)cbase, (const int64_t*)totals, key_out, off_out);
-  NMOD_RP_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   hipLaunchKernelGGL(rp_place_kernel, dim3(grid_for(nreads, kWaves)), dim3(64 * kWaves), 0, s, nreads, cs, start, roff, pos_lo, pos_hi,
                      (const int64_t*)cmin, (const int64_t*)cbase, (const int64_t*)soff, cur, eidx);
-  NMOD_RP_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   const int64_t npos = ht[0];
   if (prm->dtype == NMOD_DTYPE_F32)
     rc = order_rows<float>(npos, off_out, eidx, val, base, sig_out, base_out, large, lrow, loff, prm->device, s);
@@ -551,9 +538,9 @@ extern "C" int nmod_pivot_reads(const nmod_params* prm, int64_t nreads, int32_t 
   else
     rc = order_rows<double>(npos, off_out, eidx, val, base, sig_out, base_out, large, lrow, loff, prm->device, s);
   if (rc != NMOD_OK) return rc;
-  NMOD_RP_HIP(body.release(s));
-  NMOD_RP_HIP(head.release(s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(body.release(s));
+  NMOD_HIP(head.release(s));
+  NMOD_HIP(hipStreamSynchronize(s));
   *npos_out = ht[0];
   *nsamples_out = ht[1];
   return NMOD_OK;
@@ -577,7 +564,7 @@ extern "C" int nmod_select_tested(const nmod_params* prm, int64_t min_coverage,
   const int64_t m = npos0 > 0 ? npos0 : 1;
   const size_t b = align256(m * 8), b_bs = align256((scan_blocks(m) + 1) * 8);
   DevScratch scr;
-  NMOD_RP_HIP(scr.alloc(256 + 3 * b + b_bs, s, prm->device));
+  NMOD_HIP(scr.alloc(256 + 3 * b + b_bs, s, prm->device));
   char* p = static_cast<char*>(scr.p);
   int* err = (int*)p;
   int64_t* tot = (int64_t*)(p + 64);
@@ -586,44 +573,44 @@ extern "C" int nmod_select_tested(const nmod_params* prm, int64_t min_coverage,
   int64_t* match = (int64_t*)(p + 256 + b);
   int64_t* tidx = (int64_t*)(p + 256 + 2 * b);
   int64_t* bsum = (int64_t*)(p + 256 + 3 * b);
-  NMOD_RP_HIP(hipMemsetAsync(p, 0, 256, s));
+  NMOD_HIP(hipMemsetAsync(p, 0, 256, s));
   hipLaunchKernelGGL(rp_check_off_kernel, dim3(grid_for(npos0 + 1, 256)), dim3(256), 0, s, npos0, off0, nsig0, err);
   hipLaunchKernelGGL(rp_check_off_kernel, dim3(grid_for(npos1 + 1, 256)), dim3(256), 0, s, npos1, off1, nsig1, err);
-  NMOD_RP_HIP(hipGetLastError());
+  NMOD_HIP(hipGetLastError());
   int herr = 0;
-  NMOD_RP_HIP(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+  NMOD_HIP(hipStreamSynchronize(s));
   if (herr) return NMOD_ERR_INVALID_ARG;
   int64_t nt = 0;
   if (npos0 > 0 && npos1 > 0) {
     hipLaunchKernelGGL(rp_match_kernel, dim3(grid_for(npos0, 256)), dim3(256), 0, s, npos0, key0, off0, npos1, key1, off1, min_coverage,
                        flag, match);
-    NMOD_RP_HIP(hipGetLastError());
-    NMOD_RP_HIP((scan_i64<kScanId, false>(flag, tidx, npos0, bsum, tot, s)));
-    NMOD_RP_HIP(hipMemcpyAsync(&nt, tot, 8, hipMemcpyDeviceToHost, s));
-    NMOD_RP_HIP(hipStreamSynchronize(s));
+    NMOD_HIP(hipGetLastError());
+    NMOD_HIP((scan_i64<kScanId, false>(flag, tidx, npos0, bsum, tot, s)));
+    NMOD_HIP(hipMemcpyAsync(&nt, tot, 8, hipMemcpyDeviceToHost, s));
+    NMOD_HIP(hipStreamSynchronize(s));
   }
   if (nt > cap || (nt > 0 && (!rows0 || !rows1))) return NMOD_ERR_INVALID_ARG;
   int32_t out_dtype = prm->dtype;
   int64_t ns[2] = {0, 0};
   if (nt == 0) {
-    NMOD_RP_HIP(hipMemsetAsync(off0_out, 0, 8, s));
-    NMOD_RP_HIP(hipMemsetAsync(off1_out, 0, 8, s));
+    NMOD_HIP(hipMemsetAsync(off0_out, 0, 8, s));
+    NMOD_HIP(hipMemsetAsync(off1_out, 0, 8, s));
   } else {
     // the tested rows' lengths go to off*_out[0, nt) and are scanned there in place; the sums land at off*_out[nt]
     hipLaunchKernelGGL(rp_compact_kernel, dim3(grid_for(npos0, 256)), dim3(256), 0, s, npos0, (const int64_t*)flag, (const int64_t*)tidx,
                        (const int64_t*)match, off0, off1, rows0, rows1, off0_out, off1_out);
-    NMOD_RP_HIP(hipGetLastError());
-    NMOD_RP_HIP((scan_i64<kScanId, false>(off0_out, off0_out, nt, bsum, off0_out + nt, s)));
-    NMOD_RP_HIP((scan_i64<kScanId, false>(off1_out, off1_out, nt, bsum, off1_out + nt, s)));
-    NMOD_RP_HIP(hipMemcpyAsync(&ns[0], off0_out + nt, 8, hipMemcpyDeviceToHost, s));
-    NMOD_RP_HIP(hipMemcpyAsync(&ns[1], off1_out + nt, 8, hipMemcpyDeviceToHost, s));
-    NMOD_RP_HIP(hipStreamSynchronize(s));
+    NMOD_HIP(hipGetLastError());
+    NMOD_HIP((scan_i64<kScanId, false>(off0_out, off0_out, nt, bsum, off0_out + nt, s)));
+    NMOD_HIP((scan_i64<kScanId, false>(off1_out, off1_out, nt, bsum, off1_out + nt, s)));
+    NMOD_HIP(hipMemcpyAsync(&ns[0], off0_out + nt, 8, hipMemcpyDeviceToHost, s));
+    NMOD_HIP(hipMemcpyAsync(&ns[1], off1_out + nt, 8, hipMemcpyDeviceToHost, s));
+    NMOD_HIP(hipStreamSynchronize(s));
     // detect.encode_pair over the tested samples: one dtype for both groups
     const bool passthrough = prm->dtype == NMOD_DTYPE_F32 || (prm->dtype == NMOD_DTYPE_F64 && ns[0] + ns[1] > kDeviceEncodeAbove);
     if (!passthrough) {
       const int three = 3;
-      NMOD_RP_HIP(hipMemcpyAsync(bits, &three, 4, hipMemcpyHostToDevice, s));
+      NMOD_HIP(hipMemcpyAsync(bits, &three, 4, hipMemcpyHostToDevice, s));
       const dim3 g(grid_for(nt, kWaves * 16)), bl(64 * kWaves);
       for (int grp = 0; grp < 2; ++grp) {
         const int64_t* rows = grp ? rows1 : rows0; const int64_t* off = grp ? off1 : off0; const void* sig = grp ? sig1 : sig0;
@@ -632,16 +619,16 @@ extern "C" int nmod_select_tested(const nmod_params* prm, int64_t min_coverage,
         else
           hipLaunchKernelGGL(rp_dtype_kernel<double>, g, bl, 0, s, nt, (const int64_t*)rows, off, (const double*)sig, bits);
       }
-      NMOD_RP_HIP(hipGetLastError());
+      NMOD_HIP(hipGetLastError());
       int hb = 0;
-      NMOD_RP_HIP(hipMemcpyAsync(&hb, bits, 4, hipMemcpyDeviceToHost, s));
-      NMOD_RP_HIP(hipStreamSynchronize(s));
+      NMOD_HIP(hipMemcpyAsync(&hb, bits, 4, hipMemcpyDeviceToHost, s));
+      NMOD_HIP(hipStreamSynchronize(s));
       out_dtype = (hb & 1) ? NMOD_DTYPE_F32 : (hb & 2) ? NMOD_DTYPE_I16_MILLI : NMOD_DTYPE_F64;
       if (prm->dtype == NMOD_DTYPE_I16_MILLI && !(hb & 1)) out_dtype = NMOD_DTYPE_I16_MILLI;
     }
   }
-  NMOD_RP_HIP(scr.release(s));
-  NMOD_RP_HIP(hipStreamSynchronize(s));
+  NMOD_HIP(scr.release(s));
+  NMOD_HIP(hipStreamSynchronize(s));
   *ntested_out = nt; *nsamples0_out = ns[0]; *nsamples1_out = ns[1]; *dtype_out = out_dtype;
   return NMOD_OK;
 }
@@ -653,7 +640,7 @@ extern "C" int nmod_gather_tested(const nmod_params* prm, int64_t ntested, const
                                   int32_t* run_out, int64_t* key_out, uint8_t* base0_out, uint8_t* base1_out) {
   int rc = begin_call(prm);
   if (rc != NMOD_OK) return rc;
-  if (ntested < 0 || !elem_size(out_dtype) || (prm->dtype == NMOD_DTYPE_F32 && out_dtype != NMOD_DTYPE_F32)) return NMOD_ERR_INVALID_ARG;
+  if (ntested < 0 || !elem_bytes(out_dtype) || (prm->dtype == NMOD_DTYPE_F32 && out_dtype != NMOD_DTYPE_F32)) return NMOD_ERR_INVALID_ARG;
   if (ntested == 0) return NMOD_OK;
   if (!rows0 || !rows1 || !off0 || !off1 || !sig0 || !sig1 || !base0 || !base1 || !key1 || !off0_out || !off1_out || !sig0_out ||
       !sig1_out || !run_out || !key_out || !base0_out || !base1_out)
@@ -669,15 +656,15 @@ extern "C" int nmod_gather_tested(const nmod_params* prm, int64_t ntested, const
   }
   DevScratch scr;
   const size_t b = align256(ntested * 8);
-  NMOD_RP_HIP(scr.alloc(b + align256((scan_blocks(ntested) + 1) * 8), s, prm->device));
+  NMOD_HIP(scr.alloc(b + align256((scan_blocks(ntested) + 1) * 8), s, prm->device));
   int64_t* brk = (int64_t*)scr.p;
   int64_t* bsum = (int64_t*)((char*)scr.p + b);
   hipLaunchKernelGGL(rp_meta_kernel, dim3(grid_for(ntested, 256)), dim3(256), 0, s, ntested, rows0, rows1, key1, base0, base1, key_out,
                      base0_out, base1_out, brk);
-  NMOD_RP_HIP(hipGetLastError());
-  NMOD_RP_HIP((scan_i64<kScanId, true>(brk, brk, ntested, bsum, nullptr, s)));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP((scan_i64<kScanId, true>(brk, brk, ntested, bsum, nullptr, s)));
   hipLaunchKernelGGL(rp_run_kernel, dim3(grid_for(ntested, 256)), dim3(256), 0, s, ntested, (const int64_t*)brk, run_out);
-  NMOD_RP_HIP(hipGetLastError());
-  NMOD_RP_HIP(scr.release(s));
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(scr.release(s));
   return NMOD_OK;
 }
