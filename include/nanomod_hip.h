@@ -539,6 +539,56 @@ int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void* sig, const
                     const double* keep_lo, const double* keep_hi /* ncodes each, both NULL = keep everything */,
                     const nmod_kmer_out* out);
 
+/* Per-read shift and scale against a k-mer model (K11; the reference project has no such step): a robust weighted linear fit of a
+ * read's event levels x against the model levels mu of their k-mers, x ~ a + b mu, and the rescaled events (x - a) / b, so that the reads
+ * of a sample sit on the scale of a model built by nmod_kmer_model from another run.
+ *   Inputs: a read set as flat arrays in nmod_pivot_reads' layout: off[nreads + 1] (int64 CSR event offsets; required, there is no stride
+ *     form), val (prm->dtype) and base (one byte per event, the read's own base), events in read direction for both strands.
+ *   Model: k in 1 .. 8, center in 0 .. k - 1, mean[4^k] and sd[4^k] (doubles, in the call's memspace).
+ *   Code of an event: event j of a read of n events has the code c_j of the bytes base[j - center .. j + k - 1 - center]: A = 0, C = 1,
+ *     G = 2, T = 3, upper case only, the first base most significant (kmermodel.kmer_codes' convention); c_j = -1 when the window leaves
+ *     the read or holds any other byte.
+ *   Eligible: c_j >= 0, mean[c_j] and sd[c_j] finite with sd[c_j] > 0, and x_j finite.  x_j is the value as a double (int16 k / 1000.0, a
+ *     division; float32 up-cast; float64 as is), mu_j and s_j the model entries, w_j = 1.0 / (s_j * s_j) when `weighted`, else 1.
+ *   Fit over a kept set K: W = sum w, mb = sum w mu / W, xb = sum w x / W, Smm = sum w (mu - mb)^2, Smx = sum w (mu - mb)(x - xb),
+ *     b = Smx / Smm, a = xb - b mb.  The sums are taken in fp64 about the read's first eligible event (mu_0, x_0) — mu - mu_0 and
+ *     x - x_0 in place of mu and x, which changes no centred sum in exact arithmetic and makes Smm exactly 0 for a read of one level —
+ *     in a fixed order (a chain per lane, then a fixed lane / wave reduction; no float atomics).
+ *     Round 0 uses K = the eligible events; each of clip_rounds further rounds keeps the eligible events with
+ *     |x_j - a - b mu_j| <= clip_sigma |b| s_j, (a, b) from the round before, and fits again.
+ *   A read fails, at the first round where it applies, with NMOD_RESCALE_TOO_FEW (|K| < min_events), NMOD_RESCALE_DEGENERATE (Smm not
+ *     > 0, b not finite or b <= 0, a not finite), after the last round with NMOD_RESCALE_OUT_OF_RANGE (b outside [scale_lo, scale_hi]), and before any
+ *     with NMOD_RESCALE_TOO_LARGE (n > NMOD_MAX_DEEP).
+ *   Outputs per read (a NULL member is skipped): shift = a, scale = b, n_used = |K| of the last round that ran, status (NMOD_RESCALE_*
+ *     bits).  A failed read gets shift = 0 and scale = 1, and its events are copied unchanged.
+ *   Apply: val_out has the dtype and layout of val and may be val itself.  Every event of a fitted read, eligible or not:
+ *     r = 1.0 / b, x' = (x - a) * r (a non-finite x stays as it is); float64: x', float32: (float)x', int16: rint(1000.0 * x'), ties to
+ *     even, saturated to +-32 767, and a saturation sets NMOD_RESCALE_CLAMPED on the read.  Compiled with contraction off: bit-defined.
+ *   Modes: NMOD_RESCALE_FIT_APPLY; NMOD_RESCALE_FIT_ONLY (val_out is not touched); NMOD_RESCALE_APPLY_ONLY: shift / scale are INPUTS
+ *     (left as they are), the model and base are not read, n_used = 0; a read whose scale is not finite or <= 0, or whose shift is not
+ *     finite, is DEGENERATE and copied unchanged.
+ * Reads struct_size, device, stream, memspace, dtype of prm and nothing else.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no
+ * host read and no synchronisation; scratch (8 bytes per read + 24 bytes per model entry) comes stream-ordered from the library's pool.
+ * NMOD_MEM_HOST: copy in, run, copy back, synchronise (one staged copy).  nreads == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG before any
+ * device work: an unknown mode, k or center out of range, clip_rounds outside 0 .. 8, clip_sigma not finite or <= 0 with clip_rounds > 0,
+ * min_events < 2, scale_lo not > 0 or not finite or > scale_hi, nreads < 0 or beyond 2^32 - 2, NULL off / val with nreads > 0, NULL base
+ * or model (or its arrays) when the mode fits, NULL val_out when it applies, NULL shift / scale in APPLY_ONLY, opts / out NULL or of
+ * another struct_size, an unknown dtype, host offsets that decrease.
+ * A read's outputs are the same bits whatever else is in the batch, in any order of the reads, from host or device memory, in place or
+ * not.  A read is computed by one wave (up to NMOD_RESCALE_WAVE_MAX events) or one workgroup: a single very long read is not split. */
+enum { NMOD_RESCALE_FIT_APPLY = 0, NMOD_RESCALE_FIT_ONLY = 1, NMOD_RESCALE_APPLY_ONLY = 2 };
+enum { NMOD_RESCALE_TOO_FEW = 1, NMOD_RESCALE_DEGENERATE = 2, NMOD_RESCALE_OUT_OF_RANGE = 4, NMOD_RESCALE_CLAMPED = 8, NMOD_RESCALE_TOO_LARGE = 16 };
+#define NMOD_RESCALE_WAVE_MAX 2048         /* events of a read: up to here a wave computes it, beyond a workgroup */
+typedef struct nmod_rescale_model { int32_t k, center; const double *mean, *sd; /* 4^k each */ } nmod_rescale_model;
+typedef struct nmod_rescale_opts { int32_t struct_size, mode, weighted, clip_rounds, min_events, reserved;
+  double clip_sigma, scale_lo, scale_hi; } nmod_rescale_opts;
+typedef struct nmod_rescale_out { int32_t struct_size; int32_t reserved;
+  double *shift, *scale;          /* nreads each; inputs in NMOD_RESCALE_APPLY_ONLY */
+  int32_t* n_used; uint8_t* status; /* nreads each */
+  void* val_out;                  /* the events, prm->dtype, in val's layout */ } nmod_rescale_out;
+int nmod_rescale_reads(const nmod_params* prm, int64_t nreads, const int64_t* off, const void* val, const uint8_t* base,
+                       const nmod_rescale_model* model, const nmod_rescale_opts* opts, const nmod_rescale_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

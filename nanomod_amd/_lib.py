@@ -117,6 +117,42 @@ def make_kmer_out(**members):
     return o
 
 
+RESCALE_FIT_APPLY, RESCALE_FIT_ONLY, RESCALE_APPLY_ONLY = 0, 1, 2
+RESCALE_MODE_BY_NAME = {'fit_apply': RESCALE_FIT_APPLY, 'fit_only': RESCALE_FIT_ONLY, 'apply_only': RESCALE_APPLY_ONLY}
+RESCALE_TOO_FEW, RESCALE_DEGENERATE, RESCALE_OUT_OF_RANGE, RESCALE_CLAMPED, RESCALE_TOO_LARGE = 1, 2, 4, 8, 16
+RESCALE_FAILED = RESCALE_TOO_FEW | RESCALE_DEGENERATE | RESCALE_OUT_OF_RANGE | RESCALE_TOO_LARGE
+RESCALE_WAVE_MAX = 2048   # nmod_rescale_reads: events of a read up to which one wave computes it (a workgroup beyond)
+
+
+class NmodRescaleModel(C.Structure):
+    _fields_ = [('k', C.c_int32), ('center', C.c_int32), ('mean', C.c_void_p), ('sd', C.c_void_p)]
+
+
+class NmodRescaleOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'mode', 'weighted', 'clip_rounds', 'min_events', 'reserved')] + \
+               [(n, C.c_double) for n in ('clip_sigma', 'scale_lo', 'scale_hi')]
+
+
+class NmodRescaleOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in ('shift', 'scale', 'n_used', 'status', 'val_out')]
+
+
+def make_rescale_opts(mode=RESCALE_FIT_APPLY, weighted=True, clip_sigma=3.0, clip_rounds=2, min_events=50, scale_lo=0.5, scale_hi=2.0):
+    o = NmodRescaleOpts()
+    o.struct_size = C.sizeof(NmodRescaleOpts)
+    o.mode, o.weighted, o.clip_rounds, o.min_events = int(mode), int(bool(weighted)), int(clip_rounds), int(min_events)
+    o.clip_sigma, o.scale_lo, o.scale_hi = float(clip_sigma), float(scale_lo), float(scale_hi)
+    return o
+
+
+def make_rescale_out(**members):
+    o = NmodRescaleOut()
+    o.struct_size = C.sizeof(NmodRescaleOut)
+    for k, v in members.items():
+        setattr(o, k, v)
+    return o
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -172,6 +208,8 @@ _SIGNATURES = {
     'nmod_one_sample': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(NmodOneOut)]),
     'nmod_kmer_model': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.POINTER(NmodKmerOut)]),
+    'nmod_rescale_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
+                                     C.POINTER(NmodRescaleOpts), C.POINTER(NmodRescaleOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

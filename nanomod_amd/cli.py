@@ -77,14 +77,14 @@ def build_parser():
                    '(nmod_pivot_reads), as read-level .npz containers always are')
     pr = sub.add_parser('profile', help='reduce one read group to a per-position control profile (coverage, mean, sd) for detect1')
     pr.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
-    pr.add_argument('--wrkBase1', required=True, help='the control read group: a per-position .npz container')
+    pr.add_argument('--wrkBase1', required=True, help='the control read group: a .npz container (per position or read-level)')
     pr.add_argument('--MinCoverage', type=int, default=5)
     pr.add_argument('--outFolder', default='mRes')
     pr.add_argument('--FileID', default='mod', help='the profile is written to <outFolder>/<FileID>_profile.npz')
     pr.add_argument('--device', type=int, default=0)
     o = sub.add_parser('detect1', help='one read group against a stored profile: KS against N(mean, sd^2), t, window combine')
     o.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
-    o.add_argument('--wrkBase1', required=True, help='the sample read group: a per-position .npz container')
+    o.add_argument('--wrkBase1', required=True, help='the sample read group: a .npz container (per position or read-level)')
     o.add_argument('--refProfile', required=True, help="a profile written by 'profile' (a control) or by onesample.save_profile (a model)")
     o.add_argument('--FileID', default='mod')
     o.add_argument('--outFolder', default='mRes')
@@ -103,7 +103,7 @@ def build_parser():
     o.add_argument('--fdrAlpha', type=float, default=0.05)
     km = sub.add_parser('kmermodel', help='pool a control read group into a k-mer level model (level and spread per k-mer) on the device')
     km.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
-    km.add_argument('--wrkBase1', required=True, help='the control read group: a per-position .npz container')
+    km.add_argument('--wrkBase1', required=True, help='the control read group: a .npz container (per position or read-level)')
     km.add_argument('--kmer', type=int, default=5, help='k, 1 .. 8')
     km.add_argument('--kmerCenter', type=int, default=2, help='offset of the position inside its k-mer in read direction, 0 .. k - 1')
     km.add_argument('--MinCoverage', type=int, default=5)
@@ -115,11 +115,73 @@ def build_parser():
     kp = sub.add_parser('kmerprofile', help="the 'model' profile a k-mer model predicts for the positions of a read group, for detect1")
     kp.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
     kp.add_argument('--kmerModel', required=True, help="a k-mer model written by 'kmermodel'")
-    kp.add_argument('--wrkBase1', required=True, help='the sample read group: a per-position .npz container')
+    kp.add_argument('--wrkBase1', required=True, help='the sample read group: a .npz container (per position or read-level)')
     kp.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
     kp.add_argument('--outFolder', default='mRes')
     kp.add_argument('--FileID', default='mod', help='the profile is written to <outFolder>/<FileID>_profile.npz')
+    kp.add_argument('--device', type=int, default=0, help='the device that groups a read-level --wrkBase1 by position')
+    rs = sub.add_parser('rescale', help='put the reads of a read-level container on the scale of a k-mer model: a per-read shift and '
+                        'scale fitted and applied on the device')
+    rs.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rs.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rs.add_argument('--kmerModel', required=True, help="a k-mer model written by 'kmermodel'")
+    rs.add_argument('--outReads', required=True, help='the rescaled read-level .npz container to write')
+    rs.add_argument('--unweighted', action='store_true', help='fit with equal weights instead of 1 / sd^2 of the k-mer')
+    rs.add_argument('--clipSigma', type=float, default=3.0, help='a clipping round keeps the events within clipSigma * scale * sd of the fit')
+    rs.add_argument('--clipRounds', type=int, default=2, help='clipping rounds after the plain fit, 0 .. 8')
+    rs.add_argument('--minEvents', type=int, default=50, help='a read with fewer fitted events in any round fails')
+    rs.add_argument('--scaleLo', type=float, default=0.5, help='a read whose scale lies below fails')
+    rs.add_argument('--scaleHi', type=float, default=2.0, help='a read whose scale lies above fails')
+    rs.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rs.add_argument('--dropFailed', action='store_true', help='leave the reads whose fit failed out of --outReads (default: unchanged)')
+    rs.add_argument('--outFolder', default='mRes')
+    rs.add_argument('--FileID', default='mod', help='the per-read table is written to <outFolder>/<FileID>_read_scale.txt')
+    rs.add_argument('--device', type=int, default=0)
     return p
+
+
+def validate_rescale(a):
+    """the checks of rescale"""
+    errs = []
+    if not 0 <= a.clipRounds <= 8:
+        errs.append('Error: --clipRounds should be in 0 .. 8')
+    if a.clipRounds > 0 and not 0.0 < a.clipSigma < float('inf'):
+        errs.append('Error: --clipSigma should be finite and positive')
+    if a.minEvents < 2:
+        errs.append('Error: --minEvents should be not less than 2')
+    if not (0.0 < a.scaleLo < float('inf') and a.scaleLo <= a.scaleHi):
+        errs.append('Error: --scaleLo should be positive, finite and not above --scaleHi')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    for f in (a.wrkBase1, a.kmerModel):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_rescale(a, log=print):
+    from . import kmermodel, rescale
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    reads = container.load_reads(a.wrkBase1)
+    out, table = rescale.rescale_reads(reads, kmermodel.load_kmer_model(a.kmerModel), weighted=not a.unweighted, clip_sigma=a.clipSigma,
+                                       clip_rounds=a.clipRounds, min_events=a.minEvents, scale_range=(a.scaleLo, a.scaleHi),
+                                       min_positions=a.minPositions, drop_failed=a.dropFailed, device=a.device,
+                                       log=(lambda *x: None) if quiet else log)
+    container.save_reads(a.outReads, out['chrom'], out['strand'], out['start'], out['off'], out['norm_mean'], out['base'])
+    os.makedirs(a.outFolder, exist_ok=True)
+    rescale.write_read_scale(os.path.join(a.outFolder, a.FileID + '_read_scale.txt'), reads, table)
+    if not quiet:
+        log('Rescaled reads are saved in %s' % a.outReads)
+    return out, table
+
+
+def load_group_input(path, device=0):
+    """a per-position container; a read-level one is grouped by position on the device first (engine.reads_to_group)"""
+    if container.is_read_level(path):
+        return engine.reads_to_group(container.load_reads(path), device)
+    return container.load_group(path)
 
 
 def validate_kmer(a):
@@ -150,7 +212,7 @@ def validate_kmer(a):
 def run_kmermodel(a, log=print):
     from . import kmermodel
     quiet = a.outLevel > detect.OUTPUT_ERROR
-    model = kmermodel.build_kmer_model(container.load_group(a.wrkBase1), a.kmer, a.kmerCenter, a.MinCoverage, a.clipSigma, a.clipRounds,
+    model = kmermodel.build_kmer_model(load_group_input(a.wrkBase1, a.device), a.kmer, a.kmerCenter, a.MinCoverage, a.clipSigma, a.clipRounds,
                                        a.device, (lambda *x: None) if quiet else log)
     os.makedirs(a.outFolder, exist_ok=True)
     path = os.path.join(a.outFolder, a.FileID + '_kmer_model.npz')
@@ -163,7 +225,7 @@ def run_kmermodel(a, log=print):
 
 def run_kmerprofile(a, log=print):
     from . import kmermodel, onesample
-    prof = kmermodel.model_profile(kmermodel.load_kmer_model(a.kmerModel), container.load_group(a.wrkBase1), a.minPositions)
+    prof = kmermodel.model_profile(kmermodel.load_kmer_model(a.kmerModel), load_group_input(a.wrkBase1, a.device), a.minPositions)
     os.makedirs(a.outFolder, exist_ok=True)
     path = os.path.join(a.outFolder, a.FileID + '_profile.npz')
     onesample.save_profile(path, prof)
@@ -198,7 +260,7 @@ def validate1(a):
 
 def run_profile(a, log=print):
     from . import onesample
-    prof = onesample.build_profile(container.load_group(a.wrkBase1), a.MinCoverage, a.device, log)
+    prof = onesample.build_profile(load_group_input(a.wrkBase1, a.device), a.MinCoverage, a.device, log)
     os.makedirs(a.outFolder, exist_ok=True)
     path = os.path.join(a.outFolder, a.FileID + '_profile.npz')
     onesample.save_profile(path, prof)
@@ -332,7 +394,7 @@ def load_input(path, a, log=print):
             mod, _, fn = a.fast5Reader.partition(':')
             reader = getattr(importlib.import_module(mod), fn)
         return fast5_ingest.ingest_folder(path, opts, reader=reader, log=log)
-    g = container.load_group(path)
+    g = load_group_input(path, getattr(a, 'device', 0))
     roi = getattr(a, 'roi', {})
     if roi:
         # a container holds aggregated positions: only the position-level part of the region filter applies
@@ -503,6 +565,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'rescale':
+        errs = validate_rescale(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_rescale(a)
+        return 0
     if a.cmd in ('kmermodel', 'kmerprofile'):
         errs = validate_kmer(a)
         if errs:

@@ -360,6 +360,94 @@ def kmer_model_host(sig, off, code, ncodes, keep_lo=None, keep_hi=None, *, strid
     return res
 
 
+def _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_range, k=None, center=None):
+    """nmod_rescale_opts from the Python arguments; ValueError for what the C entry refuses"""
+    import math
+    if isinstance(mode, str):
+        if mode not in L.RESCALE_MODE_BY_NAME:
+            raise ValueError("mode must be one of 'fit_apply', 'fit_only', 'apply_only'")
+        mode = L.RESCALE_MODE_BY_NAME[mode]
+    if mode not in (L.RESCALE_FIT_APPLY, L.RESCALE_FIT_ONLY, L.RESCALE_APPLY_ONLY):
+        raise ValueError('unknown rescale mode %r' % (mode,))
+    clip_sigma, clip_rounds, min_events = float(clip_sigma), int(clip_rounds), int(min_events)
+    lo, hi = (float(v) for v in scale_range)
+    if not 0 <= clip_rounds <= 8:
+        raise ValueError('clip_rounds must be in 0 .. 8')
+    if clip_rounds > 0 and not (math.isfinite(clip_sigma) and clip_sigma > 0.0):
+        raise ValueError('clip_sigma must be finite and positive')
+    if min_events < 2:
+        raise ValueError('min_events must be at least 2')
+    if not (math.isfinite(lo) and lo > 0.0 and lo <= hi):
+        raise ValueError('scale_range must be (lo, hi) with 0 < lo <= hi, lo finite')
+    if mode != L.RESCALE_APPLY_ONLY:
+        if k is None or not 1 <= int(k) <= 8:
+            raise ValueError('k must be in 1 .. 8')
+        if not 0 <= int(center) < int(k):
+            raise ValueError('center must be in 0 .. k - 1')
+    return L.make_rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, lo, hi)
+
+
+def rescale_reads_host(val, off, base, model=None, *, mode='fit_apply', weighted=True, clip_sigma=3.0, clip_rounds=2, min_events=50,
+                       scale_range=(0.5, 2.0), shift=None, scale=None, device=0):
+    """Per-read shift and scale against a k-mer model and the rescaled events (nmod_rescale_reads, include/nanomod_hip.h) on
+    host-resident reads: val float32, int16 (milli-units) or float64 and base (S1 / uint8), one entry per event, reads by `off`
+    (int64[nreads + 1]); model: a mapping with k, center, mean, sd (a kmermodel model) — not needed for mode 'apply_only', which
+    takes shift / scale (float64[nreads]) instead.  Returns a dict of numpy arrays: shift, scale (float64), n_used (int32), status
+    (uint8, L.RESCALE_* bits) and, unless mode is 'fit_only', val: the rescaled events in val's dtype."""
+    lib = L.load()
+    val = np.ascontiguousarray(val)
+    if val.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('val must be float32, int16 (milli-units) or float64')
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError('off must be int64[nreads + 1]')
+    nreads = off.shape[0] - 1
+    if nreads and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
+        raise ValueError('off must start at or above 0 and never decrease')
+    nev = int(off[-1]) if nreads else 0
+    if val.ndim != 1 or val.shape[0] < nev:
+        raise ValueError('val is shorter than its offsets say')
+    k = center = None
+    mean = sd = None
+    if model is not None:
+        k, center = int(model['k']), int(model['center'])
+    opts = _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_range, k, center)
+    fit, apply = opts.mode != L.RESCALE_APPLY_ONLY, opts.mode != L.RESCALE_FIT_ONLY
+    m = L.NmodRescaleModel()
+    if fit:
+        mean = np.ascontiguousarray(model['mean'], dtype=np.float64)
+        sd = np.ascontiguousarray(model['sd'], dtype=np.float64)
+        if mean.shape != (4 ** k,) or sd.shape != (4 ** k,):
+            raise ValueError('model mean / sd must be float64[4^k]')
+        base = np.asarray(base)
+        base = np.ascontiguousarray(base if base.dtype == np.uint8 else base.astype('S1').view(np.uint8))
+        if base.ndim != 1 or base.shape[0] < nev:
+            raise ValueError('base is shorter than its offsets say')
+        m.k, m.center, m.mean, m.sd = k, center, mean.ctypes.data, sd.ctypes.data
+        shift_a, scale_a = np.empty(nreads, np.float64), np.empty(nreads, np.float64)
+    else:
+        if shift is None or scale is None:
+            raise ValueError("mode 'apply_only' needs shift and scale")
+        shift_a = np.array(shift, dtype=np.float64, order='C')
+        scale_a = np.array(scale, dtype=np.float64, order='C')
+        if shift_a.shape != (nreads,) or scale_a.shape != (nreads,):
+            raise ValueError('shift / scale must be float64[nreads]')
+        base = None
+    res = dict(shift=shift_a, scale=scale_a, n_used=np.zeros(nreads, np.int32), status=np.zeros(nreads, np.uint8))
+    if apply:
+        res['val'] = np.empty_like(val)
+        res['val'][nev:] = val[nev:]
+    if nreads and off[0] > 0 and apply:
+        res['val'][:off[0]] = val[:off[0]]
+    _join_warm_up(device)
+    out = L.make_rescale_out(shift=_np_ptr(shift_a), scale=_np_ptr(scale_a), n_used=_np_ptr(res['n_used']), status=_np_ptr(res['status']),
+                             val_out=_np_ptr(res['val']) if apply else None)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(val.dtype))
+    rc = lib.nmod_rescale_reads(C.byref(prm), nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
+    L.check(rc, 'nmod_rescale_reads')
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -658,6 +746,62 @@ class DeviceDetector:
         L.check(rc, 'nmod_kmer_model')
         return res
 
+    def rescale_reads(self, val, off, base, mean=None, sd=None, k=None, center=None, *, mode='fit_apply', weighted=True, clip_sigma=3.0,
+                      clip_rounds=2, min_events=50, scale_range=(0.5, 2.0), shift=None, scale=None, inplace=False, out=None):
+        """Per-read shift and scale against a k-mer model and the rescaled events (nmod_rescale_reads, NMOD_MEM_DEVICE), enqueued on
+        the current stream without synchronising or reading anything back.  val: float32, int16 or float64 CUDA vector of events,
+        base: uint8 CUDA vector (one byte per event), off: int64 CUDA vector of nreads + 1 event offsets; mean / sd: float64 CUDA
+        vectors of 4^k model entries.  mode 'apply_only' takes shift / scale (float64 CUDA vectors) instead of the model.  inplace:
+        the rescaled events overwrite val.  Returns a dict of CUDA tensors: shift, scale, n_used (int32), status (uint8) and, unless
+        mode is 'fit_only', val — which pivot_reads' device form takes on the same stream.  out: such a dict from an earlier call of
+        the same shape and mode, written again instead of allocating (a timing loop)."""
+        torch = self.torch
+        dtype = self._dtype_of(val)
+        opts = _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_range, k, center)
+        fit, apply = opts.mode != L.RESCALE_APPLY_ONLY, opts.mode != L.RESCALE_FIT_ONLY
+        dev = 'cuda:%d' % self.device
+        if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
+            raise ValueError('rescale_reads: off must be a contiguous int64 CUDA vector of nreads + 1 elements')
+        nreads = off.numel() - 1
+        checks = [(val, None, 'val', None)]
+        if fit:
+            checks += [(base, torch.uint8, 'base', None), (mean, torch.float64, 'mean', 4 ** int(k)), (sd, torch.float64, 'sd', 4 ** int(k))]
+        else:
+            checks += [(shift, torch.float64, 'shift', nreads), (scale, torch.float64, 'scale', nreads)]
+        for t, dt, name, m in checks:
+            if t is None or not (t.is_cuda and t.is_contiguous() and (dt is None or t.dtype == dt) and (m is None or t.numel() == m)):
+                raise ValueError('rescale_reads: %s must be a contiguous CUDA vector%s' % (name, '' if m is None else ' of %d elements' % m))
+        if fit and base.numel() != val.numel():
+            raise ValueError('rescale_reads: base needs one byte per event')
+        res = out
+        if res is not None:
+            want = dict(shift=(torch.float64, nreads), scale=(torch.float64, nreads), n_used=(torch.int32, nreads), status=(torch.uint8, nreads))
+            if apply:
+                want['val'] = (val.dtype, val.numel())
+            for name, (dt, m) in want.items():
+                t = res.get(name)
+                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == m):
+                    raise ValueError('rescale_reads: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
+        else:
+            res = dict(n_used=torch.zeros(nreads, dtype=torch.int32, device=dev), status=torch.zeros(nreads, dtype=torch.uint8, device=dev))
+            if fit:
+                res['shift'] = torch.empty(nreads, dtype=torch.float64, device=dev)
+                res['scale'] = torch.empty(nreads, dtype=torch.float64, device=dev)
+            else:
+                res['shift'], res['scale'] = shift, scale
+            if apply:
+                res['val'] = val if inplace else torch.empty_like(val)
+        m = L.NmodRescaleModel()
+        if fit:
+            m.k, m.center, m.mean, m.sd = int(k), int(center), mean.data_ptr(), sd.data_ptr()
+        o = L.make_rescale_out(shift=res['shift'].data_ptr(), scale=res['scale'].data_ptr(), n_used=res['n_used'].data_ptr(),
+                               status=res['status'].data_ptr(), val_out=res['val'].data_ptr() if apply else None)
+        prm = self._params(dtype, 0, 0, 0, 0)
+        rc = self.lib.nmod_rescale_reads(C.byref(prm), nreads, off.data_ptr(), val.data_ptr(), base.data_ptr() if fit else None,
+                                         C.byref(m), C.byref(opts), C.byref(o))
+        L.check(rc, 'nmod_rescale_reads')
+        return res
+
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
         rc = self.lib.nmod_synth_fill(C.byref(prm), seed, pos_begin, npos, group, n_per_pos,
@@ -763,12 +907,13 @@ class _CallTimer:
         return False
 
 
-def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=None):
+def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=None, val=None):
     """nmod_pivot_reads (myDetect.py:104-124) on a read-level set (container.READ_FIELDS): returns device tensors key
     (cs << 40 | pos, ascending), off, sig (the input dtype), base (uint8) and the host list `names` the chrom ids index.
     Inside a position the samples come in read order; the base is the last read's.  pos_lo / pos_hi: the inclusive
     event-level window (myDetect.py:112-114).  timer: a dict that collects the device time (s) of the copy ('h2d') and of
-    nmod_pivot_reads ('pivot'), measured with HIP events."""
+    nmod_pivot_reads ('pivot'), measured with HIP events.  val: the events as a device tensor that takes the place of
+    reads['norm_mean'] (the output of DeviceDetector.rescale_reads, say): it is used where it lies, on the current stream."""
     import torch
     lib = L.load()
     _join_warm_up(device)
@@ -777,8 +922,14 @@ def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=Non
     strand = np.asarray(reads['strand']).astype(str)
     start = np.ascontiguousarray(reads['start'], dtype=np.int64)
     off = np.ascontiguousarray(reads['off'], dtype=np.int64)
-    val = np.ascontiguousarray(reads['norm_mean'])
-    dtype = _dtype_code(val.dtype)
+    if val is None:
+        val = np.ascontiguousarray(reads['norm_mean'])
+        dtype = _dtype_code(val.dtype)
+    else:
+        if not (val.is_cuda and val.device.index == device and val.is_contiguous() and val.dim() == 1
+                and val.numel() >= (int(off[-1]) if len(off) else 0)):
+            raise ValueError('val must be a contiguous CUDA vector on device %d of one value per event' % device)
+        dtype = _torch_dtype_code(val)
     nreads = len(start)
     if len(off) != nreads + 1 or len(chrom) != nreads or len(strand) != nreads:
         raise ValueError('reads: chrom / strand / start need one entry per read and off nreads + 1')
@@ -810,7 +961,8 @@ def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=Non
     dev = torch.device('cuda', device)
     t = lambda x: torch.from_numpy(x).to(dev)
     with _CallTimer(timer, 'h2d', dev):
-        d_cs, d_start, d_off, d_val, d_base = t(cs), t(start), t(off), t(val), t(base)
+        d_cs, d_start, d_off, d_base = t(cs), t(start), t(off), t(base)
+        d_val = val if torch.is_tensor(val) else t(val)
     key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
     roff = torch.empty(cap + 1, dtype=torch.int64, device=dev)
     sig = torch.empty(max(nev, 1), dtype=d_val.dtype, device=dev)
@@ -824,6 +976,20 @@ def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=Non
     L.check(rc, 'nmod_pivot_reads')
     p, ns = npos.value, nsamp.value
     return dict(key=key[:p], off=roff[:p + 1], sig=sig[:ns], base=rbase[:p], names=names)
+
+
+def reads_to_group(reads, device=0, pos_lo=None, pos_hi=None):
+    """A read-level set (container.READ_FIELDS) as a per-position container (container.FIELDS): pivot_reads on the device and a copy
+    back.  Rows come in the reference's order (sorted chromosome, '+' before '-', ascending position), the samples of a position in
+    read order, the base of a position from its last read — what fast5_ingest.GroupBuilder builds from the same reads; sig keeps the
+    dtype of the events."""
+    g = pivot_reads(reads, device, pos_lo, pos_hi)
+    key = g['key'].cpu().numpy()
+    names = np.array(g['names'], dtype=str)
+    chrom = names[key >> 41] if len(key) else np.zeros(0, dtype=str)
+    strand = np.where((key >> 40) & 1, '-', '+').astype('U1')
+    base = g['base'].cpu().numpy().view('S1').astype('U1')
+    return dict(chrom=chrom, strand=strand, pos=key & ((1 << 40) - 1), base=base, off=g['off'].cpu().numpy(), sig=g['sig'].cpu().numpy())
 
 
 def group_to_device(g, names, device=0):
