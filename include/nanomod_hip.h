@@ -589,6 +589,64 @@ typedef struct nmod_rescale_out { int32_t struct_size; int32_t reserved;
 int nmod_rescale_reads(const nmod_params* prm, int64_t nreads, const int64_t* off, const void* val, const uint8_t* base,
                        const nmod_rescale_model* model, const nmod_rescale_opts* opts, const nmod_rescale_out* out);
 
+/* Per-read modification calls against a k-mer model (K12; the reference project has no such step): every event of every read is scored
+ * against the model level of its k-mer, the scores of neighbouring events OF THE SAME READ are combined by Fisher's method, and an event
+ * whose combined p-value is at most alpha is called.  The single-molecule counterpart of nmod_one_sample: which reads are modified where.
+ *   Inputs: exactly those of nmod_rescale_reads: off[nreads + 1] (int64 CSR event offsets; required, there is no stride form), val
+ *     (prm->dtype) and base (one byte per event, the read's own base), events in read direction for both strands; the model is K11's
+ *     struct as it is: k in 1 .. 8, center in 0 .. k - 1, mean[4^k] and sd[4^k] (doubles, in the call's memspace).
+ *   Code of an event: event j of a read of n events has the code c_j of the bytes base[j - center .. j + k - 1 - center]: A = 0, C = 1,
+ *     G = 2, T = 3, upper case only, the first base most significant (kmermodel.kmer_codes' convention); c_j = -1 when the window leaves
+ *     the read or holds any other byte.
+ *   Eligible: c_j >= 0, mean[c_j] and sd[c_j] finite with sd[c_j] > 0, and x_j finite.  x_j is the value as a double (int16 k / 1000.0, a
+ *     division; float32 up-cast; float64 as is), mu_j and s_j the model entries.
+ *   An eligible event j, compiled with contraction off:
+ *     z_j = (x_j - mu_j) / s_j,  u_j = |z_j| * 0.70710678118654752,
+ *     p_j = max(erfc(u_j), DBL_MIN): the two-sided normal tail, clamped like every p-value of the library,
+ *     l_j = log(erfcx(u_j)) - u_j * u_j: the logarithm of the UNCLAMPED tail.  It does not underflow, so a window keeps what its events
+ *       say beyond |z| = 37.52, where p_j sits at DBL_MIN.
+ *   Window of j: the ELIGIBLE events i of the same read with |i - j| <= nb and 0 <= i < n.  Ineligible events and events beyond the ends
+ *     of the read take no part (a read is a wall: no window reaches into a neighbouring read).  W_j = the number of events in the window
+ *     (at least 1: j itself), X_j = -2 * sum l_i with the terms added in ascending i, and
+ *     P_j = max(chi2.sf(X_j, 2 W_j), DBL_MIN) — Fisher's method over the events that exist, chi2.sf with an even number of degrees of
+ *     freedom as the closed sum exp(-X/2) sum_{m < W} (X/2)^m / m!.  nb == 0: P_j is p_j, the same bits.
+ *   An ineligible event gets z = p = p_win = NaN, whatever its neighbours are.
+ *   Per read: n_sites = the eligible events, n_called = #{j : P_j <= alpha}, status 0 or NMOD_CALLS_TOO_LARGE (n > NMOD_MAX_DEEP: NaN
+ *     events and zero counts).  A read without an eligible event is not an error: zero counts, status 0.
+ *   Outputs (a NULL member is skipped; out->struct_size = sizeof(nmod_calls_out)): per event, in val's layout, z, p and p_win = P as
+ *     doubles (every p-value of the library is fp64); per read n_sites, n_called (int32) and status (uint8).
+ * Reads struct_size, device, stream, memspace, dtype of prm and nothing else; the window width is opts->nb, not prm->nb.
+ * NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and no synchronisation; scratch (8 bytes per read + 16 bytes per
+ * model entry) comes stream-ordered from the library's pool.  NMOD_MEM_HOST: copy in, run, copy back, synchronise (one staged copy).
+ * nreads == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG before any device work: nb outside 0 .. NMOD_MAX_NB, alpha not in (0, 1], k or center out
+ * of range, nreads < 0 or beyond 2^32 - 2, NULL off / val / base / model arrays with nreads > 0, model / opts / out NULL or (opts, out) of
+ * another struct_size, an unknown dtype, host offsets that decrease.
+ * A read's outputs are the same bits whatever else is in the batch, in any order of the reads, from host or device memory, and whichever
+ * output members were requested.  A read is computed by one wave (up to NMOD_CALLS_WAVE_MAX events) or one workgroup: a single very long
+ * read is not split.  No float atomics: the counts are integer reductions. */
+#define NMOD_CALLS_TOO_LARGE 16            /* status of a read beyond NMOD_MAX_DEEP events */
+#define NMOD_CALLS_WAVE_MAX 2048           /* events of a read: up to here a wave computes it, beyond a workgroup */
+typedef struct nmod_calls_opts { int32_t struct_size, nb; double alpha; } nmod_calls_opts;
+typedef struct nmod_calls_out { int32_t struct_size; int32_t reserved;
+  double *z, *p, *p_win;            /* one per event, in val's layout */
+  int32_t *n_sites, *n_called; uint8_t* status; /* nreads each */ } nmod_calls_out;
+int nmod_read_calls(const nmod_params* prm, int64_t nreads, const int64_t* off, const void* val, const uint8_t* base,
+                    const nmod_rescale_model* model, const nmod_calls_opts* opts, const nmod_calls_out* out);
+
+/* Per-position call counts over pivoted scores (K12): the rows nmod_pivot_reads makes when the p_win track of nmod_read_calls is handed
+ * to it as `val` with dtype F64 — one row of doubles per position, one score per read that covers it.
+ *   Per position: n_valid = #{s : 0 <= s <= 1} (the validity rule of nmod_fdr_adjust; NaN means no call), n_called = #{valid s <= alpha},
+ *     frac = (double)n_called / (double)n_valid, NaN when n_valid == 0.
+ *   Outputs (a NULL member is skipped; out->struct_size = sizeof(nmod_site_out)): int32 n_valid, n_called and double frac, npos each.
+ * Rows: CSR when `off` is given, else the fixed stride prm->stride0.  Reads struct_size, device, stream, memspace, stride0 of prm and
+ * nothing else (the scores are doubles whatever prm->dtype says).  Both memspaces as above; npos == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG
+ * before any device work: alpha not in (0, 1], neither offsets nor a stride, npos < 0 or beyond 2^31 - 2, a NULL score with npos > 0, out
+ * NULL or of another struct_size, host offsets that decrease.  Integer counts: order-free, the same bits in CSR and stride form.  A wave
+ * per row; not tuned. */
+typedef struct nmod_site_out { int32_t struct_size; int32_t reserved; int32_t *n_valid, *n_called; double* frac; } nmod_site_out;
+int nmod_site_calls(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */, double alpha,
+                    const nmod_site_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

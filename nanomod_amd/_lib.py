@@ -153,6 +153,48 @@ def make_rescale_out(**members):
     return o
 
 
+CALLS_TOO_LARGE = 16       # nmod_read_calls: status of a read beyond MAX_DEEP events
+CALLS_WAVE_MAX = 2048      # nmod_read_calls: events of a read up to which one wave computes it (a workgroup beyond)
+CALLS_EVENT_FIELDS = ('z', 'p', 'p_win')
+SITE_FIELDS = ('n_valid', 'n_called', 'frac')
+
+
+class NmodCallsOpts(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('nb', C.c_int32), ('alpha', C.c_double)]
+
+
+class NmodCallsOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + \
+               [(n, C.c_void_p) for n in CALLS_EVENT_FIELDS + ('n_sites', 'n_called', 'status')]
+
+
+class NmodSiteOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in SITE_FIELDS]
+
+
+def make_calls_opts(nb=2, alpha=0.01):
+    o = NmodCallsOpts()
+    o.struct_size = C.sizeof(NmodCallsOpts)
+    o.nb, o.alpha = int(nb), float(alpha)
+    return o
+
+
+def make_calls_out(**members):
+    o = NmodCallsOut()
+    o.struct_size = C.sizeof(NmodCallsOut)
+    for k, v in members.items():
+        setattr(o, k, v)
+    return o
+
+
+def make_site_out(**members):
+    o = NmodSiteOut()
+    o.struct_size = C.sizeof(NmodSiteOut)
+    for k, v in members.items():
+        setattr(o, k, v)
+    return o
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -210,6 +252,9 @@ _SIGNATURES = {
                                   C.POINTER(NmodKmerOut)]),
     'nmod_rescale_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
                                      C.POINTER(NmodRescaleOpts), C.POINTER(NmodRescaleOut)]),
+    'nmod_read_calls': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
+                                  C.POINTER(NmodCallsOpts), C.POINTER(NmodCallsOut)]),
+    'nmod_site_calls': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -137,7 +137,57 @@ def build_parser():
     rs.add_argument('--outFolder', default='mRes')
     rs.add_argument('--FileID', default='mod', help='the per-read table is written to <outFolder>/<FileID>_read_scale.txt')
     rs.add_argument('--device', type=int, default=0)
+    rc = sub.add_parser('readcalls', help='call the events of every read against a k-mer model on the device: which reads are modified '
+                        'where, and the share of called reads per position')
+    rc.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rc.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rc.add_argument('--kmerModel', required=True, help="a k-mer model written by 'kmermodel'")
+    rc.add_argument('--neighborPvalues', type=int, default=2, help='events of the same read on each side whose p-values are combined '
+                    "(Fisher's method), 0 .. 64")
+    rc.add_argument('--callAlpha', type=float, default=0.01, help='an event is called when its combined p-value is at most this, (0, 1]')
+    rc.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rc.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the model's scale first (the fit of "
+                    "'rescale' with its defaults, on the device)")
+    rc.add_argument('--outEvents', default='', help='optional: a .npz file for the per-event tracks z, p, p_win (with off)')
+    rc.add_argument('--outFolder', default='mRes')
+    rc.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_calls.txt and <FileID>_site_calls.txt')
+    rc.add_argument('--device', type=int, default=0)
     return p
+
+
+def validate_readcalls(a):
+    """the checks of readcalls"""
+    errs = []
+    if not 0 <= a.neighborPvalues <= L.MAX_NB:
+        errs.append('Error: --neighborPvalues should be in 0 .. %d' % L.MAX_NB)
+    if not 0.0 < a.callAlpha <= 1.0:
+        errs.append('Error: --callAlpha should be larger than 0 and not larger than 1')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    for f in (a.wrkBase1, a.kmerModel):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_readcalls(a, log=print):
+    from . import kmermodel, readcalls
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    reads = container.load_reads(a.wrkBase1)
+    res = readcalls.call_reads(reads, kmermodel.load_kmer_model(a.kmerModel), nb=a.neighborPvalues, alpha=a.callAlpha,
+                               min_positions=a.minPositions, rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device,
+                               log=(lambda *x: None) if quiet else log)
+    table, sites = res[0], res[1]
+    os.makedirs(a.outFolder, exist_ok=True)
+    readcalls.write_read_calls(os.path.join(a.outFolder, a.FileID + '_read_calls.txt'), table)
+    readcalls.write_site_calls(os.path.join(a.outFolder, a.FileID + '_site_calls.txt'), sites)
+    if a.outEvents:
+        np.savez(a.outEvents, off=np.asarray(reads['off'], dtype=np.int64), **res[2])
+    if not quiet:
+        log('Read calls are saved in %s' % os.path.join(a.outFolder, a.FileID + '_read_calls.txt'))
+    return res
 
 
 def validate_rescale(a):
@@ -565,6 +615,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readcalls':
+        errs = validate_readcalls(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readcalls(a)
+        return 0
     if a.cmd == 'rescale':
         errs = validate_rescale(a)
         if errs:

@@ -448,6 +448,105 @@ def rescale_reads_host(val, off, base, model=None, *, mode='fit_apply', weighted
     return res
 
 
+def _calls_opts(nb, alpha, k, center, want):
+    """nmod_calls_opts from the Python arguments; ValueError for what the C entry refuses"""
+    nb, alpha = int(nb), float(alpha)
+    if not 0 <= nb <= L.MAX_NB:
+        raise ValueError('nb must be in 0 .. %d' % L.MAX_NB)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError('alpha must be in (0, 1]')
+    if k is None or not 1 <= int(k) <= 8:
+        raise ValueError('k must be in 1 .. 8')
+    if center is None or not 0 <= int(center) < int(k):
+        raise ValueError('center must be in 0 .. k - 1')
+    want = tuple(want)
+    if any(w not in L.CALLS_EVENT_FIELDS for w in want):
+        raise ValueError("want must name tracks of 'z', 'p', 'p_win'")
+    return L.make_calls_opts(nb, alpha), want
+
+
+def read_calls_host(val, off, base, model, *, nb=2, alpha=0.01, want=('z', 'p', 'p_win'), device=0):
+    """Per-read modification calls against a k-mer model (nmod_read_calls, include/nanomod_hip.h) on host-resident reads: val
+    float32, int16 (milli-units) or float64 and base (S1 / uint8), one entry per event, reads by `off` (int64[nreads + 1]); model: a
+    mapping with k, center, mean, sd (a kmermodel model).  Returns a dict of numpy arrays: the per-event tracks named in `want`
+    (float64, in val's layout: z, the two-sided normal p, and p_win, Fisher's combination over the events of the same read within nb)
+    and per read n_sites, n_called (int32) and status (uint8, L.CALLS_TOO_LARGE)."""
+    lib = L.load()
+    val = np.ascontiguousarray(val)
+    if val.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('val must be float32, int16 (milli-units) or float64')
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError('off must be int64[nreads + 1]')
+    nreads = off.shape[0] - 1
+    if nreads and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
+        raise ValueError('off must start at or above 0 and never decrease')
+    nev = int(off[-1]) if nreads else 0
+    if val.ndim != 1 or val.shape[0] < nev:
+        raise ValueError('val is shorter than its offsets say')
+    if model is None:
+        raise ValueError('read_calls needs a k-mer model')
+    k, center = int(model['k']), int(model['center'])
+    opts, want = _calls_opts(nb, alpha, k, center, want)
+    mean = np.ascontiguousarray(model['mean'], dtype=np.float64)
+    sd = np.ascontiguousarray(model['sd'], dtype=np.float64)
+    if mean.shape != (4 ** k,) or sd.shape != (4 ** k,):
+        raise ValueError('model mean / sd must be float64[4^k]')
+    base = np.asarray(base)
+    base = np.ascontiguousarray(base if base.dtype == np.uint8 else base.astype('S1').view(np.uint8))
+    if base.ndim != 1 or base.shape[0] < nev:
+        raise ValueError('base is shorter than its offsets say')
+    m = L.NmodRescaleModel()
+    m.k, m.center, m.mean, m.sd = k, center, mean.ctypes.data, sd.ctypes.data
+    res = {w: np.full(val.shape[0], np.nan) for w in want}
+    res.update(n_sites=np.zeros(nreads, np.int32), n_called=np.zeros(nreads, np.int32), status=np.zeros(nreads, np.uint8))
+    _join_warm_up(device)
+    out = L.make_calls_out(**{name: _np_ptr(a) for name, a in res.items()})
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(val.dtype))
+    rc = lib.nmod_read_calls(C.byref(prm), nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
+    L.check(rc, 'nmod_read_calls')
+    if nreads and off[0] > 0:
+        for w in want:                                          # events before the first read belong to no read
+            res[w][:off[0]] = np.nan
+    return res
+
+
+def site_calls_host(score, off, *, stride=0, alpha=0.01, device=0):
+    """Per-position call counts over pivoted scores (nmod_site_calls): score float64, one row per position by `off` (int64[npos + 1])
+    or, with off None, a fixed `stride`.  Returns a dict of numpy arrays: n_valid (scores in [0, 1]), n_called (valid scores <= alpha),
+    both int32, and frac = n_called / n_valid (float64, NaN without a valid score)."""
+    lib = L.load()
+    score = np.ascontiguousarray(score, dtype=np.float64)
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError('alpha must be in (0, 1]')
+    if score.ndim != 1:
+        raise ValueError('score must be a float64 vector')
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if off.ndim != 1 or off.shape[0] < 1:
+            raise ValueError('off must be int64[npos + 1]')
+        npos = off.shape[0] - 1
+        if npos and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
+            raise ValueError('off must start at or above 0 and never decrease')
+        if score.shape[0] < (int(off[-1]) if npos else 0):
+            raise ValueError('score is shorter than its offsets say')
+    else:
+        stride = int(stride)
+        if stride <= 0:
+            raise ValueError('either off or a positive stride')
+        if score.shape[0] % stride:
+            raise ValueError('score must hold whole rows of the stride')
+        npos = score.shape[0] // stride
+    res = dict(n_valid=np.zeros(npos, np.int32), n_called=np.zeros(npos, np.int32), frac=np.full(npos, np.nan))
+    _join_warm_up(device)
+    out = L.make_site_out(**{name: _np_ptr(a) for name, a in res.items()})
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
+    rc = lib.nmod_site_calls(C.byref(prm), npos, _np_ptr(score), _np_ptr(off), alpha, C.byref(out))
+    L.check(rc, 'nmod_site_calls')
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -800,6 +899,82 @@ class DeviceDetector:
         rc = self.lib.nmod_rescale_reads(C.byref(prm), nreads, off.data_ptr(), val.data_ptr(), base.data_ptr() if fit else None,
                                          C.byref(m), C.byref(opts), C.byref(o))
         L.check(rc, 'nmod_rescale_reads')
+        return res
+
+    def read_calls(self, val, off, base, mean, sd, k, center, *, nb=2, alpha=0.01, want=('z', 'p', 'p_win'), out=None):
+        """Per-read modification calls against a k-mer model (nmod_read_calls, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising or reading anything back.  val: float32, int16 or float64 CUDA vector of events (the `val` of rescale_reads, say),
+        base: uint8 CUDA vector (one byte per event), off: int64 CUDA vector of nreads + 1 event offsets; mean / sd: float64 CUDA
+        vectors of 4^k model entries.  Returns a dict of CUDA tensors: the per-event tracks named in `want` (float64: z, p, p_win) and per
+        read n_sites, n_called (int32) and status (uint8).  p_win is what pivot_reads' device form takes as `val` for site_calls.
+        out: such a dict from an earlier call of the same shape, written again instead of allocating (a timing loop)."""
+        torch = self.torch
+        dtype = self._dtype_of(val)
+        opts, want = _calls_opts(nb, alpha, k, center, want)
+        dev = 'cuda:%d' % self.device
+        if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
+            raise ValueError('read_calls: off must be a contiguous int64 CUDA vector of nreads + 1 elements')
+        nreads = off.numel() - 1
+        for t, dt, name, m in ((val, None, 'val', None), (base, torch.uint8, 'base', None), (mean, torch.float64, 'mean', 4 ** int(k)),
+                               (sd, torch.float64, 'sd', 4 ** int(k))):
+            if t is None or not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and (dt is None or t.dtype == dt) and (m is None or t.numel() == m)):
+                raise ValueError('read_calls: %s must be a contiguous CUDA vector%s' % (name, '' if m is None else ' of %d elements' % m))
+        if base.numel() != val.numel():
+            raise ValueError('read_calls: base needs one byte per event')
+        shapes = {w: (torch.float64, val.numel()) for w in want}
+        shapes.update(n_sites=(torch.int32, nreads), n_called=(torch.int32, nreads), status=(torch.uint8, nreads))
+        res = out
+        if res is not None:
+            for name, (dt, m) in shapes.items():
+                t = res.get(name)
+                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == m):
+                    raise ValueError('read_calls: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
+        else:
+            res = {name: torch.empty(m, dtype=dt, device=dev) for name, (dt, m) in shapes.items()}
+        md = L.NmodRescaleModel()
+        md.k, md.center, md.mean, md.sd = int(k), int(center), mean.data_ptr(), sd.data_ptr()
+        o = L.make_calls_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(dtype, 0, 0, 0, 0)
+        rc = self.lib.nmod_read_calls(C.byref(prm), nreads, off.data_ptr(), val.data_ptr(), base.data_ptr(), C.byref(md), C.byref(opts), C.byref(o))
+        L.check(rc, 'nmod_read_calls')
+        return res
+
+    def site_calls(self, score, *, off=None, stride=0, npos=None, alpha=0.01, out=None):
+        """Per-position call counts over pivoted scores (nmod_site_calls, NMOD_MEM_DEVICE) on the current stream: score a float64 CUDA
+        vector, rows by `off` (int64 CUDA vector) or a fixed `stride`.  Returns a dict of CUDA tensors n_valid, n_called (int32) and
+        frac (float64)."""
+        torch = self.torch
+        alpha = float(alpha)
+        if not 0.0 < alpha <= 1.0:
+            raise ValueError('alpha must be in (0, 1]')
+        if not (score.is_cuda and score.dtype == torch.float64 and score.is_contiguous() and score.dim() == 1):
+            raise ValueError('site_calls: score must be a contiguous float64 CUDA vector')
+        if off is not None:
+            if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
+                raise ValueError('site_calls: off must be a contiguous int64 CUDA vector of npos + 1 elements')
+            npos = off.numel() - 1
+        else:
+            stride = int(stride)
+            if stride <= 0:
+                raise ValueError('site_calls: either off or a positive stride')
+            if npos is None:
+                npos = score.numel() // stride
+            if npos * stride > score.numel():
+                raise ValueError('site_calls: score is shorter than npos rows of the stride')
+        dev = 'cuda:%d' % self.device
+        shapes = dict(n_valid=torch.int32, n_called=torch.int32, frac=torch.float64)
+        res = out
+        if res is not None:
+            for name, dt in shapes.items():
+                t = res.get(name)
+                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == npos):
+                    raise ValueError('site_calls: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, npos))
+        else:
+            res = {name: torch.empty(npos, dtype=dt, device=dev) for name, dt in shapes.items()}
+        o = L.make_site_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
+        rc = self.lib.nmod_site_calls(C.byref(prm), npos, score.data_ptr(), off.data_ptr() if off is not None else None, alpha, C.byref(o))
+        L.check(rc, 'nmod_site_calls')
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
