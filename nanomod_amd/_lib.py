@@ -6,6 +6,7 @@ fails loudly with instructions to build it.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -86,6 +87,16 @@ class NmodMixOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in MIX_FIELDS] + [('iters', C.c_void_p), ('status', C.c_void_p), ('resp', C.c_void_p)]
 
 
+def make_out(cls, **members):
+    """an out struct of class `cls`: struct_size filled in where the struct has one, the named members set, the rest left NULL"""
+    o = cls()
+    if hasattr(cls, 'struct_size'):
+        o.struct_size = C.sizeof(cls)
+    for k, v in members.items():
+        setattr(o, k, v)
+    return o
+
+
 ONE_FIELDS = ('ks_d', 'ks_p', 't_t', 't_p', 'shift', 'mean', 'std', 'comb_st', 'comb_p')
 
 
@@ -93,12 +104,7 @@ class NmodOneOut(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(name, C.c_void_p) for name in ONE_FIELDS] + [('status', C.c_void_p)]
 
 
-def make_one_out(**members):
-    o = NmodOneOut()
-    o.struct_size = C.sizeof(NmodOneOut)
-    for k, v in members.items():
-        setattr(o, k, v)
-    return o
+make_one_out = functools.partial(make_out, NmodOneOut)
 
 
 KMER_COUNT_FIELDS = ('n_positions', 'n_samples', 'n_clipped')
@@ -109,12 +115,7 @@ class NmodKmerOut(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(name, C.c_void_p) for name in KMER_FIELDS] + [('pos_status', C.c_void_p)]
 
 
-def make_kmer_out(**members):
-    o = NmodKmerOut()
-    o.struct_size = C.sizeof(NmodKmerOut)
-    for k, v in members.items():
-        setattr(o, k, v)
-    return o
+make_kmer_out = functools.partial(make_out, NmodKmerOut)
 
 
 RESCALE_FIT_APPLY, RESCALE_FIT_ONLY, RESCALE_APPLY_ONLY = 0, 1, 2
@@ -145,12 +146,7 @@ def make_rescale_opts(mode=RESCALE_FIT_APPLY, weighted=True, clip_sigma=3.0, cli
     return o
 
 
-def make_rescale_out(**members):
-    o = NmodRescaleOut()
-    o.struct_size = C.sizeof(NmodRescaleOut)
-    for k, v in members.items():
-        setattr(o, k, v)
-    return o
+make_rescale_out = functools.partial(make_out, NmodRescaleOut)
 
 
 CALLS_TOO_LARGE = 16       # nmod_read_calls: status of a read beyond MAX_DEEP events
@@ -179,20 +175,8 @@ def make_calls_opts(nb=2, alpha=0.01):
     return o
 
 
-def make_calls_out(**members):
-    o = NmodCallsOut()
-    o.struct_size = C.sizeof(NmodCallsOut)
-    for k, v in members.items():
-        setattr(o, k, v)
-    return o
-
-
-def make_site_out(**members):
-    o = NmodSiteOut()
-    o.struct_size = C.sizeof(NmodSiteOut)
-    for k, v in members.items():
-        setattr(o, k, v)
-    return o
+make_calls_out = functools.partial(make_out, NmodCallsOut)
+make_site_out = functools.partial(make_out, NmodSiteOut)
 
 
 class NanomodLibraryError(RuntimeError):

@@ -169,6 +169,194 @@ def argsort_device(key):
     return order.to(torch.int64)
 
 
+# ------------------------------------------------------------------------------------------ the shared argument layer
+# What the secondary entry points (fdr, mix, one-sample, k-mer model, rescale, read calls, site calls) have in common, in their
+# *_host form over numpy arrays and their DeviceDetector form over CUDA tensors: every rule lives here once, the entry points
+# keep their own specifics.  The C side's counterpart is csrc/entry_common.hpp / entry_device.hpp.
+_SIGNAL_DTYPES = 'float32, int16 (milli-units) or float64'
+
+
+def _dtype_code(a, name='values'):
+    try:
+        return {np.dtype(np.float32): L.DTYPE_F32, np.dtype(np.int16): L.DTYPE_I16_MILLI, np.dtype(np.float64): L.DTYPE_F64}[np.dtype(a)]
+    except KeyError:
+        raise ValueError('%s must be %s' % (name, _SIGNAL_DTYPES))
+
+
+def _signal(a, name):
+    """a numpy signal as a contiguous array and its L.DTYPE_* code"""
+    a = np.ascontiguousarray(a)
+    return a, _dtype_code(a.dtype, name)
+
+
+def _rows(sig, off, stride, npos, name, off_name='off'):
+    """npos rows of `sig` by `off` (int64[npos + 1]) or, with off None, a fixed `stride`: the contiguous offsets (or None) and the
+    stride the params take (0 beside offsets)"""
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    _check_csr(off, npos, off_name)
+    if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
+        raise ValueError('%s is shorter than its offsets / stride say' % name)
+    return off, (stride if off is None else 0)
+
+
+def _read_layout(val, off, name, count='nreads'):
+    """event vectors by `off` (int64[nreads + 1]): the contiguous offsets, nreads, and the number of events up to the last read's end"""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError('off must be int64[%s + 1]' % count)
+    n = off.shape[0] - 1
+    if n and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
+        raise ValueError('off must start at or above 0 and never decrease')
+    nev = int(off[-1]) if n else 0
+    if val.ndim != 1 or val.shape[0] < nev:
+        raise ValueError('%s is shorter than its offsets say' % name)
+    return off, n, nev
+
+
+def _side(a, dtype, n, name, count='npos', optional=True):
+    """a host side vector as a contiguous `dtype` array of n elements; None stays None when it is optional"""
+    if a is None and optional:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != (n,):
+        raise ValueError('%s must be %s[%s]' % (name, np.dtype(dtype).name, count))
+    return a
+
+
+def _check_kmer(k, center, center_unguarded=False):
+    """k in 1 .. 8 and center in 0 .. k - 1.  center_unguarded: _rescale_opts' copy of the rule converts a missing center as it is
+    (TypeError); _calls_opts' copy refuses it like any other (ValueError)"""
+    if k is None or not 1 <= int(k) <= 8:
+        raise ValueError('k must be in 1 .. 8')
+    if (center is None and not center_unguarded) or not 0 <= int(center) < int(k):
+        raise ValueError('center must be in 0 .. k - 1')
+
+
+def _check_alpha(alpha):
+    alpha = float(alpha)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError('alpha must be in (0, 1]')
+    return alpha
+
+
+def _model_len(k):
+    return 4 ** int(k)
+
+
+def _model_struct(k, center, mean_ptr, sd_ptr):
+    m = L.NmodRescaleModel()
+    m.k, m.center, m.mean, m.sd = int(k), int(center), mean_ptr, sd_ptr
+    return m
+
+
+def _host_model(model):
+    """a k-mer model mapping (k, center, mean, sd) as a filled nmod_rescale_model, and the arrays it points to: keep them alive"""
+    k = int(model['k'])
+    mean = np.ascontiguousarray(model['mean'], dtype=np.float64)
+    sd = np.ascontiguousarray(model['sd'], dtype=np.float64)
+    if mean.shape != (_model_len(k),) or sd.shape != (_model_len(k),):
+        raise ValueError('model mean / sd must be float64[4^k]')
+    return _model_struct(k, model['center'], mean.ctypes.data, sd.ctypes.data), (mean, sd)
+
+
+def _host_base(base, nev):
+    """the bases of the events (S1 or uint8) as a contiguous uint8 vector of at least nev entries"""
+    base = np.asarray(base)
+    base = np.ascontiguousarray(base if base.dtype == np.uint8 else base.astype('S1').view(np.uint8))
+    if base.ndim != 1 or base.shape[0] < nev:
+        raise ValueError('base is shorter than its offsets say')
+    return base
+
+
+# The outputs of an entry, name -> (kind, length): kind is a dtype name numpy and torch share (or a dtype object of the form that is
+# asked).  The numpy allocation, the torch allocation and the check of a caller's `out=` dict all read these tables.
+def _mix_shapes(npos, nresp=None):
+    shapes = dict({k: ('float64', npos) for k in L.MIX_FIELDS}, iters=('int32', npos), status=('uint8', npos))
+    if nresp is not None:
+        shapes['resp'] = ('float32', nresp)
+    return shapes
+
+
+def _one_shapes(method_id, npos):
+    return dict({k: ('float64', npos) for k in L.ONE_FIELDS if method_id != L.METHOD_KS or not k.startswith('comb_')}, status=('uint8', npos))
+
+
+def _kmer_shapes(npos, ncodes):
+    m = max(ncodes, 0)
+    return dict({k: ('int64', m) for k in L.KMER_COUNT_FIELDS}, mean=('float64', m), sd=('float64', m), pos_status=('uint8', npos))
+
+
+def _rescale_shapes(nreads, val_kind=None, nval=0):
+    """val_kind None: mode 'fit_only', no rescaled events"""
+    shapes = dict(shift=('float64', nreads), scale=('float64', nreads), n_used=('int32', nreads), status=('uint8', nreads))
+    if val_kind is not None:
+        shapes['val'] = (val_kind, nval)
+    return shapes
+
+
+def _calls_shapes(want, nval, nreads):
+    return dict({w: ('float64', nval) for w in want}, n_sites=('int32', nreads), n_called=('int32', nreads), status=('uint8', nreads))
+
+
+def _site_shapes(npos):
+    return dict(n_valid=('int32', npos), n_called=('int32', npos), frac=('float64', npos))
+
+
+def _host_outputs(shapes, fill=()):
+    """numpy arrays for a table of outputs; the names in `fill` start as 0 (NaN for a float), the others uninitialised"""
+    res = {}
+    for name, (kind, n) in shapes.items():
+        dt = np.dtype(kind)
+        res[name] = np.empty(n, dt) if name not in fill else np.full(n, np.nan if dt.kind == 'f' else 0, dt)
+    return res
+
+
+def _call(lib, name, prm, *args):
+    """one C entry on `prm`; NanomodLibraryError with the library's message unless it returns NMOD_OK"""
+    L.check(getattr(lib, name)(C.byref(prm), *args), name)
+
+
+def _np_ptrs(res):
+    return {k: _np_ptr(a) for k, a in res.items()}
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _cuda_vecs(where, items, one_dim=False, missing=None):
+    """ValueError unless every t of `items` (name, t, dtype, n) is a contiguous CUDA tensor of `dtype` (None: any) and n elements
+    (None: any).  one_dim: also of one dimension — read_calls, site_calls (its scores) and fdr ask for that, the other entries take
+    any contiguous shape.  missing: what a None is: 'ok' (an optional argument), 'refused' (ValueError), or by default no case of
+    its own (not a tensor).  One call per group of tensors: the device entries sit in timing loops."""
+    for name, t, dtype, n in items:
+        if t is None and missing == 'ok':
+            continue
+        if (t is None and missing == 'refused') or not (t.is_cuda and t.is_contiguous() and (dtype is None or t.dtype == dtype)
+                                                        and (n is None or t.numel() == n) and (not one_dim or t.dim() == 1)):
+            raise ValueError('%s: %s must be a contiguous %sCUDA vector%s' % (where, name, '' if dtype is None else '%s ' % dtype,
+                                                                              '' if n is None else ' of %d elements' % n))
+
+
+def _device_offsets(torch, off, what, count):
+    """the number of rows (reads, positions) an int64 CUDA vector of offsets describes"""
+    _cuda_vecs(what, (('off', off, torch.int64, None),))
+    if off.numel() < 1:
+        raise ValueError('%s: off must hold %s + 1 elements' % (what, count))
+    return off.numel() - 1
+
+
+def _device_model(torch, what, val, base, mean, sd, k, center, one_dim):
+    """the events, bases and k-mer model of a device read entry, checked, as a filled nmod_rescale_model"""
+    n = _model_len(k)
+    _cuda_vecs(what, (('val', val, None, None), ('base', base, torch.uint8, None), ('mean', mean, torch.float64, n), ('sd', sd, torch.float64, n)),
+               one_dim, missing='refused')
+    if base.numel() != val.numel():
+        raise ValueError('%s: base needs one byte per event' % what)
+    return _model_struct(k, center, mean.data_ptr(), sd.data_ptr())
+
+
 FDR_SUMMARY_FIELDS = ('tested', 'excluded', 'rejected', 'p_crit')
 
 
@@ -197,8 +385,7 @@ def fdr_adjust_host(tracks, method='bh', alpha=0.05, device=0):
     qarr = (C.c_void_p * max(nt, 1))(*[t.ctypes.data for t in qs])
     summ = (L.NmodFdrSummary * max(nt, 1))()
     prm = L.make_params(device=device, memspace=L.MEM_HOST)
-    rc = lib.nmod_fdr_adjust(C.byref(prm), n, nt, parr, _fdr_method(method), float(alpha), qarr, C.cast(summ, C.c_void_p))
-    L.check(rc, 'nmod_fdr_adjust')
+    _call(lib, 'nmod_fdr_adjust', prm, n, nt, parr, _fdr_method(method), float(alpha), qarr, C.cast(summ, C.c_void_p))
     return qs, [{f: getattr(summ[t], f) for f in FDR_SUMMARY_FIELDS} for t in range(nt)]
 
 
@@ -239,42 +426,28 @@ def mix_fraction_host(sig0, off0, sig1, off1, *, mix_group=1, model='equal', max
     lib = L.load()
     mix_group, model, max_iter, tol = _mix_args(mix_group, model, max_iter, tol)
     _join_warm_up(device)
-    sig0 = np.ascontiguousarray(sig0)
-    sig1 = np.ascontiguousarray(sig1)
-    if sig0.dtype != sig1.dtype or sig0.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('sig0/sig1 must both be float32, both int16 (milli-units) or both float64')
-    dtype = _dtype_code(sig0.dtype)
+    sig0, dtype = _signal(sig0, 'sig0')
+    sig1, dtype1 = _signal(sig1, 'sig1')
+    if dtype != dtype1:
+        raise ValueError('sig0 and sig1 must share a dtype')
     if off0 is not None:
         npos = len(off0) - 1
     elif off1 is not None:
         npos = len(off1) - 1
     else:
         npos = sig0.shape[0] // stride0
-    off0 = None if off0 is None else np.ascontiguousarray(off0, dtype=np.int64)
-    off1 = None if off1 is None else np.ascontiguousarray(off1, dtype=np.int64)
-    _check_csr(off0, npos, 'off0')
-    _check_csr(off1, npos, 'off1')
-    for sig, off, stride, name in ((sig0, off0, stride0, 'sig0'), (sig1, off1, stride1, 'sig1')):
-        if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
-            raise ValueError('%s is shorter than its offsets / stride say' % name)
-    if gate is not None:
-        gate = np.ascontiguousarray(gate, dtype=np.float64)
-        if gate.shape != (npos,):
-            raise ValueError('gate must be float64[npos]')
-    res = {k: np.empty(npos, dtype=np.float64) for k in L.MIX_FIELDS}
-    res['iters'] = np.empty(npos, dtype=np.int32)
-    res['status'] = np.empty(npos, dtype=np.uint8)
+    off0, stride0 = _rows(sig0, off0, stride0, npos, 'sig0', 'off0')
+    off1, stride1 = _rows(sig1, off1, stride1, npos, 'sig1', 'off1')
+    gate = _side(gate, np.float64, npos, 'gate')
+    nresp = None
     if want_resp:
-        ysig, yoff, ystride = (sig1, off1, stride1) if mix_group == 1 else (sig0, off0, stride0)
-        res['resp'] = np.empty((int(yoff[-1]) if yoff is not None else npos * ystride) if npos else 0, dtype=np.float32)
-    out = L.NmodMixOut()
-    for k, a in res.items():
-        setattr(out, k, _np_ptr(a))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride0 if off0 is None else 0,
-                        stride1=stride1 if off1 is None else 0)
-    rc = lib.nmod_mix_fraction(C.byref(prm), npos, _np_ptr(sig0), _np_ptr(off0), _np_ptr(sig1), _np_ptr(off1), mix_group, model,
-                               max_iter, tol, _np_ptr(gate), float(gate_max), C.byref(out))
-    L.check(rc, 'nmod_mix_fraction')
+        yoff, ystride = (off1, stride1) if mix_group == 1 else (off0, stride0)
+        nresp = (int(yoff[-1]) if yoff is not None else npos * ystride) if npos else 0
+    res = _host_outputs(_mix_shapes(npos, nresp))
+    out = L.make_out(L.NmodMixOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride0, stride1=stride1)
+    _call(lib, 'nmod_mix_fraction', prm, npos, _np_ptr(sig0), _np_ptr(off0), _np_ptr(sig1), _np_ptr(off1), mix_group, model, max_iter, tol,
+          _np_ptr(gate), float(gate_max), C.byref(out))
     return res
 
 
@@ -286,37 +459,19 @@ def one_sample_host(sig, off, ref_mean, ref_sd, ref_n=None, run_id=None, *, stri
     method is not 'ks' (run_id is then required), comb_st / comb_p: the window combine of the KS track."""
     lib = L.load()
     _join_warm_up(device)
-    sig = np.ascontiguousarray(sig)
-    if sig.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('sig must be float32, int16 (milli-units) or float64')
+    sig, dtype = _signal(sig, 'sig')
     ref_mean = np.ascontiguousarray(ref_mean, dtype=np.float64)
-    ref_sd = np.ascontiguousarray(ref_sd, dtype=np.float64)
     npos = ref_mean.shape[0]
-    off = None if off is None else np.ascontiguousarray(off, dtype=np.int64)
-    _check_csr(off, npos, 'off')
-    if ref_sd.shape != (npos,):
-        raise ValueError('ref_sd must be float64[npos]')
-    if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
-        raise ValueError('sig is shorter than its offsets / stride say')
-    if ref_n is not None:
-        ref_n = np.ascontiguousarray(ref_n, dtype=np.int32)
-        if ref_n.shape != (npos,):
-            raise ValueError('ref_n must be int32[npos]')
+    off, stride = _rows(sig, off, stride, npos, 'sig')
+    ref_sd = _side(ref_sd, np.float64, npos, 'ref_sd', optional=False)
+    ref_n = _side(ref_n, np.int32, npos, 'ref_n')
     method_id = L.METHOD_BY_NAME[method] if isinstance(method, str) else method
-    run = None
-    if run_id is not None:
-        run = np.ascontiguousarray(run_id, dtype=np.int32)
-        if run.shape != (npos,):
-            raise ValueError('run_id must be int32[npos]')
-    names = [k for k in L.ONE_FIELDS if method_id != L.METHOD_KS or not k.startswith('comb_')]
-    res = {k: np.empty(npos, dtype=np.float64) for k in names}
-    res['status'] = np.empty(npos, dtype=np.uint8)
-    out = L.make_one_out(**{k: _np_ptr(a) for k, a in res.items()})
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(sig.dtype), method=method_id, nb=nb,
-                        weights_dif=weights_dif, stride0=stride if off is None else 0)
-    rc = lib.nmod_one_sample(C.byref(prm), npos, _np_ptr(sig), _np_ptr(off), _np_ptr(ref_mean), _np_ptr(ref_sd), _np_ptr(ref_n),
-                             _np_ptr(run), C.byref(out))
-    L.check(rc, 'nmod_one_sample')
+    run = _side(run_id, np.int32, npos, 'run_id')
+    res = _host_outputs(_one_shapes(method_id, npos))
+    out = L.make_out(L.NmodOneOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, method=method_id, nb=nb, weights_dif=weights_dif, stride0=stride)
+    _call(lib, 'nmod_one_sample', prm, npos, _np_ptr(sig), _np_ptr(off), _np_ptr(ref_mean), _np_ptr(ref_sd), _np_ptr(ref_n), _np_ptr(run),
+          C.byref(out))
     return res
 
 
@@ -328,35 +483,21 @@ def kmer_model_host(sig, off, code, ncodes, keep_lo=None, keep_hi=None, *, strid
     pos_status (uint8[npos], L.STATUS_* bits of the positions dropped whole)."""
     lib = L.load()
     _join_warm_up(device)
-    sig = np.ascontiguousarray(sig)
-    if sig.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('sig must be float32, int16 (milli-units) or float64')
+    sig, dtype = _signal(sig, 'sig')
     code = np.ascontiguousarray(code, dtype=np.int32)
     npos = code.shape[0]
-    off = None if off is None else np.ascontiguousarray(off, dtype=np.int64)
-    _check_csr(off, npos, 'off')
+    off, stride = _rows(sig, off, stride, npos, 'sig')
     if code.ndim != 1:
         raise ValueError('code must be int32[npos]')
-    if npos and sig.shape[0] < (int(off[-1]) if off is not None else npos * stride):
-        raise ValueError('sig is shorter than its offsets / stride say')
     ncodes = int(ncodes)
     if (keep_lo is None) != (keep_hi is None):
         raise ValueError('keep_lo and keep_hi come together')
-    if keep_lo is not None:
-        keep_lo = np.ascontiguousarray(keep_lo, dtype=np.float64)
-        keep_hi = np.ascontiguousarray(keep_hi, dtype=np.float64)
-        if keep_lo.shape != (ncodes,) or keep_hi.shape != (ncodes,):
-            raise ValueError('keep_lo / keep_hi must be float64[ncodes]')
-    m = max(ncodes, 0)
-    res = {k: np.empty(m, dtype=np.int64) for k in L.KMER_COUNT_FIELDS}
-    res['mean'] = np.empty(m, dtype=np.float64)
-    res['sd'] = np.empty(m, dtype=np.float64)
-    res['pos_status'] = np.empty(npos, dtype=np.uint8)
-    out = L.make_kmer_out(**{k: _np_ptr(a) for k, a in res.items()})
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(sig.dtype), stride0=stride if off is None else 0)
-    rc = lib.nmod_kmer_model(C.byref(prm), npos, _np_ptr(sig), _np_ptr(off), _np_ptr(code), ncodes, _np_ptr(keep_lo), _np_ptr(keep_hi),
-                             C.byref(out))
-    L.check(rc, 'nmod_kmer_model')
+    keep_lo = _side(keep_lo, np.float64, ncodes, 'keep_lo', 'ncodes')
+    keep_hi = _side(keep_hi, np.float64, ncodes, 'keep_hi', 'ncodes')
+    res = _host_outputs(_kmer_shapes(npos, ncodes))
+    out = L.make_out(L.NmodKmerOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride)
+    _call(lib, 'nmod_kmer_model', prm, npos, _np_ptr(sig), _np_ptr(off), _np_ptr(code), ncodes, _np_ptr(keep_lo), _np_ptr(keep_hi), C.byref(out))
     return res
 
 
@@ -380,10 +521,7 @@ def _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_ran
     if not (math.isfinite(lo) and lo > 0.0 and lo <= hi):
         raise ValueError('scale_range must be (lo, hi) with 0 < lo <= hi, lo finite')
     if mode != L.RESCALE_APPLY_ONLY:
-        if k is None or not 1 <= int(k) <= 8:
-            raise ValueError('k must be in 1 .. 8')
-        if not 0 <= int(center) < int(k):
-            raise ValueError('center must be in 0 .. k - 1')
+        _check_kmer(k, center, center_unguarded=True)
     return L.make_rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, lo, hi)
 
 
@@ -395,56 +533,35 @@ def rescale_reads_host(val, off, base, model=None, *, mode='fit_apply', weighted
     takes shift / scale (float64[nreads]) instead.  Returns a dict of numpy arrays: shift, scale (float64), n_used (int32), status
     (uint8, L.RESCALE_* bits) and, unless mode is 'fit_only', val: the rescaled events in val's dtype."""
     lib = L.load()
-    val = np.ascontiguousarray(val)
-    if val.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('val must be float32, int16 (milli-units) or float64')
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if off.ndim != 1 or off.shape[0] < 1:
-        raise ValueError('off must be int64[nreads + 1]')
-    nreads = off.shape[0] - 1
-    if nreads and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
-        raise ValueError('off must start at or above 0 and never decrease')
-    nev = int(off[-1]) if nreads else 0
-    if val.ndim != 1 or val.shape[0] < nev:
-        raise ValueError('val is shorter than its offsets say')
+    val, dtype = _signal(val, 'val')
+    off, nreads, nev = _read_layout(val, off, 'val')
     k = center = None
-    mean = sd = None
     if model is not None:
         k, center = int(model['k']), int(model['center'])
     opts = _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_range, k, center)
     fit, apply = opts.mode != L.RESCALE_APPLY_ONLY, opts.mode != L.RESCALE_FIT_ONLY
-    m = L.NmodRescaleModel()
     if fit:
-        mean = np.ascontiguousarray(model['mean'], dtype=np.float64)
-        sd = np.ascontiguousarray(model['sd'], dtype=np.float64)
-        if mean.shape != (4 ** k,) or sd.shape != (4 ** k,):
-            raise ValueError('model mean / sd must be float64[4^k]')
-        base = np.asarray(base)
-        base = np.ascontiguousarray(base if base.dtype == np.uint8 else base.astype('S1').view(np.uint8))
-        if base.ndim != 1 or base.shape[0] < nev:
-            raise ValueError('base is shorter than its offsets say')
-        m.k, m.center, m.mean, m.sd = k, center, mean.ctypes.data, sd.ctypes.data
-        shift_a, scale_a = np.empty(nreads, np.float64), np.empty(nreads, np.float64)
+        m, alive = _host_model(model)
+        base = _host_base(base, nev)
     else:
         if shift is None or scale is None:
             raise ValueError("mode 'apply_only' needs shift and scale")
-        shift_a = np.array(shift, dtype=np.float64, order='C')
-        scale_a = np.array(scale, dtype=np.float64, order='C')
-        if shift_a.shape != (nreads,) or scale_a.shape != (nreads,):
+        shift = np.array(shift, dtype=np.float64, order='C')
+        scale = np.array(scale, dtype=np.float64, order='C')
+        if shift.shape != (nreads,) or scale.shape != (nreads,):
             raise ValueError('shift / scale must be float64[nreads]')
-        base = None
-    res = dict(shift=shift_a, scale=scale_a, n_used=np.zeros(nreads, np.int32), status=np.zeros(nreads, np.uint8))
-    if apply:
-        res['val'] = np.empty_like(val)
+        m, base = L.NmodRescaleModel(), None
+    res = _host_outputs(_rescale_shapes(nreads, val.dtype if apply else None, val.shape[0]), fill=('n_used', 'status'))
+    if not fit:
+        res.update(shift=shift, scale=scale)                     # the pairs to apply: the entry's own copies of the caller's
+    if apply:                                                    # events outside [off[0], off[-1]) belong to no read: copied through
         res['val'][nev:] = val[nev:]
-    if nreads and off[0] > 0 and apply:
-        res['val'][:off[0]] = val[:off[0]]
+        if nreads and off[0] > 0:
+            res['val'][:off[0]] = val[:off[0]]
     _join_warm_up(device)
-    out = L.make_rescale_out(shift=_np_ptr(shift_a), scale=_np_ptr(scale_a), n_used=_np_ptr(res['n_used']), status=_np_ptr(res['status']),
-                             val_out=_np_ptr(res['val']) if apply else None)
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(val.dtype))
-    rc = lib.nmod_rescale_reads(C.byref(prm), nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
-    L.check(rc, 'nmod_rescale_reads')
+    out = L.make_out(L.NmodRescaleOut, **_np_ptrs({'val_out' if name == 'val' else name: a for name, a in res.items()}))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype)
+    _call(lib, 'nmod_rescale_reads', prm, nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
     return res
 
 
@@ -453,12 +570,8 @@ def _calls_opts(nb, alpha, k, center, want):
     nb, alpha = int(nb), float(alpha)
     if not 0 <= nb <= L.MAX_NB:
         raise ValueError('nb must be in 0 .. %d' % L.MAX_NB)
-    if not 0.0 < alpha <= 1.0:
-        raise ValueError('alpha must be in (0, 1]')
-    if k is None or not 1 <= int(k) <= 8:
-        raise ValueError('k must be in 1 .. 8')
-    if center is None or not 0 <= int(center) < int(k):
-        raise ValueError('center must be in 0 .. k - 1')
+    alpha = _check_alpha(alpha)
+    _check_kmer(k, center)
     want = tuple(want)
     if any(w not in L.CALLS_EVENT_FIELDS for w in want):
         raise ValueError("want must name tracks of 'z', 'p', 'p_win'")
@@ -472,39 +585,19 @@ def read_calls_host(val, off, base, model, *, nb=2, alpha=0.01, want=('z', 'p', 
     (float64, in val's layout: z, the two-sided normal p, and p_win, Fisher's combination over the events of the same read within nb)
     and per read n_sites, n_called (int32) and status (uint8, L.CALLS_TOO_LARGE)."""
     lib = L.load()
-    val = np.ascontiguousarray(val)
-    if val.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('val must be float32, int16 (milli-units) or float64')
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    if off.ndim != 1 or off.shape[0] < 1:
-        raise ValueError('off must be int64[nreads + 1]')
-    nreads = off.shape[0] - 1
-    if nreads and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
-        raise ValueError('off must start at or above 0 and never decrease')
-    nev = int(off[-1]) if nreads else 0
-    if val.ndim != 1 or val.shape[0] < nev:
-        raise ValueError('val is shorter than its offsets say')
+    val, dtype = _signal(val, 'val')
+    off, nreads, nev = _read_layout(val, off, 'val')
     if model is None:
         raise ValueError('read_calls needs a k-mer model')
-    k, center = int(model['k']), int(model['center'])
-    opts, want = _calls_opts(nb, alpha, k, center, want)
-    mean = np.ascontiguousarray(model['mean'], dtype=np.float64)
-    sd = np.ascontiguousarray(model['sd'], dtype=np.float64)
-    if mean.shape != (4 ** k,) or sd.shape != (4 ** k,):
-        raise ValueError('model mean / sd must be float64[4^k]')
-    base = np.asarray(base)
-    base = np.ascontiguousarray(base if base.dtype == np.uint8 else base.astype('S1').view(np.uint8))
-    if base.ndim != 1 or base.shape[0] < nev:
-        raise ValueError('base is shorter than its offsets say')
-    m = L.NmodRescaleModel()
-    m.k, m.center, m.mean, m.sd = k, center, mean.ctypes.data, sd.ctypes.data
-    res = {w: np.full(val.shape[0], np.nan) for w in want}
-    res.update(n_sites=np.zeros(nreads, np.int32), n_called=np.zeros(nreads, np.int32), status=np.zeros(nreads, np.uint8))
+    opts, want = _calls_opts(nb, alpha, int(model['k']), int(model['center']), want)
+    m, alive = _host_model(model)
+    base = _host_base(base, nev)
+    shapes = _calls_shapes(want, val.shape[0], nreads)
+    res = _host_outputs(shapes, fill=shapes)
     _join_warm_up(device)
-    out = L.make_calls_out(**{name: _np_ptr(a) for name, a in res.items()})
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=_dtype_code(val.dtype))
-    rc = lib.nmod_read_calls(C.byref(prm), nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
-    L.check(rc, 'nmod_read_calls')
+    out = L.make_out(L.NmodCallsOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype)
+    _call(lib, 'nmod_read_calls', prm, nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m), C.byref(opts), C.byref(out))
     if nreads and off[0] > 0:
         for w in want:                                          # events before the first read belong to no read
             res[w][:off[0]] = np.nan
@@ -517,20 +610,11 @@ def site_calls_host(score, off, *, stride=0, alpha=0.01, device=0):
     both int32, and frac = n_called / n_valid (float64, NaN without a valid score)."""
     lib = L.load()
     score = np.ascontiguousarray(score, dtype=np.float64)
-    alpha = float(alpha)
-    if not 0.0 < alpha <= 1.0:
-        raise ValueError('alpha must be in (0, 1]')
+    alpha = _check_alpha(alpha)
     if score.ndim != 1:
         raise ValueError('score must be a float64 vector')
     if off is not None:
-        off = np.ascontiguousarray(off, dtype=np.int64)
-        if off.ndim != 1 or off.shape[0] < 1:
-            raise ValueError('off must be int64[npos + 1]')
-        npos = off.shape[0] - 1
-        if npos and (off[0] < 0 or bool(np.any(np.diff(off) < 0))):
-            raise ValueError('off must start at or above 0 and never decrease')
-        if score.shape[0] < (int(off[-1]) if npos else 0):
-            raise ValueError('score is shorter than its offsets say')
+        off, npos, _ = _read_layout(score, off, 'score', 'npos')
     else:
         stride = int(stride)
         if stride <= 0:
@@ -538,12 +622,12 @@ def site_calls_host(score, off, *, stride=0, alpha=0.01, device=0):
         if score.shape[0] % stride:
             raise ValueError('score must hold whole rows of the stride')
         npos = score.shape[0] // stride
-    res = dict(n_valid=np.zeros(npos, np.int32), n_called=np.zeros(npos, np.int32), frac=np.full(npos, np.nan))
+    shapes = _site_shapes(npos)
+    res = _host_outputs(shapes, fill=shapes)
     _join_warm_up(device)
-    out = L.make_site_out(**{name: _np_ptr(a) for name, a in res.items()})
+    out = L.make_out(L.NmodSiteOut, **_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
-    rc = lib.nmod_site_calls(C.byref(prm), npos, _np_ptr(score), _np_ptr(off), alpha, C.byref(out))
-    L.check(rc, 'nmod_site_calls')
+    _call(lib, 'nmod_site_calls', prm, npos, _np_ptr(score), _np_ptr(off), alpha, C.byref(out))
     return res
 
 
@@ -650,6 +734,7 @@ class DeviceDetector:
         self.flags = int(flags) | (L.FLAG_DEEP if deep else 0)          # L.FLAG_* (include/nanomod_hip.h: NMOD_FLAG_*); deep: FLAG_DEEP
         self._ws = None
         self.timer = None
+        self._kinds = {n: getattr(torch, n) for n in ('float64', 'float32', 'int64', 'int32', 'int16', 'uint8')}
 
     def _params(self, dtype, stride0, stride1, max_n0, max_n1):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
@@ -667,17 +752,34 @@ class DeviceDetector:
             return L.DTYPE_I16_MILLI
         if t.dtype == torch.float64:
             return L.DTYPE_F64
-        raise ValueError('signals must be float32, int16 (milli-units) or float64')
+        raise ValueError('signals must be %s' % _SIGNAL_DTYPES)
+
+    @property
+    def _dev(self):
+        return 'cuda:%d' % self.device
+
+    def _outputs(self, out, shapes, what, validate=True, zero=(), given=None):
+        """The dict of output tensors for a table of outputs (_*_shapes): the caller's `out` as it is — checked against the table
+        when `validate` (rescale_reads, read_calls, site_calls; mix, one_sample and kmer_model never checked theirs) — or fresh
+        CUDA tensors, those named in `zero` zeroed, those in `given` taken from there instead."""
+        torch, kind = self.torch, self._kinds.get                   # (a dtype name as torch's dtype, a dtype object as it is)
+        if out is None:
+            given = given or {}
+            return {name: given[name] if name in given else (torch.zeros if name in zero else torch.empty)(n, dtype=kind(k, k), device=self._dev)
+                    for name, (k, n) in shapes.items()}
+        if validate:
+            _cuda_vecs(what + ': out', ((name, out.get(name), kind(k, k), n) for name, (k, n) in shapes.items()), missing='refused')
+        return out
 
     def workspace(self, prm, npos):
         need = self.lib.nmod_workspace_bytes(C.byref(prm), npos)
         if self._ws is None or self._ws.numel() < need:
-            self._ws = self.torch.empty(need, dtype=self.torch.uint8, device='cuda:%d' % self.device)
+            self._ws = self.torch.empty(need, dtype=self.torch.uint8, device=self._dev)
         return self._ws, need
 
     def alloc_outputs(self, npos):
         torch = self.torch
-        dev = 'cuda:%d' % self.device
+        dev = self._dev
         names = []
         if self.tests & L.TEST_MWU:
             names += ['mwu_u', 'mwu_p']
@@ -714,9 +816,8 @@ class DeviceDetector:
             if name in res:
                 setattr(o, name, res[name].data_ptr())
         o.status = res['status'].data_ptr()
-        ptr = lambda t: (t.data_ptr() if t is not None else None)
-        rc = self.lib.nmod_detect_batch(C.byref(prm), npos, ptr(sig0), ptr(off0), ptr(sig1), ptr(off1),
-                                        ptr(run_id), ws.data_ptr(), need, C.byref(o))
+        rc = self.lib.nmod_detect_batch(C.byref(prm), npos, _ptr(sig0), _ptr(off0), _ptr(sig1), _ptr(off1),
+                                        _ptr(run_id), ws.data_ptr(), need, C.byref(o))
         L.check(rc, 'nmod_detect_batch')
         return res
 
@@ -728,19 +829,15 @@ class DeviceDetector:
         tensors to write q into (a track's own tensor for in place)."""
         torch = self.torch
         ps = [res[name] for name in tracks]                         # KeyError for a track the run did not produce
-        for t in ps:
-            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and t.numel() == ps[0].numel()):
-                raise ValueError('fdr: tracks must be contiguous float64 CUDA vectors of one length')
+        _cuda_vecs('fdr', (('every track (all of one length)', t, torch.float64, ps[0].numel()) for t in ps), one_dim=True)
         n = ps[0].numel() if ps else 0
-        dev = 'cuda:%d' % self.device
-        qs = [out[name] if out is not None else torch.empty(n, dtype=torch.float64, device=dev) for name in tracks]
+        qs = [out[name] if out is not None else torch.empty(n, dtype=torch.float64, device=self._dev) for name in tracks]
         nt = len(ps)
-        summary = torch.empty((max(nt, 1), 4), dtype=torch.float64, device=dev)
+        summary = torch.empty((max(nt, 1), 4), dtype=torch.float64, device=self._dev)
         parr = (C.c_void_p * max(nt, 1))(*[t.data_ptr() for t in ps])
         qarr = (C.c_void_p * max(nt, 1))(*[t.data_ptr() for t in qs])
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        rc = self.lib.nmod_fdr_adjust(C.byref(prm), n, nt, parr, _fdr_method(method), float(alpha), qarr, summary.data_ptr())
-        L.check(rc, 'nmod_fdr_adjust')
+        _call(self.lib, 'nmod_fdr_adjust', prm, n, nt, parr, _fdr_method(method), float(alpha), qarr, summary.data_ptr())
         return qs, summary
 
     def mix(self, sig0, sig1, *, off0=None, off1=None, stride0=0, stride1=0, npos=None, mix_group=1, model='equal', max_iter=200,
@@ -756,31 +853,19 @@ class DeviceDetector:
             (q,), summary = det.fdr(res, tracks=('comb_p',), method='bh', alpha=0.05)
             mix = det.mix(sig0, sig1, stride0=n, stride1=n, npos=npos, gate=q, gate_max=0.05)
         """
-        torch = self.torch
         mix_group, model, max_iter, tol = _mix_args(mix_group, model, max_iter, tol)
         dtype = self._dtype_of(sig0)
         if self._dtype_of(sig1) != dtype:
             raise ValueError('sig0 and sig1 must share a dtype')
         if npos is None:
             npos = (off0.numel() - 1) if off0 is not None else ((off1.numel() - 1) if off1 is not None else sig0.numel() // stride0)
-        dev = 'cuda:%d' % self.device
-        if gate is not None and not (gate.is_cuda and gate.dtype == torch.float64 and gate.is_contiguous() and gate.numel() == npos):
-            raise ValueError('mix: gate must be a contiguous float64 CUDA vector of npos elements')
-        res = out
-        if res is None:
-            res = {k: torch.empty(npos, dtype=torch.float64, device=dev) for k in L.MIX_FIELDS}
-            res['iters'] = torch.empty(npos, dtype=torch.int32, device=dev)
-            res['status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
-            if want_resp:
-                res['resp'] = torch.empty((sig1 if mix_group == 1 else sig0).numel(), dtype=torch.float32, device=dev)
-        o = L.NmodMixOut()
-        for k, t in res.items():
-            setattr(o, k, t.data_ptr())
+        _cuda_vecs('mix', (('gate', gate, self.torch.float64, npos),), missing='ok')
+        shapes = _mix_shapes(npos, (sig1 if mix_group == 1 else sig0).numel() if want_resp else None)
+        res = self._outputs(out, shapes, 'mix', validate=False)
+        o = L.make_out(L.NmodMixOut, **{k: t.data_ptr() for k, t in res.items()})
         prm = self._params(dtype, stride0 if off0 is None else 0, stride1 if off1 is None else 0, 0, 0)
-        ptr = lambda t: (t.data_ptr() if t is not None else None)
-        rc = self.lib.nmod_mix_fraction(C.byref(prm), npos, ptr(sig0), ptr(off0), ptr(sig1), ptr(off1), mix_group, model, max_iter,
-                                        tol, ptr(gate), float(gate_max), C.byref(o))
-        L.check(rc, 'nmod_mix_fraction')
+        _call(self.lib, 'nmod_mix_fraction', prm, npos, _ptr(sig0), _ptr(off0), _ptr(sig1), _ptr(off1), mix_group, model, max_iter, tol,
+              _ptr(gate), float(gate_max), C.byref(o))
         return res
 
     def one_sample(self, sig, ref_mean, ref_sd, ref_n=None, run_id=None, *, off=None, stride=0, npos=None, out=None):
@@ -797,23 +882,15 @@ class DeviceDetector:
         dtype = self._dtype_of(sig)
         if npos is None:
             npos = ref_mean.numel()
-        dev = 'cuda:%d' % self.device
-        for t, dt, name in ((ref_mean, torch.float64, 'ref_mean'), (ref_sd, torch.float64, 'ref_sd'), (ref_n, torch.int32, 'ref_n'),
-                            (run_id, torch.int32, 'run_id'), (off, torch.int64, 'off')):
-            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == npos + (name == 'off')):
-                raise ValueError('one_sample: %s must be a contiguous %s CUDA vector of npos%s elements' % (name, dt, ' + 1' if name == 'off' else ''))
+        _cuda_vecs('one_sample', (('ref_mean', ref_mean, torch.float64, npos), ('ref_sd', ref_sd, torch.float64, npos),
+                                  ('ref_n', ref_n, torch.int32, npos), ('run_id', run_id, torch.int32, npos),
+                                  ('off', off, torch.int64, npos + 1)), missing='ok')
         if self.method != L.METHOD_KS and run_id is None:
             raise ValueError('one_sample: run_id is needed for the combined track')
-        res = out
-        if res is None:
-            names = [k for k in L.ONE_FIELDS if self.method != L.METHOD_KS or not k.startswith('comb_')]
-            res = {k: torch.empty(npos, dtype=torch.float64, device=dev) for k in names}
-            res['status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
-        o = L.make_one_out(**{k: t.data_ptr() for k, t in res.items()})
+        res = self._outputs(out, _one_shapes(self.method, npos), 'one_sample', validate=False)
+        o = L.make_out(L.NmodOneOut, **{k: t.data_ptr() for k, t in res.items()})
         prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
-        ptr = lambda t: (t.data_ptr() if t is not None else None)
-        rc = self.lib.nmod_one_sample(C.byref(prm), npos, ptr(sig), ptr(off), ptr(ref_mean), ptr(ref_sd), ptr(ref_n), ptr(run_id), C.byref(o))
-        L.check(rc, 'nmod_one_sample')
+        _call(self.lib, 'nmod_one_sample', prm, npos, _ptr(sig), _ptr(off), _ptr(ref_mean), _ptr(ref_sd), _ptr(ref_n), _ptr(run_id), C.byref(o))
         return res
 
     def kmer_model(self, sig, code, ncodes, keep_lo=None, keep_hi=None, *, off=None, stride=0, npos=None, out=None):
@@ -827,22 +904,12 @@ class DeviceDetector:
         if npos is None:
             npos = code.numel()
         ncodes = int(ncodes)
-        dev = 'cuda:%d' % self.device
-        for t, dt, name, m in ((code, torch.int32, 'code', npos), (off, torch.int64, 'off', npos + 1),
-                               (keep_lo, torch.float64, 'keep_lo', ncodes), (keep_hi, torch.float64, 'keep_hi', ncodes)):
-            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == m):
-                raise ValueError('kmer_model: %s must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
-        res = out
-        if res is None:
-            res = {k: torch.empty(max(ncodes, 0), dtype=torch.int64, device=dev) for k in L.KMER_COUNT_FIELDS}
-            res['mean'] = torch.empty(max(ncodes, 0), dtype=torch.float64, device=dev)
-            res['sd'] = torch.empty(max(ncodes, 0), dtype=torch.float64, device=dev)
-            res['pos_status'] = torch.empty(npos, dtype=torch.uint8, device=dev)
-        o = L.make_kmer_out(**{k: t.data_ptr() for k, t in res.items()})
+        _cuda_vecs('kmer_model', (('code', code, torch.int32, npos), ('off', off, torch.int64, npos + 1), ('keep_lo', keep_lo, torch.float64, ncodes),
+                                  ('keep_hi', keep_hi, torch.float64, ncodes)), missing='ok')
+        res = self._outputs(out, _kmer_shapes(npos, ncodes), 'kmer_model', validate=False)
+        o = L.make_out(L.NmodKmerOut, **{k: t.data_ptr() for k, t in res.items()})
         prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
-        ptr = lambda t: (t.data_ptr() if t is not None else None)
-        rc = self.lib.nmod_kmer_model(C.byref(prm), npos, ptr(sig), ptr(off), ptr(code), ncodes, ptr(keep_lo), ptr(keep_hi), C.byref(o))
-        L.check(rc, 'nmod_kmer_model')
+        _call(self.lib, 'nmod_kmer_model', prm, npos, _ptr(sig), _ptr(off), _ptr(code), ncodes, _ptr(keep_lo), _ptr(keep_hi), C.byref(o))
         return res
 
     def rescale_reads(self, val, off, base, mean=None, sd=None, k=None, center=None, *, mode='fit_apply', weighted=True, clip_sigma=3.0,
@@ -858,47 +925,26 @@ class DeviceDetector:
         dtype = self._dtype_of(val)
         opts = _rescale_opts(mode, weighted, clip_sigma, clip_rounds, min_events, scale_range, k, center)
         fit, apply = opts.mode != L.RESCALE_APPLY_ONLY, opts.mode != L.RESCALE_FIT_ONLY
-        dev = 'cuda:%d' % self.device
-        if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
-            raise ValueError('rescale_reads: off must be a contiguous int64 CUDA vector of nreads + 1 elements')
-        nreads = off.numel() - 1
-        checks = [(val, None, 'val', None)]
+        nreads = _device_offsets(torch, off, 'rescale_reads', 'nreads')
         if fit:
-            checks += [(base, torch.uint8, 'base', None), (mean, torch.float64, 'mean', 4 ** int(k)), (sd, torch.float64, 'sd', 4 ** int(k))]
+            m = _device_model(torch, 'rescale_reads', val, base, mean, sd, k, center, one_dim=False)
         else:
-            checks += [(shift, torch.float64, 'shift', nreads), (scale, torch.float64, 'scale', nreads)]
-        for t, dt, name, m in checks:
-            if t is None or not (t.is_cuda and t.is_contiguous() and (dt is None or t.dtype == dt) and (m is None or t.numel() == m)):
-                raise ValueError('rescale_reads: %s must be a contiguous CUDA vector%s' % (name, '' if m is None else ' of %d elements' % m))
-        if fit and base.numel() != val.numel():
-            raise ValueError('rescale_reads: base needs one byte per event')
-        res = out
-        if res is not None:
-            want = dict(shift=(torch.float64, nreads), scale=(torch.float64, nreads), n_used=(torch.int32, nreads), status=(torch.uint8, nreads))
+            m = L.NmodRescaleModel()
+            _cuda_vecs('rescale_reads', (('val', val, None, None), ('shift', shift, torch.float64, nreads), ('scale', scale, torch.float64, nreads)),
+                       missing='refused')
+        given = {}
+        if out is None:                                             # what is not allocated: the caller's pairs, val itself in place
+            if not fit:
+                given.update(shift=shift, scale=scale)
             if apply:
-                want['val'] = (val.dtype, val.numel())
-            for name, (dt, m) in want.items():
-                t = res.get(name)
-                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == m):
-                    raise ValueError('rescale_reads: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
-        else:
-            res = dict(n_used=torch.zeros(nreads, dtype=torch.int32, device=dev), status=torch.zeros(nreads, dtype=torch.uint8, device=dev))
-            if fit:
-                res['shift'] = torch.empty(nreads, dtype=torch.float64, device=dev)
-                res['scale'] = torch.empty(nreads, dtype=torch.float64, device=dev)
-            else:
-                res['shift'], res['scale'] = shift, scale
-            if apply:
-                res['val'] = val if inplace else torch.empty_like(val)
-        m = L.NmodRescaleModel()
-        if fit:
-            m.k, m.center, m.mean, m.sd = int(k), int(center), mean.data_ptr(), sd.data_ptr()
-        o = L.make_rescale_out(shift=res['shift'].data_ptr(), scale=res['scale'].data_ptr(), n_used=res['n_used'].data_ptr(),
-                               status=res['status'].data_ptr(), val_out=res['val'].data_ptr() if apply else None)
+                given['val'] = val if inplace else torch.empty_like(val)
+        res = self._outputs(out, _rescale_shapes(nreads, val.dtype if apply else None, val.numel()), 'rescale_reads',
+                            zero=('n_used', 'status'), given=given)
+        o = L.make_out(L.NmodRescaleOut, shift=res['shift'].data_ptr(), scale=res['scale'].data_ptr(), n_used=res['n_used'].data_ptr(),
+                       status=res['status'].data_ptr(), val_out=_ptr(res['val'] if apply else None))
         prm = self._params(dtype, 0, 0, 0, 0)
-        rc = self.lib.nmod_rescale_reads(C.byref(prm), nreads, off.data_ptr(), val.data_ptr(), base.data_ptr() if fit else None,
-                                         C.byref(m), C.byref(opts), C.byref(o))
-        L.check(rc, 'nmod_rescale_reads')
+        _call(self.lib, 'nmod_rescale_reads', prm, nreads, off.data_ptr(), val.data_ptr(), _ptr(base) if fit else None, C.byref(m),
+              C.byref(opts), C.byref(o))
         return res
 
     def read_calls(self, val, off, base, mean, sd, k, center, *, nb=2, alpha=0.01, want=('z', 'p', 'p_win'), out=None):
@@ -908,51 +954,25 @@ class DeviceDetector:
         vectors of 4^k model entries.  Returns a dict of CUDA tensors: the per-event tracks named in `want` (float64: z, p, p_win) and per
         read n_sites, n_called (int32) and status (uint8).  p_win is what pivot_reads' device form takes as `val` for site_calls.
         out: such a dict from an earlier call of the same shape, written again instead of allocating (a timing loop)."""
-        torch = self.torch
         dtype = self._dtype_of(val)
         opts, want = _calls_opts(nb, alpha, k, center, want)
-        dev = 'cuda:%d' % self.device
-        if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
-            raise ValueError('read_calls: off must be a contiguous int64 CUDA vector of nreads + 1 elements')
-        nreads = off.numel() - 1
-        for t, dt, name, m in ((val, None, 'val', None), (base, torch.uint8, 'base', None), (mean, torch.float64, 'mean', 4 ** int(k)),
-                               (sd, torch.float64, 'sd', 4 ** int(k))):
-            if t is None or not (t.is_cuda and t.is_contiguous() and t.dim() == 1 and (dt is None or t.dtype == dt) and (m is None or t.numel() == m)):
-                raise ValueError('read_calls: %s must be a contiguous CUDA vector%s' % (name, '' if m is None else ' of %d elements' % m))
-        if base.numel() != val.numel():
-            raise ValueError('read_calls: base needs one byte per event')
-        shapes = {w: (torch.float64, val.numel()) for w in want}
-        shapes.update(n_sites=(torch.int32, nreads), n_called=(torch.int32, nreads), status=(torch.uint8, nreads))
-        res = out
-        if res is not None:
-            for name, (dt, m) in shapes.items():
-                t = res.get(name)
-                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == m):
-                    raise ValueError('read_calls: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, m))
-        else:
-            res = {name: torch.empty(m, dtype=dt, device=dev) for name, (dt, m) in shapes.items()}
-        md = L.NmodRescaleModel()
-        md.k, md.center, md.mean, md.sd = int(k), int(center), mean.data_ptr(), sd.data_ptr()
-        o = L.make_calls_out(**{name: res[name].data_ptr() for name in shapes})
+        nreads = _device_offsets(self.torch, off, 'read_calls', 'nreads')
+        md = _device_model(self.torch, 'read_calls', val, base, mean, sd, k, center, one_dim=True)
+        shapes = _calls_shapes(want, val.numel(), nreads)
+        res = self._outputs(out, shapes, 'read_calls')
+        o = L.make_out(L.NmodCallsOut, **{name: res[name].data_ptr() for name in shapes})
         prm = self._params(dtype, 0, 0, 0, 0)
-        rc = self.lib.nmod_read_calls(C.byref(prm), nreads, off.data_ptr(), val.data_ptr(), base.data_ptr(), C.byref(md), C.byref(opts), C.byref(o))
-        L.check(rc, 'nmod_read_calls')
+        _call(self.lib, 'nmod_read_calls', prm, nreads, off.data_ptr(), val.data_ptr(), base.data_ptr(), C.byref(md), C.byref(opts), C.byref(o))
         return res
 
     def site_calls(self, score, *, off=None, stride=0, npos=None, alpha=0.01, out=None):
         """Per-position call counts over pivoted scores (nmod_site_calls, NMOD_MEM_DEVICE) on the current stream: score a float64 CUDA
         vector, rows by `off` (int64 CUDA vector) or a fixed `stride`.  Returns a dict of CUDA tensors n_valid, n_called (int32) and
         frac (float64)."""
-        torch = self.torch
-        alpha = float(alpha)
-        if not 0.0 < alpha <= 1.0:
-            raise ValueError('alpha must be in (0, 1]')
-        if not (score.is_cuda and score.dtype == torch.float64 and score.is_contiguous() and score.dim() == 1):
-            raise ValueError('site_calls: score must be a contiguous float64 CUDA vector')
+        alpha = _check_alpha(alpha)
+        _cuda_vecs('site_calls', (('score', score, self.torch.float64, None),), one_dim=True)
         if off is not None:
-            if not (off.is_cuda and off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 1):
-                raise ValueError('site_calls: off must be a contiguous int64 CUDA vector of npos + 1 elements')
-            npos = off.numel() - 1
+            npos = _device_offsets(self.torch, off, 'site_calls', 'npos')
         else:
             stride = int(stride)
             if stride <= 0:
@@ -961,20 +981,11 @@ class DeviceDetector:
                 npos = score.numel() // stride
             if npos * stride > score.numel():
                 raise ValueError('site_calls: score is shorter than npos rows of the stride')
-        dev = 'cuda:%d' % self.device
-        shapes = dict(n_valid=torch.int32, n_called=torch.int32, frac=torch.float64)
-        res = out
-        if res is not None:
-            for name, dt in shapes.items():
-                t = res.get(name)
-                if t is None or not (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == npos):
-                    raise ValueError('site_calls: out[%r] must be a contiguous %s CUDA vector of %d elements' % (name, dt, npos))
-        else:
-            res = {name: torch.empty(npos, dtype=dt, device=dev) for name, dt in shapes.items()}
-        o = L.make_site_out(**{name: res[name].data_ptr() for name in shapes})
+        shapes = _site_shapes(npos)
+        res = self._outputs(out, shapes, 'site_calls')
+        o = L.make_out(L.NmodSiteOut, **{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
-        rc = self.lib.nmod_site_calls(C.byref(prm), npos, score.data_ptr(), off.data_ptr() if off is not None else None, alpha, C.byref(o))
-        L.check(rc, 'nmod_site_calls')
+        _call(self.lib, 'nmod_site_calls', prm, npos, score.data_ptr(), _ptr(off), alpha, C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
@@ -1000,7 +1011,7 @@ class DeviceDetector:
         of 1 000 reads are replaced by a uniform draw over +-5 units (mis-segmented events)"""
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
         rc = self.lib.nmod_synth_fill_events(C.byref(prm), seed, pos_begin, npos, group, n_per_pos,
-                                             off.data_ptr() if off is not None else None, plant_period,
+                                             _ptr(off), plant_period,
                                              int(plant_shift_milli), int(spread_milli), int(outlier_permille), out.data_ptr())
         L.check(rc, 'nmod_synth_fill_events')
         return out
@@ -1040,13 +1051,6 @@ def downsample_ks(sig0, off0, sig1, off1, positions, cov, *, iters=100, quantile
 
 # ---------------------------------------------------------------------------------------------------- read-level input
 _TORCH_OF_DTYPE = {L.DTYPE_F32: 'float32', L.DTYPE_I16_MILLI: 'int16', L.DTYPE_F64: 'float64'}
-
-
-def _dtype_code(a):
-    try:
-        return {np.dtype(np.float32): L.DTYPE_F32, np.dtype(np.int16): L.DTYPE_I16_MILLI, np.dtype(np.float64): L.DTYPE_F64}[np.dtype(a)]
-    except KeyError:
-        raise ValueError('values must be float32, int16 (milli-units) or float64')
 
 
 def _torch_dtype_code(t):
