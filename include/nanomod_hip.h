@@ -647,6 +647,64 @@ typedef struct nmod_site_out { int32_t struct_size; int32_t reserved; int32_t *n
 int nmod_site_calls(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */, double alpha,
                     const nmod_site_out* out);
 
+/* Per-read log-likelihood ratios between two k-mer models (K13; the reference project has no such step): every event of every read is
+ * scored against the level of its k-mer in the unmodified table `model` and in the modified table `alt`, the ratios of the events OF THE
+ * SAME READ inside a window are summed, and an event is called modified, canonical or left ambiguous by that sum.  Where nmod_read_calls
+ * asks "is this level an outlier of the null", this asks "which of the two levels is it".
+ *   Inputs: exactly those of nmod_read_calls: flat reads in nmod_pivot_reads' layout, off[nreads + 1] (int64 CSR event offsets; required,
+ *     there is no stride form), val (prm->dtype) and base (one byte per event), events in read direction; two nmod_rescale_model structs,
+ *     `model` (mean0, sd0) and `alt` (mean1, sd1).  alt->k and alt->center must equal model's.  All four tables live in the call's
+ *     memspace.
+ *   Code of an event: K11 / K12's rule word for word: the bytes base[j - center .. j + k - 1 - center], A = 0, C = 1, G = 2, T = 3, upper
+ *     case only, the first base most significant; a window that leaves the read, or a byte that is not A / C / G / T, gives code -1.
+ *   Per code c, once per call: the code is usable iff mean0, sd0, mean1, sd1 are all finite and both spreads are > 0;
+ *     g_c = log(sd0_c / sd1_c), one division and then log.
+ *   Per event j, compiled with contraction off: the event is a candidate iff its code is usable and x_j is finite (x_j the value as a
+ *     double: int16 k / 1000.0, a division; float32 up-cast; float64 as is);
+ *       z0 = (x - mu0) / sd0,  z1 = (x - mu1) / sd1,  d = 0.5 * ((z0 - z1) * (z0 + z1)),  llr_j = g_c + d,
+ *     which is ln N(x; mu1, sd1^2) - ln N(x; mu0, sd0^2): a positive value favours the modified model.  The event is ELIGIBLE iff it is a
+ *     candidate and fabs(llr_j) <= NMOD_LLR_MAX (1e300): every window sum is then finite, and the inf - inf case of a near-zero spread is
+ *     gone.  An ineligible event gets NaN in every per-event output and takes no part in any window.
+ *   Window of j: the eligible events i of the same read with j - nb_lo <= i <= j + nb_hi and 0 <= i < n; nb_lo and nb_hi lie in
+ *     0 .. NMOD_MAX_NB, independently.  A read is a wall, as in K12.  (The k-mer cover of base j — the events whose k-mer contains the
+ *     base — is nb_lo = k - 1 - center, nb_hi = center: the default of the Python layers.)
+ *   Per eligible event: L_j = the sum of llr_i over the window, the terms added in ascending i (nb_lo = nb_hi = 0: L_j is llr_j, the same
+ *     bits);  t = L_j + prior_logit;  p_mod_j = t >= 0 ? 1 / (1 + exp(-t)) : exp(t) / (1 + exp(t)).  p_mod is a posterior, not a
+ *     p-value: it is not clamped and may be 0 or 1.
+ *   Calls, with thr > 0 finite: event j is MOD iff L_j >= thr, otherwise CAN iff L_j <= -thr, otherwise ambiguous.
+ *   Per read: n_sites = the eligible events, n_mod, n_can (int32), status 0 or NMOD_CALLS_TOO_LARGE (n > NMOD_MAX_DEEP: NaN events and zero
+ *     counts, as in K12).  A read without an eligible event is not an error.
+ *   Outputs (a NULL member is skipped; out->struct_size = sizeof of the out struct): per event, in val's layout, llr, llr_win = L and
+ *     p_mod as doubles; per read n_sites, n_mod, n_can (int32) and status (uint8).  Requesting fewer outputs never changes the bits of
+ *     the others.
+ * Reads struct_size, device, stream, memspace, dtype of prm and nothing else.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no
+ * host read and no synchronisation; scratch (8 bytes per read + 40 bytes per code) comes stream-ordered from the library's pool.
+ * NMOD_MEM_HOST: copy in, run, copy back, synchronise (one staged copy).  nreads == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG before any device
+ * work: a window bound outside 0 .. NMOD_MAX_NB, thr not finite or <= 0, prior_logit not finite or |prior_logit| > 700, k or center out of
+ * range or differing between the two models, and the size, NULL and offset rules of nmod_read_calls (nreads < 0 or beyond 2^32 - 2, NULL
+ * off / val / base / table arrays with nreads > 0, model / alt / opts / out NULL or (opts, out) of another struct_size, an unknown dtype,
+ * host offsets that decrease).
+ * A read's bits depend on the read alone: not on the batch, the order of the reads, the memspace or the outputs asked for.  A read is
+ * computed by one wave (up to NMOD_CALLS_WAVE_MAX events) or one workgroup.  No float atomics: the counts are integer reductions.
+ * Stops here: two tables only; one window per call; no per-site prior; the k-mers of both tables must match. */
+#define NMOD_LLR_MAX 1e300                 /* an event whose |llr| lies beyond is ineligible */
+typedef struct nmod_llr_opts { int32_t struct_size, nb_lo, nb_hi, reserved; double thr, prior_logit; } nmod_llr_opts;
+typedef struct nmod_llr_out { int32_t struct_size; int32_t reserved;
+  double *llr, *llr_win, *p_mod;    /* one per event, in val's layout */
+  int32_t *n_sites, *n_mod, *n_can; uint8_t* status; /* nreads each */ } nmod_llr_out;
+int nmod_read_llr(const nmod_params* prm, int64_t nreads, const int64_t* off, const void* val, const uint8_t* base,
+                  const nmod_rescale_model* model, const nmod_rescale_model* alt, const nmod_llr_opts* opts, const nmod_llr_out* out);
+
+/* Per-position counts over pivoted window sums (K13): the rows nmod_pivot_reads makes when the llr_win track of nmod_read_llr is handed
+ * to it as `val` with dtype F64 — one row of doubles per position, one sum per read that covers it.
+ *   Per row: n_valid = #{s : fabs(s) <= DBL_MAX}, n_mod = #{s >= thr}, n_can = #{s <= -thr},
+ *     frac = (double)n_mod / (double)(n_mod + n_can), NaN when that denominator is 0: the modified share of the confident reads.
+ *   Outputs (a NULL member is skipped): int32 n_valid, n_mod, n_can and double frac, npos each.
+ * Argument rules, memspaces and the CSR / stride forms are those of nmod_site_calls, with thr (finite, > 0) in the place of alpha. */
+typedef struct nmod_site_llr_out { int32_t struct_size; int32_t reserved; int32_t *n_valid, *n_mod, *n_can; double* frac; } nmod_site_llr_out;
+int nmod_site_llr(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */, double thr,
+                  const nmod_site_llr_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -179,6 +179,36 @@ make_calls_out = functools.partial(make_out, NmodCallsOut)
 make_site_out = functools.partial(make_out, NmodSiteOut)
 
 
+LLR_MAX = 1e300            # nmod_read_llr: an event whose |llr| lies beyond is ineligible
+LLR_PRIOR_LOGIT_MAX = 700.0
+LLR_EVENT_FIELDS = ('llr', 'llr_win', 'p_mod')
+LLR_READ_FIELDS = ('n_sites', 'n_mod', 'n_can', 'status')
+SITE_LLR_FIELDS = ('n_valid', 'n_mod', 'n_can', 'frac')
+
+
+class NmodLlrOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'nb_lo', 'nb_hi', 'reserved')] + [('thr', C.c_double), ('prior_logit', C.c_double)]
+
+
+class NmodLlrOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in LLR_EVENT_FIELDS + LLR_READ_FIELDS]
+
+
+class NmodSiteLlrOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in SITE_LLR_FIELDS]
+
+
+def make_llr_opts(nb_lo=0, nb_hi=0, thr=2.5, prior_logit=0.0):
+    o = NmodLlrOpts()
+    o.struct_size = C.sizeof(NmodLlrOpts)
+    o.nb_lo, o.nb_hi, o.thr, o.prior_logit = int(nb_lo), int(nb_hi), float(thr), float(prior_logit)
+    return o
+
+
+make_llr_out = functools.partial(make_out, NmodLlrOut)
+make_site_llr_out = functools.partial(make_out, NmodSiteLlrOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -239,6 +269,9 @@ _SIGNATURES = {
     'nmod_read_calls': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
                                   C.POINTER(NmodCallsOpts), C.POINTER(NmodCallsOut)]),
     'nmod_site_calls': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteOut)]),
+    'nmod_read_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
+                                C.POINTER(NmodRescaleModel), C.POINTER(NmodLlrOpts), C.POINTER(NmodLlrOut)]),
+    'nmod_site_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteLlrOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -152,7 +152,73 @@ def build_parser():
     rc.add_argument('--outFolder', default='mRes')
     rc.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_calls.txt and <FileID>_site_calls.txt')
     rc.add_argument('--device', type=int, default=0)
+    rl = sub.add_parser('readllr', help='call the events of every read between an unmodified and a modified k-mer model on the device '
+                        '(log-likelihood ratios): modified, canonical or neither, and the modified share per position')
+    rl.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rl.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rl.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
+    rl.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rl.add_argument('--llrThreshold', type=float, default=2.5, help='an event is called when its window sum reaches +- this, > 0')
+    rl.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
+                    'before and after, 0 .. 64 each')
+    rl.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state behind p_mod, inside (0, 1)')
+    rl.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rl.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first (the "
+                    "fit of 'rescale' with its defaults, on the device)")
+    rl.add_argument('--outEvents', default='', help='optional: a .npz file for the per-event tracks llr, llr_win, p_mod (with off)')
+    rl.add_argument('--outFolder', default='mRes')
+    rl.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_llr.txt and <FileID>_site_llr.txt')
+    rl.add_argument('--device', type=int, default=0)
     return p
+
+
+def parse_llr_window(text):
+    """--llrWindow: 'kmer', or (lo, hi) of 'LO,HI'; None for anything else"""
+    if text == 'kmer':
+        return 'kmer'
+    parts = text.split(',')
+    if len(parts) != 2 or not all(q.strip().isdigit() for q in parts):
+        return None
+    return int(parts[0]), int(parts[1])
+
+
+def validate_readllr(a):
+    """the checks of readllr"""
+    errs = []
+    win = parse_llr_window(a.llrWindow)
+    if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
+        errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
+    if not 0.0 < a.llrThreshold < float('inf'):
+        errs.append('Error: --llrThreshold should be finite and larger than 0')
+    if not 0.0 < a.prior < 1.0:
+        errs.append('Error: --prior should lie between 0 and 1, both excluded')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    for f in (a.wrkBase1, a.kmerModel, a.altModel):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_readllr(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    reads = container.load_reads(a.wrkBase1)
+    res = readllr.call_reads_llr(reads, kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
+                                 window=parse_llr_window(a.llrWindow), thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions,
+                                 rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device,
+                                 log=(lambda *x: None) if quiet else log)
+    table, sites = res[0], res[1]
+    os.makedirs(a.outFolder, exist_ok=True)
+    readllr.write_read_llr(os.path.join(a.outFolder, a.FileID + '_read_llr.txt'), table)
+    readllr.write_site_llr(os.path.join(a.outFolder, a.FileID + '_site_llr.txt'), sites)
+    if a.outEvents:
+        np.savez(a.outEvents, off=np.asarray(reads['off'], dtype=np.int64), **res[2])
+    if not quiet:
+        log('Read calls are saved in %s' % os.path.join(a.outFolder, a.FileID + '_read_llr.txt'))
+    return res
 
 
 def validate_readcalls(a):
@@ -615,6 +681,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readllr':
+        errs = validate_readllr(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readllr(a)
+        return 0
     if a.cmd == 'readcalls':
         errs = validate_readcalls(a)
         if errs:

@@ -260,6 +260,23 @@ def _host_model(model):
     return _model_struct(k, model['center'], mean.ctypes.data, sd.ctypes.data), (mean, sd)
 
 
+def _host_score_rows(score, off, stride):
+    """pivoted scores (float64) by `off` (int64[npos + 1]) or, with off None, whole rows of a fixed `stride`: the contiguous scores and
+    offsets (or None), the stride and npos"""
+    score = np.ascontiguousarray(score, dtype=np.float64)
+    if score.ndim != 1:
+        raise ValueError('score must be a float64 vector')
+    if off is not None:
+        off, npos, _ = _read_layout(score, off, 'score', 'npos')
+        return score, off, stride, npos
+    stride = int(stride)
+    if stride <= 0:
+        raise ValueError('either off or a positive stride')
+    if score.shape[0] % stride:
+        raise ValueError('score must hold whole rows of the stride')
+    return score, None, stride, score.shape[0] // stride
+
+
 def _host_base(base, nev):
     """the bases of the events (S1 or uint8) as a contiguous uint8 vector of at least nev entries"""
     base = np.asarray(base)
@@ -609,25 +626,101 @@ def site_calls_host(score, off, *, stride=0, alpha=0.01, device=0):
     or, with off None, a fixed `stride`.  Returns a dict of numpy arrays: n_valid (scores in [0, 1]), n_called (valid scores <= alpha),
     both int32, and frac = n_called / n_valid (float64, NaN without a valid score)."""
     lib = L.load()
-    score = np.ascontiguousarray(score, dtype=np.float64)
     alpha = _check_alpha(alpha)
-    if score.ndim != 1:
-        raise ValueError('score must be a float64 vector')
-    if off is not None:
-        off, npos, _ = _read_layout(score, off, 'score', 'npos')
-    else:
-        stride = int(stride)
-        if stride <= 0:
-            raise ValueError('either off or a positive stride')
-        if score.shape[0] % stride:
-            raise ValueError('score must hold whole rows of the stride')
-        npos = score.shape[0] // stride
+    score, off, stride, npos = _host_score_rows(score, off, stride)
     shapes = _site_shapes(npos)
     res = _host_outputs(shapes, fill=shapes)
     _join_warm_up(device)
     out = L.make_out(L.NmodSiteOut, **_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
     _call(lib, 'nmod_site_calls', prm, npos, _np_ptr(score), _np_ptr(off), alpha, C.byref(out))
+    return res
+
+
+def _check_thr(thr):
+    import math
+    thr = float(thr)
+    if not (math.isfinite(thr) and thr > 0.0):
+        raise ValueError('thr must be finite and positive')
+    return thr
+
+
+def _llr_opts(window, thr, prior_logit, k, center, alt_k, alt_center, want):
+    """nmod_llr_opts from the Python arguments; ValueError for what the C entry refuses.  window: 'kmer' (the events whose k-mer holds
+    the base: k - 1 - center before, center after) or (lo, hi)"""
+    import math
+    _check_kmer(k, center)
+    if alt_k is None or alt_center is None or (int(alt_k), int(alt_center)) != (int(k), int(center)):
+        raise ValueError('the two models must share k and center')
+    if isinstance(window, str):
+        if window != 'kmer':
+            raise ValueError("window must be 'kmer' or (lo, hi)")
+        lo, hi = int(k) - 1 - int(center), int(center)
+    else:
+        try:
+            lo, hi = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError("window must be 'kmer' or (lo, hi)")
+    if not (0 <= lo <= L.MAX_NB and 0 <= hi <= L.MAX_NB):
+        raise ValueError('the window bounds must be in 0 .. %d' % L.MAX_NB)
+    thr, prior_logit = _check_thr(thr), float(prior_logit)
+    if not (math.isfinite(prior_logit) and abs(prior_logit) <= L.LLR_PRIOR_LOGIT_MAX):
+        raise ValueError('prior_logit must be finite and within +-%g' % L.LLR_PRIOR_LOGIT_MAX)
+    want = tuple(want)
+    if any(w not in L.LLR_EVENT_FIELDS for w in want):
+        raise ValueError("want must name tracks of 'llr', 'llr_win', 'p_mod'")
+    return L.make_llr_opts(lo, hi, thr, prior_logit), want
+
+
+def _llr_shapes(want, nval, nreads):
+    return dict({w: ('float64', nval) for w in want}, n_sites=('int32', nreads), n_mod=('int32', nreads), n_can=('int32', nreads),
+                status=('uint8', nreads))
+
+
+def _site_llr_shapes(npos):
+    return dict(n_valid=('int32', npos), n_mod=('int32', npos), n_can=('int32', npos), frac=('float64', npos))
+
+
+def read_llr_host(val, off, base, model, alt, *, window='kmer', thr=2.5, prior_logit=0.0, want=('llr', 'llr_win', 'p_mod'), device=0):
+    """Per-read log-likelihood ratios between two k-mer models (nmod_read_llr, include/nanomod_hip.h) on host-resident reads: val, off
+    and base as for read_calls_host; model (unmodified) and alt (modified): mappings with k, center, mean, sd of one k and center.
+    window: 'kmer' or (lo, hi) events of the same read before and after.  Returns a dict of numpy arrays: the per-event tracks named in
+    `want` (float64, in val's layout: llr, the window sum llr_win, the posterior p_mod at prior_logit) and per read n_sites, n_mod,
+    n_can (int32) and status (uint8, L.CALLS_TOO_LARGE)."""
+    lib = L.load()
+    val, dtype = _signal(val, 'val')
+    off, nreads, nev = _read_layout(val, off, 'val')
+    if model is None or alt is None:
+        raise ValueError('read_llr needs two k-mer models')
+    opts, want = _llr_opts(window, thr, prior_logit, int(model['k']), int(model['center']), int(alt['k']), int(alt['center']), want)
+    m0, alive0 = _host_model(model)
+    m1, alive1 = _host_model(alt)
+    base = _host_base(base, nev)
+    shapes = _llr_shapes(want, val.shape[0], nreads)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodLlrOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype)
+    _call(lib, 'nmod_read_llr', prm, nreads, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m0), C.byref(m1), C.byref(opts), C.byref(out))
+    if nreads and off[0] > 0:
+        for w in want:                                          # events before the first read belong to no read
+            res[w][:off[0]] = np.nan
+    return res
+
+
+def site_llr_host(score, off, *, stride=0, thr=2.5, device=0):
+    """Per-position counts over pivoted window sums (nmod_site_llr): score float64, one row per position by `off` (int64[npos + 1]) or,
+    with off None, a fixed `stride`.  Returns a dict of numpy arrays: n_valid (finite sums), n_mod (sums >= thr), n_can (sums <= -thr),
+    all int32, and frac = n_mod / (n_mod + n_can) (float64, NaN without a confident read)."""
+    lib = L.load()
+    thr = _check_thr(thr)
+    score, off, stride, npos = _host_score_rows(score, off, stride)
+    shapes = _site_llr_shapes(npos)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodSiteLlrOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
+    _call(lib, 'nmod_site_llr', prm, npos, _np_ptr(score), _np_ptr(off), thr, C.byref(out))
     return res
 
 
@@ -970,22 +1063,59 @@ class DeviceDetector:
         vector, rows by `off` (int64 CUDA vector) or a fixed `stride`.  Returns a dict of CUDA tensors n_valid, n_called (int32) and
         frac (float64)."""
         alpha = _check_alpha(alpha)
-        _cuda_vecs('site_calls', (('score', score, self.torch.float64, None),), one_dim=True)
-        if off is not None:
-            npos = _device_offsets(self.torch, off, 'site_calls', 'npos')
-        else:
-            stride = int(stride)
-            if stride <= 0:
-                raise ValueError('site_calls: either off or a positive stride')
-            if npos is None:
-                npos = score.numel() // stride
-            if npos * stride > score.numel():
-                raise ValueError('site_calls: score is shorter than npos rows of the stride')
+        stride, npos = self._score_rows('site_calls', score, off, stride, npos)
         shapes = _site_shapes(npos)
         res = self._outputs(out, shapes, 'site_calls')
         o = L.make_out(L.NmodSiteOut, **{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
         _call(self.lib, 'nmod_site_calls', prm, npos, score.data_ptr(), _ptr(off), alpha, C.byref(o))
+        return res
+
+    def _score_rows(self, what, score, off, stride, npos):
+        """the rows of a float64 CUDA vector of pivoted scores, by `off` or a fixed `stride`: (stride, npos), checked"""
+        _cuda_vecs(what, (('score', score, self.torch.float64, None),), one_dim=True)
+        if off is not None:
+            return stride, _device_offsets(self.torch, off, what, 'npos')
+        stride = int(stride)
+        if stride <= 0:
+            raise ValueError('%s: either off or a positive stride' % what)
+        if npos is None:
+            npos = score.numel() // stride
+        if npos * stride > score.numel():
+            raise ValueError('%s: score is shorter than npos rows of the stride' % what)
+        return stride, npos
+
+    def read_llr(self, val, off, base, mean, sd, alt_mean, alt_sd, k, center, *, window='kmer', thr=2.5, prior_logit=0.0,
+                 want=('llr', 'llr_win', 'p_mod'), out=None):
+        """Per-read log-likelihood ratios between two k-mer models (nmod_read_llr, NMOD_MEM_DEVICE), enqueued on the current stream
+        without synchronising or reading anything back.  val, off, base as for read_calls; mean / sd (unmodified) and alt_mean / alt_sd
+        (modified): float64 CUDA vectors of 4^k entries each; window: 'kmer' or (lo, hi).  Returns a dict of CUDA tensors: the per-event
+        tracks named in `want` (float64: llr, llr_win, p_mod) and per read n_sites, n_mod, n_can (int32) and status (uint8).  llr_win is
+        what pivot_reads' device form takes as `val` for site_llr.  out: such a dict from an earlier call of the same shape."""
+        dtype = self._dtype_of(val)
+        opts, want = _llr_opts(window, thr, prior_logit, k, center, k, center, want)
+        nreads = _device_offsets(self.torch, off, 'read_llr', 'nreads')
+        m0 = _device_model(self.torch, 'read_llr', val, base, mean, sd, k, center, one_dim=True)
+        m1 = _device_model(self.torch, 'read_llr', val, base, alt_mean, alt_sd, k, center, one_dim=True)
+        shapes = _llr_shapes(want, val.numel(), nreads)
+        res = self._outputs(out, shapes, 'read_llr')
+        o = L.make_out(L.NmodLlrOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(dtype, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_llr', prm, nreads, off.data_ptr(), val.data_ptr(), base.data_ptr(), C.byref(m0), C.byref(m1), C.byref(opts),
+              C.byref(o))
+        return res
+
+    def site_llr(self, score, *, off=None, stride=0, npos=None, thr=2.5, out=None):
+        """Per-position counts over pivoted window sums (nmod_site_llr, NMOD_MEM_DEVICE) on the current stream: score a float64 CUDA
+        vector, rows by `off` (int64 CUDA vector) or a fixed `stride`.  Returns a dict of CUDA tensors n_valid, n_mod, n_can (int32) and
+        frac (float64)."""
+        thr = _check_thr(thr)
+        stride, npos = self._score_rows('site_llr', score, off, stride, npos)
+        shapes = _site_llr_shapes(npos)
+        res = self._outputs(out, shapes, 'site_llr')
+        o = L.make_out(L.NmodSiteLlrOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
+        _call(self.lib, 'nmod_site_llr', prm, npos, score.data_ptr(), _ptr(off), thr, C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

@@ -1,0 +1,118 @@
+"""Per-read calls by the log-likelihood ratio between two k-mer models (K13; include/nanomod_hip.h: nmod_read_llr,
+nmod_site_llr).
+
+`readcalls` scores every event against the unmodified model alone: an outlier test.  With a second table, built by `kmermodel` from a
+fully modified control, every event has a log-likelihood ratio ln N(x; modified) - ln N(x; unmodified); summed over the events of the
+same read whose k-mer covers a base it says which of the two levels the read shows there: modified (the sum is at least `thr`),
+canonical (at most -thr) or neither.  Per position, the modified share of the reads that are one or the other.
+
+    canonical, modified = (kmermodel.load_kmer_model(p) for p in ('control_kmer_model.npz', 'modified_kmer_model.npz'))
+    table, sites = call_reads_llr(container.load_reads('sample_reads.npz'), canonical, modified, rescale=dict(min_events=50))
+    write_read_llr('run_read_llr.txt', table); write_site_llr('run_site_llr.txt', sites)
+
+The rescaling (K11, against the unmodified model), the ratios, the grouping by position and the counts all run in the HIP library on
+the device, one after the other on one stream; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _lib as L
+from . import engine
+from . import rescale as _rescale
+from .readcalls import _RESCALE_KEYS
+
+
+def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None, events=False, device=0,
+                   log=print):
+    """Call the events of a read-level set (container.READ_FIELDS) between an unmodified and a modified k-mer model
+    (kmermodel.KMER_MODEL_FIELDS, one k and center).  window: 'kmer' (the events whose k-mer holds the base) or (lo, hi) events of the
+    same read before and after; thr: the window sum from which an event is called; prior: the prior probability of the modified state
+    behind the posterior track p_mod (it does not move the calls).  rescale: None, or a dict of rescale.rescale_reads' fit options: the
+    reads are first put on the unmodified model's scale on the device.
+    Returns (table, sites) — and with `events` a third dict of the per-event tracks llr, llr_win, p_mod (float64, in the reads' layout):
+    table: one entry per read: index, chrom, strand, start, events, n_sites (scored events), n_mod, n_can, status (L.CALLS_TOO_LARGE)
+      and, when rescaled, shift, scale, rescale_status;
+    sites: one entry per covered position in the reference's row order: chrom, strand, pos, base, n_reads (the events there), n_valid
+      (the scored ones), n_mod, n_can, frac = n_mod / (n_mod + n_can) (NaN without a confident read).
+    One summary line goes to `log`."""
+    import torch
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    if rescale is not None:
+        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
+        if unknown:
+            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    val = np.ascontiguousarray(reads['norm_mean'])
+    if val.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('reads: norm_mean must be float32, int16 (milli-units) or float64')
+    off = np.ascontiguousarray(reads['off'], dtype=np.int64)
+    nreads = len(off) - 1
+    if nreads < 0 or len(reads['start']) != nreads:
+        raise ValueError('reads: off needs nreads + 1 entries')
+    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
+    if len(base) != len(val) or (nreads and (off[0] != 0 or off[-1] != len(val))):
+        raise ValueError('reads: norm_mean and base need one entry per event of off')
+    engine._join_warm_up(device)
+    det = engine.DeviceDetector(device)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    d_val, d_off, d_base = t(val), t(off), t(base)
+    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+    fit = None
+    if rescale is not None:
+        fit = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)
+        d_val = fit['val']
+    want = L.LLR_EVENT_FIELDS if events else ('llr_win',)
+    calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
+                         prior_logit=prior_logit, want=want)
+    piv = engine.pivot_reads(reads, device, val=calls['llr_win'])
+    counts = det.site_llr(piv['sig'], off=piv['off'], thr=thr)
+
+    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
+                 start=np.asarray(reads['start'], dtype=np.int64), events=np.diff(off),
+                 **{f: calls[f].cpu().numpy() for f in L.LLR_READ_FIELDS})
+    if fit is not None:
+        table.update(shift=fit['shift'].cpu().numpy(), scale=fit['scale'].cpu().numpy(), rescale_status=fit['status'].cpu().numpy())
+    key = piv['key'].cpu().numpy()
+    names = np.array(piv['names'], dtype=str)
+    row_off = piv['off'].cpu().numpy()
+    sites = dict(chrom=names[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                 pos=key & ((1 << 40) - 1), base=piv['base'].cpu().numpy().view('S1').astype('U1'), n_reads=np.diff(row_off).astype(np.int32),
+                 **{f: counts[f].cpu().numpy() for f in L.SITE_LLR_FIELDS})
+    log('readllr: %d read(s), %d of %d event(s) scored, %d modified and %d canonical at threshold %g over %d + 1 + %d event(s); '
+        '%d position(s), %d with a modified call%s'
+        % (nreads, int(table['n_sites'].sum()), len(val), int(table['n_mod'].sum()), int(table['n_can'].sum()), float(thr), opts.nb_lo, opts.nb_hi,
+           len(key), int((sites['n_mod'] > 0).sum()),
+           '' if fit is None else '; %d read(s) not rescaled' % int(((table['rescale_status'] & L.RESCALE_FAILED) != 0).sum())))
+    if events:
+        return table, sites, {f: calls[f].cpu().numpy() for f in L.LLR_EVENT_FIELDS}
+    return table, sites
+
+
+def write_read_llr(path, table):
+    """<FileID>_read_llr.txt: per read 'index chrom strand start events n_sites n_mod n_can status' as '%d %s %s %d %d %d %d %d %d'"""
+    cols = [np.asarray(table['index']).tolist(), np.asarray(table['chrom']).astype(str).tolist(), np.asarray(table['strand']).astype(str).tolist()] + \
+           [np.asarray(table[f]).tolist() for f in ('start', 'events', 'n_sites', 'n_mod', 'n_can', 'status')]
+    with open(path, 'w') as f:
+        f.writelines('%d %s %s %d %d %d %d %d %d\n' % row for row in zip(*cols))
+
+
+def write_site_llr(path, sites):
+    """<FileID>_site_llr.txt: per position 'chrom strand pos+1 base n_reads n_valid n_mod n_can frac' as '%s %s %d %s %d %d %d %d %.6f'
+    (the position 1-based like every text output; frac 'nan' where no read is confident)"""
+    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
+            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
+           [np.asarray(sites[f]).tolist() for f in ('n_reads', 'n_valid', 'n_mod', 'n_can', 'frac')]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
