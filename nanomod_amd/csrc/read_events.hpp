@@ -1,5 +1,6 @@
-// What the kernels that walk the events of a read share (K11 nmod_rescale_reads, K12 nmod_read_calls): the value of an event as a
-// double, the 2-bit code of a base, and the k-mer code rolled over a run of consecutive events.
+// The events of a read, for the kernels that walk them (K11 nmod_rescale_reads, K12 nmod_read_calls, K13 nmod_read_llr): the value of an
+// event as a double, the 2-bit code of a base, and the k-mer code rolled over a run of consecutive events.  The walk itself — lists,
+// draw, tiles, launches — is read_walk.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

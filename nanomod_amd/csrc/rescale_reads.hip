@@ -1,18 +1,18 @@
 // nmod_rescale_reads — per-read shift and scale against a k-mer model, and the rescaled events, on the device (K11).
 // The reference project has no such step; the definition is the one in include/nanomod_hip.h (tests/rescale_ref.py restates it
-// in numpy).  All on the caller's stream:
+// in numpy).  The walk over the reads is read_walk.hpp's, shared with K12 and K13; all on the caller's stream:
 //   rs_table_kernel      (fitting modes) a thread per code: the model as (mu, sd, w) with sd = -1 for an entry that makes its
 //                        events ineligible, so that the fit reads one table and divides nothing per event
-//   rs_classify_kernel   a thread per read: the read's class by its length, ballot-compacted into one list per class
+//   read_classify_kernel (read_walk.hpp) a thread per read: the read's class by its length, ballot-compacted into one list per class
 //   rs_read_kernel<.., 1>  a wave per read of up to NMOD_RESCALE_WAVE_MAX events, four waves a workgroup
 //   rs_read_kernel<.., 4>  a workgroup of four waves per longer read
 // Both forms are one function.  A lane takes runs of 8 consecutive events (run c of the read on lane c mod lanes) and rolls the
 // 2-bit code over the run's bases and a k - 1 byte halo; per fit it chains W, sum w mu', sum w x', sum w mu' mu', sum w mu' x'
 // (primes: about the read's first eligible event) in fp64 in event order, and the lanes' words are summed in a fixed order
 // (wave_sum_f64, block_sum_f64).  The apply pass follows the fits in the same kernel, while the read's events are L2-resident.
-// The grids are persistent; a wave / workgroup draws its next read with one returning atomic on a ticket word (a read is
-// hundreds of events or more: the ticket is noise, and the lengths differ by orders of magnitude).  No float atomics: a read's
-// bits depend on the read alone — its class comes from its length — not on the batch, the list order or the memspace.
+// The grids are persistent; a wave / workgroup draws its next read with one returning atomic on a ticket word (draw_read,
+// read_walk.hpp; a read is hundreds of events or more: the ticket is noise, and the lengths differ by orders of magnitude).  No float
+// atomics: a read's bits depend on the read alone — its class comes from its length — not on the batch, the list order or the memspace.
 // The table lives in LDS up to 1 024 codes (k <= 5: 24 KiB); beyond it is read through L2.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -20,16 +20,11 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
-#include "entry_common.hpp"
-#include "entry_device.hpp"
-#include "read_events.hpp"
+#include "read_walk.hpp"
 
 namespace nmod {
 
-constexpr int kRsThreads = 256;
-constexpr int kRsWaves = kRsThreads / 64;
 constexpr int kRsLdsCodes = 1024;                 // the table lives in LDS up to here: 24 bytes per code
-constexpr double kRsDblMax = 1.7976931348623157e308;
 
 struct RsArgs {
   const void* val; void* val_out; const uint8_t* base; const int64_t* off; int64_t nreads;
@@ -39,7 +34,7 @@ struct RsArgs {
   int32_t mode, weighted, clip_rounds, min_events;
   double clip_sigma, scale_lo, scale_hi;
   double* shift; double* scale; int32_t* n_used; uint8_t* status;
-  uint32_t* list[2]; uint32_t* count;             // count[0 .. 1]: the lists' lengths, count[2 .. 3]: their ticket words
+  ReadLists w;
 };
 
 __global__ __launch_bounds__(256) void rs_table_kernel(RsArgs a) {
@@ -47,28 +42,11 @@ __global__ __launch_bounds__(256) void rs_table_kernel(RsArgs a) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= a.ncodes) return;
   const double mu = a.mean[c], sd = a.sd[c];
-  const bool ok = fabs(mu) <= kRsDblMax && sd > 0.0 && sd <= kRsDblMax;
+  const bool ok = fabs(mu) <= kDblMax && sd > 0.0 && sd <= kDblMax;
   a.tab[c] = ok ? mu : 0.0;
   a.tab[a.ncodes + c] = ok ? sd : -1.0;
   a.tab[2 * a.ncodes + c] = !ok ? 0.0 : (a.weighted ? 1.0 / (sd * sd) : 1.0);
 }
-
-__global__ __launch_bounds__(256) void rs_classify_kernel(RsArgs a) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t b0 = (int64_t)blockIdx.x * 256; b0 < a.nreads; b0 += (int64_t)gridDim.x * 256) {
-    const int64_t i = b0 + threadIdx.x;
-    int cls = -1;
-    if (i < a.nreads) {
-      int64_t b, n;
-      csr_row(a.off, 0, i, b, n);
-      cls = n <= NMOD_RESCALE_WAVE_MAX ? 0 : 1;
-    }
-    compact_to_lists<2>(cls, lane, a.list, a.count, i);
-  }
-}
-
-// (rs_load, rs_base2 and rs_run — the value, the base code and the rolled k-mer code of a run of events — are in read_events.hpp,
-// which nmod_read_calls shares)
 
 // sum / maximum over the group that computes a read (a wave, or the workgroup), the same bits in every thread
 template <int WAVES>
@@ -104,7 +82,7 @@ template <int DT>
 __device__ __forceinline__ bool rs_apply_one(const void* val, void* out, int64_t i, double a0, double r) {
 #pragma clang fp contract(off)
   const double x = rs_load<DT>(val, i);
-  if (!(fabs(x) <= kRsDblMax)) {                                // a non-finite value stays as it is
+  if (!(fabs(x) <= kDblMax)) {                                  // a non-finite value stays as it is
     if constexpr (DT == NMOD_DTYPE_F32) static_cast<float*>(out)[i] = static_cast<const float*>(val)[i];
     else if constexpr (DT == NMOD_DTYPE_F64) static_cast<double*>(out)[i] = x;
     return false;
@@ -122,42 +100,30 @@ __device__ __forceinline__ bool rs_apply_one(const void* val, void* out, int64_t
 
 // WAVES == 1: a wave per read (list 0), the workgroup's waves independent; else the workgroup per read (list 1)
 template <int DT, int WAVES, bool LDS_TAB>
-__global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
+__global__ __launch_bounds__(kRwThreads) void rs_read_kernel(RsArgs a) {
 #pragma clang fp contract(off)
   constexpr int CLS = WAVES == 1 ? 0 : 1;
   constexpr int T = WAVES * 64;                                 // threads of a read
   __shared__ double lds_tab[LDS_TAB ? 3 * kRsLdsCodes : 1];
-  __shared__ double sh[kRsWaves];
+  __shared__ double sh[kRwWaves];
   __shared__ unsigned sh_item;
   const bool fit = a.mode != NMOD_RESCALE_APPLY_ONLY, apply = a.mode != NMOD_RESCALE_FIT_ONLY;
   const int nc = a.ncodes;
   const double* tmu = a.tab; const double* tsd = a.tab + nc; const double* tw = a.tab + 2 * nc;
   if constexpr (LDS_TAB) {
-    if (fit) for (int c = threadIdx.x; c < 3 * nc; c += kRsThreads) lds_tab[c] = a.tab[c];
+    if (fit) for (int c = threadIdx.x; c < 3 * nc; c += kRwThreads) lds_tab[c] = a.tab[c];
     tmu = lds_tab; tsd = lds_tab + nc; tw = lds_tab + 2 * nc;
     __syncthreads();
   }
   const int lane = threadIdx.x & 63;
   const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  const unsigned cnt = a.count[CLS];
+  const unsigned cnt = a.w.count[CLS];
   const int k = a.k, center = a.center;
 
   for (;;) {
-    unsigned item = 0;
-    if constexpr (WAVES == 1) {
-      // Every lane takes part in the draw and lane 0 alone adds one: the broadcast below is then reached by the whole wave on
-      // every path.  (Under `if (lane == 0)` the draw would share its condition with the stores of `if (t == 0)` at the end of
-      // the body, and a compiler that threads the two lets the other lanes reach the broadcast without lane 0.)
-      const unsigned got = atomicAdd(&a.count[2 + CLS], lane == 0 ? 1u : 0u);
-      item = (unsigned)__builtin_amdgcn_readlane((int)got, 0);
-    } else {
-      __syncthreads();                                          // the last read's uses of sh / sh_item are over
-      if (threadIdx.x == 0) sh_item = atomicAdd(&a.count[2 + CLS], 1u);
-      __syncthreads();
-      item = sh_item;
-    }
+    const unsigned item = draw_read<WAVES>(a.w, sh_item);
     if (item >= cnt) break;
-    const int64_t read = (int64_t)a.list[CLS][item];
+    const int64_t read = (int64_t)a.w.list[CLS][item];
     int64_t begin, n;
     csr_row(a.off, 0, read, begin, n);
     const uint8_t* bs = a.base + begin;
@@ -169,7 +135,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
       st = NMOD_RESCALE_TOO_LARGE;
     } else if (!fit) {
       fa = a.shift[read]; fb = a.scale[read];
-      if (!(fabs(fa) <= kRsDblMax) || !(fb > 0.0) || !(fb <= kRsDblMax)) st = NMOD_RESCALE_DEGENERATE;
+      if (!(fabs(fa) <= kDblMax) || !(fb > 0.0) || !(fb <= kDblMax)) st = NMOD_RESCALE_DEGENERATE;
     } else {
       // the read's first eligible event: the origin of the sums.  A step of the group at a time, until one has it
       double first = 0.0;                                       // n - j of it (0: none)
@@ -180,7 +146,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
           rs_run(bs, n, c * kRsRun, k, center, [&](int64_t j, int code) {
             if (code < 0 || mine != 0.0 || !(tsd[code] > 0.0)) return;
             const double x = rs_load<DT>(a.val, begin + j);
-            if (fabs(x) <= kRsDblMax) mine = (double)(n - j);
+            if (fabs(x) <= kDblMax) mine = (double)(n - j);
           });
         }
         first = rs_max<WAVES>(mine, sh);
@@ -204,7 +170,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
               const double sd = tsd[code];
               if (!(sd > 0.0)) return;
               const double x = rs_load<DT>(a.val, begin + j);
-              if (!(fabs(x) <= kRsDblMax)) return;
+              if (!(fabs(x) <= kDblMax)) return;
               const double mu = tmu[code];
               if (round > 0 && !(fabs(x - ca - cb * mu) <= lim * sd)) return;
               const double w = tw[code], dm = mu - mu0, dx = x - x0;
@@ -220,10 +186,10 @@ __global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
         const double mb = sm / W, xb = sx / W;
         const double Smm = smm - sm * mb, Smx = smx - sm * xb;
         const double b = Smx / Smm;
-        if (!(Smm > 0.0) || !(fabs(b) <= kRsDblMax) || !(b > 0.0)) { st = NMOD_RESCALE_DEGENERATE; break; }
+        if (!(Smm > 0.0) || !(fabs(b) <= kDblMax) || !(b > 0.0)) { st = NMOD_RESCALE_DEGENERATE; break; }
         fb = b;
         fa = (x0 + xb) - b * (mu0 + mb);
-        if (!(fabs(fa) <= kRsDblMax)) { st = NMOD_RESCALE_DEGENERATE; break; }
+        if (!(fabs(fa) <= kDblMax)) { st = NMOD_RESCALE_DEGENERATE; break; }
       }
       if (!st && !(fb >= a.scale_lo && fb <= a.scale_hi)) st = NMOD_RESCALE_OUT_OF_RANGE;
     }
@@ -251,17 +217,9 @@ __global__ __launch_bounds__(kRsThreads) void rs_read_kernel(RsArgs a) {
   }
 }
 
-template <int DT, bool LDS_TAB>
-static void rs_launch(const RsArgs& a, int num_cus, hipStream_t stream) {
-  const int64_t cap = (int64_t)num_cus * (LDS_TAB ? 6 : 8);
-  hipLaunchKernelGGL((rs_read_kernel<DT, 1, LDS_TAB>), dim3(persistent_grid(a.nreads, kRsWaves, cap)), dim3(kRsThreads), 0, stream, a);
-  hipLaunchKernelGGL((rs_read_kernel<DT, kRsWaves, LDS_TAB>), dim3(persistent_grid(a.nreads, 1, cap)), dim3(kRsThreads), 0, stream, a);
-}
-
-template <int DT>
-static void rs_launch_dt(const RsArgs& a, int num_cus, hipStream_t stream) {
-  if (a.ncodes <= kRsLdsCodes) rs_launch<DT, true>(a, num_cus, stream); else rs_launch<DT, false>(a, num_cus, stream);
-}
+struct RsKernels {
+  template <int DT, int WAVES, bool LDS_TAB> static auto kernel() { return &rs_read_kernel<DT, WAVES, LDS_TAB>; }
+};
 
 }  // namespace nmod
 
@@ -275,24 +233,21 @@ extern "C" int nmod_rescale_reads(const nmod_params* prm, int64_t nreads, const 
   const int mode = opts->mode;
   if (mode != NMOD_RESCALE_FIT_APPLY && mode != NMOD_RESCALE_FIT_ONLY && mode != NMOD_RESCALE_APPLY_ONLY) return NMOD_ERR_INVALID_ARG;
   const bool fit = mode != NMOD_RESCALE_APPLY_ONLY, apply = mode != NMOD_RESCALE_FIT_ONLY;
-  if (nreads < 0 || nreads > (int64_t)UINT32_MAX - 1) return NMOD_ERR_INVALID_ARG;
-  if (fit && (!model || model->k < 1 || model->k > 8 || model->center < 0 || model->center >= model->k)) return NMOD_ERR_INVALID_ARG;
+  if (!read_count_ok(nreads) || (fit && !kmer_model_ok(model))) return NMOD_ERR_INVALID_ARG;
   if (opts->clip_rounds < 0 || opts->clip_rounds > 8) return NMOD_ERR_INVALID_ARG;
-  if (opts->clip_rounds > 0 && !(opts->clip_sigma > 0.0 && opts->clip_sigma <= kRsDblMax)) return NMOD_ERR_INVALID_ARG;
+  if (opts->clip_rounds > 0 && !(opts->clip_sigma > 0.0 && opts->clip_sigma <= kDblMax)) return NMOD_ERR_INVALID_ARG;
   if (opts->min_events < 2) return NMOD_ERR_INVALID_ARG;
-  if (!(opts->scale_lo > 0.0) || !(opts->scale_lo <= kRsDblMax) || !(opts->scale_lo <= opts->scale_hi)) return NMOD_ERR_INVALID_ARG;
+  if (!(opts->scale_lo > 0.0) || !(opts->scale_lo <= kDblMax) || !(opts->scale_lo <= opts->scale_hi)) return NMOD_ERR_INVALID_ARG;
   if (nreads > 0) {
     if (!off || !val) return NMOD_ERR_INVALID_ARG;
     if (fit && (!base || !model->mean || !model->sd)) return NMOD_ERR_INVALID_ARG;
     if (apply && !out->val_out) return NMOD_ERR_INVALID_ARG;
     if (!fit && (!out->shift || !out->scale)) return NMOD_ERR_INVALID_ARG;
   }
-  const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && nreads > 0 && !csr_offsets_ok(off, nreads)) return NMOD_ERR_INVALID_ARG;
-  if (nreads == 0) return NMOD_OK;
   int num_cus = 0;
-  const int rc = select_device(prm, &num_cus);
-  if (rc != NMOD_OK) return rc;
+  const int rc = rows_begin(prm, nreads, off, &num_cus);
+  if (rc != NMOD_OK || nreads == 0) return rc;
+  const bool host = prm->memspace == NMOD_MEM_HOST;
   hipStream_t stream = (hipStream_t)prm->stream;
   const size_t nr = (size_t)nreads, esz = elem_bytes(prm->dtype);
   const size_t tot = host ? (size_t)off[nreads] : 0;
@@ -311,7 +266,8 @@ extern "C" int nmod_rescale_reads(const nmod_params* prm, int64_t nreads, const 
   // one slab: the work lists with their count and ticket words and the table; for the host entry the inputs and outputs as well
   // (an in-place host call has two device copies of the events: the bits are the same)
   Slab slab(host);
-  const size_t o_list = slab.take(nr * 4 * 2), o_count = slab.take(16), o_tab = slab.take(nc * 24);
+  const ReadListSpace lists(slab, nr);
+  const size_t o_tab = slab.take(nc * 24);
   slab.in(a.off, (nr + 1) * 8); slab.in(a.val, tot * esz);
   if (fit) { slab.in(a.base, tot); slab.in(a.mean, nc * 8); slab.in(a.sd, nc * 8); }
   if (fit) { slab.out(a.shift, nr * 8); slab.out(a.scale, nr * 8); }
@@ -319,18 +275,12 @@ extern "C" int nmod_rescale_reads(const nmod_params* prm, int64_t nreads, const 
   slab.out(a.n_used, nr * 4); slab.out(a.status, nr);
   slab.out(a.val_out, tot * esz);
   NMOD_HIP(slab.commit(stream, prm->device));
-  a.list[0] = slab.at<uint32_t>(o_list); a.list[1] = a.list[0] + nr;
-  a.count = slab.at<uint32_t>(o_count);
   a.tab = slab.at<double>(o_tab);
 
-  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
+  NMOD_HIP(lists.fill(slab, a.off, nreads, num_cus, stream, a.w));
   if (fit) hipLaunchKernelGGL(rs_table_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, stream, a);
-  const int64_t cb = (nreads + 255) / 256, ccap = (int64_t)num_cus * 16;
-  hipLaunchKernelGGL(rs_classify_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, a);
-  if (prm->dtype == NMOD_DTYPE_F32) rs_launch_dt<NMOD_DTYPE_F32>(a, num_cus, stream);
-  else if (prm->dtype == NMOD_DTYPE_I16_MILLI) rs_launch_dt<NMOD_DTYPE_I16_MILLI>(a, num_cus, stream);
-  else rs_launch_dt<NMOD_DTYPE_F64>(a, num_cus, stream);
-  NMOD_HIP(hipGetLastError());
-  NMOD_HIP(slab.finish(stream));
-  return NMOD_OK;
+  // (workgroups a CU: six beside the 24 KiB table in LDS, eight without it)
+  if (a.ncodes <= kRsLdsCodes) launch_read_kernels<RsKernels, true>(a, prm->dtype, (int64_t)num_cus * 6, 0, stream);
+  else launch_read_kernels<RsKernels, false>(a, prm->dtype, (int64_t)num_cus * 8, 0, stream);
+  return launches_end(slab, stream);
 }

@@ -1,22 +1,23 @@
-"""Batches of reads larger than the grids of K11 (nmod_rescale_reads) and K12 (nmod_read_calls), and what they must give.  Both
-entries define a read's outputs by the read alone, so a batch whose read i is read idx[i] of a small set of D distinct reads has the
-distinct reads' outputs, gathered: per_read[idx] and per_event[ev].  The restatements (rescale_ref, readcalls_ref) loop over reads in
-Python and only ever see the D distinct reads; the batch and its expectation are built without a Python loop over its reads.  Nothing
+"""Batches of reads larger than the grids of K11 (nmod_rescale_reads), K12 (nmod_read_calls) and K13 (nmod_read_llr), and what they
+must give.  The entries define a read's outputs by the read alone, so a batch whose read i is read idx[i] of a small set of D distinct
+reads has the distinct reads' outputs, gathered: per_read[idx] and per_event[ev].  The restatements (rescale_ref, readcalls_ref,
+readllr_ref) loop over reads in Python and only ever see the D distinct reads; the batch and its expectation are built without a Python loop over its reads.  Nothing
 here calls the library."""
 import functools
 
 import numpy as np
 
 import readcalls_ref as Q
+import readllr_ref as F
 import rescale_ref as R
 
 WAVE_MAX = R.WAVE_MAX
-assert Q.WAVE_MAX == WAVE_MAX                     # both entries split their classes at the same length
+assert Q.WAVE_MAX == WAVE_MAX == F.WAVE_MAX       # the entries split their classes at the same length
 
 # The grids, restated from the launch code; the tests size their batches from these and assert that they did.
-WAVES_PER_BLOCK = 4                               # kRsWaves = kRsThreads / 64, kRcWaves = kRcThreads / 64: a short read takes a wave
-BLOCKS_PER_CU = 8                                 # rs_launch: cap = num_cus * (LDS_TAB ? 6 : 8); rc_launch: cap = num_cus * 2 — the largest
-CLASSIFY_READS_PER_CU = 16 * 256                  # r[sc]_classify_kernel: ccap = num_cus * 16 blocks of 256 threads, a thread per read
+WAVES_PER_BLOCK = 4                               # read_walk.hpp: kRwWaves = kRwThreads / 64, a short read takes a wave
+BLOCKS_PER_CU = 8                                 # the caps: nmod_rescale_reads num_cus * 6 (table in LDS) or 8; nmod_read_calls num_cus * 2; rl_launch at most num_cus * 5 — the largest
+CLASSIFY_READS_PER_CU = 16 * 256                  # read_classify_kernel: ccap = num_cus * 16 blocks of 256 threads, a thread per read
 CLASSIFY_BEYOND = 100000                          # reads past the first stride of the classify grid in the second-pass batches
 
 RESCALE_MIN_EVENTS = 30
@@ -24,6 +25,10 @@ RESCALE_FIELDS = ('shift', 'scale', 'n_used', 'status')
 CALLS_ALPHA = 0.01
 CALLS_EVENT_FIELDS = ('z', 'p', 'p_win')
 CALLS_READ_FIELDS = ('n_sites', 'n_called', 'status')
+LLR_THR = F.PARITY_THR
+LLR_PRIOR_LOGIT = F.PARITY_PRIOR_LOGIT
+LLR_EVENT_FIELDS = ('llr', 'llr_win', 'p_mod')
+LLR_READ_FIELDS = ('n_sites', 'n_mod', 'n_can', 'status')
 
 
 def short_units(cus):
@@ -35,8 +40,13 @@ def long_units(cus):
 
 
 def calls_inner(nb):
-    """the events a tile of K12 owns: kRcTile - 2 * halo, the halo whole runs of 8"""
+    """the events a tile of K12 owns: kRwTile - 2 * halo, the halo whole runs of 8"""
     return 512 - 2 * 8 * ((nb + 7) // 8)
+
+
+def llr_inner(window):
+    """the events a tile of K13 owns: kRwTile less the halo before and the halo after, each whole runs of 8"""
+    return 512 - 8 * ((window[0] + 7) // 8) - 8 * ((window[1] + 7) // 8)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the batch builder
@@ -171,6 +181,51 @@ def calls_expected(k, center, nb, dtype):
 
 def calls_gather(small, idx, ev):
     return gather(small, idx, ev, CALLS_READ_FIELDS, CALLS_EVENT_FIELDS + ('W',))
+
+
+# ------------------------------------------------------------------------------------------------------------ the distinct sets: K13
+
+@functools.lru_cache(maxsize=None)
+def llr_distinct(k, center, window, dtype):
+    """K13's distinct reads: dict(val, off, base, mean, sd, alt_mean, alt_sd, names).  The short lengths and the three around the tile's
+    own events for this window; reads drawn from the unmodified and from the modified table in turn (n_mod and n_can differ widely), with
+    no eligible event, with the holes of both tables and 'N' bytes; long reads just past WAVE_MAX (more than a tile per wave: 4 tiles of
+    at most 512 own events, and no multiple of any tile), one a tile longer, one of 5 000."""
+    rng = np.random.default_rng(6300 + 1000 * k + 100 * center + 7 * window[0] + window[1])
+    mean, sd = R.make_model(k)
+    mean1, sd1 = F.make_alt_model(k, mean, sd)
+    inner = llr_inner(window)
+    assert WAVE_MAX + 1 > WAVES_PER_BLOCK * 384 and (WAVE_MAX + 1) % inner and 5000 % inner
+    reads, names = [], []
+
+    def add(name, b, x):
+        names.append(name); reads.append((b, x))
+
+    for i, n in enumerate(sorted(set(short_lengths(k)) | {inner - 1, inner, inner + 1})):
+        src = (mean, sd) if i % 2 == 0 else (mean1, sd1)
+        add('short_%d' % n, *R.draw_read(rng, n, k, center, src[0], src[1], 0.0, 1.0, contaminate=i % 4 < 2, n_letters=2 if i % 3 == 0 else 0))
+    for tag, n in (('short', 600), ('long', WAVE_MAX + 1)):
+        add(tag + '_none_eligible', np.full(n, ord('n'), np.uint8), np.zeros(n))
+        add(tag + '_unmodified', *R.draw_read(rng, n, k, center, mean, sd, 0.0, 1.0, contaminate=False))
+        add(tag + '_modified', *R.draw_read(rng, n, k, center, mean1, sd1, 0.0, 1.0, contaminate=False))
+        b = np.tile(np.frombuffer(b'AATACGGCGTAACCCCTTTGGGACCA', np.uint8), n // 26 + 1)[:n].copy()   # (k = 3) runs through the holes of both tables
+        b[[n // 3, n // 3 + 1, n - 2]] = ord('N')
+        add(tag + '_holes', b, R.draw_values(rng, b, k, center, mean, sd, 0.0, 1.0))
+    add('long_contaminated', *R.draw_read(rng, WAVE_MAX + 1, k, center, mean1, sd1, 0.0, 1.0, n_letters=3))
+    add('long_plus_tile', *R.draw_read(rng, WAVE_MAX + 1 + inner, k, center, mean, sd, 0.0, 1.0))
+    add('long_5000', *R.draw_read(rng, 5000, k, center, mean1, sd1, 0.0, 1.0))
+    val, off, base = _stack(reads, dtype)
+    return dict(val=val, off=off, base=base, mean=mean, sd=sd, alt_mean=mean1, alt_sd=sd1, names=tuple(names))
+
+
+@functools.lru_cache(maxsize=None)
+def llr_expected(k, center, window, dtype):
+    d = llr_distinct(k, center, window, dtype)
+    return F.restate(d['val'], d['off'], d['base'], k, center, d['mean'], d['sd'], d['alt_mean'], d['alt_sd'], window, LLR_THR, LLR_PRIOR_LOGIT)
+
+
+def llr_gather(small, idx, ev):
+    return gather(small, idx, ev, LLR_READ_FIELDS, LLR_EVENT_FIELDS + ('gate_llr', 'gate_L'))
 
 
 # ----------------------------------------------------------------------------------------------------------------- the index vectors

@@ -1,6 +1,7 @@
-"""K11 (nmod_rescale_reads) and K12 (nmod_read_calls) on batches larger than their grids (tests/read_batch_cases.py): every wave and
-workgroup of the persistent kernels goes round its ticket loop at least twice with real work, many waves fill the work lists at once
-with partial ballot masks, and one batch per entry makes the classify kernel take a second stride.  A batch is a small set of distinct
+"""K11 (nmod_rescale_reads), K12 (nmod_read_calls) and K13 (nmod_read_llr) on batches larger than their grids
+(tests/read_batch_cases.py): every wave and workgroup of the persistent kernels goes round its ticket loop at least twice with real
+work, many waves fill the work lists at once with partial ballot masks, and one batch per entry makes the classify kernel take a second
+stride.  A batch is a small set of distinct
 reads repeated in a seeded order, so its expected outputs are the distinct reads' outputs gathered — from the restatements through the
 gates of the neighbouring GPU files, and bit for bit from the device's own outputs on the distinct reads.  Every output tensor is
 filled with a sentinel byte before the call: a read that no unit took would keep it.  The measured times: profiles/read_batches.txt."""
@@ -10,6 +11,7 @@ import pytest
 import read_batch_cases as B
 import rescale_ref as R
 import test_read_calls_gpu as TC                  # K12's checker and gate, as they are
+import test_read_llr_gpu as TL                    # K13's checker and gates, as they are
 import test_rescale_gpu as TR                     # K11's checker and gate, as they are
 
 pytestmark = pytest.mark.gpu
@@ -17,6 +19,7 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 0xA5
 RESCALE_CASES = [(3, 1, 'int16'), (6, 2, 'float32'), (3, 1, 'float64')]                  # the LDS table, the table through L2, the LDS table
 CALLS_KD = [(3, 1, 'int16'), (6, 2, 'float32')]                                          # the LDS table, the table through L2
+LLR_KD = [(3, 1, 'int16'), (6, 2, 'float32')]                                            # the LDS table, the table through L2
 
 
 def _torch():
@@ -70,7 +73,8 @@ def _assert_gathered_bits(big, small, idx_t, ev_t, read_fields, event_fields):
 
 
 def _guard(off, kind, cus):
-    """the batch has more than twice as many reads of each class it is about as the largest grid has units for the class"""
+    """the batch has more than twice as many reads of each class it is about as the largest grid has units for the class (B.BLOCKS_PER_CU
+    is K11's cap, above K12's 2 and rl_launch's 5 a CU)"""
     n_short, n_long = B.class_counts(off)
     if kind in ('short', 'mixed'):
         assert n_short > 2 * B.BLOCKS_PER_CU * B.WAVES_PER_BLOCK * cus, (n_short, cus)
@@ -249,4 +253,73 @@ def test_calls_classify_takes_a_second_stride():
     _assert_gathered_bits(big, small, _t(b['idx']), _t(b['ev']), B.CALLS_READ_FIELDS, B.CALLS_EVENT_FIELDS)
     exp = B.calls_expected(3, 1, 2, 'int16')
     for f in B.CALLS_READ_FIELDS:
+        assert np.array_equal(big[f].cpu().numpy(), exp[f][b['idx']]), f
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ K13
+
+class _Llr:
+    def __init__(self, k, center, window, dtype):
+        self.k, self.center, self.window, self.dtype = k, center, window, dtype
+        self.d = B.llr_distinct(k, center, window, dtype)
+        self.det = _det()
+        self.models = [_t(self.d[f]) for f in ('mean', 'sd', 'alt_mean', 'alt_sd')]
+
+    def call(self, b, want=B.LLR_EVENT_FIELDS):
+        torch = _torch()
+        val, off, base = _t(b['val']), _t(b['off']), _t(b['base'])
+        nreads = off.numel() - 1
+        shapes = {w: (torch.float64, val.numel()) for w in want}
+        shapes.update(n_sites=(torch.int32, nreads), n_mod=(torch.int32, nreads), n_can=(torch.int32, nreads), status=(torch.uint8, nreads))
+        out = _filled(shapes)
+        res = self.det.read_llr(val, off, base, *self.models, self.k, self.center, window=self.window, thr=B.LLR_THR,
+                                prior_logit=B.LLR_PRIOR_LOGIT, want=want, out=out)
+        assert res is out
+        _assert_no_sentinel(res, shapes)
+        return res
+
+
+def _llr_case(kind, k, center, window, dtype, host=False):
+    c = _Llr(k, center, window, dtype)
+    b = _batch(c.d, kind, _cus())
+    small = c.call(c.d)
+    big = c.call(b)
+    _assert_gathered_bits(big, small, _t(b['idx']), _t(b['ev']), B.LLR_READ_FIELDS, B.LLR_EVENT_FIELDS)
+    got = {f: big[f].cpu().numpy() for f in B.LLR_READ_FIELDS + B.LLR_EVENT_FIELDS}
+    del big
+    TL._check_against(got, B.llr_gather(B.llr_expected(k, center, window, dtype), b['idx'], b['ev']))
+    if window == (0, 0):
+        assert TL._bits(got['llr_win']) == TL._bits(got['llr'])
+    if host:
+        m0, m1 = TL._models(c.d, k, center)
+        h = TL._engine().read_llr_host(b['val'], b['off'], b['base'], m0, m1, window=window, thr=B.LLR_THR, prior_logit=B.LLR_PRIOR_LOGIT)
+        for f in B.LLR_READ_FIELDS + B.LLR_EVENT_FIELDS:
+            assert h[f].dtype == got[f].dtype and TL._bits(h[f]) == TL._bits(got[f]), 'host entry: %s' % f
+
+
+@pytest.mark.parametrize('k,center,dtype', LLR_KD)
+@pytest.mark.parametrize('window', [(0, 0), (2, 0), (64, 64)])
+def test_llr_short_batch_beyond_the_grid(window, k, center, dtype):
+    _llr_case('short', k, center, window, dtype)
+
+
+@pytest.mark.parametrize('k,center,dtype', LLR_KD)
+@pytest.mark.parametrize('window', [(2, 0), (64, 64)])
+@pytest.mark.parametrize('kind', ['long', 'mixed'])
+def test_llr_long_and_mixed_batches_beyond_the_grid(kind, window, k, center, dtype):
+    _llr_case(kind, k, center, window, dtype)
+
+
+def test_llr_host_entry_on_the_mixed_batch():
+    _llr_case('mixed', 3, 1, (2, 0), 'int16', host=True)
+
+
+def test_llr_classify_takes_a_second_stride():
+    c = _Llr(3, 1, (2, 0), 'int16')
+    b = _batch(c.d, 'classify', _cus())
+    small = c.call(c.d)
+    big = c.call(b)
+    _assert_gathered_bits(big, small, _t(b['idx']), _t(b['ev']), B.LLR_READ_FIELDS, B.LLR_EVENT_FIELDS)
+    exp = B.llr_expected(3, 1, (2, 0), 'int16')
+    for f in B.LLR_READ_FIELDS:
         assert np.array_equal(big[f].cpu().numpy(), exp[f][b['idx']]), f
