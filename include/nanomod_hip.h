@@ -686,7 +686,8 @@ int nmod_site_calls(const nmod_params* prm, int64_t npos, const double* score, c
  * host offsets that decrease).
  * A read's bits depend on the read alone: not on the batch, the order of the reads, the memspace or the outputs asked for.  A read is
  * computed by one wave (up to NMOD_CALLS_WAVE_MAX events) or one workgroup.  No float atomics: the counts are integer reductions.
- * Stops here: two tables only; one window per call; no per-site prior; the k-mers of both tables must match. */
+ * Stops here: two tables only; one window per call; no per-site prior (nmod_site_stoich, K14, estimates the share per site from the
+ * window sums); the k-mers of both tables must match. */
 #define NMOD_LLR_MAX 1e300                 /* an event whose |llr| lies beyond is ineligible */
 typedef struct nmod_llr_opts { int32_t struct_size, nb_lo, nb_hi, reserved; double thr, prior_logit; } nmod_llr_opts;
 typedef struct nmod_llr_out { int32_t struct_size; int32_t reserved;
@@ -704,6 +705,69 @@ int nmod_read_llr(const nmod_params* prm, int64_t nreads, const int64_t* off, co
 typedef struct nmod_site_llr_out { int32_t struct_size; int32_t reserved; int32_t *n_valid, *n_mod, *n_can; double* frac; } nmod_site_llr_out;
 int nmod_site_llr(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */, double thr,
                   const nmod_site_llr_out* out);
+
+/* Per-position modified fraction by maximum likelihood, with a likelihood interval, a test of "nothing is modified here" and a posterior
+ * per read (K14; the reference project has no such step).  The rows are those of nmod_site_llr: per position the window sums L of the
+ * reads that cover it.  If a share pi of the molecules is modified, the log-likelihood of the row relative to "all canonical" is
+ *     l(pi) = sum_i log(1 - pi + pi e^{s_i}),
+ * concave on [0, 1]; nmod_site_llr's hard-call share is replaced by its maximiser.
+ *   Inputs, memspaces, the CSR / stride forms, the NULL and struct_size rules: exactly those of nmod_site_llr.
+ *   A score is VALID iff fabs(s) <= DBL_MAX; n = the number of valid scores of the row.  Per valid score, once:
+ *       t = -expm1(-fabs(s))   in [0, 1] (1 from |s| of about 37 on),   the side: s >= 0 ("plus", -0.0 included) or s < 0 ("minus").
+ *     An invalid score takes no part (it counts as t = 0).
+ *   One EVALUATION at pi, compiled with contraction off, per valid score with q = 1 - pi on the plus side and q = pi on the minus side:
+ *       qt = q * t,   u = t / (1 - qt),   S += u (plus) or -u (minus),   D += u * u,   g += log1p(-qt).
+ *     S(pi) is the score function dl/dpi (decreasing), -D its derivative, g the reduced log-likelihood: l(pi) = g(pi) + P with
+ *     P = the sum of the valid s >= 0.  A zero denominator (t = 1 at q = 1: the ends only) gives u = +inf and g = -inf, which is wanted.
+ *     No exp is evaluated inside an iteration and nothing overflows for any valid s.
+ *   The estimate pi^: 0 iff S(0) <= 0 (NMOD_STOICH_AT_ZERO); otherwise 1 iff S(1) >= 0 (NMOD_STOICH_AT_ONE); otherwise the root of S in
+ *     (0, 1) by the BRACKETED ITERATION below with F = S.
+ *   The bracketed iteration on a bracket (a, b): x = a + 0.5 (b - a); then for k = 1 .. max_iter:
+ *       evaluate at x;  the root lies right of x (a = x) or left of it (b = x) by the sign rule of the root in question;
+ *       x' = the Newton point of the root in question;  if x' != x and not (a < x' < b) with the new a, b:  x' = a + 0.5 (b - a)
+ *         (x' == x: the Newton step is below the spacing of doubles at x, or the function is exactly 0 there, and x stays);
+ *       step = |x' - x|;  x = x';  stop iff tol > 0 and (b - a <= tol or step <= tol).
+ *     The result is x: a point of a bracket that holds the root.  tol == 0 runs max_iter evaluations.  A root whose loop ends without
+ *     the stop test holding sets NMOD_STOICH_NOT_CONVERGED; the values are written all the same.
+ *       pi^:    right iff S(x) > 0;                       x' = x + S / D.
+ *       pi_lo:  right iff h(x) > ci_drop;                 x' = x + (h - ci_drop) / (2 S)      with h(x) = 2 (g(pi^) - g(x)).
+ *       pi_hi:  right iff h(x) <= ci_drop;                the same x'.
+ *     iters = the evaluations the iteration for pi^ made (0 at either end); max_iter bounds each of the three roots on its own.
+ *   l^ = 0 at pi^ = 0, else max(g(pi^) + P, 0);  stat = 2 l^ (>= 0; +inf when P overflows);
+ *   p_null = 1 at pi^ = 0, else max(0.5 erfc(sqrt(l^)), DBL_MIN): the 1/2 chi2_0 + 1/2 chi2_1 boundary law of the likelihood-ratio test of
+ *     pi = 0.  It is ASYMPTOTIC, assumes that both tables are right and the reads independent, and is conservative when the two levels
+ *     are well separated (a simulation of canonical rows of 20 and 200 reads rejected 2.5 - 4.8 % at the 5 % level: tests/test_site_stoich.py).
+ *   The interval {pi : h(pi) <= ci_drop} (the P terms cancel: no inf - inf): pi_lo = 0 iff h(0) <= ci_drop, else the root in (0, pi^);
+ *     pi_hi = 1 iff h(1) <= ci_drop, else the root in (pi^, 1).  ci_drop = 3.841458820694124 (the 0.95 quantile of chi2_1) is the
+ *     default of the Python layers.
+ *   resp (optional, float64, in the score layout): the posterior of every read at pi^, with e = exp(-fabs(s)):
+ *       0 at pi^ = 0;  1 at pi^ = 1;  else  s >= 0: pi^ / (pi^ + (1 - pi^) e),   s < 0: (pi^ e) / ((1 - pi^) + pi^ e);
+ *     NaN for an invalid score and for every score of a row without an estimate.
+ *   Outputs (npos each; a NULL member is skipped; requesting fewer never changes the bits of the others): doubles pi, pi_lo, pi_hi, stat,
+ *     p_null; int32 n_valid, iters; uint8 status; and resp.  Status bits:
+ *       NMOD_STOICH_TOO_FEW        n < min_valid: NaN outputs, iters 0 (n_valid is written)
+ *       NMOD_STOICH_FLAT           every valid score is 0, S is 0 everywhere and pi is not identified: NaN outputs, iters 0
+ *       NMOD_STOICH_NOT_CONVERGED  see above
+ *       NMOD_STOICH_AT_ZERO, NMOD_STOICH_AT_ONE    pi^ = 0, pi^ = 1
+ *       NMOD_STOICH_TOO_LARGE      a row beyond NMOD_MAX_DEEP scores: NaN outputs, n_valid 0, iters 0
+ * Sums: a fixed-order chain per lane (the lane's scores in ascending index), then fixed-order lane, wave and LDS reductions; no float
+ * atomics.  A row of up to NMOD_STOICH_SMALL scores is computed by 16 lanes, up to NMOD_STOICH_WAVE by a wave, a longer one by a workgroup:
+ * a row's bits depend on the row alone, not on the batch, the order of the rows, CSR versus stride, the memspace or the outputs asked for.
+ * Reads struct_size, device, stream, memspace, stride0 of prm.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and
+ * no synchronisation; scratch (12 bytes per row) comes stream-ordered from the library's pool.  npos == 0 is NMOD_OK.
+ * NMOD_ERR_INVALID_ARG before any device work: opts NULL or of another struct_size, max_iter outside 1 .. 200, min_valid < 1, tol not
+ * finite or < 0, ci_drop not finite or <= 0, and nmod_site_llr's rules for prm, npos, score, off / stride0 and out.
+ * Stops here: two states only; the reads are treated as independent; the strands are not pooled; no prior on pi. */
+#define NMOD_STOICH_SMALL 256              /* scores of a row up to which 16 lanes compute it */
+#define NMOD_STOICH_WAVE 1024              /* ... up to which one wave does (a workgroup beyond) */
+enum { NMOD_STOICH_TOO_FEW = 1, NMOD_STOICH_FLAT = 2, NMOD_STOICH_NOT_CONVERGED = 4, NMOD_STOICH_AT_ZERO = 8, NMOD_STOICH_AT_ONE = 16,
+       NMOD_STOICH_TOO_LARGE = 32 };
+typedef struct nmod_stoich_opts { int32_t struct_size, max_iter, min_valid, reserved; double tol, ci_drop; } nmod_stoich_opts;
+typedef struct nmod_stoich_out { int32_t struct_size; int32_t reserved;
+  double *pi, *pi_lo, *pi_hi, *stat, *p_null; int32_t *n_valid, *iters; uint8_t* status; /* npos each */
+  double* resp;                                                                            /* one per score, in its layout */ } nmod_stoich_out;
+int nmod_site_stoich(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */,
+                     const nmod_stoich_opts* opts, const nmod_stoich_out* out);
 
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One

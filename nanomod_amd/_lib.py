@@ -209,6 +209,34 @@ make_llr_out = functools.partial(make_out, NmodLlrOut)
 make_site_llr_out = functools.partial(make_out, NmodSiteLlrOut)
 
 
+STOICH_TOO_FEW, STOICH_FLAT, STOICH_NOT_CONVERGED, STOICH_AT_ZERO, STOICH_AT_ONE, STOICH_TOO_LARGE = 1, 2, 4, 8, 16, 32
+STOICH_NO_ESTIMATE = STOICH_TOO_FEW | STOICH_FLAT | STOICH_TOO_LARGE
+STOICH_SMALL, STOICH_WAVE = 256, 1024     # nmod_site_stoich: scores of a row up to which 16 lanes / one wave compute it (a workgroup beyond)
+STOICH_MAX_ITER = 200
+STOICH_CI_DROP_95 = 3.841458820694124     # the 0.95 quantile of chi2_1
+STOICH_FIELDS = ('pi', 'pi_lo', 'pi_hi', 'stat', 'p_null')
+STOICH_INT_FIELDS = ('n_valid', 'iters')
+
+
+class NmodStoichOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'max_iter', 'min_valid', 'reserved')] + [('tol', C.c_double), ('ci_drop', C.c_double)]
+
+
+class NmodStoichOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + \
+               [(n, C.c_void_p) for n in STOICH_FIELDS + STOICH_INT_FIELDS + ('status', 'resp')]
+
+
+def make_stoich_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP_95):
+    o = NmodStoichOpts()
+    o.struct_size = C.sizeof(NmodStoichOpts)
+    o.max_iter, o.min_valid, o.tol, o.ci_drop = int(max_iter), int(min_valid), float(tol), float(ci_drop)
+    return o
+
+
+make_stoich_out = functools.partial(make_out, NmodStoichOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -272,6 +300,7 @@ _SIGNATURES = {
     'nmod_read_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
                                 C.POINTER(NmodRescaleModel), C.POINTER(NmodLlrOpts), C.POINTER(NmodLlrOut)]),
     'nmod_site_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteLlrOut)]),
+    'nmod_site_stoich': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NmodStoichOpts), C.POINTER(NmodStoichOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

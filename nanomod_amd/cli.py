@@ -165,6 +165,11 @@ def build_parser():
     rl.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
     rl.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first (the "
                     "fit of 'rescale' with its defaults, on the device)")
+    rl.add_argument('--siteFraction', type=int, default=0, choices=[0, 1], help='1: also estimate the modified share of every position '
+                    'by maximum likelihood over all its window sums, with an interval and a test of "nothing is modified" '
+                    '(<FileID>_site_stoich.txt)')
+    rl.add_argument('--minValid', type=int, default=3, help='--siteFraction: scored reads a position needs for an estimate, > 0')
+    rl.add_argument('--ciLevel', type=float, default=0.95, help='--siteFraction: the level of the likelihood interval, inside (0, 1)')
     rl.add_argument('--outEvents', default='', help='optional: a .npz file for the per-event tracks llr, llr_win, p_mod (with off)')
     rl.add_argument('--outFolder', default='mRes')
     rl.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_llr.txt and <FileID>_site_llr.txt')
@@ -194,6 +199,10 @@ def validate_readllr(a):
         errs.append('Error: --prior should lie between 0 and 1, both excluded')
     if a.minPositions < 1:
         errs.append('Error: --minPositions should be larger than 0')
+    if a.minValid < 1:
+        errs.append('Error: --minValid should be larger than 0')
+    if not 0.0 < a.ciLevel < 1.0:
+        errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
     for f in (a.wrkBase1, a.kmerModel, a.altModel):
         if not os.path.isfile(f):
             errs.append('Error: input %s does not exist' % f)
@@ -209,11 +218,14 @@ def run_readllr(a, log=print):
     res = readllr.call_reads_llr(reads, kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                  window=parse_llr_window(a.llrWindow), thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions,
                                  rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device,
-                                 log=(lambda *x: None) if quiet else log)
+                                 log=(lambda *x: None) if quiet else log,
+                                 **(dict(stoich=dict(min_valid=a.minValid, ci_level=a.ciLevel)) if a.siteFraction else {}))
     table, sites = res[0], res[1]
     os.makedirs(a.outFolder, exist_ok=True)
     readllr.write_read_llr(os.path.join(a.outFolder, a.FileID + '_read_llr.txt'), table)
     readllr.write_site_llr(os.path.join(a.outFolder, a.FileID + '_site_llr.txt'), sites)
+    if a.siteFraction:
+        readllr.write_site_stoich(os.path.join(a.outFolder, a.FileID + '_site_stoich.txt'), sites)
     if a.outEvents:
         np.savez(a.outEvents, off=np.asarray(reads['off'], dtype=np.int64), **res[2])
     if not quiet:

@@ -24,6 +24,29 @@ __device__ __forceinline__ bool group_any(bool f, int lane) {
   else return ((b >> (lane & 48)) & 0xFFFFull) != 0ull;
 }
 
+// sum over the G lanes of the caller's group (a row of 16, or the wave), the same bits in every lane of it (every step adds the
+// two halves in both orders).  Reached by whole waves.
+template <int G>
+__device__ __forceinline__ double group_sum_f64(double v) {
+  if constexpr (G == 64) {
+    return wave_sum_f64(v);
+  } else {
+    static_assert(G == 16, "group_sum_f64: a row or the wave");
+    auto step = [](double x, auto tag) {
+      constexpr int C = decltype(tag)::value;
+      long long b = __double_as_longlong(x);
+      int lo = dpp_i<C>(0, (int)(unsigned)b);
+      int hi = dpp_i<C>(0, (int)(unsigned)((unsigned long long)b >> 32));
+      return x + __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+    };
+    v = step(v, std::integral_constant<int, NMOD_QP(1, 0, 3, 2)>{});
+    v = step(v, std::integral_constant<int, NMOD_QP(2, 3, 0, 1)>{});
+    v = step(v, std::integral_constant<int, kDppRowHalfMirror>{});
+    v = step(v, std::integral_constant<int, kDppRowMirror>{});
+    return v;
+  }
+}
+
 // Appends i to the work list of its class (cls < 0: to none): the lanes of a class are ballot-compacted, one atomic per wave
 // and class on the class's count word.  Reached by whole waves.
 template <int NC>

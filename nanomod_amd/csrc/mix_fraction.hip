@@ -89,28 +89,6 @@ __global__ __launch_bounds__(256) void mix_classify_kernel(MixArgs a) {
   }
 }
 
-// sum over the G lanes of a group, the same bits in every lane of it (every step adds the two halves in both orders)
-template <int G>
-__device__ __forceinline__ double mix_group_sum(double v) {
-  if constexpr (G == 64) {
-    return wave_sum_f64(v);
-  } else {
-    static_assert(G == 16, "mix_group_sum: a row or the wave");
-    auto step = [](double x, auto tag) {
-      constexpr int C = decltype(tag)::value;
-      long long b = __double_as_longlong(x);
-      int lo = dpp_i<C>(0, (int)(unsigned)b);
-      int hi = dpp_i<C>(0, (int)(unsigned)((unsigned long long)b >> 32));
-      return x + __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-    };
-    v = step(v, std::integral_constant<int, NMOD_QP(1, 0, 3, 2)>{});
-    v = step(v, std::integral_constant<int, NMOD_QP(2, 3, 0, 1)>{});
-    v = step(v, std::integral_constant<int, kDppRowHalfMirror>{});
-    v = step(v, std::integral_constant<int, kDppRowMirror>{});
-    return v;
-  }
-}
-
 // softplus(x) = ln(1 + e^x) without overflow
 __device__ __forceinline__ double mix_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
@@ -142,13 +120,13 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
       varies |= x != x0;
       acc += x;
     }
-    const double mu = mix_group_sum<G>(acc) / (double)rn;
+    const double mu = group_sum_f64<G>(acc) / (double)rn;
     acc = 0.0;
     for (int64_t k = gl; k < rn; k += G) {
       const double dx = mix_load<DT>(a.r, rb + k) - mu;
       acc += dx * dx;
     }
-    const double s2 = mix_group_sum<G>(acc) / (double)rn;
+    const double s2 = group_sum_f64<G>(acc) / (double)rn;
     // Y: loaded once
     double y[kMixPer];
     const int ny = (int)yn;
@@ -160,7 +138,7 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
       bad |= !isfinite(y[j]);
       acc += y[j];
     }
-    const double d = mix_group_sum<G>(acc) / (double)yn - mu;
+    const double d = group_sum_f64<G>(acc) / (double)yn - mu;
     bad = group_any<G>(bad, lane);
     varies = group_any<G>(varies, lane);                 // a constant reference group has s2 == 0 whatever its sums round to
     bool degenerate = !have || bad || !varies || !(s2 > 0.0);
@@ -185,8 +163,8 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
         sy += r * y[j];
         if constexpr (MODEL == NMOD_MIX_FREE_VAR) rr[j] = r;
       }
-      sr = mix_group_sum<G>(sr);
-      sy = mix_group_sum<G>(sy);
+      sr = group_sum_f64<G>(sr);
+      sy = group_sum_f64<G>(sy);
       const double pn = sr / dn, mn = sy / sr;
       double vn = v;
       bool fl = false;
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
           const double e = y[j] - mn;
           sq += rr[j] * (e * e);
         }
-        vn = mix_group_sum<G>(sq) / sr;
+        vn = group_sum_f64<G>(sq) / sr;
         fl = vn < vfloor;
         if (fl) vn = vfloor;
       }
@@ -228,7 +206,7 @@ __global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
       ll += idx < ny ? l1 + mix_softplus(-t) : 0.0;
       if (resp && have && idx < ny) resp[yb + idx] = degenerate ? __int_as_float(0x7FC00000) : (float)(1.0 / (1.0 + exp(t)));
     }
-    ll = 2.0 * mix_group_sum<G>(ll);
+    ll = 2.0 * group_sum_f64<G>(ll);
     if (have && gl == 0) {
       if (degenerate) {
         mix_write_nan(a.out, pos, NMOD_MIX_DEGENERATE);

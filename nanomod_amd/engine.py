@@ -724,6 +724,53 @@ def site_llr_host(score, off, *, stride=0, thr=2.5, device=0):
     return res
 
 
+def _stoich_opts(min_valid, ci_level, max_iter, tol):
+    """nmod_stoich_opts from the Python arguments; ValueError for what the C entry refuses.  ci_level in (0, 1) becomes the drop of
+    2 l that bounds the interval: the ci_level quantile of chi2_1, the square of a normal quantile"""
+    import math
+    from statistics import NormalDist
+    if int(min_valid) != min_valid or int(min_valid) < 1:
+        raise ValueError('min_valid must be an integer >= 1, not %r' % (min_valid,))
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= L.STOICH_MAX_ITER:
+        raise ValueError('max_iter must be an integer in 1 .. %d, not %r' % (L.STOICH_MAX_ITER, max_iter))
+    tol, ci_level = float(tol), float(ci_level)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError('tol must be finite and >= 0, not %r' % (tol,))
+    if not 0.0 < ci_level < 1.0:
+        raise ValueError('ci_level must lie inside (0, 1), not %r' % (ci_level,))
+    ci_drop = NormalDist().inv_cdf((1.0 + ci_level) / 2.0) ** 2
+    if not (math.isfinite(ci_drop) and ci_drop > 0.0):
+        raise ValueError('ci_level %r gives no usable interval' % (ci_level,))
+    return L.make_stoich_opts(int(max_iter), int(min_valid), tol, ci_drop)
+
+
+def _stoich_shapes(npos, nresp=None):
+    shapes = dict({k: ('float64', npos) for k in L.STOICH_FIELDS}, n_valid=('int32', npos), iters=('int32', npos), status=('uint8', npos))
+    if nresp is not None:
+        shapes['resp'] = ('float64', nresp)
+    return shapes
+
+
+def site_stoich_host(score, off, *, stride=0, min_valid=3, ci_level=0.95, max_iter=60, tol=1e-12, resp=False, device=0):
+    """Per-position modified fraction by maximum likelihood over pivoted window sums (nmod_site_stoich, include/nanomod_hip.h): score
+    float64, one row per position by `off` (int64[npos + 1]) or, with off None, a fixed `stride`.  Returns a dict of numpy arrays: pi
+    (the estimate), pi_lo, pi_hi (the likelihood interval at ci_level), stat (twice the log-likelihood ratio against pi = 0) and p_null
+    (its asymptotic boundary p-value), float64; n_valid, iters (int32); status (uint8, L.STOICH_* bits); and with `resp` the posterior
+    of every read at the estimate (float64, in the score layout)."""
+    lib = L.load()
+    opts = _stoich_opts(min_valid, ci_level, max_iter, tol)
+    score, off, stride, npos = _host_score_rows(score, off, stride)
+    shapes = _stoich_shapes(npos, score.shape[0] if resp else None)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodStoichOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
+    _call(lib, 'nmod_site_stoich', prm, npos, _np_ptr(score), _np_ptr(off), C.byref(opts), C.byref(out))
+    if resp and npos and off is not None and off[0] > 0:
+        res['resp'][:off[0]] = np.nan                               # scores before the first row belong to no row
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1116,6 +1163,26 @@ class DeviceDetector:
         o = L.make_out(L.NmodSiteLlrOut, **{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
         _call(self.lib, 'nmod_site_llr', prm, npos, score.data_ptr(), _ptr(off), thr, C.byref(o))
+        return res
+
+    def site_stoich(self, score, *, off=None, stride=0, npos=None, min_valid=3, ci_level=0.95, max_iter=60, tol=1e-12, resp=False, out=None):
+        """Per-position modified fraction by maximum likelihood over pivoted window sums (nmod_site_stoich, NMOD_MEM_DEVICE) on the
+        current stream, nothing read back: score a float64 CUDA vector, rows by `off` (int64 CUDA vector) or a fixed `stride`.  Returns
+        a dict of CUDA tensors pi, pi_lo, pi_hi, stat, p_null (float64), n_valid, iters (int32), status (uint8, L.STOICH_* bits) and
+        with `resp` the posterior of every read (float64, in the score layout; a score outside every row keeps NaN).  p_null is a
+        track fdr() takes as it is:
+
+            st = det.site_stoich(piv['sig'], off=piv['off'])
+            (q,), summary = det.fdr(st, tracks=('p_null',))
+        """
+        opts = _stoich_opts(min_valid, ci_level, max_iter, tol)
+        stride, npos = self._score_rows('site_stoich', score, off, stride, npos)
+        shapes = _stoich_shapes(npos, score.numel() if resp else None)
+        given = {'resp': self.torch.full((score.numel(),), float('nan'), dtype=self.torch.float64, device=self._dev)} if resp and out is None else None
+        res = self._outputs(out, shapes, 'site_stoich', given=given)
+        o = L.make_out(L.NmodStoichOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
+        _call(self.lib, 'nmod_site_stoich', prm, npos, score.data_ptr(), _ptr(off), C.byref(opts), C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

@@ -25,8 +25,11 @@ from . import rescale as _rescale
 from .readcalls import _RESCALE_KEYS
 
 
+_STOICH_KEYS = ('min_valid', 'ci_level', 'max_iter', 'tol')
+
+
 def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None, events=False, device=0,
-                   log=print):
+                   log=print, stoich=None):
     """Call the events of a read-level set (container.READ_FIELDS) between an unmodified and a modified k-mer model
     (kmermodel.KMER_MODEL_FIELDS, one k and center).  window: 'kmer' (the events whose k-mer holds the base) or (lo, hi) events of the
     same read before and after; thr: the window sum from which an event is called; prior: the prior probability of the modified state
@@ -37,6 +40,9 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
       and, when rescaled, shift, scale, rescale_status;
     sites: one entry per covered position in the reference's row order: chrom, strand, pos, base, n_reads (the events there), n_valid
       (the scored ones), n_mod, n_can, frac = n_mod / (n_mod + n_can) (NaN without a confident read).
+    stoich: None, or a dict of engine.site_stoich_host's options (min_valid, ci_level, max_iter, tol; {} for the defaults): the
+      modified share of every position by maximum likelihood over all its window sums (K14, nmod_site_stoich) on the same stream;
+      `sites` gains pi, pi_lo, pi_hi, stat, p_null (float64), iters (int32) and stoich_status (uint8, L.STOICH_* bits).
     One summary line goes to `log`."""
     import torch
     m0 = _rescale.masked_model(model, min_positions)
@@ -53,6 +59,11 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
         if unknown:
             raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
     opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    if stoich is not None:
+        unknown = sorted(set(stoich) - set(_STOICH_KEYS))
+        if unknown:
+            raise ValueError('stoich: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_STOICH_KEYS)))
+        engine._stoich_opts(*(stoich.get(key, default) for key, default in zip(_STOICH_KEYS, (3, 0.95, 60, 1e-12))))
     val = np.ascontiguousarray(reads['norm_mean'])
     if val.dtype not in (np.float32, np.int16, np.float64):
         raise ValueError('reads: norm_mean must be float32, int16 (milli-units) or float64')
@@ -78,6 +89,7 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
                          prior_logit=prior_logit, want=want)
     piv = engine.pivot_reads(reads, device, val=calls['llr_win'])
     counts = det.site_llr(piv['sig'], off=piv['off'], thr=thr)
+    share = det.site_stoich(piv['sig'], off=piv['off'], **stoich) if stoich is not None else None
 
     table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
                  start=np.asarray(reads['start'], dtype=np.int64), events=np.diff(off),
@@ -90,11 +102,16 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
     sites = dict(chrom=names[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
                  pos=key & ((1 << 40) - 1), base=piv['base'].cpu().numpy().view('S1').astype('U1'), n_reads=np.diff(row_off).astype(np.int32),
                  **{f: counts[f].cpu().numpy() for f in L.SITE_LLR_FIELDS})
+    clause = ''
+    if share is not None:
+        sites.update({f: share[f].cpu().numpy() for f in L.STOICH_FIELDS + ('iters',)}, stoich_status=share['status'].cpu().numpy())
+        clause = '; %d position(s) with a modified share, %d of them with an interval above 0' % (
+            int(((sites['stoich_status'] & L.STOICH_NO_ESTIMATE) == 0).sum()), int((sites['pi_lo'] > 0.0).sum()))
     log('readllr: %d read(s), %d of %d event(s) scored, %d modified and %d canonical at threshold %g over %d + 1 + %d event(s); '
-        '%d position(s), %d with a modified call%s'
+        '%d position(s), %d with a modified call%s%s'
         % (nreads, int(table['n_sites'].sum()), len(val), int(table['n_mod'].sum()), int(table['n_can'].sum()), float(thr), opts.nb_lo, opts.nb_hi,
            len(key), int((sites['n_mod'] > 0).sum()),
-           '' if fit is None else '; %d read(s) not rescaled' % int(((table['rescale_status'] & L.RESCALE_FAILED) != 0).sum())))
+           '' if fit is None else '; %d read(s) not rescaled' % int(((table['rescale_status'] & L.RESCALE_FAILED) != 0).sum()), clause))
     if events:
         return table, sites, {f: calls[f].cpu().numpy() for f in L.LLR_EVENT_FIELDS}
     return table, sites
@@ -116,3 +133,15 @@ def write_site_llr(path, sites):
            [np.asarray(sites[f]).tolist() for f in ('n_reads', 'n_valid', 'n_mod', 'n_can', 'frac')]
     with open(path, 'w') as f:
         f.writelines('%s %s %d %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
+
+
+def write_site_stoich(path, sites):
+    """<FileID>_site_stoich.txt: per position 'chrom strand pos+1 base n_reads n_valid pi pi_lo pi_hi stat p_null status' as
+    '%s %s %d %s %d %d %.6f %.6f %.6f %.3f %.3E %d' (the position 1-based; 'nan' as Python spells it where the position has no
+    estimate; `sites` of call_reads_llr(..., stoich=...))"""
+    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
+            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
+           [np.asarray(sites[f]).tolist() for f in ('n_reads', 'n_valid', 'pi', 'pi_lo', 'pi_hi', 'stat')] + \
+           [['%.3E' % p if p == p else 'nan' for p in np.asarray(sites['p_null']).tolist()], np.asarray(sites['stoich_status']).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %s %d %d %.6f %.6f %.6f %.3f %s %d\n' % row for row in zip(*cols))
