@@ -1,12 +1,13 @@
 // The host half that the library's C entry points share: error recording, the checks of nmod_params, device selection with
-// the cached CU count, the small size helpers, and the slab of a call with its host-memspace staging.  (The device-side
-// helpers the K8 / K9 / K10 kernels share are in entry_device.hpp.)
+// the cached CU count, the small size helpers, the dtype dispatcher, the slab of a call with its host-memspace staging, rows_begin and
+// launches_end.  (Device-side helpers of K8 .. K14 and the q-values: entry_device.hpp; the walks: pos_walk.hpp, read_walk.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/nanomod_hip.h"
 #include "scratch_pool.hpp"
@@ -73,6 +74,14 @@ inline int select_device(const nmod_params* prm, int* num_cus) {
   return NMOD_OK;
 }
 
+// f(std::integral_constant<int, DT>) for the DT of a checked dtype: the one place a run-time dtype picks a template instance
+template <class F>
+inline auto for_dtype(int32_t dtype, F f) {
+  if (dtype == NMOD_DTYPE_F32) return f(std::integral_constant<int, NMOD_DTYPE_F32>{});
+  if (dtype == NMOD_DTYPE_I16_MILLI) return f(std::integral_constant<int, NMOD_DTYPE_I16_MILLI>{});
+  return f(std::integral_constant<int, NMOD_DTYPE_F64>{});
+}
+
 // blocks of a persistent launch: one per `per_block` items of work, at least 1 and at most `cap`
 inline unsigned persistent_grid(int64_t work, int64_t per_block, int64_t cap) {
   const int64_t b = (work + per_block - 1) / per_block;
@@ -126,5 +135,18 @@ struct Slab {
     staged[n++] = Staged{ref, host_ptr, take(b + tail), b, download};
   }
 };
+
+// After an entry's own checks: the offsets of a host call, then the device.  NMOD_OK with no rows: there is nothing to do
+inline int rows_begin(const nmod_params* prm, int64_t nrows, const int64_t* off, int* num_cus) {
+  if (prm->memspace == NMOD_MEM_HOST && off && nrows > 0 && !csr_offsets_ok(off, nrows)) return NMOD_ERR_INVALID_ARG;
+  if (nrows == 0) return NMOD_OK;
+  return select_device(prm, num_cus);
+}
+// the end of an entry: what the launches left behind, the downloads of a host call, the slab
+inline int launches_end(Slab& slab, hipStream_t stream) {
+  NMOD_HIP(hipGetLastError());
+  NMOD_HIP(slab.finish(stream));
+  return NMOD_OK;
+}
 
 }  // namespace nmod

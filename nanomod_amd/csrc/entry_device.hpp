@@ -1,5 +1,5 @@
-// Device-side helpers that the per-position kernels of K8 / K9 / K10 and the q-value kernels share (their host half:
-// entry_common.hpp).
+// Device-side helpers that the per-position kernels (K8, K9, K10, K14), the per-read kernels (K11 .. K13) and the q-value kernels share
+// (their host half: entry_common.hpp; the classed position walk: pos_walk.hpp; the read walk: read_walk.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -32,6 +32,7 @@
 #include "entry_common.hpp"
 #include "entry_device.hpp"
 #include "radix_sort.hpp"
+#include "special_math.hpp"
 
 namespace nmod {
 
@@ -42,7 +43,6 @@ constexpr int kKmVec = 8;                         // int16 samples per lane and 
 constexpr int kKmStep = 64 * kKmVec;              // samples per wave and step
 constexpr int kKmLdsCodes = 4096;                 // the table lives in LDS up to here: 28 bytes per code = 112 KiB
 constexpr int kKmLdsBytesPerCode = 28;            // S1, S2 (64-bit), N, positions, clipped (32-bit)
-constexpr double kKmDblMax = 1.7976931348623157e308;
 
 struct KmArgs {
   const void* sig; const int64_t* off; int64_t stride; const int32_t* code;
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) void km_moments_kernel(KmArgs a) {
       double sum = 0.0;
       for (int64_t k = lane; k < n; k += 64) {
         const double x = km_load<DT>(a.sig, b + k);
-        bad |= !(fabs(x) <= kKmDblMax);
+        bad |= !(fabs(x) <= kDblMax);
         const bool in = !clip || (lo <= x && x <= hi);
         sum += in ? x : 0.0;
         nk += in ? 1u : 0u;
@@ -564,7 +564,5 @@ extern "C" int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void*
     hipLaunchKernelGGL(km_combine_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, a,
                        (const uint64_t*)(in_tmp ? key_tmp : a.key), (const uint32_t*)(in_tmp ? val_tmp : a.val));
   }
-  NMOD_HIP(hipGetLastError());
-  NMOD_HIP(slab.finish(stream));
-  return NMOD_OK;
+  return launches_end(slab, stream);
 }

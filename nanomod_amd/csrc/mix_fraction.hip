@@ -2,14 +2,15 @@
 // The reference has no such step; the definition is the one in include/nanomod_hip.h (tests/mix_ref.py restates it in numpy).
 // One group is the reference group R (its mean mu and variance s2 are fixed), the other the mixed group Y:
 //   y ~ (1 - pi) N(mu, s2) + pi N(m, v).  All on the caller's stream:
-//   mix_classify_kernel     a thread per position: the gate, the size checks, and the position's class by |Y|; the indices of the
-//                           positions to compute are ballot-compacted into one list per class (one atomic per wave and class on a
-//                           device count word); skipped / degenerate-by-size / too-large positions get their outputs here
+//   pos_classify_kernel<MixRule>  (pos_walk.hpp) a thread per position: the gate, the size checks, and the position's class by |Y|,
+//                           ballot-compacted into one list per class (one atomic per wave and class on a device count word);
+//                           skipped / degenerate-by-size / too-large positions get their outputs here
 //   mix_em_kernel<16>       |Y| <= 256: 16 lanes x 16 doubles hold a position's Y in registers over all iterations, four positions
 //                           per wave, DPP row sums only; a finished position freezes while the others of its wave go on
 //   mix_em_kernel<64>       |Y| <= 1 024: the whole wave x 16 doubles
 //   mix_stream_kernel       beyond: a workgroup per position re-reads Y every iteration (L2-resident up to 65 535 float32
 //                           samples), partial sums through LDS in a fixed order; up to NMOD_MAX_DEEP
+// The EM itself is written once (mix_estimate) over two row policies, MixRegRow<G> and MixBlockRow, which supply the sums over Y.
 // The EM grids are persistent and read their list's length from the device: no host read anywhere.  Every sum is a fixed-order
 // chain per lane followed by a fixed-order lane / wave reduction, no atomics: a position's numbers do not depend on the other
 // positions of the batch, on the list order the atomics happened to give, or on CSR versus stride.
@@ -19,8 +20,7 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
-#include "entry_common.hpp"
-#include "entry_device.hpp"
+#include "pos_walk.hpp"
 
 namespace nmod {
 
@@ -38,7 +38,7 @@ struct MixArgs {
   int max_iter; double tol;
   const double* gate; double gate_max;
   nmod_mix_out out;
-  uint32_t* list[3]; uint32_t* count;                        // per class: indices of the positions to compute, their number
+  PosLists<3> pl;                                            // per class: indices of the positions to compute, their number
 };
 
 template <int DT>
@@ -58,290 +58,221 @@ __device__ __forceinline__ void mix_write_nan(const nmod_mix_out& o, int64_t i, 
   if (o.status) o.status[i] = (uint8_t)status;
 }
 
-__global__ __launch_bounds__(256) void mix_classify_kernel(MixArgs a) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.npos; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + threadIdx.x;
-    const bool in = i < a.npos;
-    int cls = -1;
-    int64_t yb = 0, yn = 0;
-    if (in) {
-      int64_t rb, rn;
-      csr_row(a.roff, a.rstride, i, rb, rn);
-      csr_row(a.yoff, a.ystride, i, yb, yn);
-      unsigned st = 0;
-      if (a.gate && !(a.gate[i] <= a.gate_max)) st = NMOD_MIX_SKIPPED;                 // NaN compares false: skipped
-      else if (rn > NMOD_MAX_DEEP || yn > NMOD_MAX_DEEP) st = NMOD_MIX_TOO_LARGE;
-      else if (rn < 2 || yn < 2) st = NMOD_MIX_DEGENERATE;
-      else cls = yn <= kMixSmall ? 0 : (yn <= kMixWave ? 1 : 2);
-      if (cls < 0) mix_write_nan(a.out, i, st);
-    }
-    compact_to_lists<3>(cls, lane, a.list, a.count, i);
-    if (a.out.resp) {                                       // the reads of the positions left out: NaN, a wave per row
-      unsigned long long mask = __ballot(in && cls < 0);
-      while (mask) {
-        const int src = __ffsll((long long)mask) - 1;
-        mask &= mask - 1ull;
-        const int64_t b = __shfl((long long)yb, src), n = __shfl((long long)yn, src);
-        for (int64_t k = lane; k < n; k += 64) a.out.resp[b + k] = __int_as_float(0x7FC00000);
-      }
-    }
+// the class of position i by |Y|; the gate and the size checks leave a position out (the resp of its reads: NaN, by the classify kernel)
+struct MixRule {
+  static constexpr int NC = 3;
+  using Track = float;
+  static __device__ __forceinline__ float* track(const MixArgs& a) { return a.out.resp; }
+  static __device__ __forceinline__ int cls(const MixArgs& a, int64_t i, int64_t& yb, int64_t& yn) {
+    int64_t rb, rn;
+    csr_row(a.roff, a.rstride, i, rb, rn);
+    csr_row(a.yoff, a.ystride, i, yb, yn);
+    unsigned st;
+    if (a.gate && !(a.gate[i] <= a.gate_max)) st = NMOD_MIX_SKIPPED;                   // NaN compares false: skipped
+    else if (rn > NMOD_MAX_DEEP || yn > NMOD_MAX_DEEP) st = NMOD_MIX_TOO_LARGE;
+    else if (rn < 2 || yn < 2) st = NMOD_MIX_DEGENERATE;
+    else return yn <= kMixSmall ? 0 : (yn <= kMixWave ? 1 : 2);
+    mix_write_nan(a.out, i, st);
+    return -1;
   }
-}
+};
 
 // softplus(x) = ln(1 + e^x) without overflow
 __device__ __forceinline__ double mix_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
 
-// The register-resident form: a group of G lanes per position, lane g of it keeps y[g + G j], j < 16.  Everything between the
-// loads and the stores runs with all lanes on (a group without a position, or a finished one, computes and does not commit),
-// so the DPP sums always see a full row.
-template <int G, int DT, int MODEL>
-__global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
-  constexpr int CLS = G == 16 ? 0 : 1;
-  constexpr int GPB = kMixThreads / G;
-  const int64_t cnt = (int64_t)a.count[CLS];
-  const int lane = threadIdx.x & 63, gl = threadIdx.x & (G - 1), gidx = threadIdx.x / G;
-  for (int64_t w0 = (int64_t)blockIdx.x * GPB; w0 < cnt; w0 += (int64_t)gridDim.x * GPB) {
-    const int64_t w = w0 + gidx;
-    const bool have = w < cnt;
-    int64_t pos = 0, yb = 0, yn = 0, rb = 0, rn = 0;
-    if (have) {
-      pos = (int64_t)a.list[CLS][w];
-      csr_row(a.yoff, a.ystride, pos, yb, yn);
-      csr_row(a.roff, a.rstride, pos, rb, rn);
-    }
-    // R: two passes, mean then the squares about it
-    bool bad = false, varies = false;
-    const double x0 = rn > 0 ? mix_load<DT>(a.r, rb) : 0.0;
-    double acc = 0.0;
-    for (int64_t k = gl; k < rn; k += G) {
-      const double x = mix_load<DT>(a.r, rb + k);
-      bad |= !isfinite(x);
-      varies |= x != x0;
-      acc += x;
-    }
-    const double mu = group_sum_f64<G>(acc) / (double)rn;
-    acc = 0.0;
-    for (int64_t k = gl; k < rn; k += G) {
-      const double dx = mix_load<DT>(a.r, rb + k) - mu;
-      acc += dx * dx;
-    }
-    const double s2 = group_sum_f64<G>(acc) / (double)rn;
-    // Y: loaded once
-    double y[kMixPer];
-    const int ny = (int)yn;
-    acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < kMixPer; ++j) {
-      const int idx = gl + G * j;
-      y[j] = idx < ny ? mix_load<DT>(a.y, yb + idx) : 0.0;
-      bad |= !isfinite(y[j]);
-      acc += y[j];
-    }
-    const double d = group_sum_f64<G>(acc) / (double)yn - mu;
-    bad = group_any<G>(bad, lane);
-    varies = group_any<G>(varies, lane);                 // a constant reference group has s2 == 0 whatever its sums round to
-    bool degenerate = !have || bad || !varies || !(s2 > 0.0);
+// the parameters of one evaluation; t(y) = ln of the ratio of y's weighted densities, reference component over modified
+struct MixAt {
+  double c0, m, mu, hv, hs;
+  __device__ __forceinline__ double t(double y) const {
+    const double dy = y - m, dm = y - mu;
+    return c0 + dy * dy * hv - dm * dm * hs;
+  }
+};
 
-    const double sd = sqrt(s2), hs = 1.0 / (2.0 * s2), vfloor = s2 / 16.0, dn = (double)yn;
-    double pi = 0.5, m = mu + 2.0 * d, v = s2;
-    int iters = 0;
-    bool active = !degenerate, floored = false;
-    for (int k = 1; k <= a.max_iter; ++k) {
-      if (!__any(active)) break;
-      double c0 = log((1.0 - pi) / pi);
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) c0 += 0.5 * log(v / s2);
-      const double hv = 1.0 / (2.0 * v);
-      double rr[MODEL == NMOD_MIX_FREE_VAR ? kMixPer : 1];
-      double sr = 0.0, sy = 0.0;
+// A row policy hands the samples of Y to the EM: each(f) calls f(y, j, idx, live) for the caller's samples in a fixed order (idx: the
+// sample's place in the row, live: whether there is one), sum() adds a per-thread chain over the row, keep() / resp() hold or
+// recompute the responsibilities between the two passes of a free-variance iteration.
+// MixRegRow: a position in the registers of a group of G lanes, lane g of it keeps y[g + G j], j < 16.  Reached with all lanes on (a
+// group without a position, or a finished one, computes and does not commit), so the DPP sums always see a full row.
+template <int G, int DT>
+struct MixRegRow {
+  static constexpr int kLanes = G;
+  const void* sig; int64_t yb, yn;
+  double y[kMixPer], rr[kMixPer];
+  static __device__ __forceinline__ int lane() { return threadIdx.x & (G - 1); }
+  static __device__ __forceinline__ bool any(bool f) { return __any(f); }
+  __device__ __forceinline__ bool flag(bool f) const { return group_any<G>(f, threadIdx.x & 63); }
+  __device__ __forceinline__ double sum(double v) const { return group_sum_f64<G>(v); }
+  __device__ __forceinline__ void load() {                  // Y: loaded once
 #pragma unroll
-      for (int j = 0; j < kMixPer; ++j) {
-        const double dy = y[j] - m, dm = y[j] - mu;
-        const double t = c0 + dy * dy * hv - dm * dm * hs;
-        const double r = gl + G * j < ny ? 1.0 / (1.0 + exp(t)) : 0.0;
-        sr += r;
-        sy += r * y[j];
-        if constexpr (MODEL == NMOD_MIX_FREE_VAR) rr[j] = r;
-      }
-      sr = group_sum_f64<G>(sr);
-      sy = group_sum_f64<G>(sy);
-      const double pn = sr / dn, mn = sy / sr;
-      double vn = v;
-      bool fl = false;
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) {
-        double sq = 0.0;
+    for (int j = 0; j < kMixPer; ++j) y[j] = lane() + G * j < (int)yn ? mix_load<DT>(sig, yb + lane() + G * j) : 0.0;
+  }
+  template <class F>
+  __device__ __forceinline__ void each(F f) const {
 #pragma unroll
-        for (int j = 0; j < kMixPer; ++j) {
-          const double e = y[j] - mn;
-          sq += rr[j] * (e * e);
-        }
-        vn = group_sum_f64<G>(sq) / sr;
-        fl = vn < vfloor;
-        if (fl) vn = vfloor;
-      }
-      double delta = fmax(fabs(pn - pi), fabs(mn - m) / sd);
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) delta = fmax(delta, fabs(sqrt(vn) - sqrt(v)) / sd);
-      if (active) {
-        if (!(sr > 0.0)) {                                  // every responsibility underflowed
-          degenerate = true; active = false;
-        } else {
-          pi = pn; m = mn; v = vn; floored = fl; iters = k;
-          if (a.tol > 0.0 && delta <= a.tol) active = false;
-        }
-      }
-    }
-    const bool not_converged = active;                      // still running when max_iter was reached
+    for (int j = 0; j < kMixPer; ++j) f(y[j], j, (int64_t)(lane() + G * j), lane() + G * j < (int)yn);
+  }
+  __device__ __forceinline__ void keep(int j, double r) { rr[j] = r; }
+  __device__ __forceinline__ double resp(const MixAt&, double, int j) const { return rr[j]; }
+};
 
-    // final evaluation: llr and the posteriors
-    double c0 = log((1.0 - pi) / pi);
-    if constexpr (MODEL == NMOD_MIX_FREE_VAR) c0 += 0.5 * log(v / s2);
-    const double hv = 1.0 / (2.0 * v), l1 = log(1.0 - pi);
-    double ll = 0.0;
-    float* resp = a.out.resp;
-#pragma unroll
-    for (int j = 0; j < kMixPer; ++j) {
-      const int idx = gl + G * j;
-      const double dy = y[j] - m, dm = y[j] - mu;
-      const double t = c0 + dy * dy * hv - dm * dm * hs;
-      ll += idx < ny ? l1 + mix_softplus(-t) : 0.0;
-      if (resp && have && idx < ny) resp[yb + idx] = degenerate ? __int_as_float(0x7FC00000) : (float)(1.0 / (1.0 + exp(t)));
+// MixBlockRow: a position of a workgroup, thread t takes y[t + 1024 j], read again on every pass; the second pass of a free-variance
+// iteration evaluates the responsibilities again instead of storing them.  Everything a decision rests on is a block sum, the same
+// bits in every thread: the control flow is uniform over the workgroup.
+template <int DT>
+struct MixBlockRow {
+  static constexpr int kLanes = kMixStreamThreads;
+  const void* sig; int64_t yb, yn; double* sh;
+  static __device__ __forceinline__ int lane() { return threadIdx.x; }
+  static __device__ __forceinline__ bool any(bool f) { return f; }
+  __device__ __forceinline__ bool flag(bool f) const { return __syncthreads_or(f) != 0; }
+  __device__ __forceinline__ double sum(double v) const { return block_sum_f64<kMixStreamWaves>(v, sh); }
+  __device__ __forceinline__ void load() {}
+  template <class F>
+  __device__ __forceinline__ void each(F f) const {
+    for (int64_t i = lane(); i < yn; i += kLanes) f(mix_load<DT>(sig, yb + i), 0, i, true);
+  }
+  __device__ __forceinline__ void keep(int, double) {}
+  __device__ __forceinline__ double resp(const MixAt& at, double y, int) const { return 1.0 / (1.0 + exp(at.t(y))); }
+};
+
+// A position from its rows to its outputs: the moments of R (two passes, mean then the squares about it), the start values from
+// Y's mean, the iteration, the final llr / resp pass and the commit by `lead`, the thread that writes.  A row without a position
+// (have false: rn == yn == 0), a degenerate or a finished one computes along and keeps its state.
+template <int DT, int MODEL, class Row>
+__device__ __forceinline__ void mix_estimate(const MixArgs& a, Row& row, bool have, bool lead, int64_t pos, int64_t rb, int64_t rn) {
+  constexpr bool FREE = MODEL == NMOD_MIX_FREE_VAR;
+  bool bad = false, varies = false;
+  const double x0 = rn > 0 ? mix_load<DT>(a.r, rb) : 0.0;
+  double acc = 0.0;
+  for (int64_t k = Row::lane(); k < rn; k += Row::kLanes) {
+    const double x = mix_load<DT>(a.r, rb + k);
+    bad |= !isfinite(x);
+    varies |= x != x0;
+    acc += x;
+  }
+  const double mu = row.sum(acc) / (double)rn;
+  acc = 0.0;
+  for (int64_t k = Row::lane(); k < rn; k += Row::kLanes) {
+    const double dx = mix_load<DT>(a.r, rb + k) - mu;
+    acc += dx * dx;
+  }
+  const double s2 = row.sum(acc) / (double)rn;
+  acc = 0.0;
+  row.load();
+  row.each([&](double y, int, int64_t, bool) { bad |= !isfinite(y); acc += y; });
+  const double dn = (double)row.yn, d = row.sum(acc) / dn - mu;
+  bad = row.flag(bad);
+  varies = row.flag(varies);                                // a constant reference group has s2 == 0 whatever its sums round to
+  bool degenerate = !have || bad || !varies || !(s2 > 0.0);
+
+  const double sd = sqrt(s2), vfloor = s2 / 16.0;
+  MixAt at{0.0, mu + 2.0 * d, mu, 0.0, 1.0 / (2.0 * s2)};
+  double pi = 0.5, v = s2;
+  int iters = 0;
+  bool active = !degenerate, floored = false;
+  auto set_at = [&] {
+    at.c0 = log((1.0 - pi) / pi);
+    if constexpr (FREE) at.c0 += 0.5 * log(v / s2);
+    at.hv = 1.0 / (2.0 * v);
+  };
+  for (int k = 1; k <= a.max_iter; ++k) {
+    if (!Row::any(active)) break;
+    set_at();
+    double sr = 0.0, sy = 0.0;
+    row.each([&](double y, int j, int64_t, bool live) {
+      const double t = at.t(y);
+      const double r = live ? 1.0 / (1.0 + exp(t)) : 0.0;
+      sr += r;
+      sy += r * y;
+      if constexpr (FREE) row.keep(j, r);
+    });
+    sr = row.sum(sr);
+    sy = row.sum(sy);
+    const double pn = sr / dn, mn = sy / sr;
+    double vn = v;
+    bool fl = false;
+    if constexpr (FREE) {                                   // the second pass, about the new mean
+      double sq = 0.0;
+      row.each([&](double y, int j, int64_t, bool) {
+        const double e = y - mn;
+        sq += row.resp(at, y, j) * (e * e);
+      });
+      vn = row.sum(sq) / sr;
+      fl = vn < vfloor;
+      if (fl) vn = vfloor;
     }
-    ll = 2.0 * group_sum_f64<G>(ll);
-    if (have && gl == 0) {
-      if (degenerate) {
-        mix_write_nan(a.out, pos, NMOD_MIX_DEGENERATE);
+    double delta = fmax(fabs(pn - pi), fabs(mn - at.m) / sd);
+    if constexpr (FREE) delta = fmax(delta, fabs(sqrt(vn) - sqrt(v)) / sd);
+    if (active) {
+      if (!(sr > 0.0)) {                                    // every responsibility underflowed
+        degenerate = true; active = false;
       } else {
-        if (a.out.pi) a.out.pi[pos] = pi;
-        if (a.out.mu_mod) a.out.mu_mod[pos] = m;
-        if (a.out.sd_mod) a.out.sd_mod[pos] = sqrt(v);
-        if (a.out.llr) a.out.llr[pos] = ll;
-        if (a.out.iters) a.out.iters[pos] = iters;
-        if (a.out.status) a.out.status[pos] = (uint8_t)((not_converged ? NMOD_MIX_NOT_CONVERGED : 0) | (floored ? NMOD_MIX_VAR_FLOORED : 0));
+        pi = pn; at.m = mn; v = vn; floored = fl; iters = k;
+        if (a.tol > 0.0 && delta <= a.tol) active = false;
       }
+    }
+  }
+  const bool not_converged = active;                        // still running when max_iter was reached
+
+  // final evaluation: llr and the posteriors
+  set_at();
+  const double l1 = log(1.0 - pi);
+  double ll = 0.0;
+  float* const resp = a.out.resp;
+  row.each([&](double y, int, int64_t idx, bool live) {
+    const double t = at.t(y);
+    ll += live ? l1 + mix_softplus(-t) : 0.0;
+    if (resp && live) resp[row.yb + idx] = degenerate ? __int_as_float(0x7FC00000) : (float)(1.0 / (1.0 + exp(t)));
+  });
+  ll = 2.0 * row.sum(ll);
+  if (have && lead) {
+    if (degenerate) {
+      mix_write_nan(a.out, pos, NMOD_MIX_DEGENERATE);
+    } else {
+      if (a.out.pi) a.out.pi[pos] = pi;
+      if (a.out.mu_mod) a.out.mu_mod[pos] = at.m;
+      if (a.out.sd_mod) a.out.sd_mod[pos] = sqrt(v);
+      if (a.out.llr) a.out.llr[pos] = ll;
+      if (a.out.iters) a.out.iters[pos] = iters;
+      if (a.out.status) a.out.status[pos] = (uint8_t)((not_converged ? NMOD_MIX_NOT_CONVERGED : 0) | (floored ? NMOD_MIX_VAR_FLOORED : 0));
     }
   }
 }
 
-// The streaming form: a workgroup per position, Y re-read every iteration.  The free-variance model makes two passes per
-// iteration (the second, about the new mean, evaluates the responsibilities again instead of storing them).
+template <int G, int DT, int MODEL>
+__global__ __launch_bounds__(kMixThreads) void mix_em_kernel(MixArgs a) {
+  for (GroupWalk<G == 16 ? 0 : 1, G, kMixThreads> it(a.pl); it.more(); it.next()) {
+    const bool have = it.have();
+    MixRegRow<G, DT> row{a.y, 0, 0};
+    int64_t pos = 0, rb = 0, rn = 0;
+    if (have) {
+      pos = it.pos();
+      csr_row(a.yoff, a.ystride, pos, row.yb, row.yn);
+      csr_row(a.roff, a.rstride, pos, rb, rn);
+    }
+    mix_estimate<DT, MODEL>(a, row, have, row.lane() == 0, pos, rb, rn);
+  }
+}
+
 template <int DT, int MODEL>
 __global__ __launch_bounds__(kMixStreamThreads) void mix_stream_kernel(MixArgs a) {
   __shared__ double sh[kMixStreamWaves];
-  const int64_t cnt = (int64_t)a.count[2];
-  const int tid = threadIdx.x;
-  for (int64_t w = blockIdx.x; w < cnt; w += gridDim.x) {
-    const int64_t pos = (int64_t)a.list[2][w];
-    int64_t yb, yn, rb, rn;
-    csr_row(a.yoff, a.ystride, pos, yb, yn);
+  for (BlockWalk<2> it(a.pl); it.more(); it.next()) {
+    const int64_t pos = it.pos();
+    MixBlockRow<DT> row{a.y, 0, 0, sh};
+    int64_t rb, rn;
+    csr_row(a.yoff, a.ystride, pos, row.yb, row.yn);
     csr_row(a.roff, a.rstride, pos, rb, rn);
-    int bad = 0, varies = 0;
-    const double x0 = mix_load<DT>(a.r, rb);
-    double acc = 0.0;
-    for (int64_t k = tid; k < rn; k += kMixStreamThreads) {
-      const double x = mix_load<DT>(a.r, rb + k);
-      bad |= !isfinite(x);
-      varies |= x != x0;
-      acc += x;
-    }
-    const double mu = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)rn;
-    acc = 0.0;
-    for (int64_t k = tid; k < rn; k += kMixStreamThreads) {
-      const double dx = mix_load<DT>(a.r, rb + k) - mu;
-      acc += dx * dx;
-    }
-    const double s2 = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)rn;
-    acc = 0.0;
-    for (int64_t k = tid; k < yn; k += kMixStreamThreads) {
-      const double x = mix_load<DT>(a.y, yb + k);
-      bad |= !isfinite(x);
-      acc += x;
-    }
-    const double d = block_sum_f64<kMixStreamWaves>(acc, sh) / (double)yn - mu;
-    bool degenerate = __syncthreads_or(bad) != 0;
-    degenerate = __syncthreads_or(varies) == 0 || degenerate || !(s2 > 0.0);   // (a constant reference group: s2 == 0 exactly)
-
-    const double sd = sqrt(s2), hs = 1.0 / (2.0 * s2), vfloor = s2 / 16.0, dn = (double)yn;
-    double pi = 0.5, m = mu + 2.0 * d, v = s2;
-    int iters = 0;
-    bool active = !degenerate, floored = false;                // block-uniform from here on
-    for (int k = 1; k <= a.max_iter && active; ++k) {
-      double c0 = log((1.0 - pi) / pi);
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) c0 += 0.5 * log(v / s2);
-      const double hv = 1.0 / (2.0 * v);
-      double sr = 0.0, sy = 0.0;
-      for (int64_t i = tid; i < yn; i += kMixStreamThreads) {
-        const double yv = mix_load<DT>(a.y, yb + i);
-        const double dy = yv - m, dm = yv - mu;
-        const double r = 1.0 / (1.0 + exp(c0 + dy * dy * hv - dm * dm * hs));
-        sr += r;
-        sy += r * yv;
-      }
-      sr = block_sum_f64<kMixStreamWaves>(sr, sh);
-      sy = block_sum_f64<kMixStreamWaves>(sy, sh);
-      if (!(sr > 0.0)) { degenerate = true; active = false; break; }
-      const double pn = sr / dn, mn = sy / sr;
-      double vn = v;
-      bool fl = false;
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) {
-        double sq = 0.0;
-        for (int64_t i = tid; i < yn; i += kMixStreamThreads) {
-          const double yv = mix_load<DT>(a.y, yb + i);
-          const double dy = yv - m, dm = yv - mu, e = yv - mn;
-          const double r = 1.0 / (1.0 + exp(c0 + dy * dy * hv - dm * dm * hs));
-          sq += r * (e * e);
-        }
-        vn = block_sum_f64<kMixStreamWaves>(sq, sh) / sr;
-        fl = vn < vfloor;
-        if (fl) vn = vfloor;
-      }
-      double delta = fmax(fabs(pn - pi), fabs(mn - m) / sd);
-      if constexpr (MODEL == NMOD_MIX_FREE_VAR) delta = fmax(delta, fabs(sqrt(vn) - sqrt(v)) / sd);
-      pi = pn; m = mn; v = vn; floored = fl; iters = k;
-      if (a.tol > 0.0 && delta <= a.tol) active = false;
-    }
-    const bool not_converged = active;
-
-    double c0 = log((1.0 - pi) / pi);
-    if constexpr (MODEL == NMOD_MIX_FREE_VAR) c0 += 0.5 * log(v / s2);
-    const double hv = 1.0 / (2.0 * v), l1 = log(1.0 - pi);
-    double ll = 0.0;
-    float* resp = a.out.resp;
-    for (int64_t i = tid; i < yn; i += kMixStreamThreads) {
-      const double yv = mix_load<DT>(a.y, yb + i);
-      const double dy = yv - m, dm = yv - mu;
-      const double t = c0 + dy * dy * hv - dm * dm * hs;
-      ll += l1 + mix_softplus(-t);
-      if (resp) resp[yb + i] = degenerate ? __int_as_float(0x7FC00000) : (float)(1.0 / (1.0 + exp(t)));
-    }
-    ll = 2.0 * block_sum_f64<kMixStreamWaves>(ll, sh);
-    if (tid == 0) {
-      if (degenerate) {
-        mix_write_nan(a.out, pos, NMOD_MIX_DEGENERATE);
-      } else {
-        if (a.out.pi) a.out.pi[pos] = pi;
-        if (a.out.mu_mod) a.out.mu_mod[pos] = m;
-        if (a.out.sd_mod) a.out.sd_mod[pos] = sqrt(v);
-        if (a.out.llr) a.out.llr[pos] = ll;
-        if (a.out.iters) a.out.iters[pos] = iters;
-        if (a.out.status) a.out.status[pos] = (uint8_t)((not_converged ? NMOD_MIX_NOT_CONVERGED : 0) | (floored ? NMOD_MIX_VAR_FLOORED : 0));
-      }
-    }
+    mix_estimate<DT, MODEL>(a, row, true, row.lane() == 0, pos, rb, rn);
   }
 }
 
 template <int DT, int MODEL>
 static void mix_launch(const MixArgs& a, int num_cus, hipStream_t stream) {
-  const int64_t cap = (int64_t)num_cus * 8;
-  hipLaunchKernelGGL((mix_em_kernel<16, DT, MODEL>), dim3(persistent_grid(a.npos, kMixThreads / 16, cap)), dim3(kMixThreads), 0, stream, a);
-  hipLaunchKernelGGL((mix_em_kernel<64, DT, MODEL>), dim3(persistent_grid(a.npos, kMixThreads / 64, cap)), dim3(kMixThreads), 0, stream, a);
-  const int64_t sb = a.npos < (int64_t)num_cus * 2 ? a.npos : (int64_t)num_cus * 2;
-  hipLaunchKernelGGL((mix_stream_kernel<DT, MODEL>), dim3((unsigned)sb), dim3(kMixStreamThreads), 0, stream, a);
-}
-
-template <int DT>
-static void mix_launch_model(const MixArgs& a, int model, int num_cus, hipStream_t stream) {
-  if (model == NMOD_MIX_FREE_VAR) mix_launch<DT, NMOD_MIX_FREE_VAR>(a, num_cus, stream);
-  else mix_launch<DT, NMOD_MIX_EQUAL_VAR>(a, num_cus, stream);
+  launch_groups<16, kMixThreads>(mix_em_kernel<16, DT, MODEL>, a, num_cus, stream);
+  launch_groups<64, kMixThreads>(mix_em_kernel<64, DT, MODEL>, a, num_cus, stream);
+  launch_blocks<kMixStreamThreads>(mix_stream_kernel<DT, MODEL>, a, num_cus, stream);
 }
 
 }  // namespace nmod
@@ -380,7 +311,7 @@ extern "C" int nmod_mix_fraction(const nmod_params* prm, int64_t npos, const voi
 
   // one slab: the three work lists and their count words; for the host entry the inputs and outputs as well
   Slab slab(host);
-  const size_t o_list = slab.take(np * 4 * 3), o_count = slab.take(16);
+  const PosListSpace<3> lists(slab, np);
   const size_t toty = y1 ? tot1 : tot0, totr = y1 ? tot0 : tot1;
   slab.in(a.y, toty * esz); slab.in(a.yoff, (np + 1) * 8);
   slab.in(a.r, totr * esz); slab.in(a.roff, (np + 1) * 8);
@@ -388,16 +319,11 @@ extern "C" int nmod_mix_fraction(const nmod_params* prm, int64_t npos, const voi
   slab.out(a.out.pi, np * 8); slab.out(a.out.mu_mod, np * 8); slab.out(a.out.sd_mod, np * 8); slab.out(a.out.llr, np * 8);
   slab.out(a.out.iters, np * 4); slab.out(a.out.status, np); slab.out(a.out.resp, toty * 4);
   NMOD_HIP(slab.commit(stream, prm->device));
-  for (int c = 0; c < 3; ++c) a.list[c] = slab.at<uint32_t>(o_list) + (size_t)c * np;
-  a.count = slab.at<uint32_t>(o_count);
 
-  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
-  const int64_t cb = (npos + 255) / 256;
-  hipLaunchKernelGGL(mix_classify_kernel, dim3((unsigned)(cb < (int64_t)num_cus * 16 ? cb : (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
-  if (prm->dtype == NMOD_DTYPE_F32) mix_launch_model<NMOD_DTYPE_F32>(a, model, num_cus, stream);
-  else if (prm->dtype == NMOD_DTYPE_I16_MILLI) mix_launch_model<NMOD_DTYPE_I16_MILLI>(a, model, num_cus, stream);
-  else mix_launch_model<NMOD_DTYPE_F64>(a, model, num_cus, stream);
-  NMOD_HIP(hipGetLastError());
-  NMOD_HIP(slab.finish(stream));
-  return NMOD_OK;
+  NMOD_HIP(lists.fill<MixRule>(slab, a, num_cus, stream));
+  for_dtype(prm->dtype, [&](auto dt) {
+    if (model == NMOD_MIX_FREE_VAR) mix_launch<decltype(dt)::value, NMOD_MIX_FREE_VAR>(a, num_cus, stream);
+    else mix_launch<decltype(dt)::value, NMOD_MIX_EQUAL_VAR>(a, num_cus, stream);
+  });
+  return launches_end(slab, stream);
 }

@@ -1,10 +1,10 @@
 // nmod_one_sample — one read group against a stored per-position reference (mu, sd [, n]) on the device (K9).
 // The reference project has no such step; the definition is the one in include/nanomod_hip.h (tests/one_ref.py restates it
 // in numpy).  All on the caller's stream:
-//   one_classify_kernel       a thread per position: the size and reference checks and the position's class by n; the indices
-//                             of the positions to compute are ballot-compacted into one list per class (one atomic per wave
-//                             and class on a device count word); EMPTY / TOO_LARGE / BAD_REFERENCE positions get their NaN
-//                             outputs here
+//   pos_classify_kernel<OneRule>  (pos_walk.hpp) a thread per position: the size and reference checks and the position's class
+//                             by n; the indices of the positions to compute are ballot-compacted into one list per class (one
+//                             atomic per wave and class on a device count word); EMPTY / TOO_LARGE / BAD_REFERENCE positions
+//                             get their NaN outputs here
 //   one_wave_kernel<16,16>    n <= 256, float32 / int16: 16 lanes x 16 float32 keys, four positions per wave (seg_sort)
 //   one_wave_kernel<64,16>    n <= 1 024: the whole wave x 16 keys (wave_sort)
 //   one_wave_kernel<64,32>    n <= 2 048: the whole wave x 32 keys
@@ -20,8 +20,7 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
-#include "entry_common.hpp"
-#include "entry_device.hpp"
+#include "pos_walk.hpp"
 #include "rank_stats_packed.hpp"
 #include "special_math.hpp"
 #include "wave_ops.hpp"
@@ -39,7 +38,7 @@ struct OneArgs {
   const double* ref_mean; const double* ref_sd; const int32_t* ref_n;
   int64_t npos;
   nmod_one_out out;                                           // comb_st / comb_p are the combine kernel's
-  uint32_t* list[kOneClasses]; uint32_t* count;               // per class: indices of the positions to compute, their number
+  PosLists<kOneClasses> pl;                                   // per class: indices of the positions to compute, their number
 };
 
 __device__ __forceinline__ void one_write_nan(const nmod_one_out& o, int64_t i, unsigned status) {
@@ -54,28 +53,24 @@ __device__ __forceinline__ void one_write_nan(const nmod_one_out& o, int64_t i, 
   if (o.status) o.status[i] = (uint8_t)status;
 }
 
+// the class of position i by n (every float64 position: the workgroup form's); the size and reference checks leave a position out
 template <int DT>
-__global__ __launch_bounds__(256) void one_classify_kernel(OneArgs a) {
-  constexpr int64_t CAP = DT == NMOD_DTYPE_F64 ? NMOD_MAX_ONE_F64 : NMOD_MAX_ONE;
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.npos; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + threadIdx.x;
-    int cls = -1;
-    if (i < a.npos) {
-      int64_t b, n;
-      csr_row(a.off, a.stride, i, b, n);
-      const double mu = a.ref_mean[i], sd = a.ref_sd[i];
-      unsigned st = 0;
-      if (n == 0) st |= NMOD_STATUS_EMPTY;
-      if (n > CAP) st |= NMOD_STATUS_TOO_LARGE;
-      if (!(fabs(mu) <= kDblMax) || !(sd > 0.0) || !(sd <= kDblMax) || (a.ref_n && a.ref_n[i] < 2)) st |= NMOD_STATUS_BAD_REFERENCE;
-      if (st) one_write_nan(a.out, i, st);
-      else if constexpr (DT == NMOD_DTYPE_F64) cls = 3;
-      else cls = n <= kOneSmall ? 0 : (n <= kOneWave ? 1 : (n <= kOneWave2 ? 2 : 3));
-    }
-    compact_to_lists<kOneClasses>(cls, lane, a.list, a.count, i);
+struct OneRule {
+  static constexpr int NC = kOneClasses;
+  using Track = void;                                         // no per-sample output
+  static __device__ __forceinline__ int cls(const OneArgs& a, int64_t i, int64_t& b, int64_t& n) {
+    constexpr int64_t CAP = DT == NMOD_DTYPE_F64 ? NMOD_MAX_ONE_F64 : NMOD_MAX_ONE;
+    csr_row(a.off, a.stride, i, b, n);
+    const double mu = a.ref_mean[i], sd = a.ref_sd[i];
+    unsigned st = 0;
+    if (n == 0) st |= NMOD_STATUS_EMPTY;
+    if (n > CAP) st |= NMOD_STATUS_TOO_LARGE;
+    if (!(fabs(mu) <= kDblMax) || !(sd > 0.0) || !(sd <= kDblMax) || (a.ref_n && a.ref_n[i] < 2)) st |= NMOD_STATUS_BAD_REFERENCE;
+    if (st) { one_write_nan(a.out, i, st); return -1; }
+    if constexpr (DT == NMOD_DTYPE_F64) return 3;
+    else return n <= kOneSmall ? 0 : (n <= kOneWave ? 1 : (n <= kOneWave2 ? 2 : 3));
   }
-}
+};
 
 // Both D terms of the order statistic of rank k (1-based): k/n - F_k and F_k - (k-1)/n, F the reference's normal CDF.
 // zs = 1 / (sd sqrt 2), rn = 1 / n.  No contraction: the wave and the block kernels must round every step alike.
@@ -140,11 +135,10 @@ __device__ __forceinline__ double one_group_max(double v) {
 template <int LG, int R, int DT>
 __global__ __launch_bounds__(kOneThreads) void one_wave_kernel(OneArgs a) {
   constexpr int CLS = LG == 16 ? 0 : (R == 16 ? 1 : 2);
-  constexpr int GPB = kOneThreads / LG;
   constexpr int CAP = LG * R;
   __shared__ float keys[kOneThreads * R];                     // the sorted keys of every group: slot e of group g at g * CAP + e
   const float inf = __builtin_inff();
-  const int64_t cnt = (int64_t)a.count[CLS];
+  const int64_t cnt = (int64_t)a.pl.count[CLS];
   const int lane = threadIdx.x & 63, gl = threadIdx.x & (LG - 1), gidx = threadIdx.x / LG;
   float* wkeys = keys + (threadIdx.x >> 6) * (64 * R);
   const float* gkeys = keys + gidx * CAP;
@@ -152,12 +146,14 @@ __global__ __launch_bounds__(kOneThreads) void one_wave_kernel(OneArgs a) {
 #pragma unroll
   for (int b = 0; b < 6; ++b) sel.s[b] = ((lane >> b) & 1) ? inf : -inf;
 
-  for (int64_t w0 = (int64_t)blockIdx.x * GPB; w0 < cnt; w0 += (int64_t)gridDim.x * GPB) {
+  // pos_walk.hpp's GroupWalk spelled out: through the struct these kernels, which sit at the register limit, compile to another
+  // allocation, and the float32 forms lost up to 16 % (profiles/pos_walk.txt); as written they are the instructions they were
+  for (int64_t w0 = (int64_t)blockIdx.x * (kOneThreads / LG); w0 < cnt; w0 += (int64_t)gridDim.x * (kOneThreads / LG)) {
     const int64_t w = w0 + gidx;
     const bool have = w < cnt;
     int64_t pos = 0, begin = 0, n64 = 0;
     if (have) {
-      pos = (int64_t)a.list[CLS][w];
+      pos = (int64_t)a.pl.list[CLS][w];
       csr_row(a.off, a.stride, pos, begin, n64);
     }
     const int n = (int)n64;                                   // <= CAP by the class
@@ -211,7 +207,7 @@ __global__ __launch_bounds__(kOneThreads) void one_wave_kernel(OneArgs a) {
   }
 }
 
-// order-preserving unsigned image of a double and back (big_rank.hpp's form)
+// order-preserving unsigned image of a double and back
 __device__ __forceinline__ unsigned long long one_image(double v) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
@@ -236,10 +232,9 @@ __global__ __launch_bounds__(kOneBlockThreads) void one_block_kernel(OneArgs a) 
   __shared__ unsigned long long lds[NMOD_MAX_ONE_F64];
   Key* keys = reinterpret_cast<Key*>(lds);
   double* sh = reinterpret_cast<double*>(lds);
-  const int64_t cnt = (int64_t)a.count[3];
   const int tid = threadIdx.x;
-  for (int64_t w = blockIdx.x; w < cnt; w += gridDim.x) {
-    const int64_t pos = (int64_t)a.list[3][w];
+  for (BlockWalk<3> it(a.pl); it.more(); it.next()) {
+    const int64_t pos = it.pos();
     int64_t begin, n64;
     csr_row(a.off, a.stride, pos, begin, n64);
     const int n = (int)n64;                                   // <= the cap by the classifier
@@ -309,17 +304,16 @@ __global__ __launch_bounds__(kOneBlockThreads) void one_block_kernel(OneArgs a) 
 }
 
 template <int DT>
-static void one_launch(const OneArgs& a, int num_cus, hipStream_t stream) {
-  const int64_t cb = (a.npos + 255) / 256;
-  hipLaunchKernelGGL(one_classify_kernel<DT>, dim3((unsigned)(cb < (int64_t)num_cus * 16 ? cb : (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
-  const int64_t cap = (int64_t)num_cus * 8;
+static hipError_t one_launch(const Slab& slab, const PosListSpace<kOneClasses>& lists, OneArgs& a, int num_cus, hipStream_t stream) {
+  const hipError_t e = lists.fill<OneRule<DT>>(slab, a, num_cus, stream);
+  if (e != hipSuccess) return e;
   if constexpr (DT != NMOD_DTYPE_F64) {
-    hipLaunchKernelGGL((one_wave_kernel<16, 16, DT>), dim3(persistent_grid(a.npos, kOneThreads / 16, cap)), dim3(kOneThreads), 0, stream, a);
-    hipLaunchKernelGGL((one_wave_kernel<64, 16, DT>), dim3(persistent_grid(a.npos, kOneThreads / 64, cap)), dim3(kOneThreads), 0, stream, a);
-    hipLaunchKernelGGL((one_wave_kernel<64, 32, DT>), dim3(persistent_grid(a.npos, kOneThreads / 64, cap)), dim3(kOneThreads), 0, stream, a);
+    launch_groups<16, kOneThreads>(one_wave_kernel<16, 16, DT>, a, num_cus, stream);
+    launch_groups<64, kOneThreads>(one_wave_kernel<64, 16, DT>, a, num_cus, stream);
+    launch_groups<64, kOneThreads>(one_wave_kernel<64, 32, DT>, a, num_cus, stream);
   }
-  const int64_t sb = a.npos < (int64_t)num_cus * 2 ? a.npos : (int64_t)num_cus * 2;
-  hipLaunchKernelGGL(one_block_kernel<DT>, dim3((unsigned)sb), dim3(kOneBlockThreads), 0, stream, a);
+  launch_blocks<kOneBlockThreads>(one_block_kernel<DT>, a, num_cus, stream);
+  return hipSuccess;
 }
 
 }  // namespace nmod
@@ -339,9 +333,8 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   if (!off && prm->stride0 <= 0) return NMOD_ERR_INVALID_ARG;
   if (want_comb && !run_id) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && off && !csr_offsets_ok(off, npos)) return NMOD_ERR_INVALID_ARG;
   int num_cus = 0;
-  int rc = select_device(prm, &num_cus);
+  int rc = rows_begin(prm, npos, off, &num_cus);
   if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
   const size_t np = (size_t)npos, esz = elem_bytes(prm->dtype);
@@ -358,7 +351,7 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   // one slab: the work lists and their count words, the KS track where the caller wants the combined pair without it; for the
   // host entry the inputs and outputs as well
   Slab slab(host);
-  const size_t o_list = slab.take(np * 4 * kOneClasses), o_count = slab.take(16);
+  const PosListSpace<kOneClasses> lists(slab, np);
   const bool own_d = want_comb && !out->ks_d, own_p = want_comb && !out->ks_p;
   const size_t o_ksd = slab.take(own_d ? np * 8 : 0), o_ksp = slab.take(own_p ? np * 8 : 0);
   slab.in(a.sig, tot * esz); slab.in(a.off, (np + 1) * 8);
@@ -371,13 +364,8 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   NMOD_HIP(slab.commit(stream, prm->device));
   if (own_d) a.out.ks_d = slab.at<double>(o_ksd);
   if (own_p) a.out.ks_p = slab.at<double>(o_ksp);
-  for (int c = 0; c < kOneClasses; ++c) a.list[c] = slab.at<uint32_t>(o_list) + (size_t)c * np;
-  a.count = slab.at<uint32_t>(o_count);
 
-  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
-  if (prm->dtype == NMOD_DTYPE_F32) one_launch<NMOD_DTYPE_F32>(a, num_cus, stream);
-  else if (prm->dtype == NMOD_DTYPE_I16_MILLI) one_launch<NMOD_DTYPE_I16_MILLI>(a, num_cus, stream);
-  else one_launch<NMOD_DTYPE_F64>(a, num_cus, stream);
+  NMOD_HIP(for_dtype(prm->dtype, [&](auto dt) { return one_launch<decltype(dt)::value>(slab, lists, a, num_cus, stream); }));
   NMOD_HIP(hipGetLastError());
   if (want_comb) {
     // the window combine of the KS track (K3): the code behind nmod_combine_track, on the same stream.  A member of the pair the

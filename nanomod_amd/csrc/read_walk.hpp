@@ -135,26 +135,13 @@ static void launch_read_forms(const Args& a, int64_t cap, size_t lds_bytes, hipS
 }
 template <class K, bool LDS_TAB, class Args>
 static void launch_read_kernels(const Args& a, int32_t dtype, int64_t cap, size_t lds_bytes, hipStream_t stream) {
-  if (dtype == NMOD_DTYPE_F32) launch_read_forms<K, NMOD_DTYPE_F32, LDS_TAB>(a, cap, lds_bytes, stream);
-  else if (dtype == NMOD_DTYPE_I16_MILLI) launch_read_forms<K, NMOD_DTYPE_I16_MILLI, LDS_TAB>(a, cap, lds_bytes, stream);
-  else launch_read_forms<K, NMOD_DTYPE_F64, LDS_TAB>(a, cap, lds_bytes, stream);
+  for_dtype(dtype, [&](auto dt) { launch_read_forms<K, decltype(dt)::value, LDS_TAB>(a, cap, lds_bytes, stream); });
 }
 
 // Host checks of the entries, in the order they have always run: the count of reads, the model's k and center ...
 inline bool read_count_ok(int64_t nreads) { return nreads >= 0 && nreads <= (int64_t)UINT32_MAX - 1; }
 inline bool kmer_model_ok(const nmod_rescale_model* m) { return m && m->k >= 1 && m->k <= 8 && m->center >= 0 && m->center < m->k; }
-// ... and, after the entry's own: the offsets of a host call, then the device.  NMOD_OK with no rows: there is nothing to do
-inline int rows_begin(const nmod_params* prm, int64_t nrows, const int64_t* off, int* num_cus) {
-  if (prm->memspace == NMOD_MEM_HOST && off && nrows > 0 && !csr_offsets_ok(off, nrows)) return NMOD_ERR_INVALID_ARG;
-  if (nrows == 0) return NMOD_OK;
-  return select_device(prm, num_cus);
-}
-// the end of an entry: what the launches left behind, the downloads of a host call, the slab
-inline int launches_end(Slab& slab, hipStream_t stream) {
-  NMOD_HIP(hipGetLastError());
-  NMOD_HIP(slab.finish(stream));
-  return NMOD_OK;
-}
+// ... and, after the entry's own, rows_begin (entry_common.hpp): the offsets of a host call, then the device
 
 // Per-position counts over rows of pivoted scores (nmod_site_calls, nmod_site_llr): a wave per row, rows strided over the grid's waves.
 // Rule: N counters (the first is n_valid), `count(score, c)` adds one score to them, `frac(c)` is the row's fraction from the totals

@@ -2,8 +2,8 @@
 // likelihood-ratio test of pi = 0 and a posterior per read, on the device (K14).  The reference project has no such step;
 // the definition is the one in include/nanomod_hip.h (tests/stoich_ref.py restates it in numpy).  K8's shape (mix_fraction.hip): a few
 // fixed-point iterations over a row that stays on chip.  All on the caller's stream:
-//   st_classify_kernel   a thread per row: the row's class by its length, ballot-compacted into one list per class; a row beyond
-//                        NMOD_MAX_DEEP gets its NaN outputs, status and NaN resp here
+//   pos_classify_kernel<StRule>  (pos_walk.hpp) a thread per row: the row's class by its length, ballot-compacted into one list per
+//                        class; a row beyond NMOD_MAX_DEEP gets its NaN outputs, status and NaN resp here
 //   st_reg_kernel<16>    rows <= 256: 16 lanes x 16 signed t values hold a row in registers over all iterations, four rows per wave,
 //                        DPP row sums only; a finished row freezes while the others of its wave go on
 //   st_reg_kernel<64>    rows <= 1 024: the whole wave x 16 doubles
@@ -20,7 +20,8 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
-#include "read_walk.hpp"
+#include "pos_walk.hpp"
+#include "special_math.hpp"
 
 namespace nmod {
 
@@ -37,7 +38,7 @@ struct StArgs {
   const double* score; const int64_t* off; int64_t stride; int64_t npos;
   int max_iter, min_valid; double tol, drop;
   nmod_stoich_out out;
-  uint32_t* list[3]; uint32_t* count;             // per class: indices of the rows, their number
+  PosLists<3> pl;                                 // per class: indices of the rows, their number
 };
 
 __device__ __forceinline__ void st_write_nan(const nmod_stoich_out& o, int64_t i, int n_valid, unsigned status) {
@@ -52,30 +53,17 @@ __device__ __forceinline__ void st_write_nan(const nmod_stoich_out& o, int64_t i
   if (o.status) o.status[i] = (uint8_t)status;
 }
 
-__global__ __launch_bounds__(256) void st_classify_kernel(StArgs a) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.npos; base += (int64_t)gridDim.x * 256) {
-    const int64_t i = base + threadIdx.x;
-    const bool in = i < a.npos;
-    int cls = -1;
-    int64_t yb = 0, yn = 0;
-    if (in) {
-      csr_row(a.off, a.stride, i, yb, yn);
-      if (yn > NMOD_MAX_DEEP) st_write_nan(a.out, i, 0, NMOD_STOICH_TOO_LARGE);
-      else cls = yn <= kStSmall ? 0 : (yn <= kStWave ? 1 : 2);
-    }
-    compact_to_lists<3>(cls, lane, a.list, a.count, i);
-    if (a.out.resp) {                                       // the scores of the rows left out: NaN, a wave per row
-      unsigned long long mask = __ballot(in && cls < 0);
-      while (mask) {
-        const int src = __ffsll((long long)mask) - 1;
-        mask &= mask - 1ull;
-        const int64_t b = __shfl((long long)yb, src), n = __shfl((long long)yn, src);
-        for (int64_t k = lane; k < n; k += 64) a.out.resp[b + k] = nan_f64();
-      }
-    }
+// the class of row i by its length; a row beyond NMOD_MAX_DEEP is left out (its scores' resp: NaN, by the classify kernel)
+struct StRule {
+  static constexpr int NC = 3;
+  using Track = double;
+  static __device__ __forceinline__ double* track(const StArgs& a) { return a.out.resp; }
+  static __device__ __forceinline__ int cls(const StArgs& a, int64_t i, int64_t& yb, int64_t& yn) {
+    csr_row(a.off, a.stride, i, yb, yn);
+    if (yn > NMOD_MAX_DEEP) { st_write_nan(a.out, i, 0, NMOD_STOICH_TOO_LARGE); return -1; }
+    return yn <= kStSmall ? 0 : (yn <= kStWave ? 1 : 2);
   }
-}
+};
 
 __device__ __forceinline__ bool st_valid(double s) { return fabs(s) <= kDblMax; }
 
@@ -216,16 +204,12 @@ __device__ __forceinline__ double st_resp(double s, double pihat, bool est) {
 
 template <int G>
 __global__ __launch_bounds__(kStThreads) void st_reg_kernel(StArgs a) {
-  constexpr int CLS = G == 16 ? 0 : 1;
-  constexpr int GPB = kStThreads / G;
-  const int64_t cnt = (int64_t)a.count[CLS];
-  const int gl = threadIdx.x & (G - 1), gidx = threadIdx.x / G;
-  for (int64_t w0 = (int64_t)blockIdx.x * GPB; w0 < cnt; w0 += (int64_t)gridDim.x * GPB) {
-    const int64_t w = w0 + gidx;
-    const bool have = w < cnt;
+  const int gl = threadIdx.x & (G - 1);
+  for (GroupWalk<G == 16 ? 0 : 1, G, kStThreads> it(a.pl); it.more(); it.next()) {
+    const bool have = it.have();
     int64_t pos = 0, yb = 0, yn = 0;
     if (have) {
-      pos = (int64_t)a.list[CLS][w];
+      pos = it.pos();
       csr_row(a.off, a.stride, pos, yb, yn);
     }
     const int ny = (int)yn;
@@ -259,10 +243,9 @@ __global__ __launch_bounds__(kStThreads) void st_reg_kernel(StArgs a) {
 __global__ __launch_bounds__(kStBlockThreads) void st_block_kernel(StArgs a) {
   __shared__ double stage[kStStage];
   __shared__ double sh[kStBlockWaves];
-  const int64_t cnt = (int64_t)a.count[2];
   const int tid = threadIdx.x;
-  for (int64_t w = blockIdx.x; w < cnt; w += gridDim.x) {
-    const int64_t pos = (int64_t)a.list[2][w];
+  for (BlockWalk<2> it(a.pl); it.more(); it.next()) {
+    const int64_t pos = it.pos();
     int64_t yb, yn;
     csr_row(a.off, a.stride, pos, yb, yn);
     const double* sc = a.score + yb;
@@ -318,20 +301,15 @@ extern "C" int nmod_site_stoich(const nmod_params* prm, int64_t npos, const doub
 
   // one slab: the three work lists and their count words; for the host entry the inputs and outputs as well
   Slab slab(host);
-  const size_t o_list = slab.take(np * 4 * 3), o_count = slab.take(16);
+  const PosListSpace<3> lists(slab, np);
   slab.in(a.off, (np + 1) * 8); slab.in(a.score, tot * 8);
   slab.out(a.out.pi, np * 8); slab.out(a.out.pi_lo, np * 8); slab.out(a.out.pi_hi, np * 8); slab.out(a.out.stat, np * 8);
   slab.out(a.out.p_null, np * 8); slab.out(a.out.n_valid, np * 4); slab.out(a.out.iters, np * 4); slab.out(a.out.status, np);
   slab.out(a.out.resp, tot * 8);
   NMOD_HIP(slab.commit(stream, prm->device));
-  for (int c = 0; c < 3; ++c) a.list[c] = slab.at<uint32_t>(o_list) + (size_t)c * np;
-  a.count = slab.at<uint32_t>(o_count);
-
-  NMOD_HIP(hipMemsetAsync(a.count, 0, 16, stream));
-  const int64_t cb = (npos + 255) / 256, ccap = (int64_t)num_cus * 16, cap = (int64_t)num_cus * 8;
-  hipLaunchKernelGGL(st_classify_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(st_reg_kernel<16>, dim3(persistent_grid(npos, kStThreads / 16, cap)), dim3(kStThreads), 0, stream, a);
-  hipLaunchKernelGGL(st_reg_kernel<64>, dim3(persistent_grid(npos, kStThreads / 64, cap)), dim3(kStThreads), 0, stream, a);
-  hipLaunchKernelGGL(st_block_kernel, dim3(persistent_grid(npos, 1, (int64_t)num_cus * 2)), dim3(kStBlockThreads), 0, stream, a);
+  NMOD_HIP(lists.fill<StRule>(slab, a, num_cus, stream));
+  launch_groups<16, kStThreads>(st_reg_kernel<16>, a, num_cus, stream);
+  launch_groups<64, kStThreads>(st_reg_kernel<64>, a, num_cus, stream);
+  launch_blocks<kStBlockThreads>(st_block_kernel, a, num_cus, stream);
   return launches_end(slab, stream);
 }

@@ -20,7 +20,7 @@ import stoich_ref as F
 # ------------------------------------------------------------------------------------------------------------------------ the grids
 # Restated from the launch code as functions of the CU count; the tests size their batches from these and assert that they did.
 
-CLASSIFY_POSITIONS_PER_CU = 16 * 256              # mix_fraction.hip nmod_mix_fraction, one_sample.hip one_launch, site_stoich.hip nmod_site_stoich:
+CLASSIFY_POSITIONS_PER_CU = 16 * 256              # pos_walk.hpp PosListSpace::fill (mix_fraction.hip, one_sample.hip, site_stoich.hip):
                                                   # the classify grid is at most num_cus * 16 blocks of 256 threads, a thread per position
 CLASSIFY_BEYOND = 100000                          # positions past the first stride of the classify grid in the classify batches
 
@@ -31,13 +31,13 @@ def classify_stride(cus):
 
 def mix_units(cus):
     """mix_fraction.hip mix_launch: cap = num_cus * 8 blocks of kMixThreads = 256 threads for mix_em_kernel<16> (256 / 16 lane groups a
-    block) and mix_em_kernel<64> (256 / 64 waves a block); sb = num_cus * 2 workgroups for mix_stream_kernel"""
+    block) and mix_em_kernel<64> (256 / 64 waves a block), num_cus * 2 workgroups for mix_stream_kernel (pos_walk.hpp launch_groups / launch_blocks)"""
     return (8 * 16 * cus, 8 * 4 * cus, 2 * cus)
 
 
 def one_units(cus):
     """one_sample.hip one_launch: cap = num_cus * 8 blocks of kOneThreads = 256 threads for one_wave_kernel<16,16> (16 lane groups a
-    block), <64,16> and <64,32> (4 waves a block); sb = num_cus * 2 workgroups for one_block_kernel"""
+    block), <64,16> and <64,32> (4 waves a block); num_cus * 2 workgroups for one_block_kernel"""
     return (8 * 16 * cus, 8 * 4 * cus, 8 * 4 * cus, 2 * cus)
 
 

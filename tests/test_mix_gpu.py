@@ -116,25 +116,29 @@ def test_parity_stride(nm, dtype, model, n):
     _check(res, x, y, model, 50, 1e-8, 'stride %s model %d n %d' % (dtype, model, n))
 
 
-def _edge_rows():
+def _edge_rows(ny=60):
+    """the edge positions with mixed groups of ny samples (position 1: of one)"""
     rng = np.random.default_rng(11)
-    ok_x, ok_y, _ = M.planted_rows(rng, 50, 60, 0.5, 4.0)
+    ok_x, ok_y, _ = M.planted_rows(rng, 50, ny, 0.5, 4.0)
     x, y = [], []
     x.append(ok_x[:1]); y.append(ok_y)                                                   # 0: a reference group of 1
     x.append(ok_x); y.append(ok_y[:1])                                                   # 1: a mixed group of 1
     x.append(np.full(13, 700, np.int16)); y.append(ok_y)                                 # 2: a constant reference group
-    x.append(np.array([1000, 3000], np.int16)); y.append(np.full(6, 2000, np.int16))     # 3: all of Y equal to mu
-    x.append(np.arange(-1000, 1001, 40, dtype=np.int16)); y.append(np.r_[np.full(30, 400), np.full(30, 401)].astype(np.int16))   # 4: floor
+    x.append(np.array([1000, 3000], np.int16)); y.append(np.full(ny, 2000, np.int16))    # 3: all of Y equal to mu
+    x.append(np.arange(-1000, 1001, 40, dtype=np.int16)); y.append(np.r_[np.full(ny // 2, 400), np.full(ny // 2, 401)].astype(np.int16))   # 4: floor
     x.append(ok_x); y.append(ok_y)                                                       # 5: an ordinary position
     return x, y
 
 
+@pytest.mark.parametrize('ny', [60, 600, 1100])
 @pytest.mark.parametrize('model', [M.EQUAL, M.FREE])
-def test_degenerate_and_edge_statuses(nm, model):
-    x, y = _edge_rows()
+def test_degenerate_and_edge_statuses(nm, model, ny):
+    """|Y| = 60, 600 and 1 100: the 16-lane, the whole-wave and the streaming form, which run one EM through their own row policies"""
+    assert 60 <= M.SMALL < 600 <= M.WAVE < 1100
+    x, y = _edge_rows(ny)
     xd, yd = _encode(x, 'f64'), _encode(y, 'f64')
     res = _run(nm, xd, yd, model=model)
-    _check(res, xd, yd, model, 200, 1e-6, 'edge model %d' % model)
+    _check(res, xd, yd, model, 200, 1e-6, 'edge model %d |Y| %d' % (model, ny))
     assert list(res['status'][:3]) == [M.DEGENERATE] * 3 and list(res['iters'][:3]) == [0, 0, 0]
     # all of Y equal to mu: d = 0, every t_i = 0, r_i = 1/2, the parameters reproduce themselves: converged after one iteration.
     # In the free model v' = 0 < s2 / 16: the floor is active, sd moves from s to s / 4, and the next iterations settle
@@ -159,7 +163,7 @@ def test_degenerate_and_edge_statuses(nm, model):
     r3 = _run(nm, xd, yd, model=model, tol=0.0, max_iter=37)
     live = r3['status'] & M.DEGENERATE == 0
     assert (r3['iters'][live] == 37).all() and (r3['status'][live] & M.NOT_CONVERGED).all()
-    _check(r3, xd, yd, model, 37, 0.0, 'tol 0 model %d' % model)
+    _check(r3, xd, yd, model, 37, 0.0, 'tol 0 model %d |Y| %d' % (model, ny))
     r4 = _run(nm, xd, yd, model=model, max_iter=1)
     assert (r4['iters'][live] == 1).all()
 

@@ -102,7 +102,7 @@ def test_mix_fraction_on_a_batch_larger_than_its_grids(cus, dtype, model):
 
 
 def test_mix_classify_past_one_stride(cus):
-    """16 * 256 CUs + 100 000 positions, about 95 % of them left out by mix_classify_kernel — degenerate by size, gated off, a NaN gate —
+    """16 * 256 CUs + 100 000 positions, about 95 % of them left out by pos_classify_kernel<MixRule> — degenerate by size, gated off, a NaN gate —
     and the pool's positions of every class on both sides of the stride"""
     b = G.mix_classify_batch('f32', cus)
     npos, stride = len(b['idx']), G.classify_stride(cus)
