@@ -391,7 +391,9 @@ int nmod_argsort_keys(const nmod_params* prm, int64_t n, const int64_t* keys, in
  * reference's record order (sorted (chrom, strand), ascending position).  strand_lo[i] / strand_hi[i]: index of the
  * first / last record of record i's (chrom, strand); value[i]: the p-value or statistic the ranking uses
  * (record[sorted_ind][use_pind]); w: the window half-width AFTER the reference's in-place increment (window + 1);
- * movesize: 1 when WindOvlp == 1, else w; na: base filter ('\0' = none).  Writes the indices of the ranked window
+ * movesize: 1 when WindOvlp == 1, else w; na: base filter ('\0' = none); percentile: which of a window's sorted contributing
+ * values is its key, 0 <= percentile <= 1 (anything else, NaN included, is NMOD_ERR_INVALID_ARG).  A window holding a NaN value
+ * has no defined rank.  Writes the indices of the ranked window
  * centres to ranked_out (capacity npos) and their number to *n_ranked.  Host memory only; synchronises. */
 int nmod_region_rank(const nmod_params* prm, int64_t npos, const int32_t* strand_lo, const int32_t* strand_hi,
                      const int64_t* pos, const char* base, const double* value, int32_t w, int32_t movesize,

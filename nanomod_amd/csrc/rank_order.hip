@@ -188,6 +188,7 @@ extern "C" int nmod_region_rank(const nmod_params* prm, int64_t npos, const int3
   if (npos == 0) return NMOD_OK;
   if (!strand_lo || !strand_hi || !pos || !base || !value || !ranked_out || w < 0 || movesize < 1) return NMOD_ERR_INVALID_ARG;
   if (prm->memspace != NMOD_MEM_HOST) return NMOD_ERR_INVALID_ARG;              // post-processing of host-side records
+  if (!(percentile >= 0.0 && percentile <= 1.0)) return NMOD_ERR_INVALID_ARG;   // (NaN too) the selected member would lie outside the window
   int rc = select_device(prm, nullptr);
   if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;

@@ -512,6 +512,15 @@ def main():
                 tag = 'track600_nb%d_%s' % (nb, method)
                 exp, table = run_reference_table(myDetect, fx, nb, 2.0, method, tag)
                 save_expected(tag, exp, table)
+        # region ranking (RegionRankbyST=1) on the ragged rows: four (chrom, strand) segments of 60-90 positions with gaps, inserted
+        # out of sorted order; windows of 7 and 9 positions fit the runs between gaps (about 12 positions)
+        fx = dict(np.load(os.path.join(OUT, 'ragged_inputs.npz')))
+        for tag, method, window, ovlp, pct, na, ru in (('w2_o0', 'stouffer', 2, 0, 0.1, '', 'pv'), ('w2_o1', 'fisher', 2, 1, 0.0, '', 'pv'),
+                                                       ('w3_o1_ks', 'ks', 3, 1, 0.5, '', 'pv'), ('w2_o1_st', 'stouffer', 2, 1, 0.1, '', 'st'),
+                                                       ('w3_o1_A', 'stouffer', 3, 1, 0.1, 'A', 'pv')):
+            rr = run_reference_region_rank(myDetect, fx, method, window, ovlp, pct, na, ru)
+            np.savez_compressed(os.path.join(OUT, 'ragged_regionrank_%s.npz' % tag), method=method, window=window,
+                                WindOvlp=ovlp, percentile=pct, NA=na, rankUse=ru, **rr)
     print('golden fixtures written to', os.path.abspath(OUT))
 
 
