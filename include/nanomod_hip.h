@@ -771,6 +771,61 @@ typedef struct nmod_stoich_out { int32_t struct_size; int32_t reserved;
 int nmod_site_stoich(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */,
                      const nmod_stoich_opts* opts, const nmod_stoich_out* out);
 
+/* The modified shares of two samples compared per site: each sample's estimate, the pooled one, the likelihood-ratio test of
+ * pi0 = pi1 and the profile-likelihood interval of delta = pi1 - pi0 (K15; the reference project has no such step).  Per site two
+ * rows of float64 window sums, as nmod_site_stoich takes one: row 0 (sample 0, the control condition) from score0 by off0 or
+ * prm->stride0, row 1 from score1 by off1 or prm->stride1; the two may differ in length.  Memspaces, the NULL and struct_size rules:
+ * those of nmod_site_stoich.
+ *   Per row X, K14's quantities unchanged: a score is VALID iff fabs(s) <= DBL_MAX, n_X = the valid scores; t = -expm1(-fabs(s)) with
+ *     the side of s; S_X(pi), D_X(pi), g_X(pi) are K14's EVALUATION over row X, each row's sums on their own.
+ *   No estimate (NaN outputs, iters 0, n_valid0 / n_valid1 still written):
+ *       NMOD_DIFF_TOO_LARGE      either row beyond NMOD_MAX_DEEP scores (n_valid0 = n_valid1 = 0)
+ *       NMOD_DIFF_TOO_FEW        n_0 < min_valid or n_1 < min_valid
+ *       NMOD_DIFF_FLAT           otherwise, the sum of t is 0 in either row
+ *   pi0, pi1: K14's estimate of each row alone, by the same rule: 0 iff S(0) <= 0, else 1 iff S(1) >= 0, else the root of S by K14's
+ *     BRACKETED ITERATION on (0, 1) with its stop test.
+ *   pi_pool: the same rule and iteration on S_0 + S_1 with D_0 + D_1 as the slope (x' = x + (S_0 + S_1) / (D_0 + D_1)).
+ *     iters = the evaluations the iteration for pi_pool made (0 at either end).  NMOD_DIFF_POOL_AT_END: pi_pool is 0 or 1.
+ *   stat = max(2 (g^ - g_pool), 0) with g^ = g_0(pi0) + g_1(pi1), g_pool = g_0(pi_pool) + g_1(pi_pool); the sums of s of K14's l
+ *     cancel between the two: no inf - inf.  p_diff = max(erfc(sqrt(stat / 2)), DBL_MIN), the chi2_1 tail.  With pi_pool at an end
+ *     the null sits on the boundary and the tail is conservative.
+ *   delta = pi1 - pi0.
+ *   The interval of delta.  For d in [-1, 1]: I(d) = [max(0, -d), min(1, 1 - d)], the pair at (x, d) is (pi0, pi1) =
+ *     (x, min(max(x + d, 0), 1)), and h(d) = g_0(x*) + g_1(x* + d) at the INNER maximiser x*: the lower end of I(d) iff
+ *     S_0 + S_1 <= 0 at the pair there; else the upper end iff S_0 + S_1 >= 0 there; else the root of S_0(x) + S_1(x + d) in I(d) by
+ *     the bracketed iteration (slope D_0 + D_1).  h is concave, h(delta) = g^, h(0) = g_pool.  The interval is
+ *     {d : 2 (g^ - h(d)) <= ci_drop}:  delta_lo = -1 iff 2 (g^ - (g_0(1) + g_1(0))) <= ci_drop, else the root in (-1, delta);
+ *     delta_hi = 1 iff 2 (g^ - (g_0(0) + g_1(1))) <= ci_drop, else the root in (delta, 1).  The OUTER roots run K14's bracketed
+ *     iteration for pi_lo / pi_hi with H(d) = 2 (g^ - h(d)) in the place of h and the envelope slope S_1(x* + d) in the place of S:
+ *         delta_lo: right iff H(d) > ci_drop;   delta_hi: right iff H(d) <= ci_drop;   d' = d + (H - ci_drop) / (2 S_1(x* + d))
+ *     where x* is interior; where x* is an end of I(d) the step is the bisection step d' = a + 0.5 (b - a).  Every outer evaluation
+ *     runs its own inner iteration from the midpoint of I(d).  max_iter bounds every root, inner and outer, on its own; one still
+ *     running then sets NMOD_DIFF_NOT_CONVERGED, the values are written all the same.  With delta_lo and delta_hi both NULL no
+ *     interval root is run.
+ *   stat is the profile deviance at d = 0: p_diff <= alpha and "0 outside the interval at level 1 - alpha" are one statement.
+ *   Outputs (npos each; a NULL member is skipped; requesting fewer never changes the bits of the others): doubles pi0, pi1, pi_pool,
+ *     delta, delta_lo, delta_hi, stat, p_diff; int32 n_valid0, n_valid1, iters; uint8 status.  No per-read posterior: K14 has it.
+ * Sums as in K14.  The class of a site follows the longer of its rows: both up to NMOD_DIFF_SMALL scores: 16 lanes; up to
+ * NMOD_DIFF_WAVE: a wave; beyond: a workgroup.  A site's bits depend on its two rows alone, not on the batch, the order of the sites,
+ * CSR versus stride, the memspace or the outputs asked for.  Reads struct_size, device, stream, memspace, stride0, stride1 of prm.
+ * NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and no synchronisation.  npos == 0 is NMOD_OK.
+ * NMOD_ERR_INVALID_ARG before any device work: nmod_site_stoich's refusals, for both rows' arguments.
+ * Limits: two conditions only, no replicates or covariates; the reads are treated as independent; both k-mer tables are taken as
+ * right; each strand is its own site; the chi2_1 law is asymptotic and slightly liberal at low coverage (of 40 000 simulated null pairs,
+ * rejected at the 5 % level: 0.050 at 20 v 20 reads, levels 1 sd apart, pi 0.3; 0.053 at 200 v 200, 1 sd, 0.3; 0.052 at 200 v 200, 3 sd,
+ * 0.5; 0.057 at 20 v 20, 3 sd, 0.5; 0.064 at 10 v 10, 3 sd, 0.5; 0.063 at 200 v 200, 3 sd, 0.02; below 0.001 at pi 0 and at pi 1:
+ * tests/test_site_diff.py, profiles/site_diff.txt). */
+#define NMOD_DIFF_SMALL 128                /* scores of the longer row up to which 16 lanes compute a site */
+#define NMOD_DIFF_WAVE 512                 /* ... up to which one wave does (a workgroup beyond) */
+enum { NMOD_DIFF_TOO_FEW = 1, NMOD_DIFF_FLAT = 2, NMOD_DIFF_NOT_CONVERGED = 4, NMOD_DIFF_POOL_AT_END = 8, NMOD_DIFF_TOO_LARGE = 32 };
+typedef struct nmod_diff_opts { int32_t struct_size, max_iter, min_valid, reserved; double tol, ci_drop; } nmod_diff_opts;
+typedef struct nmod_diff_out { int32_t struct_size; int32_t reserved;
+  double *pi0, *pi1, *pi_pool, *delta, *delta_lo, *delta_hi, *stat, *p_diff; int32_t *n_valid0, *n_valid1, *iters; uint8_t* status;
+} nmod_diff_out;
+int nmod_site_diff(const nmod_params* prm, int64_t npos, const double* score0, const int64_t* off0 /* or prm->stride0 */,
+                   const double* score1, const int64_t* off1 /* or prm->stride1 */,
+                   const nmod_diff_opts* opts, const nmod_diff_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -237,6 +237,31 @@ def make_stoich_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP
 make_stoich_out = functools.partial(make_out, NmodStoichOut)
 
 
+DIFF_TOO_FEW, DIFF_FLAT, DIFF_NOT_CONVERGED, DIFF_POOL_AT_END, DIFF_TOO_LARGE = 1, 2, 4, 8, 32
+DIFF_NO_ESTIMATE = DIFF_TOO_FEW | DIFF_FLAT | DIFF_TOO_LARGE
+DIFF_SMALL, DIFF_WAVE = 128, 512          # nmod_site_diff: scores of the longer row up to which 16 lanes / one wave compute a site
+DIFF_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat', 'p_diff')
+DIFF_INT_FIELDS = ('n_valid0', 'n_valid1', 'iters')
+
+
+class NmodDiffOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'max_iter', 'min_valid', 'reserved')] + [('tol', C.c_double), ('ci_drop', C.c_double)]
+
+
+class NmodDiffOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in DIFF_FIELDS + DIFF_INT_FIELDS + ('status',)]
+
+
+def make_diff_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP_95):
+    o = NmodDiffOpts()
+    o.struct_size = C.sizeof(NmodDiffOpts)
+    o.max_iter, o.min_valid, o.tol, o.ci_drop = int(max_iter), int(min_valid), float(tol), float(ci_drop)
+    return o
+
+
+make_diff_out = functools.partial(make_out, NmodDiffOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -301,6 +326,8 @@ _SIGNATURES = {
                                 C.POINTER(NmodRescaleModel), C.POINTER(NmodLlrOpts), C.POINTER(NmodLlrOut)]),
     'nmod_site_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteLlrOut)]),
     'nmod_site_stoich': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NmodStoichOpts), C.POINTER(NmodStoichOut)]),
+    'nmod_site_diff': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodDiffOpts),
+                                 C.POINTER(NmodDiffOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -174,6 +174,26 @@ def build_parser():
     rl.add_argument('--outFolder', default='mRes')
     rl.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_llr.txt and <FileID>_site_llr.txt')
     rl.add_argument('--device', type=int, default=0)
+    rd = sub.add_parser('readdiff', help='compare the modified share of every site between two read-level samples on the device: the '
+                        'share of each, their difference with a profile-likelihood interval, and the likelihood-ratio test of equal shares')
+    rd.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rd.add_argument('--wrkBase1', required=True, help='sample 0, the control condition: a read-level .npz container')
+    rd.add_argument('--wrkBase2', required=True, help='sample 1: a read-level .npz container')
+    rd.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
+    rd.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rd.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
+                    'before and after, 0 .. 64 each')
+    rd.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state, inside (0, 1)')
+    rd.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rd.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first")
+    rd.add_argument('--minCoverage', type=int, default=1, help='reads a site needs in each sample to be compared, > 0')
+    rd.add_argument('--minValid', type=int, default=3, help='scored reads a site needs in each sample for an estimate, > 0')
+    rd.add_argument('--ciLevel', type=float, default=0.95, help='the level of the interval of delta, inside (0, 1)')
+    rd.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_diff over all compared sites')
+    rd.add_argument('--fdrAlpha', type=float, default=0.05)
+    rd.add_argument('--outFolder', default='mRes')
+    rd.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_diff.txt')
+    rd.add_argument('--device', type=int, default=0)
     return p
 
 
@@ -209,6 +229,51 @@ def validate_readllr(a):
     if not errs and not container.is_read_level(a.wrkBase1):
         errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
     return errs
+
+
+def validate_readdiff(a):
+    """the checks of readdiff, in validate_readllr's manner"""
+    errs = []
+    win = parse_llr_window(a.llrWindow)
+    if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
+        errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
+    if not 0.0 < a.prior < 1.0:
+        errs.append('Error: --prior should lie between 0 and 1, both excluded')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    if a.minCoverage < 1:
+        errs.append('Error: --minCoverage should be larger than 0')
+    if a.minValid < 1:
+        errs.append('Error: --minValid should be larger than 0')
+    if not 0.0 < a.ciLevel < 1.0:
+        errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
+    if not 0.0 < a.fdrAlpha <= 1.0:
+        errs.append('Error: --fdrAlpha should be in (0, 1]')
+    for f in (a.wrkBase1, a.wrkBase2, a.kmerModel, a.altModel):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs:
+        for opt, f in (('--wrkBase1', a.wrkBase1), ('--wrkBase2', a.wrkBase2)):
+            if not container.is_read_level(f):
+                errs.append('Error: %s %s is not a read-level container (per-position containers have no reads)' % (opt, f))
+    return errs
+
+
+def run_readdiff(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    sites = readllr.compare_reads_llr(container.load_reads(a.wrkBase1), container.load_reads(a.wrkBase2),
+                                      kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
+                                      window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions,
+                                      rescale={} if a.rescale else None, min_coverage=a.minCoverage,
+                                      diff=dict(min_valid=a.minValid, ci_level=a.ciLevel), fdr=None if a.fdr == 'none' else a.fdr,
+                                      fdr_alpha=a.fdrAlpha, device=a.device, log=(lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_site_diff.txt')
+    readllr.write_site_diff(path, sites)
+    if not quiet:
+        log('Site comparisons are saved in %s' % path)
+    return sites
 
 
 def run_readllr(a, log=print):
@@ -693,6 +758,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readdiff':
+        errs = validate_readdiff(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readdiff(a)
+        return 0
     if a.cmd == 'readllr':
         errs = validate_readllr(a)
         if errs:

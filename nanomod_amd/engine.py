@@ -771,6 +771,42 @@ def site_stoich_host(score, off, *, stride=0, min_valid=3, ci_level=0.95, max_it
     return res
 
 
+def _diff_opts(min_valid, ci_level, max_iter, tol):
+    """nmod_diff_opts from the Python arguments: the checks and the conversion of ci_level are those of _stoich_opts"""
+    o = _stoich_opts(min_valid, ci_level, max_iter, tol)
+    return L.make_diff_opts(o.max_iter, o.min_valid, o.tol, o.ci_drop)
+
+
+def _diff_shapes(npos, interval=True):
+    shapes = dict({k: ('float64', npos) for k in L.DIFF_FIELDS if interval or k not in ('delta_lo', 'delta_hi')},
+                  **{k: ('int32', npos) for k in L.DIFF_INT_FIELDS})
+    shapes['status'] = ('uint8', npos)
+    return shapes
+
+
+def site_diff_host(score0, off0, score1, off1, *, stride0=0, stride1=0, min_valid=3, ci_level=0.95, max_iter=60, tol=1e-12, interval=True,
+                   device=0):
+    """The modified shares of two samples compared per site (nmod_site_diff, include/nanomod_hip.h): per sample the float64 window
+    sums, one row per site by its `off` (int64[npos + 1]) or, with off None, its fixed stride; both samples hold the same sites in the
+    same order.  Returns a dict of numpy arrays: pi0, pi1, pi_pool, delta = pi1 - pi0, with `interval` its profile-likelihood interval
+    delta_lo, delta_hi at ci_level, stat (the likelihood-ratio statistic of pi0 = pi1) and p_diff (its chi2_1 tail), float64;
+    n_valid0, n_valid1, iters (int32); status (uint8, L.DIFF_* bits)."""
+    lib = L.load()
+    opts = _diff_opts(min_valid, ci_level, max_iter, tol)
+    score0, off0, stride0, npos = _host_score_rows(score0, off0, stride0)
+    score1, off1, stride1, npos1 = _host_score_rows(score1, off1, stride1)
+    if npos1 != npos:
+        raise ValueError('the two samples must hold the same sites: %d rows against %d' % (npos, npos1))
+    shapes = _diff_shapes(npos, interval)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodDiffOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride0 if off0 is None else 0,
+                        stride1=stride1 if off1 is None else 0)
+    _call(lib, 'nmod_site_diff', prm, npos, _np_ptr(score0), _np_ptr(off0), _np_ptr(score1), _np_ptr(off1), C.byref(opts), C.byref(out))
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1185,6 +1221,25 @@ class DeviceDetector:
         _call(self.lib, 'nmod_site_stoich', prm, npos, score.data_ptr(), _ptr(off), C.byref(opts), C.byref(o))
         return res
 
+    def site_diff(self, score0, score1, *, off0=None, off1=None, stride0=0, stride1=0, npos=None, min_valid=3, ci_level=0.95, max_iter=60,
+                  tol=1e-12, interval=True, out=None):
+        """The modified shares of two samples compared per site (nmod_site_diff, NMOD_MEM_DEVICE) on the current stream, nothing read
+        back: score0 / score1 float64 CUDA vectors, the rows of each by its `off` (int64 CUDA vector) or fixed stride, the same sites
+        in the same order (engine.match_score_rows makes them).  Returns a dict of CUDA tensors pi0, pi1, pi_pool, delta, with
+        `interval` delta_lo and delta_hi, stat, p_diff (float64), n_valid0, n_valid1, iters (int32) and status (uint8, L.DIFF_*
+        bits).  p_diff is a track fdr() takes as it is."""
+        opts = _diff_opts(min_valid, ci_level, max_iter, tol)
+        stride0, npos0 = self._score_rows('site_diff', score0, off0, stride0, npos)
+        stride1, npos1 = self._score_rows('site_diff', score1, off1, stride1, npos)
+        if npos0 != npos1:
+            raise ValueError('site_diff: the two samples must hold the same sites: %d rows against %d' % (npos0, npos1))
+        shapes = _diff_shapes(npos0, interval)
+        res = self._outputs(out, shapes, 'site_diff')
+        o = L.make_out(L.NmodDiffOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, stride0 if off0 is None else 0, stride1 if off1 is None else 0, 0, 0)
+        _call(self.lib, 'nmod_site_diff', prm, npos0, score0.data_ptr(), _ptr(off0), score1.data_ptr(), _ptr(off1), C.byref(opts), C.byref(o))
+        return res
+
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
         rc = self.lib.nmod_synth_fill(C.byref(prm), seed, pos_begin, npos, group, n_per_pos,
@@ -1439,3 +1494,41 @@ def select_tested(g0, g1, min_coverage, device=0, out_level=3, log=print, timer=
     meta = dict(chrom=chrom, strand=strand, pos=pos, base=base, n0=np.diff(h0).astype(np.int32), n1=np.diff(h1).astype(np.int32),
                 names=names, chrom_id=cid.astype(np.int32))
     return meta, sig0, off0, sig1, off1, run
+
+
+def match_score_rows(g0, g1, min_coverage, device=0):
+    """The rows of two pivoted score tracks (pivot_reads(..., val=llr_win) of two samples, the same `names`) that both hold with at
+    least min_coverage scores, in key order (nmod_select_tested), gathered as float64 (nmod_gather_tested): the inputs of
+    DeviceDetector.site_diff.  The dtype nmod_select_tested proposes is ignored: it is meant for signal levels and would narrow score
+    rows that happen to be float32-exact or to lie on the 0.001 grid.  Returns device tensors key, base (sample 1's), off0, off1,
+    sig0, sig1."""
+    import torch
+    lib = L.load()
+    if list(g0['names']) != list(g1['names']):
+        raise ValueError('both samples must be pivoted with the same chromosome names')
+    s0, s1 = g0['sig'], g1['sig']
+    if s0.dtype != torch.float64 or s1.dtype != torch.float64:
+        raise ValueError('match_score_rows takes float64 score rows (pivot_reads with val=llr_win)')
+    dev = torch.device('cuda', device)
+    prm = L.make_params(device=device, memspace=L.MEM_DEVICE, dtype=L.DTYPE_F64, stream=torch.cuda.current_stream(dev).cuda_stream)
+    n0, n1 = g0['key'].numel(), g1['key'].numel()
+    cap = min(n0, n1)
+    rows0 = torch.empty(max(cap, 1), dtype=torch.int64, device=dev); rows1 = torch.empty_like(rows0)
+    off0 = torch.empty(cap + 1, dtype=torch.int64, device=dev); off1 = torch.empty_like(off0)
+    nt, ns0, ns1, odt = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    ptr = lambda x: x.data_ptr() if x.numel() else None
+    L.check(lib.nmod_select_tested(C.byref(prm), int(min_coverage), n0, ptr(g0['key']), g0['off'].data_ptr(), ptr(s0), s0.numel(),
+                                   n1, ptr(g1['key']), g1['off'].data_ptr(), ptr(s1), s1.numel(), cap, rows0.data_ptr(),
+                                   rows1.data_ptr(), off0.data_ptr(), off1.data_ptr(), C.byref(nt), C.byref(ns0), C.byref(ns1),
+                                   C.byref(odt)), 'nmod_select_tested')
+    npos = nt.value
+    sig0 = torch.empty(ns0.value, dtype=torch.float64, device=dev); sig1 = torch.empty(ns1.value, dtype=torch.float64, device=dev)
+    run = torch.empty(npos, dtype=torch.int32, device=dev)
+    key = torch.empty(npos, dtype=torch.int64, device=dev)
+    b0 = torch.empty(npos, dtype=torch.uint8, device=dev); b1 = torch.empty_like(b0)
+    off0, off1 = off0[:npos + 1], off1[:npos + 1]
+    L.check(lib.nmod_gather_tested(C.byref(prm), npos, rows0.data_ptr(), rows1.data_ptr(), g0['off'].data_ptr(), ptr(s0),
+                                   ptr(g0['base']), g1['off'].data_ptr(), ptr(s1), ptr(g1['base']), ptr(g1['key']), L.DTYPE_F64,
+                                   off0.data_ptr(), off1.data_ptr(), ptr(sig0), ptr(sig1), ptr(run), ptr(key), ptr(b0), ptr(b1)),
+            'nmod_gather_tested')
+    return dict(key=key, base=b1, off0=off0, off1=off1, sig0=sig0, sig1=sig1, names=list(g1['names']))

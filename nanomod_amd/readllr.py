@@ -145,3 +145,118 @@ def write_site_stoich(path, sites):
            [['%.3E' % p if p == p else 'nan' for p in np.asarray(sites['p_null']).tolist()], np.asarray(sites['stoich_status']).tolist()]
     with open(path, 'w') as f:
         f.writelines('%s %s %d %s %d %d %.6f %.6f %.6f %.3f %s %d\n' % row for row in zip(*cols))
+
+
+_DIFF_KEYS = ('min_valid', 'ci_level', 'max_iter', 'tol')
+SITE_DIFF_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat', 'p_diff')
+
+
+def _checked_reads(reads, which):
+    """the arrays of a read-level set (container.READ_FIELDS) that K13 takes, checked: val, off, base"""
+    missing = [f for f in ('chrom', 'strand', 'start', 'off', 'norm_mean', 'base') if f not in reads]
+    if missing:
+        raise ValueError('%s is not a read-level set (no %s): per-position containers have no reads' % (which, ', '.join(missing)))
+    val = np.ascontiguousarray(reads['norm_mean'])
+    if val.dtype not in (np.float32, np.int16, np.float64):
+        raise ValueError('%s: norm_mean must be float32, int16 (milli-units) or float64' % which)
+    off = np.ascontiguousarray(reads['off'], dtype=np.int64)
+    nreads = len(off) - 1
+    if nreads < 0 or len(reads['start']) != nreads:
+        raise ValueError('%s: off needs nreads + 1 entries' % which)
+    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
+    if len(base) != len(val) or (nreads and (off[0] != 0 or off[-1] != len(val))):
+        raise ValueError('%s: norm_mean and base need one entry per event of off' % which)
+    return val, off, base
+
+
+def compare_reads_llr(reads0, reads1, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None,
+                      min_coverage=1, diff={}, fdr=None, fdr_alpha=0.05, names=None, device=0, log=print):
+    """Compare the modified share of every site between two read-level sets (container.READ_FIELDS): reads0 the control condition,
+    reads1 the other.  Per sample the optional rescaling (K11) and the window sums (K13) as in call_reads_llr; both are grouped by
+    position with one list of chromosome names, the sites both hold with at least min_coverage reads are matched
+    (engine.match_score_rows) and compared by nmod_site_diff (K15), all on the device and on one stream.  diff: a dict of
+    engine.site_diff_host's options (min_valid, ci_level, max_iter, tol; {} for the defaults).  fdr: None, 'bh' or 'by': p_diff goes
+    through nmod_fdr_adjust on the device at fdr_alpha and `sites` gains q.  names: the chromosome names both pivots use (default:
+    those of both sets together; a list that lacks one of them is refused).
+    Returns `sites`, one entry per matched site in the reference's row order: chrom, strand, pos, base, n_reads0, n_reads1, n_valid0,
+    n_valid1, pi0, pi1, pi_pool, delta, delta_lo, delta_hi, stat, p_diff, [q,] diff_status (uint8, L.DIFF_* bits).  One summary line
+    goes to `log`."""
+    import torch
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    if rescale is not None:
+        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
+        if unknown:
+            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    unknown = sorted(set(diff) - set(_DIFF_KEYS))
+    if unknown:
+        raise ValueError('diff: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_DIFF_KEYS)))
+    engine._diff_opts(*(diff.get(key, default) for key, default in zip(_DIFF_KEYS, (3, 0.95, 60, 1e-12))))
+    if fdr is not None:
+        engine._fdr_method(fdr)
+    if int(min_coverage) != min_coverage or int(min_coverage) < 1:
+        raise ValueError('min_coverage must be an integer >= 1, not %r' % (min_coverage,))
+    samples = [_checked_reads(reads0, 'reads0'), _checked_reads(reads1, 'reads1')]
+    both = engine.chrom_names(reads0, reads1)
+    names = both if names is None else [str(n) for n in names]
+    lacking = sorted(set(both) - set(names))
+    if lacking or names != sorted(set(names)):
+        raise ValueError('names must be the sorted chromosome names of both samples; missing or out of order: %s' % (', '.join(lacking) or 'order'))
+    engine._join_warm_up(device)
+    det = engine.DeviceDetector(device)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+    pivots = []
+    for reads, (val, off, base) in zip((reads0, reads1), samples):
+        d_val, d_off, d_base = t(val), t(off), t(base)
+        if rescale is not None:
+            d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
+        calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
+                             prior_logit=prior_logit, want=('llr_win',))
+        pivots.append(engine.pivot_reads(reads, device, names=names, val=calls['llr_win']))
+    rows = engine.match_score_rows(pivots[0], pivots[1], int(min_coverage), device)
+    res = det.site_diff(rows['sig0'], rows['sig1'], off0=rows['off0'], off1=rows['off1'], **diff)
+    q = None
+    if fdr is not None:
+        (q,), _ = det.fdr(res, tracks=('p_diff',), method=fdr, alpha=fdr_alpha)
+    key = rows['key'].cpu().numpy()
+    nm = np.array(names, dtype=str)
+    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                 pos=key & ((1 << 40) - 1), base=rows['base'].cpu().numpy().view('S1').astype('U1'),
+                 n_reads0=np.diff(rows['off0'].cpu().numpy()).astype(np.int32), n_reads1=np.diff(rows['off1'].cpu().numpy()).astype(np.int32),
+                 n_valid0=res['n_valid0'].cpu().numpy(), n_valid1=res['n_valid1'].cpu().numpy(),
+                 **{f: res[f].cpu().numpy() for f in SITE_DIFF_FIELDS})
+    if q is not None:
+        sites['q'] = q.cpu().numpy()
+    sites['diff_status'] = res['status'].cpu().numpy()
+    est = (sites['diff_status'] & L.DIFF_NO_ESTIMATE) == 0
+    log('readdiff: %d and %d read(s); %d site(s) in both samples with at least %d read(s), %d with an estimate, %d with an interval of '
+        'delta that excludes 0%s'
+        % (len(samples[0][1]) - 1, len(samples[1][1]) - 1, len(key), int(min_coverage), int(est.sum()),
+           int((est & ((sites['delta_lo'] > 0.0) | (sites['delta_hi'] < 0.0))).sum()),
+           '' if q is None else '; %d with q <= %g (%s)' % (int((sites['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
+    return sites
+
+
+def write_site_diff(path, sites):
+    """<FileID>_site_diff.txt: per site 'chrom strand pos+1 base n_reads0 n_reads1 n_valid0 n_valid1 pi0 pi1 pi_pool delta delta_lo
+    delta_hi stat p_diff [q] status' as '%s %s %d %s %d %d %d %d' + six '%.6f' + '%.3f %.3E [%.3E] %d' (the position 1-based; 'nan' as
+    Python spells it where the site has no estimate; `sites` of compare_reads_llr)"""
+    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
+    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
+            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
+           [np.asarray(sites[f]).tolist() for f in ('n_reads0', 'n_reads1', 'n_valid0', 'n_valid1', 'pi0', 'pi1', 'pi_pool', 'delta',
+                                                    'delta_lo', 'delta_hi', 'stat')] + \
+           [sci(sites['p_diff'])] + ([sci(sites['q'])] if 'q' in sites else []) + [np.asarray(sites['diff_status']).tolist()]
+    fmt = '%s %s %d %s %d %d %d %d %.6f %.6f %.6f %.6f %.6f %.6f %.3f %s ' + ('%s ' if 'q' in sites else '') + '%d\n'
+    with open(path, 'w') as f:
+        f.writelines(fmt % row for row in zip(*cols))
