@@ -10,7 +10,11 @@
  * CU count and of each kernel's occupancy (atomics, idempotent), and one HIP
  * memory pool per device, owned by the library, from which the scratch of the
  * large-position pass is allocated stream-ordered (freed slabs stay cached in
- * that pool until nmod_trim_scratch(); the device's default pool is not touched),
+ * that pool until nmod_trim_scratch(); the device's default pool is not touched) — the NMOD_MEM_DEVICE entries that promise not
+ * to synchronise keep the slab of a call parked under its (device, stream) for the next call on that stream instead of freeing it,
+ * up to 2 slabs for each of up to 32 streams, a stream whose parked slabs are idle giving way to a new one (giving a reused block
+ * back to a HIP pool while its previous free is still queued makes hipFreeAsync wait on the host; with 32 other streams all busy a
+ * slab is freed that way all the same, and a call may then wait for the stream's previous call of the same scratch size) —
  * and the four tunables of nmod_host_pipeline_config (atomics; they change how a
  * host-resident batch is chunked and copied, never a result).  The library
  * reads no environment variable that changes which kernel runs: the choice
@@ -278,8 +282,10 @@ const char* nmod_build_info(void);
  * NMOD_ERR_TOO_LARGE, or with NMOD_FLAG_DEEP and both groups within NMOD_MAX_DEEP "deep_rank_kernel<f32|i16|f64>". */
 int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char* buf, int32_t buflen);
 
-/* Returns the slabs cached in the library's scratch pool of `device` to the driver (see the header comment), and frees the
- * pinned ring + streams the NMOD_MEM_HOST pipeline caches for it. */
+/* Returns the slabs cached in the library's scratch pool of `device` to the driver (see the header comment), those parked per stream
+ * included, and frees the pinned ring + streams the NMOD_MEM_HOST pipeline caches for it.  Synchronises the device when a slab is
+ * parked, and returns once the parked bytes show as free in hipMemGetInfo (it waits at most 0.1 s for that): call it when no other
+ * thread has work of the library in flight on the device. */
 int nmod_trim_scratch(int32_t device);
 
 /* Replaces combin_pvalues / get_combin_pvalue on a whole KS track

@@ -89,7 +89,8 @@ inline unsigned persistent_grid(int64_t work, int64_t per_block, int64_t cap) {
 }
 
 // The device slab of one call, planned before it is allocated: every take() reserves a 256-byte-aligned range, commit()
-// allocates the sum (a slab of no bytes still allocates something) on the caller's stream, finish() gives it back.
+// allocates the sum (a slab of no bytes still allocates something) on the caller's stream, finish() gives it back (a device-memspace
+// call parks it for the next call on the stream: scratch_pool.hpp).
 // in() / out() stage one argument of a host-memspace call: the range, the copy to (in) or from (out) the device, and the
 // repointing of the argument to its device copy are declared by that one statement.  For a device-memspace call, and for
 // an argument the caller left null, they do nothing.
@@ -100,7 +101,7 @@ struct Slab {
   Staged staged[kMaxStaged];
   DevScratch mem;
 
-  explicit Slab(bool host_memspace) : host(host_memspace) {}
+  explicit Slab(bool host_memspace) : host(host_memspace) { mem.park = !host_memspace; }   // a device call must not wait: scratch_pool.hpp
   size_t take(size_t b) { const size_t o = bytes; bytes += (size_t)align256((int64_t)b); return o; }
   template <class T> T* at(size_t o) const { return reinterpret_cast<T*>(static_cast<char*>(mem.p) + o); }
 

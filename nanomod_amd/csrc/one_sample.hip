@@ -354,6 +354,8 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
   const PosListSpace<kOneClasses> lists(slab, np);
   const bool own_d = want_comb && !out->ks_d, own_p = want_comb && !out->ks_p;
   const size_t o_ksd = slab.take(own_d ? np * 8 : 0), o_ksp = slab.take(own_p ? np * 8 : 0);
+  const bool own_c = want_comb && (!out->comb_st || !out->comb_p);             // a member of the combined pair the caller left out
+  const size_t o_spare = slab.take(own_c ? np * 8 : 0);
   slab.in(a.sig, tot * esz); slab.in(a.off, (np + 1) * 8);
   slab.in(a.ref_mean, np * 8); slab.in(a.ref_sd, np * 8); slab.in(a.ref_n, np * 4);
   if (want_comb) slab.in(d_run, np * 4);
@@ -375,15 +377,10 @@ extern "C" int nmod_one_sample(const nmod_params* prm, int64_t npos, const void*
     cp.struct_size = (int32_t)sizeof(cp); cp.device = prm->device; cp.stream = prm->stream; cp.memspace = NMOD_MEM_DEVICE;
     cp.dtype = NMOD_DTYPE_F64; cp.method = prm->method; cp.nb = prm->nb; cp.weights_dif = prm->weights_dif;
     double* cst = a.out.comb_st; double* cpv = a.out.comb_p;
-    DevScratch spare;
-    if (!cst || !cpv) {
-      NMOD_HIP(spare.alloc(np * 8, stream, prm->device));
-      if (!cst) cst = (double*)spare.p;
-      if (!cpv) cpv = (double*)spare.p;
-    }
+    if (!cst) cst = slab.at<double>(o_spare);
+    if (!cpv) cpv = slab.at<double>(o_spare);
     rc = nmod_combine_track(&cp, npos, a.out.ks_d, a.out.ks_p, d_run, cst, cpv);
     if (rc != NMOD_OK) return rc;
-    NMOD_HIP(spare.release(stream));
   }
   NMOD_HIP(slab.finish(stream));
   return NMOD_OK;

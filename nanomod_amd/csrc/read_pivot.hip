@@ -655,6 +655,7 @@ extern "C" int nmod_gather_tested(const nmod_params* prm, int64_t ntested, const
     if (rc != NMOD_OK) return rc;
   }
   DevScratch scr;
+  scr.park = true;                                  // enqueued only: the slab is kept for the stream's next call (scratch_pool.hpp)
   const size_t b = align256(ntested * 8);
   NMOD_HIP(scr.alloc(b + align256((scan_blocks(ntested) + 1) * 8), s, prm->device));
   int64_t* brk = (int64_t*)scr.p;

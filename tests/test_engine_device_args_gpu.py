@@ -1,5 +1,5 @@
-"""The argument layer of DeviceDetector's secondary entries (fdr, mix, one_sample, kmer_model, rescale_reads, read_calls, site_calls)
-on the GPU: what each refuses with ValueError before the library is called (a side vector of the wrong dtype or length, a CPU tensor,
+"""The argument layer of DeviceDetector's secondary entries (fdr, mix, one_sample, kmer_model, rescale_reads, read_calls, site_calls,
+read_llr, site_llr, site_stoich, site_diff) on the GPU: what each refuses with ValueError before the library is called (a side vector of the wrong dtype or length, a CPU tensor,
 a non-contiguous slice, a malformed `out=` dict), which entries also refuse a tensor of two dimensions and which take it, that a
 well-formed `out=` dict comes back as the same objects with the same values, and that each entry agrees bit for bit with its *_host
 counterpart on the same data (both reach the same kernels).  Tiny shapes: 4 positions of 10 float32 samples, 4 codes, 3 reads of 6
@@ -49,9 +49,16 @@ class Ctx:
         h['score'] = rng.uniform(size=NPOS * ROW)
         h['score'][::7] = np.nan
         h['score'][3::5] *= 0.01
+        # a second table for read_llr, and window sums of two samples for site_llr, site_stoich and site_diff
+        h['alt_mean'] = h['mean'] + np.array([0.5, -0.4, 0.6, 0.3])
+        h['alt_sd'] = np.array([0.3, 0.25, 0.2, 0.35])
+        for name, share in (('lscore0', 0.2), ('lscore1', 0.7)):
+            h[name] = np.where(rng.uniform(size=NPOS * ROW) < share, 4.0, -4.0) + 2.0 * rng.normal(size=NPOS * ROW)
+            h[name][5::11] = np.nan
         self.h = h
         self.d = {k: torch.from_numpy(v).to('cuda:0') for k, v in h.items()}
         self.model = dict(k=1, center=0, mean=h['mean'], sd=h['sd'])
+        self.alt = dict(k=1, center=0, mean=h['alt_mean'], sd=h['alt_sd'])
 
     def host(self, res):
         self.torch.cuda.synchronize()
@@ -316,3 +323,169 @@ def test_site_calls_agrees_with_host_and_out(ctx, layout):
     for out in bad:
         with pytest.raises(ValueError):
             call(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- read_llr
+LLR_OPTS = dict(window=(1, 1), thr=1.0, prior_logit=0.25)
+LLR_WAYS = READ_WAYS + [(n, w) for n in ('alt_mean', 'alt_sd') for w in WAYS]
+
+
+def sentinel(out, torch):
+    """the tensors of an out dict overwritten with values no entry writes there"""
+    for t in out.values():
+        t.fill_(-12345.0 if t.dtype.is_floating_point else 0xA5 if t.dtype == torch.uint8 else -77)
+    return out
+
+
+def _llr(ctx, want=('llr', 'llr_win', 'p_mod'), **kw):
+    d = ctx.d
+    a = dict(val=d['val'], off=d['off'], base=d['base'], mean=d['mean'], sd=d['sd'], alt_mean=d['alt_mean'], alt_sd=d['alt_sd'], out=None)
+    a.update(kw)
+    return ctx.det.read_llr(a['val'], a['off'], a['base'], a['mean'], a['sd'], a['alt_mean'], a['alt_sd'], 1, 0, want=want, out=a['out'], **LLR_OPTS)
+
+
+@pytest.mark.parametrize('name,way', LLR_WAYS)
+def test_read_llr_refuses(ctx, name, way):
+    with pytest.raises(ValueError):
+        _llr(ctx, **{name: wrong(ctx.d[name], ctx.torch)[way]})
+
+
+@pytest.mark.parametrize('name', ['mean', 'sd', 'alt_mean', 'alt_sd', 'val', 'base'])
+def test_read_llr_refuses_two_dimensions(ctx, name):
+    with pytest.raises(ValueError):                                       # read_llr asks for dim() == 1
+        _llr(ctx, **{name: two_dim(ctx.d[name])})
+
+
+@pytest.mark.parametrize('want', [('llr_win',), ('llr', 'llr_win', 'p_mod')])
+def test_read_llr_agrees_with_host_and_out(ctx, want):
+    h, torch = ctx.h, ctx.torch
+    exp = ctx.engine.read_llr_host(h['val'], h['off'], h['base'], ctx.model, ctx.alt, want=want, **LLR_OPTS)
+    first = _llr(ctx, want)
+    assert_same_dict(ctx.host(first), exp)
+    assert set(exp) == set(want) | {'n_sites', 'n_mod', 'n_can', 'status'} and exp['n_sites'].sum() == NEV and exp['n_can'].sum() > 0
+    again = _llr(ctx, want, out=sentinel(first, torch))
+    assert again is first and all(again[k] is first[k] for k in exp)
+    assert_same_dict(ctx.host(again), exp)
+    bad = [dict(first, status=first['status'].to(torch.int32)), dict(first, llr_win=first['llr_win'][:-1]),
+           dict(first, n_sites=first['n_sites'].cpu()), {k: v for k, v in first.items() if k != 'n_can'}]
+    for out in bad:
+        with pytest.raises(ValueError):
+            _llr(ctx, want, out=out)
+
+
+# ---------------------------------------------------------------------------------------------- site_llr and site_stoich
+# (device method, host counterpart, options of both, an output of one element per position, an output a malformed dict leaves out)
+SITE_ENTRIES = {
+    'site_llr': ('site_llr', 'site_llr_host', dict(thr=1.0), 'frac', 'n_can'),
+    'site_stoich': ('site_stoich', 'site_stoich_host', dict(min_valid=2), 'pi', 'p_null'),
+    'site_stoich_resp': ('site_stoich', 'site_stoich_host', dict(min_valid=2, resp=True), 'pi', 'resp'),
+}
+
+
+def _site(ctx, entry, score, **kw):
+    method, _, opts, _, _ = SITE_ENTRIES[entry]
+    return getattr(ctx.det, method)(score, **dict(opts, **kw))
+
+
+@pytest.mark.parametrize('entry', list(SITE_ENTRIES))
+@pytest.mark.parametrize('way', WAYS)
+def test_site_rows_refuse(ctx, entry, way):
+    score = wrong(ctx.d['lscore1'], ctx.torch)[way]
+    with pytest.raises(ValueError):                                       # ('length': 41 scores are no 5 rows of 10)
+        _site(ctx, entry, score, stride=ROW, npos=NPOS + 1 if way == 'length' else None)
+
+
+@pytest.mark.parametrize('entry', list(SITE_ENTRIES))
+@pytest.mark.parametrize('way', ['dtype', 'cpu', 'strided'])
+def test_site_rows_refuse_off(ctx, entry, way):
+    with pytest.raises(ValueError):
+        _site(ctx, entry, ctx.d['lscore1'], off=wrong(ctx.d['row_off'], ctx.torch)[way])
+
+
+@pytest.mark.parametrize('entry', list(SITE_ENTRIES))
+def test_site_rows_two_dimensions(ctx, entry):
+    _, host_fn, opts, _, _ = SITE_ENTRIES[entry]
+    with pytest.raises(ValueError):                                       # the entries ask for dim() == 1 of the scores ...
+        _site(ctx, entry, two_dim(ctx.d['lscore1']), stride=ROW)
+    exp = getattr(ctx.engine, host_fn)(ctx.h['lscore1'], ctx.h['row_off'], **opts)
+    got = _site(ctx, entry, ctx.d['lscore1'], off=ctx.d['row_off'].view(1, NPOS + 1))              # ... not of the offsets
+    assert_same_dict(ctx.host(got), exp)
+
+
+@pytest.mark.parametrize('entry', list(SITE_ENTRIES))
+@pytest.mark.parametrize('layout', ['csr', 'stride'])
+def test_site_rows_agree_with_host_and_out(ctx, entry, layout):
+    h, d, torch = ctx.h, ctx.d, ctx.torch
+    _, host_fn, opts, per_pos, left_out = SITE_ENTRIES[entry]
+    exp = getattr(ctx.engine, host_fn)(h['lscore1'], h['row_off'] if layout == 'csr' else None, stride=ROW, **opts)
+    call = lambda out=None: _site(ctx, entry, d['lscore1'], off=d['row_off'] if layout == 'csr' else None, stride=ROW, out=out)
+    first = call()
+    assert_same_dict(ctx.host(first), exp)
+    assert exp['n_valid'].sum() == np.isfinite(h['lscore1']).sum() and np.isfinite(exp[per_pos]).any()
+    again = call(sentinel(first, torch))
+    assert again is first and all(again[k] is first[k] for k in exp)
+    assert_same_dict(ctx.host(again), exp)
+    bad = [dict(first, **{per_pos: first[per_pos].float()}), dict(first, n_valid=torch.cat([first['n_valid'], first['n_valid'][:1]])),
+           dict(first, n_valid=first['n_valid'].cpu()), {k: v for k, v in first.items() if k != left_out}]
+    for out in bad:
+        with pytest.raises(ValueError):
+            call(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------- site_diff
+DIFF_LAYOUTS = {'csr': (True, True), 'stride': (False, False), 'csr_and_stride': (True, False), 'stride_and_csr': (False, True)}
+
+
+def _diff(ctx, layout='csr', interval=True, **kw):
+    d = ctx.d
+    csr0, csr1 = DIFF_LAYOUTS[layout]
+    a = dict(score0=d['lscore0'], score1=d['lscore1'], off0=d['row_off'] if csr0 else None, off1=d['row_off'] if csr1 else None, out=None, npos=None)
+    a.update(kw)
+    return ctx.det.site_diff(a['score0'], a['score1'], off0=a['off0'], off1=a['off1'], stride0=ROW, stride1=ROW, npos=a['npos'], min_valid=2,
+                             interval=interval, out=a['out'])
+
+
+@pytest.mark.parametrize('name', ['score0', 'score1'])
+@pytest.mark.parametrize('way', WAYS)
+def test_site_diff_refuses(ctx, way, name):
+    score = wrong(ctx.d['l' + name], ctx.torch)[way]
+    with pytest.raises(ValueError):                                       # ('length': 41 scores are no 5 rows of 10)
+        _diff(ctx, 'stride', **{name: score, 'npos': NPOS + 1 if way == 'length' else None})
+
+
+@pytest.mark.parametrize('name', ['off0', 'off1'])
+@pytest.mark.parametrize('way', WAYS)
+def test_site_diff_refuses_off(ctx, way, name):
+    with pytest.raises(ValueError):                                       # ('length': the two samples no longer hold the same sites)
+        _diff(ctx, 'csr', **{name: wrong(ctx.d['row_off'], ctx.torch)[way]})
+
+
+def test_site_diff_two_dimensions(ctx):
+    for name in ('score0', 'score1'):
+        with pytest.raises(ValueError):                                   # site_diff asks for dim() == 1 of the scores ...
+            _diff(ctx, 'stride', **{name: two_dim(ctx.d['l' + name])})
+    exp = ctx.engine.site_diff_host(ctx.h['lscore0'], ctx.h['row_off'], ctx.h['lscore1'], ctx.h['row_off'], min_valid=2)
+    got = _diff(ctx, 'csr', off0=ctx.d['row_off'].view(1, NPOS + 1), off1=ctx.d['row_off'].view(NPOS + 1, 1))   # ... not of the offsets
+    assert_same_dict(ctx.host(got), exp)
+
+
+@pytest.mark.parametrize('interval', [True, False])
+@pytest.mark.parametrize('layout', list(DIFF_LAYOUTS))
+def test_site_diff_agrees_with_host_and_out(ctx, layout, interval):
+    h, torch = ctx.h, ctx.torch
+    csr0, csr1 = DIFF_LAYOUTS[layout]
+    exp = ctx.engine.site_diff_host(h['lscore0'], h['row_off'] if csr0 else None, h['lscore1'], h['row_off'] if csr1 else None, stride0=ROW,
+                                    stride1=ROW, min_valid=2, interval=interval)
+    first = _diff(ctx, layout, interval)
+    assert_same_dict(ctx.host(first), exp)
+    assert ('delta_lo' in exp) == ('delta_hi' in exp) == interval and np.isfinite(exp['p_diff']).any() and np.nanmin(exp['p_diff']) < 0.05
+    again = _diff(ctx, layout, interval, out=sentinel(first, torch))
+    assert again is first and all(again[k] is first[k] for k in exp)
+    assert_same_dict(ctx.host(again), exp)
+    bad = [dict(first, p_diff=first['p_diff'].float()), dict(first, iters=torch.cat([first['iters'], first['iters'][:1]])),
+           dict(first, status=first['status'].cpu()), {k: v for k, v in first.items() if k != 'pi_pool'}]
+    if interval:
+        bad.append({k: v for k, v in first.items() if k != 'delta_hi'})
+    for out in bad:
+        with pytest.raises(ValueError):
+            _diff(ctx, layout, interval, out=out)
