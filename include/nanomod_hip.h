@@ -832,6 +832,81 @@ int nmod_site_diff(const nmod_params* prm, int64_t npos, const double* score0, c
                    const double* score1, const int64_t* off1 /* or prm->stride1 */,
                    const nmod_diff_opts* opts, const nmod_diff_out* out);
 
+/* Same-read co-occurrence of modification calls at pairs of sites: per pair the 2 x 2 table of the reads that have a call at both
+ * sites, its log odds ratio, phi and the two-sided exact test (K16; the reference project has no such step).  K11 .. K15 reduce over
+ * the reads of one position; this entry keeps the read: it walks the reads and counts, per pair of candidate sites, the reads by
+ * their two calls.  Memspaces, the NULL and struct_size rules: those of nmod_read_llr and nmod_site_stoich.
+ *   Inputs.  Reads in nmod_pivot_reads' layout: nreads, cs[r] (int32, 2 * chrom index + (strand == '-')), start[r] (int64, >= 0),
+ *     roff[nreads + 1] (int64); score: float64, one per event in read direction (K13's llr_win).  Candidate sites: nsites keys
+ *     (int64, cs << 40 | pos), strictly ascending.  Event i of a read of n events lies at position start + i on '+' and at
+ *     start + n - 1 - i on '-' (nmod_pivot_reads' rule); a read COVERS the sites whose cs is its own and whose pos lies in
+ *     [start, start + n - 1].
+ *   The CALL of read r at a site it covers, with L the score of its event at that position:  MOD (1) iff L >= thr;  CAN (0) iff
+ *     L <= -thr;  otherwise none (a NaN is none).  thr is finite and > 0, as in K13.
+ *   PAIRS.  Site b is a partner of site a iff b > a, key_b >> 40 == key_a >> 40 and pos_b - pos_a <= max_dist, max_dist in
+ *     1 .. NMOD_PAIRS_MAX_DIST.  The partners of a are contiguous in key order: pair (a, b) has the index poff[a] + (b - a - 1),
+ *     poff[nsites + 1] (int64) being the exclusive scan of the partner counts, poff[nsites] = npairs.
+ *   nmod_pair_index computes poff (on prm->stream) and synchronises the stream once to return *npairs_out (a host pointer), as
+ *     nmod_select_tested does.  NMOD_ERR_INVALID_ARG: nsites outside 0 .. 2^31 - 2, max_dist out of range, a NULL pointer, host keys
+ *     that do not strictly ascend (nothing is enqueued), npairs > 2^31 - 1 (poff is written by then).  Device keys are not checked.
+ *     Reads struct_size, device, stream, memspace of prm.
+ *   nmod_site_pairs.  A read takes part in pair j = (a, b) iff it has a call at both sites: counts[4 j + 2 call_a + call_b] += 1.
+ *     The table of pair j is (n11, n10, n01, n00) = counts[4 j + 3], [4 j + 2], [4 j + 1], [4 j]: the first index is site a's call.
+ *     counts are int32, zeroed by the entry on the stream.  With N = n11 + n10 + n01 + n00, r1 = n11 + n10, r0 = N - r1,
+ *     c1 = n11 + n01, c0 = N - c1:
+ *       log_or = log(((n11 + 0.5) (n00 + 0.5)) / ((n10 + 0.5) (n01 + 0.5)))       (both products exact below 2^26 reads)
+ *       se     = sqrt(((1 / (n11 + 0.5) + 1 / (n10 + 0.5)) + 1 / (n01 + 0.5)) + 1 / (n00 + 0.5))
+ *       phi    = double(n11 n00 - n10 n01) / sqrt(double(r1 r0) * double(c1 c0)), the integer products in 64 bits; NaN iff a margin is 0
+ *       first[j] = a, second[j] = b (int32)
+ *       p_fisher, the two-sided exact test conditional on the margins:  lo = max(0, r1 + c1 - N), hi = min(r1, c1), the support
+ *         has L = hi - lo + 1 tables x = n11;  mode = ((r1 + 1) (c1 + 1)) / (N + 2) in 64-bit integer division, clamped into
+ *         [lo, hi];  w(mode) = 1;  w(x + 1) = w(x) * (double((c1 - x) (r1 - x)) / double((x + 1) (N - c1 - r1 + x + 1))) upwards and
+ *         w(x - 1) = w(x) * (double(x (N - c1 - r1 + x)) / double((c1 - x + 1) (r1 - x + 1))) downwards: one correctly rounded division
+ *         and one multiplication per step.  The integer products are taken in 64 bits and are exact as doubles while N < 2^26 (they
+ *         stay below 2^52); up to 2^31 - 1 reads they still fit 64 bits and are rounded once more.  With cut = w(n11) * (1 + 1e-7) (the
+ *         tie slack of R's fisher.test):  p = min(T / S, 1), then max(p, DBL_MIN), where S is the sum of every w(x) and T the sum of
+ *         those with w(x) <= cut.  L = 1 gives p = 1.  No weight overflows: every ratio on the far side of the mode is <= 1; a
+ *         w(n11) that underflows to 0 gives DBL_MIN.
+ *       Orders.  L <= NMOD_PAIRS_THREAD_MAX (one thread): U = the w(x) above the mode added in ascending x from 0.0, D = those below
+ *         it in descending x from 0.0, S = (1.0 + U) + D; T likewise over the weights <= cut (the mode's 1.0 replaced by 0.0 when
+ *         1.0 > cut).  Beyond (one wave): the elements of each side are dealt to the lanes in tiles of 64, element mode + 1 + 64 t +
+ *         lane (mode - 1 - 64 t - lane below), an element outside the support having the ratio 0; the weights of a tile are the
+ *         inclusive product scan of its ratios over the lanes (steps 1, 2, 4, 8, 16, 32: v[l] = v[l] * v[l - d] for l >= d, the old
+ *         values) times the carry, the weight of lane 63 of the tile before (1.0 for the first).  A lane adds its weights in tile
+ *         order, the side above first, then the side below; the 64 lane sums are added as the library's wave sum does (partners
+ *         l ^ 1, l ^ 2, then the mirror of each 8 lanes, then of each 16; the four rows of 16 in order from 0.0); S = 1.0 + that
+ *         sum, T likewise.  The class of a pair depends on its own L alone: a pair's bits depend on its table alone.
+ *     Status: NMOD_PAIRS_TOO_FEW: N < opts->min_reads (min_reads >= 1): log_or, se, phi, p_fisher are NaN, the counts (and first,
+ *       second) are still written.  NMOD_PAIRS_DEGENERATE: a margin is 0: phi is NaN and p_fisher = 1 (NaN under TOO_FEW).
+ *     Outputs (a NULL member is skipped; requesting fewer never changes the bits of the others): counts int32[4 npairs]; first,
+ *       second int32[npairs]; log_or, se, phi, p_fisher double[npairs]; status uint8[npairs].  p_fisher is per pair and unadjusted:
+ *       nmod_fdr_adjust takes it (a NaN is left out of the family).
+ *     opts->flags: NMOD_PAIRS_FORCE_DIRECT: the read kernel adds to the counters in device memory even where the call would keep
+ *       its table in LDS (npairs <= NMOD_PAIRS_LDS_MAX: every workgroup sums into an LDS table and flushes its non-zero counters at
+ *       the end).  Integer atomics in both: the counts do not depend on the form, the order of the reads, or the memspace.
+ *     Reads struct_size, device, stream, memspace of prm.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read
+ *     and no synchronisation; key, poff and the reads are not checked (an event index outside its read or a pair index outside
+ *     [0, npairs) is skipped).  NMOD_MEM_HOST: one staged copy.  nreads == 0: zero counts; npairs == 0: NMOD_OK, nothing to do.
+ *     NMOD_ERR_INVALID_ARG before any device work: nreads outside 0 .. 2^31 - 1, nsites outside 0 .. 2^31 - 2, npairs outside
+ *     0 .. 2^31 - 1, thr not finite or <= 0, min_reads < 1, unknown flags, a NULL input that is needed, host offsets that decrease,
+ *     host keys that do not strictly ascend, host poff that does not start at 0, ascend and end at npairs.
+ * Limits: hard calls only, no posterior-weighted table; pairs only; both sites on one (chrom, strand); a molecule sequenced twice
+ * counts twice. */
+#define NMOD_PAIRS_MAX_DIST 65536          /* largest max_dist */
+#define NMOD_PAIRS_LDS_MAX 2048            /* pairs up to which the read kernel keeps the call's table in LDS (32 KiB) */
+#define NMOD_PAIRS_THREAD_MAX 64           /* tables of a pair's support up to which one thread computes p_fisher (a wave beyond) */
+#define NMOD_PAIRS_FORCE_DIRECT 1          /* opts->flags */
+enum { NMOD_PAIRS_TOO_FEW = 1, NMOD_PAIRS_DEGENERATE = 2 };
+typedef struct nmod_pairs_opts { int32_t struct_size, min_reads, flags, reserved; double thr; } nmod_pairs_opts;
+typedef struct nmod_pairs_out { int32_t struct_size; int32_t reserved;
+  int32_t *counts, *first, *second; double *log_or, *se, *phi, *p_fisher; uint8_t* status;
+} nmod_pairs_out;
+int nmod_pair_index(const nmod_params* prm, int64_t nsites, const int64_t* key, int64_t max_dist, int64_t* poff_out,
+                    int64_t* npairs_out /* host */);
+int nmod_site_pairs(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                    const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
+                    const nmod_pairs_opts* opts, const nmod_pairs_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

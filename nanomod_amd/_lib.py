@@ -262,6 +262,33 @@ def make_diff_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP_9
 make_diff_out = functools.partial(make_out, NmodDiffOut)
 
 
+PAIRS_MAX_DIST = 65536      # nmod_pair_index: largest max_dist
+PAIRS_LDS_MAX = 2048        # nmod_site_pairs: pairs up to which the read kernel keeps the call's table in LDS
+PAIRS_THREAD_MAX = 64       # nmod_site_pairs: tables of a pair's support up to which one thread computes p_fisher (a wave beyond)
+PAIRS_FORCE_DIRECT = 1      # nmod_pairs_opts.flags
+PAIRS_TOO_FEW, PAIRS_DEGENERATE = 1, 2
+PAIRS_INT_FIELDS = ('counts', 'first', 'second')
+PAIRS_FIELDS = ('log_or', 'se', 'phi', 'p_fisher')
+
+
+class NmodPairsOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'min_reads', 'flags', 'reserved')] + [('thr', C.c_double)]
+
+
+class NmodPairsOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in PAIRS_INT_FIELDS + PAIRS_FIELDS + ('status',)]
+
+
+def make_pairs_opts(thr=2.5, min_reads=10, flags=0):
+    o = NmodPairsOpts()
+    o.struct_size = C.sizeof(NmodPairsOpts)
+    o.min_reads, o.flags, o.thr = int(min_reads), int(flags), float(thr)
+    return o
+
+
+make_pairs_out = functools.partial(make_out, NmodPairsOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -328,6 +355,9 @@ _SIGNATURES = {
     'nmod_site_stoich': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NmodStoichOpts), C.POINTER(NmodStoichOut)]),
     'nmod_site_diff': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodDiffOpts),
                                  C.POINTER(NmodDiffOut)]),
+    'nmod_pair_index': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    'nmod_site_pairs': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.POINTER(NmodPairsOpts), C.POINTER(NmodPairsOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -194,6 +194,29 @@ def build_parser():
     rd.add_argument('--outFolder', default='mRes')
     rd.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_diff.txt')
     rd.add_argument('--device', type=int, default=0)
+    rp = sub.add_parser('readpairs', help='same-read co-occurrence of modification calls at pairs of nearby sites of one read-level sample '
+                        'on the device: per pair the 2 x 2 table of the reads called at both sites, log odds ratio, phi and the exact test')
+    rp.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rp.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rp.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
+    rp.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rp.add_argument('--sites', default='stoich', help="'stoich': the positions whose modified share (readllr --siteFraction) has a "
+                    "Benjamini-Hochberg q of at most --siteAlpha; or a FILE of lines 'chrom strand pos' (1-based; the first three "
+                    'columns of <FileID>_site_stoich.txt work)')
+    rp.add_argument('--maxDist', type=int, default=100, help='pairs of sites up to this far apart, 1 .. %d' % L.PAIRS_MAX_DIST)
+    rp.add_argument('--llrThreshold', type=float, default=2.5, help='a read is called at a site when its window sum reaches +- this, > 0')
+    rp.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
+                    'before and after, 0 .. 64 each')
+    rp.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state, inside (0, 1)')
+    rp.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rp.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first")
+    rp.add_argument('--minReads', type=int, default=10, help='reads called at both sites a pair needs for its statistics, > 0')
+    rp.add_argument('--siteAlpha', type=float, default=0.05, help="--sites stoich: the level of the sites' q-values, in (0, 1]")
+    rp.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_fisher over all pairs')
+    rp.add_argument('--fdrAlpha', type=float, default=0.05)
+    rp.add_argument('--outFolder', default='mRes')
+    rp.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_pairs.txt')
+    rp.add_argument('--device', type=int, default=0)
     return p
 
 
@@ -257,6 +280,52 @@ def validate_readdiff(a):
             if not container.is_read_level(f):
                 errs.append('Error: %s %s is not a read-level container (per-position containers have no reads)' % (opt, f))
     return errs
+
+
+def validate_readpairs(a):
+    """the checks of readpairs, in validate_readllr's manner"""
+    errs = []
+    win = parse_llr_window(a.llrWindow)
+    if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
+        errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
+    if not 0.0 < a.llrThreshold < float('inf'):
+        errs.append('Error: --llrThreshold should be finite and larger than 0')
+    if not 0.0 < a.prior < 1.0:
+        errs.append('Error: --prior should lie between 0 and 1, both excluded')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    if not 1 <= a.maxDist <= L.PAIRS_MAX_DIST:
+        errs.append('Error: --maxDist should be in 1 .. %d' % L.PAIRS_MAX_DIST)
+    if a.minReads < 1:
+        errs.append('Error: --minReads should be larger than 0')
+    if not 0.0 < a.siteAlpha <= 1.0:
+        errs.append('Error: --siteAlpha should be in (0, 1]')
+    if not 0.0 < a.fdrAlpha <= 1.0:
+        errs.append('Error: --fdrAlpha should be in (0, 1]')
+    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_readpairs(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
+    pairs = readllr.cooccur_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel),
+                                      kmermodel.load_kmer_model(a.altModel), sites=sites, max_dist=a.maxDist, thr=a.llrThreshold,
+                                      min_reads=a.minReads, window=parse_llr_window(a.llrWindow), prior=a.prior,
+                                      min_positions=a.minPositions, rescale={} if a.rescale else None,
+                                      fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, site_alpha=a.siteAlpha, device=a.device,
+                                      log=(lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_site_pairs.txt')
+    readllr.write_site_pairs(path, pairs)
+    if not quiet:
+        log('Site pairs are saved in %s' % path)
+    return pairs
 
 
 def run_readdiff(a, log=print):
@@ -758,6 +827,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readpairs':
+        errs = validate_readpairs(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readpairs(a)
+        return 0
     if a.cmd == 'readdiff':
         errs = validate_readdiff(a)
         if errs:

@@ -807,6 +807,92 @@ def site_diff_host(score0, off0, score1, off1, *, stride0=0, stride1=0, min_vali
     return res
 
 
+PAIRS_OUTPUTS = L.PAIRS_INT_FIELDS + L.PAIRS_FIELDS + ('status',)
+
+
+def _check_max_dist(max_dist):
+    if int(max_dist) != max_dist or not 1 <= int(max_dist) <= L.PAIRS_MAX_DIST:
+        raise ValueError('max_dist must be an integer in 1 .. %d, not %r' % (L.PAIRS_MAX_DIST, max_dist))
+    return int(max_dist)
+
+
+def _pairs_opts(thr, min_reads, force_direct, want):
+    """nmod_pairs_opts from the Python arguments; ValueError for what the C entry refuses"""
+    thr = _check_thr(thr)
+    if int(min_reads) != min_reads or int(min_reads) < 1:
+        raise ValueError('min_reads must be an integer >= 1, not %r' % (min_reads,))
+    want = tuple(want)
+    if any(w not in PAIRS_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(PAIRS_OUTPUTS))
+    return L.make_pairs_opts(thr, int(min_reads), L.PAIRS_FORCE_DIRECT if force_direct else 0), want
+
+
+def _check_pair_counts(nreads, nsites, npairs):
+    if nreads > 2 ** 31 - 1:
+        raise ValueError('at most 2^31 - 1 reads')
+    if nsites > 2 ** 31 - 2:
+        raise ValueError('at most 2^31 - 2 sites')
+    if int(npairs) != npairs or not 0 <= int(npairs) <= 2 ** 31 - 1:
+        raise ValueError('npairs must be an integer in 0 .. 2^31 - 1, not %r' % (npairs,))
+    return int(npairs)
+
+
+def _pairs_shapes(want, npairs):
+    kinds = dict(counts=('int32', 4 * npairs), first=('int32', npairs), second=('int32', npairs), status=('uint8', npairs),
+                 **{k: ('float64', npairs) for k in L.PAIRS_FIELDS})
+    return {k: kinds[k] for k in PAIRS_OUTPUTS if k in want}
+
+
+def _host_keys(key):
+    key = np.ascontiguousarray(key, dtype=np.int64)
+    if key.ndim != 1 or (key.shape[0] and (key[0] < 0 or bool(np.any(np.diff(key) <= 0)))):
+        raise ValueError('key must be an int64 vector of cs << 40 | pos, strictly ascending')
+    return key
+
+
+def pair_index_host(key, max_dist=100, device=0):
+    """The pairs of candidate sites at most max_dist apart on one (chrom, strand) (nmod_pair_index, include/nanomod_hip.h): key int64,
+    cs << 40 | pos, strictly ascending.  Returns poff (int64[nsites + 1]): pair (a, b) has the index poff[a] + (b - a - 1), poff[-1]
+    pairs in all."""
+    lib = L.load()
+    max_dist = _check_max_dist(max_dist)
+    key = _host_keys(key)
+    _check_pair_counts(0, key.shape[0], 0)
+    poff = np.zeros(key.shape[0] + 1, dtype=np.int64)
+    npairs = C.c_int64(0)
+    _join_warm_up(device)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_pair_index', prm, key.shape[0], _np_ptr(key), max_dist, _np_ptr(poff), C.byref(npairs))
+    return poff
+
+
+def site_pairs_host(cs, start, roff, score, key, poff, *, thr=2.5, min_reads=10, force_direct=False, want=PAIRS_OUTPUTS, device=0):
+    """Same-read co-occurrence of calls at pairs of sites (nmod_site_pairs, include/nanomod_hip.h) on host-resident reads: cs (int32,
+    2 * chrom index + (strand == '-')), start (int64) and roff (int64[nreads + 1]) as nmod_pivot_reads takes them, score (float64, one
+    per event in read direction: K13's llr_win), key and poff as pair_index_host gives them.  Returns a dict of numpy arrays, those
+    named in `want`: counts (int32[4 npairs]: n00, n01, n10, n11 of each pair, the first index site a's call), first, second (int32),
+    log_or, se, phi, p_fisher (float64) and status (uint8, L.PAIRS_* bits)."""
+    lib = L.load()
+    opts, want = _pairs_opts(thr, min_reads, force_direct, want)
+    score = np.ascontiguousarray(score, dtype=np.float64)
+    roff, nreads, _ = _read_layout(score, roff, 'score')
+    cs = _side(cs, np.int32, nreads, 'cs', 'nreads', optional=False)
+    start = _side(start, np.int64, nreads, 'start', 'nreads', optional=False)
+    key = _host_keys(key)
+    poff = _side(poff, np.int64, key.shape[0] + 1, 'poff', 'nsites + 1', optional=False)
+    if poff[0] != 0 or bool(np.any(np.diff(poff) < 0)):
+        raise ValueError('poff must start at 0 and never decrease')
+    npairs = _check_pair_counts(nreads, key.shape[0], int(poff[-1]))
+    shapes = _pairs_shapes(want, npairs)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_pairs_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_site_pairs', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(poff), npairs, C.byref(opts), C.byref(out))
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1240,6 +1326,43 @@ class DeviceDetector:
         _call(self.lib, 'nmod_site_diff', prm, npos0, score0.data_ptr(), _ptr(off0), score1.data_ptr(), _ptr(off1), C.byref(opts), C.byref(o))
         return res
 
+    def pair_index(self, key, max_dist=100):
+        """The pairs of candidate sites at most max_dist apart on one (chrom, strand) (nmod_pair_index, NMOD_MEM_DEVICE) on the current
+        stream: key an int64 CUDA vector of cs << 40 | pos, strictly ascending (not checked).  Synchronises the stream once to learn
+        the number of pairs.  Returns (poff, npairs): poff an int64 CUDA vector of nsites + 1 offsets."""
+        torch = self.torch
+        max_dist = _check_max_dist(max_dist)
+        _cuda_vecs('pair_index', (('key', key, torch.int64, None),), one_dim=True)
+        _check_pair_counts(0, key.numel(), 0)
+        poff = torch.empty(key.numel() + 1, dtype=torch.int64, device=self._dev)
+        npairs = C.c_int64(0)
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_pair_index', prm, key.numel(), key.data_ptr(), max_dist, poff.data_ptr(), C.byref(npairs))
+        return poff, int(npairs.value)
+
+    def site_pairs(self, cs, start, roff, score, key, poff, npairs, *, thr=2.5, min_reads=10, force_direct=False, want=PAIRS_OUTPUTS,
+                   out=None):
+        """Same-read co-occurrence of calls at pairs of sites (nmod_site_pairs, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising or reading anything back.  cs (int32), start (int64), roff (int64, nreads + 1) and score (float64, one per event:
+        read_llr's llr_win) are CUDA vectors in pivot_reads' layout of the reads; key, poff and npairs as pair_index gives them.
+        Returns a dict of CUDA tensors, those named in `want`: counts (int32, 4 per pair: n00, n01, n10, n11), first, second (int32),
+        log_or, se, phi, p_fisher (float64), status (uint8, L.PAIRS_* bits).  p_fisher is a track fdr() takes as it is.  out: such a
+        dict from an earlier call of the same shape."""
+        torch = self.torch
+        opts, want = _pairs_opts(thr, min_reads, force_direct, want)
+        nreads = _device_offsets(torch, roff, 'site_pairs', 'nreads')
+        _cuda_vecs('site_pairs', (('cs', cs, torch.int32, nreads), ('start', start, torch.int64, nreads), ('score', score, torch.float64, None),
+                                  ('key', key, torch.int64, None), ('poff', poff, torch.int64, key.numel() + 1 if key is not None else None)),
+                   one_dim=True, missing='refused')
+        npairs = _check_pair_counts(nreads, key.numel(), npairs)
+        shapes = _pairs_shapes(want, npairs)
+        res = self._outputs(out, shapes, 'site_pairs')
+        o = L.make_pairs_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_site_pairs', prm, nreads, cs.data_ptr(), start.data_ptr(), roff.data_ptr(), score.data_ptr(), key.numel(),
+              key.data_ptr(), poff.data_ptr(), npairs, C.byref(opts), C.byref(o))
+        return res
+
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):
         prm = self._params(self._dtype_of(out), 0, 0, 0, 0)
         rc = self.lib.nmod_synth_fill(C.byref(prm), seed, pos_begin, npos, group, n_per_pos,
@@ -1316,6 +1439,18 @@ def chrom_names(*read_sets):
     return [str(n) for n in np.unique(np.concatenate(heads) if heads else np.zeros(0, str)).tolist()]
 
 
+def chrom_strand_ids(chrom, strand, names, what='reads'):
+    """the (chrom, strand) ids 2 * index in `names` + (strand == '-') of str arrays chrom and strand (int32): nmod_pivot_reads' cs and the
+    upper bits of its keys"""
+    n = len(chrom)
+    if not np.all(np.isin(strand, ('+', '-'))):
+        raise ValueError("%s: strand must be '+' or '-'" % what)
+    cid = np.searchsorted(np.array(names, dtype=str), chrom) if n else np.zeros(0, np.int64)
+    if n and (np.any(cid >= len(names)) or np.any(np.array(names, dtype=str)[np.minimum(cid, len(names) - 1)] != chrom)):
+        raise ValueError('%s: a chromosome is missing from names' % what)
+    return (2 * cid + (strand == '-')).astype(np.int32)
+
+
 class _CallTimer:
     """HIP events around one library call on the current stream; adds its device time (s) to timer[name] when timer is a dict"""
 
@@ -1364,13 +1499,8 @@ def pivot_reads(reads, device=0, pos_lo=None, pos_hi=None, names=None, timer=Non
     nreads = len(start)
     if len(off) != nreads + 1 or len(chrom) != nreads or len(strand) != nreads:
         raise ValueError('reads: chrom / strand / start need one entry per read and off nreads + 1')
-    if not np.all(np.isin(strand, ('+', '-'))):
-        raise ValueError("reads: strand must be '+' or '-'")
-    cid = np.searchsorted(np.array(names, dtype=str), chrom) if nreads else np.zeros(0, np.int64)
-    if nreads and (np.any(cid >= len(names)) or np.any(np.array(names, dtype=str)[np.minimum(cid, len(names) - 1)] != chrom)):
-        raise ValueError('reads: a chromosome is missing from names')
-    cs = (2 * cid + (strand == '-')).astype(np.int32)
-    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
+    cs = chrom_strand_ids(chrom, strand, names)
+    base =np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
     lo = -1 if pos_lo is None else int(pos_lo)
     hi = -1 if pos_hi is None else int(pos_hi)
     nev = int(off[-1]) if len(off) else 0

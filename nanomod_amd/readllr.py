@@ -12,6 +12,10 @@ canonical (at most -thr) or neither.  Per position, the modified share of the re
 
 The rescaling (K11, against the unmodified model), the ratios, the grouping by position and the counts all run in the HIP library on
 the device, one after the other on one stream; there is no CPU fallback.
+
+compare_reads_llr compares the modified share of every site between two samples (K15); cooccur_reads_llr keeps the read and asks of every
+pair of nearby candidate sites whether they are modified on the same molecules (K16, nmod_site_pairs): a 2 x 2 table of the reads
+called at both sites, its log odds ratio, phi and the exact test.
 """
 from __future__ import annotations
 
@@ -258,5 +262,137 @@ def write_site_diff(path, sites):
                                                     'delta_lo', 'delta_hi', 'stat')] + \
            [sci(sites['p_diff'])] + ([sci(sites['q'])] if 'q' in sites else []) + [np.asarray(sites['diff_status']).tolist()]
     fmt = '%s %s %d %s %d %d %d %d %.6f %.6f %.6f %.6f %.6f %.6f %.3f %s ' + ('%s ' if 'q' in sites else '') + '%d\n'
+    with open(path, 'w') as f:
+        f.writelines(fmt % row for row in zip(*cols))
+
+
+_PAIR_STAT_FIELDS = ('log_or', 'se', 'phi', 'p_fisher')
+
+
+def read_sites_file(path):
+    """A list of candidate sites: lines 'chrom strand pos' with 1-based positions; further columns are ignored, so the first three of
+    <FileID>_site_stoich.txt work, and so do empty lines and lines that start with '#'.  Returns (chrom, strand, pos) arrays, pos
+    0-based."""
+    chrom, strand, pos = [], [], []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith('#'):
+                continue
+            if len(parts) < 3 or parts[1] not in ('+', '-') or not parts[2].isdigit() or int(parts[2]) < 1:
+                raise ValueError("%s, line %d: expected 'chrom strand pos' with strand + or - and a 1-based position" % (path, ln))
+            chrom.append(parts[0]); strand.append(parts[1]); pos.append(int(parts[2]) - 1)
+    return np.array(chrom, dtype=str), np.array(strand, dtype=str).astype('U1'), np.array(pos, dtype=np.int64)
+
+
+def site_keys(sites, names):
+    """(chrom, strand, pos) arrays as nmod_pivot_reads' keys cs << 40 | pos over the chromosome list `names`: sorted, duplicates
+    dropped; a site on a chromosome outside `names` can be covered by no read and is dropped too"""
+    chrom, strand, pos = (np.asarray(x) for x in sites)
+    chrom, strand, pos = chrom.astype(str), strand.astype(str), pos.astype(np.int64)
+    if not (len(chrom) == len(strand) == len(pos)):
+        raise ValueError('sites: chrom, strand and pos need one entry per site')
+    if len(pos) and (pos.min() < 0 or pos.max() >= 1 << 40):
+        raise ValueError('sites: positions must lie in 0 .. 2^40 - 1')
+    known = np.isin(chrom, np.array(names, dtype=str)) if len(chrom) else np.zeros(0, bool)
+    cs = engine.chrom_strand_ids(chrom[known], strand[known], names, 'sites').astype(np.int64)
+    return np.unique((cs << 40) | pos[known])
+
+
+def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, thr=2.5, min_reads=10, window='kmer', prior=0.5,
+                      min_positions=1, rescale=None, fdr=None, fdr_alpha=0.05, site_alpha=0.05, device=0, log=print):
+    """Same-read co-occurrence of modification calls at pairs of sites of one read-level set (container.READ_FIELDS): are two sites
+    modified on the same molecules?  The optional rescaling (K11) and the window sums (K13) as in call_reads_llr; then the candidate
+    sites; then, read by read, the 2 x 2 table of every pair of candidate sites on one (chrom, strand) at most max_dist apart over the
+    reads that have a call (modified: window sum >= thr, canonical: <= -thr) at both, with its log odds ratio, phi and two-sided exact
+    test (K16, nmod_pair_index / nmod_site_pairs), all on the device and on one stream.
+    sites: 'stoich': the positions to which nmod_site_stoich (K14) gives an estimate whose Benjamini-Hochberg q of p_null is at most
+      site_alpha; or (chrom, strand, pos) arrays, pos 0-based (read_sites_file reads them from a text file).
+    min_reads: reads with a call at both sites below which a pair gets no statistics.  fdr: None, 'bh' or 'by': p_fisher goes through
+    nmod_fdr_adjust on the device at fdr_alpha and `pairs` gains q.
+    Returns `pairs`, one entry per pair in key order: chrom, strand, pos_a, pos_b (0-based), dist, n11, n10, n01, n00 (the first index
+    is site a's call), log_or, se, phi, p_fisher, [q,] status (uint8, L.PAIRS_* bits).  One summary line goes to `log`."""
+    import torch
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    if rescale is not None:
+        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
+        if unknown:
+            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    engine._pairs_opts(thr, min_reads, False, ())
+    max_dist = engine._check_max_dist(max_dist)
+    if fdr is not None:
+        engine._fdr_method(fdr)
+    engine._check_alpha(fdr_alpha)
+    site_alpha = engine._check_alpha(site_alpha)
+    by_stoich = isinstance(sites, str)
+    if by_stoich and sites != 'stoich':
+        raise ValueError("sites must be 'stoich' or (chrom, strand, pos) arrays")
+    val, off, base = _checked_reads(reads, 'reads')
+    nreads = len(off) - 1
+    names = engine.chrom_names(reads)
+    cs = engine.chrom_strand_ids(np.asarray(reads['chrom']).astype(str), np.asarray(reads['strand']).astype(str), names)
+    start = np.ascontiguousarray(reads['start'], dtype=np.int64)
+    host_key = None if by_stoich else site_keys(sites, names)
+    engine._join_warm_up(device)
+    det = engine.DeviceDetector(device)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    d_val, d_off, d_base = t(val), t(off), t(base)
+    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+    if rescale is not None:
+        d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
+    llr_win = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
+                           prior_logit=prior_logit, want=('llr_win',))['llr_win']
+    if by_stoich:
+        piv = engine.pivot_reads(reads, device, names=names, val=llr_win)
+        share = det.site_stoich(piv['sig'], off=piv['off'])
+        (q_site,), _ = det.fdr(share, tracks=('p_null',), method='bh', alpha=site_alpha)
+        keep = ((share['status'] & L.STOICH_NO_ESTIMATE) == 0) & (q_site <= site_alpha)       # (a NaN q compares false)
+        d_key = piv['key'][keep].contiguous()
+    else:
+        d_key = t(host_key)
+    poff, npairs = det.pair_index(d_key, max_dist)
+    res = det.site_pairs(t(cs), t(start), d_off, llr_win, d_key, poff, npairs, thr=thr, min_reads=min_reads)
+    q = None
+    if fdr is not None:
+        (q,), _ = det.fdr(res, tracks=('p_fisher',), method=fdr, alpha=fdr_alpha)
+    key = d_key.cpu().numpy()
+    first, second = res['first'].cpu().numpy().astype(np.int64), res['second'].cpu().numpy().astype(np.int64)
+    counts = res['counts'].cpu().numpy().reshape(-1, 4)
+    nm = np.array(names, dtype=str)
+    ka, kb = key[first], key[second]
+    pos_a, pos_b = ka & ((1 << 40) - 1), kb & ((1 << 40) - 1)
+    pairs = dict(chrom=nm[ka >> 41] if len(ka) else np.zeros(0, dtype=str), strand=np.where((ka >> 40) & 1, '-', '+').astype('U1'),
+                 pos_a=pos_a, pos_b=pos_b, dist=pos_b - pos_a, n11=counts[:, 3].copy(), n10=counts[:, 2].copy(), n01=counts[:, 1].copy(),
+                 n00=counts[:, 0].copy(), **{f: res[f].cpu().numpy() for f in _PAIR_STAT_FIELDS})
+    if q is not None:
+        pairs['q'] = q.cpu().numpy()
+    pairs['status'] = res['status'].cpu().numpy()
+    tested = (pairs['status'] & L.PAIRS_TOO_FEW) == 0
+    log('readpairs: %d read(s); %d candidate site(s)%s, %d pair(s) at most %d apart, %d with at least %d read(s) called at both sites%s'
+        % (nreads, len(key), ' with q <= %g of the modified share' % site_alpha if by_stoich else '', npairs, max_dist, int(tested.sum()),
+           int(min_reads), '' if q is None else '; %d with q <= %g (%s)' % (int((pairs['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
+    return pairs
+
+
+def write_site_pairs(path, pairs):
+    """<FileID>_site_pairs.txt: per pair 'chrom strand pos_a+1 pos_b+1 dist n11 n10 n01 n00 log_or se phi p_fisher [q] status' as
+    '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %.3E [%.3E] %d' (the positions 1-based; 'nan' as Python spells it where the pair has no
+    value; `pairs` of cooccur_reads_llr)"""
+    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
+    cols = [np.asarray(pairs['chrom']).astype(str).tolist(), np.asarray(pairs['strand']).astype(str).tolist(),
+            (np.asarray(pairs['pos_a'], dtype=np.int64) + 1).tolist(), (np.asarray(pairs['pos_b'], dtype=np.int64) + 1).tolist()] + \
+           [np.asarray(pairs[f]).tolist() for f in ('dist', 'n11', 'n10', 'n01', 'n00', 'log_or', 'se', 'phi')] + \
+           [sci(pairs['p_fisher'])] + ([sci(pairs['q'])] if 'q' in pairs else []) + [np.asarray(pairs['status']).tolist()]
+    fmt = '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %s ' + ('%s ' if 'q' in pairs else '') + '%d\n'
     with open(path, 'w') as f:
         f.writelines(fmt % row for row in zip(*cols))
