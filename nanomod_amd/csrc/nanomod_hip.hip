@@ -886,6 +886,7 @@ static int enqueue_outputs(Batch& b) {
   fa.max_n0 = std::max<int64_t>(std::min<int64_t>(b.max0, NMOD_MAX_RANKED), 1);
   fa.max_n1 = std::max<int64_t>(std::min<int64_t>(b.max1, NMOD_MAX_RANKED), 1);
   fa.min_cap = 0;
+  if (b.stride0 > 0 && b.stride1 > 0) fa.ks_scale = ks_size_scale(b.stride0, b.stride1);   // (else 0: K2 works it out per position)
   if (b.deep_possible) { fa.deep_lim0 = std::max<int64_t>(b.max0, 1); fa.deep_lim1 = std::max<int64_t>(b.max1, 1); }   // (K2 leaves them to the deep form)
   if ((prm->flags & NMOD_FLAG_CHECK_FINITE) && prm->dtype != NMOD_DTYPE_I16_MILLI) {
     // one pass over the samples: the float64 samples themselves where the keys are their float32 images

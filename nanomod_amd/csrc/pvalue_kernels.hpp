@@ -24,8 +24,20 @@ struct FinalizeArgs {
   const uint8_t* nonfinite;             // [npos] or null: 1 where nonfinite_scan_kernel found a NaN / infinite sample (NMOD_FLAG_CHECK_FINITE)
   int64_t deep_lim0, deep_lim1;         // NMOD_FLAG_DEEP: a position with a group beyond NMOD_MAX_RANKED and both within these limits is
                                         // the deep form's (deep_rank.hpp writes its outputs): skipped here.  0: no deep form in this batch
+  double ks_scale;                      // fixed strides: en + 0.12 + 0.11/en of ks_2samp, the same for every position (ks_size_scale on the
+                                        // host); 0 where a group is CSR and the sizes differ per position
   nmod_out out;
 };
+
+// ks_2samp's size term: en = sqrt(n0 n1 / (n0 + n1)); D is scaled by en + 0.12 + 0.11/en.  Host and device evaluate this one
+// expression: a square root, two divisions and two additions, each correctly rounded on both sides and none of them next to a
+// multiplication that could be contracted, so a fixed-stride batch (the host's value in FinalizeArgs) and the same rows as CSR
+// (per position) agree bit for bit.
+__host__ __device__ __forceinline__ double ks_size_scale(int64_t n0, int64_t n1) {
+  const double prod = (double)n0 * (double)n1;
+  const double en = sqrt(prod / (double)(n0 + n1));
+  return en + 0.12 + 0.11 / en;
+}
 
 // K1's facts of position p in the workspace (the wave-resident, counting and large-position forms)
 struct K1Facts {
@@ -55,8 +67,9 @@ __device__ __forceinline__ void finalize_position(const FinalizeArgs& a, int64_t
       // prob = kstwobign.sf((en + 0.12 + 0.11/en) * d)
       // KS-only mode: the exact rational, correctly rounded (<= 1 ulp from the float-CDF form)
       d = src.ks_d(prod);
-      double en = sqrt(prod / (double)(n0 + n1));
-      pv = kolmogorov_sf((en + 0.12 + 0.11 / en) * d);
+      // (fixed strides: every position that is not empty has the strides for sizes, and the term is a launch constant)
+      const double scale = a.ks_scale > 0.0 ? a.ks_scale : ks_size_scale(n0, n1);
+      pv = kolmogorov_sf(scale * d);
     }
     if (a.out.ks_d) a.out.ks_d[p] = clamp_stat(d);
     if (a.out.ks_p) a.out.ks_p[p] = clamp_p(pv);

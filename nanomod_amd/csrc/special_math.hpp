@@ -2,7 +2,7 @@
 //
 // Each function states the scipy 1.2.1 primitive it stands for (the reference
 // reaches them through scipy.stats at myDetect.py:331,335,341,393,401).  They
-// are written for gfx950 only (ocml exp/log/erfc/erfcx/lgamma/log1p in fp64);
+// are written for gfx950 only (ocml exp/log/erfc/lgamma/log1p in fp64);
 // relative accuracy target 1e-12 down to p = DBL_MIN.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,22 +21,33 @@ __device__ __forceinline__ double clamp_stat(double s) { return (s > kDblMax) ? 
 // kstwobign.sf == scipy.special.kolmogorov: Q(x) = 2 sum_{k>=1} (-1)^(k-1) exp(-2 k^2 x^2).
 // Small x uses the theta-function dual 1 - sqrt(2 pi)/x sum exp(-(2k-1)^2 pi^2/(8 x^2)),
 // which is what keeps the value accurate where the alternating series cancels.
+// Every term of either series is a power of one exponential, e^(1, 9, 25, 49) with e = exp(-pi^2/(8 x^2)) and
+// e^(k^2) with e = exp(-2 x^2): one exp per branch, the powers by multiplication (a wave of positions on both sides
+// of 0.82 runs both branches — twelve calls of exp before, two now).  A power e^n carries n times the rounding of e,
+// against a term that is e^(n-1) times smaller than the first: 5.6e-14 against mpmath over 0.2 <= x <= 18, the same
+// as with one exp per term (the rounding of x itself dominates both; tests/test_tail_math_host.py).
 __device__ inline double kolmogorov_sf(double x) {
   if (!(x > 0.0)) return (x != x) ? x : 1.0;
   if (x < 0.82) {
     const double pi2_8 = 1.2337005501361697;  // pi^2/8
     double w = pi2_8 / (x * x);
-    double s = exp(-w) + exp(-9.0 * w) + exp(-25.0 * w) + exp(-49.0 * w);
+    const double e = exp(-w);
+    const double e2 = e * e, e4 = e2 * e2, e8 = e4 * e4, e9 = e8 * e;
+    const double e16 = e8 * e8, e24 = e16 * e8, e25 = e24 * e;
+    const double e48 = e24 * e24, e49 = e48 * e;
+    double s = e + e9 + e25 + e49;
     return 1.0 - kSqrt2Pi / x * s;
   }
-  double q = -2.0 * x * x;
+  const double e = exp(-2.0 * x * x), e2 = e * e;
+  double t = e, r = e2 * e;                    // t_k = e^(k^2), r_k = e^(2k+1) = t_(k+1) / t_k
   double s = 0.0, sign = 1.0;
 #pragma unroll 1
   for (int k = 1; k <= 8; ++k) {
-    double t = exp(q * (double)(k * k));
     s += sign * t;
     sign = -sign;
     if (t < 1e-18 * s) break;
+    t *= r;
+    r *= e2;
   }
   return 2.0 * s;
 }
@@ -44,37 +55,49 @@ __device__ inline double kolmogorov_sf(double x) {
 // norm.sf(z) = ndtr(-z)
 __device__ __forceinline__ double norm_sf(double z) { return 0.5 * erfc(z * kInvSqrt2); }
 
-// norm.isf(p) = -ndtri(p).  Acklam's rational approximation (relative error 1.2e-9 over the whole double
-// range) followed by ONE Newton step on log Q(z) - log p; Q is evaluated through erfcx so the step is well
-// conditioned out to p = DBL_MIN (z = 37.52).  Checked against ndtri on 3e5 points from 1e-307 to 0.5: 7e-13.
+// norm.isf(p) = -ndtri(p).  Wichura's AS241, routine PPND16 (Applied Statistics 37 (1988) 477-484): three pairs of
+// degree-7 polynomials, on 0.425^2 - (q - 1/2)^2 for 0.075 <= q <= 0.5 and on r = sqrt(-log q) below (r <= 5 and
+// 5 < r <= 27; r = 26.62 at q = DBL_MIN), one division for all of them.  Against mpmath from DBL_MIN to 0.5: 8e-16
+// relative in z (tests/test_tail_math_host.py).  (Acklam's approximation with a Newton step through erfcx stood
+// here before: 7e-13, with two logarithms, erfcx, a square root and a division for every p.)
+// Every coefficient is positive and so is every argument (0.5 - q, r, r - 1.6, r - 5): the unflipped half cannot
+// come out negative, and z = +0 exactly at p = 0.5.
 __device__ inline double norm_isf(double p) {
   if (p != p) return p;
   if (p <= 0.0) return __builtin_inf();
   if (p >= 1.0) return -__builtin_inf();
   const bool flip = p > 0.5;
   const double q = flip ? 1.0 - p : p;          // exact for p in (0.5, 1)
-  const double lq = log(q);
-  double z;
-  if (q < 0.02425) {
-    const double t = sqrt(-2.0 * lq);
-    z = -(((((-7.784894002430293e-03 * t - 3.223964580411365e-01) * t - 2.400758277161838e+00) * t - 2.549732539343734e+00) * t
-            + 4.374664141464968e+00) * t + 2.938163982698783e+00) /
-         ((((7.784695709041462e-03 * t + 3.224671290700398e-01) * t + 2.445134137142996e+00) * t + 3.754408661907416e+00) * t + 1.0);
+  double num, den;
+  if (q >= 0.075) {
+    const double c = 0.5 - q, r = 0.180625 - c * c;
+    num = (((((((2.5090809287301226727e+3 * r + 3.3430575583588128105e+4) * r + 6.7265770927008700853e+4) * r
+              + 4.5921953931549871457e+4) * r + 1.3731693765509461125e+4) * r + 1.9715909503065514427e+3) * r
+              + 1.3314166789178437745e+2) * r + 3.387132872796366608) * c;
+    den = ((((((5.2264952788528545610e+3 * r + 2.8729085735721942674e+4) * r + 3.9307895800092710610e+4) * r
+              + 2.1213794301586595867e+4) * r + 5.3941960214247511077e+3) * r + 6.8718700749205790830e+2) * r
+              + 4.2313330701600911252e+1) * r + 1.0;
   } else {
-    const double c = q - 0.5, r = c * c;
-    z = -(((((-3.969683028665376e+01 * r + 2.209460984245205e+02) * r - 2.759285104469687e+02) * r + 1.383577518672690e+02) * r
-            - 3.066479806614716e+01) * r + 2.506628277459239e+00) * c /
-         (((((-5.447609879822406e+01 * r + 1.615858368580409e+02) * r - 1.556989798598866e+02) * r + 6.680131188771972e+01) * r
-            - 1.328068155288572e+01) * r + 1.0);
+    double r = sqrt(-log(q));
+    if (r <= 5.0) {
+      r -= 1.6;
+      num = ((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r
+               + 1.27045825245236838258) * r + 3.64784832476320460504) * r + 5.76949722146069140550) * r
+               + 4.63033784615654529590) * r + 1.42343711074968357734;
+      den = ((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r
+               + 1.48103976427480074590e-1) * r + 6.89767334985100004550e-1) * r + 1.67638483018380384940) * r
+               + 2.05319162663775882187) * r + 1.0;
+    } else {
+      r -= 5.0;
+      num = ((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r
+               + 2.65321895265761230930e-2) * r + 2.96560571828504891230e-1) * r + 1.78482653991729133580) * r
+               + 5.46378491116411436990) * r + 6.65790464350110377720;
+      den = ((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r
+               + 7.86869131145613259100e-4) * r + 1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r
+               + 5.99832206555887937690e-1) * r + 1.0;
+    }
   }
-  if (z < 0.0) z = 0.0;
-  {
-    const double u = z * kInvSqrt2;
-    const double ex = 0.5 * erfcx(u);           // Q(z) = ex * exp(-u^2)
-    const double lQ = log(ex) - u * u;
-    z += (lQ - lq) * ex * kSqrt2Pi;             // Q / phi = ex * sqrt(2 pi)
-    if (z < 0.0) z = 0.0;
-  }
+  const double z = num / den;
   return flip ? -z : z;
 }
 
