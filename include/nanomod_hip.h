@@ -547,6 +547,78 @@ int nmod_kmer_model(const nmod_params* prm, int64_t npos, const void* sig, const
                     const double* keep_lo, const double* keep_hi /* ncodes each, both NULL = keep everything */,
                     const nmod_kmer_out* out);
 
+/* The MODIFIED k-mer table learnt from a mixed sample (K17; the reference project has no such step — its simulations mix modified
+ * and unmodified reads at a share, mySimulate.py --Percentages).  Per k-mer code the unmodified component is fixed at a control
+ * table's entry (mean0[c], sd0[c]: what nmod_kmer_model gave for an unmodified control), the events of all positions of the code
+ * are pooled as K10 pools them, and y ~ (1 - pi) N(mean0, sd0^2) + pi N(m, v) is fitted by K8's EM on the pooled HISTOGRAM: events
+ * lie on the 0.001 grid, so the pooled data of a code is an integer histogram, built once, exactly and order-free.
+ *   Usable codes, windows: code c is usable iff mean0[c] and sd0[c] are finite, sd0[c] > 0 and |mean0[c]| <= 1000.  Its window is
+ *     the integers lo_c .. lo_c + NMOD_KMIX_BINS - 1 with lo_c = llrint(1000.0 * mean0[c]) - NMOD_KMIX_HALF: +-2.048 units, +-10 sd
+ *     at the usual 0.2.  An unusable code gets NMOD_KMIX_NO_MODEL, NaN estimates, iters 0, zero counts and a zero histogram row.
+ *   Samples: a sample has the integer k — int16: the value itself; float32 (up-cast) / float64: k = rint(1000.0 * x), ties to
+ *     even.  For float rows the estimate is therefore that of the rows ROUNDED TO THE 3-DECIMAL GRID every event file is written on.
+ *     A NaN or infinite sample is counted in n_outside and sets NMOD_STATUS_NONFINITE in pos_status; it does NOT drop its position
+ *     (a deliberate difference from K10: the pass stays streaming).  So does a finite x whose 1000.0 * x is not: outside, no flag.
+ *   Positions dropped whole, flagged in pos_status as K10 flags them: NMOD_STATUS_NO_CODE (code[i] < 0; device memory: outside
+ *     [0, ncodes) — never an out-of-range write), NMOD_STATUS_EMPTY (n == 0), NMOD_STATUS_TOO_LARGE (n > NMOD_MAX_DEEP), set together
+ *     where they apply together.  A position of an unusable code takes no part either (its pos_status carries no bit for that: the
+ *     code's NMOD_KMIX_NO_MODEL says it).  Every other position has status 0, or NMOD_STATUS_NONFINITE as above.
+ *   Histogram and counts per code, over its remaining positions: hist[c][b] = the samples with k == lo_c + b; n_used = sum_b hist;
+ *     n_outside = the samples outside the window; n_positions = the positions with at least one sample inside.  Limit, as in K10:
+ *     fewer than 2^32 samples per code.
+ *   EM: K8's definition with weights h_b = hist[c][b] at x_b = (double)(lo_c + b) / 1000.0.  n = n_used, mu = mean0[c], s = sd0[c],
+ *     s2 = s * s, ybar = ((double)S1 / (double)n) / 1000.0 with S1 = sum_b h_b (lo_c + b) exact in int64.  Start pi = 0.5,
+ *     m = mu + 2 (ybar - mu), v = s2; iteration k = 1, 2, ...:
+ *       t_b = ln((1 - pi) / pi) [+ 1/2 ln(v / s2), free model] + (x_b - m)^2 / (2 v) - (x_b - mu)^2 / (2 s2)     r_b = 1 / (1 + exp(t_b))
+ *       W = sum h_b r_b,  pi' = W / n,  m' = sum h_b r_b x_b / W,  free model: v' = max(sum h_b r_b (x_b - m')^2 / W, s2 / 16)
+ *       delta = max(|pi' - pi|, |m' - m| / s [, |sqrt(v') - sqrt(v)| / s]);  take the primed values
+ *     and stop when delta <= tol (tol > 0) or k == max_iter; tol == 0 runs exactly max_iter iterations.  With the final parameters
+ *     and one more evaluation of t_b: llr = 2 sum_b h_b [ln(1 - pi) + softplus(-t_b)].  Sums run over the bins in an order that is a
+ *     fixed function of the bin index (bin b belongs to thread b mod 256, which chains its bins upwards; then a fixed-order
+ *     reduction over the threads); an empty bin adds exactly 0.0.  No float atomics anywhere: a code's outputs are bit-identical
+ *     under any order of the positions, CSR or stride, host or device memory, any other codes in the batch and any CU count; for
+ *     float rows that round to the same k they are those of the int16 rows.
+ *   llr is A SCORE, NOT A TEST, for K8's reason (pi = 0 lies on the boundary with m unidentified) and one more: the pooled events of
+ *     a k-mer are not exactly normal, because the level varies between positions, so at 10^6 samples ANY second component is
+ *     "significant".  Select k-mers by effect size (pi, |m - mu| / s), as nanomod_amd.kmermodel.learn_alt_model does.
+ *   Status per code (NMOD_KMIX_* bits):
+ *     NMOD_KMIX_NOT_CONVERGED  max_iter iterations ran without the stopping rule ending them (tol == 0: always); the estimates are written
+ *     NMOD_KMIX_DEGENERATE     W underflowed to 0 (!(W > 0)): NaN estimates, iters 0
+ *     NMOD_KMIX_NO_MODEL       the code is unusable (above)
+ *     NMOD_KMIX_VAR_FLOORED    the variance floor was active in the last iteration
+ *     NMOD_KMIX_TOO_FEW        n_used < max(opts->min_samples, 2): NaN estimates, iters 0; the counts and the histogram are written
+ * Outputs, a NULL member skipped: n_positions, n_used, n_outside, pi, mu_mod (= m), sd_mod (= sqrt v), llr, iters, status (ncodes
+ * each), hist (optional, ncodes * NMOD_KMIX_BINS counts) and pos_status (optional, npos).  Rows: CSR when `off` is given, else the
+ * fixed stride prm->stride0.  Reads struct_size, device, stream, memspace, dtype, stride0 of prm and nothing else.  NMOD_MEM_DEVICE:
+ * everything is enqueued on prm->stream and the call returns WITHOUT synchronising or reading the device; the scratch comes
+ * stream-ordered from the library's pool: 16 KiB of histogram per code unless out->hist is given (k = 8: 1 GiB), 24 bytes per
+ * position and 1 KiB per 2 048 positions for the grouping by code, 36 bytes per code.  NMOD_MEM_HOST: copy in, run, copy back,
+ * synchronise (one staged copy, like K10).  npos == 0 is NMOD_OK with zero counts and NMOD_KMIX_TOO_FEW (NMOD_KMIX_NO_MODEL for an
+ * unusable code).  NMOD_ERR_INVALID_ARG before any device work: npos < 0 or beyond 2^31 - 2, ncodes outside 1 ..
+ * NMOD_MAX_KMER_CODES, a NULL mean0 / sd0 / opts / out, opts or out of another struct_size, a model outside {0, 1}, max_iter outside
+ * 1 .. 10 000, tol negative, NaN or infinite, min_samples < 0, a NULL sig / code with npos > 0, neither offsets nor a stride, an
+ * unknown dtype, host offsets that decrease, and (host memory only) a code outside [-1, ncodes).  int16 is the tuned form of the
+ * histogram pass (every sample byte read once, in aligned 8-byte pieces); float32 / float64 go through the same kernel a sample at
+ * a time and are not tuned. */
+#define NMOD_KMIX_HALF 2048
+#define NMOD_KMIX_BINS 4096
+#define NMOD_KMIX_NOT_CONVERGED 1
+#define NMOD_KMIX_DEGENERATE    2
+#define NMOD_KMIX_NO_MODEL      4
+#define NMOD_KMIX_VAR_FLOORED   8
+#define NMOD_KMIX_TOO_FEW      16
+typedef struct nmod_kmix_opts { int32_t struct_size, model /* 0 equal variance, 1 free */, max_iter, reserved;
+  int64_t min_samples; double tol; } nmod_kmix_opts;
+typedef struct nmod_kmix_out { int32_t struct_size, reserved;
+  int64_t *n_positions, *n_used, *n_outside;          /* ncodes each; a NULL member is skipped */
+  double  *pi, *mu_mod, *sd_mod, *llr;                /* ncodes each */
+  int32_t *iters; uint8_t *status;                    /* ncodes each */
+  uint32_t *hist;                                     /* ncodes * NMOD_KMIX_BINS, optional */
+  uint8_t *pos_status;                                /* npos, optional */ } nmod_kmix_out;
+int nmod_kmer_mix(const nmod_params* prm, int64_t npos, const void* sig, const int64_t* off /* or prm->stride0 */,
+                  const int32_t* code, int32_t ncodes, const double* mean0, const double* sd0,
+                  const nmod_kmix_opts* opts, const nmod_kmix_out* out);
+
 /* Per-read shift and scale against a k-mer model (K11; the reference project has no such step): a robust weighted linear fit of a
  * read's event levels x against the model levels mu of their k-mers, x ~ a + b mu, and the rescaled events (x - a) / b, so that the reads
  * of a sample sit on the scale of a model built by nmod_kmer_model from another run.

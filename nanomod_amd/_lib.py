@@ -118,6 +118,32 @@ class NmodKmerOut(C.Structure):
 make_kmer_out = functools.partial(make_out, NmodKmerOut)
 
 
+KMIX_HALF, KMIX_BINS = 2048, 4096         # nmod_kmer_mix: a code's window is llrint(1000 mean0) - KMIX_HALF .. + KMIX_BINS - 1
+KMIX_NOT_CONVERGED, KMIX_DEGENERATE, KMIX_NO_MODEL, KMIX_VAR_FLOORED, KMIX_TOO_FEW = 1, 2, 4, 8, 16
+KMIX_NO_ESTIMATE = KMIX_DEGENERATE | KMIX_NO_MODEL | KMIX_TOO_FEW
+KMIX_COUNT_FIELDS = ('n_positions', 'n_used', 'n_outside')
+KMIX_FIELDS = ('pi', 'mu_mod', 'sd_mod', 'llr')
+
+
+class NmodKmixOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'model', 'max_iter', 'reserved')] + [('min_samples', C.c_int64), ('tol', C.c_double)]
+
+
+class NmodKmixOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + \
+               [(n, C.c_void_p) for n in KMIX_COUNT_FIELDS + KMIX_FIELDS + ('iters', 'status', 'hist', 'pos_status')]
+
+
+def make_kmix_opts(model=MIX_FREE_VAR, max_iter=200, tol=1e-6, min_samples=2):
+    o = NmodKmixOpts()
+    o.struct_size = C.sizeof(NmodKmixOpts)
+    o.model, o.max_iter, o.min_samples, o.tol = int(model), int(max_iter), int(min_samples), float(tol)
+    return o
+
+
+make_kmix_out = functools.partial(make_out, NmodKmixOut)
+
+
 RESCALE_FIT_APPLY, RESCALE_FIT_ONLY, RESCALE_APPLY_ONLY = 0, 1, 2
 RESCALE_MODE_BY_NAME = {'fit_apply': RESCALE_FIT_APPLY, 'fit_only': RESCALE_FIT_ONLY, 'apply_only': RESCALE_APPLY_ONLY}
 RESCALE_TOO_FEW, RESCALE_DEGENERATE, RESCALE_OUT_OF_RANGE, RESCALE_CLAMPED, RESCALE_TOO_LARGE = 1, 2, 4, 8, 16
@@ -344,6 +370,8 @@ _SIGNATURES = {
     'nmod_one_sample': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(NmodOneOut)]),
     'nmod_kmer_model': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.POINTER(NmodKmerOut)]),
+    'nmod_kmer_mix': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.POINTER(NmodKmixOpts), C.POINTER(NmodKmixOut)]),
     'nmod_rescale_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
                                      C.POINTER(NmodRescaleOpts), C.POINTER(NmodRescaleOut)]),
     'nmod_read_calls': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),

@@ -112,7 +112,24 @@ def build_parser():
     km.add_argument('--outFolder', default='mRes')
     km.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_kmer_model.npz and <FileID>_kmer_model.txt')
     km.add_argument('--device', type=int, default=0)
-    kp = sub.add_parser('kmerprofile', help="the 'model' profile a k-mer model predicts for the positions of a read group, for detect1")
+    kx = sub.add_parser('kmermix', help='learn the modified k-mer model from a mixed (native, partly modified) sample against the k-mer '
+                        'model of an unmodified control, on the device: the table --altModel takes, without a fully modified control')
+    kx.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    kx.add_argument('--wrkBase1', required=True, help='the mixed sample: a .npz container (per position or read-level)')
+    kx.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel' from the control")
+    kx.add_argument('--sites', default='', help="optional: pool only the positions listed in this file, lines 'chrom strand pos' (1-based; "
+                    'the first three columns of <FileID>_sign_test.txt, _sign_test_fdr.txt or _site_stoich.txt)')
+    kx.add_argument('--MinCoverage', type=int, default=5)
+    kx.add_argument('--mixModel', default='free', choices=['equal', 'free'], help="the modified component's variance: the control's, or its own")
+    kx.add_argument('--minSamples', type=int, default=1000, help='a k-mer is kept only with at least this many pooled events in its window')
+    kx.add_argument('--minPi', type=float, default=0.05, help='... and a modified share of its pooled events of at least this, [0, 1]')
+    kx.add_argument('--minShift', type=float, default=1.0, help="... and a modified level at least this many control sd away from the control's")
+    kx.add_argument('--maxIter', type=int, default=200, help='EM iterations per k-mer at most, 1 .. 10000')
+    kx.add_argument('--tol', type=float, default=1e-6, help='the EM stops when no parameter moved by more than this, >= 0')
+    kx.add_argument('--outFolder', default='mRes')
+    kx.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_alt_kmer_model.npz and <FileID>_kmer_mix.txt')
+    kx.add_argument('--device', type=int, default=0)
+    kp = sub.add_parser('kmerprofile',help="the 'model' profile a k-mer model predicts for the positions of a read group, for detect1")
     kp.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
     kp.add_argument('--kmerModel', required=True, help="a k-mer model written by 'kmermodel'")
     kp.add_argument('--wrkBase1', required=True, help='the sample read group: a .npz container (per position or read-level)')
@@ -157,7 +174,7 @@ def build_parser():
     rl.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
     rl.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
     rl.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
-    rl.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rl.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
     rl.add_argument('--llrThreshold', type=float, default=2.5, help='an event is called when its window sum reaches +- this, > 0')
     rl.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
                     'before and after, 0 .. 64 each')
@@ -180,7 +197,7 @@ def build_parser():
     rd.add_argument('--wrkBase1', required=True, help='sample 0, the control condition: a read-level .npz container')
     rd.add_argument('--wrkBase2', required=True, help='sample 1: a read-level .npz container')
     rd.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
-    rd.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rd.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
     rd.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
                     'before and after, 0 .. 64 each')
     rd.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state, inside (0, 1)')
@@ -199,7 +216,7 @@ def build_parser():
     rp.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
     rp.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
     rp.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
-    rp.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a modified control")
+    rp.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
     rp.add_argument('--sites', default='stoich', help="'stoich': the positions whose modified share (readllr --siteFraction) has a "
                     "Benjamini-Hochberg q of at most --siteAlpha; or a FILE of lines 'chrom strand pos' (1-based; the first three "
                     'columns of <FileID>_site_stoich.txt work)')
@@ -483,6 +500,43 @@ def run_kmermodel(a, log=print):
     if not quiet:
         log('K-mer model is saved in %s' % path)
     return model
+
+
+def validate_kmermix(a):
+    """the checks of kmermix"""
+    errs = []
+    if a.MinCoverage < 3:
+        errs.append('Error: --MinCoverage should be not less than 3')
+    if a.minSamples < 2:
+        errs.append('Error: --minSamples should be not less than 2')
+    if not 0.0 <= a.minPi <= 1.0:
+        errs.append('Error: --minPi should be in [0, 1]')
+    if not 0.0 <= a.minShift < float('inf'):
+        errs.append('Error: --minShift should be finite and not negative')
+    if not 1 <= a.maxIter <= 10000:
+        errs.append('Error: --maxIter should be in 1 .. 10000')
+    if not 0.0 <= a.tol < float('inf'):
+        errs.append('Error: --tol should be finite and not negative')
+    for f in (a.wrkBase1, a.kmerModel) + ((a.sites,) if a.sites else ()):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    return errs
+
+
+def run_kmermix(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    model = kmermodel.load_kmer_model(a.kmerModel)
+    alt, table = kmermodel.learn_alt_model(load_group_input(a.wrkBase1, a.device), model, readllr.read_sites_file(a.sites) if a.sites else None,
+                                           a.MinCoverage, a.mixModel, a.maxIter, a.tol, a.minSamples, a.minPi, a.minShift, a.device,
+                                           (lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + '_alt_kmer_model.npz')
+    kmermodel.save_kmer_model(path, alt)
+    kmermodel.write_kmer_mix_table(os.path.join(a.outFolder, a.FileID + '_kmer_mix.txt'), model, table)
+    if not quiet:
+        log('Modified k-mer model is saved in %s' % path)
+    return alt, table
 
 
 def run_kmerprofile(a, log=print):
@@ -861,6 +915,13 @@ def main(argv=None):
             print('\n'.join(errs))
             return 1
         run_rescale(a)
+        return 0
+    if a.cmd == 'kmermix':
+        errs = validate_kmermix(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_kmermix(a)
         return 0
     if a.cmd in ('kmermodel', 'kmerprofile'):
         errs = validate_kmer(a)

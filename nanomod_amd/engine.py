@@ -304,6 +304,15 @@ def _kmer_shapes(npos, ncodes):
     return dict({k: ('int64', m) for k in L.KMER_COUNT_FIELDS}, mean=('float64', m), sd=('float64', m), pos_status=('uint8', npos))
 
 
+def _kmix_shapes(npos, ncodes, want_hist=False):
+    m = max(ncodes, 0)
+    shapes = dict({k: ('int64', m) for k in L.KMIX_COUNT_FIELDS}, **{k: ('float64', m) for k in L.KMIX_FIELDS})
+    shapes.update(iters=('int32', m), status=('uint8', m), pos_status=('uint8', npos))
+    if want_hist:
+        shapes['hist'] = ('uint32' if isinstance(want_hist, bool) else want_hist, m * L.KMIX_BINS)
+    return shapes
+
+
 def _rescale_shapes(nreads, val_kind=None, nval=0):
     """val_kind None: mode 'fit_only', no rescaled events"""
     shapes = dict(shift=('float64', nreads), scale=('float64', nreads), n_used=('int32', nreads), status=('uint8', nreads))
@@ -515,6 +524,42 @@ def kmer_model_host(sig, off, code, ncodes, keep_lo=None, keep_hi=None, *, strid
     out = L.make_out(L.NmodKmerOut, **_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride)
     _call(lib, 'nmod_kmer_model', prm, npos, _np_ptr(sig), _np_ptr(off), _np_ptr(code), ncodes, _np_ptr(keep_lo), _np_ptr(keep_hi), C.byref(out))
+    return res
+
+
+def _kmix_opts(model, max_iter, tol, min_samples):
+    """nmod_kmix_opts from the Python arguments; ValueError for what the C entry refuses"""
+    _, model, max_iter, tol = _mix_args(1, model, max_iter, tol)
+    if int(min_samples) != min_samples or int(min_samples) < 0:
+        raise ValueError('min_samples must be an integer >= 0, not %r' % (min_samples,))
+    return L.make_kmix_opts(model, max_iter, tol, int(min_samples))
+
+
+def kmer_mix_host(sig, off, code, ncodes, mean0, sd0, *, stride=0, model='free', max_iter=200, tol=1e-6, min_samples=2, want_hist=False,
+                  device=0):
+    """The modified component per k-mer code of host-resident rows (nmod_kmer_mix, include/nanomod_hip.h): sig float32, int16
+    (milli-units) or float64, rows by `off` (int64[npos + 1]) or a fixed `stride`; code int32[npos] in [-1, ncodes) (-1: the position
+    takes no part); mean0 / sd0 float64[ncodes]: the unmodified component, a control's k-mer table.  model 'equal' / 'free' as
+    mix_fraction_host.  Returns a dict of numpy arrays: n_positions, n_used, n_outside (int64[ncodes]), pi, mu_mod, sd_mod, llr
+    (float64[ncodes]; llr is a score, not a test), iters (int32), status (uint8, L.KMIX_* bits), pos_status (uint8[npos], L.STATUS_*
+    bits) and with want_hist `hist` (uint32[ncodes * L.KMIX_BINS], the pooled histogram of every code's window)."""
+    lib = L.load()
+    opts = _kmix_opts(model, max_iter, tol, min_samples)
+    _join_warm_up(device)
+    sig, dtype = _signal(sig, 'sig')
+    code = np.ascontiguousarray(code, dtype=np.int32)
+    if code.ndim != 1:
+        raise ValueError('code must be int32[npos]')
+    npos = code.shape[0]
+    off, stride = _rows(sig, off, stride, npos, 'sig')
+    ncodes = int(ncodes)
+    mean0 = _side(mean0, np.float64, ncodes, 'mean0', 'ncodes', optional=False)
+    sd0 = _side(sd0, np.float64, ncodes, 'sd0', 'ncodes', optional=False)
+    res = _host_outputs(_kmix_shapes(npos, ncodes, bool(want_hist)))
+    out = L.make_out(L.NmodKmixOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype, stride0=stride)
+    _call(lib, 'nmod_kmer_mix', prm, npos, _np_ptr(sig), _np_ptr(off), _np_ptr(code), ncodes, _np_ptr(mean0), _np_ptr(sd0), C.byref(opts),
+          C.byref(out))
     return res
 
 
@@ -1172,6 +1217,29 @@ class DeviceDetector:
         o = L.make_out(L.NmodKmerOut, **{k: t.data_ptr() for k, t in res.items()})
         prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
         _call(self.lib, 'nmod_kmer_model', prm, npos, _ptr(sig), _ptr(off), _ptr(code), ncodes, _ptr(keep_lo), _ptr(keep_hi), C.byref(o))
+        return res
+
+    def kmer_mix(self, sig, code, ncodes, mean0, sd0, *, off=None, stride=0, npos=None, model='free', max_iter=200, tol=1e-6, min_samples=2,
+                 want_hist=False, out=None):
+        """The modified component per k-mer code (nmod_kmer_mix, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising.  sig: float32, int16 or float64 CUDA rows by `off` (int64 CUDA tensor) or a fixed `stride`; code: int32 CUDA
+        vector (a value outside [0, ncodes): the position takes no part, L.STATUS_NO_CODE); mean0 / sd0: float64 CUDA vectors of
+        ncodes, the unmodified component.  Returns a dict of CUDA tensors: n_positions, n_used, n_outside (int64), pi, mu_mod, sd_mod,
+        llr (float64; a score, not a test), iters (int32), status (uint8, L.KMIX_* bits), each of ncodes, pos_status (uint8, npos) and
+        with want_hist `hist` (int32 holding the uint32 counts, ncodes * L.KMIX_BINS).  int16 is the tuned form."""
+        torch = self.torch
+        opts = _kmix_opts(model, max_iter, tol, min_samples)
+        dtype = self._dtype_of(sig)
+        if npos is None:
+            npos = code.numel()
+        ncodes = int(ncodes)
+        _cuda_vecs('kmer_mix', (('code', code, torch.int32, npos), ('mean0', mean0, torch.float64, ncodes), ('sd0', sd0, torch.float64, ncodes)),
+                   missing='refused')
+        _cuda_vecs('kmer_mix', (('off', off, torch.int64, npos + 1),), missing='ok')
+        res = self._outputs(out, _kmix_shapes(npos, ncodes, 'int32' if want_hist else False), 'kmer_mix', validate=False)
+        o = L.make_out(L.NmodKmixOut, **{k: t.data_ptr() for k, t in res.items()})
+        prm = self._params(dtype, stride if off is None else 0, 0, 0, 0)
+        _call(self.lib, 'nmod_kmer_mix', prm, npos, _ptr(sig), _ptr(off), _ptr(code), ncodes, _ptr(mean0), _ptr(sd0), C.byref(opts), C.byref(o))
         return res
 
     def rescale_reads(self, val, off, base, mean=None, sd=None, k=None, center=None, *, mode='fit_apply', weighted=True, clip_sigma=3.0,

@@ -9,6 +9,12 @@ lets a control of one genome serve a sample of another, or a control that covers
     prof = model_profile(model, container.load_group('sample.npz'))       # a kind-'model' profile of the sample's positions
     onesample.mtest1({... 'nmod_profile': prof ...})
 
+A second table, the MODIFIED one that readllr's --altModel takes, is either built the same way from a fully modified control or learnt
+from a mixed (native, partly modified) sample against the control's table (K17, nmod_kmer_mix):
+
+    alt, table = learn_alt_model(container.load_group('native.npz'), model)
+    save_kmer_model('native_alt_kmer_model.npz', alt)
+
 The pooling runs in the HIP library; there is no CPU fallback.  Events are int16-exact (3-decimal), and that is the streaming form
 of the device entry; float32 / float64 rows are reduced too, by a form that is not tuned.
 """
@@ -147,6 +153,91 @@ def write_kmer_table(path, model):
     cols = [np.asarray(model[f]).tolist() for f in ('n_positions', 'n_samples', 'mean', 'sd')]
     with open(path, 'w') as f:
         f.writelines('%s %d %d %.6f %.6f\n' % ((kmer_string(c, k),) + row) for c, row in enumerate(zip(*cols)))
+
+
+KMER_MIX_COLUMNS = ('kmer', 'n_positions', 'n_used', 'n_outside', 'mean0', 'sd0', 'pi', 'mu_mod', 'sd_mod', 'llr', 'iters', 'status', 'kept')
+
+
+def _listed_rows(group, sites):
+    """which rows of a per-position group are among `sites` ((chrom, strand, pos) arrays, pos 0-based)"""
+    chrom, strand, pos = (np.asarray(x) for x in sites)
+    if not (len(chrom) == len(strand) == len(pos)):
+        raise ValueError('sites: chrom, strand and pos need one entry per site')
+    n = len(group['pos'])
+    _, inv = np.unique(np.concatenate([np.asarray(group['chrom']).astype(str), chrom.astype(str)]), return_inverse=True)
+    minus = np.concatenate([np.asarray(group['strand']).astype(str), strand.astype(str)]) == '-'
+    key = ((inv.astype(np.int64) * 2 + minus) << 40) | np.concatenate([np.asarray(group['pos'], dtype=np.int64), pos.astype(np.int64)])
+    return np.isin(key[:n], key[n:])
+
+
+def select_alt_codes(res, mean0, sd0, min_samples=1000, min_pi=0.05, min_shift=1.0):
+    """The codes of a kmer_mix result whose modified component goes into the table: the status has none of L.KMIX_DEGENERATE /
+    TOO_FEW / NO_MODEL, n_used >= min_samples, pi >= min_pi and |mu_mod - mean0| >= min_shift * sd0.  By effect size, not by llr: at
+    the pooled sample sizes of a k-mer any second component has a large llr (include/nanomod_hip.h).  L.KMIX_NOT_CONVERGED does not
+    exclude a code."""
+    with np.errstate(invalid='ignore'):
+        return ((np.asarray(res['status']) & L.KMIX_NO_ESTIMATE) == 0) & (np.asarray(res['n_used']) >= min_samples) & \
+               (np.asarray(res['pi']) >= min_pi) & (np.abs(np.asarray(res['mu_mod']) - mean0) >= min_shift * sd0)
+
+
+def alt_model_from(model, res, kept):
+    """the version-1 k-mer model of the kept codes' modified components: mean / sd NaN elsewhere (a NaN entry is an unusable code to
+    every --altModel), n_samples = n_used, n_clipped = n_outside, clip_sigma 0"""
+    kept = np.asarray(kept, dtype=bool)
+    return dict(version=np.int32(KMER_MODEL_VERSION), k=np.int32(model['k']), center=np.int32(model['center']), clip_sigma=np.float64(0.0),
+                n_positions=np.asarray(res['n_positions'], dtype=np.int64), n_samples=np.asarray(res['n_used'], dtype=np.int64),
+                n_clipped=np.asarray(res['n_outside'], dtype=np.int64),
+                mean=np.where(kept, res['mu_mod'], np.nan).astype(np.float64), sd=np.where(kept, res['sd_mod'], np.nan).astype(np.float64))
+
+
+def learn_alt_model(group, model, sites=None, min_coverage=5, mix_model='free', max_iter=200, tol=1e-6, min_samples=1000, min_pi=0.05,
+                    min_shift=1.0, device=0, log=print):
+    """The MODIFIED k-mer model learnt from a mixed sample (K17, nmod_kmer_mix): `group` is the per-position container of a native,
+    partly modified sample, `model` the k-mer model of an unmodified control (build_kmer_model).  Per k-mer the unmodified component is
+    fixed at the control's entry, the events of the k-mer's positions are pooled, and y ~ (1 - pi) N(mean0, sd0^2) + pi N(m, v) is
+    fitted on the device (mix_model 'free': v free, 'equal': v = sd0^2).  The codes come from group_codes; positions below
+    min_coverage reads take no part, and with `sites` ((chrom, strand, pos) arrays, pos 0-based: what readllr.read_sites_file returns
+    for the first three columns of a _sign_test.txt, _sign_test_fdr.txt or _site_stoich.txt) neither do the positions not listed — so
+    only positions `detect` flagged may be pooled.
+    A k-mer is KEPT by select_alt_codes(min_samples, min_pi, min_shift).  The three thresholds are defaults of judgement, not
+    measurements: 1 000 events, a twentieth of the events, one control sd.  pi is the share over all pooled events of the k-mer, not
+    per site (that is K14's job, with the learnt table).
+    Returns (alt, table): alt a dict of KMER_MODEL_FIELDS (alt_model_from) that save_kmer_model and every --altModel take as it is;
+    table every per-code output of the fit, mean0, sd0 and `kept`."""
+    k, center = _check_k(model['k'], model['center'])
+    ncodes = 4 ** k
+    mean0, sd0 = np.asarray(model['mean'], dtype=np.float64), np.asarray(model['sd'], dtype=np.float64)
+    if mean0.shape != (ncodes,) or sd0.shape != (ncodes,):
+        raise ValueError('model mean / sd must be float64[4^k]')
+    off = np.ascontiguousarray(group['off'], dtype=np.int64)
+    codes = group_codes(group, k, center)
+    no_context = int((codes < 0).sum())
+    thin = (np.diff(off) < min_coverage) & (codes >= 0)
+    codes[thin] = -1
+    unlisted = np.zeros(len(codes), bool)
+    if sites is not None:
+        unlisted = ~_listed_rows(group, sites) & (codes >= 0)
+        codes[unlisted] = -1
+    sig = _encode(group['sig']) if len(codes) else np.zeros(0, np.int16)
+    res = engine.kmer_mix_host(sig, off, codes, ncodes, mean0, sd0, model=mix_model, max_iter=max_iter, tol=tol, min_samples=2, device=device)
+    kept = select_alt_codes(res, mean0, sd0, min_samples, min_pi, min_shift)
+    st = res['status']
+    log('kmer mix: k = %d, %d position(s) pooled over %d k-mer(s); %d k-mer(s) kept (n_used >= %d, pi >= %g, shift >= %g sd0), %d not '
+        'converged, %d without a control entry; dropped: %d without a full k-mer, %d below MinCoverage%s'
+        % (k, int(res['n_positions'].sum()), int((res['n_positions'] > 0).sum()), int(kept.sum()), int(min_samples), float(min_pi),
+           float(min_shift), int(((st & L.KMIX_NOT_CONVERGED) != 0).sum()), int(((st & L.KMIX_NO_MODEL) != 0).sum()), no_context,
+           int(thin.sum()), (', %d not among the sites' % int(unlisted.sum())) if sites is not None else ''))
+    table = dict({f: res[f] for f in L.KMIX_COUNT_FIELDS + L.KMIX_FIELDS + ('iters', 'status')}, mean0=mean0, sd0=sd0, kept=kept)
+    return alt_model_from(model, res, kept), table
+
+
+def write_kmer_mix_table(path, model, table):
+    """<FileID>_kmer_mix.txt: per k-mer the KMER_MIX_COLUMNS 'kmer n_positions n_used n_outside mean0 sd0 pi mu_mod sd_mod llr iters
+    status kept' as '%s %d %d %d' + five '%.6f' + '%.3f %d %d %d' (Python's spelling of nan)"""
+    k = int(model['k'])
+    cols = [np.asarray(table[f]).tolist() for f in KMER_MIX_COLUMNS[1:-1]] + [np.asarray(table['kept']).astype(int).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%s %d %d %d %.6f %.6f %.6f %.6f %.6f %.3f %d %d %d\n' % ((kmer_string(c, k),) + row) for c, row in enumerate(zip(*cols)))
 
 
 def model_profile(model, group, min_positions=1):
