@@ -650,6 +650,8 @@ void ks_rank_kernel(RankStatsArgs args) {
     }
     Q4Raw ra = load_q4(sig_c, off_c, idx_a, have_a);                          // the round being ranked next (raw)
     Q1Raw rt = load_q1(sig_c, off_c, idx_t, have_t);                          // first one-per-lane round
+    [[maybe_unused]] Q4Raw ra1 = ra;                                           // fixed stride: the round after `ra`, ranked with it
+    if constexpr (UNIFORM) ra1 = load_q4(sig_q, off_q, 4 * LG + 4 * gl, 1 < full);
 
     if constexpr (PACKED) {
       // two keys per register through the network, then the sorted keys as floats; the top C - m keys of the position
@@ -710,12 +712,56 @@ void ks_rank_kernel(RankStatsArgs args) {
     // everything requested before the sort has arrived; from here the number of outstanding loads is known
     __builtin_amdgcn_s_waitcnt(0x0F70);
     walk.collect();
-    if (!coop) {
+    if constexpr (UNIFORM) {
+      // Fixed stride: every wave runs the same rounds, and a round lasts as long as its chain of LDS probes (1 + log2 C
+      // dependent round trips) however many samples walk it side by side — with the waves of a SIMD in step, nothing else
+      // fills that time.  So the rounds are made fewer and wider: the full rounds go two at a time (eight searches in
+      // flight; `ra` and `ra1` hold rounds c and c + 1), and the last full round takes the first one-per-lane round along
+      // (five).  200 v 200: 8 + 5 instead of 4 + 4 + 4 + 1.  The bins are sums: the order of the samples does not matter.
+      const int merged = (full_w > 0 && tail_w > 0) ? 1 : 0;
+      const int plain = full_w - merged;                              // full rounds ranked without a one-per-lane sample
+      int c = 0;
+#pragma unroll 1
+      for (; c + 2 <= plain; c += 2) {
+        // (past the last round the last round again — a load that is never used, from an address that exists)
+        const Q4Raw rb = load_q4(sig_q, off_q, min(c + 2, full - 1) * (4 * LG) + 4 * gl, true);
+        const Q4Raw rb1 = load_q4(sig_q, off_q, min(c + 3, full - 1) * (4 * LG) + 4 * gl, true);
+        float x0[4], x1[4];
+        q4_values(x0, ra, true);
+        q4_values(x1, ra1, true);
+        const float xa[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+        if (s_full) rank_and_count(std::integral_constant<int, 8>{}, std::true_type{}, keys, xa);
+        else rank_and_count(std::integral_constant<int, 8>{}, std::false_type{}, keys, xa);
+        ra = rb; ra1 = rb1;
+      }
+      if (c < plain) {                                                // an odd round left over: `ra1` already holds the one after it
+        float xa[4];
+        q4_values(xa, ra, true);
+        if (s_full) rank_and_count(std::integral_constant<int, 4>{}, std::true_type{}, keys, xa);
+        else rank_and_count(std::integral_constant<int, 4>{}, std::false_type{}, keys, xa);
+        ra = ra1;
+      }
+      if (merged) {
+        float x4[4];
+        q4_values(x4, ra, true);
+        const float xa[5] = {x4[0], x4[1], x4[2], x4[3], q1_value(rt, full * (4 * LG) + gl < q)};
+        const int idx = full * (4 * LG) + LG + gl;
+        rt = load_q1(sig_q, off_q, idx, idx < q);
+        if (s_full) rank_and_count(std::integral_constant<int, 5>{}, std::true_type{}, keys, xa);
+        else rank_and_count(std::integral_constant<int, 5>{}, std::false_type{}, keys, xa);
+      }
+#pragma unroll 1
+      for (int ct = merged; ct < tail_w; ++ct) {
+        float xq[1] = {q1_value(rt, full * (4 * LG) + ct * LG + gl < q)};
+        const int idx = full * (4 * LG) + (ct + 1) * LG + gl;
+        rt = load_q1(sig_q, off_q, idx, idx < q);
+        if (s_full) rank_and_count(std::integral_constant<int, 1>{}, std::true_type{}, keys, xq);
+        else rank_and_count(std::integral_constant<int, 1>{}, std::false_type{}, keys, xq);
+      }
+    } else if (!coop) {
 #pragma unroll 1
       for (int c = 0; c < full_w; ++c) {
-        // (UNIFORM: past the last round the last round again — a load that is never used, from an address that exists)
-        const Q4Raw rb = UNIFORM ? load_q4(sig_q, off_q, min(c + 1, full - 1) * (4 * LG) + 4 * gl, true)
-                                 : load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
+        const Q4Raw rb = load_q4(sig_q, off_q, (c + 1) * (4 * LG) + 4 * gl, c + 1 < full);
         float xa[4];
         q4_values(xa, ra, c < full);
         if (s_full) rank_and_count(std::integral_constant<int, 4>{}, std::true_type{}, keys, xa);

@@ -5,6 +5,10 @@ hardware (gfx950 included) the program must keep
     VALU writes a VGPR  ->  a DPP instruction reads it as its DPP source:   2 wait states
     a VALU instruction writes EXEC (v_cmpx*)  ->  a DPP instruction:        5 wait states
       (EXEC written by the scalar unit — s_mov / s_and / s_or ... exec — needs none: LLVM's GCNHazardRecognizer::checkDPPHazards)
+    a VALU instruction writes EXEC (v_cmpx*)  ->  v_readlane / v_readfirstlane / v_writelane:   4 wait states
+      (gfx90a and later: LLVM's VALUWriteEXECRWLane.  The register allocator places v_readlane / v_writelane of its own
+      wherever it spills a scalar register into the lanes of a vector register, so a v_cmpx in inline asm can meet one
+      anywhere: DESIGN_NOTES.md A.14 records a build in which it did)
 (one wait state per intervening instruction, s_nop N = N + 1).  The assembler's hazard recognizer handles what the compiler
 emits; inline asm is opaque text to the scheduler, so this script re-checks the final ISA of a translation unit:
 
@@ -18,6 +22,7 @@ import sys
 import tempfile
 
 DPP_MOD = re.compile(r'\b(quad_perm:|row_shl:|row_shr:|row_ror:|row_mirror|row_half_mirror|row_bcast:|row_newbcast:|row_share:|row_xmask:|wave_shl|wave_shr|wave_rol|wave_ror)')
+RW_LANE = ('v_readlane_b32', 'v_readfirstlane_b32', 'v_writelane_b32')
 REG = re.compile(r'^v(\d+)$|^v\[(\d+):(\d+)\]$')
 
 
@@ -69,6 +74,14 @@ def check(text):
                     bad.append((func, ln, 'DPP %d wait state(s) after an EXEC write: "%s" -> "%s"' % (dist, t, txt)))
                 dist += wait_states(mn, t)
                 if dist >= 5:
+                    break
+        if mnem.split('_e')[0] in RW_LANE:
+            dist = 0
+            for mn, dst, wexec, t in reversed(window):
+                if wexec and dist < 4:
+                    bad.append((func, ln, '%s %d wait state(s) after a VALU write of EXEC: "%s" -> "%s"' % (mnem, dist, t, txt)))
+                dist += wait_states(mn, t)
+                if dist >= 4:
                     break
         dst = regs(ops[0].split()[0]) if (ops and mnem.startswith('v_')) else set()
         wexec = mnem.startswith('v_cmpx') or (mnem.startswith('v_') and bool(ops) and ops[0].split()[0] in ('exec', 'exec_lo', 'exec_hi'))

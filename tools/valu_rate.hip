@@ -7,6 +7,19 @@
 #include "../nanomod_amd/csrc/packed_sort_i16.hpp"
 using namespace nmod;
 
+// A level of K1's binary search written as a masked add (measured against the select form and not adopted: DESIGN_NOTES.md
+// A.14): EXEC &= (t < x), the add under that mask, EXEC restored from `live` (read once, ahead of the steps)
+__device__ __forceinline__ unsigned long long exec_live() {
+  unsigned long long live;
+  asm volatile("s_mov_b64 %0, exec" : "=s"(live));
+  return live;
+}
+template <int STEP_BYTES>
+__device__ __forceinline__ unsigned masked_step(unsigned off, float t, float x, unsigned long long live) {
+  asm("v_cmpx_lt_f32 vcc, %1, %2\n\tv_add_u32 %0, %3, %0\n\ts_mov_b64 exec, %4" : "+v"(off) : "v"(t), "v"(x), "n"(STEP_BYTES), "s"(live) : "vcc");
+  return off;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k(float* out, int iters, float seed) {
   int lane = threadIdx.x & 63;
@@ -60,6 +73,15 @@ __global__ __launch_bounds__(256) void k(float* out, int iters, float seed) {
         const unsigned t0 = pk_lane_xor<2>(u[0]), t1 = pk_lane_xor<2>(u[1]), t2 = pk_lane_xor<2>(u[2]), t3 = pk_lane_xor<2>(u[3]);
         const unsigned t4 = pk_lane_xor<2>(u[4]), t5 = pk_lane_xor<2>(u[5]), t6 = pk_lane_xor<2>(u[6]), t7 = pk_lane_xor<2>(u[7]);
         pk_lane_stage<0>(u, t0, t1, t2, t3, t4, t5, t6, t7, 0x3333333333333333ull);
+      } else if constexpr (MODE == 12) {  // a level of K1's binary search as a select: v_cmp + (2 wait states) + v_cndmask + v_add, 16 chains
+        unsigned* u = reinterpret_cast<unsigned*>(x);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[r] = (__uint_as_float(u[r]) < seed) ? u[r] + 8u : u[r];
+      } else if constexpr (MODE == 13) {  // ... as a masked add: v_cmpx + v_add + s_mov exec, EXEC read once
+        unsigned* u = reinterpret_cast<unsigned*>(x);
+        const unsigned long long live = exec_live();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) u[r] = masked_step<8>(u[r], __uint_as_float(u[r]), c, live);
       } else if constexpr (MODE == 8) {   // v_cndmask pairs: cmp + 2 cndmask
 #pragma unroll
         for (int r = 0; r < 16; r += 2) { bool g = x[r] > x[r + 1]; float a = g ? x[r + 1] : x[r], b = g ? x[r] : x[r + 1]; x[r] = a; x[r + 1] = b; }
@@ -72,16 +94,17 @@ __global__ __launch_bounds__(256) void k(float* out, int iters, float seed) {
   out[blockIdx.x * 256 + threadIdx.x] = s;
 }
 
+// lds_bytes: dynamic LDS per block, to hold the occupancy down (40 000 bytes: four blocks per compute unit, 4 waves per SIMD, as K1 runs)
 template <int MODE>
-void run(const char* name, int valu_per_block, float* d) {
+void run(const char* name, int valu_per_block, float* d, size_t lds_bytes = 0) {
   const int iters = 2000, blocks = 256 * 8;
   hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-  hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), 0, 0, d, 10, 1.0f);
+  hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), lds_bytes, 0, d, 10, 1.0f);
   hipEventRecord(a);
-  hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), 0, 0, d, iters, 1.0f);
+  hipLaunchKernelGGL(k<MODE>, dim3(blocks), dim3(256), lds_bytes, 0, d, iters, 1.0f);
   hipEventRecord(b); hipEventSynchronize(b);
   float ms; hipEventElapsedTime(&ms, a, b);
-  // per SIMD: 8 waves x iters x 4 reps x valu_per_block instructions
+  // per SIMD: 8 waves x iters x 4 reps x valu_per_block instructions (the same work, whatever the occupancy)
   double insts = 8.0 * iters * 4 * valu_per_block;
   double cyc = ms * 1e-3 * 2.4e9;
   printf("%-34s %7.3f ms  %6.2f cycles per VALU instruction per SIMD (at 2.4 GHz)\n", name, ms, cyc / insts);
@@ -102,5 +125,9 @@ int main(int argc, char** argv) {
   if (only < 0 || only == 9) run<9>("packed i16 CE (v_pk_min+v_pk_max)", 16, d);
   if (only < 0 || only == 10) run<10>("within-register CE (2 sdwa) + add", 48, d);
   if (only < 0 || only == 11) run<11>("packed cross-lane stage (8 dpp+16 pk)", 24, d);
+  if (only < 0 || only == 12) run<12>("search level, select (3 VALU)", 48, d);
+  if (only < 0 || only == 13) run<13>("search level, masked add (2 VALU)", 32, d);
+  if (only < 0 || only == 12) run<12>("select, 4 waves per SIMD", 48, d, 40000);
+  if (only < 0 || only == 13) run<13>("masked add, 4 waves per SIMD", 32, d, 40000);
   return 0;
 }
