@@ -979,6 +979,85 @@ int nmod_site_pairs(const nmod_params* prm, int64_t nreads, const int32_t* cs, c
                     const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
                     const nmod_pairs_opts* opts, const nmod_pairs_out* out);
 
+/* Soft same-read linkage of pairs of sites from window sums: per pair the two marginal modified shares, the linkage D of the two
+ * hidden states with a likelihood interval, the correlation r and the likelihood-ratio test of independence (K18; the reference
+ * project has no such step).  K16 counts a read at a site only where its window sum lies beyond +-thr; here every read with a VALID
+ * score at both sites takes part with its likelihood, as in K14.  Memspaces, the NULL and struct_size rules: those of nmod_site_pairs
+ * and nmod_site_stoich.
+ *   ROWS.  Reads, scores, keys, poff and npairs are nmod_site_pairs' arguments, under its rules and refusals.  A read takes part in
+ *     pair j = (a, b) iff it covers both sites and its scores there, s_a and s_b, are VALID (fabs(s) <= DBL_MAX, as in K14).  The row of
+ *     pair j holds those reads IN ASCENDING READ INDEX: rows prow_off[j] .. prow_off[j + 1] - 1 of sa, sb (float64) and read (int32).
+ *     nmod_pair_rows_count computes prow_off[npairs + 1] (int64; integer atomics and a scan, on prm->stream) and synchronises the
+ *       stream once to return *nrows_out (a host pointer), as nmod_pair_index does.  NMOD_ERR_INVALID_ARG: nmod_site_pairs' refusals
+ *       for the shared arguments, a NULL prow_off_out or nrows_out, nrows > 2^31 - 1 (prow_off is written by then).
+ *     nmod_pair_rows_fill writes sa, sb, read (nrows each; a NULL one is skipped).  Every read takes the next free row of its pair by
+ *       an integer atomic, then the 64-bit keys pair << 32 | read are sorted (radix_sort.hpp) and the scores gathered: no float
+ *       atomics, and two runs give the same bytes in either memspace.  NMOD_ERR_INVALID_ARG: the same refusals, nrows outside
+ *       0 .. 2^31 - 1, a NULL prow_off, host prow_off that does not start at 0, ascend and end at nrows.  Device prow_off is not
+ *       checked: a row outside its pair's range is skipped.  nrows == 0: NMOD_OK, nothing to do.
+ *   nmod_pair_linkage(prm, npairs, sa, sb, prow_off, opts, out): per pair its row of (s_a, s_b); a read with either score invalid takes
+ *     no part (it counts as t = 0 in both rows), n = the reads that do.  The joint law of the two hidden states (1: modified):
+ *         pi11 = pa pb + D,   pi10 = pa qb - D,   pi01 = qa pb - D,   pi00 = qa qb + D,     q = 1 - p.
+ *     A TWO-STAGE estimate: the margins from the marginal likelihoods, then D with the margins fixed.
+ *     Stage 1.  pa = K14's estimate over the row of s_a, pb over the row of s_b: the same rule (0 iff S(0) <= 0, else 1 iff S(1) >= 0,
+ *       else the root), the same EVALUATION, BRACKETED ITERATION and stop test, in the same order of operations and of the sums: pa and
+ *       pb have the bits nmod_site_stoich gives for that row.  Each margin's likelihood is correctly specified whatever D is.
+ *     Stage 2.  Per read u_a = K14's u at pa with the sign of the side: + t / (1 - qa t) on the plus side, - t / (1 - pa t) on the minus
+ *       side; u_b likewise at pb; v = u_a * u_b.  The read's likelihood relative to independence is exactly 1 + D v.
+ *       The range of D: d_min = -min(pa pb, qa qb), d_max = min(pa qb, qa pb).  One evaluation at D, contraction off, per read:
+ *           dv = max(D * v, -1),   w = v / (1 + dv),   S += w,   Q += w * w,   g += log1p(dv).
+ *       A zero denominator (the ends only) gives w = +-inf and g = -inf, which is wanted, as in K14.
+ *       D^: d_min iff S(d_min) <= 0 (NMOD_LINK_AT_MIN); else d_max iff S(d_max) >= 0 (NMOD_LINK_AT_MAX); else the root of S in
+ *       (d_min, d_max) by K14's bracketed iteration, right iff S(x) > 0, x' = x + S / Q.  iters = its evaluations (0 at either end).
+ *     stat = max(2 g(D^), 0);  p_indep = max(erfc(sqrt(stat / 2)), DBL_MIN), the chi2_1 tail;  r = D^ / sqrt((pa qa) (pb qb)).
+ *     The interval {d : 2 (g(D^) - g(d)) <= ci_drop}: d_lo = d_min iff that holds at d_min, else the root in (d_min, D^) by K14's pi_lo
+ *       iteration (h = 2 (g(D^) - g(x)), x' = x + (h - ci_drop) / (2 S)); d_hi = d_max iff it holds at d_max, else the root in
+ *       (D^, d_max) by K14's pi_hi iteration.  With d_lo and d_hi both NULL no interval root is run.  max_iter bounds each of the five
+ *       roots on its own; one still running then sets NMOD_LINK_NOT_CONVERGED, the values are written all the same.
+ *     Status bits:
+ *       NMOD_LINK_TOO_FEW      n < min_reads: NaN outputs, iters 0 (n_valid is written)
+ *       NMOD_LINK_FLAT         K14's FLAT on either margin (the sum of t of a row is 0): NaN outputs, iters 0
+ *       NMOD_LINK_DEGENERATE   a margin is 0 or 1, the range of D is a point: d = d_lo = d_hi = 0, stat = 0, p_indep = 1, r = NaN, iters 0
+ *       NMOD_LINK_AT_MIN, NMOD_LINK_AT_MAX, NMOD_LINK_NOT_CONVERGED   see above
+ *       NMOD_LINK_TOO_LARGE    a row beyond NMOD_MAX_DEEP reads: NaN outputs, n_valid 0, iters 0
+ *     Outputs (npairs each; a NULL member is skipped; requesting fewer never changes the bits of the others): doubles pa, pb, d, d_lo,
+ *       d_hi, r, stat, p_indep; int32 n_valid, iters; uint8 status.  p_indep is per pair and unadjusted: nmod_fdr_adjust takes it.
+ *     Sums as in K14: the lane's reads in ascending index, then the library's lane, wave and LDS reductions; no float atomics.  A row of
+ *     up to NMOD_LINK_SMALL reads is computed by 16 lanes, up to NMOD_LINK_WAVE by a wave, a longer one by a workgroup (K14's steps, which
+ *     the bits of pa and pb rest on; not tuned for this kernel): a pair's bits depend on its row alone, not on the batch, the order of
+ *     the pairs, the memspace or the outputs asked for.  Reads struct_size, device, stream, memspace of prm.  NMOD_MEM_DEVICE:
+ *     everything is enqueued on prm->stream, no host read and no synchronisation.  npairs == 0 is NMOD_OK.
+ *     NMOD_ERR_INVALID_ARG before any device work: opts NULL or of another struct_size, max_iter outside 1 .. 200, min_reads < 1, tol
+ *     not finite or < 0, ci_drop not finite or <= 0, npairs outside 0 .. 2^31 - 2, a NULL prow_off, NULL sa or sb where a row has a
+ *     read, host prow_off that decreases.
+ *   What this is and is not.  D is information-orthogonal to the margins at D = 0 (the expected cross term factorises into a
+ *     zero-mean score), so stat has the chi2_1 law of the full likelihood-ratio test under independence; it never exceeds the full
+ *     likelihood-ratio statistic, the margins being held at values the full fit is free to move (in a simulation of 4 000 pairs per
+ *     cell against the full model by EM to 1e-11 the largest excess was 0 to rounding and the median ratio 0.96 - 0.999).  The full EM
+ *     needed a median of 560 iterations at 1 sd separation and did not converge in 2 000 for 7 - 9 % of the pairs, which is why it is
+ *     not what is built.  Null rejection at the 5 % level (tests/test_site_linkage.py): 0.053 at 200 reads, 3 sd, shares 0.3 / 0.5;
+ *     0.057 at 20 reads, 3 sd, 0.5 / 0.5 (4 000 seeded null pairs each).  It is liberal below about 20 reads (0.068 at 10 reads, 3 sd,
+ *     0.5 / 0.5) and conservative near an end of the range or at low separation (0.032 at 200 reads, 1 sd, 0.3 / 0.3; 0.024 at 200
+ *     reads, 3 sd, 0.05 / 0.05).  The default min_reads of the Python layers is 20.
+ * Stops at: pairs only; the reads are treated as independent; both k-mer tables are taken as right; no interval for the pi cells;
+ * p_indep is unadjusted. */
+#define NMOD_LINK_SMALL 256                /* reads of a row up to which 16 lanes compute it (K14's step) */
+#define NMOD_LINK_WAVE 1024                /* ... up to which one wave does (a workgroup beyond) */
+enum { NMOD_LINK_TOO_FEW = 1, NMOD_LINK_FLAT = 2, NMOD_LINK_NOT_CONVERGED = 4, NMOD_LINK_AT_MIN = 8, NMOD_LINK_AT_MAX = 16,
+       NMOD_LINK_TOO_LARGE = 32, NMOD_LINK_DEGENERATE = 64 };
+typedef struct nmod_link_opts { int32_t struct_size, max_iter, min_reads, reserved; double tol, ci_drop; } nmod_link_opts;
+typedef struct nmod_link_out { int32_t struct_size; int32_t reserved;
+  double *pa, *pb, *d, *d_lo, *d_hi, *r, *stat, *p_indep; int32_t *n_valid, *iters; uint8_t* status;
+} nmod_link_out;
+int nmod_pair_rows_count(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                         const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
+                         int64_t* prow_off_out, int64_t* nrows_out /* host */);
+int nmod_pair_rows_fill(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                        const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
+                        const int64_t* prow_off, int64_t nrows, double* sa, double* sb, int32_t* read);
+int nmod_pair_linkage(const nmod_params* prm, int64_t npairs, const double* sa, const double* sb, const int64_t* prow_off,
+                      const nmod_link_opts* opts, const nmod_link_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -315,6 +315,31 @@ def make_pairs_opts(thr=2.5, min_reads=10, flags=0):
 make_pairs_out = functools.partial(make_out, NmodPairsOut)
 
 
+LINK_TOO_FEW, LINK_FLAT, LINK_NOT_CONVERGED, LINK_AT_MIN, LINK_AT_MAX, LINK_TOO_LARGE, LINK_DEGENERATE = 1, 2, 4, 8, 16, 32, 64
+LINK_NO_ESTIMATE = LINK_TOO_FEW | LINK_FLAT | LINK_TOO_LARGE
+LINK_SMALL, LINK_WAVE = 256, 1024         # nmod_pair_linkage: reads of a row up to which 16 lanes / one wave compute it (K14's steps)
+LINK_FIELDS = ('pa', 'pb', 'd', 'd_lo', 'd_hi', 'r', 'stat', 'p_indep')
+LINK_INT_FIELDS = ('n_valid', 'iters')
+
+
+class NmodLinkOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'max_iter', 'min_reads', 'reserved')] + [('tol', C.c_double), ('ci_drop', C.c_double)]
+
+
+class NmodLinkOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in LINK_FIELDS + LINK_INT_FIELDS + ('status',)]
+
+
+def make_link_opts(max_iter=60, min_reads=20, tol=1e-12, ci_drop=STOICH_CI_DROP_95):
+    o = NmodLinkOpts()
+    o.struct_size = C.sizeof(NmodLinkOpts)
+    o.max_iter, o.min_reads, o.tol, o.ci_drop = int(max_iter), int(min_reads), float(tol), float(ci_drop)
+    return o
+
+
+make_link_out = functools.partial(make_out, NmodLinkOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -386,6 +411,12 @@ _SIGNATURES = {
     'nmod_pair_index': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     'nmod_site_pairs': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.POINTER(NmodPairsOpts), C.POINTER(NmodPairsOut)]),
+    'nmod_pair_rows_count': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.POINTER(C.c_int64)]),
+    'nmod_pair_rows_fill': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'nmod_pair_linkage': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodLinkOpts),
+                                    C.POINTER(NmodLinkOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -231,6 +231,10 @@ def build_parser():
     rp.add_argument('--siteAlpha', type=float, default=0.05, help="--sites stoich: the level of the sites' q-values, in (0, 1]")
     rp.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_fisher over all pairs')
     rp.add_argument('--fdrAlpha', type=float, default=0.05)
+    rp.add_argument('--soft', type=int, default=0, choices=[0, 1], help='1: also the soft linkage of every pair from the window sums of all '
+                    'the reads that cover both sites (marginal shares, linkage D with its interval, r, the test of independence), written to '
+                    '<FileID>_site_linkage.txt')
+    rp.add_argument('--ciLevel', type=float, default=0.95, help='--soft 1: the level of the likelihood interval of D, inside (0, 1)')
     rp.add_argument('--outFolder', default='mRes')
     rp.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_pairs.txt')
     rp.add_argument('--device', type=int, default=0)
@@ -319,6 +323,8 @@ def validate_readpairs(a):
         errs.append('Error: --siteAlpha should be in (0, 1]')
     if not 0.0 < a.fdrAlpha <= 1.0:
         errs.append('Error: --fdrAlpha should be in (0, 1]')
+    if not 0.0 < a.ciLevel < 1.0:
+        errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
     for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
         if not os.path.isfile(f):
             errs.append('Error: input %s does not exist' % f)
@@ -336,12 +342,17 @@ def run_readpairs(a, log=print):
                                       min_reads=a.minReads, window=parse_llr_window(a.llrWindow), prior=a.prior,
                                       min_positions=a.minPositions, rescale={} if a.rescale else None,
                                       fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, site_alpha=a.siteAlpha, device=a.device,
-                                      log=(lambda *x: None) if quiet else log)
+                                      log=(lambda *x: None) if quiet else log, **(dict(soft=True, ci_level=a.ciLevel) if a.soft else {}))
     os.makedirs(a.outFolder, exist_ok=True)
     path = os.path.join(a.outFolder, a.FileID + '_site_pairs.txt')
     readllr.write_site_pairs(path, pairs)
     if not quiet:
         log('Site pairs are saved in %s' % path)
+    if a.soft:
+        path = os.path.join(a.outFolder, a.FileID + '_site_linkage.txt')
+        readllr.write_site_linkage(path, pairs)
+        if not quiet:
+            log('Site linkage is saved in %s' % path)
     return pairs
 
 

@@ -1,4 +1,4 @@
-// The scaffold that the kernels which walk classed positions share (K8 nmod_mix_fraction, K9 nmod_one_sample, K14 nmod_site_stoich).
+// The scaffold that the kernels which walk classed positions share (K8 nmod_mix_fraction, K9 nmod_one_sample, K14 nmod_site_stoich, K15 nmod_site_diff, K18 nmod_pair_linkage).
 // One copy of: the work lists per class and the kernel that fills them, the loop heads of the two persistent forms, the lists' share
 // of the slab and the launches under their caps of workgroups per CU.  What differs — the rule that classes a position, the arithmetic
 // on a row, its outputs — stays with each kernel.  Nothing here multiplies and adds: contraction is the callers' concern.

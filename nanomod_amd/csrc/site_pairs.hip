@@ -17,12 +17,23 @@
 // covers nor max_dist are bounded by the stage.  Counters: integer atomics only, on the int32 counters in device memory (direct form)
 // or on a table in LDS that a workgroup flushes at the end of its persistent loop, one global atomic per non-zero counter (table form,
 // up to NMOD_PAIRS_LDS_MAX pairs): the counts depend on neither the form nor the order of the reads.  No float atomics anywhere.
+//
+// nmod_pair_rows_count / nmod_pair_rows_fill — the rows of K18 (nmod_pair_linkage, site_linkage.hip) on the same walk, sp_walk_reads,
+// whose work per (read, site) and per (read, pair) is a parameter: per pair the reads whose scores at both sites are valid.
+//   sp_rows_kernel<., false>  the walk with "the score is valid" as the staged byte: one integer atomic per (read, pair) on the pair's count
+//   sp_scan_kernel            the counts' exclusive scan in place (prow_off)
+//   lr_init_kernel            every slot of the fill names itself and sorts last
+//   sp_rows_kernel<., true>   the walk again: a read takes the next free row of its pair (an atomic cursor) and writes its key
+//                             pair << 32 | read, its slot and its two scores
+//   rs_sort_pairs             (radix_sort.hpp) the keys ascending: within a pair the rows in the order of the reads
+//   lr_gather_kernel          sa, sb and read in that order: the same bytes whatever order the atomics fell in
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
+#include "radix_sort.hpp"
 #include "read_walk.hpp"
 
 namespace nmod {
@@ -32,14 +43,26 @@ constexpr int64_t kSpPosMask = ((int64_t)1 << 40) - 1;
 constexpr int kSpNone = 2;                        // the staged byte of a site without a call (0: CAN, 1: MOD)
 constexpr int kSpScanPer = 8, kSpScanChunk = 256 * kSpScanPer;
 
-struct SpArgs {
+// what the walk over the reads takes: the reads, the scores, the sites and their pair index, the two lists of the reads
+struct SpWalk {
   int64_t nreads; const int32_t* cs; const int64_t* start; const int64_t* roff; const double* score;
   int64_t nsites; const int64_t* key; const int64_t* poff; int64_t npairs;
+  ReadLists w;
+};
+
+struct SpArgs : SpWalk {
   double thr; int32_t min_reads;
   int32_t* counts;                                // the caller's, or the slab's when the caller asked for none
   nmod_pairs_out out;
   uint32_t* big; uint32_t* big_count;             // the pairs whose p_fisher takes a wave
-  ReadLists w;
+};
+
+// K18's rows (nmod_pair_rows_count / nmod_pair_rows_fill): per pair the reads whose scores at both sites are valid
+struct SpRowArgs : SpWalk {
+  unsigned long long* cnt;                        // count: reads per pair (prow_off before its scan)
+  const int64_t* prow_off; int64_t nrows;         // fill: the rows of pair j are prow_off[j] .. prow_off[j + 1] - 1
+  int32_t* cursor;                                // the rows of each pair taken so far
+  uint64_t* keys; uint32_t* vals; double* ta; double* tb;   // per slot: pair << 32 | read, the slot, the two scores
 };
 
 // ---------------------------------------------------------------------------------------------------------------- the pair index
@@ -92,26 +115,31 @@ __global__ __launch_bounds__(256) void sp_scan_kernel(int64_t* poff, int64_t nsi
 
 // ---------------------------------------------------------------------------------------------------------------- the read kernel
 
-// WAVES == 1: a wave per read (list 0), the workgroup's waves independent; else the workgroup per read (list 1).
-// TABLE: the counters of the call live in the workgroup's LDS until the end
-template <int WAVES, bool TABLE>
-__global__ __launch_bounds__(kRwThreads) void sp_read_kernel(SpArgs a) {
+// One read as the walk hands it to its callers: where its events lie and its scores
+struct SpRead {
+  int64_t read, start, n; bool minus; const double* sc; const int64_t* key;
+  // the score of the read's event at site s; false: no event of this read (keys that do not ascend)
+  __device__ __forceinline__ bool score_at(int64_t s, double& l) const {
+    const int64_t pos = key[s] & kSpPosMask;
+    const int64_t i = minus ? start + n - 1 - pos : pos - start;
+    if (i < 0 || i >= n) return false;
+    l = sc[i];
+    return true;
+  }
+};
+
+// The walk of a persistent grid over the reads of list WAVES == 1 ? 0 : 1 (a wave per read, the workgroup's waves independent; else the
+// workgroup per read): site search, staged windows, forward halo.  What happens per (read, site) and per (read, pair) is the callers':
+//   state_of(rd, s)            the byte staged for site s of the read, kSpNone: the read takes no part in a pair of s
+//   per_pair(rd, idx, ca, cb, s, b)   pair idx = (s, b) with the staged bytes ca, cb of its two sites, neither kSpNone
+template <int WAVES, class StateOf, class PerPair>
+__device__ __forceinline__ void sp_walk_reads(const SpWalk& a, uint8_t* stage, unsigned& sh_item, StateOf state_of, PerPair per_pair) {
   constexpr int CLS = WAVES == 1 ? 0 : 1;
   constexpr int T = WAVES * 64;                                 // threads of a read
   constexpr int PER = kSpWin / T;                               // sites of a tile a thread owns
-  extern __shared__ int lds_tab[];                              // 4 * npairs counters when TABLE, else nothing
-  __shared__ uint8_t lds_stage[WAVES == 1 ? kRwWaves : 1][kSpWin];
-  __shared__ unsigned sh_item;
-  const int ncell = TABLE ? (int)(4 * a.npairs) : 0;
-  if constexpr (TABLE) {
-    for (int c = threadIdx.x; c < ncell; c += kRwThreads) lds_tab[c] = 0;
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  uint8_t* stage = lds_stage[WAVES == 1 ? wave : 0];
   const unsigned cnt = a.w.count[CLS];
-  const double thr = a.thr;
   const int64_t nsites = a.nsites, npairs = a.npairs;
   auto sync = [] { if constexpr (WAVES == 1) wave_lds_sync(); else __syncthreads(); };
 
@@ -124,19 +152,11 @@ __global__ __launch_bounds__(kRwThreads) void sp_read_kernel(SpArgs a) {
     const int64_t cs = a.cs[read], start = a.start[read];
     if (n <= 0 || cs < 0 || start < 0 || start > kSpPosMask) continue;
     const int64_t last_pos = start + n - 1 < kSpPosMask ? start + n - 1 : kSpPosMask;
-    const bool minus = (cs & 1) != 0;
     // the candidate sites the read covers: c_lo .. c_hi - 1 (the same search in every thread of the read)
     const int64_t c_lo = sp_bound<false>(a.key, 0, nsites, (cs << 40) | start);
     const int64_t c_hi = sp_bound<true>(a.key, c_lo, nsites, (cs << 40) | last_pos);
     if (c_hi - c_lo < 2) continue;
-    const double* sc = a.score + begin;
-    auto call_of = [&](int64_t s) -> int {
-      const int64_t pos = a.key[s] & kSpPosMask;
-      const int64_t i = minus ? start + n - 1 - pos : pos - start;
-      if (i < 0 || i >= n) return kSpNone;                      // (keys that do not ascend: no event of this read)
-      const double l = sc[i];
-      return l >= thr ? 1 : (l <= -thr ? 0 : kSpNone);
-    };
+    const SpRead rd{read, start, n, (cs & 1) != 0, a.score + begin, a.key};
 
     for (int64_t a0 = c_lo; a0 < c_hi - 1; a0 += kSpWin) {      // a tile of own sites a0 .. a_end - 1
       const int64_t a_end = a0 + kSpWin < c_hi ? a0 + kSpWin : c_hi;
@@ -146,7 +166,7 @@ __global__ __launch_bounds__(kRwThreads) void sp_read_kernel(SpArgs a) {
       int ca[PER]; int64_t pb[PER], ea[PER];
       for (int64_t w0 = a0; w0 < reach; w0 += kSpWin) {         // (reach >= a_end > a0: the first window is the tile itself)
         const int wn = (int)(reach - w0 < kSpWin ? reach - w0 : kSpWin);
-        for (int e = t; e < wn; e += T) stage[e] = (uint8_t)call_of(w0 + e);
+        for (int e = t; e < wn; e += T) stage[e] = (uint8_t)state_of(rd, w0 + e);
         sync();
         if (w0 == a0) {
 #pragma unroll
@@ -171,20 +191,91 @@ __global__ __launch_bounds__(kRwThreads) void sp_read_kernel(SpArgs a) {
             if (cb == kSpNone) continue;
             const int64_t idx = pb[j] + (b - s - 1);
             if (idx < 0 || idx >= npairs) continue;             // (a poff that is not the keys': outside the counters)
-            const int64_t cell = 4 * idx + 2 * ca[j] + cb;
-            if constexpr (TABLE) atomicAdd(&lds_tab[cell], 1); else atomicAdd(&a.counts[cell], 1);
+            per_pair(rd, idx, ca[j], cb, s, b);
           }
         }
         sync();                                                 // the window is read before the next one is staged
       }
     }
   }
+}
+
+// K16: the staged byte is the read's call at the site, a pair's counter takes one.
+// TABLE: the counters of the call live in the workgroup's LDS until the end
+template <int WAVES, bool TABLE>
+__global__ __launch_bounds__(kRwThreads) void sp_read_kernel(SpArgs a) {
+  extern __shared__ int lds_tab[];                              // 4 * npairs counters when TABLE, else nothing
+  __shared__ uint8_t lds_stage[WAVES == 1 ? kRwWaves : 1][kSpWin];
+  __shared__ unsigned sh_item;
+  const int ncell = TABLE ? (int)(4 * a.npairs) : 0;
+  if constexpr (TABLE) {
+    for (int c = threadIdx.x; c < ncell; c += kRwThreads) lds_tab[c] = 0;
+    __syncthreads();
+  }
+  const double thr = a.thr;
+  int32_t* const counts = a.counts;
+  sp_walk_reads<WAVES>(a, lds_stage[WAVES == 1 ? threadIdx.x >> 6 : 0], sh_item,
+    [thr](const SpRead& rd, int64_t s) -> int {
+      double l;
+      if (!rd.score_at(s, l)) return kSpNone;
+      return l >= thr ? 1 : (l <= -thr ? 0 : kSpNone);
+    },
+    [=](const SpRead&, int64_t idx, int ca, int cb, int64_t, int64_t) {
+      const int64_t cell = 4 * idx + 2 * ca + cb;
+      if constexpr (TABLE) atomicAdd(&lds_tab[cell], 1); else atomicAdd(&counts[cell], 1);
+    });
   if constexpr (TABLE) {
     __syncthreads();
     for (int c = threadIdx.x; c < ncell; c += kRwThreads) {
       const int v = lds_tab[c];
       if (v) atomicAdd(&a.counts[c], v);
     }
+  }
+}
+
+// K18's rows: the staged byte says whether the read's score at the site is valid.  FILL false: a pair's count takes one; true: the read
+// takes the next free row of its pair, in the order the atomics fall (lr_gather_kernel puts the rows of a pair in order)
+template <int WAVES, bool FILL>
+__global__ __launch_bounds__(kRwThreads) void sp_rows_kernel(SpRowArgs a) {
+  __shared__ uint8_t lds_stage[WAVES == 1 ? kRwWaves : 1][kSpWin];
+  __shared__ unsigned sh_item;
+  sp_walk_reads<WAVES>(a, lds_stage[WAVES == 1 ? threadIdx.x >> 6 : 0], sh_item,
+    [](const SpRead& rd, int64_t s) -> int {
+      double l;
+      return rd.score_at(s, l) && fabs(l) <= kDblMax ? 1 : kSpNone;
+    },
+    [&a](const SpRead& rd, int64_t idx, int, int, int64_t s, int64_t b) {
+      if constexpr (!FILL) {
+        atomicAdd(&a.cnt[idx], 1ull);
+      } else {
+        const int64_t r0 = a.prow_off[idx], r1 = a.prow_off[idx + 1];
+        const int64_t slot = r0 + atomicAdd(&a.cursor[idx], 1);
+        if (slot < r0 || slot >= r1 || slot >= a.nrows) return;   // (offsets that are not this call's counts: outside the rows)
+        double la = 0.0, lb = 0.0;
+        rd.score_at(s, la);
+        rd.score_at(b, lb);
+        a.keys[slot] = ((uint64_t)idx << 32) | (uint64_t)(uint32_t)rd.read;
+        a.vals[slot] = (uint32_t)slot;
+        a.ta[slot] = la; a.tb[slot] = lb;
+      }
+    });
+}
+
+// before the fill: every slot names itself and sorts last, so that a slot no read took (offsets that are not this call's counts) is
+// still a row of the gather
+__global__ __launch_bounds__(256) void lr_init_kernel(uint64_t* keys, uint32_t* vals, int64_t nrows) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * 256) { keys[i] = ~0ull; vals[i] = (uint32_t)i; }
+}
+
+// after the sort of the keys: row i is the slot vals[i]
+__global__ __launch_bounds__(256) void lr_gather_kernel(const uint64_t* keys, const uint32_t* vals, const double* ta, const double* tb, int64_t nrows,
+                                                        double* sa, double* sb, int32_t* read) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * 256) {
+    const uint32_t v = vals[i];
+    const bool ok = v < (uint64_t)nrows && keys[i] != ~0ull;
+    if (sa) sa[i] = ok ? ta[v] : nan_f64();
+    if (sb) sb[i] = ok ? tb[v] : nan_f64();
+    if (read) read[i] = (int32_t)(uint32_t)keys[i];
   }
 }
 
@@ -325,6 +416,47 @@ static bool sp_keys_ascend(const int64_t* key, int64_t n) {
   return true;
 }
 
+// The checks of the reads, the sites and the pair index that the entries which walk the reads share (nmod_site_pairs, the two
+// nmod_pair_rows entries), before any device work
+static bool sp_walk_args_ok(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
+                            int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs) {
+  if (nreads < 0 || nreads > (int64_t)INT32_MAX) return false;
+  if (nsites < 0 || nsites > (int64_t)INT32_MAX - 1 || npairs < 0 || npairs > (int64_t)INT32_MAX) return false;
+  if (nreads > 0 && (!cs || !start || !roff)) return false;
+  if ((nsites > 0 && !key) || (npairs > 0 && (!poff || nsites < 2))) return false;
+  if (prm->memspace == NMOD_MEM_HOST) {
+    if (nreads > 0 && !csr_offsets_ok(roff, nreads)) return false;
+    if (nreads > 0 && roff[nreads] > 0 && !score) return false;
+    if (!sp_keys_ascend(key, nsites)) return false;
+    if (poff && (poff[0] != 0 || !csr_offsets_ok(poff, nsites) || poff[nsites] != npairs)) return false;
+    if (!poff && npairs != 0) return false;
+  } else if (nreads > 0 && !score) {
+    return false;
+  }
+  return true;
+}
+
+static void sp_walk_args(SpWalk& a, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
+                         int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs) {
+  a.nreads = nreads; a.cs = cs; a.start = start; a.roff = roff; a.score = score;
+  a.nsites = nsites; a.key = key; a.poff = poff; a.npairs = npairs;
+}
+
+// the inputs of a host call that the walk reads, staged
+static void sp_walk_stage(Slab& slab, SpWalk& a, size_t tot) {
+  const size_t nr = (size_t)a.nreads, ns = (size_t)a.nsites;
+  slab.in(a.cs, nr * 4); slab.in(a.start, nr * 8); slab.in(a.roff, (nr + 1) * 8); slab.in(a.score, tot * 8);
+  slab.in(a.key, ns * 8); slab.in(a.poff, (ns + 1) * 8);
+}
+
+// the two forms of the rows kernel under eight workgroups a CU
+template <bool FILL>
+static void sp_launch_rows(const SpRowArgs& a, int num_cus, hipStream_t stream) {
+  const int64_t cap = (int64_t)num_cus * 8;
+  hipLaunchKernelGGL((sp_rows_kernel<1, FILL>), dim3(persistent_grid(a.nreads, kRwWaves, cap)), dim3(kRwThreads), 0, stream, a);
+  hipLaunchKernelGGL((sp_rows_kernel<kRwWaves, FILL>), dim3(persistent_grid(a.nreads, 1, cap)), dim3(kRwThreads), 0, stream, a);
+}
+
 template <int WAVES, bool TABLE>
 static void sp_launch_read(const SpArgs& a, int64_t cap, hipStream_t stream) {
   const size_t lds = TABLE ? (size_t)a.npairs * 16 : 0;
@@ -374,32 +506,19 @@ extern "C" int nmod_site_pairs(const nmod_params* prm, int64_t nreads, const int
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_pairs_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_pairs_out)) return NMOD_ERR_INVALID_ARG;
   if (!(opts->thr > 0.0) || !(opts->thr <= kDblMax) || opts->min_reads < 1 || (opts->flags & ~NMOD_PAIRS_FORCE_DIRECT)) return NMOD_ERR_INVALID_ARG;
-  if (nreads < 0 || nreads > (int64_t)INT32_MAX) return NMOD_ERR_INVALID_ARG;
-  if (nsites < 0 || nsites > (int64_t)INT32_MAX - 1 || npairs < 0 || npairs > (int64_t)INT32_MAX) return NMOD_ERR_INVALID_ARG;
-  if (nreads > 0 && (!cs || !start || !roff)) return NMOD_ERR_INVALID_ARG;
-  if ((nsites > 0 && !key) || (npairs > 0 && (!poff || nsites < 2))) return NMOD_ERR_INVALID_ARG;
+  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, poff, npairs)) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host) {
-    if (nreads > 0 && !csr_offsets_ok(roff, nreads)) return NMOD_ERR_INVALID_ARG;
-    if (nreads > 0 && roff[nreads] > 0 && !score) return NMOD_ERR_INVALID_ARG;
-    if (!sp_keys_ascend(key, nsites)) return NMOD_ERR_INVALID_ARG;
-    if (poff && (poff[0] != 0 || !csr_offsets_ok(poff, nsites) || poff[nsites] != npairs)) return NMOD_ERR_INVALID_ARG;
-    if (!poff && npairs != 0) return NMOD_ERR_INVALID_ARG;
-  } else if (nreads > 0 && !score) {
-    return NMOD_ERR_INVALID_ARG;
-  }
   if (npairs == 0) return NMOD_OK;
   int num_cus = 0;
   const int rc = select_device(prm, &num_cus);
   if (rc != NMOD_OK) return rc;
   hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t nr = (size_t)nreads, ns = (size_t)nsites, np = (size_t)npairs;
+  const size_t nr = (size_t)nreads, np = (size_t)npairs;
   const size_t tot = host && nreads > 0 ? (size_t)roff[nreads] : 0;
 
   SpArgs a;
   memset(&a, 0, sizeof(a));
-  a.nreads = nreads; a.cs = cs; a.start = start; a.roff = roff; a.score = score;
-  a.nsites = nsites; a.key = key; a.poff = poff; a.npairs = npairs;
+  sp_walk_args(a, nreads, cs, start, roff, score, nsites, key, poff, npairs);
   a.thr = opts->thr; a.min_reads = opts->min_reads;
   a.out = *out;
 
@@ -409,8 +528,7 @@ extern "C" int nmod_site_pairs(const nmod_params* prm, int64_t nreads, const int
   const ReadListSpace lists(slab, nr);
   const size_t o_big = slab.take(np * 4), o_bigc = slab.take(4);
   const size_t o_counts = a.out.counts ? 0 : slab.take(np * 16);
-  slab.in(a.cs, nr * 4); slab.in(a.start, nr * 8); slab.in(a.roff, (nr + 1) * 8); slab.in(a.score, tot * 8);
-  slab.in(a.key, ns * 8); slab.in(a.poff, (ns + 1) * 8);
+  sp_walk_stage(slab, a, tot);
   slab.out(a.out.counts, np * 16); slab.out(a.out.first, np * 4); slab.out(a.out.second, np * 4);
   slab.out(a.out.log_or, np * 8); slab.out(a.out.se, np * 8); slab.out(a.out.phi, np * 8); slab.out(a.out.p_fisher, np * 8);
   slab.out(a.out.status, np);
@@ -440,5 +558,95 @@ extern "C" int nmod_site_pairs(const nmod_params* prm, int64_t nreads, const int
     if (a.out.p_fisher)
       hipLaunchKernelGGL(sp_pair_wave_kernel, dim3(persistent_grid(npairs, 4, (int64_t)num_cus * 8)), dim3(256), 0, stream, a);
   }
+  return launches_end(slab, stream);
+}
+
+extern "C" int nmod_pair_rows_count(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                    const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
+                                    int64_t* prow_off_out, int64_t* nrows_out) {
+  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!prow_off_out || !nrows_out) return NMOD_ERR_INVALID_ARG;
+  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, poff, npairs)) return NMOD_ERR_INVALID_ARG;
+  const bool host = prm->memspace == NMOD_MEM_HOST;
+  if (host && npairs == 0) { prow_off_out[0] = 0; *nrows_out = 0; return NMOD_OK; }
+  int num_cus = 0;
+  const int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
+  hipStream_t stream = (hipStream_t)prm->stream;
+  const size_t nr = (size_t)nreads, np = (size_t)npairs;
+  const size_t tot = host && nreads > 0 ? (size_t)roff[nreads] : 0;
+  int64_t* prow_off = prow_off_out;
+  int64_t total = 0;
+
+  SpRowArgs a;
+  memset(&a, 0, sizeof(a));
+  sp_walk_args(a, nreads, cs, start, roff, score, nsites, key, poff, npairs);
+
+  Slab slab(host);
+  const ReadListSpace lists(slab, nr);
+  sp_walk_stage(slab, a, tot);
+  slab.out(prow_off, (np + 1) * 8);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  a.cnt = reinterpret_cast<unsigned long long*>(prow_off);
+  NMOD_HIP(hipMemsetAsync(prow_off, 0, (np + 1) * 8, stream));
+  if (nreads > 0 && npairs > 0) {
+    NMOD_HIP(lists.fill(slab, a.roff, nreads, num_cus, stream, a.w));
+    sp_launch_rows<false>(a, num_cus, stream);
+  }
+  hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(256), 0, stream, prow_off, npairs);
+  NMOD_HIP(hipMemcpyAsync(&total, prow_off + npairs, 8, hipMemcpyDeviceToHost, stream));
+  NMOD_HIP(hipStreamSynchronize(stream));
+  const int rc_end = launches_end(slab, stream);
+  if (rc_end != NMOD_OK) return rc_end;
+  if (total > (int64_t)INT32_MAX) return NMOD_ERR_INVALID_ARG;
+  *nrows_out = total;
+  return NMOD_OK;
+}
+
+extern "C" int nmod_pair_rows_fill(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                   const double* score, int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs,
+                                   const int64_t* prow_off, int64_t nrows, double* sa, double* sb, int32_t* read) {
+  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (nrows < 0 || nrows > (int64_t)INT32_MAX || !prow_off) return NMOD_ERR_INVALID_ARG;
+  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, poff, npairs)) return NMOD_ERR_INVALID_ARG;
+  const bool host = prm->memspace == NMOD_MEM_HOST;
+  if (host && (prow_off[0] != 0 || !csr_offsets_ok(prow_off, npairs) || prow_off[npairs] != nrows)) return NMOD_ERR_INVALID_ARG;
+  if (nrows > 0 && (npairs == 0 || nreads == 0)) return NMOD_ERR_INVALID_ARG;
+  if (nrows == 0) return NMOD_OK;
+  int num_cus = 0;
+  const int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
+  hipStream_t stream = (hipStream_t)prm->stream;
+  const size_t nr = (size_t)nreads, np = (size_t)npairs, nw = (size_t)nrows;
+  const size_t tot = host ? (size_t)roff[nreads] : 0;
+
+  SpRowArgs a;
+  memset(&a, 0, sizeof(a));
+  sp_walk_args(a, nreads, cs, start, roff, score, nsites, key, poff, npairs);
+  a.prow_off = prow_off; a.nrows = nrows;
+
+  // one slab: the read lists, the cursors, per slot its key, its number and its two scores, the sort's second buffers and scratch; for
+  // the host entry the inputs and outputs as well
+  Slab slab(host);
+  const ReadListSpace lists(slab, nr);
+  const size_t o_cursor = slab.take(np * 4), o_keys = slab.take(nw * 8), o_keys2 = slab.take(nw * 8), o_vals = slab.take(nw * 4),
+               o_vals2 = slab.take(nw * 4), o_ta = slab.take(nw * 8), o_tb = slab.take(nw * 8), o_sort = slab.take(rs_scratch_bytes(nrows));
+  sp_walk_stage(slab, a, tot);
+  slab.in(a.prow_off, (np + 1) * 8);
+  slab.out(sa, nw * 8); slab.out(sb, nw * 8); slab.out(read, nw * 4);
+  NMOD_HIP(slab.commit(stream, prm->device));
+  a.cursor = slab.at<int32_t>(o_cursor);
+  a.keys = slab.at<uint64_t>(o_keys); a.vals = slab.at<uint32_t>(o_vals);
+  a.ta = slab.at<double>(o_ta); a.tb = slab.at<double>(o_tb);
+
+  NMOD_HIP(hipMemsetAsync(a.cursor, 0, np * 4, stream));
+  const unsigned row_grid = persistent_grid(nrows, 256, (int64_t)num_cus * 16);
+  hipLaunchKernelGGL(lr_init_kernel, dim3(row_grid), dim3(256), 0, stream, a.keys, a.vals, nrows);
+  NMOD_HIP(lists.fill(slab, a.roff, nreads, num_cus, stream, a.w));
+  sp_launch_rows<true>(a, num_cus, stream);
+  // pair << 32 | read ascending: the slots of a pair are contiguous already, the sort puts them in the order of the reads
+  NMOD_HIP(rs_sort_pairs(a.keys, a.vals, slab.at<uint64_t>(o_keys2), slab.at<uint32_t>(o_vals2), nrows, slab.at<char>(o_sort), stream));
+  hipLaunchKernelGGL(lr_gather_kernel, dim3(row_grid), dim3(256), 0, stream, (const uint64_t*)a.keys, (const uint32_t*)a.vals, (const double*)a.ta,
+                     (const double*)a.tb, nrows, sa, sb, read);
   return launches_end(slab, stream);
 }

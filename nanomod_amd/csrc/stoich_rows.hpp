@@ -1,5 +1,5 @@
-// What the kernels over rows of window sums share (K14 nmod_site_stoich, K15 nmod_site_diff): whether a score is valid, its signed t,
-// one score's terms of an evaluation, K14's two row policies and the bracketed iteration of include/nanomod_hip.h.  Both units are
+// What the kernels over rows of window sums share (K14 nmod_site_stoich, K15 nmod_site_diff, K18 nmod_pair_linkage): whether a score is
+// valid, its signed t, one score's terms of an evaluation, K14's two row policies and the bracketed iteration of include/nanomod_hip.h.  The units are
 // compiled with contraction off; every operation here is the header's, in its order.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -919,6 +919,34 @@ def site_pairs_host(cs, start, roff, score, key, poff, *, thr=2.5, min_reads=10,
     log_or, se, phi, p_fisher (float64) and status (uint8, L.PAIRS_* bits)."""
     lib = L.load()
     opts, want = _pairs_opts(thr, min_reads, force_direct, want)
+    cs, start, roff, score, key, poff, nreads, npairs = _host_pair_reads(cs, start, roff, score, key, poff)
+    shapes = _pairs_shapes(want, npairs)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_pairs_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_site_pairs', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(poff), npairs, C.byref(opts), C.byref(out))
+    return res
+
+
+def _link_opts(min_reads, ci_level, max_iter, tol):
+    """nmod_link_opts from the Python arguments: the checks and the conversion of ci_level are those of _stoich_opts"""
+    if int(min_reads) != min_reads or int(min_reads) < 1:
+        raise ValueError('min_reads must be an integer >= 1, not %r' % (min_reads,))
+    o = _stoich_opts(1, ci_level, max_iter, tol)
+    return L.make_link_opts(o.max_iter, int(min_reads), o.tol, o.ci_drop)
+
+
+def _link_shapes(npairs, interval=True):
+    shapes = dict({k: ('float64', npairs) for k in L.LINK_FIELDS if interval or k not in ('d_lo', 'd_hi')},
+                  **{k: ('int32', npairs) for k in L.LINK_INT_FIELDS})
+    shapes['status'] = ('uint8', npairs)
+    return shapes
+
+
+def _host_pair_reads(cs, start, roff, score, key, poff):
+    """the reads, sites and pair index of a host call as site_pairs_host checks them"""
     score = np.ascontiguousarray(score, dtype=np.float64)
     roff, nreads, _ = _read_layout(score, roff, 'score')
     cs = _side(cs, np.int32, nreads, 'cs', 'nreads', optional=False)
@@ -928,13 +956,47 @@ def site_pairs_host(cs, start, roff, score, key, poff, *, thr=2.5, min_reads=10,
     if poff[0] != 0 or bool(np.any(np.diff(poff) < 0)):
         raise ValueError('poff must start at 0 and never decrease')
     npairs = _check_pair_counts(nreads, key.shape[0], int(poff[-1]))
-    shapes = _pairs_shapes(want, npairs)
+    return cs, start, roff, score, key, poff, nreads, npairs
+
+
+def pair_rows_host(cs, start, roff, score, key, poff, device=0):
+    """Per pair of sites the reads with a valid score at both (nmod_pair_rows_count, nmod_pair_rows_fill, include/nanomod_hip.h):
+    the arguments of site_pairs_host.  Returns a dict of numpy arrays: prow_off (int64[npairs + 1]) and, per row, sa, sb (float64: the
+    read's scores at the pair's two sites) and read (int32); within a pair the rows are in ascending read index."""
+    lib = L.load()
+    cs, start, roff, score, key, poff, nreads, npairs = _host_pair_reads(cs, start, roff, score, key, poff)
+    prow_off = np.zeros(npairs + 1, dtype=np.int64)
+    nrows = C.c_int64(0)
+    _join_warm_up(device)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    shared = (prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key), _np_ptr(poff), npairs)
+    _call(lib, 'nmod_pair_rows_count', *shared, _np_ptr(prow_off), C.byref(nrows))
+    n = int(nrows.value)
+    res = dict(prow_off=prow_off, sa=np.zeros(n), sb=np.zeros(n), read=np.zeros(n, dtype=np.int32))
+    _call(lib, 'nmod_pair_rows_fill', *shared, _np_ptr(prow_off), n, _np_ptr(res['sa']), _np_ptr(res['sb']), _np_ptr(res['read']))
+    return res
+
+
+def pair_linkage_host(sa, sb, prow_off, *, min_reads=20, ci_level=0.95, max_iter=60, tol=1e-12, interval=True, device=0):
+    """Soft same-read linkage of pairs of sites (nmod_pair_linkage, include/nanomod_hip.h) on host-resident rows: sa, sb (float64) and
+    prow_off (int64[npairs + 1]) as pair_rows_host gives them.  Returns a dict of numpy arrays: pa, pb (the marginal shares, K14's
+    estimates), d (the linkage), with `interval` its likelihood interval d_lo, d_hi at ci_level, r, stat (the likelihood-ratio
+    statistic of independence) and p_indep (its chi2_1 tail), float64; n_valid, iters (int32); status (uint8, L.LINK_* bits)."""
+    lib = L.load()
+    opts = _link_opts(min_reads, ci_level, max_iter, tol)
+    sa = np.ascontiguousarray(sa, dtype=np.float64)
+    sb = np.ascontiguousarray(sb, dtype=np.float64)
+    if sa.ndim != 1 or sb.shape != sa.shape:
+        raise ValueError('sa and sb must be float64 vectors of one length')
+    prow_off, npairs, _ = _read_layout(sa, prow_off, 'sa')
+    if npairs > 2 ** 31 - 2:
+        raise ValueError('at most 2^31 - 2 pairs')
+    shapes = _link_shapes(npairs, interval)
     res = _host_outputs(shapes, fill=shapes)
     _join_warm_up(device)
-    out = L.make_pairs_out(**_np_ptrs(res))
+    out = L.make_link_out(**_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_site_pairs', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
-          _np_ptr(poff), npairs, C.byref(opts), C.byref(out))
+    _call(lib, 'nmod_pair_linkage', prm, npairs, _np_ptr(sa), _np_ptr(sb), _np_ptr(prow_off), C.byref(opts), C.byref(out))
     return res
 
 
@@ -1429,6 +1491,48 @@ class DeviceDetector:
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
         _call(self.lib, 'nmod_site_pairs', prm, nreads, cs.data_ptr(), start.data_ptr(), roff.data_ptr(), score.data_ptr(), key.numel(),
               key.data_ptr(), poff.data_ptr(), npairs, C.byref(opts), C.byref(o))
+        return res
+
+    def pair_rows(self, cs, start, roff, score, key, poff, npairs):
+        """Per pair of sites the reads with a valid score at both (nmod_pair_rows_count, nmod_pair_rows_fill, NMOD_MEM_DEVICE) on the
+        current stream: the arguments of site_pairs.  Synchronises the stream once to learn the number of rows.  Returns a dict of CUDA
+        tensors: prow_off (int64, npairs + 1) and, per row, sa, sb (float64) and read (int32); within a pair the rows are in ascending
+        read index."""
+        torch = self.torch
+        nreads = _device_offsets(torch, roff, 'pair_rows', 'nreads')
+        _cuda_vecs('pair_rows', (('cs', cs, torch.int32, nreads), ('start', start, torch.int64, nreads), ('score', score, torch.float64, None),
+                                 ('key', key, torch.int64, None), ('poff', poff, torch.int64, key.numel() + 1 if key is not None else None)),
+                   one_dim=True, missing='refused')
+        npairs = _check_pair_counts(nreads, key.numel(), npairs)
+        prow_off = torch.empty(npairs + 1, dtype=torch.int64, device=self._dev)
+        nrows = C.c_int64(0)
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        shared = (prm, nreads, cs.data_ptr(), start.data_ptr(), roff.data_ptr(), score.data_ptr(), key.numel(), key.data_ptr(), poff.data_ptr(), npairs)
+        _call(self.lib, 'nmod_pair_rows_count', *shared, prow_off.data_ptr(), C.byref(nrows))
+        n = int(nrows.value)
+        # (a tensor of no elements has no address: one spare row keeps the pointers real)
+        sa, sb = (torch.empty(n + 1, dtype=torch.float64, device=self._dev)[:n] for _ in range(2))
+        read = torch.empty(n + 1, dtype=torch.int32, device=self._dev)[:n]
+        _call(self.lib, 'nmod_pair_rows_fill', *shared, prow_off.data_ptr(), n, sa.data_ptr(), sb.data_ptr(), read.data_ptr())
+        return dict(prow_off=prow_off, sa=sa, sb=sb, read=read)
+
+    def pair_linkage(self, sa, sb, prow_off, *, min_reads=20, ci_level=0.95, max_iter=60, tol=1e-12, interval=True, out=None):
+        """Soft same-read linkage of pairs of sites (nmod_pair_linkage, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising or reading anything back: sa, sb (float64) and prow_off (int64, npairs + 1) CUDA vectors as pair_rows gives
+        them.  Returns a dict of CUDA tensors pa, pb, d, with `interval` d_lo and d_hi, r, stat, p_indep (float64), n_valid, iters
+        (int32) and status (uint8, L.LINK_* bits).  p_indep is a track fdr() takes as it is."""
+        torch = self.torch
+        opts = _link_opts(min_reads, ci_level, max_iter, tol)
+        npairs = _device_offsets(torch, prow_off, 'pair_linkage', 'npairs')
+        _cuda_vecs('pair_linkage', (('sa', sa, torch.float64, None), ('sb', sb, torch.float64, sa.numel() if sa is not None else None)),
+                   one_dim=True, missing='refused')
+        if npairs > 2 ** 31 - 2:
+            raise ValueError('pair_linkage: at most 2^31 - 2 pairs')
+        shapes = _link_shapes(npairs, interval)
+        res = self._outputs(out, shapes, 'pair_linkage')
+        o = L.make_link_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_pair_linkage', prm, npairs, sa.data_ptr(), sb.data_ptr(), prow_off.data_ptr(), C.byref(opts), C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

@@ -267,6 +267,7 @@ def write_site_diff(path, sites):
 
 
 _PAIR_STAT_FIELDS = ('log_or', 'se', 'phi', 'p_fisher')
+LINK_MIN_READS = 20         # reads valid at both sites below which the soft linkage of a pair is not fitted (include/nanomod_hip.h, K18)
 
 
 def read_sites_file(path):
@@ -300,7 +301,8 @@ def site_keys(sites, names):
 
 
 def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, thr=2.5, min_reads=10, window='kmer', prior=0.5,
-                      min_positions=1, rescale=None, fdr=None, fdr_alpha=0.05, site_alpha=0.05, device=0, log=print):
+                      min_positions=1, rescale=None, fdr=None, fdr_alpha=0.05, site_alpha=0.05, device=0, log=print, soft=False,
+                      ci_level=0.95):
     """Same-read co-occurrence of modification calls at pairs of sites of one read-level set (container.READ_FIELDS): are two sites
     modified on the same molecules?  The optional rescaling (K11) and the window sums (K13) as in call_reads_llr; then the candidate
     sites; then, read by read, the 2 x 2 table of every pair of candidate sites on one (chrom, strand) at most max_dist apart over the
@@ -311,7 +313,13 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
     min_reads: reads with a call at both sites below which a pair gets no statistics.  fdr: None, 'bh' or 'by': p_fisher goes through
     nmod_fdr_adjust on the device at fdr_alpha and `pairs` gains q.
     Returns `pairs`, one entry per pair in key order: chrom, strand, pos_a, pos_b (0-based), dist, n11, n10, n01, n00 (the first index
-    is site a's call), log_or, se, phi, p_fisher, [q,] status (uint8, L.PAIRS_* bits).  One summary line goes to `log`."""
+    is site a's call), log_or, se, phi, p_fisher, [q,] status (uint8, L.PAIRS_* bits).  One summary line goes to `log`.
+    soft: also the soft linkage of every pair from the window sums of all the reads that cover both sites with a valid sum, not only
+      those beyond +-thr (K18, nmod_pair_rows_count / nmod_pair_rows_fill / nmod_pair_linkage, on the same stream): `pairs` gains n_cov
+      (those reads), pa, pb (the marginal modified shares), d (the linkage) with its likelihood interval d_lo, d_hi at ci_level, r,
+      pi11, pi10, pi01, pi00 (the cells of the joint law from pa, pb and d), stat, p_indep (the likelihood-ratio test of independence),
+      link_status (uint8, L.LINK_* bits) and with fdr q_indep; a second line goes to `log`.  A pair needs max(min_reads, LINK_MIN_READS)
+      such reads: below that the chi2 law of stat is liberal.  Without `soft` nothing changes."""
     import torch
     m0 = _rescale.masked_model(model, min_positions)
     m1 = _rescale.masked_model(alt_model, min_positions)
@@ -328,6 +336,9 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
             raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
     opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
     engine._pairs_opts(thr, min_reads, False, ())
+    link_min_reads = max(int(min_reads), LINK_MIN_READS)
+    if soft:
+        engine._link_opts(link_min_reads, ci_level, 60, 1e-12)
     max_dist = engine._check_max_dist(max_dist)
     if fdr is not None:
         engine._fdr_method(fdr)
@@ -361,10 +372,17 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
     else:
         d_key = t(host_key)
     poff, npairs = det.pair_index(d_key, max_dist)
-    res = det.site_pairs(t(cs), t(start), d_off, llr_win, d_key, poff, npairs, thr=thr, min_reads=min_reads)
+    d_cs, d_start = t(cs), t(start)
+    res = det.site_pairs(d_cs, d_start, d_off, llr_win, d_key, poff, npairs, thr=thr, min_reads=min_reads)
     q = None
     if fdr is not None:
         (q,), _ = det.fdr(res, tracks=('p_fisher',), method=fdr, alpha=fdr_alpha)
+    link = q_indep = None
+    if soft:
+        rows = det.pair_rows(d_cs, d_start, d_off, llr_win, d_key, poff, npairs)
+        link = det.pair_linkage(rows['sa'], rows['sb'], rows['prow_off'], min_reads=link_min_reads, ci_level=ci_level)
+        if fdr is not None:
+            (q_indep,), _ = det.fdr(link, tracks=('p_indep',), method=fdr, alpha=fdr_alpha)
     key = d_key.cpu().numpy()
     first, second = res['first'].cpu().numpy().astype(np.int64), res['second'].cpu().numpy().astype(np.int64)
     counts = res['counts'].cpu().numpy().reshape(-1, 4)
@@ -381,6 +399,18 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
     log('readpairs: %d read(s); %d candidate site(s)%s, %d pair(s) at most %d apart, %d with at least %d read(s) called at both sites%s'
         % (nreads, len(key), ' with q <= %g of the modified share' % site_alpha if by_stoich else '', npairs, max_dist, int(tested.sum()),
            int(min_reads), '' if q is None else '; %d with q <= %g (%s)' % (int((pairs['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
+    if link is not None:
+        lk = {f: link[f].cpu().numpy() for f in L.LINK_FIELDS + ('n_valid', 'status')}
+        pairs.update(n_cov=lk['n_valid'], **{f: lk[f] for f in ('pa', 'pb', 'd', 'd_lo', 'd_hi', 'r')})
+        pa, pb, d = lk['pa'], lk['pb'], lk['d']
+        pairs.update(pi11=pa * pb + d, pi10=pa * (1.0 - pb) - d, pi01=(1.0 - pa) * pb - d, pi00=(1.0 - pa) * (1.0 - pb) + d,
+                     stat=lk['stat'], p_indep=lk['p_indep'], link_status=lk['status'])
+        if q_indep is not None:
+            pairs['q_indep'] = q_indep.cpu().numpy()
+        fitted = (lk['status'] & L.LINK_NO_ESTIMATE) == 0
+        log('readpairs: soft linkage of %d pair(s) with at least %d read(s) valid at both sites%s'
+            % (int(fitted.sum()), link_min_reads,
+               '' if q_indep is None else '; %d with q_indep <= %g (%s)' % (int((pairs['q_indep'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
     return pairs
 
 
@@ -394,5 +424,19 @@ def write_site_pairs(path, pairs):
            [np.asarray(pairs[f]).tolist() for f in ('dist', 'n11', 'n10', 'n01', 'n00', 'log_or', 'se', 'phi')] + \
            [sci(pairs['p_fisher'])] + ([sci(pairs['q'])] if 'q' in pairs else []) + [np.asarray(pairs['status']).tolist()]
     fmt = '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %s ' + ('%s ' if 'q' in pairs else '') + '%d\n'
+    with open(path, 'w') as f:
+        f.writelines(fmt % row for row in zip(*cols))
+
+
+def write_site_linkage(path, pairs):
+    """<FileID>_site_linkage.txt: per pair 'chrom strand pos_a+1 pos_b+1 dist n_cov pa pb d d_lo d_hi r pi11 pi10 pi01 pi00 stat p_indep
+    [q_indep] link_status' as '%s %s %d %d %d %d' + ten '%.6f' + '%.3f %.3E [%.3E] %d' (the positions 1-based; 'nan' as Python spells it
+    where the pair has no estimate; `pairs` of cooccur_reads_llr(..., soft=True))"""
+    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
+    cols = [np.asarray(pairs['chrom']).astype(str).tolist(), np.asarray(pairs['strand']).astype(str).tolist(),
+            (np.asarray(pairs['pos_a'], dtype=np.int64) + 1).tolist(), (np.asarray(pairs['pos_b'], dtype=np.int64) + 1).tolist()] + \
+           [np.asarray(pairs[f]).tolist() for f in ('dist', 'n_cov', 'pa', 'pb', 'd', 'd_lo', 'd_hi', 'r', 'pi11', 'pi10', 'pi01', 'pi00', 'stat')] + \
+           [sci(pairs['p_indep'])] + ([sci(pairs['q_indep'])] if 'q_indep' in pairs else []) + [np.asarray(pairs['link_status']).tolist()]
+    fmt = '%s %s %d %d %d %d' + ' %.6f' * 10 + ' %.3f %s ' + ('%s ' if 'q_indep' in pairs else '') + '%d\n'
     with open(path, 'w') as f:
         f.writelines(fmt % row for row in zip(*cols))
