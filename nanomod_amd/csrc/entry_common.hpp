@@ -6,6 +6,7 @@
 #include <atomic>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 
@@ -14,7 +15,11 @@
 
 namespace nmod {
 
-extern thread_local hipError_t g_last_hip;       // nanomod_hip.hip; only feeds nmod_strerror's text
+// errors.hip; they only feed nmod_strerror's text: the last HIP error of the thread (NMOD_HIP below sets it), the last RCCL
+// error and the library's words for it (comm.hip sets them)
+extern thread_local hipError_t g_last_hip;
+extern thread_local int g_last_rccl;
+extern thread_local const char* g_last_rccl_text;
 
 // return NMOD_ERR_HIP from the calling entry when a hipError_t-valued expression fails, remembering which error it was
 #define NMOD_HIP(call)                                   \
@@ -26,6 +31,15 @@ extern thread_local hipError_t g_last_hip;       // nanomod_hip.hip; only feeds 
 constexpr int kMaxDevices = 64;
 
 inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+// a positive integer from the environment (the host-resident entry's and the down-sampling branch's sizes), else dflt
+inline int64_t env_i64(const char* name, int64_t dflt) {
+  const char* s = getenv(name);
+  if (!s || !*s) return dflt;
+  char* e = nullptr;
+  const long long v = strtoll(s, &e, 10);
+  return (e && *e == '\0' && v > 0) ? (int64_t)v : dflt;
+}
 
 // bytes of a sample; 0: not a dtype
 inline size_t elem_bytes(int32_t dtype) {

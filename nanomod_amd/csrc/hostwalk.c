@@ -23,7 +23,7 @@
 #include <math.h>
 
 /* x == k / 1000.0 with |k| <= 32 767?  Division-free: q = fl(k / 1000) by one Newton step on k * fl(1 / 1000), correctly rounded
- * for every such k (the same test as csrc/host_pipeline.hpp's narrow_f64_to_i16; tests/test_abi_and_host.py checks both exhaustively) */
+ * for every such k (the same test as csrc/host_pipeline.hip's narrow_f64_to_i16; tests/test_abi_and_host.py checks both exhaustively) */
 static inline int narrow_one(double x, short* out) {
   if (!(fabs(x) <= 33.0)) return 0;
   const double k = nearbyint(x * 1000.0);

@@ -1,6 +1,7 @@
-// C-ABI implementation (include/nanomod_hip.h): argument checking, workspace
-// carving, size-class binning, kernel launches on the caller's stream, the
-// host-memory staging mode, the HIP-event timer and the wave-primitive self test.
+// The detect unit of the C ABI (include/nanomod_hip.h): argument checking, workspace carving, size-class binning, the float64
+// front end and the K1 / K2 / K3 launches of one device-resident batch on the caller's stream — nmod_detect_batch,
+// nmod_combine_track, nmod_describe_dispatch, nmod_last_dispatch_stats and the small entries that describe the build.
+// What the other units call is declared in detect_internal.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -9,16 +10,12 @@
 #include <vector>
 #include <string>
 #include <stdio.h>
-#include <atomic>
-#include <mutex>
-#include <thread>
-#include <chrono>
-#include <functional>
-#include <condition_variable>
-#include <dlfcn.h>
 
 #include "../../include/nanomod_hip.h"
 #include "entry_common.hpp"
+#include "detect_internal.hpp"
+#include "evtimer.hpp"
+#include "host_pipeline.hpp"
 #include "rank_stats.hpp"
 #include "rank_stats_launch.hpp"
 #include "item_claim.hpp"
@@ -29,34 +26,6 @@
 #include "scratch_pool.hpp"
 
 namespace nmod {
-
-thread_local hipError_t g_last_hip = hipSuccess;   // only feeds nmod_strerror's text; NMOD_HIP (entry_common.hpp) sets it
-thread_local char g_errbuf[256];
-
-// ---------------------------------------------------------------- event timer
-struct EvTimer {
-  int capacity;
-  std::vector<hipEvent_t> start[NMOD_KERNEL_COUNT], stop[NMOD_KERNEL_COUNT];
-  int used[NMOD_KERNEL_COUNT];
-};
-
-// A slot counts only when BOTH of its events were recorded: a failed hipEventRecord drops the sample (and is
-// remembered in g_last_hip) instead of leaving an event pair that nmod_evtimer_read would fail on.
-struct ScopedKernelTimer {
-  EvTimer* t; int k; hipStream_t s; int slot;
-  ScopedKernelTimer(void* timer, int kernel, hipStream_t stream) : t((EvTimer*)timer), k(kernel), s(stream), slot(-1) {
-    if (t && t->used[k] < t->capacity) {
-      const hipError_t e = hipEventRecord(t->start[k][t->used[k]], s);
-      if (e == hipSuccess) slot = t->used[k]; else g_last_hip = e;
-    }
-  }
-  ~ScopedKernelTimer() {
-    if (slot >= 0) {
-      const hipError_t e = hipEventRecord(t->stop[k][slot], s);
-      if (e == hipSuccess) t->used[k] = slot + 1; else g_last_hip = e;
-    }
-  }
-};
 
 // ---------------------------------------------------------------- workspace
 struct Workspace {
@@ -70,7 +39,7 @@ struct Workspace {
 // raw counters of dispatch_stats_kernel: [0] the 256-capacity counting form's gate, [1] positions it produced, [2] float64 redo,
 // [kStatsClass + c] positions of launch class c, [kStatsGate + c] the any-coverage counting form's gate of class c (summed over the
 // chunks of a host-resident batch), [kStatsLeft + c] positions it left to the class's sorting form
-constexpr int kStatsClass = 8, kStatsGate = 64, kStatsLeft = 128, kStatsTried = 192, kStatsWords = 256;
+constexpr int kStatsClass = 8, kStatsGate = 64, kStatsLeft = 128, kStatsTried = 192;   // (kStatsWords = 256: detect_internal.hpp)
 constexpr int kMetaInts = 320;
 constexpr int kMetaMax = 3 * kClassStride;      // [168..169] max n0 / n1
 constexpr int kMetaBigTotal = kMetaMax + 2;     // [170..171] u64: scratch floats the large positions need
@@ -324,17 +293,7 @@ __global__ __launch_bounds__(256) void f64_redo_list_kernel(F64Args a) {
 }
 
 
-// ---------------------------------------------------------------- dispatch statistics (nmod_last_dispatch_stats)
-// Which K1 form took how many positions of a batch is decided on the device (class lists, the probes' gates, the counting forms'
-// per-position flags) and never leaves it on the hot path.  detect_device returns where those facts sit in the caller's
-// workspace (StatsArgs); dispatch_stats_kernel reduces them to kStatsWords counters when somebody asks (device-resident batches: on request,
-// nothing is launched otherwise; host-resident batches: once per chunk into a per-call accumulator, the path is PCIe-bound).
-struct StatsArgs {
-  int64_t npos; int32_t uniform_cls;             // >= 0: one class holds all npos positions (no class lists were built)
-  const int32_t* meta; const int32_t* work_meta; const int32_t* gates; const uint8_t* cnt_done;
-  int32_t cnt256_ran, cw_ran, f64;
-  unsigned long long* acc;
-};
+// ---------------------------------------------------------------- dispatch statistics (nmod_last_dispatch_stats; StatsArgs: detect_internal.hpp)
 __global__ __launch_bounds__(256) void dispatch_stats_kernel(StatsArgs a) {
   const int c256 = kNumGeneralClasses + 2;
   auto count_of = [&](int c) -> int64_t { return a.uniform_cls >= 0 ? (c == a.uniform_cls ? a.npos : 0) : (int64_t)a.meta[c]; };
@@ -368,14 +327,14 @@ struct DispatchRec {
   int64_t npos = 0;
 };
 thread_local DispatchRec g_dispatch;
-static hipError_t enqueue_dispatch_stats(const StatsArgs& a, hipStream_t stream) {
+hipError_t enqueue_dispatch_stats(const StatsArgs& a, hipStream_t stream) {
   const unsigned blocks = a.cnt256_ran ? (unsigned)std::max<int64_t>(1, std::min<int64_t>((a.npos + 255) / 256, 512)) : 1u;
   hipLaunchKernelGGL(dispatch_stats_kernel, dim3(blocks), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- helpers
-static int check_params(const nmod_params* prm) {
+int check_params(const nmod_params* prm) {
   if (!prm || prm->struct_size != (int32_t)sizeof(nmod_params)) return NMOD_ERR_INVALID_ARG;
   if (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI && prm->dtype != NMOD_DTYPE_F64) return NMOD_ERR_INVALID_ARG;
   if (prm->memspace != NMOD_MEM_HOST && prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
@@ -400,8 +359,8 @@ static int fill_combine_args(const nmod_params* prm, CombineArgs& ca) {
   return NMOD_OK;
 }
 
-static int launch_combine(const nmod_params* prm, hipStream_t stream, int64_t npos, const double* ks_d,
-                          const double* ks_p, const int32_t* run_id, double* comb_st, double* comb_p) {
+int launch_combine(const nmod_params* prm, hipStream_t stream, int64_t npos, const double* ks_d,
+                   const double* ks_p, const int32_t* run_id, double* comb_st, double* comb_p) {
   CombineArgs ca;
   memset(&ca, 0, sizeof(ca));
   int rc = fill_combine_args(prm, ca);
@@ -414,139 +373,6 @@ static int launch_combine(const nmod_params* prm, hipStream_t stream, int64_t np
   NMOD_HIP(hipGetLastError());
   return NMOD_OK;
 }
-
-// Scratch slab of the large-position pass: stream-ordered allocation from a memory pool the LIBRARY owns (one per
-// device, created on first use).  Freed slabs stay in that pool (release threshold = max: with the default
-// threshold every batch would return its slab to the OS at the next synchronisation and map it again — measured
-// 20 ms per 1.3 GB); the device's default pool, which the caller's own hipMallocAsync traffic uses, is never
-// touched.  nmod_trim_scratch() returns the cached slabs to the driver.
-static std::mutex g_pool_mutex;
-static hipMemPool_t g_pool[kMaxDevices] = {nullptr};        // guarded by g_pool_mutex
-
-hipMemPool_t scratch_pool(int dev) {            // (declared in scratch_pool.hpp: read_pivot.hip takes its scratch here too)
-  if (dev < 0 || dev >= kMaxDevices) return nullptr;
-  std::lock_guard<std::mutex> lock(g_pool_mutex);
-  if (!g_pool[dev]) {
-    hipMemPoolProps props;
-    memset(&props, 0, sizeof(props));
-    props.allocType = hipMemAllocationTypePinned;
-    props.handleTypes = hipMemHandleTypeNone;
-    props.location.type = hipMemLocationTypeDevice;
-    props.location.id = dev;
-    hipMemPool_t pool = nullptr;
-    if (hipMemPoolCreate(&pool, &props) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    uint64_t keep = UINT64_MAX;
-    (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-    g_pool[dev] = pool;
-  }
-  return g_pool[dev];
-}
-
-// The slabs parked per stream (scratch_pool.hpp says why).  One small table under one mutex; no HIP call that can wait is made
-// while it is held.
-namespace {
-struct ParkedBlock { void* p = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
-struct ParkedStream { bool live = false; int dev = 0; hipStream_t s = nullptr; uint64_t used = 0; ParkedBlock b[kParkSlots]; };
-std::mutex g_park_mutex;
-ParkedStream g_park[kParkStreams];                            // guarded by g_park_mutex
-uint64_t g_park_clock = 0;
-
-ParkedStream* parked_find(int dev, hipStream_t s) {
-  for (ParkedStream& e : g_park) if (e.live && e.dev == dev && e.s == s) return &e;
-  return nullptr;
-}
-bool parked_idle(const ParkedStream& e) {
-  for (const ParkedBlock& b : e.b) if (b.p && hipEventQuery(b.done) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return true;
-}
-}  // namespace
-
-void* parked_take(int dev, hipStream_t s, size_t need, size_t* bytes) {
-  std::lock_guard<std::mutex> lock(g_park_mutex);
-  ParkedStream* e = parked_find(dev, s);
-  if (!e) return nullptr;
-  ParkedBlock* best = nullptr;
-  for (ParkedBlock& b : e->b) if (b.p && b.bytes >= need && (!best || b.bytes < best->bytes)) best = &b;
-  if (!best) return nullptr;
-  e->used = ++g_park_clock;
-  void* p = best->p;
-  *bytes = best->bytes;
-  best->p = nullptr;                                          // (the slot keeps its event for the next slab)
-  return p;
-}
-
-hipError_t parked_put(int dev, hipStream_t s, void* p, size_t bytes) {
-  void* to_free[kParkSlots + 1]; int nfree = 0;               // freed on s after the table is released: all of them are idle or were last used on s
-  {
-    std::lock_guard<std::mutex> lock(g_park_mutex);
-    ParkedStream* e = parked_find(dev, s);
-    if (!e) {
-      ParkedStream* lru = nullptr;
-      for (ParkedStream& c : g_park) {
-        if (!c.live) { e = &c; break; }
-        if ((!lru || c.used < lru->used) && parked_idle(c)) lru = &c;
-      }
-      if (!e && lru) {
-        for (ParkedBlock& b : lru->b) if (b.p) { to_free[nfree++] = b.p; b.p = nullptr; }
-        e = lru;
-      }
-      if (e) { e->live = true; e->dev = dev; e->s = s; }
-    }
-    if (!e) to_free[nfree++] = p;                             // every stream of the table is busy
-    else {
-      e->used = ++g_park_clock;
-      ParkedBlock* slot = nullptr;
-      for (ParkedBlock& b : e->b) if (!b.p) { slot = &b; break; }
-      if (!slot) for (ParkedBlock& b : e->b) if (b.bytes < bytes && (!slot || b.bytes < slot->bytes)) slot = &b;
-      if (slot && !slot->done && hipEventCreateWithFlags(&slot->done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); slot->done = nullptr; slot = nullptr; }
-      if (slot && hipEventRecord(slot->done, s) == hipSuccess) {
-        if (slot->p) to_free[nfree++] = slot->p;              // the smallest gives way
-        slot->p = p; slot->bytes = bytes;
-      } else {
-        (void)hipGetLastError();
-        to_free[nfree++] = p;
-      }
-    }
-  }
-  hipError_t err = hipSuccess;
-  for (int i = 0; i < nfree; ++i) { const hipError_t e = hipFreeAsync(to_free[i], s); if (e != hipSuccess) err = e; }
-  return err;
-}
-
-hipError_t parked_trim(int dev, size_t* freed_bytes, size_t* free_before) {
-  *freed_bytes = 0; *free_before = 0;
-  void* blocks[kParkStreams * kParkSlots]; hipStream_t on[kParkStreams * kParkSlots]; int n = 0;
-  {
-    std::lock_guard<std::mutex> lock(g_park_mutex);
-    for (ParkedStream& e : g_park) {
-      if (!e.live || e.dev != dev) continue;
-      for (ParkedBlock& b : e.b) {
-        if (b.p) { on[n] = e.s; blocks[n++] = b.p; *freed_bytes += b.bytes; }
-        if (b.done) (void)hipEventDestroy(b.done);
-        b = ParkedBlock();
-      }
-      e.live = false;
-    }
-  }
-  if (!n) return hipSuccess;
-  int cur = 0;
-  hipError_t err = hipGetDevice(&cur);
-  if (err == hipSuccess) err = hipSetDevice(dev);
-  if (err == hipSuccess) err = hipDeviceSynchronize();        // whatever was queued behind a parked slab has run
-  { size_t total = 0; if (err == hipSuccess && hipMemGetInfo(free_before, &total) != hipSuccess) { (void)hipGetLastError(); *free_before = 0; *freed_bytes = 0; } }
-  // Each slab is freed on the stream it was parked under, as a call used to free it, and the device is synchronised: measured, only
-  // then does hipMemPoolTrimTo hand the block back (freed with hipFree, or on the null stream, it stayed in the pool).  A stream that
-  // has been destroyed since is refused by the runtime: that slab goes back with hipFree.
-  for (int i = 0; i < n; ++i) {
-    hipError_t e = hipFreeAsync(blocks[i], on[i]);
-    if (e != hipSuccess) { (void)hipGetLastError(); e = hipFree(blocks[i]); }
-    if (e != hipSuccess && err == hipSuccess) err = e;
-  }
-  { const hipError_t e = hipDeviceSynchronize(); if (err == hipSuccess) err = e; }
-  (void)hipSetDevice(cur);
-  return err;
-}
-
 
 // ---------------------------------------------------------------- the deep form (NMOD_FLAG_DEEP, deep_rank.hpp)
 // Enqueues K1 of the ndeep positions of class kDeepClass (`tiles` tiles in all, from the classifier) on `stream`: the tile
@@ -923,9 +749,9 @@ static int enqueue_outputs(Batch& b) {
 }
 
 // One batch in device memory on prm->stream.  stats (may be null): where the facts of nmod_last_dispatch_stats sit in `workspace`.
-static int detect_device(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
-                         const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
-                         int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const F64Src* f64 = nullptr) {
+int detect_device(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
+                  const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
+                  int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const F64Src* f64) {
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1 || !out) return NMOD_ERR_INVALID_ARG;
   if ((prm->stride0 <= 0 && !off0) || (prm->stride1 <= 0 && !off1)) return NMOD_ERR_INVALID_ARG;
@@ -968,11 +794,11 @@ struct DevBuf {
 
 // ---------------------------------------------------------------- float64 front end
 // Gives every position order-preserving float32 keys (f64_encode_kernel) and runs the batch on them; see F64Args.
-// Device memory only (the host entry hands its chunks over as device memory, host_pipeline.hpp).  bounds: the first and
+// Device memory only (the host entry hands its chunks over as device memory, host_pipeline.hip).  bounds: the first and
 // one-past-last element of each array in use, {b0, e0, b1, e1}, when the caller knows them (no round trip for the offsets).
-static int detect_f64(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
-                      const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
-                      int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const int64_t* bounds = nullptr) {
+int detect_f64(const nmod_params* prm, int64_t npos, const void* sig0, const int64_t* off0,
+               const void* sig1, const int64_t* off1, const int32_t* run_id, void* workspace,
+               int64_t workspace_bytes, nmod_out* out, StatsArgs* stats, const int64_t* bounds) {
   if (npos == 0) return NMOD_OK;
   if (!sig0 || !sig1 || !out) return NMOD_ERR_INVALID_ARG;
   if ((prm->stride0 <= 0 && !off0) || (prm->stride1 <= 0 && !off1)) return NMOD_ERR_INVALID_ARG;
@@ -1017,180 +843,10 @@ static int detect_f64(const nmod_params* prm, int64_t npos, const void* sig0, co
   return rc;
 }
 
-#include "host_pipeline.hpp"
-
-
-// ---------------------------------------------------------------- down-sampling branch (myDetect.py:345-361)
-// Virtual rows: row v = (flagged position k, iteration it) of group g holds rsz[k] samples — drawn WITH replacement from the
-// position's rn[k] samples when rn[k] > rsz[k] (np.random.choice semantics), the samples themselves otherwise.  The draws are a
-// counter-based function of (seed, k, it, g, j): reproducible, any launch shape.
-struct ResampleArgs {
-  const char* rows; int esz; const int64_t* roff; const int32_t* rn; const int32_t* rsz; const int64_t* vbase;
-  int64_t nrows; int32_t iters; uint64_t seed; int32_t group; int64_t k0;      // k0: index of the chunk's first position among all flagged ones
-  char* out; int64_t* voff;                                                     // voff[nrows * iters + 1]: offsets of the virtual rows
-};
-__device__ __forceinline__ uint64_t draw_mix(uint64_t seed, int64_t k, int32_t it, int32_t g, uint32_t j) {
-  uint64_t x = seed + 0x9E3779B97F4A7C15ull * (uint64_t)((k * 2 + g) * 1000003ll + it);
-  x ^= (uint64_t)j * 0xD1B54A32D192ED03ull;
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nv = a.nrows * a.iters;
-  for (int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); v < nv; v += (int64_t)gridDim.x * 4) {
-    const int64_t k = v / a.iters;
-    const int32_t it = (int32_t)(v - k * a.iters);
-    const int n = a.rn[k], sz = a.rsz[k];
-    const int64_t vo = a.vbase[k] + (int64_t)it * sz;
-    if (lane == 0) { a.voff[v] = vo; if (v == nv - 1) a.voff[nv] = vo + sz; }
-    const char* src = a.rows + a.roff[k] * a.esz;
-    char* dst = a.out + vo * a.esz;
-    const bool draw = n > sz;
-    for (int j = lane; j < sz; j += 64) {
-      int64_t idx = j;
-      if (draw) idx = (int64_t)__umul64hi(draw_mix(a.seed, a.k0 + k, it, a.group, (uint32_t)j), (uint64_t)n);   // floor(u n / 2^64): uniform on [0, n)
-      if (a.esz == 4) reinterpret_cast<uint32_t*>(dst)[j] = reinterpret_cast<const uint32_t*>(src)[idx];
-      else if (a.esz == 2) reinterpret_cast<uint16_t*>(dst)[j] = reinterpret_cast<const uint16_t*>(src)[idx];
-      else reinterpret_cast<uint64_t*>(dst)[j] = reinterpret_cast<const uint64_t*>(src)[idx];
-    }
-  }
-}
-// the pair at index `kth` of the p-sorted iterations of every position (np.argsort(p_array)[kth]; ties in p by iteration number)
-__global__ __launch_bounds__(256) void select_quantile_kernel(int64_t nrows, int32_t iters, int32_t kth, const double* d, const double* p,
-                                                              double* out_d, double* out_p) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < nrows; k += (int64_t)gridDim.x * 4) {
-    const double* pk = p + k * iters;
-    for (int e = lane; e < iters; e += 64) {
-      const double pe = pk[e];
-      int rank = 0;
-      for (int j = 0; j < iters; ++j) { const double pj = pk[j]; rank += (pj < pe || (pj == pe && j < e) || (pe != pe && pj == pj)) ? 1 : 0; }   // (NaN last)
-      if (rank == kth) { out_p[k] = pe; out_d[k] = d[k * iters + e]; }
-    }
-  }
-}
-
-// ---------------------------------------------------------------- self test kernels
-__global__ void selftest_perm_kernel(int* out) {
-  int lane = threadIdx.x & 63;
-  float x = (float)lane;
-  int k = 0;
-  out[64 * k++ + lane] = (int)lane_xor<1>(x);
-  out[64 * k++ + lane] = (int)lane_xor<2>(x);
-  out[64 * k++ + lane] = (int)lane_xor<4>(x);
-  out[64 * k++ + lane] = (int)lane_xor<8>(x);
-  out[64 * k++ + lane] = (int)lane_xor<16>(x);
-  out[64 * k++ + lane] = (int)lane_mirror<2>(x, lane);
-  out[64 * k++ + lane] = (int)lane_mirror<4>(x, lane);
-  out[64 * k++ + lane] = (int)lane_mirror<8>(x, lane);
-  out[64 * k++ + lane] = (int)lane_mirror<16>(x, lane);
-  out[64 * k++ + lane] = (int)lane_mirror<32>(x, lane);
-  out[64 * k++ + lane] = (int)lane_mirror<64>(x, lane);
-  out[64 * k++ + lane] = (int)lane_prev(x, -1.0f);
-  out[64 * k++ + lane] = (int)lane_next(x, -1.0f);
-  out[64 * k++ + lane] = wave_scan_max_i32((lane * 37) % 64 == 5 ? 1000 : (lane * 7) % 23);
-  out[64 * k++ + lane] = (int)wave_max_u32((unsigned)((lane * 29) % 61));
-  out[64 * k++ + lane] = (int)wave_sum_u64((unsigned long long)lane * 3ull + (1ull << 33)) ;
-  out[64 * k++ + lane] = (int)(wave_sum_u64((unsigned long long)lane * 3ull + (1ull << 33)) >> 32);
-  out[64 * k++ + lane] = (int)wave_sum_f64(0.5 * lane);
-}
-
-template <int R>
-__global__ void selftest_sort_kernel(const float* in, float* out, int* runs) {
-  int lane = threadIdx.x & 63;
-  const float inf = __builtin_inff();
-  LaneSel sel;
-#pragma unroll
-  for (int b = 0; b < 6; ++b) sel.s[b] = ((lane >> b) & 1) ? inf : -inf;
-  float x[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) x[r] = in[r * 64 + lane];
-  wave_sort<R>(x, sel, lane);
-  store_sorted<R>(out, x, lane);
-  unsigned pp;
-  seg_runs_and_ties<R, 64, 1>(runs + lane * R, x, lane, false, pp);
-}
-
-template <int R>
-static int selftest_sort(int code) {
-  const int N = 64 * R;
-  std::vector<float> h(N), sorted(N), got(N);
-  std::vector<int> runs(N);
-  uint32_t s = 12345u + R;
-  for (int i = 0; i < N; ++i) { s = s * 1664525u + 1013904223u; h[i] = (float)((int)((s >> 8) % 97) - 48) * 0.25f; }   // many ties
-  sorted = h; std::sort(sorted.begin(), sorted.end());
-  float *din, *dout; int* druns;
-  NMOD_HIP(hipMalloc(&din, N * 4)); NMOD_HIP(hipMalloc(&dout, N * 4)); NMOD_HIP(hipMalloc(&druns, N * 4));
-  NMOD_HIP(hipMemcpy(din, h.data(), N * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(selftest_sort_kernel<R>, dim3(1), dim3(64), 0, 0, din, dout, druns);
-  NMOD_HIP(hipMemcpy(got.data(), dout, N * 4, hipMemcpyDeviceToHost));
-  NMOD_HIP(hipMemcpy(runs.data(), druns, N * 4, hipMemcpyDeviceToHost));
-  hipFree(din); hipFree(dout); hipFree(druns);
-  for (int i = 0; i < N; ++i) if (got[i] != sorted[i]) return code;
-  for (int i = 0; i < N; ++i) {
-    int st = i, en = i + 1;
-    while (st > 0 && sorted[st - 1] == sorted[i]) --st;
-    while (en < N && sorted[en] == sorted[i]) ++en;
-    if (runs[i] != (st | (en << 16))) return code + 1;
-  }
-  return NMOD_OK;
-}
-
 }  // namespace nmod
 
 // =================================================================== C ABI
 using namespace nmod;
-
-namespace nmod {
-// ---------------------------------------------------------------- RCCL, bound at run time (nmod_comm_*, nmod_allgather_tracks)
-// No link-time dependency: a PyTorch process already holds torch's librccl.so (its "nccl" backend) and a second copy beside it
-// would be a second set of communicator state; a process without one takes librccl.so.1 from the loader path.
-struct IdByValue { char internal[NMOD_COMM_ID_BYTES]; };      // ncclUniqueId is passed by value
-struct RcclApi {
-  void* handle = nullptr;
-  int (*GetUniqueId)(void*) = nullptr;
-  int (*CommInitRank)(void**, int, IdByValue, int) = nullptr;
-  int (*AllGather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-};
-thread_local int g_last_rccl = 0;
-thread_local const char* g_last_rccl_text = nullptr;
-static RcclApi* rccl_api() {
-  static std::once_flag once;
-  static RcclApi api;
-  static bool ok = false;
-  std::call_once(once, [] {
-    const char* names[] = {"librccl.so", "librccl.so.1"};
-    for (const char* n : names) { api.handle = dlopen(n, RTLD_NOW | RTLD_NOLOAD); if (api.handle) break; }     // a copy the process already holds
-    if (!api.handle) for (const char* n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) { api.handle = dlopen(n, RTLD_NOW | RTLD_LOCAL); if (api.handle) break; }
-    if (!api.handle) return;
-    auto sym = [&](const char* n) { return dlsym(api.handle, n); };
-    api.GetUniqueId = (int (*)(void*))sym("ncclGetUniqueId");
-    api.CommInitRank = (int (*)(void**, int, IdByValue, int))sym("ncclCommInitRank");
-    api.AllGather = (int (*)(const void*, void*, size_t, int, void*, hipStream_t))sym("ncclAllGather");
-    api.GroupStart = (int (*)())sym("ncclGroupStart");
-    api.GroupEnd = (int (*)())sym("ncclGroupEnd");
-    api.CommDestroy = (int (*)(void*))sym("ncclCommDestroy");
-    api.GetErrorString = (const char* (*)(int))sym("ncclGetErrorString");
-    ok = api.GetUniqueId && api.CommInitRank && api.AllGather && api.GroupStart && api.GroupEnd && api.CommDestroy;
-  });
-  return ok ? &api : nullptr;
-}
-#define NMOD_RCCL(api, call)                                                                         \
-  do {                                                                                               \
-    const int r_ = (call);                                                                           \
-    if (r_ != 0) { g_last_rccl = r_; g_last_rccl_text = (api)->GetErrorString ? (api)->GetErrorString(r_) : nullptr; return NMOD_ERR_RCCL; } \
-  } while (0)
-constexpr int kNcclFloat64 = 8;                  // ncclDataType_t: ncclFloat64 / ncclDouble
-
-}  // namespace nmod
-struct nmod_comm { void* comm; int nranks, rank, device; };
 
 extern "C" {
 
@@ -1200,24 +856,6 @@ int nmod_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
-}
-
-const char* nmod_strerror(int rc) {
-  switch (rc) {
-    case NMOD_OK: return "ok";
-    case NMOD_ERR_INVALID_ARG: return "invalid argument";
-    case NMOD_ERR_HIP:
-      snprintf(g_errbuf, sizeof(g_errbuf), "HIP runtime error: %s", hipGetErrorString(g_last_hip));
-      return g_errbuf;
-    case NMOD_ERR_TOO_LARGE: return "a position has more samples in a group than NMOD_MAX_RANKED (65535; NMOD_MAX_DEEP with NMOD_FLAG_DEEP)";
-    case NMOD_ERR_WORKSPACE: return "workspace missing or smaller than nmod_workspace_bytes()";
-    case NMOD_ERR_NO_DEVICE: return "no HIP device";
-    case NMOD_ERR_NO_RCCL: return "librccl.so could not be bound (neither loaded in this process nor on the loader path)";
-    case NMOD_ERR_RCCL:
-      snprintf(g_errbuf, sizeof(g_errbuf), "RCCL error %d: %s", g_last_rccl, g_last_rccl_text ? g_last_rccl_text : "?");
-      return g_errbuf;
-    default: return "unknown error code";
-  }
 }
 
 int nmod_item_claim_plan(int64_t items, int64_t waves, int32_t flags, int64_t* plan) {
@@ -1283,69 +921,6 @@ int nmod_combine_track(const nmod_params* prm, int64_t npos, const double* ks_d,
   return NMOD_OK;
 }
 
-int nmod_synth_fill(const nmod_params* prm, uint64_t seed, int64_t pos_begin, int64_t npos, int32_t group,
-                    int32_t n_per_pos, int64_t plant_period, float plant_shift, void* sig_out) {
-  int rc = check_params(prm);
-  if (rc != NMOD_OK) return rc;
-  if (npos < 0 || n_per_pos <= 0 || !sig_out || (group != 0 && group != 1)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_DEVICE) return NMOD_ERR_INVALID_ARG;
-  if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(prm->device));
-  if (npos == 0) return NMOD_OK;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  SynthArgs sa;
-  sa.seed = seed; sa.pos_begin = pos_begin; sa.npos = npos; sa.group = group; sa.n_per_pos = n_per_pos;
-  sa.plant_period = plant_period; sa.plant_shift = plant_shift; sa.dtype = prm->dtype; sa.out = sig_out;
-  int64_t total = npos * (int64_t)n_per_pos;
-  unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-  ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_SYNTH, stream);
-  hipLaunchKernelGGL(synth_kernel, dim3(blocks), dim3(256), 0, stream, sa);
-  NMOD_HIP(hipGetLastError());
-  return NMOD_OK;
-}
-
-int nmod_synth_fill_csr(const nmod_params* prm, uint64_t seed, int64_t pos_begin, int64_t npos, int32_t group,
-                        const int64_t* off, int64_t plant_period, float plant_shift, void* sig_out) {
-  int rc = check_params(prm);
-  if (rc != NMOD_OK) return rc;
-  if (npos < 0 || !off || !sig_out || (group != 0 && group != 1)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_DEVICE || (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI)) return NMOD_ERR_INVALID_ARG;
-  if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(prm->device));
-  if (npos == 0) return NMOD_OK;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  SynthCsrArgs sa;
-  sa.seed = seed; sa.pos_begin = pos_begin; sa.npos = npos; sa.group = group; sa.dtype = prm->dtype;
-  sa.plant_period = plant_period; sa.plant_shift = plant_shift; sa.off = off; sa.out = sig_out;
-  unsigned blocks = (unsigned)std::min<int64_t>((npos + 3) / 4, 256 * 32);
-  ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_SYNTH, stream);
-  hipLaunchKernelGGL(synth_csr_kernel, dim3(blocks), dim3(256), 0, stream, sa);
-  NMOD_HIP(hipGetLastError());
-  return NMOD_OK;
-}
-
-int nmod_synth_fill_events(const nmod_params* prm, uint64_t seed, int64_t pos_begin, int64_t npos, int32_t group,
-                           int32_t n_per_pos, const int64_t* off, int64_t plant_period, int32_t plant_shift_milli,
-                           int32_t spread_milli, int32_t outlier_permille, void* sig_out) {
-  int rc = check_params(prm);
-  if (rc != NMOD_OK) return rc;
-  if (npos < 0 || !sig_out || (group != 0 && group != 1) || n_per_pos < 0 || (n_per_pos == 0 && !off)) return NMOD_ERR_INVALID_ARG;
-  if (spread_milli < 0 || spread_milli > 8000 || plant_shift_milli < -16000 || plant_shift_milli > 16000 || outlier_permille < 0 || outlier_permille > 1000) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_DEVICE || (prm->dtype != NMOD_DTYPE_F32 && prm->dtype != NMOD_DTYPE_I16_MILLI)) return NMOD_ERR_INVALID_ARG;
-  if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(prm->device));
-  if (npos == 0) return NMOD_OK;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  SynthEventArgs sa;
-  sa.seed = seed; sa.pos_begin = pos_begin; sa.npos = npos; sa.group = group; sa.n_per_pos = n_per_pos; sa.off = off;
-  sa.plant_period = plant_period; sa.plant_shift_milli = plant_shift_milli; sa.spread_milli = spread_milli; sa.dtype = prm->dtype; sa.outlier_permille = outlier_permille; sa.out = sig_out;
-  unsigned blocks = (unsigned)std::min<int64_t>((npos + 3) / 4, 256 * 32);
-  ScopedKernelTimer tm(prm->timer, NMOD_KERNEL_SYNTH, stream);
-  hipLaunchKernelGGL(synth_event_kernel, dim3(blocks), dim3(256), 0, stream, sa);
-  NMOD_HIP(hipGetLastError());
-  return NMOD_OK;
-}
-
 int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char* buf, int32_t buflen) {
   int rc = check_params(prm);
   if (rc != NMOD_OK) return rc;
@@ -1380,24 +955,6 @@ int nmod_describe_dispatch(const nmod_params* prm, int64_t n0, int64_t n1, char*
   snprintf(buf, buflen, "%s<%s%s> (event-like rows) | %s", counting[f.count], prm->dtype == NMOD_DTYPE_F64 ? "f32 keys" : dt, all ? "" : ",ks", form);
   return NMOD_OK;
 }
-
-int nmod_host_pipeline_config(int64_t chunk_bytes, int32_t slots, int32_t threads, int32_t mode) {
-  if (chunk_bytes < 0 || slots < 0 || slots > kHpMaxSlots || threads < 0 || threads > 256 || mode < 0 || mode > 2) return NMOD_ERR_INVALID_ARG;
-  g_hp_chunk_bytes.store(chunk_bytes); g_hp_slots.store(slots); g_hp_threads.store(threads); g_hp_mode.store(mode);
-  return NMOD_OK;
-}
-
-int nmod_narrow_probe(const double* v, int64_t n, int16_t* out) {
-  if (!v || !out || n < 0) return NMOD_ERR_INVALID_ARG;
-  return narrow_f64_to_i16(v, out, (size_t)n) ? 1 : 0;
-}
-
-int nmod_last_host_stats(nmod_host_stats* st) {
-  if (!st) return NMOD_ERR_INVALID_ARG;
-  *st = g_host_stats;
-  return NMOD_OK;
-}
-
 
 static void assemble_dispatch_stats(const unsigned long long* raw, int64_t npos, nmod_dispatch_stats* st) {
   memset(st, 0, sizeof(*st));
@@ -1442,429 +999,6 @@ const char* nmod_build_info(void) {
   static const std::string info = "arch=gfx950 abi=" + std::to_string(NMOD_ABI_VERSION) + " hip=" + std::to_string(HIP_VERSION_MAJOR) + "." +
                                   std::to_string(HIP_VERSION_MINOR);
   return info.c_str();
-}
-
-int nmod_downsample_ks(const nmod_params* prm, int64_t nflag, const void* sig0, const int64_t* off0, const void* sig1, const int64_t* off1,
-                       const int64_t* positions, const int64_t* cov, int32_t iters, double quantile, uint64_t seed,
-                       double* ks_d, double* ks_p) {
-  int rc = check_params(prm);
-  if (rc != NMOD_OK) return rc;
-  if (nflag < 0 || iters <= 0 || iters > 65536 || !(quantile >= 0.0 && quantile < 1.0)) return NMOD_ERR_INVALID_ARG;
-  if (prm->memspace != NMOD_MEM_HOST) return NMOD_ERR_INVALID_ARG;                 // (the caller's arrays are host memory: mtest2's batch)
-  if (nflag == 0) return NMOD_OK;
-  if (!sig0 || !sig1 || !off0 || !off1 || !positions || !cov || !ks_d || !ks_p) return NMOD_ERR_INVALID_ARG;
-  if (nmod_device_count() <= prm->device || prm->device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(prm->device));
-  hipStream_t stream = (hipStream_t)prm->stream;
-  const int esz = prm->dtype == NMOD_DTYPE_F32 ? 4 : (prm->dtype == NMOD_DTYPE_F64 ? 8 : 2);
-  const int kth = (int)((double)iters * quantile);
-  int num_cus = 0;
-  NMOD_HIP(device_cus(prm->device, &num_cus));
-  const int64_t max_elements = env_i64("NMOD_DOWNSAMPLE_ELEMENTS", (int64_t)1 << 27);
-  const int64_t group_cap = (prm->flags & NMOD_FLAG_DEEP) ? NMOD_MAX_DEEP : NMOD_MAX_RANKED;   // (NMOD_FLAG_DEEP: deep groups and resamples too)
-  std::vector<int32_t> rn[2], rsz[2];
-  std::vector<int64_t> roff[2], vbase[2];
-  std::vector<char> rows[2];
-  const void* sig[2] = {sig0, sig1};
-  const int64_t* off[2] = {off0, off1};
-  int64_t lo = 0;
-  while (lo < nflag) {
-    // ---- the chunk: as many flagged positions as fit max_elements virtual samples (at least one)
-    int64_t hi = lo, tot = 0, maxsz[2] = {1, 1};
-    for (int g = 0; g < 2; ++g) { rn[g].clear(); rsz[g].clear(); roff[g].clear(); vbase[g].clear(); rows[g].clear(); }
-    int64_t at[2] = {0, 0}, vat[2] = {0, 0};
-    while (hi < nflag) {
-      const int64_t p = positions[hi];
-      int64_t n[2], z[2];
-      for (int g = 0; g < 2; ++g) {
-        n[g] = off[g][p + 1] - off[g][p];
-        if (n[g] <= 0 || n[g] > group_cap) return n[g] > group_cap ? NMOD_ERR_TOO_LARGE : NMOD_ERR_INVALID_ARG;
-        z[g] = (cov[hi] > 0 && n[g] > cov[hi]) ? cov[hi] : n[g];
-      }
-      const int64_t add = (z[0] + z[1]) * (int64_t)iters;
-      if (hi > lo && tot + add > max_elements) break;
-      tot += add;
-      for (int g = 0; g < 2; ++g) {
-        rn[g].push_back((int32_t)n[g]); rsz[g].push_back((int32_t)z[g]); roff[g].push_back(at[g]); vbase[g].push_back(vat[g]);
-        const char* src = (const char*)sig[g] + off[g][p] * esz;
-        rows[g].insert(rows[g].end(), src, src + n[g] * esz);
-        at[g] += n[g]; vat[g] += z[g] * (int64_t)iters; maxsz[g] = std::max(maxsz[g], z[g]);
-      }
-      ++hi;
-    }
-    const int64_t nrows = hi - lo, nv = nrows * (int64_t)iters;
-    if (nv > INT32_MAX) return NMOD_ERR_INVALID_ARG;
-    // every exit below this point — an allocation or launch failing included — first waits for the stream: the asynchronous copies
-    // read the host vectors of this scope (rows / roff / vbase / rn / rsz)
-    struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } } drain{stream};
-    // ---- device buffers of the chunk (stream-ordered, from the library's pool)
-    nmod_params dp = *prm;
-    dp.memspace = NMOD_MEM_DEVICE; dp.tests = NMOD_TEST_KS; dp.method = NMOD_METHOD_KS; dp.want_mstd = 0; dp.flags = prm->flags & NMOD_FLAG_DEEP;
-    dp.stride0 = 0; dp.stride1 = 0; dp.max_n0 = (int32_t)maxsz[0]; dp.max_n1 = (int32_t)maxsz[1];
-    const int64_t wsb = nmod_workspace_bytes(&dp, nv);
-    DevScratch d_rows[2], d_meta[2], d_virt[2], d_voff[2], d_ws, d_res;
-    for (int g = 0; g < 2; ++g) {
-      const size_t mbytes = (size_t)nrows * (4 + 4 + 8 + 8);
-      NMOD_HIP(d_rows[g].alloc(rows[g].size(), stream, prm->device));
-      NMOD_HIP(d_meta[g].alloc(mbytes, stream, prm->device));
-      NMOD_HIP(d_virt[g].alloc((size_t)vat[g] * esz + 256, stream, prm->device));
-      NMOD_HIP(d_voff[g].alloc((size_t)(nv + 1) * 8, stream, prm->device));
-      char* m = (char*)d_meta[g].p;
-      NMOD_HIP(hipMemcpyAsync(d_rows[g].p, rows[g].data(), rows[g].size(), hipMemcpyHostToDevice, stream));
-      NMOD_HIP(hipMemcpyAsync(m, roff[g].data(), (size_t)nrows * 8, hipMemcpyHostToDevice, stream));
-      NMOD_HIP(hipMemcpyAsync(m + nrows * 8, vbase[g].data(), (size_t)nrows * 8, hipMemcpyHostToDevice, stream));
-      NMOD_HIP(hipMemcpyAsync(m + nrows * 16, rn[g].data(), (size_t)nrows * 4, hipMemcpyHostToDevice, stream));
-      NMOD_HIP(hipMemcpyAsync(m + nrows * 20, rsz[g].data(), (size_t)nrows * 4, hipMemcpyHostToDevice, stream));
-      ResampleArgs ra;
-      ra.rows = (const char*)d_rows[g].p; ra.esz = esz; ra.roff = (const int64_t*)m; ra.vbase = (const int64_t*)(m + nrows * 8);
-      ra.rn = (const int32_t*)(m + nrows * 16); ra.rsz = (const int32_t*)(m + nrows * 20);
-      ra.nrows = nrows; ra.iters = iters; ra.seed = seed; ra.group = g; ra.k0 = lo; ra.out = (char*)d_virt[g].p; ra.voff = (int64_t*)d_voff[g].p;
-      hipLaunchKernelGGL(resample_kernel, dim3((unsigned)std::min<int64_t>((nv + 3) / 4, (int64_t)num_cus * 32)), dim3(256), 0, stream, ra);
-      NMOD_HIP(hipGetLastError());
-    }
-    NMOD_HIP(d_ws.alloc((size_t)wsb, stream, prm->device));
-    NMOD_HIP(d_res.alloc((size_t)nv * 17 + (size_t)nrows * 16 + 64, stream, prm->device));
-    double* v_d = (double*)d_res.p; double* v_p = v_d + nv; double* o_d = v_p + nv; double* o_p = o_d + nrows;
-    nmod_out vout;
-    memset(&vout, 0, sizeof(vout));
-    vout.ks_d = v_d; vout.ks_p = v_p; vout.status = (uint8_t*)(o_p + nrows);
-    // the 100 resamples of every flagged position through the same KS kernel as everything else
-    if (prm->dtype == NMOD_DTYPE_F64) {
-      const int64_t bounds[4] = {0, vat[0], 0, vat[1]};
-      rc = detect_f64(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout, nullptr, bounds);
-    } else {
-      rc = detect_device(&dp, nv, d_virt[0].p, (const int64_t*)d_voff[0].p, d_virt[1].p, (const int64_t*)d_voff[1].p, nullptr, d_ws.p, wsb, &vout, nullptr);
-    }
-    if (rc != NMOD_OK) { hipStreamSynchronize(stream); return rc; }
-    hipLaunchKernelGGL(select_quantile_kernel, dim3((unsigned)std::min<int64_t>((nrows + 3) / 4, (int64_t)num_cus * 32)), dim3(256), 0, stream,
-                       nrows, iters, kth, v_d, v_p, o_d, o_p);
-    NMOD_HIP(hipGetLastError());
-    NMOD_HIP(hipMemcpyAsync(ks_d + lo, o_d, (size_t)nrows * 8, hipMemcpyDeviceToHost, stream));
-    NMOD_HIP(hipMemcpyAsync(ks_p + lo, o_p, (size_t)nrows * 8, hipMemcpyDeviceToHost, stream));
-    NMOD_HIP(hipStreamSynchronize(stream));          // (the host vectors are reused by the next chunk)
-    lo = hi;
-  }
-  return NMOD_OK;
-}
-
-int nmod_trim_scratch(int32_t device) {
-  if (device < 0 || device >= kMaxDevices) return NMOD_ERR_INVALID_ARG;
-  hp_trim(device);                                // the pinned ring + streams of the host-resident entry
-  size_t parked_bytes = 0, free_before = 0;
-  NMOD_HIP(parked_trim(device, &parked_bytes, &free_before));   // the slabs parked per stream go back to the pool first
-  std::lock_guard<std::mutex> lock(g_pool_mutex);
-  if (g_pool[device]) {
-    // A block freed a moment ago (a parked slab) is not always the pool's to release at the first try, even after the device has been
-    // synchronised: trim until the pool reserves no more than is in use, a bounded number of times
-    for (int tries = 0;; ++tries) {
-      NMOD_HIP(hipMemPoolTrimTo(g_pool[device], 0));
-      uint64_t reserved = 0, used = 0;
-      if (hipMemPoolGetAttribute(g_pool[device], hipMemPoolAttrReservedMemCurrent, &reserved) != hipSuccess ||
-          hipMemPoolGetAttribute(g_pool[device], hipMemPoolAttrUsedMemCurrent, &used) != hipSuccess) { (void)hipGetLastError(); break; }
-      if (reserved <= used || tries == 200) break;
-      std::this_thread::sleep_for(std::chrono::milliseconds(1));
-    }
-  }
-  // The runtime hands a block that was freed a moment ago back to the driver shortly AFTER hipMemPoolTrimTo has returned (measured:
-  // within a millisecond).  A caller that reads hipMemGetInfo next should see it: wait, for at most a tenth of a second, until the
-  // parked bytes show as free
-  if (parked_bytes) {
-    int cur = 0;
-    if (hipGetDevice(&cur) == hipSuccess && hipSetDevice(device) == hipSuccess) {
-      for (int tries = 0; tries < 100; ++tries) {
-        size_t free_now = 0, total = 0;
-        if (hipMemGetInfo(&free_now, &total) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (free_now >= free_before + parked_bytes - parked_bytes / 16) break;
-        std::this_thread::sleep_for(std::chrono::milliseconds(1));
-      }
-      (void)hipSetDevice(cur);
-    } else (void)hipGetLastError();
-  }
-  return NMOD_OK;
-}
-
-int nmod_evtimer_create(int32_t capacity_per_kernel, void** timer) {
-  if (!timer || capacity_per_kernel <= 0) return NMOD_ERR_INVALID_ARG;
-  EvTimer* t = new EvTimer();
-  t->capacity = capacity_per_kernel;
-  for (int k = 0; k < NMOD_KERNEL_COUNT; ++k) {
-    t->used[k] = 0;
-    t->start[k].assign(capacity_per_kernel, nullptr); t->stop[k].assign(capacity_per_kernel, nullptr);
-  }
-  for (int k = 0; k < NMOD_KERNEL_COUNT; ++k) {
-    for (int i = 0; i < capacity_per_kernel; ++i) {
-      hipError_t e = hipEventCreate(&t->start[k][i]);
-      if (e == hipSuccess) e = hipEventCreate(&t->stop[k][i]);
-      if (e != hipSuccess) {                       // free what was created so far
-        g_last_hip = e;
-        for (int kk = 0; kk < NMOD_KERNEL_COUNT; ++kk)
-          for (int ii = 0; ii < capacity_per_kernel; ++ii) {
-            if (t->start[kk][ii]) hipEventDestroy(t->start[kk][ii]);
-            if (t->stop[kk][ii]) hipEventDestroy(t->stop[kk][ii]);
-          }
-        delete t;
-        return NMOD_ERR_HIP;
-      }
-    }
-  }
-  *timer = t;
-  return NMOD_OK;
-}
-
-int nmod_evtimer_reset(void* timer) {
-  if (!timer) return NMOD_ERR_INVALID_ARG;
-  EvTimer* t = (EvTimer*)timer;
-  for (int k = 0; k < NMOD_KERNEL_COUNT; ++k) t->used[k] = 0;
-  return NMOD_OK;
-}
-
-int nmod_evtimer_read(void* timer, int32_t kernel, double* total_ms, int32_t* launches) {
-  if (!timer || kernel < 0 || kernel >= NMOD_KERNEL_COUNT || !total_ms || !launches) return NMOD_ERR_INVALID_ARG;
-  EvTimer* t = (EvTimer*)timer;
-  double tot = 0.0;
-  for (int i = 0; i < t->used[kernel]; ++i) {
-    float ms = 0.f;
-    NMOD_HIP(hipEventSynchronize(t->stop[kernel][i]));
-    NMOD_HIP(hipEventElapsedTime(&ms, t->start[kernel][i], t->stop[kernel][i]));
-    tot += ms;
-  }
-  *total_ms = tot; *launches = t->used[kernel];
-  return NMOD_OK;
-}
-
-int nmod_evtimer_destroy(void* timer) {
-  if (!timer) return NMOD_ERR_INVALID_ARG;
-  EvTimer* t = (EvTimer*)timer;
-  for (int k = 0; k < NMOD_KERNEL_COUNT; ++k)
-    for (int i = 0; i < t->capacity; ++i) { hipEventDestroy(t->start[k][i]); hipEventDestroy(t->stop[k][i]); }
-  delete t;
-  return NMOD_OK;
-}
-
-// ---- save_test's table (myDetect.py:532-536), buffered
-// '%.3f' and '%.3E' exactly as printf (and Python) round them — the exact binary value, half to even — without going
-// through printf for every number (350 ns each: the table writer was the largest piece of a 4.6 M-position mtest2).
-// x87 extended precision carries 64 bits: |v| * 1000 is exact in it for every double below 2^63 / 1000, so '%.3f' is
-// decided exactly; '%.3E' scales by a power of ten (relative error ~2^-62) and hands every value whose fourth
-// significant digit is within 1e-7 of a rounding boundary to snprintf.
-#if !defined(__HIP_DEVICE_COMPILE__)                      // (host code; the device pass parses it with a 64-bit long double)
-static_assert(sizeof(long double) >= 10 && __LDBL_MANT_DIG__ >= 64, "the fast formats need a 64-bit significand");
-#endif
-static inline char* put_digits(char* p, unsigned long long v) {
-  char tmp[24]; int n = 0;
-  do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-  while (n) *p++ = tmp[--n];
-  return p;
-}
-static inline char* put_3(char* p, unsigned v) { p[0] = (char)('0' + v / 100); p[1] = (char)('0' + v / 10 % 10); p[2] = (char)('0' + v % 10); return p + 3; }
-static inline char* put_f3(char* p, double v) {          // '%.3f' as Python formats it
-  if (v != v) { memcpy(p, "nan", 3); return p + 3; }
-  if (v == INFINITY) { memcpy(p, "inf", 3); return p + 3; }
-  if (v == -INFINITY) { memcpy(p, "-inf", 4); return p + 4; }
-  const double a = fabs(v);
-  if (!(a < 9.0e15)) return p + snprintf(p, 400, "%.3f", v);
-  const long double x = (long double)a * 1000.0L;         // exact: 53 + 10 bits
-  unsigned long long d = (unsigned long long)x;           // truncation
-  const long double frac = x - (long double)d;            // exact
-  if (frac > 0.5L || (frac == 0.5L && (d & 1ull))) ++d;   // half to even on the exact value
-  if (signbit(v)) *p++ = '-';
-  p = put_digits(p, d / 1000);
-  *p++ = '.';
-  return put_3(p, (unsigned)(d % 1000));
-}
-struct Pow10Table {                                       // 10^i, i = -360 .. 360, as long double
-  long double v[721];
-  Pow10Table() { for (int i = 0; i <= 720; ++i) v[i] = powl(10.0L, (long double)(i - 360)); }
-  long double operator()(int i) const { return v[i + 360]; }
-};
-static inline char* put_e3(char* p, double v) {          // '%.3E'
-  static const Pow10Table pow10;
-  if (v != v) { memcpy(p, "NAN", 3); return p + 3; }      // Python upper-cases non-finite values under %E
-  if (v == INFINITY) { memcpy(p, "INF", 3); return p + 3; }
-  if (v == -INFINITY) { memcpy(p, "-INF", 4); return p + 4; }
-  const double a = fabs(v);
-  if (a == 0.0) { if (signbit(v)) *p++ = '-'; memcpy(p, "0.000E+00", 9); return p + 9; }
-  int e2;
-  frexp(a, &e2);                                          // a = f * 2^e2, 0.5 <= f < 1
-  int k = (int)floor((e2 - 1) * 0.30102999566398120);     // floor(log10 a) or one less
-  long double x = (long double)a * pow10(3 - k);          // want 1000 <= x < 10000
-  if (x >= 10000.0L) { ++k; x = (long double)a * pow10(3 - k); }
-  else if (x < 1000.0L) { --k; x = (long double)a * pow10(3 - k); }
-  if (!(x >= 1000.0L && x < 10000.0L)) return p + snprintf(p, 64, "%.3E", v);
-  unsigned d = (unsigned)x;
-  const long double frac = x - (long double)d;
-  // (near a boundary of the fourth digit — or of the power of ten itself — the scaled value is not trusted)
-  if (fabsl(frac - 0.5L) < 1e-7L || frac < 1e-7L || frac > 1.0L - 1e-7L) return p + snprintf(p, 64, "%.3E", v);
-  if (frac > 0.5L) ++d;
-  if (d == 10000u) { d = 1000u; ++k; }
-  if (signbit(v)) *p++ = '-';
-  *p++ = (char)('0' + d / 1000); *p++ = '.';
-  p = put_3(p, d % 1000);
-  *p++ = 'E'; *p++ = k < 0 ? '-' : '+';
-  const unsigned ak = (unsigned)(k < 0 ? -k : k);
-  if (ak >= 100) { return put_3(p, ak); }
-  p[0] = (char)('0' + ak / 10); p[1] = (char)('0' + ak % 10);
-  return p + 2;
-}
-
-// test hook: the two formats on an array of values, NUL-separated (tests/test_abi_and_host.py compares with Python)
-extern "C" int nmod_format_probe(const double* v, int64_t n, int32_t sci, char* out, int64_t cap) {
-  if (!v || !out || n < 0) return NMOD_ERR_INVALID_ARG;
-  char* p = out;
-  for (int64_t i = 0; i < n; ++i) {
-    if (p - out + 420 > cap) return NMOD_ERR_INVALID_ARG;
-    p = sci ? put_e3(p, v[i]) : put_f3(p, v[i]);
-    *p++ = '\0';
-  }
-  return NMOD_OK;
-}
-
-int nmod_write_sign_test(const char* path, int64_t npos, const int32_t* chrom_id, const char* chrom_names,
-                         int32_t n_chroms, const char* strand, const int64_t* pos0, const char* base,
-                         const int32_t* n0, const int32_t* n1, const double* mwu_u, const double* mwu_p,
-                         const double* t_t, const double* t_p, const double* ks_d, const double* ks_p,
-                         const double* comb_st, const double* comb_p, int32_t with_comb) {
-  if (!path || npos < 0 || n_chroms < 0) return NMOD_ERR_INVALID_ARG;
-  if (npos > 0 && (!chrom_id || !chrom_names || !strand || !pos0 || !base || !n0 || !n1 || !mwu_u || !mwu_p || !t_t ||
-                   !t_p || !ks_d || !ks_p || (with_comb && (!comb_st || !comb_p)))) return NMOD_ERR_INVALID_ARG;
-  std::vector<const char*> names(n_chroms);
-  size_t longest = 0;
-  const char* q = chrom_names;
-  std::vector<size_t> name_len(n_chroms);
-  for (int i = 0; i < n_chroms; ++i) { names[i] = q; name_len[i] = strlen(q); longest = std::max(longest, name_len[i]); q += name_len[i] + 1; }
-  for (int64_t i = 0; i < npos; ++i) if (chrom_id[i] < 0 || chrom_id[i] >= n_chroms) return NMOD_ERR_INVALID_ARG;
-  FILE* f = fopen(path, "w");
-  if (!f) return NMOD_ERR_INVALID_ARG;
-  // lines are formatted by several host threads, a block of positions each, and written in order
-  const size_t line_cap = longest + 4096;              // '%.3f' of a value near DBL_MAX prints ~310 digits, eight of them never do
-  auto format_block = [&](int64_t lo, int64_t hi, std::vector<char>& buf) {
-    buf.clear();
-    buf.reserve((size_t)(hi - lo) * 160);
-    std::vector<char> line(line_cap);
-    for (int64_t i = lo; i < hi; ++i) {
-      char* p = line.data();
-      {                                                       // "%s %c %lld %c %d %d "
-        const char* nm = names[chrom_id[i]];
-        const size_t ln = name_len[chrom_id[i]];
-        memcpy(p, nm, ln); p += ln;
-        *p++ = ' '; *p++ = strand[i]; *p++ = ' ';
-        const long long ps = (long long)(pos0[i] + 1);
-        if (ps < 0) { *p++ = '-'; p = put_digits(p, 0ull - (unsigned long long)ps); } else p = put_digits(p, (unsigned long long)ps);
-        *p++ = ' '; *p++ = base[i]; *p++ = ' ';
-        if (n0[i] < 0) { *p++ = '-'; p = put_digits(p, (unsigned long long)(-(long long)n0[i])); } else p = put_digits(p, (unsigned long long)n0[i]);
-        *p++ = ' ';
-        if (n1[i] < 0) { *p++ = '-'; p = put_digits(p, (unsigned long long)(-(long long)n1[i])); } else p = put_digits(p, (unsigned long long)n1[i]);
-        *p++ = ' ';
-      }
-      p = put_f3(p, mwu_u[i]); *p++ = ' '; p = put_e3(p, mwu_p[i]); *p++ = ' ';
-      p = put_f3(p, t_t[i]); *p++ = ' '; p = put_e3(p, t_p[i]); *p++ = ' ';
-      p = put_f3(p, ks_d[i]); *p++ = ' '; p = put_e3(p, ks_p[i]);
-      if (with_comb) { *p++ = ' '; p = put_f3(p, comb_st[i]); *p++ = ' '; p = put_e3(p, comb_p[i]); }
-      *p++ = '\n';
-      buf.insert(buf.end(), line.data(), p);
-    }
-  };
-  const int64_t kBlock = 1 << 16;
-  unsigned hw = std::thread::hardware_concurrency();
-  const int nthreads = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), 16, (npos + kBlock - 1) / kBlock}));
-  bool ok = true;
-  std::vector<std::vector<char>> bufs(nthreads);
-  for (int64_t base_pos = 0; base_pos < npos && ok; base_pos += kBlock * nthreads) {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nthreads; ++t) {
-      const int64_t lo = base_pos + (int64_t)t * kBlock, hi = std::min(npos, lo + kBlock);
-      if (lo >= npos) { bufs[t].clear(); continue; }
-      if (nthreads == 1) format_block(lo, hi, bufs[t]);
-      else th.emplace_back(format_block, lo, hi, std::ref(bufs[t]));
-    }
-    for (auto& x : th) x.join();
-    for (int t = 0; t < nthreads && ok; ++t)
-      if (!bufs[t].empty()) ok = fwrite(bufs[t].data(), 1, bufs[t].size(), f) == bufs[t].size();
-  }
-  const bool closed = fclose(f) == 0;
-  return (ok && closed) ? NMOD_OK : NMOD_ERR_INVALID_ARG;
-}
-
-int nmod_comm_unique_id(void* id_out) {
-  if (!id_out) return NMOD_ERR_INVALID_ARG;
-  RcclApi* api = rccl_api();
-  if (!api) return NMOD_ERR_NO_RCCL;
-  NMOD_RCCL(api, api->GetUniqueId(id_out));
-  return NMOD_OK;
-}
-
-int nmod_comm_init_rank(const void* unique_id, int32_t nranks, int32_t rank, int32_t device, nmod_comm** comm_out) {
-  if (!unique_id || !comm_out || nranks < 1 || rank < 0 || rank >= nranks) return NMOD_ERR_INVALID_ARG;
-  *comm_out = nullptr;
-  if (nmod_device_count() <= device || device < 0) return NMOD_ERR_NO_DEVICE;
-  RcclApi* api = rccl_api();
-  if (!api) return NMOD_ERR_NO_RCCL;
-  NMOD_HIP(hipSetDevice(device));
-  IdByValue id;
-  memcpy(id.internal, unique_id, NMOD_COMM_ID_BYTES);
-  void* c = nullptr;
-  NMOD_RCCL(api, api->CommInitRank(&c, nranks, id, rank));
-  nmod_comm* h = new nmod_comm();
-  h->comm = c; h->nranks = nranks; h->rank = rank; h->device = device;
-  *comm_out = h;
-  return NMOD_OK;
-}
-
-int nmod_allgather_tracks(nmod_comm* comm, void* stream, int64_t block_len, int32_t ntracks, const double* const* local, double* const* full) {
-  if (!comm || !comm->comm || block_len < 0 || ntracks < 0 || ntracks > 64 || (ntracks > 0 && (!local || !full))) return NMOD_ERR_INVALID_ARG;
-  for (int t = 0; t < ntracks; ++t) if (!local[t] || !full[t]) return NMOD_ERR_INVALID_ARG;
-  if (block_len == 0 || ntracks == 0) return NMOD_OK;
-  RcclApi* api = rccl_api();
-  if (!api) return NMOD_ERR_NO_RCCL;
-  NMOD_HIP(hipSetDevice(comm->device));
-  // one group: the tracks' gathers are fused into one launch on the caller's stream; nothing is synchronised here
-  NMOD_RCCL(api, api->GroupStart());
-  int first_bad = 0;
-  for (int t = 0; t < ntracks; ++t) {
-    const int r = api->AllGather(local[t], full[t], (size_t)block_len, kNcclFloat64, comm->comm, (hipStream_t)stream);
-    if (r != 0 && first_bad == 0) first_bad = r;
-  }
-  const int rend = api->GroupEnd();
-  if (first_bad != 0 || rend != 0) { g_last_rccl = first_bad ? first_bad : rend; g_last_rccl_text = api->GetErrorString ? api->GetErrorString(g_last_rccl) : nullptr; return NMOD_ERR_RCCL; }
-  return NMOD_OK;
-}
-
-int nmod_comm_destroy(nmod_comm* comm) {
-  if (!comm) return NMOD_ERR_INVALID_ARG;
-  RcclApi* api = rccl_api();
-  int rc = NMOD_OK;
-  if (api && comm->comm) { const int r = api->CommDestroy(comm->comm); if (r != 0) { g_last_rccl = r; g_last_rccl_text = api->GetErrorString ? api->GetErrorString(r) : nullptr; rc = NMOD_ERR_RCCL; } }
-  delete comm;
-  return rc;
-}
-
-int nmod_selftest(int32_t device) {
-  if (nmod_device_count() <= device || device < 0) return NMOD_ERR_NO_DEVICE;
-  NMOD_HIP(hipSetDevice(device));
-  const int NP = 18;
-  int* d; std::vector<int> h(64 * NP);
-  NMOD_HIP(hipMalloc(&d, 64 * NP * 4));
-  hipLaunchKernelGGL(selftest_perm_kernel, dim3(1), dim3(64), 0, 0, d);
-  NMOD_HIP(hipMemcpy(h.data(), d, 64 * NP * 4, hipMemcpyDeviceToHost));
-  hipFree(d);
-  int scan_in[64], run = 0, mx = 0;
-  for (int l = 0; l < 64; ++l) { scan_in[l] = (l * 37) % 64 == 5 ? 1000 : (l * 7) % 23; mx = std::max(mx, (l * 29) % 61); }
-  unsigned long long tot = 0; double ftot = 0;
-  for (int l = 0; l < 64; ++l) { tot += (unsigned long long)l * 3ull + (1ull << 33); ftot += 0.5 * l; }
-  for (int l = 0; l < 64; ++l) {
-    run = std::max(run, scan_in[l]);
-    const int expect[NP] = {l ^ 1, l ^ 2, l ^ 4, l ^ 8, l ^ 16, l ^ 1, l ^ 3, l ^ 7, l ^ 15, l ^ 31, l ^ 63,
-                            l == 0 ? -1 : l - 1, l == 63 ? -1 : l + 1, run, mx, (int)(unsigned)tot, (int)(tot >> 32), (int)ftot};
-    for (int k = 0; k < NP; ++k) if (h[64 * k + l] != expect[k]) return 1 + k;
-  }
-  int rc;
-  if ((rc = selftest_sort<1>(100)) != NMOD_OK) return rc;
-  if ((rc = selftest_sort<2>(110)) != NMOD_OK) return rc;
-  if ((rc = selftest_sort<4>(120)) != NMOD_OK) return rc;
-  if ((rc = selftest_sort<8>(130)) != NMOD_OK) return rc;
-  if ((rc = selftest_sort<16>(140)) != NMOD_OK) return rc;
-  if ((rc = selftest_sort<32>(150)) != NMOD_OK) return rc;
-  return NMOD_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The library's per-device scratch pool (nanomod_hip.hip: scratch_pool) and the stream-ordered slab taken from it, shared by
+// The library's per-device scratch pool (scratch_pool.hip) and the stream-ordered slab taken from it, shared by
 // the translation units that need large temporary buffers (the large-position and deep passes, the read pivot).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,7 +8,7 @@ namespace nmod {
 
 hipMemPool_t scratch_pool(int dev);      // created on first use; nmod_trim_scratch returns its cached slabs to the driver
 
-// Slabs parked per stream (nanomod_hip.hip).  The entries that promise not to synchronise do not give their slab back to the pool at
+// Slabs parked per stream (scratch_pool.hip).  The entries that promise not to synchronise do not give their slab back to the pool at
 // the end of a call: hipFreeAsync of a block that the pool handed out again while its previous free was still pending on the stream
 // waits on the host for that free (measured on ROCm 7: the second of two equal calls on a busy stream returned only when the first had
 // run, whatever the pool's reuse attributes).  Such a slab is parked under its (device, stream) instead, and the next call on that

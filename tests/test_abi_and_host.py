@@ -38,7 +38,7 @@ def test_shipped_binary_has_no_experiment_switches():
     src_dir = os.path.join(ROOT, 'nanomod_amd', 'csrc')
     tested = {}
     for fn in sorted(os.listdir(src_dir)):
-        if fn.endswith(('.hpp', '.hip')):
+        if fn.endswith(('.hpp', '.hip', '.cpp')):
             text = open(os.path.join(src_dir, fn)).read().replace('\\\n', ' ')      # (continued lines as one)
             for ln in text.splitlines():
                 if re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b', ln):
@@ -93,8 +93,11 @@ def test_dispatch_stats_without_a_call_and_form_flags():
     assert L.FLAG_NO_HOST_NARROW == 16
     prm = L.make_params(flags=64)                             # (an unknown flag bit)
     assert lib.nmod_workspace_bytes(C.byref(prm), 10) > 0 and lib.nmod_detect_batch(C.byref(prm), 1, None, None, None, None, None, None, 0, None) == -1
-    src = open(os.path.join(ROOT, 'nanomod_amd', 'csrc', 'nanomod_hip.hip')).read() + open(os.path.join(ROOT, 'nanomod_amd', 'csrc', 'rank_stats_inst.hip')).read()
-    assert 'getenv("NMOD_NO_COUNT' not in src
+    csrc = os.path.join(ROOT, 'nanomod_amd', 'csrc')
+    units = [fn for fn in sorted(os.listdir(csrc)) if fn.endswith(('.hip', '.hpp', '.cpp'))]
+    assert {'nanomod_hip.hip', 'rank_stats_inst.hip', 'host_pipeline.hip', 'entry_common.hpp', 'table_writer.cpp'} <= set(units), units
+    for fn in units:
+        assert 'getenv("NMOD_NO_COUNT' not in open(os.path.join(csrc, fn)).read(), fn
 
 
 def test_cabi_collective_argument_plumbing_without_a_gpu():
@@ -124,7 +127,7 @@ def test_cabi_collective_argument_plumbing_without_a_gpu():
 
 
 def test_host_narrowing_accepts_exactly_the_int16_grid():
-    """nmod_narrow_probe (the float64 -> int16 narrowing of the host-resident entry, host_pipeline.hpp): every k / 1000.0 with
+    """nmod_narrow_probe (the float64 -> int16 narrowing of the host-resident entry, host_pipeline.hip): every k / 1000.0 with
     |k| <= 32 767 narrows to k — the division-free quotient test is exact for all 65 535 of them, through the vector loop and its
     scalar tail — and nothing else does: a neighbouring double, |k| = 32 768, NaN, infinities, huge values, half a milli-unit"""
     import nanomod_amd._lib as L
@@ -150,11 +153,18 @@ def test_host_narrowing_accepts_exactly_the_int16_grid():
 
 
 def test_makefile_rebuilds_every_unit_when_a_header_changes():
-    """every translation unit depends on $(HDRS): touching radix_sort.hpp (included by rank_order.hip only) must put
-    rank_order.o into `make -n`'s plan (round 5 left it stale)"""
+    """every translation unit depends on $(HDRS): touching radix_sort.hpp (included by the units that sort only) must put
+    every object of the Makefile's OBJS list and the four K1 instances into `make -n`'s plan (round 5 left rank_order.o
+    stale), so a unit added to the list later cannot be left out of the dependency rule"""
     csrc = os.path.join(ROOT, 'nanomod_amd', 'csrc')
     if not os.path.exists(os.path.join(csrc, 'build', 'rank_order.o')):
         pytest.skip('no objects built here')
+    mk = open(os.path.join(csrc, 'Makefile')).read().replace('\\\n', ' ')
+    m = re.search(r'^OBJS\s*=\s*\$\(addprefix \$\(OBJDIR\)/,(.*)\)\s*$', mk, re.M)
+    assert m, 'no OBJS list in the Makefile'
+    objs = m.group(1).split() + ['rank_stats_d%d_a%d.o' % (d, a) for d in (0, 1) for a in (0, 1)]
+    hips = {fn[:-4] + '.o' for fn in os.listdir(csrc) if fn.endswith('.hip') and fn != 'rank_stats_inst.hip'}
+    assert hips <= set(objs) and {'nanomod_hip.o', 'rank_order.o', 'radix_sort.o', 'table_writer.o'} <= set(objs), hips ^ set(objs)
     hdr = os.path.join(csrc, 'radix_sort.hpp')
     st = os.stat(hdr)
     try:
@@ -162,8 +172,8 @@ def test_makefile_rebuilds_every_unit_when_a_header_changes():
         plan = subprocess.check_output(['make', '-n', '-C', csrc], text=True)
     finally:
         os.utime(hdr, ns=(st.st_atime_ns, st.st_mtime_ns))
-    for obj in ('rank_order.o', 'nanomod_hip.o', 'rank_stats_d0_a0.o', 'rank_stats_d1_a1.o'):
-        assert obj in plan, obj
+    for obj in objs:
+        assert '-o build/%s' % obj in plan, obj
 
 
 def test_no_gpu_fails_loudly_not_silently():

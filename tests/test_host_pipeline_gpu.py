@@ -1,4 +1,4 @@
-"""-m gpu: the host-resident entry (NMOD_MEM_HOST, host_pipeline.hpp) — what a drop-in mtest2 takes, everything on this path
+"""-m gpu: the host-resident entry (NMOD_MEM_HOST, host_pipeline.hip) — what a drop-in mtest2 takes, everything on this path
 is host memory in the reference (myDetect.py:416-445).  The chunked, overlapped path must return what the device-resident
 path returns on the same rows, bit for bit, wherever the chunk cuts fall: inside runs, at run edges, one position per chunk;
 from pageable and from page-locked arrays; with a device footprint bounded by the chunk size."""

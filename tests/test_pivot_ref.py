@@ -106,6 +106,7 @@ def _const(text, name):
 def test_mirrored_size_steps_equal_the_sources():
     from nanomod_amd import detect
     rs, rp, ro = _src('radix_sort.hpp'), _src('read_pivot.hip'), _src('rank_order.hip')
+    rk = _src('radix_sort.hip')                    # the sort's kernels (the header keeps its constants)
     assert _const(rs, 'kRsThreads') == Z.RS_THREADS
     assert _const(rs, 'kRsItems') == Z.RS_ITEMS
     assert _const(rs, 'kRsScanChunk') == Z.RS_SCAN_CHUNK
@@ -117,8 +118,8 @@ def test_mirrored_size_steps_equal_the_sources():
     assert _const(rp, 'kDeviceEncodeAbove') == Z.DEVICE_ENCODE_ABOVE == detect.DEVICE_ENCODE_ABOVE
     assert (1 << _const(rp, 'kPosBits')) == Z.POS_LIMIT
     # the rounds of the two one-block scans are their block size
-    assert len(re.findall(r'for \(int64_t b0 = 0; b0 < nb; b0 \+= (\d+)\)', rs)) == 1
-    assert int(re.findall(r'for \(int64_t b0 = 0; b0 < nb; b0 \+= (\d+)\)', rs)[0]) == Z.RS_TOPS_ROUND
+    assert len(re.findall(r'for \(int64_t b0 = 0; b0 < nb; b0 \+= (\d+)\)', rk)) == 1
+    assert int(re.findall(r'for \(int64_t b0 = 0; b0 < nb; b0 \+= (\d+)\)', rk)[0]) == Z.RS_TOPS_ROUND
     assert [int(x) for x in re.findall(r'for \(int64_t b0 = 0; b0 < nb; b0 \+= (\d+)\)', rp)] == [Z.SCAN_TOPS_ROUND]
     # the two grid caps
     assert [int(x) for x in re.findall(r'persistent_grid\(n, per_block, (\d+)\)', rp)] == [Z.PIVOT_GRID_CAP]

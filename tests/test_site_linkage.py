@@ -178,7 +178,9 @@ def test_header_symbols_abi_and_struct_sizes():
         assert name in L._SIGNATURES and getattr(lib, name).argtypes is not None
     src = open(os.path.join(ROOT, 'nanomod_amd', 'csrc', 'site_linkage.hip')).read()
     assert '#include "stoich_rows.hpp"' in src and 'st_solve<0>' in src and 'atomic' not in src.split('#include', 1)[1]      # K14's functions; no atomics
-    assert re.search(r'site_linkage\.o: site_linkage\.hip .*\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -ffp-contract=off', open(os.path.join(ROOT, 'nanomod_amd', 'csrc', 'Makefile')).read())
+    mk = open(os.path.join(ROOT, 'nanomod_amd', 'csrc', 'Makefile')).read()      # contraction off for the unit: its target-specific flag, used by the one .hip rule
+    assert re.search(r'^\$\(OBJDIR\)/site_linkage\.o: CXXFLAGS \+= -ffp-contract=off$', mk, re.M)
+    assert re.search(r'^\$\(OBJDIR\)/%\.o: %\.hip .*\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -c', mk, re.M) and 'site_linkage.o' in re.search(r'^OBJS\s*=((?:.*\\\n)*.*)$', mk, re.M).group(1)
 
 
 def _small_case():
