@@ -1058,6 +1058,84 @@ int nmod_pair_rows_fill(const nmod_params* prm, int64_t nreads, const int32_t* c
 int nmod_pair_linkage(const nmod_params* prm, int64_t npairs, const double* sa, const double* sb, const int64_t* prow_off,
                       const nmod_link_opts* opts, const nmod_link_out* out);
 
+/* Per-read two-state hidden Markov smoothing of the window sums at the candidate sites a read covers: along each molecule the posterior
+ * of "modified" at every site given all the read's scores, hard states at a posterior threshold, the runs of modified sites, and the
+ * read's log-likelihood under the chain and under independence (K19; the reference project has no such step).  K16 and K18 keep the
+ * read but look at two sites at a time; here the whole read is one chain.  Memspaces, the NULL and struct_size rules: those of
+ * nmod_site_pairs.
+ *   Inputs.  Reads, score (K13's llr_win, float64, one per event in read direction) and the candidate-site keys (int64, cs << 40 | pos,
+ *     strictly ascending) are nmod_site_pairs' arguments, under its rules, refusals, COVERS rule and strand-aware event index.  There
+ *     are no pairs, no max_dist and no poff.
+ *   ENTRIES of a read: the candidate sites it covers whose score there is VALID (fabs(s) <= DBL_MAX, as in K14), in ascending key:
+ *     j = 0 .. m - 1 at positions x_j with scores s_j.  An invalid score is skipped: the chain runs over the valid neighbours with the
+ *     larger gap.  m = 0 is not an error.  The entries of read r are the rows hoff[r] .. hoff[r + 1] - 1 of the per-entry outputs.
+ *   Model.  opts->pi, the stationary modified share (1e-9 <= pi <= 1 - 1e-9), and opts->length, the correlation length in bases
+ *     (1e-3 <= length <= 1e9).  With q = 1 - pi (formed once on the host) and d = x_j - x_(j-1) >= 1, an exact integer as a double:
+ *         rho = exp(-(d / length)),   eps = -expm1(-(d / length)),
+ *         T_j = [[q + pi rho, pi eps], [q eps, pi + q rho]]     rows the state at j - 1, columns the state at j;
+ *     every entry is a sum of non-negative terms, nothing is formed by 1 - x.  Emissions, scaled so that the larger is 1:
+ *     e_j = (exp(-max(s_j, 0)), exp(min(s_j, 0))).  Initial law (q, pi).  Contraction is off for the whole translation unit.
+ *   Per entry.  post_j = P(state_j = 1 | all scores of the read's entries) by scaled forward-backward:
+ *     post_j = a_j1 b_j1 / (a_j0 b_j0 + a_j1 b_j1) with a the forward and b the backward vector; a posterior, not clamped: it may be 0
+ *     or 1.  site_j = the index of the site in key (int32).  state_j (uint8): 1 iff post_j >= call_post; 0 iff post_j <= 1 - call_post,
+ *     that difference formed once on the host; 2 otherwise (a NaN too).  call_post lies in (0.5, 1).  state is decided from the post
+ *     that is written: the two outputs agree bit for bit.
+ *   Per read.  n_sites = m (int32); n_mod, n_can = the entries in state 1 and 0; n_runs = the maximal runs of consecutive entries in
+ *     state 1;  ll = sum_j (log c_j + max(s_j, 0)) with c_j the forward normalisers: the chain's log-likelihood relative to "every site
+ *     canonical";  ll_indep = sum_j (log(q e_j0 + pi e_j1) + max(s_j, 0)), the same under independence: 2 (ll - ll_indep) says whether
+ *     the molecule carries domains, and the sum of ll over the reads is what length is chosen by.  status (uint8): NMOD_HMM_NO_SITE
+ *     when m = 0 (ll = ll_indep = 0, the counts 0).
+ *   Per site (int32[nsites] each, integer atomics, zeroed by the entry on the stream): site_n = the reads with an entry there,
+ *     site_mod = the entries in state 1, site_can = those in state 0.
+ *   ORDER of the operations.  A step is the matrix A_k = T_k diag(e_k) (T_0 = I) forwards, k = j; backwards the transpose of
+ *     T_j diag(e_j) for j = m - k, and I at k = 0: step k of the backward scan belongs to entry m - 1 - k.  Both passes are one scan
+ *     over steps k = 0 .. m - 1 with a row vector x: x_k = x_(k-1) A_k, from (q, pi) forwards and (1, 1) backwards; a_j = x_j forwards,
+ *     b_j = x_(m-1-j) backwards.  A product of two matrices is c_rc = l_r0 r_0c + l_r1 r_1c and a vector step y_c = x_0 m_0c + x_1 m_1c:
+ *     two multiplications and one addition each, no fused operation.  Every product is then scaled by 2^-ex, ex the exponent frexp
+ *     gives for its largest entry, and ex is added to an integer exponent: scaling adds no rounding (unless an entry turns subnormal).
+ *     A read of up to NMOD_HMM_WAVE_MAX entries is computed by T = 64 threads, a longer one by T = 256, in tiles of T * NMOD_HMM_CHUNK
+ *     steps: thread t of the tile at k0 owns steps k0 + t * NMOD_HMM_CHUNK + c, c = 0 .. NMOD_HMM_CHUNK - 1 (a step beyond m - 1 is I).
+ *     It multiplies its steps left to right into P_t.  The 64 lanes of a wave scan those products: for d = 1, 2, 4, 8, 16, 32 lane l >= d
+ *     takes P_l = P_(l-d) P_l from the old values.  The vector in front of a thread's chunk is the tile's carry, times the scanned
+ *     product of lane 63 of every wave in front of its own in ascending order, times that of the lane before it; from there it replays
+ *     its steps one vector step each.  The carry of the next tile is the vector of thread T - 1 after its chunk.
+ *     ll = (log(x_0 + x_1) + E ln 2) + S, x and E the last forward carry and its exponent, ln 2 = 0.6931471805599453, S the sum of
+ *     max(s_j, 0); S and ll_indep add a thread's entries in ascending order, then the library's wave sum, then the waves in order.
+ *     The order is fixed by (m, t) alone: an entry's and a read's bits depend on the read and the sites alone, not on the batch, the
+ *     order of the reads, the memspace or the outputs asked for.  No float atomics.
+ *   nmod_read_sites_count(prm, nreads, cs, start, roff, score, nsites, key, hoff_out, nrows_out) computes hoff[nreads + 1] (int64), the
+ *     exclusive scan of m, on prm->stream and synchronises the stream once to return *nrows_out (a host pointer), as
+ *     nmod_pair_rows_count does.  NMOD_ERR_INVALID_ARG: the shared refusals, a NULL hoff_out or nrows_out, nrows > 2^31 - 1 (hoff is
+ *     written by then).
+ *   nmod_read_hmm(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, opts, out).  Outputs (a NULL member is skipped;
+ *     requesting fewer never changes the bits of the others): post double[nrows], site int32[nrows], state uint8[nrows]; n_sites, n_mod,
+ *     n_can, n_runs int32[nreads]; ll, ll_indep double[nreads]; status uint8[nreads]; site_n, site_mod, site_can int32[nsites].  When
+ *     none of post, state, n_mod, n_can, n_runs and the site counts is asked for, the backward pass is not run.
+ *     Reads struct_size, device, stream, memspace of prm.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and
+ *     no synchronisation; hoff is not checked: a row outside its read's hoff range or outside [0, nrows) is skipped.  NMOD_MEM_HOST:
+ *     one staged copy.  nreads == 0 or nrows == 0: NMOD_OK with zeroed site counts (with reads, each gets NMOD_HMM_NO_SITE).
+ *     NMOD_ERR_INVALID_ARG before any device work: the shared refusals of nmod_site_pairs (nreads, nsites, NULL inputs, host offsets
+ *     that decrease, host keys that do not strictly ascend); pi, length or call_post outside its range or not finite; opts or out NULL
+ *     or of another struct_size; nrows outside 0 .. 2^31 - 1 or positive without reads or sites; a NULL hoff; host hoff that does not
+ *     start at 0, ascend and end at nrows.
+ *   Scratch: 32 B per row (position, score, forward vector), 36 B where site is not asked for.
+ * Stops at: two states; one (pi, length) for all sites and reads, no per-site prior; posterior decoding only, no Viterbi path; no
+ * Baum-Welch: length is chosen on a grid by the caller and pi is given; the reads are independent and both k-mer tables are taken as
+ * right; one (chrom, strand) per read. */
+#define NMOD_HMM_CHUNK 4                   /* steps of a tile a thread owns */
+#define NMOD_HMM_WAVE_MAX 1024             /* entries of a read up to which one wave computes it (a workgroup of four beyond) */
+enum { NMOD_HMM_NO_SITE = 1 };
+typedef struct nmod_hmm_opts { int32_t struct_size, reserved; double pi, length, call_post; } nmod_hmm_opts;
+typedef struct nmod_hmm_out { int32_t struct_size; int32_t reserved;
+  double* post; int32_t* site; uint8_t* state; int32_t *n_sites, *n_mod, *n_can, *n_runs; double *ll, *ll_indep; uint8_t* status;
+  int32_t *site_n, *site_mod, *site_can;
+} nmod_hmm_out;
+int nmod_read_sites_count(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                          const double* score, int64_t nsites, const int64_t* key, int64_t* hoff_out, int64_t* nrows_out /* host */);
+int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                  const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                  const nmod_hmm_opts* opts, const nmod_hmm_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

@@ -340,6 +340,31 @@ def make_link_opts(max_iter=60, min_reads=20, tol=1e-12, ci_drop=STOICH_CI_DROP_
 make_link_out = functools.partial(make_out, NmodLinkOut)
 
 
+HMM_CHUNK, HMM_WAVE_MAX = 4, 1024         # nmod_read_hmm: steps of a tile a thread owns; entries of a read up to which one wave computes it
+HMM_NO_SITE = 1
+HMM_ENTRY_FIELDS = ('post', 'site', 'state')
+HMM_READ_FIELDS = ('n_sites', 'n_mod', 'n_can', 'n_runs', 'll', 'll_indep', 'status')
+HMM_SITE_FIELDS = ('site_n', 'site_mod', 'site_can')
+
+
+class NmodHmmOpts(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('pi', C.c_double), ('length', C.c_double), ('call_post', C.c_double)]
+
+
+class NmodHmmOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in HMM_ENTRY_FIELDS + HMM_READ_FIELDS + HMM_SITE_FIELDS]
+
+
+def make_hmm_opts(pi=0.5, length=200.0, call_post=0.9):
+    o = NmodHmmOpts()
+    o.struct_size = C.sizeof(NmodHmmOpts)
+    o.pi, o.length, o.call_post = float(pi), float(length), float(call_post)
+    return o
+
+
+make_hmm_out = functools.partial(make_out, NmodHmmOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -417,6 +442,10 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'nmod_pair_linkage': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodLinkOpts),
                                     C.POINTER(NmodLinkOut)]),
+    'nmod_read_sites_count': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int64)]),
+    'nmod_read_hmm': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                C.POINTER(NmodHmmOpts), C.POINTER(NmodHmmOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

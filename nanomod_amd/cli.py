@@ -238,7 +238,40 @@ def build_parser():
     rp.add_argument('--outFolder', default='mRes')
     rp.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_pairs.txt')
     rp.add_argument('--device', type=int, default=0)
+    rh = sub.add_parser('readhmm', help='per-read two-state HMM smoothing of the window sums at candidate sites of one read-level sample on the '
+                        'device: per read and site the posterior of "modified" given the whole read, the modified stretches of every molecule, and '
+                        'the log-likelihood with and without correlation along the read')
+    rh.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rh.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rh.add_argument('--kmerModel', '--model', dest='kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
+    rh.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
+    rh.add_argument('--sites', default='stoich', help="'stoich': the positions whose modified share (readllr --siteFraction) has a "
+                    "Benjamini-Hochberg q of at most --siteAlpha; or a FILE of lines 'chrom strand pos' (1-based)")
+    rh.add_argument('--hmmPi', type=float, default=None, help='the stationary modified share, 1e-9 .. 1 - 1e-9; default: the mean of the '
+                    "candidate sites' estimated shares")
+    rh.add_argument('--hmmLength', type=float, default=200.0, help='the correlation length in bases, 1e-3 .. 1e9')
+    rh.add_argument('--fitLength', default=None, help='LEN,LEN,...: the length among these with the largest log-likelihood over all reads is used')
+    rh.add_argument('--callPost', type=float, default=0.9, help='the posterior from which an entry is called, inside (0.5, 1)')
+    rh.add_argument('--llrThreshold', type=float, default=2.5, help="K13's call threshold (it does not move the window sums), > 0")
+    rh.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
+                    'before and after, 0 .. 64 each')
+    rh.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state, inside (0, 1)')
+    rh.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rh.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first")
+    rh.add_argument('--siteAlpha', type=float, default=0.05, help="--sites stoich: the level of the sites' q-values, in (0, 1]")
+    rh.add_argument('--outFolder', default='mRes')
+    rh.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_hmm.txt, _read_domains.txt and _site_hmm.txt')
+    rh.add_argument('--device', type=int, default=0)
     return p
+
+
+def parse_fit_length(text):
+    """--fitLength: the list of lengths of 'LEN,LEN,...'; None for anything else"""
+    try:
+        vals = [float(q) for q in text.split(',')]
+    except ValueError:
+        return None
+    return vals if vals and all(v == v for v in vals) else None
 
 
 def parse_llr_window(text):
@@ -331,6 +364,60 @@ def validate_readpairs(a):
     if not errs and not container.is_read_level(a.wrkBase1):
         errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
     return errs
+
+
+def validate_readhmm(a):
+    """the checks of readhmm, in validate_readpairs' manner"""
+    errs = []
+    win = parse_llr_window(a.llrWindow)
+    if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
+        errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
+    if not 0.0 < a.llrThreshold < float('inf'):
+        errs.append('Error: --llrThreshold should be finite and larger than 0')
+    if not 0.0 < a.prior < 1.0:
+        errs.append('Error: --prior should lie between 0 and 1, both excluded')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    if a.hmmPi is not None and not 1e-9 <= a.hmmPi <= 1.0 - 1e-9:
+        errs.append('Error: --hmmPi should be in 1e-9 .. 1 - 1e-9')
+    if not 1e-3 <= a.hmmLength <= 1e9:
+        errs.append('Error: --hmmLength should be in 1e-3 .. 1e9')
+    if a.fitLength is not None:
+        grid = parse_fit_length(a.fitLength)
+        if grid is None or not all(1e-3 <= v <= 1e9 for v in grid):
+            errs.append('Error: --fitLength should be LEN,LEN,... with every length in 1e-3 .. 1e9')
+    if not 0.5 < a.callPost < 1.0:
+        errs.append('Error: --callPost should lie between 0.5 and 1, both excluded')
+    if not 0.0 < a.siteAlpha <= 1.0:
+        errs.append('Error: --siteAlpha should be in (0, 1]')
+    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_readhmm(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
+    res = readllr.smooth_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
+                                   sites=sites, pi=a.hmmPi, length=a.hmmLength, fit_length=None if a.fitLength is None else parse_fit_length(a.fitLength),
+                                   call_post=a.callPost, window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None,
+                                   site_alpha=a.siteAlpha, thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
+                                   log=(lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    for suffix, write, what in (('_read_hmm.txt', readllr.write_read_hmm, 'Read chains are'), ('_read_domains.txt', readllr.write_read_domains, 'Read domains are'),
+                                ('_site_hmm.txt', readllr.write_site_hmm, 'Smoothed site counts are')):
+        path = os.path.join(a.outFolder, a.FileID + suffix)
+        write(path, res)
+        if not quiet:
+            log('%s saved in %s' % (what, path))
+    if not quiet:
+        for v, ll in res['profile']:
+            log('length %g: log-likelihood %.6f%s' % (v, ll, ' *' if v == res['length'] else ''))
+    return res
 
 
 def run_readpairs(a, log=print):
@@ -892,6 +979,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readhmm':
+        errs = validate_readhmm(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readhmm(a)
+        return 0
     if a.cmd == 'readpairs':
         errs = validate_readpairs(a)
         if errs:

@@ -47,13 +47,15 @@ static __global__ __launch_bounds__(256) void read_classify_kernel(const int64_t
 struct ReadListSpace {
   size_t o_list, o_count;
   ReadListSpace(Slab& slab, size_t nreads) : o_list(slab.take(nreads * 4 * 2)), o_count(slab.take(16)) {}
-  hipError_t fill(const Slab& slab, const int64_t* off, int64_t nreads, int num_cus, hipStream_t stream, ReadLists& w) const {
+  // (wave_max: the class step in rows of `off`; K19 classes the reads by their entries, not their events)
+  hipError_t fill(const Slab& slab, const int64_t* off, int64_t nreads, int num_cus, hipStream_t stream, ReadLists& w,
+                  int64_t wave_max = kRwWaveMax) const {
     w.list[0] = slab.at<uint32_t>(o_list); w.list[1] = w.list[0] + nreads;
     w.count = slab.at<uint32_t>(o_count);
     const hipError_t e = hipMemsetAsync(w.count, 0, 16, stream);
     if (e != hipSuccess) return e;
     const int64_t cb = (nreads + 255) / 256, ccap = (int64_t)num_cus * 16;
-    hipLaunchKernelGGL(read_classify_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, off, nreads, kRwWaveMax, w);
+    hipLaunchKernelGGL(read_classify_kernel, dim3((unsigned)(cb < ccap ? cb : ccap)), dim3(256), 0, stream, off, nreads, wave_max, w);
     return hipSuccess;
   }
 };

@@ -10,7 +10,8 @@
 //   sp_pair_kernel       a thread per pair: first / second, status, log_or, se, phi, and p_fisher while the support has up to
 //                        NMOD_PAIRS_THREAD_MAX tables; the pairs beyond go to a list
 //   sp_pair_wave_kernel  a wave per listed pair: p_fisher by product scans over the lanes
-// A read finds the candidate sites it covers by two binary searches in the keys.  Their calls are gathered from the scores, one gather
+// A read finds the candidate sites it covers by two binary searches in the keys (site_search.hpp, with the scan kernel, the read's score at
+// a site and the host checks: shared with K19, read_hmm.hip).  Their calls are gathered from the scores, one gather
 // per site with the strand-aware event index, and staged one byte per site in a window of kSpWin sites of wave- or workgroup-private
 // LDS.  The first window of a tile holds the tile's own sites: a thread keeps the calls of the sites it owns in registers and walks
 // their partners from the stage; the partners beyond the tile follow window by window (the forward halo), so neither the sites a read
@@ -35,13 +36,12 @@
 #include "../../include/nanomod_hip.h"
 #include "radix_sort.hpp"
 #include "read_walk.hpp"
+#include "site_search.hpp"
 
 namespace nmod {
 
 constexpr int kSpWin = 256;                       // sites of a window of the stage: one byte each
-constexpr int64_t kSpPosMask = ((int64_t)1 << 40) - 1;
 constexpr int kSpNone = 2;                        // the staged byte of a site without a call (0: CAN, 1: MOD)
-constexpr int kSpScanPer = 8, kSpScanChunk = 256 * kSpScanPer;
 
 // what the walk over the reads takes: the reads, the scores, the sites and their pair index, the two lists of the reads
 struct SpWalk {
@@ -67,17 +67,6 @@ struct SpRowArgs : SpWalk {
 
 // ---------------------------------------------------------------------------------------------------------------- the pair index
 
-// the first index in [lo, hi) whose key is >= k (UPPER: > k)
-template <bool UPPER>
-__device__ __forceinline__ int64_t sp_bound(const int64_t* key, int64_t lo, int64_t hi, int64_t k) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    const int64_t v = key[mid];
-    if (UPPER ? v <= k : v < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void sp_index_kernel(const int64_t* key, int64_t nsites, int64_t max_dist, int64_t* cnt) {
   for (int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x; a < nsites; a += (int64_t)gridDim.x * 256) {
     const int64_t k = key[a], last = k | kSpPosMask;            // the last key of a's cs
@@ -86,47 +75,7 @@ __global__ __launch_bounds__(256) void sp_index_kernel(const int64_t* key, int64
   }
 }
 
-// poff[0, nsites): the counts, replaced by their exclusive scan; poff[nsites]: their sum.  One workgroup, a chunk at a time
-__global__ __launch_bounds__(256) void sp_scan_kernel(int64_t* poff, int64_t nsites) {
-  __shared__ int64_t sh[256];
-  const int tid = threadIdx.x;
-  int64_t carry = 0;
-  for (int64_t c0 = 0; c0 < nsites; c0 += kSpScanChunk) {
-    const int64_t base = c0 + (int64_t)tid * kSpScanPer;
-    int64_t v[kSpScanPer], s = 0;
-#pragma unroll
-    for (int e = 0; e < kSpScanPer; ++e) { v[e] = base + e < nsites ? poff[base + e] : 0; s += v[e]; }
-    sh[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-      const int64_t t = tid >= d ? sh[tid - d] : 0;
-      __syncthreads();
-      sh[tid] += t;
-      __syncthreads();
-    }
-    int64_t ex = carry + sh[tid] - s;
-    carry += sh[255];
-#pragma unroll
-    for (int e = 0; e < kSpScanPer; ++e) { if (base + e < nsites) poff[base + e] = ex; ex += v[e]; }
-    __syncthreads();                                            // sh is read before the next chunk writes it
-  }
-  if (tid == 0) poff[nsites] = carry;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the read kernel
-
-// One read as the walk hands it to its callers: where its events lie and its scores
-struct SpRead {
-  int64_t read, start, n; bool minus; const double* sc; const int64_t* key;
-  // the score of the read's event at site s; false: no event of this read (keys that do not ascend)
-  __device__ __forceinline__ bool score_at(int64_t s, double& l) const {
-    const int64_t pos = key[s] & kSpPosMask;
-    const int64_t i = minus ? start + n - 1 - pos : pos - start;
-    if (i < 0 || i >= n) return false;
-    l = sc[i];
-    return true;
-  }
-};
 
 // The walk of a persistent grid over the reads of list WAVES == 1 ? 0 : 1 (a wave per read, the workgroup's waves independent; else the
 // workgroup per read): site search, staged windows, forward halo.  What happens per (read, site) and per (read, pair) is the callers':
@@ -409,31 +358,6 @@ __global__ __launch_bounds__(256) void sp_pair_wave_kernel(SpArgs a) {
     const double p = sp_fisher_wave(q, lane);
     if (lane == 0) a.out.p_fisher[j] = p;
   }
-}
-
-static bool sp_keys_ascend(const int64_t* key, int64_t n) {
-  for (int64_t i = 0; i < n; ++i) if (key[i] < 0 || (i > 0 && key[i] <= key[i - 1])) return false;
-  return true;
-}
-
-// The checks of the reads, the sites and the pair index that the entries which walk the reads share (nmod_site_pairs, the two
-// nmod_pair_rows entries), before any device work
-static bool sp_walk_args_ok(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
-                            int64_t nsites, const int64_t* key, const int64_t* poff, int64_t npairs) {
-  if (nreads < 0 || nreads > (int64_t)INT32_MAX) return false;
-  if (nsites < 0 || nsites > (int64_t)INT32_MAX - 1 || npairs < 0 || npairs > (int64_t)INT32_MAX) return false;
-  if (nreads > 0 && (!cs || !start || !roff)) return false;
-  if ((nsites > 0 && !key) || (npairs > 0 && (!poff || nsites < 2))) return false;
-  if (prm->memspace == NMOD_MEM_HOST) {
-    if (nreads > 0 && !csr_offsets_ok(roff, nreads)) return false;
-    if (nreads > 0 && roff[nreads] > 0 && !score) return false;
-    if (!sp_keys_ascend(key, nsites)) return false;
-    if (poff && (poff[0] != 0 || !csr_offsets_ok(poff, nsites) || poff[nsites] != npairs)) return false;
-    if (!poff && npairs != 0) return false;
-  } else if (nreads > 0 && !score) {
-    return false;
-  }
-  return true;
 }
 
 static void sp_walk_args(SpWalk& a, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,

@@ -945,13 +945,18 @@ def _link_shapes(npairs, interval=True):
     return shapes
 
 
-def _host_pair_reads(cs, start, roff, score, key, poff):
-    """the reads, sites and pair index of a host call as site_pairs_host checks them"""
+def _host_site_reads(cs, start, roff, score, key):
+    """the reads and sites of a host call that walks the reads over candidate sites (K16, K18, K19), checked"""
     score = np.ascontiguousarray(score, dtype=np.float64)
     roff, nreads, _ = _read_layout(score, roff, 'score')
     cs = _side(cs, np.int32, nreads, 'cs', 'nreads', optional=False)
     start = _side(start, np.int64, nreads, 'start', 'nreads', optional=False)
-    key = _host_keys(key)
+    return cs, start, roff, score, _host_keys(key), nreads
+
+
+def _host_pair_reads(cs, start, roff, score, key, poff):
+    """the reads, sites and pair index of a host call as site_pairs_host checks them"""
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
     poff = _side(poff, np.int64, key.shape[0] + 1, 'poff', 'nsites + 1', optional=False)
     if poff[0] != 0 or bool(np.any(np.diff(poff) < 0)):
         raise ValueError('poff must start at 0 and never decrease')
@@ -997,6 +1002,81 @@ def pair_linkage_host(sa, sb, prow_off, *, min_reads=20, ci_level=0.95, max_iter
     out = L.make_link_out(**_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
     _call(lib, 'nmod_pair_linkage', prm, npairs, _np_ptr(sa), _np_ptr(sb), _np_ptr(prow_off), C.byref(opts), C.byref(out))
+    return res
+
+
+HMM_OUTPUTS = L.HMM_ENTRY_FIELDS + L.HMM_READ_FIELDS + L.HMM_SITE_FIELDS
+
+
+def _hmm_opts(pi, length, call_post, want):
+    """nmod_hmm_opts from the Python arguments; ValueError for what the C entry refuses"""
+    pi, length, call_post = float(pi), float(length), float(call_post)
+    if not 1e-9 <= pi <= 1.0 - 1e-9:
+        raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
+    if not 1e-3 <= length <= 1e9:
+        raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
+    if not 0.5 < call_post < 1.0:
+        raise ValueError('call_post must lie inside (0.5, 1), not %r' % (call_post,))
+    want = tuple(want)
+    if any(w not in HMM_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(HMM_OUTPUTS))
+    return L.make_hmm_opts(pi, length, call_post), want
+
+
+def _check_hmm_counts(nreads, nsites, nrows):
+    _check_pair_counts(nreads, nsites, 0)
+    if int(nrows) != nrows or not 0 <= int(nrows) <= 2 ** 31 - 1:
+        raise ValueError('nrows must be an integer in 0 .. 2^31 - 1, not %r' % (nrows,))
+    return int(nrows)
+
+
+def _hmm_shapes(want, nrows, nreads, nsites):
+    kinds = dict(post=('float64', nrows), site=('int32', nrows), state=('uint8', nrows), ll=('float64', nreads), ll_indep=('float64', nreads),
+                 status=('uint8', nreads), **{k: ('int32', nreads) for k in ('n_sites', 'n_mod', 'n_can', 'n_runs')},
+                 **{k: ('int32', nsites) for k in L.HMM_SITE_FIELDS})
+    return {k: kinds[k] for k in HMM_OUTPUTS if k in want}
+
+
+def read_sites_host(cs, start, roff, score, key, device=0):
+    """Per read the candidate sites it covers with a valid score, counted (nmod_read_sites_count, include/nanomod_hip.h): the reads,
+    scores and keys of site_pairs_host.  Returns hoff (int64[nreads + 1]): the entries of read r are the rows hoff[r] .. hoff[r + 1] - 1
+    of read_hmm_host's per-entry outputs."""
+    lib = L.load()
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
+    _check_hmm_counts(nreads, key.shape[0], 0)
+    hoff = np.zeros(nreads + 1, dtype=np.int64)
+    nrows = C.c_int64(0)
+    _join_warm_up(device)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_sites_count', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(hoff), C.byref(nrows))
+    return hoff
+
+
+def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, device=0):
+    """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, include/nanomod_hip.h) on host-resident
+    reads: the arguments of read_sites_host and the hoff it gives (None: computed here).  pi: the stationary modified share; length: the
+    correlation length in bases; call_post: the posterior from which an entry is called.  Returns a dict of numpy arrays, hoff and those
+    named in `want`: per entry post (float64), site (int32, the index into key), state (uint8: 1 modified, 0 canonical, 2 neither); per
+    read n_sites, n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod,
+    site_can (int32)."""
+    lib = L.load()
+    opts, want = _hmm_opts(pi, length, call_post, want)
+    if hoff is None:
+        hoff = read_sites_host(cs, start, roff, score, key, device)
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
+    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
+    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
+        raise ValueError('hoff must start at 0 and never decrease')
+    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
+    shapes = _hmm_shapes(want, nrows, nreads, key.shape[0])
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_hmm_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_hmm', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
+    res['hoff'] = hoff
     return res
 
 
@@ -1533,6 +1613,44 @@ class DeviceDetector:
         o = L.make_link_out(**{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
         _call(self.lib, 'nmod_pair_linkage', prm, npairs, sa.data_ptr(), sb.data_ptr(), prow_off.data_ptr(), C.byref(opts), C.byref(o))
+        return res
+
+    def _site_reads(self, what, cs, start, roff, score, key):
+        """the reads and sites of a device entry that walks the reads over candidate sites without a pair index, checked"""
+        torch = self.torch
+        nreads = _device_offsets(torch, roff, what, 'nreads')
+        _cuda_vecs(what, (('cs', cs, torch.int32, nreads), ('start', start, torch.int64, nreads), ('score', score, torch.float64, None),
+                          ('key', key, torch.int64, None)), one_dim=True, missing='refused')
+        return nreads, (nreads, cs.data_ptr(), start.data_ptr(), roff.data_ptr(), score.data_ptr(), key.numel(), key.data_ptr())
+
+    def read_sites(self, cs, start, roff, score, key):
+        """Per read the candidate sites it covers with a valid score, counted (nmod_read_sites_count, NMOD_MEM_DEVICE) on the current
+        stream: the reads, scores and keys of site_pairs.  Synchronises the stream once to learn the number of rows.  Returns
+        (hoff, nrows): hoff an int64 CUDA vector of nreads + 1 offsets."""
+        nreads, shared = self._site_reads('read_sites', cs, start, roff, score, key)
+        _check_hmm_counts(nreads, key.numel(), 0)
+        hoff = self.torch.empty(nreads + 1, dtype=self.torch.int64, device=self._dev)
+        nrows = C.c_int64(0)
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_sites_count', prm, *shared, hoff.data_ptr(), C.byref(nrows))
+        return hoff, int(nrows.value)
+
+    def read_hmm(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, out=None):
+        """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, NMOD_MEM_DEVICE), enqueued on the
+        current stream without synchronising or reading anything back: the arguments of read_sites, hoff and nrows as it gives them.
+        Returns a dict of CUDA tensors, those named in `want`: per entry post (float64), site (int32), state (uint8); per read n_sites,
+        n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod, site_can
+        (int32).  out: such a dict from an earlier call of the same shape."""
+        torch = self.torch
+        opts, want = _hmm_opts(pi, length, call_post, want)
+        nreads, shared = self._site_reads('read_hmm', cs, start, roff, score, key)
+        _cuda_vecs('read_hmm', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
+        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
+        shapes = _hmm_shapes(want, nrows, nreads, key.numel())
+        res = self._outputs(out, shapes, 'read_hmm')
+        o = L.make_hmm_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_hmm', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

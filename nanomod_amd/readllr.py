@@ -300,6 +300,74 @@ def site_keys(sites, names):
     return np.unique((cs << 40) | pos[known])
 
 
+def _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale):
+    """The two masked models and K13's options of the entries that score a read-level set and then keep the read (cooccur_reads_llr,
+    smooth_reads_llr), with their refusals, before any device work: (m0, m1, k, center, prior_logit, opts)"""
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    if rescale is not None:
+        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
+        if unknown:
+            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    return m0, m1, k, center, prior_logit, opts
+
+
+def _sites_by_stoich(sites):
+    by_stoich = isinstance(sites, str)
+    if by_stoich and sites != 'stoich':
+        raise ValueError("sites must be 'stoich' or (chrom, strand, pos) arrays")
+    return by_stoich
+
+
+def _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_share=False):
+    """The window sums (K13, after the optional rescaling K11) of a read-level set and the candidate sites, on the device and on one
+    stream: sites 'stoich' (K14's estimates whose Benjamini-Hochberg q of p_null is at most site_alpha) or (chrom, strand, pos) arrays.
+    Returns a dict: det, names, nreads, the CUDA vectors d_cs, d_start, d_off, llr_win and d_key, and with want_share site_pi: K14's
+    estimates at the candidate sites that have one (a CUDA vector)."""
+    import torch
+    m0, m1, k, center, prior_logit, opts = setup
+    by_stoich = _sites_by_stoich(sites)
+    val, off, base = _checked_reads(reads, 'reads')
+    nreads = len(off) - 1
+    names = engine.chrom_names(reads)
+    cs = engine.chrom_strand_ids(np.asarray(reads['chrom']).astype(str), np.asarray(reads['strand']).astype(str), names)
+    start = np.ascontiguousarray(reads['start'], dtype=np.int64)
+    host_key = None if by_stoich else site_keys(sites, names)
+    engine._join_warm_up(device)
+    det = engine.DeviceDetector(device)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    d_val, d_off, d_base = t(val), t(off), t(base)
+    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+    if rescale is not None:
+        d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
+    llr_win = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
+                           prior_logit=prior_logit, want=('llr_win',))['llr_win']
+    site_pi = None
+    if by_stoich or want_share:
+        piv = engine.pivot_reads(reads, device, names=names, val=llr_win)
+        share = det.site_stoich(piv['sig'], off=piv['off'])
+        estimated = (share['status'] & L.STOICH_NO_ESTIMATE) == 0
+    if by_stoich:
+        (q_site,), _ = det.fdr(share, tracks=('p_null',), method='bh', alpha=site_alpha)
+        keep = estimated & (q_site <= site_alpha)                                             # (a NaN q compares false)
+        d_key = piv['key'][keep].contiguous()
+    else:
+        d_key = t(host_key)
+        keep = (estimated & torch.isin(piv['key'], d_key)) if want_share else None
+    if want_share:
+        site_pi = share['pi'][keep]
+    return dict(det=det, names=names, nreads=nreads, d_cs=t(cs), d_start=t(start), d_off=d_off, llr_win=llr_win, d_key=d_key, site_pi=site_pi)
+
+
 def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, thr=2.5, min_reads=10, window='kmer', prior=0.5,
                       min_positions=1, rescale=None, fdr=None, fdr_alpha=0.05, site_alpha=0.05, device=0, log=print, soft=False,
                       ci_level=0.95):
@@ -320,21 +388,7 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
       pi11, pi10, pi01, pi00 (the cells of the joint law from pa, pb and d), stat, p_indep (the likelihood-ratio test of independence),
       link_status (uint8, L.LINK_* bits) and with fdr q_indep; a second line goes to `log`.  A pair needs max(min_reads, LINK_MIN_READS)
       such reads: below that the chi2 law of stat is liberal.  Without `soft` nothing changes."""
-    import torch
-    m0 = _rescale.masked_model(model, min_positions)
-    m1 = _rescale.masked_model(alt_model, min_positions)
-    k, center = m0['k'], m0['center']
-    if (m1['k'], m1['center']) != (k, center):
-        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
-    prior = float(prior)
-    if not 0.0 < prior < 1.0:
-        raise ValueError('prior must lie inside (0, 1)')
-    prior_logit = math.log(prior / (1.0 - prior))
-    if rescale is not None:
-        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
-        if unknown:
-            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
-    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
     engine._pairs_opts(thr, min_reads, False, ())
     link_min_reads = max(int(min_reads), LINK_MIN_READS)
     if soft:
@@ -344,35 +398,10 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
         engine._fdr_method(fdr)
     engine._check_alpha(fdr_alpha)
     site_alpha = engine._check_alpha(site_alpha)
-    by_stoich = isinstance(sites, str)
-    if by_stoich and sites != 'stoich':
-        raise ValueError("sites must be 'stoich' or (chrom, strand, pos) arrays")
-    val, off, base = _checked_reads(reads, 'reads')
-    nreads = len(off) - 1
-    names = engine.chrom_names(reads)
-    cs = engine.chrom_strand_ids(np.asarray(reads['chrom']).astype(str), np.asarray(reads['strand']).astype(str), names)
-    start = np.ascontiguousarray(reads['start'], dtype=np.int64)
-    host_key = None if by_stoich else site_keys(sites, names)
-    engine._join_warm_up(device)
-    det = engine.DeviceDetector(device)
-    dev = torch.device('cuda', device)
-    t = lambda x: torch.from_numpy(x).to(dev)
-    d_val, d_off, d_base = t(val), t(off), t(base)
-    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
-    if rescale is not None:
-        d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
-    llr_win = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
-                           prior_logit=prior_logit, want=('llr_win',))['llr_win']
-    if by_stoich:
-        piv = engine.pivot_reads(reads, device, names=names, val=llr_win)
-        share = det.site_stoich(piv['sig'], off=piv['off'])
-        (q_site,), _ = det.fdr(share, tracks=('p_null',), method='bh', alpha=site_alpha)
-        keep = ((share['status'] & L.STOICH_NO_ESTIMATE) == 0) & (q_site <= site_alpha)       # (a NaN q compares false)
-        d_key = piv['key'][keep].contiguous()
-    else:
-        d_key = t(host_key)
+    by_stoich = _sites_by_stoich(sites)
+    sc = _site_scores(reads, setup, sites, site_alpha, rescale, thr, device)
+    det, names, nreads, d_off, llr_win, d_key, d_cs, d_start = (sc[f] for f in ('det', 'names', 'nreads', 'd_off', 'llr_win', 'd_key', 'd_cs', 'd_start'))
     poff, npairs = det.pair_index(d_key, max_dist)
-    d_cs, d_start = t(cs), t(start)
     res = det.site_pairs(d_cs, d_start, d_off, llr_win, d_key, poff, npairs, thr=thr, min_reads=min_reads)
     q = None
     if fdr is not None:
@@ -440,3 +469,109 @@ def write_site_linkage(path, pairs):
     fmt = '%s %s %d %d %d %d' + ' %.6f' * 10 + ' %.3f %s ' + ('%s ' if 'q_indep' in pairs else '') + '%d\n'
     with open(path, 'w') as f:
         f.writelines(fmt % row for row in zip(*cols))
+
+
+def read_domains(hoff, site, state, post, site_pos):
+    """The runs of consecutive entries in state 1 of every read, from nmod_read_hmm's per-entry tracks: a dict of arrays, one entry per
+    run: read, first, last (the positions of its first and last site), n_sites and mean_post"""
+    hoff, state = np.asarray(hoff, np.int64), np.asarray(state)
+    n = len(state)
+    one = state == 1
+    row = np.arange(n)
+    read_of = np.searchsorted(hoff, row, 'right') - 1
+    begins, ends = row == hoff[read_of], row == hoff[read_of + 1] - 1
+    first = np.flatnonzero(one & (begins | ~np.concatenate(([False], one[:-1]))))
+    last = np.flatnonzero(one & (ends | ~np.concatenate((one[1:], [False]))))
+    sums = np.add.reduceat(np.concatenate((np.asarray(post, np.float64), [0.0])), np.stack((first, last + 1), 1).ravel())[::2] if len(first) else np.zeros(0)
+    pos = np.asarray(site_pos, np.int64)[np.asarray(site, np.int64)]
+    count = last - first + 1
+    return dict(read=read_of[first], first=pos[first], last=pos[last], n_sites=count, mean_post=sums / count)
+
+
+def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length=200.0, fit_length=None, call_post=0.9, window='kmer',
+                     rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print):
+    """Per-read two-state HMM smoothing of the window sums at candidate sites (K19, nmod_read_sites_count / nmod_read_hmm): along each
+    molecule, where are the modified stretches, and what is the call at a weak site once its neighbours on the same read are taken into
+    account?  The optional rescaling (K11), the window sums (K13) and the candidate sites exactly as in cooccur_reads_llr; then, read by
+    read, a two-state chain over the candidate sites the read covers, the emission the likelihood ratio K13 computed, the correlation
+    decaying as exp(-distance / length), evaluated by forward-backward on the device and on one stream.
+    pi: the stationary modified share; None: the mean of K14's estimates over the candidate sites that have one.  length: the
+    correlation length in bases.  fit_length: None, or a list of lengths: the chain's log-likelihood summed over the reads
+    (math.fsum) is computed for each and the largest is kept (the first of equals); `profile` reports them all.  call_post: the
+    posterior from which an entry is called modified (and canonical at 1 - call_post or below).
+    Returns a dict: pi, length, profile (a list of (length, log-likelihood) pairs, empty without fit_length);
+      reads: index, chrom, strand, n_sites, n_mod, n_can, n_runs, ll, ll_indep, status (L.HMM_NO_SITE);
+      entries: hoff (int64[nreads + 1]), site (the index into `sites`), post, state;
+      sites: chrom, strand, pos (0-based), n, n_mod, n_can, share = n_mod / (n_mod + n_can) (NaN without a called entry);
+      domains: read_domains' runs.  One summary line goes to `log`."""
+    setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
+    site_alpha = engine._check_alpha(site_alpha)
+    _sites_by_stoich(sites)
+    grid = None if fit_length is None else [float(v) for v in fit_length]
+    if grid is not None and not grid:
+        raise ValueError('fit_length must name at least one length')
+    for v in (grid or [length]):
+        engine._hmm_opts(0.5 if pi is None else pi, v, call_post, ())                         # the refusals, before any device work
+    sc = _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_share=pi is None)
+    det, names, nreads, d_key = sc['det'], sc['names'], sc['nreads'], sc['d_key']
+    if pi is None:
+        if sc['site_pi'].numel() == 0:
+            raise ValueError('pi=None needs a candidate site with an estimate of its modified share (K14); there is none')
+        pi = min(max(float(sc['site_pi'].mean().item()), 1e-9), 1.0 - 1e-9)
+    shared = (sc['d_cs'], sc['d_start'], sc['d_off'], sc['llr_win'], d_key)
+    hoff, nrows = det.read_sites(*shared)
+    profile = []
+    if grid is not None:
+        for v in grid:
+            profile.append((v, math.fsum(det.read_hmm(*shared, hoff, nrows, pi=pi, length=v, call_post=call_post, want=('ll',))['ll'].cpu().tolist())))
+        length = max(profile, key=lambda p: p[1])[0]
+    res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post)
+    res = {f: v.cpu().numpy() for f, v in res.items()}
+    key = d_key.cpu().numpy()
+    nm = np.array(names, dtype=str)
+    called = (res['site_mod'] + res['site_can']).astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        share = np.where(called > 0, res['site_mod'] / called, np.nan)
+    out_sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                     pos=key & ((1 << 40) - 1), n=res['site_n'], n_mod=res['site_mod'], n_can=res['site_can'], share=share)
+    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
+                 **{f: res[f] for f in L.HMM_READ_FIELDS})
+    entries = dict(hoff=hoff.cpu().numpy(), site=res['site'], post=res['post'], state=res['state'])
+    domains = read_domains(entries['hoff'], entries['site'], entries['state'], entries['post'], out_sites['pos'])
+    log('readhmm: %d read(s), %d candidate site(s), %d entr%s; pi %.6g, length %g%s; %d modified and %d canonical at posterior %g, %d domain(s) on %d read(s)'
+        % (nreads, len(key), nrows, 'y' if nrows == 1 else 'ies', pi, length, '' if grid is None else ' (the best of %d)' % len(grid),
+           int(table['n_mod'].sum()), int(table['n_can'].sum()), float(call_post), len(domains['read']), int((table['n_runs'] > 0).sum())))
+    return dict(pi=pi, length=length, profile=profile, reads=table, entries=entries, sites=out_sites, domains=domains)
+
+
+def write_read_hmm(path, res):
+    """<FileID>_read_hmm.txt: per read 'index chrom strand n_sites n_mod n_can n_runs ll ll_indep 2(ll-ll_indep)' as
+    '%d %s %s %d %d %d %d %.6f %.6f %.6f' (`res` of smooth_reads_llr)"""
+    t = res['reads']
+    ll, ind = np.asarray(t['ll'], np.float64), np.asarray(t['ll_indep'], np.float64)
+    cols = [np.asarray(t['index']).tolist(), np.asarray(t['chrom']).astype(str).tolist(), np.asarray(t['strand']).astype(str).tolist()] + \
+           [np.asarray(t[f]).tolist() for f in ('n_sites', 'n_mod', 'n_can', 'n_runs')] + [ll.tolist(), ind.tolist(), (2.0 * (ll - ind)).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%d %s %s %d %d %d %d %.6f %.6f %.6f\n' % row for row in zip(*cols))
+
+
+def write_read_domains(path, res):
+    """<FileID>_read_domains.txt: per run of modified entries 'read chrom strand first+1 last+1 n_sites mean_post' as
+    '%d %s %s %d %d %d %.6f' (the positions 1-based; `res` of smooth_reads_llr)"""
+    d, t = res['domains'], res['reads']
+    read = np.asarray(d['read'], np.int64)
+    cols = [read.tolist(), np.asarray(t['chrom']).astype(str)[read].tolist(), np.asarray(t['strand']).astype(str)[read].tolist(),
+            (np.asarray(d['first'], np.int64) + 1).tolist(), (np.asarray(d['last'], np.int64) + 1).tolist(), np.asarray(d['n_sites']).tolist(),
+            np.asarray(d['mean_post']).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%d %s %s %d %d %d %.6f\n' % row for row in zip(*cols))
+
+
+def write_site_hmm(path, res):
+    """<FileID>_site_hmm.txt: per candidate site 'chrom strand pos+1 n n_mod n_can share' as '%s %s %d %d %d %d %.6f' (the position
+    1-based; share 'nan' where no entry is called; `res` of smooth_reads_llr)"""
+    s = res['sites']
+    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()] + \
+           [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'n_can', 'share')]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
