@@ -1119,9 +1119,9 @@ int nmod_pair_linkage(const nmod_params* prm, int64_t npairs, const double* sa, 
  *     or of another struct_size; nrows outside 0 .. 2^31 - 1 or positive without reads or sites; a NULL hoff; host hoff that does not
  *     start at 0, ascend and end at nrows.
  *   Scratch: 32 B per row (position, score, forward vector), 36 B where site is not asked for.
- * Stops at: two states; one (pi, length) for all sites and reads, no per-site prior; posterior decoding only, no Viterbi path; no
- * Baum-Welch: length is chosen on a grid by the caller and pi is given; the reads are independent and both k-mer tables are taken as
- * right; one (chrom, strand) per read. */
+ * Stops at: two states; one (pi, length) for all sites and reads, no per-site prior; posterior decoding (the most probable path is
+ * nmod_read_viterbi's, below); no Baum-Welch: length is chosen on a grid by the caller and pi is given; the reads are independent and
+ * both k-mer tables are taken as right; one (chrom, strand) per read. */
 #define NMOD_HMM_CHUNK 4                   /* steps of a tile a thread owns */
 #define NMOD_HMM_WAVE_MAX 1024             /* entries of a read up to which one wave computes it (a workgroup of four beyond) */
 enum { NMOD_HMM_NO_SITE = 1 };
@@ -1135,6 +1135,63 @@ int nmod_read_sites_count(const nmod_params* prm, int64_t nreads, const int32_t*
 int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                   const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                   const nmod_hmm_opts* opts, const nmod_hmm_out* out);
+
+/* Per-read Viterbi decoding of nmod_read_hmm's chain: the jointly most probable sequence of states of a read's entries, how firmly
+ * every entry belongs to it, and the path's log-probability (K20; the reference project has no such step).  nmod_read_hmm's state is
+ * a marginal call per entry, and a sequence of such calls need not be a likely path; a domain is a statement about a path.
+ *   Inputs, word for word nmod_read_hmm's: the reads, score, key, hoff and nrows (from nmod_read_sites_count), the ENTRIES of a read,
+ *     opts->pi and opts->length with their ranges, q = 1 - pi formed once on the host, T_j, the memspaces, the stream contract, the
+ *     NULL-skips-an-output rule, and the refusals (there is no call_post); a row outside its read's hoff range is skipped.
+ *   Model, in logarithms.  log q and log pi are formed once on the host.  The emissions le_j = (-max(s_j, 0), min(s_j, 0)), formed as
+ *     (s_j > 0 ? -s_j : 0, s_j < 0 ? s_j : 0): exact, no exp and no log.  With rho and eps as in nmod_read_hmm, the step is
+ *         L_j[r][c] = log(T_j[r][c]) + le_j[c],   T_0 = I: L_0 = [[le_00, -inf], [-inf, le_01]];
+ *     three logarithms a step: log T_j = [[log(q + pi rho), log pi + log eps], [log q + log eps, log(pi + q rho)]], each sum formed
+ *     before le is added.  The identity of the (max, +) algebra is [[0, -inf], [-inf, 0]].  Every term is <= 0
+ *     up to rounding: no +inf and no NaN arises, and nothing is rescaled.  Contraction is off for the whole translation unit.
+ *   MAX of two sums (u, v) is v where v > u and u otherwise: the first of equals, everywhere below.
+ *   Products.  Of two matrices c_rc = MAX(l_r0 + r_0c, l_r1 + r_1c); a vector step y_c = MAX(x_0 + m_0c, x_1 + m_1c), forwards from
+ *     (log q, log pi): a_j = x_j, the best score of a path over entries 0 .. j that ends in each state.
+ *   Back-pointers.  psi_j(c) = 1 iff x_1 + m_1c > x_0 + m_0c, strictly (a tie goes to state 0), from the two sums that give y_c in the
+ *     thread's replay of step j (ORDER below): path and vit agree with each other bit for bit.
+ *   Traceback.  z_(m-1) = 1 iff a_(m-1),1 > a_(m-1),0;  z_(j-1) = psi_j(z_j).  (Computed as a scan of compositions of maps
+ *     {0, 1} -> {0, 1} over tiles from the last entry to the first; integers, so any order gives the recursion's result.)
+ *   Per entry.  path_j = z_j (uint8, 0 or 1).  site_j as in nmod_read_hmm.  delta_j = M_j(1) - M_j(0) with M_j(s) = a_j(s) + b_j(s),
+ *     the score of the best path that is in state s at entry j: b is the backward vector, from nmod_read_hmm's backward scan in this
+ *     algebra (the transposes of L_j reversed, from (0, 0)); delta_j = (a_j1 + b_j1) - (a_j0 + b_j0) in that order.  delta_j > 0 says
+ *     how much score the best path loses if entry j is forced canonical, delta_j < 0 the same for modified; in exact arithmetic
+ *     path_j = 1 implies delta_j >= 0.
+ *   Per read.  n_sites = m (int32); n_mod = the entries of the path in state 1; n_runs = its maximal runs of 1;
+ *     vit = MAX(a_(m-1),0, a_(m-1),1) + S, S the sum of max(s_j, 0) in nmod_read_hmm's order: the best path's log-probability on ll's
+ *     scale, so vit <= ll up to rounding and vit - ll is the log of P(best path | the read's scores).  status (uint8):
+ *     NMOD_HMM_NO_SITE when m = 0 (vit = 0, the counts 0).
+ *   Per site (int32[nsites] each, integer atomics, zeroed by the entry on the stream): site_n = the reads with an entry there,
+ *     site_mod = the entries of the paths in state 1.
+ *   ORDER of the operations: nmod_read_hmm's, with the same NMOD_HMM_CHUNK and NMOD_HMM_WAVE_MAX: T = 64 or 256 threads by m, tiles
+ *     of T * NMOD_HMM_CHUNK steps, a thread's product of its steps left to right, the six-step scan of the lanes (d = 1 .. 32, lane
+ *     l >= d takes P_(l-d) P_l), the vector in front of a thread's chunk = the tile's carry, times the totals of the waves in front
+ *     in ascending order, times the scanned product of the lane before; then one vector step per entry, and the carry of the next
+ *     tile is thread T - 1's vector.  The backward scan: step k is the transpose of L_(m-k), the identity at k = 0, and belongs to
+ *     entry m - 1 - k.  The bits of every output depend on the read and the sites alone, not on the batch, the order of the reads,
+ *     the memspace or the outputs asked for.  No float atomics.
+ *   Passes.  When none of path, n_mod, n_runs and site_mod is asked for, the traceback is not run and no back-pointer is stored; when
+ *     delta is not asked for, the backward scan is not run and no forward vector is stored.  Asking for fewer outputs never changes
+ *     the bits of the others.
+ *   Overflow.  Scores whose sums leave the double range make vit and delta unspecified (infinite or NaN); path stays 0 or 1.
+ *   NMOD_ERR_INVALID_ARG before any device work: nmod_read_hmm's list without call_post.  nreads == 0 or nrows == 0: NMOD_OK with
+ *     zeroed site counts (with reads, each gets NMOD_HMM_NO_SITE).
+ *   Scratch: at most 33 B per row (position, score, forward vector, one byte of back-pointers), 37 B where site is not asked for; 16 B
+ *     less without delta, 1 B less without the traceback.
+ * Stops at: the single best path, no k-best list and no minimum-length constraint on a domain; the model is nmod_read_hmm's with all
+ * its limits (two states, one (pi, length), no Baum-Welch). */
+typedef struct nmod_vit_opts { int32_t struct_size, reserved; double pi, length; } nmod_vit_opts;
+typedef struct nmod_vit_out { int32_t struct_size; int32_t reserved;
+  uint8_t* path; int32_t* site; double* delta;                          /* [nrows] */
+  int32_t *n_sites, *n_mod, *n_runs; double* vit; uint8_t* status;      /* [nreads] */
+  int32_t *site_n, *site_mod;                                           /* [nsites] */
+} nmod_vit_out;
+int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                      const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                      const nmod_vit_opts* opts, const nmod_vit_out* out);
 
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One

@@ -365,6 +365,29 @@ def make_hmm_opts(pi=0.5, length=200.0, call_post=0.9):
 make_hmm_out = functools.partial(make_out, NmodHmmOut)
 
 
+VIT_ENTRY_FIELDS = ('path', 'site', 'delta')   # nmod_read_viterbi; the constants and NMOD_HMM_NO_SITE are nmod_read_hmm's
+VIT_READ_FIELDS = ('n_sites', 'n_mod', 'n_runs', 'vit', 'status')
+VIT_SITE_FIELDS = ('site_n', 'site_mod')
+
+
+class NmodVitOpts(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('pi', C.c_double), ('length', C.c_double)]
+
+
+class NmodVitOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in VIT_ENTRY_FIELDS + VIT_READ_FIELDS + VIT_SITE_FIELDS]
+
+
+def make_vit_opts(pi=0.5, length=200.0):
+    o = NmodVitOpts()
+    o.struct_size = C.sizeof(NmodVitOpts)
+    o.pi, o.length = float(pi), float(length)
+    return o
+
+
+make_vit_out = functools.partial(make_out, NmodVitOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -446,6 +469,8 @@ _SIGNATURES = {
                                         C.POINTER(C.c_int64)]),
     'nmod_read_hmm': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                 C.POINTER(NmodHmmOpts), C.POINTER(NmodHmmOut)]),
+    'nmod_read_viterbi': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.POINTER(NmodVitOpts), C.POINTER(NmodVitOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

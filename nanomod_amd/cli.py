@@ -252,6 +252,9 @@ def build_parser():
     rh.add_argument('--hmmLength', type=float, default=200.0, help='the correlation length in bases, 1e-3 .. 1e9')
     rh.add_argument('--fitLength', default=None, help='LEN,LEN,...: the length among these with the largest log-likelihood over all reads is used')
     rh.add_argument('--callPost', type=float, default=0.9, help='the posterior from which an entry is called, inside (0.5, 1)')
+    rh.add_argument('--decode', default='posterior', choices=['posterior', 'viterbi', 'both'], help="'posterior': the marginal calls; 'viterbi': "
+                    'the most probable path of every read, written to <FileID>_read_viterbi.txt, _read_domains_viterbi.txt and _site_viterbi.txt; '
+                    "'both': the two")
     rh.add_argument('--llrThreshold', type=float, default=2.5, help="K13's call threshold (it does not move the window sums), > 0")
     rh.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
                     'before and after, 0 .. 64 each')
@@ -406,12 +409,20 @@ def run_readhmm(a, log=print):
                                    sites=sites, pi=a.hmmPi, length=a.hmmLength, fit_length=None if a.fitLength is None else parse_fit_length(a.fitLength),
                                    call_post=a.callPost, window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None,
                                    site_alpha=a.siteAlpha, thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
-                                   log=(lambda *x: None) if quiet else log)
+                                   log=(lambda *x: None) if quiet else log, **({} if a.decode == 'posterior' else {'decode': a.decode}))
     os.makedirs(a.outFolder, exist_ok=True)
-    for suffix, write, what in (('_read_hmm.txt', readllr.write_read_hmm, 'Read chains are'), ('_read_domains.txt', readllr.write_read_domains, 'Read domains are'),
-                                ('_site_hmm.txt', readllr.write_site_hmm, 'Smoothed site counts are')):
+    files = []
+    if a.decode != 'viterbi':
+        files += [('_read_hmm.txt', readllr.write_read_hmm, 'Read chains are', res), ('_read_domains.txt', readllr.write_read_domains, 'Read domains are', res),
+                  ('_site_hmm.txt', readllr.write_site_hmm, 'Smoothed site counts are', res)]
+    if a.decode != 'posterior':
+        v = res['viterbi']
+        files += [('_read_viterbi.txt', readllr.write_read_viterbi, 'Viterbi paths are', v),
+                  ('_read_domains_viterbi.txt', readllr.write_read_domains, 'Viterbi domains are', v),
+                  ('_site_viterbi.txt', readllr.write_site_viterbi, 'Viterbi site counts are', v)]
+    for suffix, write, what, arg in files:
         path = os.path.join(a.outFolder, a.FileID + suffix)
-        write(path, res)
+        write(path, arg)
         if not quiet:
             log('%s saved in %s' % (what, path))
     if not quiet:

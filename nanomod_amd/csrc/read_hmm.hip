@@ -5,7 +5,8 @@
 //   read_classify_kernel     (read_walk.hpp) a thread per read: the read's class, by its events for the entries, by its entries for the chain
 //   rh_entries_kernel<., 0>  the entries of a read counted: ballots over the sites it covers (nmod_read_sites_count)
 //   sp_scan_kernel           (site_search.hpp) the counts' exclusive scan in place (hoff)
-//   rh_entries_kernel<., 1>  the same walk: entry j of the read writes its site, its position and its score to row hoff[r] + j
+//   rh_entries_kernel<., 1>  the same walk: entry j of the read writes its site, its position and its score to row hoff[r] + j (K20's
+//                            entry enqueues it too, through read_entries.hpp's rh_fill_entries)
 //   rh_hmm_kernel<1>         a wave per read of up to NMOD_HMM_WAVE_MAX entries, four waves a workgroup
 //   rh_hmm_kernel<4>         a workgroup of four waves per longer read
 // The chain of a read is two passes of one scan, rh_tile<., BWD>, over tiles of NMOD_HMM_CHUNK entries a thread: a thread forms the step
@@ -21,24 +22,13 @@
 #include <string.h>
 
 #include "../../include/nanomod_hip.h"
+#include "read_entries.hpp"
 #include "read_walk.hpp"
 #include "site_search.hpp"
 
 namespace nmod {
 
-constexpr int kHmmChunk = NMOD_HMM_CHUNK;         // entries of a tile a thread owns
-static_assert(NMOD_HMM_WAVE_MAX % (64 * NMOD_HMM_CHUNK) == 0, "the class step is a whole number of wave tiles");
 constexpr double kLn2 = 0.6931471805599453;
-
-// the entries of the reads (both entries): the reads, the scores, the sites, the lists of the reads by their events
-struct RhEntArgs {
-  int64_t nreads; const int32_t* cs; const int64_t* start; const int64_t* roff; const double* score;
-  int64_t nsites; const int64_t* key;
-  ReadLists w;
-  int64_t* cnt;                                   // count: entries per read (hoff before its scan)
-  const int64_t* hoff; int64_t nrows;             // fill: the rows of read r are hoff[r] .. hoff[r + 1] - 1
-  int32_t* site; double* xs;                      // per row: the site's index; its position and the read's score there
-};
 
 // the chain: the rows, the lists of the reads by their entries
 struct RhArgs {
@@ -107,6 +97,10 @@ __global__ __launch_bounds__(kRwThreads) void rh_entries_kernel(RhEntArgs a) {
     }
     if constexpr (!FILL) { if (t == 0) a.cnt[read] = done; }
   }
+}
+
+void rh_fill_entries(const RhEntArgs& e, int num_cus, hipStream_t stream) {
+  rh_launch(e, rh_entries_kernel<1, true>, rh_entries_kernel<kRwWaves, true>, num_cus, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the scan
@@ -334,27 +328,6 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
   }
 }
 
-// the two forms of a kernel under eight workgroups a CU
-template <class A, class K1, class K4>
-static void rh_launch(const A& a, K1 wave_form, K4 group_form, int num_cus, hipStream_t stream) {
-  const int64_t cap = (int64_t)num_cus * 8;
-  hipLaunchKernelGGL(wave_form, dim3(persistent_grid(a.nreads, kRwWaves, cap)), dim3(kRwThreads), 0, stream, a);
-  hipLaunchKernelGGL(group_form, dim3(persistent_grid(a.nreads, 1, cap)), dim3(kRwThreads), 0, stream, a);
-}
-
-static void rh_ent_args(RhEntArgs& a, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
-                        int64_t nsites, const int64_t* key) {
-  memset(&a, 0, sizeof(a));
-  a.nreads = nreads; a.cs = cs; a.start = start; a.roff = roff; a.score = score; a.nsites = nsites; a.key = key;
-}
-
-static void rh_stage_reads(Slab& slab, RhEntArgs& a, size_t tot) {
-  const size_t nr = (size_t)a.nreads, ns = (size_t)a.nsites;
-  slab.in(a.cs, nr * 4); slab.in(a.start, nr * 8); slab.in(a.roff, (nr + 1) * 8); slab.in(a.score, tot * 8); slab.in(a.key, ns * 8);
-}
-
-static bool rh_finite_in(double v, double lo, double hi) { return v >= lo && v <= hi; }   // (a NaN compares false)
-
 }  // namespace nmod
 
 using namespace nmod;
@@ -458,7 +431,7 @@ extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32
   if (nreads > 0) {
     if (nrows > 0) {
       NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
-      rh_launch(e, rh_entries_kernel<1, true>, rh_entries_kernel<kRwWaves, true>, num_cus, stream);
+      rh_fill_entries(e, num_cus, stream);
     }
     NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
     rh_launch(a, rh_hmm_kernel<1>, rh_hmm_kernel<kRwWaves>, num_cus, stream);

@@ -1080,6 +1080,54 @@ def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.
     return res
 
 
+VIT_OUTPUTS = L.VIT_ENTRY_FIELDS + L.VIT_READ_FIELDS + L.VIT_SITE_FIELDS
+
+
+def _vit_opts(pi, length, want):
+    """nmod_vit_opts from the Python arguments; ValueError for what the C entry refuses"""
+    pi, length = float(pi), float(length)
+    if not 1e-9 <= pi <= 1.0 - 1e-9:
+        raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
+    if not 1e-3 <= length <= 1e9:
+        raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
+    want = tuple(want)
+    if any(w not in VIT_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(VIT_OUTPUTS))
+    return L.make_vit_opts(pi, length), want
+
+
+def _vit_shapes(want, nrows, nreads, nsites):
+    kinds = dict(path=('uint8', nrows), site=('int32', nrows), delta=('float64', nrows), vit=('float64', nreads), status=('uint8', nreads),
+                 **{k: ('int32', nreads) for k in ('n_sites', 'n_mod', 'n_runs')}, **{k: ('int32', nsites) for k in L.VIT_SITE_FIELDS})
+    return {k: kinds[k] for k in VIT_OUTPUTS if k in want}
+
+
+def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, device=0):
+    """Per-read Viterbi decoding of read_hmm_host's chain (nmod_read_viterbi, include/nanomod_hip.h) on host-resident reads: the
+    arguments of read_hmm_host without call_post.  Returns a dict of numpy arrays, hoff and those named in `want`: per entry path (uint8,
+    the state on the most probable path), site (int32, the index into key), delta (float64, the max-marginal margin of state 1 over
+    state 0); per read n_sites, n_mod, n_runs (int32), vit (float64, the path's log-probability on ll's scale), status (uint8,
+    L.HMM_NO_SITE); per site site_n, site_mod (int32)."""
+    lib = L.load()
+    opts, want = _vit_opts(pi, length, want)
+    if hoff is None:
+        hoff = read_sites_host(cs, start, roff, score, key, device)
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
+    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
+    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
+        raise ValueError('hoff must start at 0 and never decrease')
+    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
+    shapes = _vit_shapes(want, nrows, nreads, key.shape[0])
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_vit_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_viterbi', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
+    res['hoff'] = hoff
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1651,6 +1699,23 @@ class DeviceDetector:
         o = L.make_hmm_out(**{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
         _call(self.lib, 'nmod_read_hmm', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
+        return res
+
+    def read_viterbi(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, out=None):
+        """Per-read Viterbi decoding of read_hmm's chain (nmod_read_viterbi, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising or reading anything back: the arguments of read_hmm without call_post.  Returns a dict of CUDA tensors, those
+        named in `want`: per entry path (uint8), site (int32), delta (float64); per read n_sites, n_mod, n_runs (int32), vit (float64),
+        status (uint8, L.HMM_NO_SITE); per site site_n, site_mod (int32).  out: such a dict from an earlier call of the same shape."""
+        torch = self.torch
+        opts, want = _vit_opts(pi, length, want)
+        nreads, shared = self._site_reads('read_viterbi', cs, start, roff, score, key)
+        _cuda_vecs('read_viterbi', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
+        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
+        shapes = _vit_shapes(want, nrows, nreads, key.numel())
+        res = self._outputs(out, shapes, 'read_viterbi')
+        o = L.make_vit_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_viterbi', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

@@ -471,9 +471,10 @@ def write_site_linkage(path, pairs):
         f.writelines(fmt % row for row in zip(*cols))
 
 
-def read_domains(hoff, site, state, post, site_pos):
+def read_domains(hoff, site, state, post, site_pos, delta=None):
     """The runs of consecutive entries in state 1 of every read, from nmod_read_hmm's per-entry tracks: a dict of arrays, one entry per
-    run: read, first, last (the positions of its first and last site), n_sites and mean_post"""
+    run: read, first, last (the positions of its first and last site), n_sites and mean_post.  With nmod_read_viterbi's tracks (state
+    its path, delta its margins) also min_delta, the smallest margin inside the run; post may then be None (mean_post NaN)."""
     hoff, state = np.asarray(hoff, np.int64), np.asarray(state)
     n = len(state)
     one = state == 1
@@ -482,14 +483,19 @@ def read_domains(hoff, site, state, post, site_pos):
     begins, ends = row == hoff[read_of], row == hoff[read_of + 1] - 1
     first = np.flatnonzero(one & (begins | ~np.concatenate(([False], one[:-1]))))
     last = np.flatnonzero(one & (ends | ~np.concatenate((one[1:], [False]))))
-    sums = np.add.reduceat(np.concatenate((np.asarray(post, np.float64), [0.0])), np.stack((first, last + 1), 1).ravel())[::2] if len(first) else np.zeros(0)
+    post = np.full(n, np.nan) if post is None else np.asarray(post, np.float64)
+    sums = np.add.reduceat(np.concatenate((post, [0.0])), np.stack((first, last + 1), 1).ravel())[::2] if len(first) else np.zeros(0)
     pos = np.asarray(site_pos, np.int64)[np.asarray(site, np.int64)]
     count = last - first + 1
-    return dict(read=read_of[first], first=pos[first], last=pos[last], n_sites=count, mean_post=sums / count)
+    res = dict(read=read_of[first], first=pos[first], last=pos[last], n_sites=count, mean_post=sums / count)
+    if delta is not None:
+        edges = np.stack((first, last + 1), 1).ravel()
+        res['min_delta'] = np.minimum.reduceat(np.concatenate((np.asarray(delta, np.float64), [np.inf])), edges)[::2] if len(first) else np.zeros(0)
+    return res
 
 
 def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length=200.0, fit_length=None, call_post=0.9, window='kmer',
-                     rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print):
+                     rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print, decode='posterior'):
     """Per-read two-state HMM smoothing of the window sums at candidate sites (K19, nmod_read_sites_count / nmod_read_hmm): along each
     molecule, where are the modified stretches, and what is the call at a weak site once its neighbours on the same read are taken into
     account?  The optional rescaling (K11), the window sums (K13) and the candidate sites exactly as in cooccur_reads_llr; then, read by
@@ -503,7 +509,16 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
       reads: index, chrom, strand, n_sites, n_mod, n_can, n_runs, ll, ll_indep, status (L.HMM_NO_SITE);
       entries: hoff (int64[nreads + 1]), site (the index into `sites`), post, state;
       sites: chrom, strand, pos (0-based), n, n_mod, n_can, share = n_mod / (n_mod + n_can) (NaN without a called entry);
-      domains: read_domains' runs.  One summary line goes to `log`."""
+      domains: read_domains' runs.  One summary line goes to `log`.
+    decode: 'posterior' (the above), 'viterbi' or 'both'.  'viterbi' and 'both' decode every read's most probable path as well (K20,
+    nmod_read_viterbi) at the same pi and length, chosen as above, and add the key `viterbi`, a dict laid out like the result itself:
+      reads: index, chrom, strand, n_sites, n_mod, n_runs, vit, status, and with 'both' path_logpost = vit - ll, the log of
+        P(the path | the read's scores), as the subtraction gives it;
+      entries: hoff, site, path, delta;  sites: chrom, strand, pos, n, n_mod, share = n_mod / n (NaN without an entry);
+      domains: read_domains' runs of the path with min_delta (mean_post: the posteriors' mean with 'both', NaN with 'viterbi').
+    'viterbi' leaves out reads, entries, sites and domains of the posterior decoding.  One more summary line goes to `log`."""
+    if decode not in ('posterior', 'viterbi', 'both'):
+        raise ValueError("decode must be 'posterior', 'viterbi' or 'both', not %r" % (decode,))
     setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
     site_alpha = engine._check_alpha(site_alpha)
     _sites_by_stoich(sites)
@@ -525,10 +540,17 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         for v in grid:
             profile.append((v, math.fsum(det.read_hmm(*shared, hoff, nrows, pi=pi, length=v, call_post=call_post, want=('ll',))['ll'].cpu().tolist())))
         length = max(profile, key=lambda p: p[1])[0]
-    res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post)
-    res = {f: v.cpu().numpy() for f, v in res.items()}
     key = d_key.cpu().numpy()
     nm = np.array(names, dtype=str)
+    vit = None
+    if decode != 'posterior':
+        vit = {f: v.cpu().numpy() for f, v in det.read_viterbi(*shared, hoff, nrows, pi=pi, length=length).items()}
+    if decode == 'viterbi':
+        out = dict(pi=pi, length=length, profile=profile)
+        out['viterbi'] = _viterbi_result(vit, hoff.cpu().numpy(), key, nm, reads, nreads, None, None, pi, length, log)
+        return out
+    res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post)
+    res = {f: v.cpu().numpy() for f, v in res.items()}
     called = (res['site_mod'] + res['site_can']).astype(np.float64)
     with np.errstate(invalid='ignore', divide='ignore'):
         share = np.where(called > 0, res['site_mod'] / called, np.nan)
@@ -541,7 +563,28 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
     log('readhmm: %d read(s), %d candidate site(s), %d entr%s; pi %.6g, length %g%s; %d modified and %d canonical at posterior %g, %d domain(s) on %d read(s)'
         % (nreads, len(key), nrows, 'y' if nrows == 1 else 'ies', pi, length, '' if grid is None else ' (the best of %d)' % len(grid),
            int(table['n_mod'].sum()), int(table['n_can'].sum()), float(call_post), len(domains['read']), int((table['n_runs'] > 0).sum())))
-    return dict(pi=pi, length=length, profile=profile, reads=table, entries=entries, sites=out_sites, domains=domains)
+    out = dict(pi=pi, length=length, profile=profile, reads=table, entries=entries, sites=out_sites, domains=domains)
+    if vit is not None:
+        out['viterbi'] = _viterbi_result(vit, entries['hoff'], key, nm, reads, nreads, res['ll'], res['post'], pi, length, log)
+    return out
+
+
+def _viterbi_result(vit, hoff, key, nm, reads, nreads, ll, post, pi, length, log):
+    """smooth_reads_llr's `viterbi` entry from nmod_read_viterbi's outputs (ll, post: nmod_read_hmm's, or None)"""
+    with np.errstate(invalid='ignore', divide='ignore'):
+        share = np.where(vit['site_n'] > 0, vit['site_mod'] / vit['site_n'].astype(np.float64), np.nan)
+    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                 pos=key & ((1 << 40) - 1), n=vit['site_n'], n_mod=vit['site_mod'], share=share)
+    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
+                 **{f: vit[f] for f in L.VIT_READ_FIELDS})
+    if ll is not None:
+        table['path_logpost'] = vit['vit'] - ll
+    entries = dict(hoff=hoff, site=vit['site'], path=vit['path'], delta=vit['delta'])
+    domains = read_domains(hoff, vit['site'], vit['path'], post, sites['pos'], delta=vit['delta'])
+    log('readhmm: Viterbi paths at pi %.6g, length %g: %d modified of %d entr%s, %d domain(s) on %d read(s)'
+        % (pi, length, int(table['n_mod'].sum()), len(vit['path']), 'y' if len(vit['path']) == 1 else 'ies', len(domains['read']),
+           int((table['n_runs'] > 0).sum())))
+    return dict(reads=table, entries=entries, sites=sites, domains=domains)
 
 
 def write_read_hmm(path, res):
@@ -557,14 +600,19 @@ def write_read_hmm(path, res):
 
 def write_read_domains(path, res):
     """<FileID>_read_domains.txt: per run of modified entries 'read chrom strand first+1 last+1 n_sites mean_post' as
-    '%d %s %s %d %d %d %.6f' (the positions 1-based; `res` of smooth_reads_llr)"""
+    '%d %s %s %d %d %d %.6f' (the positions 1-based; `res` of smooth_reads_llr).  With its `viterbi` entry as `res`
+    (<FileID>_read_domains_viterbi.txt) a last column min_delta follows, '%.6f' ('nan' as Python spells it for a mean_post without
+    posteriors)"""
     d, t = res['domains'], res['reads']
     read = np.asarray(d['read'], np.int64)
     cols = [read.tolist(), np.asarray(t['chrom']).astype(str)[read].tolist(), np.asarray(t['strand']).astype(str)[read].tolist(),
             (np.asarray(d['first'], np.int64) + 1).tolist(), (np.asarray(d['last'], np.int64) + 1).tolist(), np.asarray(d['n_sites']).tolist(),
             np.asarray(d['mean_post']).tolist()]
+    if 'min_delta' in d:
+        cols.append(np.asarray(d['min_delta']).tolist())
+    fmt = '%d %s %s %d %d %d %.6f' + (' %.6f' if 'min_delta' in d else '') + '\n'
     with open(path, 'w') as f:
-        f.writelines('%d %s %s %d %d %d %.6f\n' % row for row in zip(*cols))
+        f.writelines(fmt % row for row in zip(*cols))
 
 
 def write_site_hmm(path, res):
@@ -575,3 +623,25 @@ def write_site_hmm(path, res):
            [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'n_can', 'share')]
     with open(path, 'w') as f:
         f.writelines('%s %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
+
+
+def write_read_viterbi(path, res):
+    """<FileID>_read_viterbi.txt: per entry 'read site chrom strand pos+1 path delta' as '%d %d %s %s %d %d %.6f' (site: the index into
+    the candidate sites; the position 1-based; `res`: the `viterbi` entry of smooth_reads_llr)"""
+    e, s = res['entries'], res['sites']
+    hoff, site = np.asarray(e['hoff'], np.int64), np.asarray(e['site'], np.int64)
+    read = np.searchsorted(hoff, np.arange(len(site)), 'right') - 1
+    cols = [read.tolist(), site.tolist(), np.asarray(s['chrom']).astype(str)[site].tolist(), np.asarray(s['strand']).astype(str)[site].tolist(),
+            (np.asarray(s['pos'], np.int64)[site] + 1).tolist(), np.asarray(e['path']).tolist(), np.asarray(e['delta'], np.float64).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%d %d %s %s %d %d %.6f\n' % row for row in zip(*cols))
+
+
+def write_site_viterbi(path, res):
+    """<FileID>_site_viterbi.txt: per candidate site 'chrom strand pos+1 n n_mod share' as '%s %s %d %d %d %.6f' (the position 1-based;
+    share 'nan' where no read has an entry; `res`: the `viterbi` entry of smooth_reads_llr)"""
+    s = res['sites']
+    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()] + \
+           [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'share')]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %d %d %.6f\n' % row for row in zip(*cols))
