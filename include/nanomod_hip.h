@@ -1120,7 +1120,8 @@ int nmod_pair_linkage(const nmod_params* prm, int64_t npairs, const double* sa, 
  *     start at 0, ascend and end at nrows.
  *   Scratch: 32 B per row (position, score, forward vector), 36 B where site is not asked for.
  * Stops at: two states; one (pi, length) for all sites and reads, no per-site prior; posterior decoding (the most probable path is
- * nmod_read_viterbi's, below); no Baum-Welch: length is chosen on a grid by the caller and pi is given; the reads are independent and
+ * nmod_read_viterbi's, below); no Baum-Welch: pi and length are given (nmod_read_hmm_grad, below, is what a maximum-likelihood fit of
+ * both is built on; a grid of lengths is the caller's other choice); the reads are independent and
  * both k-mer tables are taken as right; one (chrom, strand) per read. */
 #define NMOD_HMM_CHUNK 4                   /* steps of a tile a thread owns */
 #define NMOD_HMM_WAVE_MAX 1024             /* entries of a read up to which one wave computes it (a workgroup of four beyond) */
@@ -1182,7 +1183,7 @@ int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, con
  *   Scratch: at most 33 B per row (position, score, forward vector, one byte of back-pointers), 37 B where site is not asked for; 16 B
  *     less without delta, 1 B less without the traceback.
  * Stops at: the single best path, no k-best list and no minimum-length constraint on a domain; the model is nmod_read_hmm's with all
- * its limits (two states, one (pi, length), no Baum-Welch). */
+ * its limits (two states, one (pi, length), no Baum-Welch: both are given, or fitted through nmod_read_hmm_grad, below). */
 typedef struct nmod_vit_opts { int32_t struct_size, reserved; double pi, length; } nmod_vit_opts;
 typedef struct nmod_vit_out { int32_t struct_size; int32_t reserved;
   uint8_t* path; int32_t* site; double* delta;                          /* [nrows] */
@@ -1192,6 +1193,54 @@ typedef struct nmod_vit_out { int32_t struct_size; int32_t reserved;
 int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                       const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                       const nmod_vit_opts* opts, const nmod_vit_out* out);
+
+/* The gradient of nmod_read_hmm's log-likelihood in the chain's two parameters, per read and summed over the batch: what a maximum-
+ * likelihood fit of (pi, length) needs from the device, one call per evaluation (K21; the reference project has no such step).  The
+ * fit itself, a few Newton-like steps on eight numbers, is the caller's (nanomod_amd/readllr.py: fit_hmm).
+ *   Inputs, word for word nmod_read_hmm's: the reads, score, key, hoff and nrows, the ENTRIES of a read, opts->pi and opts->length with
+ *     their ranges, q = 1 - pi formed once on the host, e_j, T_j, rho, eps, r = d / length, the memspaces, the stream contract, the
+ *     NULL-skips-an-output rule and the refusals (there is no call_post); a row outside its read's hoff range is skipped.
+ *   Parameters.  eta = logit(pi) and lam = ln(length): the scales on which both are unbounded and their likelihood is closest to a
+ *     quadratic.  pi q is formed once on the host.
+ *   Definition (Fisher's identity: the gradient of ll is the posterior mean of the gradient of the complete-data log-likelihood, a sum
+ *     over the initial law and the transitions).  a_j = the forward vector of entry j as nmod_read_hmm's forward pass stores it, b_j =
+ *     the backward vector at entry j as its backward pass replays it (ORDER there).  For j = 1 .. m - 1, with y0 = e_j0 b_j0,
+ *     y1 = e_j1 b_j1, A = a_(j-1) and T = T_j:
+ *         Z   = A0 (t00 y0 + t01 y1) + A1 (t10 y0 + t11 y1)
+ *         P_j = eps (A0 + A1) (y1 - y0) / Z                        (d/d pi of the transition's logarithm, averaged)
+ *         L_j = rho r (pi A0 - q A1) (y0 - y1) / Z                 (the same in lam: d rho / d lam = rho r)
+ *     each evaluated left to right as written, no fused operation; post_0 = a_01 b_01 / (a_00 b_00 + a_01 b_01) as nmod_read_hmm forms it;
+ *         g_eta = (post_0 - pi) + (pi q) SUM_j P_j,     abs_eta = |post_0 - pi| + (pi q) SUM_j |P_j|,
+ *         g_lam = SUM_j L_j,                            abs_lam = SUM_j |L_j|.
+ *     Both terms are ratios that are homogeneous of degree 0 in a and in b: the exponents the scan drops do not enter.  No division by
+ *     an entry of T occurs.  abs_eta and abs_lam are what an error bound of g_eta and g_lam is relative to (tests/hmm_fit_ref.py).
+ *     A Z that underflows (emissions of opposite sign beyond +-700 at every state) makes the terms unspecified, as it does post.
+ *   Per read (double[nreads] each): ll, bit for bit nmod_read_hmm's for the same inputs; g_eta, g_lam, abs_eta, abs_lam; status (uint8):
+ *     NMOD_HMM_NO_SITE when m = 0 (every value 0).  A read of one entry has g_lam = 0.
+ *   ORDER.  The forward pass is nmod_read_hmm's.  The backward pass is its scan; the term of transition j is formed by the thread that
+ *     replays step k = m - 1 - j, which adds its terms in the order of its steps (descending j) over all tiles into one word per sum;
+ *     then the library's wave sum, then the waves in order, as S.  The bits depend on the read and the sites alone, not on the batch,
+ *     the order of the reads, the memspace or the outputs asked for.  No float atomics.
+ *   sums (double[8]): SUM ll, SUM g_eta, SUM g_lam, SUM g_eta^2, SUM g_eta g_lam, SUM g_lam^2 over the reads, the number of reads with
+ *     m >= 1 and the number of entries (as doubles, exact below 2^53).  One workgroup of 256 threads in a second kernel on the same
+ *     stream: thread t adds reads t, t + 256, ... in ascending order (a product is rounded, then added), then the wave sum of every
+ *     word and the four waves in order.  The bits depend on the per-read values and their order alone.  The three matrix words are the
+ *     outer-product (BHHH) estimate of the information in (eta, lam).
+ *   nmod_read_hmm_grad(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, opts, out).  NMOD_MEM_DEVICE: everything is
+ *     enqueued on prm->stream, no host read and no synchronisation.  NMOD_MEM_HOST: one staged copy.  nreads == 0: NMOD_OK, sums all 0.
+ *     NMOD_ERR_INVALID_ARG before any device work: nmod_read_hmm's list without call_post.
+ *   Scratch: 36 B per row (position, score, forward vector, site), and 8 B per read for each of ll, g_eta, g_lam not asked for.
+ * Stops at: one (pi, length) for all reads and sites; the emissions and both k-mer tables are taken as right (no gradient in them);
+ * the outer-product information, not the observed Hessian: standard errors from it are right at the model and in large samples only;
+ * the caller's intervals are Wald intervals on the logit and log scales; the first derivative only. */
+typedef struct nmod_hmm_grad_opts { int32_t struct_size, reserved; double pi, length; } nmod_hmm_grad_opts;
+typedef struct nmod_hmm_grad_out { int32_t struct_size; int32_t reserved;
+  double *ll, *g_eta, *g_lam, *abs_eta, *abs_lam; uint8_t* status;     /* [nreads] */
+  double* sums;                                                         /* [8] */
+} nmod_hmm_grad_out;
+int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                       const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                       const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out);
 
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One

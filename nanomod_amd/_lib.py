@@ -388,6 +388,28 @@ def make_vit_opts(pi=0.5, length=200.0):
 make_vit_out = functools.partial(make_out, NmodVitOut)
 
 
+HMM_GRAD_READ_FIELDS = ('ll', 'g_eta', 'g_lam', 'abs_eta', 'abs_lam', 'status')   # nmod_read_hmm_grad; status: NMOD_HMM_NO_SITE
+HMM_GRAD_SUMS = ('ll', 'g_eta', 'g_lam', 'g_eta2', 'g_eta_lam', 'g_lam2', 'n_reads', 'n_entries')   # the words of its `sums`
+
+
+class NmodHmmGradOpts(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('pi', C.c_double), ('length', C.c_double)]
+
+
+class NmodHmmGradOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in HMM_GRAD_READ_FIELDS + ('sums',)]
+
+
+def make_hmm_grad_opts(pi=0.5, length=200.0):
+    o = NmodHmmGradOpts()
+    o.struct_size = C.sizeof(NmodHmmGradOpts)
+    o.pi, o.length = float(pi), float(length)
+    return o
+
+
+make_hmm_grad_out = functools.partial(make_out, NmodHmmGradOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -471,6 +493,8 @@ _SIGNATURES = {
                                 C.POINTER(NmodHmmOpts), C.POINTER(NmodHmmOut)]),
     'nmod_read_viterbi': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.POINTER(NmodVitOpts), C.POINTER(NmodVitOut)]),
+    'nmod_read_hmm_grad': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.POINTER(NmodHmmGradOpts), C.POINTER(NmodHmmGradOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -251,6 +251,10 @@ def build_parser():
                     "candidate sites' estimated shares")
     rh.add_argument('--hmmLength', type=float, default=200.0, help='the correlation length in bases, 1e-3 .. 1e9')
     rh.add_argument('--fitLength', default=None, help='LEN,LEN,...: the length among these with the largest log-likelihood over all reads is used')
+    rh.add_argument('--fitHmm', type=int, default=0, choices=[0, 1], help='1: pi and length are fitted by maximum likelihood over all reads, from '
+                    '--hmmPi (or its default) and --hmmLength; the trace and the estimates with their intervals are written to <FileID>_hmm_fit.txt; '
+                    'not together with --fitLength')
+    rh.add_argument('--fixPi', type=int, default=0, choices=[0, 1], help='--fitHmm 1: keep pi and fit the length alone')
     rh.add_argument('--callPost', type=float, default=0.9, help='the posterior from which an entry is called, inside (0.5, 1)')
     rh.add_argument('--decode', default='posterior', choices=['posterior', 'viterbi', 'both'], help="'posterior': the marginal calls; 'viterbi': "
                     'the most probable path of every read, written to <FileID>_read_viterbi.txt, _read_domains_viterbi.txt and _site_viterbi.txt; '
@@ -389,6 +393,10 @@ def validate_readhmm(a):
         grid = parse_fit_length(a.fitLength)
         if grid is None or not all(1e-3 <= v <= 1e9 for v in grid):
             errs.append('Error: --fitLength should be LEN,LEN,... with every length in 1e-3 .. 1e9')
+    if a.fitHmm and a.fitLength is not None:
+        errs.append('Error: --fitHmm 1 and --fitLength exclude each other')
+    if a.fixPi and not a.fitHmm:
+        errs.append('Error: --fixPi 1 needs --fitHmm 1')
     if not 0.5 < a.callPost < 1.0:
         errs.append('Error: --callPost should lie between 0.5 and 1, both excluded')
     if not 0.0 < a.siteAlpha <= 1.0:
@@ -409,9 +417,12 @@ def run_readhmm(a, log=print):
                                    sites=sites, pi=a.hmmPi, length=a.hmmLength, fit_length=None if a.fitLength is None else parse_fit_length(a.fitLength),
                                    call_post=a.callPost, window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None,
                                    site_alpha=a.siteAlpha, thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
-                                   log=(lambda *x: None) if quiet else log, **({} if a.decode == 'posterior' else {'decode': a.decode}))
+                                   log=(lambda *x: None) if quiet else log, **({} if a.decode == 'posterior' else {'decode': a.decode}),
+                                   **({'fit': 'mle', 'fix_pi': bool(a.fixPi)} if a.fitHmm else {}))
     os.makedirs(a.outFolder, exist_ok=True)
     files = []
+    if a.fitHmm:
+        files.append(('_hmm_fit.txt', readllr.write_hmm_fit, 'The fit of pi and length is', res['fit']))
     if a.decode != 'viterbi':
         files += [('_read_hmm.txt', readllr.write_read_hmm, 'Read chains are', res), ('_read_domains.txt', readllr.write_read_domains, 'Read domains are', res),
                   ('_site_hmm.txt', readllr.write_site_hmm, 'Smoothed site counts are', res)]

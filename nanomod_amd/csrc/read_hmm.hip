@@ -1,5 +1,6 @@
-// nmod_read_sites_count / nmod_read_hmm — per read a two-state hidden Markov chain over the candidate sites it covers, emissions from the
-// window sums (K13's llr_win), evaluated by forward-backward as a scan of 2 x 2 non-negative matrices (K19).  The reference
+// nmod_read_sites_count / nmod_read_hmm / nmod_read_hmm_grad — per read a two-state hidden Markov chain over the candidate sites it covers,
+// emissions from the window sums (K13's llr_win), evaluated by forward-backward as a scan of 2 x 2 non-negative matrices (K19; K21 is the
+// same chain's log-likelihood with its gradient in the two parameters).  The reference
 // project has no such step; the definition is the one in include/nanomod_hip.h (tests/hmm_ref.py restates it).  The walk over the reads is
 // read_walk.hpp's, the site search and the offsets' scan are site_search.hpp's (shared with K16 / K18); all on the caller's stream:
 //   read_classify_kernel     (read_walk.hpp) a thread per read: the read's class, by its events for the entries, by its entries for the chain
@@ -9,6 +10,9 @@
 //                            entry enqueues it too, through read_entries.hpp's rh_fill_entries)
 //   rh_hmm_kernel<1>         a wave per read of up to NMOD_HMM_WAVE_MAX entries, four waves a workgroup
 //   rh_hmm_kernel<4>         a workgroup of four waves per longer read
+//   rh_grad_kernel<1>, <4>   nmod_read_hmm_grad (K21): the same two forms, the same forward pass; the backward pass forms the terms of the
+//                            log-likelihood's gradient in logit(pi) and ln(length) instead of the posteriors
+//   rh_grad_sums_kernel      its batch sums: one workgroup, a fixed order
 // The chain of a read is two passes of one scan, rh_tile<., BWD>, over tiles of NMOD_HMM_CHUNK entries a thread: a thread forms the step
 // matrices of its chunk and multiplies them in order, the lanes of a wave take the inclusive scan of those products (six shuffle steps on
 // four doubles and an exponent), a workgroup hands the waves' totals on through LDS, and the thread replays its chunk as a row vector from
@@ -328,6 +332,124 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the gradient (K21)
+
+// nmod_read_hmm_grad: the chain's arguments (h.backward set: the forward vectors are stored; h.out unused) and the outputs of its own
+struct RgArgs {
+  int64_t nreads;                                 // (rh_launch reads it)
+  RhArgs h;
+  double piq;                                     // pi q, formed once on the host
+  nmod_hmm_grad_out out;                          // ll, g_eta and g_lam never NULL here: the slab's where the caller asked for none
+};
+
+// The forward pass is rh_hmm_kernel's, tile for tile (ll has its bits).  The backward pass is the same scan; at step k, entry j = m - 1 - k,
+// the lambda holds b_j and reads a_(j-1), which the forward pass left in the slab: the term of transition j (Fisher's identity) needs
+// nothing else.  A thread adds its terms in the order of its steps, then the sums of the read as S's
+template <int WAVES>
+__global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
+  __shared__ unsigned sh_item;
+  __shared__ double sh_sum[kRwWaves];
+  __shared__ RhShared sh_scan;
+  constexpr int CLS = WAVES == 1 ? 0 : 1;
+  constexpr int T = WAVES * 64;
+  constexpr int64_t TS = (int64_t)T * kHmmChunk;
+  const int lane = threadIdx.x & 63;
+  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
+  const RhArgs& a = g.h;
+  const unsigned cnt = a.w.count[CLS];
+  const nmod_hmm_grad_out& o = g.out;
+  auto read_sum = [&](double v) {
+    if constexpr (WAVES == 1) return wave_sum_f64(v); else return block_sum_f64<WAVES>(v, sh_sum);
+  };
+  for (;;) {
+    const unsigned item = draw_read<WAVES>(a.w, sh_item);
+    if (item >= cnt) break;
+    const int64_t read = (int64_t)a.w.list[CLS][item];
+    const int64_t base = a.hoff[read], m = a.hoff[read + 1] - base;
+    if (m <= 0 || base < 0 || base > a.nrows - m) {             // no entry (or offsets that are not the rows': skipped)
+      if (t == 0) {
+        o.ll[read] = 0.0; o.g_eta[read] = 0.0; o.g_lam[read] = 0.0;
+        if (o.abs_eta) o.abs_eta[read] = 0.0;
+        if (o.abs_lam) o.abs_lam[read] = 0.0;
+        if (o.status) o.status[read] = NMOD_HMM_NO_SITE;
+      }
+      continue;
+    }
+    const double* xs = a.xs + 2 * base;
+    double* alpha = a.alpha + 2 * base;
+
+    // forward: the vectors and the sum of the positive scores, a thread's entries in ascending order
+    double s_pos = 0.0;
+    Vec2 fw{a.q, a.pi, 0};
+    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+      fw = rh_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
+        alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1;
+        s_pos += fmax(xs[2 * k + 1], 0.0);
+      });
+    }
+    const double pos = read_sum(s_pos);
+    const double ll = (log(fw.x0 + fw.x1) + (double)fw.e * kLn2) + pos;
+
+    // the forward vectors of the other lanes (waves) are written
+    if constexpr (WAVES > 1) __syncthreads(); else __threadfence_block();
+
+    // backward: step k is entry j = m - 1 - k; the term of transition j for j >= 1, the posterior of the first entry at j = 0
+    double s_p = 0.0, s_l = 0.0, s_ap = 0.0, s_al = 0.0, s_post = 0.0;
+    Vec2 bw{1.0, 1.0, 0};
+    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+      bw = rh_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
+        const int64_t j = m - 1 - k;
+        if (j == 0) {
+          const double p0 = alpha[0] * x.x0, p1 = alpha[1] * x.x1;
+          s_post = p1 / (p0 + p1);
+          return;
+        }
+        double e0, e1;
+        rh_emission(xs[2 * j + 1], e0, e1);
+        const double r = (xs[2 * j] - xs[2 * (j - 1)]) / a.length;
+        const double rho = exp(-r), eps = -expm1(-r);
+        const double t00 = a.q + a.pi * rho, t01 = a.pi * eps, t10 = a.q * eps, t11 = a.pi + a.q * rho;
+        const double y0 = e0 * x.x0, y1 = e1 * x.x1;
+        const double a0 = alpha[2 * (j - 1)], a1 = alpha[2 * (j - 1) + 1];
+        const double z = a0 * (t00 * y0 + t01 * y1) + a1 * (t10 * y0 + t11 * y1);
+        const double p = eps * (a0 + a1) * (y1 - y0) / z;
+        const double l = rho * r * (a.pi * a0 - a.q * a1) * (y0 - y1) / z;
+        s_p += p; s_l += l; s_ap += fabs(p); s_al += fabs(l);
+      });
+    }
+    // (the posterior lives in one thread and the others add 0: its sum is the value itself)
+    const double sum_p = read_sum(s_p), sum_l = read_sum(s_l), sum_ap = read_sum(s_ap), sum_al = read_sum(s_al), post0 = read_sum(s_post);
+    if (t == 0) {
+      const double first = post0 - a.pi;
+      o.ll[read] = ll;
+      o.g_eta[read] = first + g.piq * sum_p;
+      o.g_lam[read] = sum_l;
+      if (o.abs_eta) o.abs_eta[read] = fabs(first) + g.piq * sum_ap;
+      if (o.abs_lam) o.abs_lam[read] = sum_al;
+      if (o.status) o.status[read] = 0;
+    }
+  }
+}
+
+// The batch sums in one workgroup of 256: thread t adds reads t, t + 256, ... in ascending order (a product is formed, then added),
+// then the block sum of every word.  Words 6 and 7: the reads with an entry and the entries, counted as doubles (exact below 2^53)
+__global__ __launch_bounds__(256) void rh_grad_sums_kernel(int64_t nreads, const int64_t* hoff, int64_t nrows, const double* ll, const double* g_eta,
+                                                           const double* g_lam, double* sums) {
+  __shared__ double sh[4];
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int64_t r = threadIdx.x; r < nreads; r += 256) {
+    const double l = ll[r], e = g_eta[r], v = g_lam[r];
+    s[0] += l; s[1] += e; s[2] += v; s[3] += e * e; s[4] += e * v; s[5] += v * v;
+    const int64_t base = hoff[r], m = hoff[r + 1] - base;
+    if (!(m <= 0 || base < 0 || base > nrows - m)) { s[6] += 1.0; s[7] += (double)m; }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const double v = block_sum_f64<4>(s[i], sh);
+    if (threadIdx.x == 0) sums[i] = v;
+  }
+}
+
 }  // namespace nmod
 
 using namespace nmod;
@@ -436,5 +558,71 @@ extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32
     NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
     rh_launch(a, rh_hmm_kernel<1>, rh_hmm_kernel<kRwWaves>, num_cus, stream);
   }
+  return launches_end(slab, stream);
+}
+
+extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                  const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                                  const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
+  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!opts || opts->struct_size != (int32_t)sizeof(nmod_hmm_grad_opts)) return NMOD_ERR_INVALID_ARG;
+  if (!out || out->struct_size != (int32_t)sizeof(nmod_hmm_grad_out)) return NMOD_ERR_INVALID_ARG;
+  if (!rh_finite_in(opts->pi, 1e-9, 1.0 - 1e-9) || !rh_finite_in(opts->length, 1e-3, 1e9)) return NMOD_ERR_INVALID_ARG;
+  if (nrows < 0 || nrows > (int64_t)INT32_MAX || (nreads > 0 && !hoff)) return NMOD_ERR_INVALID_ARG;
+  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, nullptr, 0)) return NMOD_ERR_INVALID_ARG;
+  const bool host = prm->memspace == NMOD_MEM_HOST;
+  if (host && nreads > 0 && (hoff[0] != 0 || !csr_offsets_ok(hoff, nreads) || hoff[nreads] != nrows)) return NMOD_ERR_INVALID_ARG;
+  if (nrows > 0 && (nreads == 0 || nsites == 0)) return NMOD_ERR_INVALID_ARG;
+  const size_t nr = (size_t)nreads, nw = (size_t)nrows;
+  if (host && nreads == 0) {                                    // nothing to enqueue: the sums of no read
+    if (out->sums) memset(out->sums, 0, 8 * sizeof(double));
+    return NMOD_OK;
+  }
+  int num_cus = 0;
+  const int rc = select_device(prm, &num_cus);
+  if (rc != NMOD_OK) return rc;
+  hipStream_t stream = (hipStream_t)prm->stream;
+  const size_t tot = host ? (size_t)roff[nreads] : 0;
+
+  RhEntArgs e;
+  rh_ent_args(e, nreads, cs, start, roff, score, nsites, key);
+  e.hoff = hoff; e.nrows = nrows;
+  RgArgs g;
+  memset(&g, 0, sizeof(g));
+  RhArgs& a = g.h;
+  g.nreads = a.nreads = nreads; a.nrows = nrows; a.nsites = nsites;
+  a.pi = opts->pi; a.q = 1.0 - opts->pi; a.length = opts->length;
+  a.backward = true;
+  g.piq = a.pi * a.q;
+  g.out = *out;
+  nmod_hmm_grad_out& o = g.out;
+
+  // one slab: the read lists of both walks, per row the position and the score, the forward vector and the site; the per-read values
+  // the sums are taken from where the caller asked for the sums without them; for the host entry the inputs and outputs as well
+  Slab slab(host);
+  const ReadListSpace by_events(slab, nr), by_entries(slab, nr);
+  const size_t o_xs = slab.take(nw * 16), o_alpha = slab.take(nw * 16), o_site = slab.take(nw * 4);
+  const size_t o_ll = o.ll ? 0 : slab.take(nr * 8), o_ge = o.g_eta ? 0 : slab.take(nr * 8), o_gl = o.g_lam ? 0 : slab.take(nr * 8);
+  rh_stage_reads(slab, e, tot);
+  slab.in(e.hoff, (nr + 1) * 8);
+  slab.out(o.ll, nr * 8); slab.out(o.g_eta, nr * 8); slab.out(o.g_lam, nr * 8); slab.out(o.abs_eta, nr * 8); slab.out(o.abs_lam, nr * 8);
+  slab.out(o.status, nr); slab.out(o.sums, 8 * sizeof(double));
+  NMOD_HIP(slab.commit(stream, prm->device));
+  e.xs = slab.at<double>(o_xs);
+  e.site = slab.at<int32_t>(o_site);
+  a.hoff = e.hoff; a.xs = e.xs; a.site = e.site; a.alpha = slab.at<double>(o_alpha);
+  if (!o.ll) o.ll = slab.at<double>(o_ll);
+  if (!o.g_eta) o.g_eta = slab.at<double>(o_ge);
+  if (!o.g_lam) o.g_lam = slab.at<double>(o_gl);
+
+  if (nreads > 0) {
+    if (nrows > 0) {
+      NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
+      rh_fill_entries(e, num_cus, stream);
+    }
+    NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
+    rh_launch(g, rh_grad_kernel<1>, rh_grad_kernel<kRwWaves>, num_cus, stream);
+  }
+  if (o.sums) hipLaunchKernelGGL(rh_grad_sums_kernel, dim3(1), dim3(256), 0, stream, nreads, a.hoff, nrows, o.ll, o.g_eta, o.g_lam, o.sums);
   return launches_end(slab, stream);
 }

@@ -1128,6 +1128,53 @@ def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=
     return res
 
 
+HMM_GRAD_OUTPUTS = L.HMM_GRAD_READ_FIELDS + ('sums',)
+
+
+def _hmm_grad_opts(pi, length, want):
+    """nmod_hmm_grad_opts from the Python arguments; ValueError for what the C entry refuses"""
+    pi, length = float(pi), float(length)
+    if not 1e-9 <= pi <= 1.0 - 1e-9:
+        raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
+    if not 1e-3 <= length <= 1e9:
+        raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
+    want = tuple(want)
+    if any(w not in HMM_GRAD_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(HMM_GRAD_OUTPUTS))
+    return L.make_hmm_grad_opts(pi, length), want
+
+
+def _hmm_grad_shapes(want, nreads):
+    kinds = dict({k: ('float64', nreads) for k in L.HMM_GRAD_READ_FIELDS}, status=('uint8', nreads), sums=('float64', len(L.HMM_GRAD_SUMS)))
+    return {k: kinds[k] for k in HMM_GRAD_OUTPUTS if k in want}
+
+
+def read_hmm_grad_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, device=0):
+    """The log-likelihood of read_hmm_host's chain and its gradient in eta = logit(pi) and lam = ln(length) (nmod_read_hmm_grad,
+    include/nanomod_hip.h) on host-resident reads: the arguments of read_hmm_host without call_post.  Returns a dict of numpy arrays, hoff
+    and those named in `want`: per read ll (read_hmm_host's, bit for bit), g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
+    L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS: the sums over the reads of ll, the gradient and its products, the reads with an
+    entry and the entries) — what readllr.fit_hmm takes per evaluation."""
+    lib = L.load()
+    opts, want = _hmm_grad_opts(pi, length, want)
+    if hoff is None:
+        hoff = read_sites_host(cs, start, roff, score, key, device)
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
+    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
+    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
+        raise ValueError('hoff must start at 0 and never decrease')
+    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
+    shapes = _hmm_grad_shapes(want, nreads)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_hmm_grad_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_hmm_grad', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
+    res['hoff'] = hoff
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1716,6 +1763,23 @@ class DeviceDetector:
         o = L.make_vit_out(**{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
         _call(self.lib, 'nmod_read_viterbi', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
+        return res
+
+    def read_hmm_grad(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, out=None):
+        """The log-likelihood of read_hmm's chain and its gradient in logit(pi) and ln(length) (nmod_read_hmm_grad, NMOD_MEM_DEVICE),
+        enqueued on the current stream without synchronising or reading anything back: the arguments of read_hmm without call_post.
+        Returns a dict of CUDA tensors, those named in `want`: per read ll, g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
+        L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS).  out: such a dict from an earlier call of the same shape."""
+        torch = self.torch
+        opts, want = _hmm_grad_opts(pi, length, want)
+        nreads, shared = self._site_reads('read_hmm_grad', cs, start, roff, score, key)
+        _cuda_vecs('read_hmm_grad', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
+        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
+        shapes = _hmm_grad_shapes(want, nreads)
+        res = self._outputs(out, shapes, 'read_hmm_grad')
+        o = L.make_hmm_grad_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_hmm_grad', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

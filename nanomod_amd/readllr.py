@@ -495,7 +495,8 @@ def read_domains(hoff, site, state, post, site_pos, delta=None):
 
 
 def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length=200.0, fit_length=None, call_post=0.9, window='kmer',
-                     rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print, decode='posterior'):
+                     rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print, decode='posterior', fit=None,
+                     fix_pi=False):
     """Per-read two-state HMM smoothing of the window sums at candidate sites (K19, nmod_read_sites_count / nmod_read_hmm): along each
     molecule, where are the modified stretches, and what is the call at a weak site once its neighbours on the same read are taken into
     account?  The optional rescaling (K11), the window sums (K13) and the candidate sites exactly as in cooccur_reads_llr; then, read by
@@ -516,9 +517,19 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         P(the path | the read's scores), as the subtraction gives it;
       entries: hoff, site, path, delta;  sites: chrom, strand, pos, n, n_mod, share = n_mod / n (NaN without an entry);
       domains: read_domains' runs of the path with min_delta (mean_post: the posteriors' mean with 'both', NaN with 'viterbi').
-    'viterbi' leaves out reads, entries, sites and domains of the posterior decoding.  One more summary line goes to `log`."""
+    'viterbi' leaves out reads, entries, sites and domains of the posterior decoding.  One more summary line goes to `log`.
+    fit: None, or 'mle': pi and length are fitted by maximum likelihood over all reads (K21, nmod_read_hmm_grad through fit_hmm) from
+    the pi and length chosen as above, on the device tensors already there, one call per evaluation; fix_pi keeps pi and fits length
+    alone.  The decoding uses the fitted values, the result gains the key `fit` (fit_hmm's dict) and one more line goes to `log`.
+    Not together with fit_length."""
     if decode not in ('posterior', 'viterbi', 'both'):
         raise ValueError("decode must be 'posterior', 'viterbi' or 'both', not %r" % (decode,))
+    if fit not in (None, 'mle'):
+        raise ValueError("fit must be None or 'mle', not %r" % (fit,))
+    if fit is not None and fit_length is not None:
+        raise ValueError('fit and fit_length exclude each other: the fit chooses the length itself')
+    if fix_pi and fit is None:
+        raise ValueError("fix_pi needs fit='mle'")
     setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
     site_alpha = engine._check_alpha(site_alpha)
     _sites_by_stoich(sites)
@@ -540,13 +551,21 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         for v in grid:
             profile.append((v, math.fsum(det.read_hmm(*shared, hoff, nrows, pi=pi, length=v, call_post=call_post, want=('ll',))['ll'].cpu().tolist())))
         length = max(profile, key=lambda p: p[1])[0]
+    fitted = None
+    if fit is not None:
+        fitted = fit_hmm(lambda p, v: det.read_hmm_grad(*shared, hoff, nrows, pi=p, length=v, want=('sums',))['sums'].cpu().tolist(), pi, length,
+                         fix_pi=fix_pi)
+        pi, length = fitted['pi'], fitted['length']
+        log('readhmm: maximum-likelihood fit: pi %.6g (%.6g .. %.6g), length %.6g (%.6g .. %.6g), log-likelihood %.6f; %d evaluation(s), %s; %s'
+            % (pi, fitted['pi_lo'], fitted['pi_hi'], length, fitted['length_lo'], fitted['length_hi'], fitted['ll'], fitted['n_eval'],
+               'converged' if fitted['converged'] else 'not converged', fitted['status']))
     key = d_key.cpu().numpy()
     nm = np.array(names, dtype=str)
     vit = None
     if decode != 'posterior':
         vit = {f: v.cpu().numpy() for f, v in det.read_viterbi(*shared, hoff, nrows, pi=pi, length=length).items()}
     if decode == 'viterbi':
-        out = dict(pi=pi, length=length, profile=profile)
+        out = dict(pi=pi, length=length, profile=profile, **({} if fitted is None else {'fit': fitted}))
         out['viterbi'] = _viterbi_result(vit, hoff.cpu().numpy(), key, nm, reads, nreads, None, None, pi, length, log)
         return out
     res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post)
@@ -564,9 +583,140 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         % (nreads, len(key), nrows, 'y' if nrows == 1 else 'ies', pi, length, '' if grid is None else ' (the best of %d)' % len(grid),
            int(table['n_mod'].sum()), int(table['n_can'].sum()), float(call_post), len(domains['read']), int((table['n_runs'] > 0).sum())))
     out = dict(pi=pi, length=length, profile=profile, reads=table, entries=entries, sites=out_sites, domains=domains)
+    if fitted is not None:
+        out['fit'] = fitted
     if vit is not None:
         out['viterbi'] = _viterbi_result(vit, entries['hoff'], key, nm, reads, nreads, res['ll'], res['post'], pi, length, log)
     return out
+
+
+HMM_PI_RANGE, HMM_LENGTH_RANGE = (1e-9, 1.0 - 1e-9), (1e-3, 1e9)      # nmod_read_hmm's ranges of pi and length
+FIT_MAX_HALVINGS = 20
+
+
+def _logit(p):
+    return math.log(p) - math.log1p(-p)
+
+
+def _expit(x):
+    return 1.0 / (1.0 + math.exp(-x)) if x >= 0.0 else math.exp(x) / (1.0 + math.exp(x))
+
+
+def fit_hmm(evaluate, pi0, length0, *, fix_pi=False, tol=1e-10, max_iter=50, ci_level=0.95):
+    """The maximum-likelihood fit of the read chain's pi and length (K21) by BHHH steps on eta = logit(pi) and lam = ln(length): a pure
+    host function.  evaluate(pi, length) returns the eight sums of nmod_read_hmm_grad (L.HMM_GRAD_SUMS) at those parameters: from the
+    device (DeviceDetector.read_hmm_grad(..., want=('sums',))) or from any restatement.
+    With g = (SUM g_eta, SUM g_lam) and H the 2 x 2 matrix of the summed products (the outer-product estimate of the information), the
+    step is H^-1 g and the criterion g . H^-1 g; the fit stops when the criterion is below `tol` (converged) or after `max_iter` steps.
+    A step is halved while SUM ll does not increase, at most 20 times; every trial is one evaluation.  The parameters are clamped to
+    nmod_read_hmm's ranges.  One parameter alone is fitted when fix_pi is set, when H's lam entry is 0 (no read has two entries), when
+    its eta entry is 0, or when H is singular to working precision (then pi alone); `status` says which and why.
+    Returns a dict: pi, length, eta, lam, ll (SUM ll at the result); se_eta, se_lam (from H^-1 at the result, NaN for a parameter that
+    was not fitted); pi_lo, pi_hi, length_lo, length_hi (Wald intervals at ci_level on the eta and lam scales, mapped back; the value
+    itself for a parameter that was not fitted); trace, a list of (pi, length, SUM ll, criterion) per iterate; n_eval; n_reads and
+    n_entries (the sums' last two words); converged; status."""
+    from statistics import NormalDist
+    pi0, length0, tol, ci_level = float(pi0), float(length0), float(tol), float(ci_level)
+    if not HMM_PI_RANGE[0] <= pi0 <= HMM_PI_RANGE[1]:
+        raise ValueError('pi0 must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi0,))
+    if not HMM_LENGTH_RANGE[0] <= length0 <= HMM_LENGTH_RANGE[1]:
+        raise ValueError('length0 must lie in 1e-3 .. 1e9 bases, not %r' % (length0,))
+    if not tol > 0.0 or int(max_iter) != max_iter or max_iter < 1 or not 0.0 < ci_level < 1.0:
+        raise ValueError('fit_hmm: tol must be positive, max_iter a positive integer and ci_level inside (0, 1)')
+    clamp = lambda v, r: min(max(v, r[0]), r[1])
+    eta_range, lam_range = tuple(_logit(v) for v in HMM_PI_RANGE), tuple(math.log(v) for v in HMM_LENGTH_RANGE)
+
+    def back(v, rng_t, rng, f):
+        """the parameter at v on its unbounded scale: the end of its range itself at or beyond that end"""
+        return rng[0] if v <= rng_t[0] else (rng[1] if v >= rng_t[1] else clamp(f(v), rng))
+
+    n_eval = 0
+
+    def sums_at(pi, length):
+        nonlocal n_eval
+        n_eval += 1
+        s = [float(v) for v in evaluate(pi, length)]
+        if len(s) != len(L.HMM_GRAD_SUMS):
+            raise ValueError('fit_hmm: evaluate must return the %d sums of nmod_read_hmm_grad' % len(L.HMM_GRAD_SUMS))
+        return s
+
+    def step_of(s):
+        """the free parameters, why, the step H^-1 g on them and the inverse's diagonal"""
+        g, h00, h01, h11 = (s[1], s[2]), s[3], s[4], s[5]
+        free, why = [0, 1], 'pi and length fitted'
+        if fix_pi:
+            free, why = [1], 'length fitted alone: pi is fixed'
+        if 1 in free and not h11 > 0.0:
+            free.remove(1)
+            why = 'pi fitted alone: no read has two entries, length is not identified' if free else 'nothing fitted: pi is fixed and length is not identified'
+        if 0 in free and not h00 > 0.0:
+            free.remove(0)
+            why = 'length fitted alone: the gradient in pi is 0 for every read' if free else 'nothing fitted: no read has an entry'
+        if len(free) == 2 and not h00 * h11 - h01 * h01 > 1e-12 * h00 * h11:
+            free, why = [0], 'pi fitted alone: the information matrix is singular to working precision'
+        d, var = [0.0, 0.0], [math.nan, math.nan]
+        if len(free) == 2:
+            det = h00 * h11 - h01 * h01
+            d = [(h11 * g[0] - h01 * g[1]) / det, (h00 * g[1] - h01 * g[0]) / det]
+            var = [h11 / det, h00 / det]
+        elif free:
+            i = free[0]
+            d[i], var[i] = g[i] / (h00, h11)[i], 1.0 / (h00, h11)[i]
+        return free, why, d, var
+
+    pi, length = pi0, length0
+    th = [_logit(pi), math.log(length)]
+    s = sums_at(pi, length)
+    trace, converged = [], False
+    for it in range(int(max_iter) + 1):
+        free, status, d, var = step_of(s)
+        crit = s[1] * d[0] + s[2] * d[1]
+        trace.append((pi, length, s[0], crit))
+        if not free:
+            break
+        if crit < tol:
+            converged = True
+            break
+        if it == int(max_iter):
+            status += '; stopped after %d steps' % max_iter
+            break
+        scale, moved = 1.0, False
+        for _ in range(FIT_MAX_HALVINGS + 1):
+            cand = [clamp(th[0] + scale * d[0], eta_range), clamp(th[1] + scale * d[1], lam_range)]
+            # (a parameter that does not move keeps its value, not the round trip through its scale)
+            c_pi = pi if cand[0] == th[0] else back(cand[0], eta_range, HMM_PI_RANGE, _expit)
+            c_len = length if cand[1] == th[1] else back(cand[1], lam_range, HMM_LENGTH_RANGE, math.exp)
+            if (c_pi, c_len) == (pi, length):
+                break
+            trial = sums_at(c_pi, c_len)
+            if trial[0] > s[0]:
+                th, pi, length, s, moved = cand, c_pi, c_len, trial, True
+                break
+            scale *= 0.5
+        if not moved:
+            status += '; stopped: no step increases the log-likelihood (a bound of the range, or the precision of the sums)'
+            break
+    z = NormalDist().inv_cdf(0.5 + 0.5 * ci_level)
+    se = [math.sqrt(v) if v == v else math.nan for v in var]
+    # the ends of a Wald interval mapped back (the value itself for a parameter that was not fitted); exp must not overflow
+    ends = lambda i, f, rng, val: (val, val) if se[i] != se[i] else tuple(clamp(f(th[i] + sgn * z * se[i]), rng) for sgn in (-1.0, 1.0))
+    (pi_lo, pi_hi) = ends(0, _expit, HMM_PI_RANGE, pi)
+    (len_lo, len_hi) = ends(1, lambda x: math.exp(min(x, 700.0)), HMM_LENGTH_RANGE, length)
+    return dict(pi=pi, length=length, eta=th[0], lam=th[1], ll=s[0], se_eta=se[0], se_lam=se[1], pi_lo=pi_lo, pi_hi=pi_hi, length_lo=len_lo,
+                length_hi=len_hi, trace=trace, n_eval=n_eval, n_reads=int(s[6]), n_entries=int(s[7]), converged=converged, status=status,
+                ci_level=ci_level)
+
+
+def write_hmm_fit(path, fit):
+    """<FileID>_hmm_fit.txt: the trace, one line 'iter pi length ll criterion' per iterate as '%d %.9g %.9g %.6f %.3E'; then
+    'pi estimate lo hi se_eta' and 'length estimate lo hi se_lam' as '%s %.9g %.9g %.9g %.6g' ('nan' as Python spells it for a parameter
+    that was not fitted); then 'evaluations N converged 0|1 level CI' and 'status TEXT' (`fit` of fit_hmm)"""
+    with open(path, 'w') as f:
+        f.writelines('%d %.9g %.9g %.6f %.3E\n' % ((i,) + tuple(row)) for i, row in enumerate(fit['trace']))
+        f.write('pi %.9g %.9g %.9g %.6g\n' % (fit['pi'], fit['pi_lo'], fit['pi_hi'], fit['se_eta']))
+        f.write('length %.9g %.9g %.9g %.6g\n' % (fit['length'], fit['length_lo'], fit['length_hi'], fit['se_lam']))
+        f.write('evaluations %d converged %d level %g\n' % (fit['n_eval'], int(fit['converged']), fit['ci_level']))
+        f.write('status %s\n' % fit['status'])
 
 
 def _viterbi_result(vit, hoff, key, nm, reads, nreads, ll, post, pi, length, log):
