@@ -1242,6 +1242,82 @@ int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs
                        const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                        const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out);
 
+/* Latent-class clustering of the reads by their modification pattern: a finite mixture of C classes over the reads, every class with
+ * a weight and a modified share of its own at every candidate site, fitted by EM (K22; the reference project has no such step).  K14
+ * to K21 take every read from one population; here a site whose share is 0.45 may be 35 % of the molecules at 0.8 and the rest at 0.1,
+ * and gamma says which read is which.  One EM step per call; the loop is the caller's (nanomod_amd/readllr.py: fit_classes).
+ * Memspaces, the stream contract, the NULL and struct_size rules: those of nmod_read_hmm.
+ *   ENTRIES of a read: nmod_read_hmm's, with its VALID and COVERS rules.  Entry j is at site site_j with the window sum s_j.
+ *   Model.  Class c has the weight w_c and the share theta[site][c]; the sites are independent within a class.  With
+ *     t_j = -expm1(-|s_j|), K14's form:
+ *         g(s, th)    = log1p(-((s >= 0 ? 1 - th : th) * t))              = log((1 - th) e_0 + th e_1), K19's scaled emissions
+ *         post(s, th) = s >= 0 ? th / (1 - (1 - th) * t) : th * (1 - t) / (1 - th * t),
+ *     each evaluated left to right as written, no fused operation: contraction is off for the whole translation unit.
+ *   Per read.  l_rc = SUM_j g(s_j, theta[site_j][c]);  a_rc = log(w_c) + l_rc, log(w_c) the device's log of w_in[c] (in
+ *     NMOD_MEM_DEVICE nothing is read back, so both memspaces form it on the device and agree bit for bit);  M = MAX_c a_rc, the first
+ *     of equals;  x_c = exp(a_rc - M), Z = SUM_c x_c added in ascending c from 0;  gamma_rc = x_c / Z;
+ *     ll_r = (M + log(Z)) + S_r with S_r = SUM_j max(s_j, 0): the read's log-likelihood relative to "every site canonical"; with C = 1
+ *     it is nmod_read_hmm's ll_indep with a pi per site.  cls_r (int32) = the arg max of gamma, the first of equals.  status (uint8):
+ *     NMOD_HMM_NO_SITE when m = 0, with gamma = 0, ll = 0 and cls = -1; such a read takes no part in any sum.
+ *     ORDER.  A read of up to NMOD_HMM_WAVE_MAX entries is computed by T = 64 threads, a longer one by T = 256.  Thread t adds the terms
+ *     of entries t, t + T, t + 2 T, ... in ascending order from 0.0 into one word per class and one for S; then the library's wave sum
+ *     of every word (lanes l ^ 1, l ^ 2, the mirror within 8, the mirror within 16, then 0.0 + the four rows of 16 in order), then for
+ *     T = 256 the four waves from 0.0 in order.  The classes of a site are theta[site * C .. site * C + C - 1].
+ *   Per site and class, over the rows of the site in ascending row index (that is ascending read index):
+ *     N_jc = SUM gamma_rc;  Mo_jc = SUM (gamma_rc * post(s, theta_in[j][c])), the product rounded and then added;
+ *     theta_out[j][c] = Mo_jc / N_jc clamped to 1e-9 .. 1 - 1e-9, and theta_in[j][c] where N_jc == 0 (n_site is N).
+ *     ORDER.  A site of up to NMOD_CLASSES_SMALL rows is computed by G = 16 lanes, up to NMOD_CLASSES_WAVE by G = 64, a larger one by
+ *     G = 256 threads.  Thread g adds rows g, g + G, ... of the site's list in ascending order from 0.0; then for G = 16 the first four
+ *     steps of the wave sum (l ^ 1, l ^ 2, the two mirrors; lane 0's word), for G = 64 the wave sum, for G = 256 the wave sums and the
+ *     four waves from 0.0 in order.  The bits of a site depend on its rows and their order alone.
+ *   Weights and sums: one workgroup of 256 threads.  Thread t adds reads t, t + 256, ... with an entry in ascending order, then the wave
+ *     sum of every word and the four waves in order.  sums (double[4 + C]): SUM ll, R1 = the reads with an entry, the entries (as
+ *     doubles, exact below 2^53), MAX |theta_out - theta_in| over the (site, class) cells with N > 0, and SUM_r gamma_rc per class.
+ *     w_out[c] = sums[4 + c] / R1, and w_in[c] where R1 == 0.
+ *   No float atomics.  A read's gamma, ll and cls depend on the read, theta_in and w_in alone: not on the batch, the order of the
+ *     reads, the memspace or the outputs asked for.
+ *   nmod_read_class_rows(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, out), once per data set: nmod_read_hmm's read
+ *     arguments with hoff and nrows from nmod_read_sites_count.  Per row site (int32) and s (double), nmod_read_hmm's site and score
+ *     byte for byte, and rread (int32), the row's read; the site-major view soff (int64[nsites + 1]) and srow (int32[nrows]): the rows
+ *     of site j are srow[soff[j] .. soff[j + 1] - 1] in ascending row index (a stable sort of the rows by their site).  A NULL output
+ *     is skipped.  Refusals: nmod_read_hmm's without the options.  Scratch: 36 B per row beside the sort's, 44 B without site and srow.
+ *   nmod_read_classes_step(prm, nreads, nsites, nrows, hoff, site, s, rread, soff, srow, opts, theta_in, w_in, out), once per EM step:
+ *     the reads are not walked again.  theta_in double[nsites * C], the C classes of a site contiguous; w_in double[C].  Outputs (a NULL
+ *     member is skipped; asking for fewer never changes the bits of the others): gamma double[nreads * C], ll double[nreads], cls
+ *     int32[nreads], status uint8[nreads], theta_out and n_site double[nsites * C], w_out double[C], sums double[4 + C].
+ *     NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and no synchronisation; nothing is checked: a row index
+ *     outside [0, nrows), a site outside [0, nsites), an rread outside [0, nreads) and offsets outside the rows are skipped and never
+ *     dereferenced.  NMOD_MEM_HOST: one staged copy.
+ *     NMOD_ERR_INVALID_ARG before any device work: the shared refusals (counts out of range, a NULL input, opts or out NULL or of
+ *     another struct_size, nrows positive without reads or sites); n_classes outside 1 .. NMOD_CLASSES_MAX; host theta_in or w_in
+ *     outside 1e-9 .. 1 - 1e-9 or not finite (with one class the weight 1 is the only one there is, and is accepted); host w_in not
+ *     summing to 1 within 1e-9; host hoff or soff that does not start at 0, ascend and end at nrows.
+ *     Scratch: 8 C B per read for gamma and 8 B for ll where a later kernel needs them and they are not asked for; the same per site
+ *     for theta_out and n_site when only sums asks for them.
+ * Stops at: sites independent within a class, no chain inside a class; both k-mer tables taken as right; EM finds a local maximum and
+ * the caller's restarts are the only defence; no standard errors of theta; the choice of C is the caller's (BIC in readllr.py);
+ * C <= NMOD_CLASSES_MAX; a molecule sequenced twice counts twice. */
+#define NMOD_CLASSES_MAX 8                 /* classes of a fit */
+#define NMOD_CLASSES_SMALL 64              /* rows of a site up to which 16 lanes compute it */
+#define NMOD_CLASSES_WAVE 512              /* ... up to which one wave does (a workgroup of 256 beyond) */
+typedef struct nmod_class_rows_out { int32_t struct_size; int32_t reserved;
+  int32_t* site; double* s; int32_t* rread;                             /* [nrows] */
+  int64_t* soff;                                                        /* [nsites + 1] */
+  int32_t* srow;                                                        /* [nrows] */
+} nmod_class_rows_out;
+typedef struct nmod_classes_opts { int32_t struct_size, n_classes; } nmod_classes_opts;
+typedef struct nmod_classes_out { int32_t struct_size; int32_t reserved;
+  double *gamma, *ll; int32_t* cls; uint8_t* status;                    /* [nreads * C], [nreads] ... */
+  double *theta_out, *n_site;                                           /* [nsites * C] */
+  double *w_out, *sums;                                                 /* [C], [4 + C] */
+} nmod_classes_out;
+int nmod_read_class_rows(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                         const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                         const nmod_class_rows_out* out);
+int nmod_read_classes_step(const nmod_params* prm, int64_t nreads, int64_t nsites, int64_t nrows, const int64_t* hoff,
+                           const int32_t* site, const double* s, const int32_t* rread, const int64_t* soff, const int32_t* srow,
+                           const nmod_classes_opts* opts, const double* theta_in, const double* w_in, const nmod_classes_out* out);
+
 /* ---- position shards across the GPUs of a node without any host framework (BASELINE.json north_star: "an RCCL
  * all-gather over xGMI to reassemble the per-base p-value track").  The reference has no counterpart (one CPU process).  One
  * process (or thread) per GPU computes a contiguous block of positions (+- nb recomputed neighbours) with

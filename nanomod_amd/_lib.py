@@ -87,8 +87,9 @@ class NmodMixOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in MIX_FIELDS] + [('iters', C.c_void_p), ('status', C.c_void_p), ('resp', C.c_void_p)]
 
 
-def make_out(cls, **members):
-    """an out struct of class `cls`: struct_size filled in where the struct has one, the named members set, the rest left NULL"""
+def make_out(cls, /, **members):
+    """an out struct of class `cls`: struct_size filled in where the struct has one, the named members set, the rest left NULL
+    (`cls` by position alone: nmod_classes_out has a member of that name)"""
     o = cls()
     if hasattr(cls, 'struct_size'):
         o.struct_size = C.sizeof(cls)
@@ -410,6 +411,38 @@ def make_hmm_grad_opts(pi=0.5, length=200.0):
 make_hmm_grad_out = functools.partial(make_out, NmodHmmGradOut)
 
 
+CLASSES_MAX = 8                            # nmod_read_classes_step: classes of a fit
+CLASSES_SMALL, CLASSES_WAVE = 64, 512      # rows of a site up to which 16 lanes compute it, up to which one wave does
+CLASS_ROWS_FIELDS = ('site', 's', 'rread', 'soff', 'srow')             # nmod_read_class_rows
+CLASSES_READ_FIELDS = ('gamma', 'll', 'cls', 'status')                 # nmod_read_classes_step; status: NMOD_HMM_NO_SITE
+CLASSES_SITE_FIELDS = ('theta_out', 'n_site')
+CLASSES_SUMS = ('ll', 'n_reads', 'n_entries', 'max_move')              # the first words of its `sums`; then sum gamma per class
+
+
+class NmodClassRowsOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in CLASS_ROWS_FIELDS]
+
+
+class NmodClassesOpts(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('n_classes', C.c_int32)]
+
+
+class NmodClassesOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in CLASSES_READ_FIELDS + CLASSES_SITE_FIELDS
+                                                                         + ('w_out', 'sums')]
+
+
+def make_classes_opts(n_classes=2):
+    o = NmodClassesOpts()
+    o.struct_size = C.sizeof(NmodClassesOpts)
+    o.n_classes = int(n_classes)
+    return o
+
+
+make_class_rows_out = functools.partial(make_out, NmodClassRowsOut)
+make_classes_out = functools.partial(make_out, NmodClassesOut)
+
+
 class NanomodLibraryError(RuntimeError):
     pass
 
@@ -495,6 +528,10 @@ _SIGNATURES = {
                                     C.POINTER(NmodVitOpts), C.POINTER(NmodVitOut)]),
     'nmod_read_hmm_grad': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(NmodHmmGradOpts), C.POINTER(NmodHmmGradOut)]),
+    'nmod_read_class_rows': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.POINTER(NmodClassRowsOut)]),
+    'nmod_read_classes_step': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6
+                               + [C.POINTER(NmodClassesOpts), C.c_void_p, C.c_void_p, C.POINTER(NmodClassesOut)]),
     'nmod_pivot_reads': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int64]
                          + [C.c_void_p] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'nmod_select_tested': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

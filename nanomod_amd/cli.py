@@ -269,7 +269,92 @@ def build_parser():
     rh.add_argument('--outFolder', default='mRes')
     rh.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_hmm.txt, _read_domains.txt and _site_hmm.txt')
     rh.add_argument('--device', type=int, default=0)
+    rk = sub.add_parser('readclasses', help='latent-class clustering of the reads of one read-level sample by their modification pattern on the '
+                        'device: a mixture of classes of reads, each with a modified share of its own at every candidate site, fitted by EM; per '
+                        'read its class and how firmly it belongs to it, per site and class the share')
+    rk.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
+    rk.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
+    rk.add_argument('--kmerModel', '--model', dest='kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
+    rk.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
+    rk.add_argument('--sites', default='stoich', help="'stoich': the positions whose modified share (readllr --siteFraction) has a "
+                    "Benjamini-Hochberg q of at most --siteAlpha; or a FILE of lines 'chrom strand pos' (1-based)")
+    rk.add_argument('--classes', default='2', help='C or C,C,...: the number of classes, 1 .. %d; of several the one with the smallest BIC is kept' % L.CLASSES_MAX)
+    rk.add_argument('--nInit', type=int, default=4, help='the seeded starts of every number of classes; the best final log-likelihood is kept')
+    rk.add_argument('--seed', type=int, default=0, help='the seed of the starts, >= 0')
+    rk.add_argument('--maxIter', type=int, default=500, help='the EM steps of a start at most')
+    rk.add_argument('--tol', type=float, default=1e-9, help='a start stops when the log-likelihood rises by at most tol * (|ll| + 1)')
+    rk.add_argument('--llrThreshold', type=float, default=2.5, help="K13's call threshold (it does not move the window sums), > 0")
+    rk.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
+                    'before and after, 0 .. 64 each')
+    rk.add_argument('--prior', type=float, default=0.5, help='prior probability of the modified state, inside (0, 1)')
+    rk.add_argument('--minPositions', type=int, default=1, help='use a k-mer only if its entry rests on at least this many positions')
+    rk.add_argument('--rescale', type=int, default=0, choices=[0, 1], help="1: put every read on the unmodified model's scale first")
+    rk.add_argument('--siteAlpha', type=float, default=0.05, help="--sites stoich: the level of the sites' q-values, in (0, 1]")
+    rk.add_argument('--outFolder', default='mRes')
+    rk.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_read_classes.txt, _class_sites.txt and _classes_fit.txt')
+    rk.add_argument('--device', type=int, default=0)
     return p
+
+
+def parse_classes(text):
+    """--classes: the list of counts of 'C' or 'C,C,...'; None for anything else"""
+    parts = text.split(',')
+    if not parts or not all(q.strip().isdigit() for q in parts):
+        return None
+    return [int(q) for q in parts]
+
+
+def validate_readclasses(a):
+    """the checks of readclasses, in validate_readhmm's manner"""
+    errs = []
+    win = parse_llr_window(a.llrWindow)
+    if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
+        errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
+    if not 0.0 < a.llrThreshold < float('inf'):
+        errs.append('Error: --llrThreshold should be finite and larger than 0')
+    if not 0.0 < a.prior < 1.0:
+        errs.append('Error: --prior should lie between 0 and 1, both excluded')
+    if a.minPositions < 1:
+        errs.append('Error: --minPositions should be larger than 0')
+    counts = parse_classes(a.classes)
+    if counts is None or not all(1 <= c <= L.CLASSES_MAX for c in counts):
+        errs.append('Error: --classes should be C or C,C,... with every C in 1 .. %d' % L.CLASSES_MAX)
+    if a.nInit < 1:
+        errs.append('Error: --nInit should be larger than 0')
+    if a.seed < 0:
+        errs.append('Error: --seed should not be negative')
+    if a.maxIter < 1:
+        errs.append('Error: --maxIter should be larger than 0')
+    if not 0.0 <= a.tol < float('inf'):
+        errs.append('Error: --tol should be finite and not negative')
+    if not 0.0 < a.siteAlpha <= 1.0:
+        errs.append('Error: --siteAlpha should be in (0, 1]')
+    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def run_readclasses(a, log=print):
+    from . import kmermodel, readllr
+    quiet = a.outLevel > detect.OUTPUT_ERROR
+    sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
+    res = readllr.cluster_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
+                                    sites=sites, classes=parse_classes(a.classes), n_init=a.nInit, seed=a.seed, max_iter=a.maxIter, tol=a.tol,
+                                    window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None, site_alpha=a.siteAlpha,
+                                    thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
+                                    log=(lambda *x: None) if quiet else log)
+    os.makedirs(a.outFolder, exist_ok=True)
+    for suffix, write, what in (('_read_classes.txt', readllr.write_read_classes, 'Read classes are'),
+                                ('_class_sites.txt', readllr.write_class_sites, 'Class shares per site are'),
+                                ('_classes_fit.txt', readllr.write_classes_fit, 'The fits are')):
+        path = os.path.join(a.outFolder, a.FileID + suffix)
+        write(path, res)
+        if not quiet:
+            log('%s saved in %s' % (what, path))
+    return res
 
 
 def parse_fit_length(text):
@@ -1001,6 +1086,13 @@ def write_sign_test(path, meta, res, with_comb):
 def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
+    if a.cmd == 'readclasses':
+        errs = validate_readclasses(a)
+        if errs:
+            print('\n'.join(errs))
+            return 1
+        run_readclasses(a)
+        return 0
     if a.cmd == 'readhmm':
         errs = validate_readhmm(a)
         if errs:

@@ -1175,6 +1175,120 @@ def read_hmm_grad_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length
     return res
 
 
+CLASS_ROWS_OUTPUTS = L.CLASS_ROWS_FIELDS
+CLASSES_OUTPUTS = L.CLASSES_READ_FIELDS + L.CLASSES_SITE_FIELDS + ('w_out', 'sums')
+_CLASSES_LO, _CLASSES_HI = 1e-9, 1.0 - 1e-9
+
+
+def _class_rows_shapes(nrows, nsites):
+    return dict(site=('int32', nrows), s=('float64', nrows), rread=('int32', nrows), soff=('int64', nsites + 1), srow=('int32', nrows))
+
+
+def _classes_opts(n_classes, want):
+    """nmod_classes_opts from the Python arguments; ValueError for what the C entry refuses"""
+    if int(n_classes) != n_classes or not 1 <= int(n_classes) <= L.CLASSES_MAX:
+        raise ValueError('n_classes must be an integer in 1 .. %d, not %r' % (L.CLASSES_MAX, n_classes))
+    want = tuple(want)
+    if any(w not in CLASSES_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(CLASSES_OUTPUTS))
+    return L.make_classes_opts(int(n_classes)), want
+
+
+def _classes_shapes(want, nreads, nsites, nc):
+    kinds = dict(gamma=('float64', nreads * nc), ll=('float64', nreads), cls=('int32', nreads), status=('uint8', nreads),
+                 theta_out=('float64', nsites * nc), n_site=('float64', nsites * nc), w_out=('float64', nc), sums=('float64', 4 + nc))
+    return {k: kinds[k] for k in CLASSES_OUTPUTS if k in want}
+
+
+def _check_class_params(theta, w, nsites):
+    """theta (float64[nsites, C] or flat) and w (float64[C]) of a host call, checked as the C entry checks them -> theta, w, C"""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.ndim != 1 or not 1 <= w.shape[0] <= L.CLASSES_MAX:
+        raise ValueError('w must hold 1 .. %d class weights' % L.CLASSES_MAX)
+    nc = w.shape[0]
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.size != nsites * nc:
+        raise ValueError('theta must be float64[nsites * n_classes], the classes of a site contiguous')
+    theta = theta.reshape(-1)
+    if not bool(np.all((theta >= _CLASSES_LO) & (theta <= _CLASSES_HI))):
+        raise ValueError('theta must lie in 1e-9 .. 1 - 1e-9')
+    if not (bool(np.all((w >= _CLASSES_LO) & (w <= _CLASSES_HI))) or (nc == 1 and w[0] == 1.0)):
+        raise ValueError('w must lie in 1e-9 .. 1 - 1e-9')
+    if not abs(float(w.sum()) - 1.0) <= 1e-9:
+        raise ValueError('w must sum to 1 within 1e-9')
+    return theta, w, nc
+
+
+def _check_class_offsets(off, n, nrows, name):
+    off = _side(off, np.int64, n + 1, name, 'n + 1', optional=False)
+    if off[0] != 0 or bool(np.any(np.diff(off) < 0)) or int(off[-1]) != nrows:
+        raise ValueError('%s must start at 0, never decrease and end at nrows' % name)
+    return off
+
+
+def read_class_rows_host(cs, start, roff, score, key, hoff=None, *, want=CLASS_ROWS_OUTPUTS, device=0):
+    """The rows of the latent-class fit (nmod_read_class_rows, include/nanomod_hip.h) on host-resident reads: the arguments of
+    read_hmm_host.  Returns a dict of numpy arrays, hoff and those named in `want`: per row site (int32), s (float64, the read's
+    window sum there) and rread (int32, the row's read); soff (int64[nsites + 1]) and srow (int32[nrows]): the rows of site j are
+    srow[soff[j]:soff[j + 1]] in ascending row index."""
+    want = tuple(want)
+    if any(w not in CLASS_ROWS_OUTPUTS for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(CLASS_ROWS_OUTPUTS))
+    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
+    if hoff is None:
+        hoff = read_sites_host(cs, start, roff, score, key, device)
+    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
+    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
+        raise ValueError('hoff must start at 0 and never decrease')
+    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
+    if nrows > 0 and (nreads == 0 or key.shape[0] == 0):
+        raise ValueError('rows need reads and sites')
+    shapes = {k: v for k, v in _class_rows_shapes(nrows, key.shape[0]).items() if k in want}
+    res = _host_outputs(shapes, fill=shapes)
+    lib = L.load()
+    _join_warm_up(device)
+    out = L.make_class_rows_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_class_rows', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
+          _np_ptr(hoff), nrows, C.byref(out))
+    res['hoff'] = hoff
+    return res
+
+
+def read_classes_step_host(rows, theta, w, *, want=CLASSES_OUTPUTS, device=0):
+    """One EM step of the latent-class mixture over the reads (nmod_read_classes_step, include/nanomod_hip.h) on host-resident rows:
+    `rows` as read_class_rows_host gives them (hoff, site, s, rread, soff, srow); theta float64[nsites, C] (the share of every class at
+    every site, within 1e-9 .. 1 - 1e-9), w float64[C] (the class weights, summing to 1).  Returns a dict of numpy arrays, those named
+    in `want`: per read gamma (float64[nreads * C]), ll (float64), cls (int32, -1 without an entry), status (uint8, L.HMM_NO_SITE);
+    theta_out and n_site (float64[nsites * C]); w_out (float64[C]); sums (float64[4 + C], L.CLASSES_SUMS and the classes' sums of
+    gamma)."""
+    hoff = np.ascontiguousarray(rows['hoff'], dtype=np.int64)
+    soff = np.ascontiguousarray(rows['soff'], dtype=np.int64)
+    if hoff.ndim != 1 or hoff.shape[0] < 1 or soff.ndim != 1 or soff.shape[0] < 1:
+        raise ValueError('hoff and soff must be int64 vectors of nreads + 1 and nsites + 1 offsets')
+    nreads, nsites = hoff.shape[0] - 1, soff.shape[0] - 1
+    theta, w, nc = _check_class_params(theta, w, nsites)
+    opts, want = _classes_opts(nc, want)
+    nrows = _check_hmm_counts(nreads, nsites, int(hoff[-1]))
+    if nrows > 0 and (nreads == 0 or nsites == 0):
+        raise ValueError('rows need reads and sites')
+    hoff = _check_class_offsets(hoff, nreads, nrows, 'hoff')
+    soff = _check_class_offsets(soff, nsites, nrows, 'soff')
+    site = _side(rows['site'], np.int32, nrows, 'site', 'nrows', optional=False)
+    s = _side(rows['s'], np.float64, nrows, 's', 'nrows', optional=False)
+    rread = _side(rows['rread'], np.int32, nrows, 'rread', 'nrows', optional=False)
+    srow = _side(rows['srow'], np.int32, nrows, 'srow', 'nrows', optional=False)
+    lib = L.load()
+    shapes = _classes_shapes(want, nreads, nsites, nc)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_classes_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_read_classes_step', prm, nreads, nsites, nrows, _np_ptr(hoff), _np_ptr(site), _np_ptr(s), _np_ptr(rread), _np_ptr(soff),
+          _np_ptr(srow), C.byref(opts), _np_ptr(theta), _np_ptr(w), C.byref(out))
+    return res
+
+
 def region_rank_host(strand_lo, strand_hi, pos, base, value, w, movesize, na, percentile, wind_ovlp, device=0):
     """myDetect.py:463-515 on array-shaped records (see nmod_region_rank): indices of the ranked window centres."""
     lib = L.load()
@@ -1780,6 +1894,57 @@ class DeviceDetector:
         o = L.make_hmm_grad_out(**{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
         _call(self.lib, 'nmod_read_hmm_grad', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
+        return res
+
+    def read_class_rows(self, cs, start, roff, score, key, hoff, nrows, *, want=CLASS_ROWS_OUTPUTS, out=None):
+        """The rows of the latent-class fit (nmod_read_class_rows, NMOD_MEM_DEVICE), enqueued on the current stream without
+        synchronising or reading anything back: the arguments of read_hmm.  Returns a dict of CUDA tensors, those named in `want`: per
+        row site (int32), s (float64), rread (int32); soff (int64, nsites + 1) and srow (int32): the rows of site j are
+        srow[soff[j]:soff[j + 1]] in ascending row index.  out: such a dict from an earlier call of the same shape."""
+        torch = self.torch
+        want = tuple(want)
+        if any(w not in CLASS_ROWS_OUTPUTS for w in want):
+            raise ValueError('want must name outputs of %s' % ', '.join(CLASS_ROWS_OUTPUTS))
+        nreads, shared = self._site_reads('read_class_rows', cs, start, roff, score, key)
+        _cuda_vecs('read_class_rows', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
+        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
+        shapes = {k: v for k, v in _class_rows_shapes(nrows, key.numel()).items() if k in want}
+        res = self._outputs(out, shapes, 'read_class_rows')
+        o = L.make_class_rows_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_class_rows', prm, *shared, hoff.data_ptr(), nrows, C.byref(o))
+        return res
+
+    def read_classes_step(self, rows, hoff, theta, w, *, want=CLASSES_OUTPUTS, out=None):
+        """One EM step of the latent-class mixture over the reads (nmod_read_classes_step, NMOD_MEM_DEVICE), enqueued on the current
+        stream without synchronising or reading anything back: `rows` as read_class_rows gives them (all five), hoff as read_sites
+        does; theta (float64, nsites * C, the classes of a site contiguous) and w (float64, C) CUDA vectors, not checked.  Returns a
+        dict of CUDA tensors, those named in `want`: gamma (float64, nreads * C), ll (float64), cls (int32), status (uint8); theta_out,
+        n_site (float64, nsites * C); w_out (float64, C); sums (float64, 4 + C).  out: such a dict from an earlier call of the same
+        shape."""
+        torch = self.torch
+        _cuda_vecs('read_classes_step', (('w', w, torch.float64, None),), one_dim=True, missing='refused')
+        opts, want = _classes_opts(w.numel(), want)
+        nc = w.numel()
+        nreads = _device_offsets(torch, hoff, 'read_classes_step', 'nreads')
+        for name in CLASS_ROWS_OUTPUTS:
+            if rows.get(name) is None:
+                raise ValueError('read_classes_step: rows must hold %s' % ', '.join(CLASS_ROWS_OUTPUTS))
+        nsites = _device_offsets(torch, rows['soff'], 'read_classes_step', 'nsites')
+        nrows = rows['site'].numel()
+        _check_hmm_counts(nreads, nsites, nrows)
+        _cuda_vecs('read_classes_step', (('site', rows['site'], torch.int32, nrows), ('s', rows['s'], torch.float64, nrows),
+                                         ('rread', rows['rread'], torch.int32, nrows), ('srow', rows['srow'], torch.int32, nrows),
+                                         ('theta', theta, torch.float64, nsites * nc)), missing='refused')
+        if nrows > 0 and (nreads == 0 or nsites == 0):
+            raise ValueError('read_classes_step: rows need reads and sites')
+        shapes = _classes_shapes(want, nreads, nsites, nc)
+        res = self._outputs(out, shapes, 'read_classes_step')
+        o = L.make_classes_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_classes_step', prm, nreads, nsites, nrows, hoff.data_ptr(), rows['site'].data_ptr(), rows['s'].data_ptr(),
+              rows['rread'].data_ptr(), rows['soff'].data_ptr(), rows['srow'].data_ptr(), C.byref(opts), theta.data_ptr(), w.data_ptr(),
+              C.byref(o))
         return res
 
     def synth_fill(self, out, seed, pos_begin, npos, group, n_per_pos, plant_period=0, plant_shift=0.0):

@@ -365,7 +365,15 @@ def _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_sha
         keep = (estimated & torch.isin(piv['key'], d_key)) if want_share else None
     if want_share:
         site_pi = share['pi'][keep]
-    return dict(det=det, names=names, nreads=nreads, d_cs=t(cs), d_start=t(start), d_off=d_off, llr_win=llr_win, d_key=d_key, site_pi=site_pi)
+    res = dict(det=det, names=names, nreads=nreads, d_cs=t(cs), d_start=t(start), d_off=d_off, llr_win=llr_win, d_key=d_key, site_pi=site_pi)
+    if want_share == 'per_site':                  # K14's estimate of every candidate site in d_key's order, NaN where it has none
+        pk = piv['key']
+        if pk.numel() == 0 or d_key.numel() == 0:
+            res['site_pi_at'] = torch.full((d_key.numel(),), math.nan, dtype=torch.float64, device=dev)
+        else:
+            at = torch.searchsorted(pk, d_key).clamp_(max=pk.numel() - 1)
+            res['site_pi_at'] = torch.where((pk[at] == d_key) & estimated[at], share['pi'][at], torch.full_like(share['pi'][at], math.nan))
+    return res
 
 
 def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, thr=2.5, min_reads=10, window='kmer', prior=0.5,
@@ -795,3 +803,214 @@ def write_site_viterbi(path, res):
            [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'share')]
     with open(path, 'w') as f:
         f.writelines('%s %s %d %d %d %.6f\n' % row for row in zip(*cols))
+
+
+# ---------------------------------------------------------------------------------------------------------------- K22: classes of reads
+
+CLASS_RANGE = (1e-9, 1.0 - 1e-9)                  # nmod_read_classes_step's range of theta and of the weights
+CLASS_START_CLAMP = (0.05, 0.95)                  # K14's share is clamped to this before a start is drawn around it
+
+
+def _check_fit_classes(tol, max_iter):
+    tol = float(tol)
+    if not tol >= 0.0 or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError('fit_classes: tol must not be negative and max_iter must be a positive integer')
+    return tol
+
+
+def fit_classes(step, theta0, w0, *, tol=1e-9, max_iter=500):
+    """The EM loop of the latent-class mixture over the reads (K22): a pure host function over a callable.  step(theta, w) runs one EM
+    step at (theta, w) and returns (theta_out, w_out, sums): from the device (DeviceDetector.read_classes_step, whose tensors stay on
+    the device: the loop hands them back as they are and reads `sums` alone, a sequence of host floats whose first word is SUM ll at
+    (theta, w)) or from any restatement.
+    EM never lowers SUM ll; the loop stops when its rise from one step to the next is at most tol * (|ll| + 1) (converged), or after
+    max_iter steps.  Returns a dict: theta and w, the parameters SUM ll was last evaluated at; ll; trace, the list of SUM ll per step;
+    sums, the last step's; n_iter, the steps run; converged."""
+    tol = _check_fit_classes(tol, max_iter)
+    theta, w = theta0, w0
+    trace, prev, converged, sums = [], None, False, None
+    for _ in range(int(max_iter)):
+        theta_n, w_n, sums = step(theta, w)
+        sums = [float(v) for v in sums]
+        ll = sums[0]
+        trace.append(ll)
+        if prev is not None and ll - prev <= tol * (abs(ll) + 1.0):
+            converged = True
+            break
+        if len(trace) == int(max_iter):
+            break
+        prev, theta, w = ll, theta_n, w_n
+    return dict(theta=theta, w=w, ll=trace[-1], trace=trace, sums=sums, n_iter=len(trace), converged=converged)
+
+
+def class_starts(pihat, n_classes, n_init, seed=0):
+    """The seeded starts of a fit of n_classes classes: a list of n_init arrays theta0 (float64[nsites, n_classes]).  Start i is
+    expit(logit(p_j) + z) with p_j K14's share of site j clamped to 0.05 .. 0.95 (0.5 where pihat is NaN) and z ~ N(0, 1) from
+    numpy.random.default_rng([seed, n_classes, i]); the weights of every start are equal."""
+    if int(n_classes) != n_classes or not 1 <= int(n_classes) <= L.CLASSES_MAX:
+        raise ValueError('classes must be integers in 1 .. %d, not %r' % (L.CLASSES_MAX, n_classes))
+    if int(n_init) != n_init or n_init < 1:
+        raise ValueError('n_init must be a positive integer, not %r' % (n_init,))
+    if int(seed) != seed or seed < 0:
+        raise ValueError('seed must be a non-negative integer, not %r' % (seed,))
+    p = np.asarray(pihat, np.float64)
+    p = np.clip(np.where(p == p, p, 0.5), *CLASS_START_CLAMP)
+    base = np.log(p) - np.log1p(-p)
+    out = []
+    for i in range(int(n_init)):
+        z = np.random.default_rng([int(seed), int(n_classes), i]).standard_normal((len(p), int(n_classes)))
+        out.append(np.clip(1.0 / (1.0 + np.exp(-(base[:, None] + z))), *CLASS_RANGE))
+    return out
+
+
+def class_order(w):
+    """the classes by descending weight, ties by index: the permutation new label -> old label"""
+    w = np.asarray(w, np.float64)
+    return np.lexsort((np.arange(len(w)), -w))
+
+
+def class_bic(ll, n_classes, n_sites_with_rows, n_reads):
+    """BIC = -2 ll + (C - 1 + C * nsites_with_rows) * ln(R1); +inf without a read that has an entry"""
+    if n_reads <= 0:
+        return math.inf
+    return -2.0 * float(ll) + (int(n_classes) - 1 + int(n_classes) * int(n_sites_with_rows)) * math.log(float(n_reads))
+
+
+def _classes_list(classes):
+    counts = [classes] if isinstance(classes, (int, np.integer)) else list(classes)
+    if not counts:
+        raise ValueError('classes must name at least one number of classes')
+    for c in counts:
+        if int(c) != c or not 1 <= int(c) <= L.CLASSES_MAX:
+            raise ValueError('classes must be integers in 1 .. %d, not %r' % (L.CLASSES_MAX, c))
+    return [int(c) for c in counts]
+
+
+def choose_classes(fits):
+    """From the fits of all starts and counts (dicts with C, start, ll, bic): the best start of every count (the largest ll, the first
+    of equals), the profile [(C, ll, bic)] over the counts in the order given, and the chosen fit (the smallest BIC, the first of
+    equals)"""
+    best = {}
+    for f in fits:
+        if f['C'] not in best or f['ll'] > best[f['C']]['ll']:
+            best[f['C']] = f
+    profile = [(c, best[c]['ll'], best[c]['bic']) for c in best]
+    chosen = None
+    for c in best:
+        if chosen is None or best[c]['bic'] < chosen['bic']:
+            chosen = best[c]
+    return best, profile, chosen
+
+
+def cluster_reads_llr(reads, model, alt_model, *, sites='stoich', classes=2, n_init=4, seed=0, max_iter=500, tol=1e-9, window='kmer',
+                      rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print):
+    """Latent-class clustering of the reads by their modification pattern (K22, nmod_read_class_rows / nmod_read_classes_step): do the
+    reads fall into subpopulations with a modified share of their own at every site, and which read belongs to which?  The optional
+    rescaling (K11), the window sums (K13) and the candidate sites exactly as in smooth_reads_llr; then a mixture of C classes over
+    the reads, sites independent within a class, fitted by EM on the device: one call per step, theta and the weights stay there and
+    4 + C sums come back per step (fit_classes).
+    classes: the number of classes, or a list of them: each is fitted and the smallest BIC = -2 ll + (C - 1 + C * sites with a row)
+    ln(reads with an entry) is kept; 1 is K14's per-site estimate under independence.  n_init, seed: the starts of every count
+    (class_starts); the best final ll is kept, the first of equals.  The classes are labelled by descending weight, ties by index.
+    Returns a dict: C, w (float64[C]), theta (float64[nsites, C]), ll, bic;
+      fit: one entry per start and count: C, start, w (a tuple, relabelled), ll, bic, n_iter, converged, kept (the start kept for its C);
+      reads: index, chrom, strand, n_sites, cls (-1 without an entry), gamma (the posterior of cls; float64[nreads, C]: gamma_all), ll,
+        status (L.HMM_NO_SITE);
+      sites: chrom, strand, pos (0-based), theta and n (float64[nsites, C] each; n: the expected reads of the class at the site);
+      profile: [(C, ll, bic)] over the counts.  One summary line per count and one for the choice go to `log`."""
+    import torch
+    counts = _classes_list(classes)
+    for c in counts:
+        class_starts(np.zeros(0), c, n_init, seed)                                            # the refusals, before any device work
+    _check_fit_classes(tol, max_iter)
+    setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
+    site_alpha = engine._check_alpha(site_alpha)
+    _sites_by_stoich(sites)
+    sc = _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_share='per_site')
+    det, names, nreads, d_key = sc['det'], sc['names'], sc['nreads'], sc['d_key']
+    shared = (sc['d_cs'], sc['d_start'], sc['d_off'], sc['llr_win'], d_key)
+    hoff, nrows = det.read_sites(*shared)
+    rows = det.read_class_rows(*shared, hoff, nrows)
+    pihat = sc['site_pi_at'].cpu().numpy()
+    nsites = len(pihat)
+    with_rows = int((np.diff(rows['soff'].cpu().numpy()) > 0).sum())
+    dev = torch.device('cuda', device)
+
+    def step(theta, w):
+        res = det.read_classes_step(rows, hoff, theta, w, want=('theta_out', 'w_out', 'sums'))
+        return res['theta_out'], res['w_out'], res['sums'].cpu().tolist()
+
+    fits = []
+    for c in counts:
+        for i, theta0 in enumerate(class_starts(pihat, c, n_init, seed)):
+            f = fit_classes(step, torch.from_numpy(theta0.reshape(-1)).to(dev), torch.full((c,), 1.0 / c, dtype=torch.float64, device=dev),
+                            tol=tol, max_iter=max_iter)
+            f.update(C=c, start=i, bic=class_bic(f['ll'], c, with_rows, int(f['sums'][1])))
+            fits.append(f)
+    best, profile, chosen = choose_classes(fits)
+    table_fit = []
+    for f in fits:
+        order = class_order(f['w'].cpu().numpy())
+        table_fit.append(dict(C=f['C'], start=f['start'], w=tuple(f['w'].cpu().numpy()[order].tolist()), ll=f['ll'], bic=f['bic'],
+                              n_iter=f['n_iter'], converged=f['converged'], kept=best[f['C']] is f))
+    for c, ll, bic in profile:
+        log('readclasses: %d class(es): log-likelihood %.6f, BIC %.6f; the best of %d start(s), %d step(s), %s'
+            % (c, ll, bic, int(n_init), best[c]['n_iter'], 'converged' if best[c]['converged'] else 'not converged'))
+    C_ = chosen['C']
+    fin = det.read_classes_step(rows, hoff, chosen['theta'], chosen['w'], want=('gamma', 'll', 'cls', 'status', 'n_site'))
+    order = class_order(chosen['w'].cpu().numpy())
+    rank = np.empty(C_, np.int64)
+    rank[order] = np.arange(C_)
+    gamma = fin['gamma'].cpu().numpy().reshape(nreads, C_)[:, order]
+    cls = fin['cls'].cpu().numpy()
+    cls = np.where(cls >= 0, rank[np.maximum(cls, 0)], -1).astype(np.int32)
+    key = d_key.cpu().numpy()
+    nm = np.array(names, dtype=str)
+    n_sites = np.diff(hoff.cpu().numpy()).astype(np.int32)
+    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
+                 n_sites=n_sites, cls=cls, gamma=np.where(cls >= 0, gamma[np.arange(nreads), np.maximum(cls, 0)], 0.0) if nreads else np.zeros(0),
+                 gamma_all=gamma, ll=fin['ll'].cpu().numpy(), status=fin['status'].cpu().numpy())
+    theta = chosen['theta'].cpu().numpy().reshape(nsites, C_)[:, order]
+    out_sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                     pos=key & ((1 << 40) - 1), theta=theta, n=fin['n_site'].cpu().numpy().reshape(nsites, C_)[:, order])
+    w = chosen['w'].cpu().numpy()[order]
+    log('readclasses: %d read(s), %d with an entry, %d candidate site(s), %d entr%s; %d class(es) kept%s, weights %s'
+        % (nreads, int(chosen['sums'][1]), nsites, nrows, 'y' if nrows == 1 else 'ies', C_,
+           '' if len(counts) == 1 else ' by BIC of %s' % ', '.join(str(c) for c in counts), ' '.join('%.4f' % v for v in w)))
+    return dict(C=C_, w=w, theta=theta, ll=chosen['ll'], bic=chosen['bic'], fit=table_fit, reads=table, sites=out_sites, profile=profile)
+
+
+def write_read_classes(path, res):
+    """<FileID>_read_classes.txt: a header line, then per read 'read chrom strand n_sites class gamma ll', tab-separated, as
+    '%d %s %s %d %d %.6f %.6f' (class -1 and gamma 0 for a read without an entry; `res` of cluster_reads_llr)"""
+    t = res['reads']
+    cols = [np.asarray(t['index']).tolist(), np.asarray(t['chrom']).astype(str).tolist(), np.asarray(t['strand']).astype(str).tolist(),
+            np.asarray(t['n_sites']).tolist(), np.asarray(t['cls']).tolist(), np.asarray(t['gamma'], np.float64).tolist(),
+            np.asarray(t['ll'], np.float64).tolist()]
+    with open(path, 'w') as f:
+        f.write('read\tchrom\tstrand\tn_sites\tclass\tgamma\tll\n')
+        f.writelines('%d\t%s\t%s\t%d\t%d\t%.6f\t%.6f\n' % row for row in zip(*cols))
+
+
+def write_class_sites(path, res):
+    """<FileID>_class_sites.txt: a header line, then per candidate site 'chrom strand pos+1 theta_0 N_0 theta_1 N_1 ...', tab-separated,
+    theta as '%.6f' and N as '%.3f' (the position 1-based; `res` of cluster_reads_llr)"""
+    s = res['sites']
+    theta, n = np.asarray(s['theta'], np.float64), np.asarray(s['n'], np.float64)
+    nc = theta.shape[1] if theta.ndim == 2 else int(res['C'])
+    chrom, strand, pos = np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()
+    with open(path, 'w') as f:
+        f.write('chrom\tstrand\tpos' + ''.join('\ttheta_%d\tN_%d' % (c, c) for c in range(nc)) + '\n')
+        for j in range(len(pos)):
+            f.write('%s\t%s\t%d' % (chrom[j], strand[j], pos[j]) + ''.join('\t%.6f\t%.3f' % (theta[j, c], n[j, c]) for c in range(nc)) + '\n')
+
+
+def write_classes_fit(path, res):
+    """<FileID>_classes_fit.txt: a header line, then per start and number of classes 'C start weights ll BIC iterations converged kept',
+    tab-separated, the weights as '%.6f' joined by commas, ll and BIC as '%.6f', converged and kept as 0 or 1 (`res` of
+    cluster_reads_llr)"""
+    with open(path, 'w') as f:
+        f.write('C\tstart\tweights\tll\tBIC\titerations\tconverged\tkept\n')
+        for r in res['fit']:
+            f.write('%d\t%d\t%s\t%.6f\t%.6f\t%d\t%d\t%d\n' % (r['C'], r['start'], ','.join('%.6f' % v for v in r['w']), r['ll'], r['bic'], r['n_iter'],
+                                                            int(r['converged']), int(r['kept'])))
