@@ -1,8 +1,8 @@
 // nmod_read_class_rows / nmod_read_classes_step — a finite mixture of C classes over the reads, every class with its own modified share
 // at every candidate site, fitted by EM: one step per call, the loop on the host (K22).  The reference project has no
 // such step; the definition is the one in include/nanomod_hip.h (tests/classes_ref.py restates it).  The entries of a read are K19's
-// (read_entries.hpp: rh_fill_entries), the walks are read_walk.hpp's and pos_walk.hpp's, the sort is radix_sort.hpp's and the offsets'
-// scan site_search.hpp's; all on the caller's stream:
+// (read_entries.hpp: the refusals and ChainCall's entries half for the rows; ReadDraw, ReadGeom and read_sum for the E-step), the walks
+// are read_walk.hpp's and pos_walk.hpp's, the sort is radix_sort.hpp's and the offsets' scan site_search.hpp's; all on the caller's stream:
 //   nmod_read_class_rows, once per data set
 //     rh_entries_kernel<., 1>  (read_hmm.hip) entry j of read r writes its site and score to row hoff[r] + j
 //     rc_rows_kernel           a wave per read: s and rread of its rows, the sort key (the site) and one integer atomic per row on
@@ -85,21 +85,14 @@ template <int C, int WAVES>
 __global__ __launch_bounds__(kRwThreads) void rc_read_kernel(RcArgs a) {
   __shared__ unsigned sh_item;
   __shared__ double sh_sum[kRwWaves];
-  constexpr int CLS = WAVES == 1 ? 0 : 1;
-  constexpr int T = WAVES * 64;
-  const int lane = threadIdx.x & 63;
-  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  const unsigned cnt = a.w.count[CLS];
-  auto read_sum = [&](double v) {
-    if constexpr (WAVES == 1) return wave_sum_f64(v); else return block_sum_f64<WAVES>(v, sh_sum);
-  };
+  const ReadGeom<WAVES> geo;
+  const ReadDraw<WAVES> reads(a.w, sh_item);
   for (;;) {
-    const unsigned item = draw_read<WAVES>(a.w, sh_item);
-    if (item >= cnt) break;
-    const int64_t read = (int64_t)a.w.list[CLS][item];
-    const int64_t base = a.hoff[read], m = a.hoff[read + 1] - base;
-    if (m <= 0 || base < 0 || base > a.nrows - m) {             // no entry (or offsets that are not the rows': skipped)
-      if (t == 0) {
+    const ReadRows r = reads.next(a.hoff, a.nrows);
+    if (!r.more) break;
+    const int64_t read = r.read, base = r.base, m = r.m;
+    if (r.none) {                                               // no entry
+      if (geo.t == 0) {
         if (a.gamma) {
 #pragma unroll
           for (int c = 0; c < C; ++c) a.gamma[read * C + c] = 0.0;
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(kRwThreads) void rc_read_kernel(RcArgs a) {
     double l[C], s_pos = 0.0;
 #pragma unroll
     for (int c = 0; c < C; ++c) l[c] = 0.0;
-    for (int64_t k = t; k < m; k += T) {
+    for (int64_t k = geo.t; k < m; k += geo.T) {
       const int64_t row = base + k;
       const int64_t st = a.site[row];
       const double sc = a.s[row];
@@ -129,9 +122,9 @@ __global__ __launch_bounds__(kRwThreads) void rc_read_kernel(RcArgs a) {
       s_pos += fmax(sc, 0.0);
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) l[c] = read_sum(l[c]);
-    s_pos = read_sum(s_pos);
-    if (t == 0) {
+    for (int c = 0; c < C; ++c) l[c] = read_sum<WAVES>(l[c], sh_sum);
+    s_pos = read_sum<WAVES>(s_pos, sh_sum);
+    if (geo.t == 0) {
       double av[C];
       double mx = 0.0;
 #pragma unroll
@@ -311,10 +304,6 @@ static void for_classes(int n_classes, F f) {
   }
 }
 
-static bool rc_offsets_ok(const int64_t* off, int64_t n, int64_t nrows) {
-  return off[0] == 0 && csr_offsets_ok(off, n) && off[n] == nrows;
-}
-
 }  // namespace nmod
 
 using namespace nmod;
@@ -322,44 +311,33 @@ using namespace nmod;
 extern "C" int nmod_read_class_rows(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                                     const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                                     const nmod_class_rows_out* out) {
-  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_class_rows_out)) return NMOD_ERR_INVALID_ARG;
-  if (nrows < 0 || nrows > (int64_t)INT32_MAX || (nreads > 0 && !hoff)) return NMOD_ERR_INVALID_ARG;
-  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, nullptr, 0)) return NMOD_ERR_INVALID_ARG;
-  const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && nreads > 0 && !rc_offsets_ok(hoff, nreads, nrows)) return NMOD_ERR_INVALID_ARG;
-  if (nrows > 0 && (nreads == 0 || nsites == 0)) return NMOD_ERR_INVALID_ARG;
-  const size_t nr = (size_t)nreads, ns = (size_t)nsites, nw = (size_t)nrows;
-  if (host && nreads == 0) {                                    // nothing to enqueue: the offsets of no row
+  ChainCall c(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, !out->site, false);
+  const size_t ns = c.ns, nw = c.nw;
+  if (c.host && nreads == 0) {                                  // nothing to enqueue: the offsets of no row
     if (out->soff) memset(out->soff, 0, (ns + 1) * 8);
     return NMOD_OK;
   }
-  int num_cus = 0;
-  const int rc = select_device(prm, &num_cus);
+  const int rc = select_device(prm, &c.num_cus);
   if (rc != NMOD_OK) return rc;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t tot = host ? (size_t)roff[nreads] : 0;
+  const int num_cus = c.num_cus; hipStream_t stream = c.stream;
   const int passes = nsites < 256 ? 1 : (nsites < 65536 ? 2 : (nsites < 16777216 ? 3 : 4));   // the largest key is nsites
   const bool odd = (passes & 1) != 0;
 
-  RhEntArgs e;
-  rh_ent_args(e, nreads, cs, start, roff, score, nsites, key);
-  e.hoff = hoff; e.nrows = nrows;
+  const RhEntArgs& e = c.e;
   nmod_class_rows_out o = *out;
 
-  // one slab: the read lists, per row the position and the score, the site and the row order where the caller asked for none, the
-  // sort's keys, its second buffers and scratch, the counts where soff is not asked for; for the host entry the inputs and outputs
-  Slab slab(host);
-  const ReadListSpace by_events(slab, nr);
-  const size_t o_xs = slab.take(nw * 16), o_site = o.site ? 0 : slab.take(nw * 4), o_srow = o.srow ? 0 : slab.take(nw * 4);
+  // the call's slab (ChainCall's share: the read list, per row the position and the score, the site where the caller asked for none): the
+  // row order where the caller asked for none, the sort's keys, second buffers and scratch, the counts without soff; a host entry's arguments
+  Slab& slab = c.slab;
+  const size_t o_srow = o.srow ? 0 : slab.take(nw * 4);
   const size_t o_keys = slab.take(nw * 8), o_keys2 = slab.take(nw * 8), o_vals2 = slab.take(nw * 4), o_sort = slab.take(rs_scratch_bytes(nrows));
   const size_t o_cnt = o.soff ? 0 : slab.take((ns + 1) * 8);
-  rh_stage_reads(slab, e, tot);
-  slab.in(e.hoff, (nr + 1) * 8);
+  c.stage();
   slab.out(o.site, nw * 4); slab.out(o.s, nw * 8); slab.out(o.rread, nw * 4); slab.out(o.soff, (ns + 1) * 8); slab.out(o.srow, nw * 4);
   NMOD_HIP(slab.commit(stream, prm->device));
-  e.xs = slab.at<double>(o_xs);
-  e.site = o.site ? o.site : slab.at<int32_t>(o_site);
+  c.bind(o.site);
   int32_t* srow = o.srow ? o.srow : slab.at<int32_t>(o_srow);
   int64_t* soff = o.soff ? o.soff : slab.at<int64_t>(o_cnt);
   uint32_t* spare = slab.at<uint32_t>(o_vals2);
@@ -378,8 +356,7 @@ extern "C" int nmod_read_class_rows(const nmod_params* prm, int64_t nreads, cons
   if (nrows > 0) {
     NMOD_HIP(hipMemsetAsync(e.site, 0xFF, nw * 4, stream));     // a row that no read fills: site -1
     hipLaunchKernelGGL(rc_init_kernel, dim3(persistent_grid(nrows, 256, (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
-    NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
-    rh_fill_entries(e, num_cus, stream);
+    NMOD_HIP(c.entries());
     hipLaunchKernelGGL(rc_rows_kernel, dim3(persistent_grid(nreads, 4, (int64_t)num_cus * 16)), dim3(256), 0, stream, a);
   }
   hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(256), 0, stream, soff, nsites);
@@ -402,8 +379,8 @@ extern "C" int nmod_read_classes_step(const nmod_params* prm, int64_t nreads, in
   const int nc = opts->n_classes;
   const bool host = prm->memspace == NMOD_MEM_HOST;
   if (host) {
-    if (nreads > 0 && !rc_offsets_ok(hoff, nreads, nrows)) return NMOD_ERR_INVALID_ARG;
-    if (!rc_offsets_ok(soff, nsites, nrows)) return NMOD_ERR_INVALID_ARG;
+    if (nreads > 0 && !rh_offsets_ok(hoff, nreads, nrows)) return NMOD_ERR_INVALID_ARG;
+    if (!rh_offsets_ok(soff, nsites, nrows)) return NMOD_ERR_INVALID_ARG;
     double sum = 0.0;
     for (int c = 0; c < nc; ++c) {
       if (!rh_finite_in(w_in[c], kRcLo, kRcHi) && !(nc == 1 && w_in[c] == 1.0)) return NMOD_ERR_INVALID_ARG;

@@ -1,13 +1,14 @@
 // nmod_read_sites_count / nmod_read_hmm / nmod_read_hmm_grad — per read a two-state hidden Markov chain over the candidate sites it covers,
 // emissions from the window sums (K13's llr_win), evaluated by forward-backward as a scan of 2 x 2 non-negative matrices (K19; K21 is the
-// same chain's log-likelihood with its gradient in the two parameters).  The reference
-// project has no such step; the definition is the one in include/nanomod_hip.h (tests/hmm_ref.py restates it).  The walk over the reads is
-// read_walk.hpp's, the site search and the offsets' scan are site_search.hpp's (shared with K16 / K18); all on the caller's stream:
+// same chain's log-likelihood with its gradient in the two parameters).  The reference project has no such step; the
+// definition is the one in include/nanomod_hip.h (tests/hmm_ref.py restates it).  The walk over the reads is read_walk.hpp's, the site
+// search and the offsets' scan are site_search.hpp's (shared with K16 / K18); what the chain entries of K19 - K22 share is
+// read_entries.hpp's (the refusals and ChainCall; ReadGeom, read_sum, and ReadDraw for the entries kernel).  All on the caller's stream:
 //   read_classify_kernel     (read_walk.hpp) a thread per read: the read's class, by its events for the entries, by its entries for the chain
 //   rh_entries_kernel<., 0>  the entries of a read counted: ballots over the sites it covers (nmod_read_sites_count)
 //   sp_scan_kernel           (site_search.hpp) the counts' exclusive scan in place (hoff)
-//   rh_entries_kernel<., 1>  the same walk: entry j of the read writes its site, its position and its score to row hoff[r] + j (K20's
-//                            entry enqueues it too, through read_entries.hpp's rh_fill_entries)
+//   rh_entries_kernel<., 1>  the same walk: entry j of the read writes its site, its position and its score to row hoff[r] + j (every
+//                            chain entry enqueues it through read_entries.hpp's ChainCall and rh_fill_entries)
 //   rh_hmm_kernel<1>         a wave per read of up to NMOD_HMM_WAVE_MAX entries, four waves a workgroup
 //   rh_hmm_kernel<4>         a workgroup of four waves per longer read
 //   rh_grad_kernel<1>, <4>   nmod_read_hmm_grad (K21): the same two forms, the same forward pass; the backward pass forms the terms of the
@@ -52,15 +53,12 @@ template <int WAVES, bool FILL>
 __global__ __launch_bounds__(kRwThreads) void rh_entries_kernel(RhEntArgs a) {
   __shared__ unsigned sh_item;
   __shared__ int sh_tile[kRwWaves];
-  constexpr int CLS = WAVES == 1 ? 0 : 1;
-  constexpr int T = WAVES * 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  const unsigned cnt = a.w.count[CLS];
+  const ReadGeom<WAVES> geo;
+  const ReadDraw<WAVES> reads(a.w, sh_item);
   for (;;) {
-    const unsigned item = draw_read<WAVES>(a.w, sh_item);
-    if (item >= cnt) break;
-    const int64_t read = (int64_t)a.w.list[CLS][item];
+    const ReadRows r = reads.draw();
+    if (!r.more) break;
+    const int64_t read = r.read;
     int64_t begin, n;
     csr_row(a.roff, 0, read, begin, n);
     const int64_t cs = a.cs[read], start = a.start[read];
@@ -75,19 +73,19 @@ __global__ __launch_bounds__(kRwThreads) void rh_entries_kernel(RhEntArgs a) {
       if (m <= 0) continue;
     }
     int64_t done = 0;                                           // the entries in front of the tile
-    for (int64_t s0 = c_lo; s0 < c_hi; s0 += T) {
-      const int64_t s = s0 + t;
+    for (int64_t s0 = c_lo; s0 < c_hi; s0 += geo.T) {
+      const int64_t s = s0 + geo.t;
       double l = 0.0;
       const bool v = s < c_hi && rd.score_at(s, l) && fabs(l) <= kDblMax;
       const unsigned long long b = __ballot(v);
-      int before = __popcll(b & ((1ull << lane) - 1ull)), total = __popcll(b);
+      int before = __popcll(b & ((1ull << geo.lane) - 1ull)), total = __popcll(b);
       if constexpr (WAVES > 1) {
         __syncthreads();                                        // the last tile's words are read
-        if (lane == 0) sh_tile[wave] = total;
+        if (geo.lane == 0) sh_tile[geo.wave] = total;
         __syncthreads();
         total = 0;
 #pragma unroll
-        for (int w = 0; w < WAVES; ++w) { before += w < wave ? sh_tile[w] : 0; total += sh_tile[w]; }
+        for (int w = 0; w < WAVES; ++w) { before += w < geo.wave ? sh_tile[w] : 0; total += sh_tile[w]; }
       }
       if constexpr (FILL) {
         const int64_t j = done + before, row = base + j;
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_entries_kernel(RhEntArgs a) {
       }
       done += total;
     }
-    if constexpr (!FILL) { if (t == 0) a.cnt[read] = done; }
+    if constexpr (!FILL) { if (geo.t == 0) a.cnt[read] = done; }
   }
 }
 
@@ -229,20 +227,16 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
   __shared__ int sh_last[kRwWaves + 1];
   __shared__ double sh_sum[kRwWaves];
   __shared__ RhShared sh_scan;
-  constexpr int CLS = WAVES == 1 ? 0 : 1;
-  constexpr int T = WAVES * 64;
-  constexpr int64_t TS = (int64_t)T * kHmmChunk;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  const unsigned cnt = a.w.count[CLS];
+  const ReadGeom<WAVES> geo;
+  const unsigned cnt = a.w.count[geo.CLS];
   const nmod_hmm_out& o = a.out;
   for (;;) {
     const unsigned item = draw_read<WAVES>(a.w, sh_item);
     if (item >= cnt) break;
-    const int64_t read = (int64_t)a.w.list[CLS][item];
+    const int64_t read = (int64_t)a.w.list[geo.CLS][item];
     const int64_t base = a.hoff[read], m = a.hoff[read + 1] - base;
     if (m <= 0 || base < 0 || base > a.nrows - m) {             // no entry (or offsets that are not the rows': skipped)
-      if (t == 0) {
+      if (geo.t == 0) {
         if (o.n_sites) o.n_sites[read] = 0;
         if (o.n_mod) o.n_mod[read] = 0;
         if (o.n_can) o.n_can[read] = 0;
@@ -259,7 +253,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
     // forward: the vectors, the independent likelihood and the sum of the positive scores, a thread's entries in ascending order
     double s_ind = 0.0, s_pos = 0.0;
     Vec2 fw{a.q, a.pi, 0};
-    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+    for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
       fw = rh_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
         if (a.backward) { alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1; }
         const double s = xs[2 * k + 1], up = fmax(s, 0.0);
@@ -269,9 +263,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
         s_pos += up;
       });
     }
-    double ind, pos;
-    if constexpr (WAVES == 1) { ind = wave_sum_f64(s_ind); pos = wave_sum_f64(s_pos); }
-    else { ind = block_sum_f64<WAVES>(s_ind, sh_sum); pos = block_sum_f64<WAVES>(s_pos, sh_sum); }
+    const double ind = read_sum<WAVES>(s_ind, sh_sum), pos = read_sum<WAVES>(s_pos, sh_sum);
     const double ll = (log(fw.x0 + fw.x1) + (double)fw.e * kLn2) + pos;
 
     // backward: the same scan over the reversed transposes; step k is entry m - 1 - k
@@ -280,9 +272,9 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
       if constexpr (WAVES > 1) __syncthreads();                 // the forward vectors of the other waves are written
       Vec2 bw{1.0, 1.0, 0};
       int tile_prev = 2;                                        // the state of the step in front of the tile (none: not a 1)
-      for (int64_t k0 = 0; k0 < m; k0 += TS) {
+      for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
         int st[kHmmChunk];
-        const int64_t kb = k0 + (int64_t)t * kHmmChunk;
+        const int64_t kb = k0 + (int64_t)geo.t * kHmmChunk;
         bw = rh_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
           const int64_t j = m - 1 - k, row = base + j;
           const double p0 = alpha[2 * j] * x.x0, p1 = alpha[2 * j + 1] * x.x1;
@@ -307,11 +299,11 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
         int prev = __shfl_up(last, 1);
         if constexpr (WAVES > 1) {
           __syncthreads();
-          if (lane == 63) sh_last[wave] = last;
+          if (geo.lane == 63) sh_last[geo.wave] = last;
           __syncthreads();
-          if (lane == 0 && wave > 0) prev = sh_last[wave - 1];
+          if (geo.lane == 0 && geo.wave > 0) prev = sh_last[geo.wave - 1];
         }
-        if (t == 0) prev = tile_prev;
+        if (geo.t == 0) prev = tile_prev;
 #pragma unroll
         for (int c = 0; c < kHmmChunk; ++c) {
           if (kb + c < m) { n_runs += st[c] == 1 && prev != 1; prev = st[c]; }
@@ -320,7 +312,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
       }
       read_counts<WAVES>(sh_cnt, n_mod, n_can, n_runs);
     }
-    if (t == 0) {
+    if (geo.t == 0) {
       if (o.n_sites) o.n_sites[read] = (int32_t)m;
       if (o.n_mod) o.n_mod[read] = n_mod;
       if (o.n_can) o.n_can[read] = n_can;
@@ -350,24 +342,17 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
   __shared__ unsigned sh_item;
   __shared__ double sh_sum[kRwWaves];
   __shared__ RhShared sh_scan;
-  constexpr int CLS = WAVES == 1 ? 0 : 1;
-  constexpr int T = WAVES * 64;
-  constexpr int64_t TS = (int64_t)T * kHmmChunk;
-  const int lane = threadIdx.x & 63;
-  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
+  const ReadGeom<WAVES> geo;
   const RhArgs& a = g.h;
-  const unsigned cnt = a.w.count[CLS];
+  const unsigned cnt = a.w.count[geo.CLS];
   const nmod_hmm_grad_out& o = g.out;
-  auto read_sum = [&](double v) {
-    if constexpr (WAVES == 1) return wave_sum_f64(v); else return block_sum_f64<WAVES>(v, sh_sum);
-  };
   for (;;) {
     const unsigned item = draw_read<WAVES>(a.w, sh_item);
     if (item >= cnt) break;
-    const int64_t read = (int64_t)a.w.list[CLS][item];
+    const int64_t read = (int64_t)a.w.list[geo.CLS][item];
     const int64_t base = a.hoff[read], m = a.hoff[read + 1] - base;
     if (m <= 0 || base < 0 || base > a.nrows - m) {             // no entry (or offsets that are not the rows': skipped)
-      if (t == 0) {
+      if (geo.t == 0) {
         o.ll[read] = 0.0; o.g_eta[read] = 0.0; o.g_lam[read] = 0.0;
         if (o.abs_eta) o.abs_eta[read] = 0.0;
         if (o.abs_lam) o.abs_lam[read] = 0.0;
@@ -381,13 +366,13 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
     // forward: the vectors and the sum of the positive scores, a thread's entries in ascending order
     double s_pos = 0.0;
     Vec2 fw{a.q, a.pi, 0};
-    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+    for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
       fw = rh_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
         alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1;
         s_pos += fmax(xs[2 * k + 1], 0.0);
       });
     }
-    const double pos = read_sum(s_pos);
+    const double pos = read_sum<WAVES>(s_pos, sh_sum);
     const double ll = (log(fw.x0 + fw.x1) + (double)fw.e * kLn2) + pos;
 
     // the forward vectors of the other lanes (waves) are written
@@ -396,7 +381,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
     // backward: step k is entry j = m - 1 - k; the term of transition j for j >= 1, the posterior of the first entry at j = 0
     double s_p = 0.0, s_l = 0.0, s_ap = 0.0, s_al = 0.0, s_post = 0.0;
     Vec2 bw{1.0, 1.0, 0};
-    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+    for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
       bw = rh_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
         const int64_t j = m - 1 - k;
         if (j == 0) {
@@ -418,8 +403,9 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
       });
     }
     // (the posterior lives in one thread and the others add 0: its sum is the value itself)
-    const double sum_p = read_sum(s_p), sum_l = read_sum(s_l), sum_ap = read_sum(s_ap), sum_al = read_sum(s_al), post0 = read_sum(s_post);
-    if (t == 0) {
+    const double sum_p = read_sum<WAVES>(s_p, sh_sum), sum_l = read_sum<WAVES>(s_l, sh_sum), sum_ap = read_sum<WAVES>(s_ap, sh_sum);
+    const double sum_al = read_sum<WAVES>(s_al, sh_sum), post0 = read_sum<WAVES>(s_post, sh_sum);
+    if (geo.t == 0) {
       const double first = post0 - a.pi;
       o.ll[read] = ll;
       o.g_eta[read] = first + g.piq * sum_p;
@@ -496,32 +482,22 @@ extern "C" int nmod_read_sites_count(const nmod_params* prm, int64_t nreads, con
 extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                              const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                              const nmod_hmm_opts* opts, const nmod_hmm_out* out) {
-  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_hmm_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_hmm_out)) return NMOD_ERR_INVALID_ARG;
-  if (!rh_finite_in(opts->pi, 1e-9, 1.0 - 1e-9) || !rh_finite_in(opts->length, 1e-3, 1e9)) return NMOD_ERR_INVALID_ARG;
+  if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
   if (!(opts->call_post > 0.5) || !(opts->call_post < 1.0)) return NMOD_ERR_INVALID_ARG;
-  if (nrows < 0 || nrows > (int64_t)INT32_MAX || (nreads > 0 && !hoff)) return NMOD_ERR_INVALID_ARG;
-  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, nullptr, 0)) return NMOD_ERR_INVALID_ARG;
-  const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && nreads > 0 && (hoff[0] != 0 || !csr_offsets_ok(hoff, nreads) || hoff[nreads] != nrows)) return NMOD_ERR_INVALID_ARG;
-  if (nrows > 0 && (nreads == 0 || nsites == 0)) return NMOD_ERR_INVALID_ARG;
-  const size_t nr = (size_t)nreads, ns = (size_t)nsites, nw = (size_t)nrows;
-  if (host && nreads == 0) {                                    // nothing to enqueue: the site counts of no read
+  ChainCall c(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, !out->site);
+  const size_t nr = c.nr, ns = c.ns, nw = c.nw;
+  if (c.host && nreads == 0) {                                  // nothing to enqueue: the site counts of no read
     if (out->site_n) memset(out->site_n, 0, ns * 4);
     if (out->site_mod) memset(out->site_mod, 0, ns * 4);
     if (out->site_can) memset(out->site_can, 0, ns * 4);
     return NMOD_OK;
   }
-  int num_cus = 0;
-  const int rc = select_device(prm, &num_cus);
+  const int rc = select_device(prm, &c.num_cus);
   if (rc != NMOD_OK) return rc;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t tot = host ? (size_t)roff[nreads] : 0;
 
-  RhEntArgs e;
-  rh_ent_args(e, nreads, cs, start, roff, score, nsites, key);
-  e.hoff = hoff; e.nrows = nrows;
   RhArgs a;
   memset(&a, 0, sizeof(a));
   a.nreads = nreads; a.nrows = nrows; a.nsites = nsites;
@@ -531,62 +507,45 @@ extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32
   const nmod_hmm_out& o = a.out;
   a.backward = o.post || o.state || o.n_mod || o.n_can || o.n_runs || o.site_n || o.site_mod || o.site_can;
 
-  // one slab: the read lists of both walks, per row the position and the score, the forward vector, and the site where the caller asked
-  // for none; for the host entry the inputs and outputs as well
-  Slab slab(host);
-  const ReadListSpace by_events(slab, nr), by_entries(slab, nr);
-  const size_t o_xs = slab.take(nw * 16), o_alpha = slab.take(a.backward ? nw * 16 : 0), o_site = o.site ? 0 : slab.take(nw * 4);
-  rh_stage_reads(slab, e, tot);
-  slab.in(e.hoff, (nr + 1) * 8);
+  // the call's slab (ChainCall's share: the read lists of both walks, per row the position and the score, and the site where the caller
+  // asked for none): the forward vector; for the host entry the inputs and outputs as well
+  Slab& slab = c.slab;
+  const size_t o_alpha = slab.take(a.backward ? nw * 16 : 0);
+  c.stage();
   slab.out(a.out.post, nw * 8); slab.out(a.out.site, nw * 4); slab.out(a.out.state, nw);
   slab.out(a.out.n_sites, nr * 4); slab.out(a.out.n_mod, nr * 4); slab.out(a.out.n_can, nr * 4); slab.out(a.out.n_runs, nr * 4);
   slab.out(a.out.ll, nr * 8); slab.out(a.out.ll_indep, nr * 8); slab.out(a.out.status, nr);
   slab.out(a.out.site_n, ns * 4); slab.out(a.out.site_mod, ns * 4); slab.out(a.out.site_can, ns * 4);
-  NMOD_HIP(slab.commit(stream, prm->device));
-  e.xs = slab.at<double>(o_xs);
-  e.site = o.site ? o.site : slab.at<int32_t>(o_site);
-  a.hoff = e.hoff; a.xs = e.xs; a.site = e.site; a.alpha = slab.at<double>(o_alpha);
+  NMOD_HIP(slab.commit(c.stream, prm->device));
+  c.bind(o.site);
+  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha);
 
-  if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, stream));
-  if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, stream));
-  if (o.site_can) NMOD_HIP(hipMemsetAsync(o.site_can, 0, ns * 4, stream));
+  if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, c.stream));
+  if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, c.stream));
+  if (o.site_can) NMOD_HIP(hipMemsetAsync(o.site_can, 0, ns * 4, c.stream));
   if (nreads > 0) {
-    if (nrows > 0) {
-      NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
-      rh_fill_entries(e, num_cus, stream);
-    }
-    NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
-    rh_launch(a, rh_hmm_kernel<1>, rh_hmm_kernel<kRwWaves>, num_cus, stream);
+    NMOD_HIP(c.lists(a.w));
+    rh_launch(a, rh_hmm_kernel<1>, rh_hmm_kernel<kRwWaves>, c.num_cus, c.stream);
   }
-  return launches_end(slab, stream);
+  return launches_end(slab, c.stream);
 }
 
 extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                                   const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                                   const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
-  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_hmm_grad_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_hmm_grad_out)) return NMOD_ERR_INVALID_ARG;
-  if (!rh_finite_in(opts->pi, 1e-9, 1.0 - 1e-9) || !rh_finite_in(opts->length, 1e-3, 1e9)) return NMOD_ERR_INVALID_ARG;
-  if (nrows < 0 || nrows > (int64_t)INT32_MAX || (nreads > 0 && !hoff)) return NMOD_ERR_INVALID_ARG;
-  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, nullptr, 0)) return NMOD_ERR_INVALID_ARG;
-  const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && nreads > 0 && (hoff[0] != 0 || !csr_offsets_ok(hoff, nreads) || hoff[nreads] != nrows)) return NMOD_ERR_INVALID_ARG;
-  if (nrows > 0 && (nreads == 0 || nsites == 0)) return NMOD_ERR_INVALID_ARG;
-  const size_t nr = (size_t)nreads, nw = (size_t)nrows;
-  if (host && nreads == 0) {                                    // nothing to enqueue: the sums of no read
+  if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
+  ChainCall c(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, true);
+  const size_t nr = c.nr, nw = c.nw;
+  if (c.host && nreads == 0) {                                  // nothing to enqueue: the sums of no read
     if (out->sums) memset(out->sums, 0, 8 * sizeof(double));
     return NMOD_OK;
   }
-  int num_cus = 0;
-  const int rc = select_device(prm, &num_cus);
+  const int rc = select_device(prm, &c.num_cus);
   if (rc != NMOD_OK) return rc;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t tot = host ? (size_t)roff[nreads] : 0;
 
-  RhEntArgs e;
-  rh_ent_args(e, nreads, cs, start, roff, score, nsites, key);
-  e.hoff = hoff; e.nrows = nrows;
   RgArgs g;
   memset(&g, 0, sizeof(g));
   RhArgs& a = g.h;
@@ -597,32 +556,25 @@ extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const 
   g.out = *out;
   nmod_hmm_grad_out& o = g.out;
 
-  // one slab: the read lists of both walks, per row the position and the score, the forward vector and the site; the per-read values
-  // the sums are taken from where the caller asked for the sums without them; for the host entry the inputs and outputs as well
-  Slab slab(host);
-  const ReadListSpace by_events(slab, nr), by_entries(slab, nr);
-  const size_t o_xs = slab.take(nw * 16), o_alpha = slab.take(nw * 16), o_site = slab.take(nw * 4);
+  // the call's slab (ChainCall's share: the read lists of both walks, per row the position, the score and the site): the forward vector; the
+  // per-read values the sums are taken from where the caller asked for the sums without them; for the host entry the inputs and outputs
+  Slab& slab = c.slab;
+  const size_t o_alpha = slab.take(nw * 16);
   const size_t o_ll = o.ll ? 0 : slab.take(nr * 8), o_ge = o.g_eta ? 0 : slab.take(nr * 8), o_gl = o.g_lam ? 0 : slab.take(nr * 8);
-  rh_stage_reads(slab, e, tot);
-  slab.in(e.hoff, (nr + 1) * 8);
+  c.stage();
   slab.out(o.ll, nr * 8); slab.out(o.g_eta, nr * 8); slab.out(o.g_lam, nr * 8); slab.out(o.abs_eta, nr * 8); slab.out(o.abs_lam, nr * 8);
   slab.out(o.status, nr); slab.out(o.sums, 8 * sizeof(double));
-  NMOD_HIP(slab.commit(stream, prm->device));
-  e.xs = slab.at<double>(o_xs);
-  e.site = slab.at<int32_t>(o_site);
-  a.hoff = e.hoff; a.xs = e.xs; a.site = e.site; a.alpha = slab.at<double>(o_alpha);
+  NMOD_HIP(slab.commit(c.stream, prm->device));
+  c.bind(nullptr);
+  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha);
   if (!o.ll) o.ll = slab.at<double>(o_ll);
   if (!o.g_eta) o.g_eta = slab.at<double>(o_ge);
   if (!o.g_lam) o.g_lam = slab.at<double>(o_gl);
 
   if (nreads > 0) {
-    if (nrows > 0) {
-      NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
-      rh_fill_entries(e, num_cus, stream);
-    }
-    NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
-    rh_launch(g, rh_grad_kernel<1>, rh_grad_kernel<kRwWaves>, num_cus, stream);
+    NMOD_HIP(c.lists(a.w));
+    rh_launch(g, rh_grad_kernel<1>, rh_grad_kernel<kRwWaves>, c.num_cus, c.stream);
   }
-  if (o.sums) hipLaunchKernelGGL(rh_grad_sums_kernel, dim3(1), dim3(256), 0, stream, nreads, a.hoff, nrows, o.ll, o.g_eta, o.g_lam, o.sums);
-  return launches_end(slab, stream);
+  if (o.sums) hipLaunchKernelGGL(rh_grad_sums_kernel, dim3(1), dim3(256), 0, c.stream, nreads, a.hoff, nrows, o.ll, o.g_eta, o.g_lam, o.sums);
+  return launches_end(slab, c.stream);
 }

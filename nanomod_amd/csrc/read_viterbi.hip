@@ -1,9 +1,9 @@
 // nmod_read_viterbi — per read the jointly most probable state path of K19's two-state chain over the candidate sites it covers, the
 // max-marginal margin of every entry and the path's log-probability (K20).  The reference project has no such step; the
-// definition is the one in include/nanomod_hip.h (tests/viterbi_ref.py restates it).  The entries of a read and the launch of their kernel
-// are read_entries.hpp's (shared with K19), the walk over the reads is read_walk.hpp's; all on the caller's stream:
+// definition is the one in include/nanomod_hip.h (tests/viterbi_ref.py restates it).  What the chain entries of K19 - K22 share is
+// read_entries.hpp's (the refusals and ChainCall, which enqueues the entries; ReadGeom, read_sum); all on the caller's stream:
 //   read_classify_kernel     (read_walk.hpp) a thread per read: the read's class, by its events for the entries, by its entries for the chain
-//   rh_entries_kernel<., 1>  (read_hmm.hip, through rh_fill_entries) entry j of the read writes its site, position and score to row hoff[r] + j
+//   rh_entries_kernel<., 1>  (read_hmm.hip, through ChainCall) entry j of the read writes its site, position and score to row hoff[r] + j
 //   rv_viterbi_kernel<1>     a wave per read of up to NMOD_HMM_WAVE_MAX entries, four waves a workgroup
 //   rv_viterbi_kernel<4>     a workgroup of four waves per longer read
 // K19's scan in the (max, +) algebra: rv_tile<., BWD> is rh_tile with a sum for every product and the larger for every sum, no exponent
@@ -153,20 +153,16 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
   __shared__ int sh_z;
   __shared__ double sh_sum[kRwWaves];
   __shared__ RvShared sh_scan;
-  constexpr int CLS = WAVES == 1 ? 0 : 1;
-  constexpr int T = WAVES * 64;
-  constexpr int64_t TS = (int64_t)T * kHmmChunk;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int t = WAVES == 1 ? lane : (int)threadIdx.x;
-  const unsigned cnt = a.w.count[CLS];
+  const ReadGeom<WAVES> geo;
+  const unsigned cnt = a.w.count[geo.CLS];
   const nmod_vit_out& o = a.out;
   for (;;) {
     const unsigned item = draw_read<WAVES>(a.w, sh_item);
     if (item >= cnt) break;
-    const int64_t read = (int64_t)a.w.list[CLS][item];
+    const int64_t read = (int64_t)a.w.list[geo.CLS][item];
     const int64_t base = a.hoff[read], m = a.hoff[read + 1] - base;
     if (m <= 0 || base < 0 || base > a.nrows - m) {             // no entry (or offsets that are not the rows': skipped)
-      if (t == 0) {
+      if (geo.t == 0) {
         if (o.n_sites) o.n_sites[read] = 0;
         if (o.n_mod) o.n_mod[read] = 0;
         if (o.n_runs) o.n_runs[read] = 0;
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
     // forward: the vectors, the back-pointers and the sum of the positive scores, a thread's entries in ascending order
     double s_pos = 0.0;
     LVec fw{a.lq, a.lpi};
-    for (int64_t k0 = 0; k0 < m; k0 += TS) {
+    for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
       fw = rv_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const LVec& x, unsigned psi) {
         if (a.back) { alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1; }
         if (a.trace) psi_row[k] = (uint8_t)psi;
@@ -193,8 +189,7 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
         }
       });
     }
-    double pos;
-    if constexpr (WAVES == 1) pos = wave_sum_f64(s_pos); else pos = block_sum_f64<WAVES>(s_pos, sh_sum);
+    const double pos = read_sum<WAVES>(s_pos, sh_sum);
     const int z_last = fw.x1 > fw.x0 ? 1 : 0;
     const double vit = (z_last ? fw.x1 : fw.x0) + pos;
 
@@ -206,8 +201,8 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
     if (a.trace) {
       int z_in = 0;                                             // the state of the step in front of the tile (none: step 0 is a constant)
       int tile_prev = 2;                                        // the same for the runs (none: not a 1)
-      for (int64_t k0 = 0; k0 < m; k0 += TS) {
-        const int64_t kb = k0 + (int64_t)t * kHmmChunk;
+      for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
+        const int64_t kb = k0 + (int64_t)geo.t * kHmmChunk;
         unsigned g[kHmmChunk];
 #pragma unroll
         for (int c = 0; c < kHmmChunk; ++c) {
@@ -220,18 +215,18 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
           const unsigned f = (unsigned)__shfl_up((int)h, d);
-          if (lane >= d) h = rv_compose(f, h);
+          if (geo.lane >= d) h = rv_compose(f, h);
         }
         int z = z_in;
         if constexpr (WAVES > 1) {
           __syncthreads();                                      // the last tile's maps, state and run ends are read
-          if (lane == 63) sh_map[wave] = h;
+          if (geo.lane == 63) sh_map[geo.wave] = h;
           __syncthreads();
 #pragma unroll
-          for (int w = 0; w < WAVES - 1; ++w) if (w < wave) z = rv_apply(sh_map[w], z);
+          for (int w = 0; w < WAVES - 1; ++w) if (w < geo.wave) z = rv_apply(sh_map[w], z);
         }
         const unsigned before = (unsigned)__shfl_up((int)h, 1);
-        if (lane > 0) z = rv_apply(before, z);
+        if (geo.lane > 0) z = rv_apply(before, z);
         int st[kHmmChunk];
 #pragma unroll
         for (int c = 0; c < kHmmChunk; ++c) {
@@ -255,12 +250,12 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
         for (int c = 0; c < kHmmChunk; ++c) if (kb + c < m) last = st[c];
         int prev = __shfl_up(last, 1);
         if constexpr (WAVES > 1) {
-          if (lane == 63) sh_last[wave] = last;
-          if (t == T - 1) sh_z = z;
+          if (geo.lane == 63) sh_last[geo.wave] = last;
+          if (geo.t == geo.T - 1) sh_z = z;
           __syncthreads();
-          if (lane == 0 && wave > 0) prev = sh_last[wave - 1];
+          if (geo.lane == 0 && geo.wave > 0) prev = sh_last[geo.wave - 1];
         }
-        if (t == 0) prev = tile_prev;
+        if (geo.t == 0) prev = tile_prev;
 #pragma unroll
         for (int c = 0; c < kHmmChunk; ++c) {
           if (kb + c < m) { n_runs += st[c] == 1 && prev != 1; prev = st[c]; }
@@ -274,14 +269,14 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
     // backward, for delta: the same scan over the reversed transposes from (0, 0); step k is entry m - 1 - k
     if (a.back) {
       LVec bw{0.0, 0.0};
-      for (int64_t k0 = 0; k0 < m; k0 += TS) {
+      for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
         bw = rv_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const LVec& x, unsigned) {
           const int64_t j = m - 1 - k;
           o.delta[base + j] = (alpha[2 * j + 1] + x.x1) - (alpha[2 * j] + x.x0);
         });
       }
     }
-    if (t == 0) {
+    if (geo.t == 0) {
       if (o.n_sites) o.n_sites[read] = (int32_t)m;
       if (o.n_mod) o.n_mod[read] = n_mod;
       if (o.n_runs) o.n_runs[read] = n_runs;
@@ -298,30 +293,20 @@ using namespace nmod;
 extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                                  const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                                  const nmod_vit_opts* opts, const nmod_vit_out* out) {
-  if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
+  if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_vit_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_vit_out)) return NMOD_ERR_INVALID_ARG;
-  if (!rh_finite_in(opts->pi, 1e-9, 1.0 - 1e-9) || !rh_finite_in(opts->length, 1e-3, 1e9)) return NMOD_ERR_INVALID_ARG;
-  if (nrows < 0 || nrows > (int64_t)INT32_MAX || (nreads > 0 && !hoff)) return NMOD_ERR_INVALID_ARG;
-  if (!sp_walk_args_ok(prm, nreads, cs, start, roff, score, nsites, key, nullptr, 0)) return NMOD_ERR_INVALID_ARG;
-  const bool host = prm->memspace == NMOD_MEM_HOST;
-  if (host && nreads > 0 && (hoff[0] != 0 || !csr_offsets_ok(hoff, nreads) || hoff[nreads] != nrows)) return NMOD_ERR_INVALID_ARG;
-  if (nrows > 0 && (nreads == 0 || nsites == 0)) return NMOD_ERR_INVALID_ARG;
-  const size_t nr = (size_t)nreads, ns = (size_t)nsites, nw = (size_t)nrows;
-  if (host && nreads == 0) {                                    // nothing to enqueue: the site counts of no read
+  if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
+  ChainCall c(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows, !out->site);
+  const size_t nr = c.nr, ns = c.ns, nw = c.nw;
+  if (c.host && nreads == 0) {                                  // nothing to enqueue: the site counts of no read
     if (out->site_n) memset(out->site_n, 0, ns * 4);
     if (out->site_mod) memset(out->site_mod, 0, ns * 4);
     return NMOD_OK;
   }
-  int num_cus = 0;
-  const int rc = select_device(prm, &num_cus);
+  const int rc = select_device(prm, &c.num_cus);
   if (rc != NMOD_OK) return rc;
-  hipStream_t stream = (hipStream_t)prm->stream;
-  const size_t tot = host ? (size_t)roff[nreads] : 0;
 
-  RhEntArgs e;
-  rh_ent_args(e, nreads, cs, start, roff, score, nsites, key);
-  e.hoff = hoff; e.nrows = nrows;
   RvArgs a;
   memset(&a, 0, sizeof(a));
   a.nreads = nreads; a.nrows = nrows; a.nsites = nsites;
@@ -332,32 +317,24 @@ extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const i
   a.trace = o.path || o.n_mod || o.n_runs || o.site_mod;
   a.back = o.delta != nullptr;
 
-  // one slab: the read lists of both walks, per row the position and the score, the forward vector (delta) and the back-pointers (the
-  // path), and the site where the caller asked for none; for the host entry the inputs and outputs as well
-  Slab slab(host);
-  const ReadListSpace by_events(slab, nr), by_entries(slab, nr);
-  const size_t o_xs = slab.take(nw * 16), o_alpha = slab.take(a.back ? nw * 16 : 0), o_psi = slab.take(a.trace ? nw : 0);
-  const size_t o_site = o.site ? 0 : slab.take(nw * 4);
-  rh_stage_reads(slab, e, tot);
-  slab.in(e.hoff, (nr + 1) * 8);
+  // the call's slab (ChainCall's share: the read lists of both walks, per row the position and the score, and the site where the caller
+  // asked for none): the forward vector (delta) and the back-pointers (the path); for the host entry the inputs and outputs as well
+  Slab& slab = c.slab;
+  const size_t o_alpha = slab.take(a.back ? nw * 16 : 0), o_psi = slab.take(a.trace ? nw : 0);
+  c.stage();
   slab.out(a.out.path, nw); slab.out(a.out.site, nw * 4); slab.out(a.out.delta, nw * 8);
   slab.out(a.out.n_sites, nr * 4); slab.out(a.out.n_mod, nr * 4); slab.out(a.out.n_runs, nr * 4);
   slab.out(a.out.vit, nr * 8); slab.out(a.out.status, nr);
   slab.out(a.out.site_n, ns * 4); slab.out(a.out.site_mod, ns * 4);
-  NMOD_HIP(slab.commit(stream, prm->device));
-  e.xs = slab.at<double>(o_xs);
-  e.site = o.site ? o.site : slab.at<int32_t>(o_site);
-  a.hoff = e.hoff; a.xs = e.xs; a.site = e.site; a.alpha = slab.at<double>(o_alpha); a.psi = slab.at<uint8_t>(o_psi);
+  NMOD_HIP(slab.commit(c.stream, prm->device));
+  c.bind(o.site);
+  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha); a.psi = slab.at<uint8_t>(o_psi);
 
-  if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, stream));
-  if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, stream));
+  if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, c.stream));
+  if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, c.stream));
   if (nreads > 0) {
-    if (nrows > 0) {
-      NMOD_HIP(by_events.fill(slab, e.roff, nreads, num_cus, stream, e.w));
-      rh_fill_entries(e, num_cus, stream);
-    }
-    NMOD_HIP(by_entries.fill(slab, a.hoff, nreads, num_cus, stream, a.w, NMOD_HMM_WAVE_MAX));
-    rh_launch(a, rv_viterbi_kernel<1>, rv_viterbi_kernel<kRwWaves>, num_cus, stream);
+    NMOD_HIP(c.lists(a.w));
+    rh_launch(a, rv_viterbi_kernel<1>, rv_viterbi_kernel<kRwWaves>, c.num_cus, c.stream);
   }
-  return launches_end(slab, stream);
+  return launches_end(slab, c.stream);
 }

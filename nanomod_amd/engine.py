@@ -1008,19 +1008,30 @@ def pair_linkage_host(sa, sb, prow_off, *, min_reads=20, ci_level=0.95, max_iter
 HMM_OUTPUTS = L.HMM_ENTRY_FIELDS + L.HMM_READ_FIELDS + L.HMM_SITE_FIELDS
 
 
-def _hmm_opts(pi, length, call_post, want):
-    """nmod_hmm_opts from the Python arguments; ValueError for what the C entry refuses"""
-    pi, length, call_post = float(pi), float(length), float(call_post)
+def _check_chain(pi, length):
+    """the two parameters of the read chain (K19, K20, K21) as floats; ValueError outside the ranges the C entries accept"""
+    pi, length = float(pi), float(length)
     if not 1e-9 <= pi <= 1.0 - 1e-9:
         raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
     if not 1e-3 <= length <= 1e9:
         raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
+    return pi, length
+
+
+def _check_want(want, outputs):
+    want = tuple(want)
+    if any(w not in outputs for w in want):
+        raise ValueError('want must name outputs of %s' % ', '.join(outputs))
+    return want
+
+
+def _hmm_opts(pi, length, call_post, want):
+    """nmod_hmm_opts from the Python arguments; ValueError for what the C entry refuses"""
+    call_post = float(call_post)
+    pi, length = _check_chain(pi, length)
     if not 0.5 < call_post < 1.0:
         raise ValueError('call_post must lie inside (0.5, 1), not %r' % (call_post,))
-    want = tuple(want)
-    if any(w not in HMM_OUTPUTS for w in want):
-        raise ValueError('want must name outputs of %s' % ', '.join(HMM_OUTPUTS))
-    return L.make_hmm_opts(pi, length, call_post), want
+    return L.make_hmm_opts(pi, length, call_post), _check_want(want, HMM_OUTPUTS)
 
 
 def _check_hmm_counts(nreads, nsites, nrows):
@@ -1053,6 +1064,38 @@ def read_sites_host(cs, start, roff, score, key, device=0):
     return hoff
 
 
+def _check_chain_offsets(hoff, nreads):
+    """hoff of a host chain entry (its last element is the entry's nrows: _check_class_offsets without the end)"""
+    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
+    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
+        raise ValueError('hoff must start at 0 and never decrease')
+    return hoff
+
+
+def _chain_host(entry, make_out, shapes, opts, reads, hoff, device):
+    """What the host wrappers of the chain entries (K19 .. K22) share after the checks of their own arguments.  entry: the C entry's
+    name; make_out: its out struct from pointers by name; shapes(nrows, nreads, nsites): the table of its outputs; opts: its opts
+    struct, None for an entry without one (the class rows); reads: (cs, start, roff, score, key); hoff: None, computed here.
+    Returns the outputs and hoff."""
+    cs, start, roff, score, key, nreads = _host_site_reads(*reads)
+    if hoff is None:
+        hoff = read_sites_host(cs, start, roff, score, key, device)
+    hoff = _check_chain_offsets(hoff, nreads)
+    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
+    if opts is None and nrows > 0 and (nreads == 0 or key.shape[0] == 0):   # (with opts this refusal is the library's, as it has been)
+        raise ValueError('rows need reads and sites')
+    shapes = shapes(nrows, nreads, key.shape[0])
+    res = _host_outputs(shapes, fill=shapes)
+    lib = L.load()
+    _join_warm_up(device)
+    out = make_out(**_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, entry, prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key), _np_ptr(hoff), nrows,
+          *(() if opts is None else (C.byref(opts),)), C.byref(out))
+    res['hoff'] = hoff
+    return res
+
+
 def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, device=0):
     """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, include/nanomod_hip.h) on host-resident
     reads: the arguments of read_sites_host and the hoff it gives (None: computed here).  pi: the stationary modified share; length: the
@@ -1060,24 +1103,9 @@ def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.
     named in `want`: per entry post (float64), site (int32, the index into key), state (uint8: 1 modified, 0 canonical, 2 neither); per
     read n_sites, n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod,
     site_can (int32)."""
-    lib = L.load()
     opts, want = _hmm_opts(pi, length, call_post, want)
-    if hoff is None:
-        hoff = read_sites_host(cs, start, roff, score, key, device)
-    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
-    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
-    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
-        raise ValueError('hoff must start at 0 and never decrease')
-    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
-    shapes = _hmm_shapes(want, nrows, nreads, key.shape[0])
-    res = _host_outputs(shapes, fill=shapes)
-    _join_warm_up(device)
-    out = L.make_hmm_out(**_np_ptrs(res))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_read_hmm', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
-          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
-    res['hoff'] = hoff
-    return res
+    return _chain_host('nmod_read_hmm', L.make_hmm_out, lambda nrows, nreads, nsites: _hmm_shapes(want, nrows, nreads, nsites), opts,
+                       (cs, start, roff, score, key), hoff, device)
 
 
 VIT_OUTPUTS = L.VIT_ENTRY_FIELDS + L.VIT_READ_FIELDS + L.VIT_SITE_FIELDS
@@ -1085,15 +1113,8 @@ VIT_OUTPUTS = L.VIT_ENTRY_FIELDS + L.VIT_READ_FIELDS + L.VIT_SITE_FIELDS
 
 def _vit_opts(pi, length, want):
     """nmod_vit_opts from the Python arguments; ValueError for what the C entry refuses"""
-    pi, length = float(pi), float(length)
-    if not 1e-9 <= pi <= 1.0 - 1e-9:
-        raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
-    if not 1e-3 <= length <= 1e9:
-        raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
-    want = tuple(want)
-    if any(w not in VIT_OUTPUTS for w in want):
-        raise ValueError('want must name outputs of %s' % ', '.join(VIT_OUTPUTS))
-    return L.make_vit_opts(pi, length), want
+    pi, length = _check_chain(pi, length)
+    return L.make_vit_opts(pi, length), _check_want(want, VIT_OUTPUTS)
 
 
 def _vit_shapes(want, nrows, nreads, nsites):
@@ -1108,24 +1129,9 @@ def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=
     the state on the most probable path), site (int32, the index into key), delta (float64, the max-marginal margin of state 1 over
     state 0); per read n_sites, n_mod, n_runs (int32), vit (float64, the path's log-probability on ll's scale), status (uint8,
     L.HMM_NO_SITE); per site site_n, site_mod (int32)."""
-    lib = L.load()
     opts, want = _vit_opts(pi, length, want)
-    if hoff is None:
-        hoff = read_sites_host(cs, start, roff, score, key, device)
-    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
-    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
-    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
-        raise ValueError('hoff must start at 0 and never decrease')
-    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
-    shapes = _vit_shapes(want, nrows, nreads, key.shape[0])
-    res = _host_outputs(shapes, fill=shapes)
-    _join_warm_up(device)
-    out = L.make_vit_out(**_np_ptrs(res))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_read_viterbi', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
-          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
-    res['hoff'] = hoff
-    return res
+    return _chain_host('nmod_read_viterbi', L.make_vit_out, lambda nrows, nreads, nsites: _vit_shapes(want, nrows, nreads, nsites), opts,
+                       (cs, start, roff, score, key), hoff, device)
 
 
 HMM_GRAD_OUTPUTS = L.HMM_GRAD_READ_FIELDS + ('sums',)
@@ -1133,15 +1139,8 @@ HMM_GRAD_OUTPUTS = L.HMM_GRAD_READ_FIELDS + ('sums',)
 
 def _hmm_grad_opts(pi, length, want):
     """nmod_hmm_grad_opts from the Python arguments; ValueError for what the C entry refuses"""
-    pi, length = float(pi), float(length)
-    if not 1e-9 <= pi <= 1.0 - 1e-9:
-        raise ValueError('pi must lie in 1e-9 .. 1 - 1e-9, not %r' % (pi,))
-    if not 1e-3 <= length <= 1e9:
-        raise ValueError('length must lie in 1e-3 .. 1e9 bases, not %r' % (length,))
-    want = tuple(want)
-    if any(w not in HMM_GRAD_OUTPUTS for w in want):
-        raise ValueError('want must name outputs of %s' % ', '.join(HMM_GRAD_OUTPUTS))
-    return L.make_hmm_grad_opts(pi, length), want
+    pi, length = _check_chain(pi, length)
+    return L.make_hmm_grad_opts(pi, length), _check_want(want, HMM_GRAD_OUTPUTS)
 
 
 def _hmm_grad_shapes(want, nreads):
@@ -1155,24 +1154,9 @@ def read_hmm_grad_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length
     and those named in `want`: per read ll (read_hmm_host's, bit for bit), g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
     L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS: the sums over the reads of ll, the gradient and its products, the reads with an
     entry and the entries) — what readllr.fit_hmm takes per evaluation."""
-    lib = L.load()
     opts, want = _hmm_grad_opts(pi, length, want)
-    if hoff is None:
-        hoff = read_sites_host(cs, start, roff, score, key, device)
-    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
-    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
-    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
-        raise ValueError('hoff must start at 0 and never decrease')
-    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
-    shapes = _hmm_grad_shapes(want, nreads)
-    res = _host_outputs(shapes, fill=shapes)
-    _join_warm_up(device)
-    out = L.make_hmm_grad_out(**_np_ptrs(res))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_read_hmm_grad', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
-          _np_ptr(hoff), nrows, C.byref(opts), C.byref(out))
-    res['hoff'] = hoff
-    return res
+    return _chain_host('nmod_read_hmm_grad', L.make_hmm_grad_out, lambda nrows, nreads, nsites: _hmm_grad_shapes(want, nreads), opts,
+                       (cs, start, roff, score, key), hoff, device)
 
 
 CLASS_ROWS_OUTPUTS = L.CLASS_ROWS_FIELDS
@@ -1188,10 +1172,7 @@ def _classes_opts(n_classes, want):
     """nmod_classes_opts from the Python arguments; ValueError for what the C entry refuses"""
     if int(n_classes) != n_classes or not 1 <= int(n_classes) <= L.CLASSES_MAX:
         raise ValueError('n_classes must be an integer in 1 .. %d, not %r' % (L.CLASSES_MAX, n_classes))
-    want = tuple(want)
-    if any(w not in CLASSES_OUTPUTS for w in want):
-        raise ValueError('want must name outputs of %s' % ', '.join(CLASSES_OUTPUTS))
-    return L.make_classes_opts(int(n_classes)), want
+    return L.make_classes_opts(int(n_classes)), _check_want(want, CLASSES_OUTPUTS)
 
 
 def _classes_shapes(want, nreads, nsites, nc):
@@ -1231,28 +1212,10 @@ def read_class_rows_host(cs, start, roff, score, key, hoff=None, *, want=CLASS_R
     read_hmm_host.  Returns a dict of numpy arrays, hoff and those named in `want`: per row site (int32), s (float64, the read's
     window sum there) and rread (int32, the row's read); soff (int64[nsites + 1]) and srow (int32[nrows]): the rows of site j are
     srow[soff[j]:soff[j + 1]] in ascending row index."""
-    want = tuple(want)
-    if any(w not in CLASS_ROWS_OUTPUTS for w in want):
-        raise ValueError('want must name outputs of %s' % ', '.join(CLASS_ROWS_OUTPUTS))
-    cs, start, roff, score, key, nreads = _host_site_reads(cs, start, roff, score, key)
-    if hoff is None:
-        hoff = read_sites_host(cs, start, roff, score, key, device)
-    hoff = _side(hoff, np.int64, nreads + 1, 'hoff', 'nreads + 1', optional=False)
-    if hoff[0] != 0 or bool(np.any(np.diff(hoff) < 0)):
-        raise ValueError('hoff must start at 0 and never decrease')
-    nrows = _check_hmm_counts(nreads, key.shape[0], int(hoff[-1]))
-    if nrows > 0 and (nreads == 0 or key.shape[0] == 0):
-        raise ValueError('rows need reads and sites')
-    shapes = {k: v for k, v in _class_rows_shapes(nrows, key.shape[0]).items() if k in want}
-    res = _host_outputs(shapes, fill=shapes)
-    lib = L.load()
-    _join_warm_up(device)
-    out = L.make_class_rows_out(**_np_ptrs(res))
-    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_read_class_rows', prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key),
-          _np_ptr(hoff), nrows, C.byref(out))
-    res['hoff'] = hoff
-    return res
+    want = _check_want(want, CLASS_ROWS_OUTPUTS)
+    return _chain_host('nmod_read_class_rows', L.make_class_rows_out,
+                       lambda nrows, nreads, nsites: {k: v for k, v in _class_rows_shapes(nrows, nsites).items() if k in want}, None,
+                       (cs, start, roff, score, key), hoff, device)
 
 
 def read_classes_step_host(rows, theta, w, *, want=CLASSES_OUTPUTS, device=0):
@@ -1844,76 +1807,57 @@ class DeviceDetector:
         _call(self.lib, 'nmod_read_sites_count', prm, *shared, hoff.data_ptr(), C.byref(nrows))
         return hoff, int(nrows.value)
 
+    def _chain(self, what, make_out, shapes, opts, reads, hoff, nrows, out):
+        """What the device methods of the chain entries (K19 .. K22) share after the checks of their own arguments: _chain_host's
+        arguments, `what` the method's name (the entry is nmod_<what>), hoff and nrows as read_sites gives them, out the caller's."""
+        nreads, shared = self._site_reads(what, *reads)
+        _cuda_vecs(what, (('hoff', hoff, self.torch.int64, nreads + 1),), one_dim=True, missing='refused')
+        nsites = reads[4].numel()
+        nrows = _check_hmm_counts(nreads, nsites, nrows)
+        shapes = shapes(nrows, nreads, nsites)
+        res = self._outputs(out, shapes, what)
+        o = make_out(**{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_' + what, prm, *shared, hoff.data_ptr(), nrows, *(() if opts is None else (C.byref(opts),)), C.byref(o))
+        return res
+
     def read_hmm(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, out=None):
         """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, NMOD_MEM_DEVICE), enqueued on the
         current stream without synchronising or reading anything back: the arguments of read_sites, hoff and nrows as it gives them.
         Returns a dict of CUDA tensors, those named in `want`: per entry post (float64), site (int32), state (uint8); per read n_sites,
         n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod, site_can
         (int32).  out: such a dict from an earlier call of the same shape."""
-        torch = self.torch
         opts, want = _hmm_opts(pi, length, call_post, want)
-        nreads, shared = self._site_reads('read_hmm', cs, start, roff, score, key)
-        _cuda_vecs('read_hmm', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
-        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
-        shapes = _hmm_shapes(want, nrows, nreads, key.numel())
-        res = self._outputs(out, shapes, 'read_hmm')
-        o = L.make_hmm_out(**{name: res[name].data_ptr() for name in shapes})
-        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_read_hmm', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
-        return res
+        return self._chain('read_hmm', L.make_hmm_out, lambda nrows, nreads, nsites: _hmm_shapes(want, nrows, nreads, nsites), opts,
+                           (cs, start, roff, score, key), hoff, nrows, out)
 
     def read_viterbi(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, out=None):
         """Per-read Viterbi decoding of read_hmm's chain (nmod_read_viterbi, NMOD_MEM_DEVICE), enqueued on the current stream without
         synchronising or reading anything back: the arguments of read_hmm without call_post.  Returns a dict of CUDA tensors, those
         named in `want`: per entry path (uint8), site (int32), delta (float64); per read n_sites, n_mod, n_runs (int32), vit (float64),
         status (uint8, L.HMM_NO_SITE); per site site_n, site_mod (int32).  out: such a dict from an earlier call of the same shape."""
-        torch = self.torch
         opts, want = _vit_opts(pi, length, want)
-        nreads, shared = self._site_reads('read_viterbi', cs, start, roff, score, key)
-        _cuda_vecs('read_viterbi', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
-        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
-        shapes = _vit_shapes(want, nrows, nreads, key.numel())
-        res = self._outputs(out, shapes, 'read_viterbi')
-        o = L.make_vit_out(**{name: res[name].data_ptr() for name in shapes})
-        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_read_viterbi', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
-        return res
+        return self._chain('read_viterbi', L.make_vit_out, lambda nrows, nreads, nsites: _vit_shapes(want, nrows, nreads, nsites), opts,
+                           (cs, start, roff, score, key), hoff, nrows, out)
 
     def read_hmm_grad(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, out=None):
         """The log-likelihood of read_hmm's chain and its gradient in logit(pi) and ln(length) (nmod_read_hmm_grad, NMOD_MEM_DEVICE),
         enqueued on the current stream without synchronising or reading anything back: the arguments of read_hmm without call_post.
         Returns a dict of CUDA tensors, those named in `want`: per read ll, g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
         L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS).  out: such a dict from an earlier call of the same shape."""
-        torch = self.torch
         opts, want = _hmm_grad_opts(pi, length, want)
-        nreads, shared = self._site_reads('read_hmm_grad', cs, start, roff, score, key)
-        _cuda_vecs('read_hmm_grad', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
-        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
-        shapes = _hmm_grad_shapes(want, nreads)
-        res = self._outputs(out, shapes, 'read_hmm_grad')
-        o = L.make_hmm_grad_out(**{name: res[name].data_ptr() for name in shapes})
-        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_read_hmm_grad', prm, *shared, hoff.data_ptr(), nrows, C.byref(opts), C.byref(o))
-        return res
+        return self._chain('read_hmm_grad', L.make_hmm_grad_out, lambda nrows, nreads, nsites: _hmm_grad_shapes(want, nreads), opts,
+                           (cs, start, roff, score, key), hoff, nrows, out)
 
     def read_class_rows(self, cs, start, roff, score, key, hoff, nrows, *, want=CLASS_ROWS_OUTPUTS, out=None):
         """The rows of the latent-class fit (nmod_read_class_rows, NMOD_MEM_DEVICE), enqueued on the current stream without
         synchronising or reading anything back: the arguments of read_hmm.  Returns a dict of CUDA tensors, those named in `want`: per
         row site (int32), s (float64), rread (int32); soff (int64, nsites + 1) and srow (int32): the rows of site j are
         srow[soff[j]:soff[j + 1]] in ascending row index.  out: such a dict from an earlier call of the same shape."""
-        torch = self.torch
-        want = tuple(want)
-        if any(w not in CLASS_ROWS_OUTPUTS for w in want):
-            raise ValueError('want must name outputs of %s' % ', '.join(CLASS_ROWS_OUTPUTS))
-        nreads, shared = self._site_reads('read_class_rows', cs, start, roff, score, key)
-        _cuda_vecs('read_class_rows', (('hoff', hoff, torch.int64, nreads + 1),), one_dim=True, missing='refused')
-        nrows = _check_hmm_counts(nreads, key.numel(), nrows)
-        shapes = {k: v for k, v in _class_rows_shapes(nrows, key.numel()).items() if k in want}
-        res = self._outputs(out, shapes, 'read_class_rows')
-        o = L.make_class_rows_out(**{name: res[name].data_ptr() for name in shapes})
-        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_read_class_rows', prm, *shared, hoff.data_ptr(), nrows, C.byref(o))
-        return res
+        want = _check_want(want, CLASS_ROWS_OUTPUTS)
+        return self._chain('read_class_rows', L.make_class_rows_out,
+                           lambda nrows, nreads, nsites: {k: v for k, v in _class_rows_shapes(nrows, nsites).items() if k in want}, None,
+                           (cs, start, roff, score, key), hoff, nrows, out)
 
     def read_classes_step(self, rows, hoff, theta, w, *, want=CLASSES_OUTPUTS, out=None):
         """One EM step of the latent-class mixture over the reads (nmod_read_classes_step, NMOD_MEM_DEVICE), enqueued on the current

@@ -496,3 +496,50 @@ def test_accepted_calls_reach_the_library():
         engine.one_sample_host(sig, off, np.zeros(NPOS), np.ones(NPOS), method='ks', device=NO_SUCH_DEVICE)
     with pytest.raises(L.NanomodLibraryError):
         engine.read_calls_host(val, roff, base, kmer_model(), device=NO_SUCH_DEVICE)
+
+
+# ------------------------------------------------------------------------------------------------------------ the chain entries
+# (K19 .. K22: one argument layer, engine._chain_host) the four host wrappers, the outputs `want` may name and whether the entry has
+# the chain's two parameters
+CHAIN_HOSTS = [('hmm', engine.read_hmm_host, engine.HMM_OUTPUTS, True), ('viterbi', engine.read_viterbi_host, engine.VIT_OUTPUTS, True),
+               ('grad', engine.read_hmm_grad_host, engine.HMM_GRAD_OUTPUTS, True),
+               ('class_rows', engine.read_class_rows_host, engine.CLASS_ROWS_OUTPUTS, False)]
+# three reads (the second without an event) over three sites of (chrom, strand) id 0, and their offsets of rows
+CHAIN_READS = (np.zeros(3, np.int32), np.array([10, 30, 50], np.int64), np.array([0, 4, 4, 9], np.int64), np.zeros(9),
+               np.array([11, 12, 52], np.int64))
+CHAIN_HOFF = np.array([0, 2, 2, 3], np.int64)
+CHAIN_BAD = [
+    ('pi-0', dict(pi=0.0), 'pi must lie in 1e-9 .. 1 - 1e-9, not 0.0'),
+    ('pi-nan', dict(pi=float('nan')), 'pi must lie in 1e-9 .. 1 - 1e-9, not nan'),
+    ('length-small', dict(length=1e-4), 'length must lie in 1e-3 .. 1e9 bases, not 0.0001'),
+    ('length-inf', dict(length=float('inf')), 'length must lie in 1e-3 .. 1e9 bases, not inf'),
+    ('want', dict(want=('status', 'nope')), 'want must name outputs of %s'),
+    ('hoff-from-1', dict(hoff=CHAIN_HOFF + 1), 'hoff must start at 0 and never decrease'),
+    ('hoff-down', dict(hoff=np.array([0, 2, 1, 3], np.int64)), 'hoff must start at 0 and never decrease'),
+    ('hoff-short', dict(hoff=CHAIN_HOFF[:-1]), 'hoff must be int64[nreads + 1]'),
+    ('hoff-long', dict(hoff=np.append(CHAIN_HOFF, 3)), 'hoff must be int64[nreads + 1]'),
+]
+
+
+@pytest.mark.parametrize('bad,kw,text', [pytest.param(*b, id=b[0]) for b in CHAIN_BAD])
+@pytest.mark.parametrize('name,fn,outputs,has_chain', [pytest.param(*h, id=h[0]) for h in CHAIN_HOSTS])
+def test_chain_hosts_refuse_alike_before_the_library(rec, name, fn, outputs, has_chain, bad, kw, text):
+    if not has_chain and ('pi' in kw or 'length' in kw):
+        with pytest.raises(TypeError):                                   # the class rows take neither
+            fn(*CHAIN_READS, CHAIN_HOFF, **kw)
+    else:
+        with pytest.raises(ValueError) as e:
+            fn(*CHAIN_READS, **dict(dict(hoff=CHAIN_HOFF), **kw))
+        assert str(e.value) == (text % ', '.join(outputs) if '%s' in text else text)
+    assert rec.calls == []
+
+
+@pytest.mark.parametrize('name,fn,outputs,has_chain', [pytest.param(*h, id=h[0]) for h in CHAIN_HOSTS])
+def test_chain_hosts_hand_the_same_reads_to_the_library(rec, name, fn, outputs, has_chain):
+    """the counterpart: the well-formed call reaches its entry once, with the reads, hoff and nrows in the shared places"""
+    res = fn(*CHAIN_READS, CHAIN_HOFF, want=outputs[:1], device=1)
+    entry = {'hmm': 'nmod_read_hmm', 'viterbi': 'nmod_read_viterbi', 'grad': 'nmod_read_hmm_grad', 'class_rows': 'nmod_read_class_rows'}[name]
+    got = rec.only(entry)
+    assert len(got) == (12 if has_chain else 11) and got[1] == 3 and got[6] == 3 and got[8] == addr(res['hoff']) and got[9] == 3
+    assert sorted(res) == sorted(('hoff',) + tuple(outputs[:1])) and np.array_equal(res['hoff'], CHAIN_HOFF)
+    assert got[-1]['struct_size'] > 0 and (not has_chain or (got[-2]['pi'], got[-2]['length']) == (0.5, 200.0))

@@ -115,7 +115,11 @@ def test_header_constants_bindings_and_build_rule():
     assert 'nmod_read_viterbi' in L._SIGNATURES and lib.nmod_read_viterbi.argtypes is not None and lib.nmod_abi_version() == 4
     csrc = os.path.join(ROOT, 'nanomod_amd', 'csrc')
     code = re.sub(r'//.*', '', open(os.path.join(csrc, 'read_viterbi.hip')).read())
-    assert '#include "read_entries.hpp"' in code and 'draw_read<WAVES>' in code and 'rh_fill_entries(' in code
+    # the fill of the entries is enqueued by read_entries.hpp's ChainCall, for every chain entry: one copy of that call
+    shared = re.sub(r'//.*', '', open(os.path.join(csrc, 'read_entries.hpp')).read())
+    assert '#include "read_entries.hpp"' in code and 'draw_read<WAVES>' in code and 'ChainCall c(' in code
+    assert shared.count('rh_fill_entries(e, num_cus, stream)') == 1 and 'rh_fill_entries(' not in code
+    assert 'rh_fill_entries(' not in re.sub(r'//.*', '', open(os.path.join(csrc, 'read_classes.hip')).read())
     assert 'rh_entries_kernel' not in code and 'frexp' not in code and 'ldexp' not in code      # one copy of the entries' kernel; nothing is rescaled
     assert not re.search(r'atomicAdd\(\s*\(?\s*(double|float)', code) and 'atomicAdd(&o.site_' in code
     mk = open(os.path.join(csrc, 'Makefile')).read()
