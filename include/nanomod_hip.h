@@ -1281,6 +1281,8 @@ int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs
  *     byte for byte, and rread (int32), the row's read; the site-major view soff (int64[nsites + 1]) and srow (int32[nrows]): the rows
  *     of site j are srow[soff[j] .. soff[j + 1] - 1] in ascending row index (a stable sort of the rows by their site).  A NULL output
  *     is skipped.  Refusals: nmod_read_hmm's without the options.  Scratch: 36 B per row beside the sort's, 44 B without site and srow.
+ *     A row that no read owns (NMOD_MEM_DEVICE with nrows above hoff[nreads], which is not read back) keeps site -1, s 0.0 and rread -1,
+ *     sorts behind every site in ascending row index (the last nrows - hoff[nreads] words of srow) and leaves soff[nsites] = hoff[nreads].
  *   nmod_read_classes_step(prm, nreads, nsites, nrows, hoff, site, s, rread, soff, srow, opts, theta_in, w_in, out), once per EM step:
  *     the reads are not walked again.  theta_in double[nsites * C], the C classes of a site contiguous; w_in double[C].  Outputs (a NULL
  *     member is skipped; asking for fewer never changes the bits of the others): gamma double[nreads * C], ll double[nreads], cls

@@ -159,9 +159,10 @@ def test_the_rows_are_the_entries_and_their_stable_order_by_site(det):
     assert same(part['srow'], ref['srow']) and same(part['soff'], ref['soff'])
 
 
-@pytest.mark.parametrize('nc', [1, 2, 3, 8])
+@pytest.mark.parametrize('nc', range(1, 9))
 def test_a_step_on_constructed_reads(det, nc):
-    """Measured on one MI355X: against mpmath ll within 0.054, gamma 0.011, theta_out 0.011 and n_site 0.007 of their gates, for every C.
+    """Measured on one MI355X: against mpmath ll within 0.055, gamma 0.011, theta_out 0.012 and n_site 0.008 of their gates, for every
+    C = 1 .. 8 (C = 4 .. 7: ll 0.055, 0.051, 0.053, 0.044; gamma 0.009, 0.008, 0.004, 0.005; theta_out and n_site below 0.008).
     The gate of ll is not a rounding count times sum |g| + S + 1 alone: at a clamped theta with a score of +-40 the definition's
     1 - (1 - th) t cancels to the clamp's 1e-9, and ll is then off by up to 1.96e-10 of sum |g| + S + 1 (printed below) whatever the
     order of operations; classes_ref's gate carries that term, X_U u sum x / (1 - x), derived in its docstring"""
@@ -233,6 +234,17 @@ def test_host_and_device_memspace_and_fewer_outputs_give_identical_bytes(det):
             assert same(part[f], dev[f]), (want, f)
     part = eng.read_classes_step_host(c['rows'], theta, w, want=('sums', 'theta_out'))
     assert same(part['sums'], dev['sums']) and same(part['theta_out'], dev['theta_out'])
+    for nc in (5, 8):                                                         # the slabs that scale with C, where the caller asks for none of their outputs
+        theta, w = _theta(len(c['key']), nc, 2210 + nc)
+        dev = _step(det, rows_t, hoff_t, theta, w)
+        host = eng.read_classes_step_host(c['rows'], theta, w)
+        for f in ALL:
+            assert same(host[f], dev[f]), (nc, f)
+        for want in (('sums',), ('w_out',), ('theta_out',), ('gamma', 'n_site', 'sums')):
+            part = _step(det, rows_t, hoff_t, theta, w, want=want)
+            assert set(part) == set(want)
+            for f in want:
+                assert same(part[f], dev[f]), (nc, want, f)
 
 
 def test_a_permutation_of_the_reads_and_a_larger_batch_change_no_read(det):
@@ -304,36 +316,39 @@ def test_more_reads_and_sites_than_the_grids_have_units(det):
     # sites of the wave form (65 rows), of the workgroup form (513 rows and, under the long reads, one per entry), long reads
     top = L.HMM_WAVE_MAX + 1
     n_wave, n_block, n_long = 8 * cus * 4 + 50, 2 * cus + 20, RB.long_units(cus) + 50
-    for rows_per, copies in ((L.CLASSES_SMALL + 1, n_wave), (L.CLASSES_WAVE + 1, n_block)):
-        unit = K.rows_from_entries(np.arange(rows_per + 1, dtype=np.int64), np.zeros(rows_per, np.int64), rng.normal(0.0, 3.0, rows_per), 1)
-        ut, uh = _rows_dev(unit)
-        th1 = theta[:1]
-        single = _step(det, ut, uh, th1, w, want=('gamma', 'theta_out', 'n_site'))
-        ref = K.step_ref(unit, th1, w)
-        assert np.allclose(single['theta_out'], ref['theta_out'].reshape(-1), rtol=1e-12) and np.allclose(single['n_site'], ref['n_site'].reshape(-1), rtol=1e-12)
-        big = _tile(unit, 1, copies)
-        bt, bh = _rows_dev(big)
-        res = _step(det, bt, bh, np.tile(th1, (copies, 1)), w, want=('gamma', 'theta_out', 'n_site'))
-        for f in ('gamma', 'theta_out', 'n_site'):
-            per = single[f].reshape(-1, nc)
-            assert same(res[f].reshape(copies, *per.shape), np.broadcast_to(per, (copies,) + per.shape)), (rows_per, f)
-    long_unit = K.rows_from_entries(np.array([0, top], np.int64), np.arange(top), rng.normal(0.0, 3.0, top), top)
-    th_long = rng.uniform(0.05, 0.95, (top, nc))
-    lt, lh = _rows_dev(long_unit)
-    single = _step(det, lt, lh, th_long, w, want=READ)
-    hoff = np.arange(0, (n_long + 1) * top, top, dtype=np.int64)
-    many = K.rows_from_entries(hoff, np.tile(np.arange(top), n_long), np.tile(long_unit['s'], n_long), top)
-    mt, mh = _rows_dev(many)
-    res = _step(det, mt, mh, th_long, w)
-    assert n_long > RB.long_units(cus) and top > 2 * cus
-    for f in READ:
-        assert same(res[f].reshape(n_long, -1), np.repeat(single[f].reshape(1, -1), n_long, 0)), f
-    g = single['gamma'].reshape(1, nc)
-    for j in (0, 1, top // 2, top - 1):                                        # a site of n_long equal rows, in the device's order
-        N, Mo = K.site_ref(np.full(n_long, long_unit['s'][j]), np.repeat(g, n_long, 0), th_long[j])
-        assert same(res['n_site'].reshape(top, nc)[j], N), j
-        assert np.allclose(res['theta_out'].reshape(top, nc)[j], np.clip(Mo / N, K.LO, K.HI), rtol=1e-12), j
-    assert res['sums'][1] == n_long and res['sums'][2] == n_long * top
+    for nc in (2, 7):                                                         # ... and once more with 7 classes: the odd count with the most registers
+        if nc != 2:
+            theta, w = rng.uniform(0.05, 0.95, (ns, nc)), rng.dirichlet(np.full(nc, 3.0))
+        for rows_per, copies in ((L.CLASSES_SMALL + 1, n_wave), (L.CLASSES_WAVE + 1, n_block)):
+            unit = K.rows_from_entries(np.arange(rows_per + 1, dtype=np.int64), np.zeros(rows_per, np.int64), rng.normal(0.0, 3.0, rows_per), 1)
+            ut, uh = _rows_dev(unit)
+            th1 = theta[:1]
+            single = _step(det, ut, uh, th1, w, want=('gamma', 'theta_out', 'n_site'))
+            ref = K.step_ref(unit, th1, w)
+            assert np.allclose(single['theta_out'], ref['theta_out'].reshape(-1), rtol=1e-12) and np.allclose(single['n_site'], ref['n_site'].reshape(-1), rtol=1e-12)
+            big = _tile(unit, 1, copies)
+            bt, bh = _rows_dev(big)
+            res = _step(det, bt, bh, np.tile(th1, (copies, 1)), w, want=('gamma', 'theta_out', 'n_site'))
+            for f in ('gamma', 'theta_out', 'n_site'):
+                per = single[f].reshape(-1, nc)
+                assert same(res[f].reshape(copies, *per.shape), np.broadcast_to(per, (copies,) + per.shape)), (rows_per, f)
+        long_unit = K.rows_from_entries(np.array([0, top], np.int64), np.arange(top), rng.normal(0.0, 3.0, top), top)
+        th_long = rng.uniform(0.05, 0.95, (top, nc))
+        lt, lh = _rows_dev(long_unit)
+        single = _step(det, lt, lh, th_long, w, want=READ)
+        hoff = np.arange(0, (n_long + 1) * top, top, dtype=np.int64)
+        many = K.rows_from_entries(hoff, np.tile(np.arange(top), n_long), np.tile(long_unit['s'], n_long), top)
+        mt, mh = _rows_dev(many)
+        res = _step(det, mt, mh, th_long, w)
+        assert n_long > RB.long_units(cus) and top > 2 * cus
+        for f in READ:
+            assert same(res[f].reshape(n_long, -1), np.repeat(single[f].reshape(1, -1), n_long, 0)), f
+        g = single['gamma'].reshape(1, nc)
+        for j in (0, 1, top // 2, top - 1):                                        # a site of n_long equal rows, in the device's order
+            N, Mo = K.site_ref(np.full(n_long, long_unit['s'][j]), np.repeat(g, n_long, 0), th_long[j])
+            assert same(res['n_site'].reshape(top, nc)[j], N), j
+            assert np.allclose(res['theta_out'].reshape(top, nc)[j], np.clip(Mo / N, K.LO, K.HI), rtol=1e-12), j
+        assert res['sums'][1] == n_long and res['sums'][2] == n_long * top
 
 
 # ------------------------------------------------------------------------------------------------------------ the stream
