@@ -1119,7 +1119,8 @@ int nmod_pair_linkage(const nmod_params* prm, int64_t npairs, const double* sa, 
  *     or of another struct_size; nrows outside 0 .. 2^31 - 1 or positive without reads or sites; a NULL hoff; host hoff that does not
  *     start at 0, ascend and end at nrows.
  *   Scratch: 32 B per row (position, score, forward vector), 36 B where site is not asked for.
- * Stops at: two states; one (pi, length) for all sites and reads, no per-site prior; posterior decoding (the most probable path is
+ * Stops at: two states; one (pi, length) for all sites and reads (a per-site prior on request: K23, nmod_read_hmm_prior, below);
+ * posterior decoding (the most probable path is
  * nmod_read_viterbi's, below); no Baum-Welch: pi and length are given (nmod_read_hmm_grad, below, is what a maximum-likelihood fit of
  * both is built on; a grid of lengths is the caller's other choice); the reads are independent and
  * both k-mer tables are taken as right; one (chrom, strand) per read. */
@@ -1183,7 +1184,8 @@ int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, con
  *   Scratch: at most 33 B per row (position, score, forward vector, one byte of back-pointers), 37 B where site is not asked for; 16 B
  *     less without delta, 1 B less without the traceback.
  * Stops at: the single best path, no k-best list and no minimum-length constraint on a domain; the model is nmod_read_hmm's with all
- * its limits (two states, one (pi, length), no Baum-Welch: both are given, or fitted through nmod_read_hmm_grad, below). */
+ * its limits (two states, one (pi, length) — a per-site prior on request: K23, nmod_read_viterbi_prior, below —, no Baum-Welch: both are
+ * given, or fitted through nmod_read_hmm_grad, below). */
 typedef struct nmod_vit_opts { int32_t struct_size, reserved; double pi, length; } nmod_vit_opts;
 typedef struct nmod_vit_out { int32_t struct_size; int32_t reserved;
   uint8_t* path; int32_t* site; double* delta;                          /* [nrows] */
@@ -1230,7 +1232,7 @@ int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs,
  *     enqueued on prm->stream, no host read and no synchronisation.  NMOD_MEM_HOST: one staged copy.  nreads == 0: NMOD_OK, sums all 0.
  *     NMOD_ERR_INVALID_ARG before any device work: nmod_read_hmm's list without call_post.
  *   Scratch: 36 B per row (position, score, forward vector, site), and 8 B per read for each of ll, g_eta, g_lam not asked for.
- * Stops at: one (pi, length) for all reads and sites; the emissions and both k-mer tables are taken as right (no gradient in them);
+ * Stops at: one (pi, length) for all reads and sites (a per-site prior on request: K23, nmod_read_hmm_grad_prior, below); the emissions and both k-mer tables are taken as right (no gradient in them);
  * the outer-product information, not the observed Hessian: standard errors from it are right at the model and in large samples only;
  * the caller's intervals are Wald intervals on the logit and log scales; the first derivative only. */
 typedef struct nmod_hmm_grad_opts { int32_t struct_size, reserved; double pi, length; } nmod_hmm_grad_opts;
@@ -1241,6 +1243,50 @@ typedef struct nmod_hmm_grad_out { int32_t struct_size; int32_t reserved;
 int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
                        const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
                        const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out);
+
+/* The read chain with a prior share per candidate site: nmod_read_hmm, nmod_read_viterbi and nmod_read_hmm_grad, argument for argument,
+ * with one more, site_pi (double[nsites], in the memspace of the call), after key (K23; the reference project has no such step).  One
+ * stationary share for every site is the chain's largest misspecification on real samples: the shares of neighbouring sites differ by
+ * an order of magnitude, and a chain that redraws every site from the mean share over-calls the rarely modified sites and under-calls
+ * the others (nmod_read_hmm_grad then reports the misfit as a shorter fitted length).  The opts and out structs are the counterparts';
+ * what is not restated here is the counterpart's, word for word.
+ *   Share of entry j.  pi_j = site_pi[site_j] clamped to 1e-9 .. 1 - 1e-9 (an infinity is clamped like any other value); where that word
+ *     is a NaN, pi_j = opts->pi (nmod_site_stoich gives a NaN to a site without an estimate).  opts->pi keeps its range check.
+ *     q_j = 1 - pi_j, formed on the device from the clamped pi_j (one subtraction, the same double wherever entry j is met).  The share
+ *     of a row is resolved once per call, by a gather over the rows behind the fill of the entries, not inside the scan.
+ *   Transition.  With rho, eps and r exactly as in nmod_read_hmm:
+ *         T_j = [[q_j + pi_j rho, pi_j eps], [q_j eps, pi_j + q_j rho]]     rows the state at j - 1, columns the state at j;
+ *     the share is that of the entry arrived at: "copy the neighbour's state with probability rho, else redraw from the site's own
+ *     law".  Initial law (q_0, pi_0).  Emissions, scaling, tiles, scan order, carries, the backward scan, states, runs, site counts,
+ *     ll, the S sum and the passes-not-run rules are nmod_read_hmm's;  ll_indep = SUM_j (log(q_j e_j0 + pi_j e_j1) + max(s_j, 0)).
+ *   Viterbi.  log pi_j and log q_j are formed on the device from the clamped pi_j and the q_j above (nmod_read_viterbi forms its two
+ *     logarithms on the host: with a constant site_pi the two entries may differ in the last bits of vit and delta, and in path where
+ *     delta is a tie to rounding).  The forward scan starts from (log q_0, log pi_0); L_j, MAX, the back-pointers, the traceback,
+ *     delta, vit and the tie rule are nmod_read_viterbi's with pi_j, q_j and their logarithms in place of pi, q and theirs.
+ *   Gradient.  g_lam and abs_lam are nmod_read_hmm_grad's L_j with pi_j, q_j in place of pi, q.  g_eta is the derivative of ll in a
+ *     common logit offset kappa of all shares (logit pi_j -> logit pi_j + kappa), evaluated at the shares given:
+ *         g_eta = (post_0 - pi_0) + SUM_j ((pi_j q_j) P_j),     abs_eta = |post_0 - pi_0| + SUM_j |(pi_j q_j) P_j|,
+ *     P_j nmod_read_hmm_grad's expression with T_j as above (d T_j / d pi_j = eps [[-1, 1], [-1, 1]] and d pi_j / d kappa = pi_j q_j);
+ *     the product (pi_j q_j) P_j is rounded, then added, in the order of nmod_read_hmm_grad's sums.  With a constant site_pi, ll,
+ *     g_lam, abs_lam and status have nmod_read_hmm_grad's bits, g_eta its value to rounding.  sums[8] keeps its layout and its kernel.
+ *   With site_pi constant at opts->pi, or all NaN, every output of nmod_read_hmm_prior has nmod_read_hmm's bits.
+ *   CAVEAT.  Under this law the marginal share of entry j is rho P(z_(j-1) = 1) + eps pi_j, not pi_j, while an estimate such as
+ *     nmod_site_stoich's is a marginal.  The mismatch grows where neighbouring sites less than a `length` apart have very different
+ *     shares.  A transition that preserves given marginals exactly is another model and is not built.
+ *   NMOD_ERR_INVALID_ARG before any device work: site_pi NULL with nsites > 0; everything else: the counterpart's list.  The values of
+ *     site_pi are never refused, in either memspace.  Stream contract, memspaces, NULL-skips-an-output: the counterparts'.  An entry's
+ *     and a read's bits depend on the read, the sites and site_pi alone.
+ *   Scratch, beside the counterpart's: 8 B per row for nmod_read_hmm_prior and nmod_read_hmm_grad_prior (the clamped share of the
+ *     row), 24 B per row for nmod_read_viterbi_prior (the share and its two logarithms); a host call stages site_pi as well. */
+int nmod_read_hmm_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                        const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff, int64_t nrows,
+                        const nmod_hmm_opts* opts, const nmod_hmm_out* out);
+int nmod_read_viterbi_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                            const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff, int64_t nrows,
+                            const nmod_vit_opts* opts, const nmod_vit_out* out);
+int nmod_read_hmm_grad_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                             const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff, int64_t nrows,
+                             const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out);
 
 /* Latent-class clustering of the reads by their modification pattern: a finite mixture of C classes over the reads, every class with
  * a weight and a modified share of its own at every candidate site, fitted by EM (K22; the reference project has no such step).  K14

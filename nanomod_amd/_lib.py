@@ -528,6 +528,13 @@ _SIGNATURES = {
                                     C.POINTER(NmodVitOpts), C.POINTER(NmodVitOut)]),
     'nmod_read_hmm_grad': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(NmodHmmGradOpts), C.POINTER(NmodHmmGradOut)]),
+    # K23: the three entries above with site_pi (float64[nsites]) after key
+    'nmod_read_hmm_prior': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.POINTER(NmodHmmOpts), C.POINTER(NmodHmmOut)]),
+    'nmod_read_viterbi_prior': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.POINTER(NmodVitOpts), C.POINTER(NmodVitOut)]),
+    'nmod_read_hmm_grad_prior': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.POINTER(NmodHmmGradOpts), C.POINTER(NmodHmmGradOut)]),
     'nmod_read_class_rows': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.POINTER(NmodClassRowsOut)]),
     'nmod_read_classes_step': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 6

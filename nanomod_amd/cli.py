@@ -255,6 +255,10 @@ def build_parser():
                     '--hmmPi (or its default) and --hmmLength; the trace and the estimates with their intervals are written to <FileID>_hmm_fit.txt; '
                     'not together with --fitLength')
     rh.add_argument('--fixPi', type=int, default=0, choices=[0, 1], help='--fitHmm 1: keep pi and fit the length alone')
+    rh.add_argument('--sitePrior', type=int, default=0, choices=[0, 1], help="1: every candidate site gets a prior share of its own, its estimated "
+                    'share shrunk towards pi with the weight of --priorReads reads; written to <FileID>_site_prior.txt; with --fitHmm 1 the length '
+                    'alone is fitted')
+    rh.add_argument('--priorReads', type=float, default=4.0, help='--sitePrior 1: the weight of pi in reads, > 0')
     rh.add_argument('--callPost', type=float, default=0.9, help='the posterior from which an entry is called, inside (0.5, 1)')
     rh.add_argument('--decode', default='posterior', choices=['posterior', 'viterbi', 'both'], help="'posterior': the marginal calls; 'viterbi': "
                     'the most probable path of every read, written to <FileID>_read_viterbi.txt, _read_domains_viterbi.txt and _site_viterbi.txt; '
@@ -482,6 +486,8 @@ def validate_readhmm(a):
         errs.append('Error: --fitHmm 1 and --fitLength exclude each other')
     if a.fixPi and not a.fitHmm:
         errs.append('Error: --fixPi 1 needs --fitHmm 1')
+    if a.sitePrior and not 0.0 < a.priorReads < float('inf'):
+        errs.append('Error: --priorReads should be finite and larger than 0')
     if not 0.5 < a.callPost < 1.0:
         errs.append('Error: --callPost should lie between 0.5 and 1, both excluded')
     if not 0.0 < a.siteAlpha <= 1.0:
@@ -503,11 +509,14 @@ def run_readhmm(a, log=print):
                                    call_post=a.callPost, window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None,
                                    site_alpha=a.siteAlpha, thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
                                    log=(lambda *x: None) if quiet else log, **({} if a.decode == 'posterior' else {'decode': a.decode}),
-                                   **({'fit': 'mle', 'fix_pi': bool(a.fixPi)} if a.fitHmm else {}))
+                                   **({'fit': 'mle', 'fix_pi': bool(a.fixPi or a.sitePrior)} if a.fitHmm else {}),
+                                   **({'site_prior': True, 'prior_reads': a.priorReads} if a.sitePrior else {}))
     os.makedirs(a.outFolder, exist_ok=True)
     files = []
     if a.fitHmm:
         files.append(('_hmm_fit.txt', readllr.write_hmm_fit, 'The fit of pi and length is', res['fit']))
+    if a.sitePrior:
+        files.append(('_site_prior.txt', readllr.write_site_prior, 'The per-site priors are', res))
     if a.decode != 'viterbi':
         files += [('_read_hmm.txt', readllr.write_read_hmm, 'Read chains are', res), ('_read_domains.txt', readllr.write_read_domains, 'Read domains are', res),
                   ('_site_hmm.txt', readllr.write_site_hmm, 'Smoothed site counts are', res)]

@@ -95,6 +95,11 @@ static void rh_stage_reads(Slab& slab, RhEntArgs& a, size_t tot) {
 // rh_entries_kernel<., true> in both forms on the stream (read_hmm.hip): e.w filled by the caller, rows hoff[r] + j written
 void rh_fill_entries(const RhEntArgs& e, int num_cus, hipStream_t stream);
 
+// The prior entries (K23).  rh_share_kernel behind the fill (read_hmm.hip): share[stride * row] = the share of e.site[row] from site_pi,
+// clamped to these bounds, pi where that word is a NaN; with stride 3 the logarithms of 1 - share and of share follow it
+constexpr double kSharePiLo = 1e-9, kSharePiHi = 1.0 - 1e-9;
+void rh_fill_shares(const RhEntArgs& e, const double* site_pi, double pi, int stride, double* share, int num_cus, hipStream_t stream);
+
 static bool rh_finite_in(double v, double lo, double hi) { return v >= lo && v <= hi; }   // (a NaN compares false)
 static bool rh_chain_opts_ok(double pi, double length) { return rh_finite_in(pi, 1e-9, 1.0 - 1e-9) && rh_finite_in(length, 1e-3, 1e9); }
 
@@ -120,6 +125,8 @@ struct ChainCall {
   RhEntArgs e; Slab slab;
   const ReadListSpace by_events, by_entries;      // the reads by their events (the fill) and by their entries (the chain)
   const size_t o_xs, o_site;
+  const double* site_pi = nullptr; double pi0 = 0.0; int share_stride = 0; size_t o_share = 0;   // a prior entry's: prior()
+  double* share = nullptr;                        // after bind(): per row share_stride words (NULL without a prior)
 
   // own_site: the caller asked for no per-row site, the slab holds it; chain: the entry runs a kernel over the reads by their entries
   ChainCall(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
@@ -132,12 +139,19 @@ struct ChainCall {
   }
   ChainCall(const ChainCall&) = delete;           // (the slab keeps the addresses of e's pointers)
 
-  void stage() { rh_stage_reads(slab, e, tot); slab.in(e.hoff, (nr + 1) * 8); }
+  // a prior entry, before stage(): the shares of the sites (nsites words in the call's memspace), the share of a site whose word is a
+  // NaN, the words a row (rh_fill_shares' stride)
+  void prior(const double* sp, double pi, int stride) { site_pi = sp; pi0 = pi; share_stride = stride; o_share = slab.take(nw * 8 * (size_t)stride); }
+  void stage() { rh_stage_reads(slab, e, tot); slab.in(e.hoff, (nr + 1) * 8); slab.in(site_pi, ns * 8); }
   // after the commit.  site: the caller's per-row site as the commit left it, NULL: the slab's
-  void bind(int32_t* site) { e.xs = slab.at<double>(o_xs); e.site = site ? site : slab.at<int32_t>(o_site); }
+  void bind(int32_t* site) {
+    e.xs = slab.at<double>(o_xs); e.site = site ? site : slab.at<int32_t>(o_site);
+    if (share_stride) share = slab.at<double>(o_share);
+  }
   hipError_t entries() {                          // the rows of the reads written: site, position and score
     const hipError_t err = e.nrows ? by_events.fill(slab, e.roff, e.nreads, num_cus, stream, e.w) : hipSuccess;
     if (e.nrows && err == hipSuccess) rh_fill_entries(e, num_cus, stream);
+    if (e.nrows && err == hipSuccess && share_stride) rh_fill_shares(e, site_pi, pi0, share_stride, share, num_cus, stream);
     return err;
   }
   hipError_t lists(ReadLists& w) {                // entries(), then w: the reads by their entries, for a kernel under rh_launch

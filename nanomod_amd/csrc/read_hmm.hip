@@ -14,6 +14,9 @@
 //   rh_grad_kernel<1>, <4>   nmod_read_hmm_grad (K21): the same two forms, the same forward pass; the backward pass forms the terms of the
 //                            log-likelihood's gradient in logit(pi) and ln(length) instead of the posteriors
 //   rh_grad_sums_kernel      its batch sums: one workgroup, a fixed order
+//   rh_share_kernel          the prior entries (K23: nmod_read_hmm_prior, nmod_read_viterbi_prior, nmod_read_hmm_grad_prior) alone: behind
+//                            the fill a thread per row resolves the share of the row's site once (the NaN rule, the clamp; for K20 its
+//                            two logarithms); the chain kernels' <., true> instances read that word beside xs, the others never see it
 // The chain of a read is two passes of one scan, rh_tile<., BWD>, over tiles of NMOD_HMM_CHUNK entries a thread: a thread forms the step
 // matrices of its chunk and multiplies them in order, the lanes of a wave take the inclusive scan of those products (six shuffle steps on
 // four doubles and an exponent), a workgroup hands the waves' totals on through LDS, and the thread replays its chunk as a row vector from
@@ -44,6 +47,7 @@ struct RhArgs {
   double pi, q, length, call_post, call_lo;
   bool backward;                                  // an output that needs post was asked for
   nmod_hmm_out out;
+  const double* share;                            // the prior entries: per row the clamped share of its site (unread by the other instances)
 };
 
 // ---------------------------------------------------------------------------------------------------------------- the entries
@@ -105,6 +109,26 @@ void rh_fill_entries(const RhEntArgs& e, int num_cus, hipStream_t stream) {
   rh_launch(e, rh_entries_kernel<1, true>, rh_entries_kernel<kRwWaves, true>, num_cus, stream);
 }
 
+// The share of every row, once a call: pi_j = site_pi[site_j] clamped to 1e-9 .. 1 - 1e-9 (an infinity with the rest), pi where that word
+// is a NaN (or the row has no site of this call's: a row no read owns).  stride 1: the share alone; 3: (pi_j, log q_j, log pi_j) with
+// q_j = 1 - pi_j, what the chain kernels form it as
+__global__ __launch_bounds__(256) void rh_share_kernel(int64_t nrows, const int32_t* site, int64_t nsites, const double* site_pi, double pi,
+                                                       int stride, double* share) {
+  for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < nrows; row += (int64_t)gridDim.x * 256) {
+    const int64_t s = site[row];
+    double v = s >= 0 && s < nsites ? site_pi[s] : pi;
+    if (v != v) v = pi;
+    v = v < kSharePiLo ? kSharePiLo : (v > kSharePiHi ? kSharePiHi : v);
+    share[stride * row] = v;
+    if (stride == 3) { share[3 * row + 1] = log(1.0 - v); share[3 * row + 2] = log(v); }
+  }
+}
+
+void rh_fill_shares(const RhEntArgs& e, const double* site_pi, double pi, int stride, double* share, int num_cus, hipStream_t stream) {
+  hipLaunchKernelGGL(rh_share_kernel, dim3(persistent_grid(e.nrows, 256, (int64_t)num_cus * 8)), dim3(256), 0, stream, e.nrows, e.site, e.nsites,
+                     site_pi, pi, stride, share);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the scan
 
 struct Mat2 { double a, b, c, d; int e; };          // [[a, b], [c, d]] * 2^e: rows the state before, columns the state after
@@ -149,9 +173,10 @@ __device__ __forceinline__ void rh_emission(double s, double& e0, double& e1) {
 }
 
 // Step k of the scan over the m entries at xs (position, score per entry).  Forward: T_k diag(e_k), T_0 the identity.  Backward: the
-// transpose of T_j diag(e_j) for j = m - k, the identity at k = 0.  The identity beyond the read
-template <bool BWD>
-__device__ __forceinline__ Mat2 rh_step(const RhArgs& a, const double* xs, int64_t k, int64_t m) {
+// transpose of T_j diag(e_j) for j = m - k, the identity at k = 0.  The identity beyond the read.  PRIOR: the share of T_j is pr[j], that
+// of the entry arrived at, and q_j = 1 - pr[j] is formed here (the same double wherever entry j is met); pr is unread otherwise
+template <bool BWD, bool PRIOR>
+__device__ __forceinline__ Mat2 rh_step(const RhArgs& a, const double* xs, const double* pr, int64_t k, int64_t m) {
   Mat2 o{1.0, 0.0, 0.0, 1.0, 0};
   if (k >= m || (BWD && k == 0)) return o;
   const int64_t j = BWD ? m - k : k;
@@ -161,7 +186,9 @@ __device__ __forceinline__ Mat2 rh_step(const RhArgs& a, const double* xs, int64
   if (j > 0) {
     const double r = (xs[2 * j] - xs[2 * (j - 1)]) / a.length;
     const double rho = exp(-r), eps = -expm1(-r);
-    t00 = a.q + a.pi * rho; t01 = a.pi * eps; t10 = a.q * eps; t11 = a.pi + a.q * rho;
+    double pi = a.pi, q = a.q;
+    if constexpr (PRIOR) { pi = pr[j]; q = 1.0 - pi; }
+    t00 = q + pi * rho; t01 = pi * eps; t10 = q * eps; t11 = pi + q * rho;
   }
   if constexpr (BWD) { o.a = e0 * t00; o.b = e0 * t10; o.c = e1 * t01; o.d = e1 * t11; }
   else { o.a = t00 * e0; o.b = t01 * e1; o.c = t10 * e0; o.d = t11 * e1; }
@@ -172,15 +199,16 @@ struct RhShared { Mat2 tot[kRwWaves]; Vec2 carry; };
 
 // One tile of the scan, steps k0 .. k0 + T * kHmmChunk - 1, by the T threads of the read: per_entry(k, x) with x the row vector after
 // step k, for the steps inside the read.  Returns the vector after the tile's last step (thread T - 1's), the same in every thread
-template <int WAVES, bool BWD, class F>
-__device__ __forceinline__ Vec2 rh_tile(const RhArgs& a, const double* xs, int64_t m, int64_t k0, const Vec2& carry, RhShared& sh, F per_entry) {
+template <int WAVES, bool BWD, bool PRIOR, class F>
+__device__ __forceinline__ Vec2 rh_tile(const RhArgs& a, const double* xs, const double* pr, int64_t m, int64_t k0, const Vec2& carry, RhShared& sh,
+                                        F per_entry) {
   constexpr int T = WAVES * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = WAVES == 1 ? lane : (int)threadIdx.x;
   const int64_t kb = k0 + (int64_t)t * kHmmChunk;
   Mat2 step[kHmmChunk];
 #pragma unroll
-  for (int c = 0; c < kHmmChunk; ++c) step[c] = rh_step<BWD>(a, xs, kb + c, m);
+  for (int c = 0; c < kHmmChunk; ++c) step[c] = rh_step<BWD, PRIOR>(a, xs, pr, kb + c, m);
   Mat2 prod = step[0];
 #pragma unroll
   for (int c = 1; c < kHmmChunk; ++c) prod = rh_mul(prod, step[c]);
@@ -220,7 +248,7 @@ __device__ __forceinline__ Vec2 rh_tile(const RhArgs& a, const double* xs, int64
   return out;
 }
 
-template <int WAVES>
+template <int WAVES, bool PRIOR>
 __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
   __shared__ unsigned sh_item;
   __shared__ int sh_cnt[3 * kRwWaves];
@@ -248,18 +276,22 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
       continue;
     }
     const double* xs = a.xs + 2 * base;
+    const double* pr = PRIOR ? a.share + base : nullptr;
     double* alpha = a.alpha + 2 * base;
 
     // forward: the vectors, the independent likelihood and the sum of the positive scores, a thread's entries in ascending order
     double s_ind = 0.0, s_pos = 0.0;
     Vec2 fw{a.q, a.pi, 0};
+    if constexpr (PRIOR) { fw.x0 = 1.0 - pr[0]; fw.x1 = pr[0]; }
     for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
-      fw = rh_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
+      fw = rh_tile<WAVES, false, PRIOR>(a, xs, pr, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
         if (a.backward) { alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1; }
         const double s = xs[2 * k + 1], up = fmax(s, 0.0);
         double e0, e1;
         rh_emission(s, e0, e1);
-        s_ind += log(a.q * e0 + a.pi * e1) + up;
+        double pi = a.pi, q = a.q;
+        if constexpr (PRIOR) { pi = pr[k]; q = 1.0 - pi; }
+        s_ind += log(q * e0 + pi * e1) + up;
         s_pos += up;
       });
     }
@@ -275,7 +307,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_hmm_kernel(RhArgs a) {
       for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
         int st[kHmmChunk];
         const int64_t kb = k0 + (int64_t)geo.t * kHmmChunk;
-        bw = rh_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
+        bw = rh_tile<WAVES, true, PRIOR>(a, xs, pr, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
           const int64_t j = m - 1 - k, row = base + j;
           const double p0 = alpha[2 * j] * x.x0, p1 = alpha[2 * j + 1] * x.x1;
           const double post = p1 / (p0 + p1);
@@ -336,8 +368,9 @@ struct RgArgs {
 
 // The forward pass is rh_hmm_kernel's, tile for tile (ll has its bits).  The backward pass is the same scan; at step k, entry j = m - 1 - k,
 // the lambda holds b_j and reads a_(j-1), which the forward pass left in the slab: the term of transition j (Fisher's identity) needs
-// nothing else.  A thread adds its terms in the order of its steps, then the sums of the read as S's
-template <int WAVES>
+// nothing else.  A thread adds its terms in the order of its steps, then the sums of the read as S's.  PRIOR: the shares of T_j and L_j are
+// entry j's, and the term of g_eta is (pi_j q_j) P_j, the product rounded where it is formed: the sums hold the products
+template <int WAVES, bool PRIOR>
 __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
   __shared__ unsigned sh_item;
   __shared__ double sh_sum[kRwWaves];
@@ -361,13 +394,15 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
       continue;
     }
     const double* xs = a.xs + 2 * base;
+    const double* pr = PRIOR ? a.share + base : nullptr;
     double* alpha = a.alpha + 2 * base;
 
     // forward: the vectors and the sum of the positive scores, a thread's entries in ascending order
     double s_pos = 0.0;
     Vec2 fw{a.q, a.pi, 0};
+    if constexpr (PRIOR) { fw.x0 = 1.0 - pr[0]; fw.x1 = pr[0]; }
     for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
-      fw = rh_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
+      fw = rh_tile<WAVES, false, PRIOR>(a, xs, pr, m, k0, fw, sh_scan, [&](int64_t k, const Vec2& x) {
         alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1;
         s_pos += fmax(xs[2 * k + 1], 0.0);
       });
@@ -382,7 +417,7 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
     double s_p = 0.0, s_l = 0.0, s_ap = 0.0, s_al = 0.0, s_post = 0.0;
     Vec2 bw{1.0, 1.0, 0};
     for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
-      bw = rh_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
+      bw = rh_tile<WAVES, true, PRIOR>(a, xs, pr, m, k0, bw, sh_scan, [&](int64_t k, const Vec2& x) {
         const int64_t j = m - 1 - k;
         if (j == 0) {
           const double p0 = alpha[0] * x.x0, p1 = alpha[1] * x.x1;
@@ -393,12 +428,15 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
         rh_emission(xs[2 * j + 1], e0, e1);
         const double r = (xs[2 * j] - xs[2 * (j - 1)]) / a.length;
         const double rho = exp(-r), eps = -expm1(-r);
-        const double t00 = a.q + a.pi * rho, t01 = a.pi * eps, t10 = a.q * eps, t11 = a.pi + a.q * rho;
+        double pi = a.pi, q = a.q;
+        if constexpr (PRIOR) { pi = pr[j]; q = 1.0 - pi; }
+        const double t00 = q + pi * rho, t01 = pi * eps, t10 = q * eps, t11 = pi + q * rho;
         const double y0 = e0 * x.x0, y1 = e1 * x.x1;
         const double a0 = alpha[2 * (j - 1)], a1 = alpha[2 * (j - 1) + 1];
         const double z = a0 * (t00 * y0 + t01 * y1) + a1 * (t10 * y0 + t11 * y1);
-        const double p = eps * (a0 + a1) * (y1 - y0) / z;
-        const double l = rho * r * (a.pi * a0 - a.q * a1) * (y0 - y1) / z;
+        double p = eps * (a0 + a1) * (y1 - y0) / z;
+        if constexpr (PRIOR) p = (pi * q) * p;
+        const double l = rho * r * (pi * a0 - q * a1) * (y0 - y1) / z;
         s_p += p; s_l += l; s_ap += fabs(p); s_al += fabs(l);
       });
     }
@@ -406,11 +444,11 @@ __global__ __launch_bounds__(kRwThreads) void rh_grad_kernel(RgArgs g) {
     const double sum_p = read_sum<WAVES>(s_p, sh_sum), sum_l = read_sum<WAVES>(s_l, sh_sum), sum_ap = read_sum<WAVES>(s_ap, sh_sum);
     const double sum_al = read_sum<WAVES>(s_al, sh_sum), post0 = read_sum<WAVES>(s_post, sh_sum);
     if (geo.t == 0) {
-      const double first = post0 - a.pi;
+      const double first = post0 - (PRIOR ? pr[0] : a.pi);
       o.ll[read] = ll;
-      o.g_eta[read] = first + g.piq * sum_p;
+      o.g_eta[read] = PRIOR ? first + sum_p : first + g.piq * sum_p;
       o.g_lam[read] = sum_l;
-      if (o.abs_eta) o.abs_eta[read] = fabs(first) + g.piq * sum_ap;
+      if (o.abs_eta) o.abs_eta[read] = PRIOR ? fabs(first) + sum_ap : fabs(first) + g.piq * sum_ap;
       if (o.abs_lam) o.abs_lam[read] = sum_al;
       if (o.status) o.status[read] = 0;
     }
@@ -479,10 +517,12 @@ extern "C" int nmod_read_sites_count(const nmod_params* prm, int64_t nreads, con
   return NMOD_OK;
 }
 
-extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
-                             const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
-                             const nmod_hmm_opts* opts, const nmod_hmm_out* out) {
+// nmod_read_hmm (prior false: site_pi unread) and nmod_read_hmm_prior: one body, the kernels' instances chosen at the launch
+static int rh_hmm_entry(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
+                        int64_t nsites, const int64_t* key, bool prior, const double* site_pi, const int64_t* hoff, int64_t nrows,
+                        const nmod_hmm_opts* opts, const nmod_hmm_out* out) {
   if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
+  if (prior && nsites > 0 && !site_pi) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_hmm_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_hmm_out)) return NMOD_ERR_INVALID_ARG;
   if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
@@ -511,6 +551,7 @@ extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32
   // asked for none): the forward vector; for the host entry the inputs and outputs as well
   Slab& slab = c.slab;
   const size_t o_alpha = slab.take(a.backward ? nw * 16 : 0);
+  if (prior) c.prior(site_pi, opts->pi, 1);
   c.stage();
   slab.out(a.out.post, nw * 8); slab.out(a.out.site, nw * 4); slab.out(a.out.state, nw);
   slab.out(a.out.n_sites, nr * 4); slab.out(a.out.n_mod, nr * 4); slab.out(a.out.n_can, nr * 4); slab.out(a.out.n_runs, nr * 4);
@@ -518,22 +559,37 @@ extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32
   slab.out(a.out.site_n, ns * 4); slab.out(a.out.site_mod, ns * 4); slab.out(a.out.site_can, ns * 4);
   NMOD_HIP(slab.commit(c.stream, prm->device));
   c.bind(o.site);
-  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha);
+  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha); a.share = c.share;
 
   if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, c.stream));
   if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, c.stream));
   if (o.site_can) NMOD_HIP(hipMemsetAsync(o.site_can, 0, ns * 4, c.stream));
   if (nreads > 0) {
     NMOD_HIP(c.lists(a.w));
-    rh_launch(a, rh_hmm_kernel<1>, rh_hmm_kernel<kRwWaves>, c.num_cus, c.stream);
+    if (prior) rh_launch(a, rh_hmm_kernel<1, true>, rh_hmm_kernel<kRwWaves, true>, c.num_cus, c.stream);
+    else rh_launch(a, rh_hmm_kernel<1, false>, rh_hmm_kernel<kRwWaves, false>, c.num_cus, c.stream);
   }
   return launches_end(slab, c.stream);
 }
 
-extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
-                                  const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
-                                  const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
+extern "C" int nmod_read_hmm(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                             const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                             const nmod_hmm_opts* opts, const nmod_hmm_out* out) {
+  return rh_hmm_entry(prm, nreads, cs, start, roff, score, nsites, key, false, nullptr, hoff, nrows, opts, out);
+}
+
+extern "C" int nmod_read_hmm_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                   const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff,
+                                   int64_t nrows, const nmod_hmm_opts* opts, const nmod_hmm_out* out) {
+  return rh_hmm_entry(prm, nreads, cs, start, roff, score, nsites, key, true, site_pi, hoff, nrows, opts, out);
+}
+
+// nmod_read_hmm_grad and nmod_read_hmm_grad_prior, as rh_hmm_entry
+static int rh_grad_entry(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff, const double* score,
+                         int64_t nsites, const int64_t* key, bool prior, const double* site_pi, const int64_t* hoff, int64_t nrows,
+                         const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
   if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
+  if (prior && nsites > 0 && !site_pi) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_hmm_grad_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_hmm_grad_out)) return NMOD_ERR_INVALID_ARG;
   if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
@@ -561,20 +617,34 @@ extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const 
   Slab& slab = c.slab;
   const size_t o_alpha = slab.take(nw * 16);
   const size_t o_ll = o.ll ? 0 : slab.take(nr * 8), o_ge = o.g_eta ? 0 : slab.take(nr * 8), o_gl = o.g_lam ? 0 : slab.take(nr * 8);
+  if (prior) c.prior(site_pi, opts->pi, 1);
   c.stage();
   slab.out(o.ll, nr * 8); slab.out(o.g_eta, nr * 8); slab.out(o.g_lam, nr * 8); slab.out(o.abs_eta, nr * 8); slab.out(o.abs_lam, nr * 8);
   slab.out(o.status, nr); slab.out(o.sums, 8 * sizeof(double));
   NMOD_HIP(slab.commit(c.stream, prm->device));
   c.bind(nullptr);
-  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha);
+  a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha); a.share = c.share;
   if (!o.ll) o.ll = slab.at<double>(o_ll);
   if (!o.g_eta) o.g_eta = slab.at<double>(o_ge);
   if (!o.g_lam) o.g_lam = slab.at<double>(o_gl);
 
   if (nreads > 0) {
     NMOD_HIP(c.lists(a.w));
-    rh_launch(g, rh_grad_kernel<1>, rh_grad_kernel<kRwWaves>, c.num_cus, c.stream);
+    if (prior) rh_launch(g, rh_grad_kernel<1, true>, rh_grad_kernel<kRwWaves, true>, c.num_cus, c.stream);
+    else rh_launch(g, rh_grad_kernel<1, false>, rh_grad_kernel<kRwWaves, false>, c.num_cus, c.stream);
   }
   if (o.sums) hipLaunchKernelGGL(rh_grad_sums_kernel, dim3(1), dim3(256), 0, c.stream, nreads, a.hoff, nrows, o.ll, o.g_eta, o.g_lam, o.sums);
   return launches_end(slab, c.stream);
+}
+
+extern "C" int nmod_read_hmm_grad(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                  const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                                  const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
+  return rh_grad_entry(prm, nreads, cs, start, roff, score, nsites, key, false, nullptr, hoff, nrows, opts, out);
+}
+
+extern "C" int nmod_read_hmm_grad_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                        const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff,
+                                        int64_t nrows, const nmod_hmm_grad_opts* opts, const nmod_hmm_grad_out* out) {
+  return rh_grad_entry(prm, nreads, cs, start, roff, score, nsites, key, true, site_pi, hoff, nrows, opts, out);
 }

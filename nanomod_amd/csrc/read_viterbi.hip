@@ -6,6 +6,8 @@
 //   rh_entries_kernel<., 1>  (read_hmm.hip, through ChainCall) entry j of the read writes its site, position and score to row hoff[r] + j
 //   rv_viterbi_kernel<1>     a wave per read of up to NMOD_HMM_WAVE_MAX entries, four waves a workgroup
 //   rv_viterbi_kernel<4>     a workgroup of four waves per longer read
+// nmod_read_viterbi_prior (K23) is the same entry with the <., true> instances: per row (pi_j, log q_j, log pi_j), resolved once a call by
+// read_hmm.hip's rh_share_kernel behind the fill, is read beside xs; the other instances never see it.
 // K19's scan in the (max, +) algebra: rv_tile<., BWD> is rh_tile with a sum for every product and the larger for every sum, no exponent
 // word and no rescaling, and the replay hands the back-pointers of a step to its caller with the vector.  Three passes per read: the
 // forward scan (back-pointers, a byte per row, and the forward vectors where delta is asked for, both in the call's slab), the traceback
@@ -32,6 +34,7 @@ struct RvArgs {
   double pi, q, length, lq, lpi;
   bool trace, back;                               // an output that needs the path / delta was asked for
   nmod_vit_out out;
+  const double* share;                            // the prior entry: per row (pi_j, log q_j, log pi_j) (unread by the other instances)
 };
 
 struct LMat { double a, b, c, d; };               // [[a, b], [c, d]] of logarithms: rows the state before, columns the state after
@@ -65,9 +68,10 @@ __device__ __forceinline__ LMat rv_shfl_up(const LMat& m, int d) {
 }
 
 // Step k of the scan over the m entries at xs (position, score per entry).  Forward: L_k = log T_k + le_k by column, T_0 the identity.
-// Backward: the transpose of L_j for j = m - k, the identity at k = 0.  The identity beyond the read
-template <bool BWD>
-__device__ __forceinline__ LMat rv_step(const RvArgs& a, const double* xs, int64_t k, int64_t m) {
+// Backward: the transpose of L_j for j = m - k, the identity at k = 0.  The identity beyond the read.  PRIOR: the share and its logarithms
+// are pr[3 j ..], those of the entry arrived at, and q_j = 1 - pi_j is formed here; pr is unread otherwise
+template <bool BWD, bool PRIOR>
+__device__ __forceinline__ LMat rv_step(const RvArgs& a, const double* xs, const double* pr, int64_t k, int64_t m) {
   const double ninf = -__builtin_huge_val();
   LMat o{0.0, ninf, ninf, 0.0};
   if (k >= m || (BWD && k == 0)) return o;
@@ -79,7 +83,9 @@ __device__ __forceinline__ LMat rv_step(const RvArgs& a, const double* xs, int64
     const double r = (xs[2 * j] - xs[2 * (j - 1)]) / a.length;
     const double rho = exp(-r), eps = -expm1(-r);
     const double leps = log(eps);                               // three logarithms a step: log(pi eps) = log pi + log eps, and so for q
-    l00 = log(a.q + a.pi * rho); l01 = a.lpi + leps; l10 = a.lq + leps; l11 = log(a.pi + a.q * rho);
+    double pi = a.pi, q = a.q, lq = a.lq, lpi = a.lpi;
+    if constexpr (PRIOR) { pi = pr[3 * j]; q = 1.0 - pi; lq = pr[3 * j + 1]; lpi = pr[3 * j + 2]; }
+    l00 = log(q + pi * rho); l01 = lpi + leps; l10 = lq + leps; l11 = log(pi + q * rho);
   }
   if constexpr (BWD) { o.a = l00 + le0; o.b = l10 + le0; o.c = l01 + le1; o.d = l11 + le1; }
   else { o.a = l00 + le0; o.b = l01 + le1; o.c = l10 + le0; o.d = l11 + le1; }
@@ -91,15 +97,16 @@ struct RvShared { LMat tot[kRwWaves]; LVec carry; };
 // One tile of the scan, steps k0 .. k0 + T * kHmmChunk - 1, by the T threads of the read: per_entry(k, x, psi) with x the row vector
 // after step k and psi its back-pointers, for the steps inside the read.  Returns the vector after the tile's last step (thread T - 1's),
 // the same in every thread.  (rh_tile of read_hmm.hip in the other algebra: DESIGN.md §3 K20 says why it is a sibling.)
-template <int WAVES, bool BWD, class F>
-__device__ __forceinline__ LVec rv_tile(const RvArgs& a, const double* xs, int64_t m, int64_t k0, const LVec& carry, RvShared& sh, F per_entry) {
+template <int WAVES, bool BWD, bool PRIOR, class F>
+__device__ __forceinline__ LVec rv_tile(const RvArgs& a, const double* xs, const double* pr, int64_t m, int64_t k0, const LVec& carry, RvShared& sh,
+                                        F per_entry) {
   constexpr int T = WAVES * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = WAVES == 1 ? lane : (int)threadIdx.x;
   const int64_t kb = k0 + (int64_t)t * kHmmChunk;
   LMat step[kHmmChunk];
 #pragma unroll
-  for (int c = 0; c < kHmmChunk; ++c) step[c] = rv_step<BWD>(a, xs, kb + c, m);
+  for (int c = 0; c < kHmmChunk; ++c) step[c] = rv_step<BWD, PRIOR>(a, xs, pr, kb + c, m);
   LMat prod = step[0];
 #pragma unroll
   for (int c = 1; c < kHmmChunk; ++c) prod = rv_mul(prod, step[c]);
@@ -144,7 +151,7 @@ __device__ __forceinline__ int rv_apply(unsigned f, int z) { return (int)((f >> 
 // first f, then g
 __device__ __forceinline__ unsigned rv_compose(unsigned f, unsigned g) { return ((g >> (f & 1u)) & 1u) | (((g >> ((f >> 1) & 1u)) & 1u) << 1); }
 
-template <int WAVES>
+template <int WAVES, bool PRIOR>
 __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
   __shared__ unsigned sh_item;
   __shared__ int sh_cnt[2 * kRwWaves];
@@ -172,14 +179,16 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
       continue;
     }
     const double* xs = a.xs + 2 * base;
+    const double* pr = PRIOR ? a.share + 3 * base : nullptr;
     double* alpha = a.alpha + 2 * base;
     uint8_t* psi_row = a.psi + base;
 
     // forward: the vectors, the back-pointers and the sum of the positive scores, a thread's entries in ascending order
     double s_pos = 0.0;
     LVec fw{a.lq, a.lpi};
+    if constexpr (PRIOR) { fw.x0 = pr[1]; fw.x1 = pr[2]; }
     for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
-      fw = rv_tile<WAVES, false>(a, xs, m, k0, fw, sh_scan, [&](int64_t k, const LVec& x, unsigned psi) {
+      fw = rv_tile<WAVES, false, PRIOR>(a, xs, pr, m, k0, fw, sh_scan, [&](int64_t k, const LVec& x, unsigned psi) {
         if (a.back) { alpha[2 * k] = x.x0; alpha[2 * k + 1] = x.x1; }
         if (a.trace) psi_row[k] = (uint8_t)psi;
         s_pos += fmax(xs[2 * k + 1], 0.0);
@@ -270,7 +279,7 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
     if (a.back) {
       LVec bw{0.0, 0.0};
       for (int64_t k0 = 0; k0 < m; k0 += geo.TS) {
-        bw = rv_tile<WAVES, true>(a, xs, m, k0, bw, sh_scan, [&](int64_t k, const LVec& x, unsigned) {
+        bw = rv_tile<WAVES, true, PRIOR>(a, xs, pr, m, k0, bw, sh_scan, [&](int64_t k, const LVec& x, unsigned) {
           const int64_t j = m - 1 - k;
           o.delta[base + j] = (alpha[2 * j + 1] + x.x1) - (alpha[2 * j] + x.x0);
         });
@@ -290,10 +299,12 @@ __global__ __launch_bounds__(kRwThreads) void rv_viterbi_kernel(RvArgs a) {
 
 using namespace nmod;
 
-extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
-                                 const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
-                                 const nmod_vit_opts* opts, const nmod_vit_out* out) {
+// nmod_read_viterbi (prior false: site_pi unread) and nmod_read_viterbi_prior: one body, the kernel's instances chosen at the launch
+static int rv_viterbi_entry(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                            const double* score, int64_t nsites, const int64_t* key, bool prior, const double* site_pi, const int64_t* hoff,
+                            int64_t nrows, const nmod_vit_opts* opts, const nmod_vit_out* out) {
   if (!rh_chain_args_ok(prm, nreads, cs, start, roff, score, nsites, key, hoff, nrows)) return NMOD_ERR_INVALID_ARG;
+  if (prior && nsites > 0 && !site_pi) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_vit_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_vit_out)) return NMOD_ERR_INVALID_ARG;
   if (!rh_chain_opts_ok(opts->pi, opts->length)) return NMOD_ERR_INVALID_ARG;
@@ -321,6 +332,7 @@ extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const i
   // asked for none): the forward vector (delta) and the back-pointers (the path); for the host entry the inputs and outputs as well
   Slab& slab = c.slab;
   const size_t o_alpha = slab.take(a.back ? nw * 16 : 0), o_psi = slab.take(a.trace ? nw : 0);
+  if (prior) c.prior(site_pi, opts->pi, 3);
   c.stage();
   slab.out(a.out.path, nw); slab.out(a.out.site, nw * 4); slab.out(a.out.delta, nw * 8);
   slab.out(a.out.n_sites, nr * 4); slab.out(a.out.n_mod, nr * 4); slab.out(a.out.n_runs, nr * 4);
@@ -329,12 +341,26 @@ extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const i
   NMOD_HIP(slab.commit(c.stream, prm->device));
   c.bind(o.site);
   a.hoff = c.e.hoff; a.xs = c.e.xs; a.site = c.e.site; a.alpha = slab.at<double>(o_alpha); a.psi = slab.at<uint8_t>(o_psi);
+  a.share = c.share;
 
   if (o.site_n) NMOD_HIP(hipMemsetAsync(o.site_n, 0, ns * 4, c.stream));
   if (o.site_mod) NMOD_HIP(hipMemsetAsync(o.site_mod, 0, ns * 4, c.stream));
   if (nreads > 0) {
     NMOD_HIP(c.lists(a.w));
-    rh_launch(a, rv_viterbi_kernel<1>, rv_viterbi_kernel<kRwWaves>, c.num_cus, c.stream);
+    if (prior) rh_launch(a, rv_viterbi_kernel<1, true>, rv_viterbi_kernel<kRwWaves, true>, c.num_cus, c.stream);
+    else rh_launch(a, rv_viterbi_kernel<1, false>, rv_viterbi_kernel<kRwWaves, false>, c.num_cus, c.stream);
   }
   return launches_end(slab, c.stream);
+}
+
+extern "C" int nmod_read_viterbi(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                 const double* score, int64_t nsites, const int64_t* key, const int64_t* hoff, int64_t nrows,
+                                 const nmod_vit_opts* opts, const nmod_vit_out* out) {
+  return rv_viterbi_entry(prm, nreads, cs, start, roff, score, nsites, key, false, nullptr, hoff, nrows, opts, out);
+}
+
+extern "C" int nmod_read_viterbi_prior(const nmod_params* prm, int64_t nreads, const int32_t* cs, const int64_t* start, const int64_t* roff,
+                                       const double* score, int64_t nsites, const int64_t* key, const double* site_pi, const int64_t* hoff,
+                                       int64_t nrows, const nmod_vit_opts* opts, const nmod_vit_out* out) {
+  return rv_viterbi_entry(prm, nreads, cs, start, roff, score, nsites, key, true, site_pi, hoff, nrows, opts, out);
 }

@@ -1072,12 +1072,23 @@ def _check_chain_offsets(hoff, nreads):
     return hoff
 
 
-def _chain_host(entry, make_out, shapes, opts, reads, hoff, device):
+def _host_site_pi(site_pi, nsites):
+    """the per-site shares of a host prior entry (K23): a float64 array of nsites elements, its values as they are (the entry clamps
+    them and takes a NaN for `no estimate`); nothing is converted: another dtype or length is a ValueError"""
+    if not isinstance(site_pi, np.ndarray) or site_pi.dtype != np.float64 or site_pi.shape != (nsites,):
+        raise ValueError('site_pi must be a numpy float64[nsites] array (nsites = %d)' % nsites)
+    return np.ascontiguousarray(site_pi)
+
+
+def _chain_host(entry, make_out, shapes, opts, reads, hoff, device, site_pi=None):
     """What the host wrappers of the chain entries (K19 .. K22) share after the checks of their own arguments.  entry: the C entry's
     name; make_out: its out struct from pointers by name; shapes(nrows, nreads, nsites): the table of its outputs; opts: its opts
-    struct, None for an entry without one (the class rows); reads: (cs, start, roff, score, key); hoff: None, computed here.
+    struct, None for an entry without one (the class rows); reads: (cs, start, roff, score, key); hoff: None, computed here;
+    site_pi: None, or the per-site shares: the entry is then <entry>_prior, which takes them after key (K23).
     Returns the outputs and hoff."""
     cs, start, roff, score, key, nreads = _host_site_reads(*reads)
+    if site_pi is not None:
+        site_pi = _host_site_pi(site_pi, key.shape[0])
     if hoff is None:
         hoff = read_sites_host(cs, start, roff, score, key, device)
     hoff = _check_chain_offsets(hoff, nreads)
@@ -1090,22 +1101,25 @@ def _chain_host(entry, make_out, shapes, opts, reads, hoff, device):
     _join_warm_up(device)
     out = make_out(**_np_ptrs(res))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, entry, prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0], _np_ptr(key), _np_ptr(hoff), nrows,
-          *(() if opts is None else (C.byref(opts),)), C.byref(out))
+    prior = () if site_pi is None else (_np_ptr(site_pi),)
+    _call(lib, entry + ('_prior' if prior else ''), prm, nreads, _np_ptr(cs), _np_ptr(start), _np_ptr(roff), _np_ptr(score), key.shape[0],
+          _np_ptr(key), *prior, _np_ptr(hoff), nrows, *(() if opts is None else (C.byref(opts),)), C.byref(out))
     res['hoff'] = hoff
     return res
 
 
-def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, device=0):
+def read_hmm_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, device=0, site_pi=None):
     """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, include/nanomod_hip.h) on host-resident
     reads: the arguments of read_sites_host and the hoff it gives (None: computed here).  pi: the stationary modified share; length: the
-    correlation length in bases; call_post: the posterior from which an entry is called.  Returns a dict of numpy arrays, hoff and those
+    correlation length in bases; call_post: the posterior from which an entry is called; site_pi: None, or a float64 array of one modified
+    share per candidate site (nmod_read_hmm_prior, K23: clamped to 1e-9 .. 1 - 1e-9 by the entry, a NaN stands for pi; read_viterbi_host
+    and read_hmm_grad_host take it in the same way).  Returns a dict of numpy arrays, hoff and those
     named in `want`: per entry post (float64), site (int32, the index into key), state (uint8: 1 modified, 0 canonical, 2 neither); per
     read n_sites, n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod,
     site_can (int32)."""
     opts, want = _hmm_opts(pi, length, call_post, want)
     return _chain_host('nmod_read_hmm', L.make_hmm_out, lambda nrows, nreads, nsites: _hmm_shapes(want, nrows, nreads, nsites), opts,
-                       (cs, start, roff, score, key), hoff, device)
+                       (cs, start, roff, score, key), hoff, device, site_pi)
 
 
 VIT_OUTPUTS = L.VIT_ENTRY_FIELDS + L.VIT_READ_FIELDS + L.VIT_SITE_FIELDS
@@ -1123,7 +1137,7 @@ def _vit_shapes(want, nrows, nreads, nsites):
     return {k: kinds[k] for k in VIT_OUTPUTS if k in want}
 
 
-def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, device=0):
+def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, device=0, site_pi=None):
     """Per-read Viterbi decoding of read_hmm_host's chain (nmod_read_viterbi, include/nanomod_hip.h) on host-resident reads: the
     arguments of read_hmm_host without call_post.  Returns a dict of numpy arrays, hoff and those named in `want`: per entry path (uint8,
     the state on the most probable path), site (int32, the index into key), delta (float64, the max-marginal margin of state 1 over
@@ -1131,7 +1145,7 @@ def read_viterbi_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=
     L.HMM_NO_SITE); per site site_n, site_mod (int32)."""
     opts, want = _vit_opts(pi, length, want)
     return _chain_host('nmod_read_viterbi', L.make_vit_out, lambda nrows, nreads, nsites: _vit_shapes(want, nrows, nreads, nsites), opts,
-                       (cs, start, roff, score, key), hoff, device)
+                       (cs, start, roff, score, key), hoff, device, site_pi)
 
 
 HMM_GRAD_OUTPUTS = L.HMM_GRAD_READ_FIELDS + ('sums',)
@@ -1148,15 +1162,16 @@ def _hmm_grad_shapes(want, nreads):
     return {k: kinds[k] for k in HMM_GRAD_OUTPUTS if k in want}
 
 
-def read_hmm_grad_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, device=0):
+def read_hmm_grad_host(cs, start, roff, score, key, hoff=None, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, device=0, site_pi=None):
     """The log-likelihood of read_hmm_host's chain and its gradient in eta = logit(pi) and lam = ln(length) (nmod_read_hmm_grad,
     include/nanomod_hip.h) on host-resident reads: the arguments of read_hmm_host without call_post.  Returns a dict of numpy arrays, hoff
     and those named in `want`: per read ll (read_hmm_host's, bit for bit), g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
     L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS: the sums over the reads of ll, the gradient and its products, the reads with an
-    entry and the entries) — what readllr.fit_hmm takes per evaluation."""
+    entry and the entries) — what readllr.fit_hmm takes per evaluation.  With site_pi (nmod_read_hmm_grad_prior) g_eta is the derivative
+    in a common logit offset of all shares, at the shares given."""
     opts, want = _hmm_grad_opts(pi, length, want)
     return _chain_host('nmod_read_hmm_grad', L.make_hmm_grad_out, lambda nrows, nreads, nsites: _hmm_grad_shapes(want, nreads), opts,
-                       (cs, start, roff, score, key), hoff, device)
+                       (cs, start, roff, score, key), hoff, device, site_pi)
 
 
 CLASS_ROWS_OUTPUTS = L.CLASS_ROWS_FIELDS
@@ -1807,47 +1822,58 @@ class DeviceDetector:
         _call(self.lib, 'nmod_read_sites_count', prm, *shared, hoff.data_ptr(), C.byref(nrows))
         return hoff, int(nrows.value)
 
-    def _chain(self, what, make_out, shapes, opts, reads, hoff, nrows, out):
+    def _chain(self, what, make_out, shapes, opts, reads, hoff, nrows, out, site_pi=None):
         """What the device methods of the chain entries (K19 .. K22) share after the checks of their own arguments: _chain_host's
-        arguments, `what` the method's name (the entry is nmod_<what>), hoff and nrows as read_sites gives them, out the caller's."""
+        arguments, `what` the method's name (the entry is nmod_<what>, nmod_<what>_prior with site_pi: a float64 CUDA vector of
+        nsites shares), hoff and nrows as read_sites gives them, out the caller's."""
         nreads, shared = self._site_reads(what, *reads)
         _cuda_vecs(what, (('hoff', hoff, self.torch.int64, nreads + 1),), one_dim=True, missing='refused')
         nsites = reads[4].numel()
+        if site_pi is not None:
+            if not hasattr(site_pi, 'is_cuda'):
+                raise ValueError('%s: site_pi must be a contiguous torch.float64 CUDA vector of %d elements' % (what, nsites))
+            _cuda_vecs(what, (('site_pi', site_pi, self.torch.float64, nsites),), one_dim=True)
+            if site_pi.device != reads[4].device:
+                raise ValueError('%s: site_pi must live on the device of the reads' % what)
         nrows = _check_hmm_counts(nreads, nsites, nrows)
         shapes = shapes(nrows, nreads, nsites)
         res = self._outputs(out, shapes, what)
         o = make_out(**{name: res[name].data_ptr() for name in shapes})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_' + what, prm, *shared, hoff.data_ptr(), nrows, *(() if opts is None else (C.byref(opts),)), C.byref(o))
+        prior = () if site_pi is None else (site_pi.data_ptr(),)
+        _call(self.lib, 'nmod_' + what + ('_prior' if prior else ''), prm, *shared, *prior, hoff.data_ptr(), nrows,
+              *(() if opts is None else (C.byref(opts),)), C.byref(o))
         return res
 
-    def read_hmm(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, out=None):
+    def read_hmm(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, call_post=0.9, want=HMM_OUTPUTS, out=None,
+                 site_pi=None):
         """Per-read two-state HMM smoothing of the window sums at candidate sites (nmod_read_hmm, NMOD_MEM_DEVICE), enqueued on the
         current stream without synchronising or reading anything back: the arguments of read_sites, hoff and nrows as it gives them.
         Returns a dict of CUDA tensors, those named in `want`: per entry post (float64), site (int32), state (uint8); per read n_sites,
         n_mod, n_can, n_runs (int32), ll, ll_indep (float64), status (uint8, L.HMM_NO_SITE); per site site_n, site_mod, site_can
-        (int32).  out: such a dict from an earlier call of the same shape."""
+        (int32).  out: such a dict from an earlier call of the same shape.  site_pi: None, or a float64 CUDA vector of one share per
+        candidate site (nmod_read_hmm_prior, K23; read_viterbi and read_hmm_grad take it in the same way)."""
         opts, want = _hmm_opts(pi, length, call_post, want)
         return self._chain('read_hmm', L.make_hmm_out, lambda nrows, nreads, nsites: _hmm_shapes(want, nrows, nreads, nsites), opts,
-                           (cs, start, roff, score, key), hoff, nrows, out)
+                           (cs, start, roff, score, key), hoff, nrows, out, site_pi)
 
-    def read_viterbi(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, out=None):
+    def read_viterbi(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=VIT_OUTPUTS, out=None, site_pi=None):
         """Per-read Viterbi decoding of read_hmm's chain (nmod_read_viterbi, NMOD_MEM_DEVICE), enqueued on the current stream without
         synchronising or reading anything back: the arguments of read_hmm without call_post.  Returns a dict of CUDA tensors, those
         named in `want`: per entry path (uint8), site (int32), delta (float64); per read n_sites, n_mod, n_runs (int32), vit (float64),
         status (uint8, L.HMM_NO_SITE); per site site_n, site_mod (int32).  out: such a dict from an earlier call of the same shape."""
         opts, want = _vit_opts(pi, length, want)
         return self._chain('read_viterbi', L.make_vit_out, lambda nrows, nreads, nsites: _vit_shapes(want, nrows, nreads, nsites), opts,
-                           (cs, start, roff, score, key), hoff, nrows, out)
+                           (cs, start, roff, score, key), hoff, nrows, out, site_pi)
 
-    def read_hmm_grad(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, out=None):
+    def read_hmm_grad(self, cs, start, roff, score, key, hoff, nrows, *, pi=0.5, length=200.0, want=HMM_GRAD_OUTPUTS, out=None, site_pi=None):
         """The log-likelihood of read_hmm's chain and its gradient in logit(pi) and ln(length) (nmod_read_hmm_grad, NMOD_MEM_DEVICE),
         enqueued on the current stream without synchronising or reading anything back: the arguments of read_hmm without call_post.
         Returns a dict of CUDA tensors, those named in `want`: per read ll, g_eta, g_lam, abs_eta, abs_lam (float64), status (uint8,
         L.HMM_NO_SITE); sums (float64[8], L.HMM_GRAD_SUMS).  out: such a dict from an earlier call of the same shape."""
         opts, want = _hmm_grad_opts(pi, length, want)
         return self._chain('read_hmm_grad', L.make_hmm_grad_out, lambda nrows, nreads, nsites: _hmm_grad_shapes(want, nreads), opts,
-                           (cs, start, roff, score, key), hoff, nrows, out)
+                           (cs, start, roff, score, key), hoff, nrows, out, site_pi)
 
     def read_class_rows(self, cs, start, roff, score, key, hoff, nrows, *, want=CLASS_ROWS_OUTPUTS, out=None):
         """The rows of the latent-class fit (nmod_read_class_rows, NMOD_MEM_DEVICE), enqueued on the current stream without

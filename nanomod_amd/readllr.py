@@ -367,12 +367,14 @@ def _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_sha
         site_pi = share['pi'][keep]
     res = dict(det=det, names=names, nreads=nreads, d_cs=t(cs), d_start=t(start), d_off=d_off, llr_win=llr_win, d_key=d_key, site_pi=site_pi)
     if want_share == 'per_site':                  # K14's estimate of every candidate site in d_key's order, NaN where it has none
-        pk = piv['key']
+        pk = piv['key']                           # (and its count of scored reads, 0 at a site K14 has no row for)
         if pk.numel() == 0 or d_key.numel() == 0:
             res['site_pi_at'] = torch.full((d_key.numel(),), math.nan, dtype=torch.float64, device=dev)
+            res['site_n_valid_at'] = torch.zeros(d_key.numel(), dtype=torch.int32, device=dev)
         else:
             at = torch.searchsorted(pk, d_key).clamp_(max=pk.numel() - 1)
             res['site_pi_at'] = torch.where((pk[at] == d_key) & estimated[at], share['pi'][at], torch.full_like(share['pi'][at], math.nan))
+            res['site_n_valid_at'] = torch.where(pk[at] == d_key, share['n_valid'][at], torch.zeros_like(share['n_valid'][at]))
     return res
 
 
@@ -502,9 +504,30 @@ def read_domains(hoff, site, state, post, site_pos, delta=None):
     return res
 
 
+def site_prior(pi_hat, n_valid, mean, prior_reads):
+    """The per-site shares the read chain takes as its prior (K23) from K14's estimates: pi_hat shrunk towards `mean` with the weight of
+    `prior_reads` reads, (n_valid * pi_hat + prior_reads * mean) / (n_valid + prior_reads), NaN where pi_hat is NaN (the entries take
+    their opts->pi there).  Pure numpy.  prior_reads > 0 and mean inside (0, 1): an estimate of exactly 0 or 1 from a few reads never
+    becomes a hard 0 or 1.  n_valid: the site's count of scored reads, >= 0."""
+    mean, prior_reads = float(mean), float(prior_reads)
+    if not 0.0 < mean < 1.0:
+        raise ValueError('site_prior: mean must lie inside (0, 1), not %r' % (mean,))
+    if not 0.0 < prior_reads < math.inf:
+        raise ValueError('site_prior: prior_reads must be positive and finite, not %r' % (prior_reads,))
+    pi_hat, n = np.asarray(pi_hat, np.float64), np.asarray(n_valid, np.float64)
+    if pi_hat.shape != n.shape:
+        raise ValueError('site_prior: pi_hat and n_valid must have one shape')
+    if bool(np.any(~(n >= 0.0))) or bool(np.any((pi_hat < 0.0) | (pi_hat > 1.0))):
+        raise ValueError('site_prior: n_valid must be >= 0 and pi_hat a share in 0 .. 1 (or NaN)')
+    return (n * pi_hat + prior_reads * mean) / (n + prior_reads)
+
+
+_site_prior_of = site_prior                       # (smooth_reads_llr has an argument of that name)
+
+
 def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length=200.0, fit_length=None, call_post=0.9, window='kmer',
                      rescale=None, site_alpha=0.05, thr=2.5, prior=0.5, min_positions=1, device=0, log=print, decode='posterior', fit=None,
-                     fix_pi=False):
+                     fix_pi=None, site_prior=False, prior_reads=4.0):
     """Per-read two-state HMM smoothing of the window sums at candidate sites (K19, nmod_read_sites_count / nmod_read_hmm): along each
     molecule, where are the modified stretches, and what is the call at a weak site once its neighbours on the same read are taken into
     account?  The optional rescaling (K11), the window sums (K13) and the candidate sites exactly as in cooccur_reads_llr; then, read by
@@ -529,7 +552,12 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
     fit: None, or 'mle': pi and length are fitted by maximum likelihood over all reads (K21, nmod_read_hmm_grad through fit_hmm) from
     the pi and length chosen as above, on the device tensors already there, one call per evaluation; fix_pi keeps pi and fits length
     alone.  The decoding uses the fitted values, the result gains the key `fit` (fit_hmm's dict) and one more line goes to `log`.
-    Not together with fit_length."""
+    Not together with fit_length.
+    site_prior: every candidate site gets a share of its own (K23, the _prior entries of K19 - K21): K14's estimate of the site and its
+    count of scored reads, shrunk by site_prior() towards `mean` with the weight of prior_reads reads; `mean` is the pi chosen as above
+    (or given), which also stands in at a site without an estimate.  prior_reads=4.0 is a default of judgement, not a measurement.  All three entries take the shares; fit_length works unchanged;
+    with fit='mle' the shares are held and the length alone is fitted (fix_pi is implied; an explicit fix_pi=False is refused).  The
+    result gains `site_prior`: per candidate site chrom, strand, pos (0-based), pi_hat, n_valid and prior; one more line goes to `log`."""
     if decode not in ('posterior', 'viterbi', 'both'):
         raise ValueError("decode must be 'posterior', 'viterbi' or 'both', not %r" % (decode,))
     if fit not in (None, 'mle'):
@@ -538,6 +566,12 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         raise ValueError('fit and fit_length exclude each other: the fit chooses the length itself')
     if fix_pi and fit is None:
         raise ValueError("fix_pi needs fit='mle'")
+    if site_prior:
+        if fit is not None and fix_pi is not None and not fix_pi:
+            raise ValueError("site_prior holds the shares of the sites: fit='mle' fits the length alone, fix_pi=False cannot be asked for")
+        fix_pi = True if fit is not None else fix_pi
+        _site_prior_of(np.zeros(0), np.zeros(0), 0.5, prior_reads)                            # the refusal, before any device work
+    fix_pi = bool(fix_pi)
     setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
     site_alpha = engine._check_alpha(site_alpha)
     _sites_by_stoich(sites)
@@ -546,7 +580,7 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         raise ValueError('fit_length must name at least one length')
     for v in (grid or [length]):
         engine._hmm_opts(0.5 if pi is None else pi, v, call_post, ())                         # the refusals, before any device work
-    sc = _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_share=pi is None)
+    sc = _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_share='per_site' if site_prior else pi is None)
     det, names, nreads, d_key = sc['det'], sc['names'], sc['nreads'], sc['d_key']
     if pi is None:
         if sc['site_pi'].numel() == 0:
@@ -554,14 +588,24 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
         pi = min(max(float(sc['site_pi'].mean().item()), 1e-9), 1.0 - 1e-9)
     shared = (sc['d_cs'], sc['d_start'], sc['d_off'], sc['llr_win'], d_key)
     hoff, nrows = det.read_sites(*shared)
+    prior_kw, prior_out = {}, None
+    if site_prior:
+        import torch
+        prior_out = dict(pi_hat=sc['site_pi_at'].cpu().numpy(), n_valid=sc['site_n_valid_at'].cpu().numpy())
+        prior_out['prior'] = _site_prior_of(prior_out['pi_hat'], prior_out['n_valid'], pi, prior_reads)
+        prior_kw = dict(site_pi=torch.from_numpy(np.ascontiguousarray(prior_out['prior'])).to(d_key.device))
+        known = prior_out['prior'][~np.isnan(prior_out['prior'])]
+        log('readhmm: per-site prior: %d of %d candidate site(s) with an estimate, shrunk towards %.6g with the weight of %g read(s); shares %.6g .. %.6g'
+            % (len(known), len(prior_out['prior']), pi, float(prior_reads), known.min() if len(known) else math.nan,
+               known.max() if len(known) else math.nan))
     profile = []
     if grid is not None:
         for v in grid:
-            profile.append((v, math.fsum(det.read_hmm(*shared, hoff, nrows, pi=pi, length=v, call_post=call_post, want=('ll',))['ll'].cpu().tolist())))
+            profile.append((v, math.fsum(det.read_hmm(*shared, hoff, nrows, pi=pi, length=v, call_post=call_post, want=('ll',), **prior_kw)['ll'].cpu().tolist())))
         length = max(profile, key=lambda p: p[1])[0]
     fitted = None
     if fit is not None:
-        fitted = fit_hmm(lambda p, v: det.read_hmm_grad(*shared, hoff, nrows, pi=p, length=v, want=('sums',))['sums'].cpu().tolist(), pi, length,
+        fitted = fit_hmm(lambda p, v: det.read_hmm_grad(*shared, hoff, nrows, pi=p, length=v, want=('sums',), **prior_kw)['sums'].cpu().tolist(), pi, length,
                          fix_pi=fix_pi)
         pi, length = fitted['pi'], fitted['length']
         log('readhmm: maximum-likelihood fit: pi %.6g (%.6g .. %.6g), length %.6g (%.6g .. %.6g), log-likelihood %.6f; %d evaluation(s), %s; %s'
@@ -569,14 +613,18 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
                'converged' if fitted['converged'] else 'not converged', fitted['status']))
     key = d_key.cpu().numpy()
     nm = np.array(names, dtype=str)
+    if prior_out is not None:
+        prior_out.update(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                         pos=key & ((1 << 40) - 1))
     vit = None
     if decode != 'posterior':
-        vit = {f: v.cpu().numpy() for f, v in det.read_viterbi(*shared, hoff, nrows, pi=pi, length=length).items()}
+        vit = {f: v.cpu().numpy() for f, v in det.read_viterbi(*shared, hoff, nrows, pi=pi, length=length, **prior_kw).items()}
     if decode == 'viterbi':
-        out = dict(pi=pi, length=length, profile=profile, **({} if fitted is None else {'fit': fitted}))
+        out = dict(pi=pi, length=length, profile=profile, **({} if fitted is None else {'fit': fitted}),
+                   **({} if prior_out is None else {'site_prior': prior_out}))
         out['viterbi'] = _viterbi_result(vit, hoff.cpu().numpy(), key, nm, reads, nreads, None, None, pi, length, log)
         return out
-    res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post)
+    res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post, **prior_kw)
     res = {f: v.cpu().numpy() for f, v in res.items()}
     called = (res['site_mod'] + res['site_can']).astype(np.float64)
     with np.errstate(invalid='ignore', divide='ignore'):
@@ -593,6 +641,8 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
     out = dict(pi=pi, length=length, profile=profile, reads=table, entries=entries, sites=out_sites, domains=domains)
     if fitted is not None:
         out['fit'] = fitted
+    if prior_out is not None:
+        out['site_prior'] = prior_out
     if vit is not None:
         out['viterbi'] = _viterbi_result(vit, entries['hoff'], key, nm, reads, nreads, res['ll'], res['post'], pi, length, log)
     return out
@@ -793,6 +843,16 @@ def write_read_viterbi(path, res):
             (np.asarray(s['pos'], np.int64)[site] + 1).tolist(), np.asarray(e['path']).tolist(), np.asarray(e['delta'], np.float64).tolist()]
     with open(path, 'w') as f:
         f.writelines('%d %d %s %s %d %d %.6f\n' % row for row in zip(*cols))
+
+
+def write_site_prior(path, res):
+    """<FileID>_site_prior.txt: per candidate site 'chrom strand pos+1 n_valid pi_hat prior' as '%s %s %d %d %.9g %.9g' (the position
+    1-based; 'nan' twice at a site without an estimate; `res`: smooth_reads_llr's result with site_prior)"""
+    s = res['site_prior']
+    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist(),
+            np.asarray(s['n_valid'], np.int64).tolist(), np.asarray(s['pi_hat'], np.float64).tolist(), np.asarray(s['prior'], np.float64).tolist()]
+    with open(path, 'w') as f:
+        f.writelines('%s %s %d %d %.9g %.9g\n' % row for row in zip(*cols))
 
 
 def write_site_viterbi(path, res):
