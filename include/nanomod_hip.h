@@ -904,6 +904,73 @@ int nmod_site_diff(const nmod_params* prm, int64_t npos, const double* score0, c
                    const double* score1, const int64_t* off1 /* or prm->stride1 */,
                    const nmod_diff_opts* opts, const nmod_diff_out* out);
 
+/* The modified shares of two REPLICATED conditions compared per site: every replicate's estimate, the two condition-level estimates
+ * and their test as nmod_site_diff gives them for the pooled reads, the heterogeneity of the replicates inside their conditions, and
+ * a test and an interval of delta that carry the dispersion between replicates (K24; the reference project has no such step).  An
+ * analysis of deviance: the likelihood-ratio statistic of the conditions over the mean deviance between replicates, F on (1, G - 2).
+ *   Input.  Per site G = nsamples rows of float64 window sums, CSR only: one `score` array and off[npos * G + 1], row i * G + g for
+ *     site i and sample g.  The first `ncontrol` samples of every site are condition 0, the rest condition 1:
+ *     3 <= G <= NMOD_REP_MAX_SAMPLES, 1 <= ncontrol <= G - 1 (G = 2 is refused: that is nmod_site_diff).  The two condition
+ *     SUPER-ROWS of a site are therefore contiguous: off[i G] .. off[i G + ncontrol] and off[i G + ncontrol] .. off[(i + 1) G].
+ *   Per score, K14's quantities unchanged: VALID, the signed t, the EVALUATION (S, D, g), the estimate rule (0 iff S(0) <= 0, else 1 iff
+ *     S(1) >= 0, else the root), the BRACKETED ITERATION and its stop test; contraction is off for the unit.
+ *   No estimate (NaN outputs, iters 0, n_valid still written):
+ *       NMOD_REP_TOO_LARGE       a super-row beyond NMOD_MAX_DEEP scores (n_valid 0 in every sample)
+ *       NMOD_REP_TOO_FEW         any sample with fewer than min_valid valid scores: every replicate carries an estimate, and the
+ *                                degrees of freedom are G - 2 at every site
+ *       NMOD_REP_FLAT            otherwise, the sum of t is 0 in any sample
+ *   Three nested fits per site.
+ *     Saturated:  pi_s[g] = K14's estimate of sample row g alone;  g_sat = sum_g g_g(pi_s[g]), summed in ascending g.
+ *     Condition:  pi0, pi1, pi_pool, delta, stat_cond, p_cond, iters are exactly nmod_site_diff's pi0, pi1, pi_pool, delta, stat,
+ *       p_diff, iters for the two super-rows;  g_cond = g_0(pi0) + g_1(pi1).
+ *     Heterogeneity:  df = G - 2;  stat_het = max(2 (g_sat - g_cond), 0);  p_het = max(chi2_df tail of stat_het, DBL_MIN), with
+ *       x = stat_het / 2:  even df: exp(-x) sum_{m < df/2} x^m / m!;  odd df: erfc(sqrt(x)) + exp(-x) sum_{j=1..(df-1)/2}
+ *       x^(j - 1/2) / Gamma(j + 1/2);  phi = stat_het / df, the dispersion of the site.
+ *   The replicate-aware test.  phi_used = max(phi, opts->phi_floor);  F = stat_cond / phi_used;  p_rep = max(the two-sided Student t
+ *     tail of sqrt(F) on df degrees of freedom, DBL_MIN): the F(1, df) tail.  stat_cond == 0: p_rep = 1.  Otherwise phi_used == 0:
+ *     p_rep = DBL_MIN with NMOD_REP_PHI_ZERO.  phi_floor = 0 is the default of the Python layers; phi_floor = 1 never lets the
+ *     dispersion fall below the binomial one (methylKit's rule) and is very conservative.  phi_floor must be finite and >= 0.
+ *   The interval of delta: nmod_site_diff's profile-likelihood interval of the two super-rows at the drop phi_used * ci_drop (one
+ *     multiplication).  The caller passes ci_drop = the ci_level quantile of F(1, df).  phi_used == 0: the drop is 0, the interval
+ *     is the point delta_lo = delta_hi = delta and no interval root is run.  With delta_lo and delta_hi both NULL none is run either.
+ *   Status bits: NMOD_REP_TOO_FEW, FLAT, NOT_CONVERGED (any root of the three fits or of the interval still running at max_iter; the
+ *     values are written all the same), POOL_AT_END, TOO_LARGE with nmod_site_diff's values, and NMOD_REP_PHI_ZERO.
+ *   Outputs (a NULL member is skipped; requesting fewer never changes the bits of the others): doubles pi_s[npos * G] and, npos each,
+ *     pi0, pi1, pi_pool, delta, delta_lo, delta_hi, stat_cond, p_cond, stat_het, p_het, phi, p_rep; int32 n_valid[npos * G], iters;
+ *     uint8 status.
+ * Sums.  The condition level has nmod_site_diff's bits: the class of a site follows the longer super-row with its steps
+ * (NMOD_DIFF_SMALL: 16 lanes, NMOD_DIFF_WAVE: a wave, a workgroup beyond) and each class keeps its lane layout, reduction order and
+ * LDS stage, so that pi0, pi1, pi_pool, stat_cond, p_cond, iters and, at the same drop, delta_lo / delta_hi are the bytes
+ * nmod_site_diff gives for the concatenated rows.  A sample is an index range of its super-row: an element outside it enters the
+ * sample's sums as t = 0, which adds exactly 0 to S, D and g, and the G roots run one after the other over the data already resident.
+ * A sample's sums run in the sample's own order (the lane partials are rotated by its offset before they are reduced): pi_s[g] has the
+ * same bits wherever in its super-row sample g lies, so permuting the samples inside a condition permutes pi_s bit for bit.
+ * A site's bits depend on its rows, G and ncontrol alone, not on the batch, the order of the sites, the memspace or the outputs asked
+ * for; no float atomics.  Reads struct_size, device, stream, memspace of prm.  NMOD_MEM_DEVICE: everything is enqueued on
+ * prm->stream, no host read and no synchronisation.  npos == 0 is NMOD_OK.
+ * NMOD_ERR_INVALID_ARG before any device work: nmod_site_diff's refusals (opts, out, max_iter, min_valid, tol, ci_drop, prm, npos, a
+ * decreasing host off), off NULL, nsamples outside 3 .. NMOD_REP_MAX_SAMPLES, ncontrol outside 1 .. nsamples - 1, npos * nsamples
+ * beyond INT32_MAX - 1, phi_floor not finite or < 0.
+ * Limits: two conditions, no covariates or pairing; every sample must cover the site (a site with a thin replicate has no estimate);
+ * one dispersion per site, neither shared between sites nor shrunk, so that F on as few as 1 degree of freedom (2 v 1) has little
+ * power; both k-mer tables are taken as right; the F law is an approximation.  Measured with the numpy restatement on seeded null
+ * sites (share 0.3 in both conditions, levels 2 sd apart, replicates of 50 reads whose shares are drawn Beta with intraclass
+ * correlation rho; rejected at the 5 % level, of 400 sites per cell: tests/test_site_diff_rep.py, profiles/site_diff_rep.txt):
+ *     3 v 3, rho 0:     p_cond 0.045   p_rep 0.040   p_rep at phi_floor 1 0.005   p_het 0.043
+ *     3 v 3, rho 0.05:  p_cond 0.203   p_rep 0.053   p_rep at phi_floor 1 0.025   p_het 0.375
+ *     3 v 3, rho 0.15:  p_cond 0.403   p_rep 0.058   p_rep at phi_floor 1 0.050   p_het 0.768
+ *     2 v 2, rho 0.1:   p_cond 0.278   p_rep 0.028   p_rep at phi_floor 1 0.003   p_het 0.523 */
+#define NMOD_REP_MAX_SAMPLES 16            /* the largest G */
+enum { NMOD_REP_TOO_FEW = 1, NMOD_REP_FLAT = 2, NMOD_REP_NOT_CONVERGED = 4, NMOD_REP_POOL_AT_END = 8, NMOD_REP_PHI_ZERO = 16,
+       NMOD_REP_TOO_LARGE = 32 };
+typedef struct nmod_rep_opts { int32_t struct_size, max_iter, min_valid, reserved; double tol, ci_drop, phi_floor; } nmod_rep_opts;
+typedef struct nmod_rep_out { int32_t struct_size; int32_t reserved;
+  double *pi_s /* npos * G */, *pi0, *pi1, *pi_pool, *delta, *delta_lo, *delta_hi, *stat_cond, *p_cond, *stat_het, *p_het, *phi, *p_rep;
+  int32_t *n_valid /* npos * G */, *iters; uint8_t* status;
+} nmod_rep_out;
+int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score, const int64_t* off,
+                       const nmod_rep_opts* opts, const nmod_rep_out* out);
+
 /* Same-read co-occurrence of modification calls at pairs of sites: per pair the 2 x 2 table of the reads that have a call at both
  * sites, its log odds ratio, phi and the two-sided exact test (K16; the reference project has no such step).  K11 .. K15 reduce over
  * the reads of one position; this entry keeps the read: it walks the reads and counts, per pair of candidate sites, the reads by

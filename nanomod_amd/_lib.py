@@ -289,6 +289,35 @@ def make_diff_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP_9
 make_diff_out = functools.partial(make_out, NmodDiffOut)
 
 
+REP_TOO_FEW, REP_FLAT, REP_NOT_CONVERGED, REP_POOL_AT_END, REP_PHI_ZERO, REP_TOO_LARGE = 1, 2, 4, 8, 16, 32
+REP_NO_ESTIMATE = REP_TOO_FEW | REP_FLAT | REP_TOO_LARGE
+REP_MAX_SAMPLES = 16        # nmod_site_diff_rep: the largest number of samples of a site (the smallest is 3)
+REP_SAMPLE_FIELDS = ('pi_s',)                               # npos * G doubles
+REP_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond', 'p_cond', 'stat_het', 'p_het', 'phi', 'p_rep')
+REP_SAMPLE_INT_FIELDS = ('n_valid',)                        # npos * G int32
+REP_INT_FIELDS = ('iters',)
+
+
+class NmodRepOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'max_iter', 'min_valid', 'reserved')] + \
+               [('tol', C.c_double), ('ci_drop', C.c_double), ('phi_floor', C.c_double)]
+
+
+class NmodRepOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + \
+               [(n, C.c_void_p) for n in REP_SAMPLE_FIELDS + REP_FIELDS + REP_SAMPLE_INT_FIELDS + REP_INT_FIELDS + ('status',)]
+
+
+def make_rep_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP_95, phi_floor=0.0):
+    o = NmodRepOpts()
+    o.struct_size = C.sizeof(NmodRepOpts)
+    o.max_iter, o.min_valid, o.tol, o.ci_drop, o.phi_floor = int(max_iter), int(min_valid), float(tol), float(ci_drop), float(phi_floor)
+    return o
+
+
+make_rep_out = functools.partial(make_out, NmodRepOut)
+
+
 PAIRS_MAX_DIST = 65536      # nmod_pair_index: largest max_dist
 PAIRS_LDS_MAX = 2048        # nmod_site_pairs: pairs up to which the read kernel keeps the call's table in LDS
 PAIRS_THREAD_MAX = 64       # nmod_site_pairs: tables of a pair's support up to which one thread computes p_fisher (a wave beyond)
@@ -511,6 +540,8 @@ _SIGNATURES = {
     'nmod_site_stoich': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NmodStoichOpts), C.POINTER(NmodStoichOut)]),
     'nmod_site_diff': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodDiffOpts),
                                  C.POINTER(NmodDiffOut)]),
+    'nmod_site_diff_rep': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NmodRepOpts),
+                                     C.POINTER(NmodRepOut)]),
     'nmod_pair_index': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     'nmod_site_pairs': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.POINTER(NmodPairsOpts), C.POINTER(NmodPairsOut)]),

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -194,8 +195,9 @@ def build_parser():
     rd = sub.add_parser('readdiff', help='compare the modified share of every site between two read-level samples on the device: the '
                         'share of each, their difference with a profile-likelihood interval, and the likelihood-ratio test of equal shares')
     rd.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
-    rd.add_argument('--wrkBase1', required=True, help='sample 0, the control condition: a read-level .npz container')
-    rd.add_argument('--wrkBase2', required=True, help='sample 1: a read-level .npz container')
+    rd.add_argument('--wrkBase1', required=True, help='sample 0, the control condition: a read-level .npz container; or its replicates, '
+                    'comma-separated (three or more containers in all: the replicate-aware comparison)')
+    rd.add_argument('--wrkBase2', required=True, help='sample 1: a read-level .npz container; or its replicates, comma-separated')
     rd.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
     rd.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
     rd.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
@@ -206,10 +208,13 @@ def build_parser():
     rd.add_argument('--minCoverage', type=int, default=1, help='reads a site needs in each sample to be compared, > 0')
     rd.add_argument('--minValid', type=int, default=3, help='scored reads a site needs in each sample for an estimate, > 0')
     rd.add_argument('--ciLevel', type=float, default=0.95, help='the level of the interval of delta, inside (0, 1)')
-    rd.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_diff over all compared sites')
+    rd.add_argument('--phiFloor', type=float, default=0.0, help='replicates only: the dispersion between replicates never counts as less '
+                    '(0: as estimated; 1: never below binomial), >= 0')
+    rd.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_diff (with replicates: of p_rep) over '
+                    'all compared sites')
     rd.add_argument('--fdrAlpha', type=float, default=0.05)
     rd.add_argument('--outFolder', default='mRes')
-    rd.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_diff.txt')
+    rd.add_argument('--FileID', default='mod', help='written: <outFolder>/<FileID>_site_diff.txt (with replicates: <FileID>_site_diff_rep.txt)')
     rd.add_argument('--device', type=int, default=0)
     rp = sub.add_parser('readpairs', help='same-read co-occurrence of modification calls at pairs of nearby sites of one read-level sample '
                         'on the device: per pair the 2 x 2 table of the reads called at both sites, log odds ratio, phi and the exact test')
@@ -404,9 +409,20 @@ def validate_readllr(a):
     return errs
 
 
+def readdiff_samples(a):
+    """the containers of readdiff's two conditions: (--wrkBase1's, --wrkBase2's), each a comma-separated list; one file each is the
+    two-sample comparison"""
+    return a.wrkBase1.split(','), a.wrkBase2.split(',')
+
+
 def validate_readdiff(a):
     """the checks of readdiff, in validate_readllr's manner"""
     errs = []
+    c0, c1 = readdiff_samples(a)
+    if len(c0) + len(c1) > L.REP_MAX_SAMPLES:
+        errs.append('Error: --wrkBase1 and --wrkBase2 should name at most %d containers in all' % L.REP_MAX_SAMPLES)
+    if not (math.isfinite(a.phiFloor) and a.phiFloor >= 0.0):
+        errs.append('Error: --phiFloor should be finite and not negative')
     win = parse_llr_window(a.llrWindow)
     if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
         errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
@@ -422,11 +438,11 @@ def validate_readdiff(a):
         errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
     if not 0.0 < a.fdrAlpha <= 1.0:
         errs.append('Error: --fdrAlpha should be in (0, 1]')
-    for f in (a.wrkBase1, a.wrkBase2, a.kmerModel, a.altModel):
+    for f in c0 + c1 + [a.kmerModel, a.altModel]:
         if not os.path.isfile(f):
             errs.append('Error: input %s does not exist' % f)
     if not errs:
-        for opt, f in (('--wrkBase1', a.wrkBase1), ('--wrkBase2', a.wrkBase2)):
+        for opt, f in [('--wrkBase1', f) for f in c0] + [('--wrkBase2', f) for f in c1]:
             if not container.is_read_level(f):
                 errs.append('Error: %s %s is not a read-level container (per-position containers have no reads)' % (opt, f))
     return errs
@@ -562,6 +578,21 @@ def run_readpairs(a, log=print):
 def run_readdiff(a, log=print):
     from . import kmermodel, readllr
     quiet = a.outLevel > detect.OUTPUT_ERROR
+    c0, c1 = readdiff_samples(a)
+    if len(c0) + len(c1) > 2:
+        sites = readllr.compare_reads_llr_rep([container.load_reads(f) for f in c0], [container.load_reads(f) for f in c1],
+                                              kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
+                                              window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions,
+                                              rescale={} if a.rescale else None, min_coverage=a.minCoverage,
+                                              diff=dict(min_valid=a.minValid, ci_level=a.ciLevel, phi_floor=a.phiFloor),
+                                              fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, device=a.device,
+                                              log=(lambda *x: None) if quiet else log)
+        os.makedirs(a.outFolder, exist_ok=True)
+        path = os.path.join(a.outFolder, a.FileID + '_site_diff_rep.txt')
+        readllr.write_site_diff_rep(path, sites)
+        if not quiet:
+            log('Site comparisons are saved in %s' % path)
+        return sites
     sites = readllr.compare_reads_llr(container.load_reads(a.wrkBase1), container.load_reads(a.wrkBase2),
                                       kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                       window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions,

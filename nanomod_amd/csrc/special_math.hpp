@@ -258,4 +258,22 @@ __device__ inline double chi2_sf_even(double X, int W) {
   return sum > 1.0 ? 1.0 : sum;
 }
 
+// chi2.sf(X, 2M + 1) = erfc(sqrt(x)) + exp(-x) sum_{j=1..M} x^(j - 1/2) / Gamma(j + 1/2),  x = X/2   (K24's heterogeneity test at
+// an odd number of degrees of freedom; M = 0: the chi2_1 tail).  The terms run down from j = M, the first through its logarithm as
+// above: exp(-x) alone underflows from x = 745 on, where the tail of 13 degrees of freedom is still above DBL_MIN.
+__device__ inline double chi2_sf_odd(double X, int M) {
+  double x = 0.5 * X;
+  if (x != x) return x;
+  if (!(x > 0.0)) return 1.0;
+  if (isinf(x)) return 0.0;
+  double sum = erfc(sqrt(x));
+  if (M >= 1) {
+    double tm = exp(-x + ((double)M - 0.5) * log(x) - lgamma((double)M + 0.5));
+    sum += tm;
+#pragma unroll 1
+    for (int j = M; j >= 2; --j) { tm *= ((double)j - 0.5) / x; sum += tm; }
+  }
+  return sum > 1.0 ? 1.0 : sum;
+}
+
 }  // namespace nmod

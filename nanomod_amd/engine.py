@@ -852,6 +852,101 @@ def site_diff_host(score0, off0, score1, off1, *, stride0=0, stride1=0, min_vali
     return res
 
 
+def _t_two_sided_cdf(t, df):
+    """P(|T| <= t) of Student's t on an integer df >= 1 by the finite series in theta = atan(t / sqrt(df)) (Abramowitz & Stegun
+    26.7.3 / 26.7.4): no special function beyond atan, exact to rounding for the df <= 14 nmod_site_diff_rep can have"""
+    import math
+    theta = math.atan(t / math.sqrt(df))
+    s, c2 = math.sin(theta), math.cos(theta) ** 2
+    if df % 2:
+        term, total = math.cos(theta), 0.0                          # cos, 2/3 cos^3, (2 4)/(3 5) cos^5, ... up to cos^(df - 2)
+        for j in range(1, (df - 1) // 2 + 1):
+            total += term
+            term *= c2 * (2.0 * j) / (2.0 * j + 1.0)
+        return 2.0 / math.pi * (theta + s * total)
+    term, total = 1.0, 0.0                                          # 1, 1/2 cos^2, (1 3)/(2 4) cos^4, ... up to cos^(df - 2)
+    for j in range(1, df // 2 + 1):
+        total += term
+        term *= c2 * (2.0 * j - 1.0) / (2.0 * j)
+    return s * total
+
+
+def _f1_quantile(level, df):
+    """the `level` quantile of F(1, df), the square of the two-sided t quantile, by bisection on the monotone _t_two_sided_cdf: the
+    package imports no scipy"""
+    lo, hi = 0.0, 1.0
+    while _t_two_sided_cdf(hi, df) < level:
+        lo, hi = hi, 2.0 * hi
+        if hi > 1e300:
+            return float('inf')
+    for _ in range(200):
+        mid = lo + 0.5 * (hi - lo)
+        if mid <= lo or mid >= hi:
+            break
+        if _t_two_sided_cdf(mid, df) < level:
+            lo = mid
+        else:
+            hi = mid
+    t = lo + 0.5 * (hi - lo)
+    return t * t
+
+
+def _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, tol):
+    """nmod_rep_opts from the Python arguments, and (G, ncontrol): _stoich_opts' checks and ValueError for what the C entry refuses of
+    G, ncontrol and phi_floor.  ci_level becomes the drop the interval of delta is scaled from: the ci_level quantile of F(1, G - 2)"""
+    import math
+    o = _stoich_opts(min_valid, ci_level, max_iter, tol)
+    if int(n_samples) != n_samples or not 3 <= int(n_samples) <= L.REP_MAX_SAMPLES:
+        raise ValueError('n_samples must be an integer in 3 .. %d (two samples: site_diff), not %r' % (L.REP_MAX_SAMPLES, n_samples))
+    if int(n_control) != n_control or not 1 <= int(n_control) <= int(n_samples) - 1:
+        raise ValueError('n_control must be an integer in 1 .. n_samples - 1, not %r' % (n_control,))
+    phi_floor = float(phi_floor)
+    if not (math.isfinite(phi_floor) and phi_floor >= 0.0):
+        raise ValueError('phi_floor must be finite and >= 0, not %r' % (phi_floor,))
+    ci_drop = _f1_quantile(float(ci_level), int(n_samples) - 2)
+    if not (math.isfinite(ci_drop) and ci_drop > 0.0):
+        raise ValueError('ci_level %r gives no usable interval' % (ci_level,))
+    return L.make_rep_opts(o.max_iter, o.min_valid, o.tol, ci_drop, phi_floor), int(n_samples), int(n_control)
+
+
+def _rep_shapes(npos, n_samples, interval=True):
+    shapes = {k: ('float64', npos * n_samples) for k in L.REP_SAMPLE_FIELDS}
+    shapes.update({k: ('float64', npos) for k in L.REP_FIELDS if interval or k not in ('delta_lo', 'delta_hi')})
+    shapes.update({k: ('int32', npos * n_samples) for k in L.REP_SAMPLE_INT_FIELDS})
+    shapes.update({k: ('int32', npos) for k in L.REP_INT_FIELDS})
+    shapes['status'] = ('uint8', npos)
+    return shapes
+
+
+def _rep_npos(nrows, n_samples, what):
+    if nrows % n_samples:
+        raise ValueError('%s: off must hold n_samples rows per site: %d rows of %d samples' % (what, nrows, n_samples))
+    return nrows // n_samples
+
+
+def site_diff_rep_host(score, off, n_samples, n_control, *, min_valid=3, ci_level=0.95, phi_floor=0.0, max_iter=60, tol=1e-12, interval=True,
+                       device=0):
+    """The modified shares of two replicated conditions compared per site (nmod_site_diff_rep, include/nanomod_hip.h): score float64,
+    off int64[npos * n_samples + 1], row i * n_samples + g for site i and sample g; the first n_control samples of every site are
+    condition 0.  Returns a dict of numpy arrays: pi_s and n_valid per sample (npos * n_samples); per site pi0, pi1, pi_pool, delta,
+    with `interval` delta_lo and delta_hi at ci_level, stat_cond and p_cond (site_diff's test of the pooled reads), stat_het, p_het and
+    phi (the heterogeneity of the replicates and the dispersion), p_rep (the F(1, n_samples - 2) test of delta that carries it),
+    float64; iters (int32); status (uint8, L.REP_* bits).  phi_floor: the dispersion never counts as less (1.0: never below binomial)."""
+    lib = L.load()
+    opts, n_samples, n_control = _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, tol)
+    if off is None:
+        raise ValueError('site_diff_rep takes CSR rows: off is required')
+    score, off, _, nrows = _host_score_rows(score, off, 0)
+    npos = _rep_npos(nrows, n_samples, 'site_diff_rep')
+    shapes = _rep_shapes(npos, n_samples, interval)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodRepOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, _np_ptr(score), _np_ptr(off), C.byref(opts), C.byref(out))
+    return res
+
+
 PAIRS_OUTPUTS = L.PAIRS_INT_FIELDS + L.PAIRS_FIELDS + ('status',)
 
 
@@ -1723,6 +1818,22 @@ class DeviceDetector:
         _call(self.lib, 'nmod_site_diff', prm, npos0, score0.data_ptr(), _ptr(off0), score1.data_ptr(), _ptr(off1), C.byref(opts), C.byref(o))
         return res
 
+    def site_diff_rep(self, score, off, n_samples, n_control, *, min_valid=3, ci_level=0.95, phi_floor=0.0, max_iter=60, tol=1e-12,
+                      interval=True, out=None):
+        """The modified shares of two replicated conditions compared per site (nmod_site_diff_rep, NMOD_MEM_DEVICE) on the current
+        stream, nothing read back: score a float64 CUDA vector, off an int64 CUDA vector of npos * n_samples + 1 offsets, row
+        i * n_samples + g for site i and sample g, the first n_control samples condition 0 (engine.match_score_rows_multi makes them).
+        Returns a dict of CUDA tensors as site_diff_rep_host's arrays.  p_rep, p_cond and p_het are tracks fdr() takes as they are."""
+        opts, n_samples, n_control = _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, tol)
+        _cuda_vecs('site_diff_rep', (('score', score, self.torch.float64, None),), one_dim=True)
+        npos = _rep_npos(_device_offsets(self.torch, off, 'site_diff_rep', 'npos * n_samples'), n_samples, 'site_diff_rep')
+        shapes = _rep_shapes(npos, n_samples, interval)
+        res = self._outputs(out, shapes, 'site_diff_rep')
+        o = L.make_out(L.NmodRepOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, score.data_ptr(), off.data_ptr(), C.byref(opts), C.byref(o))
+        return res
+
     def pair_index(self, key, max_dist=100):
         """The pairs of candidate sites at most max_dist apart on one (chrom, strand) (nmod_pair_index, NMOD_MEM_DEVICE) on the current
         stream: key an int64 CUDA vector of cs << 40 | pos, strictly ascending (not checked).  Synchronises the stream once to learn
@@ -2216,3 +2327,42 @@ def match_score_rows(g0, g1, min_coverage, device=0):
                                    off0.data_ptr(), off1.data_ptr(), ptr(sig0), ptr(sig1), ptr(run), ptr(key), ptr(b0), ptr(b1)),
             'nmod_gather_tested')
     return dict(key=key, base=b1, off0=off0, off1=off1, sig0=sig0, sig1=sig1, names=list(g1['names']))
+
+
+def match_score_rows_multi(pivots, n_control, min_coverage, device=0):
+    """The sites that every one of several pivoted score tracks (pivot_reads(..., val=llr_win) per sample, the same `names`; the first
+    n_control of them condition 0) holds with at least min_coverage scores, in key order, gathered site-major as float64: the inputs
+    of DeviceDetector.site_diff_rep.  Off the hot path: torch as plumbing, with the synchronisations its data-dependent shapes take.
+    Returns device tensors key, base (the last sample's), off (npos * G + 1, row i * G + g), sig, and names, n_samples, n_control."""
+    import torch
+    G = len(pivots)
+    if not 3 <= G <= L.REP_MAX_SAMPLES or not 1 <= int(n_control) <= G - 1:
+        raise ValueError('match_score_rows_multi takes 3 .. %d samples with 1 .. G - 1 of them controls' % L.REP_MAX_SAMPLES)
+    names = list(pivots[0]['names'])
+    if any(list(g['names']) != names for g in pivots):
+        raise ValueError('all samples must be pivoted with the same chromosome names')
+    if any(g['sig'].dtype != torch.float64 for g in pivots):
+        raise ValueError('match_score_rows_multi takes float64 score rows (pivot_reads with val=llr_win)')
+    dev = torch.device('cuda', device)
+    cov = [g['off'][1:] - g['off'][:-1] for g in pivots]
+    kept = [g['key'][c >= int(min_coverage)] for g, c in zip(pivots, cov)]
+    allk, cnt = torch.unique(torch.cat(kept), sorted=True, return_counts=True)        # (a pivot's keys are distinct)
+    key = allk[cnt == G]
+    npos = key.numel()
+    rows = [torch.searchsorted(g['key'], key) for g in pivots]
+    lens = torch.stack([c[r] for c, r in zip(cov, rows)], dim=1) if npos else torch.zeros((0, G), dtype=torch.int64, device=dev)
+    off = torch.zeros(npos * G + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens.reshape(-1), 0, out=off[1:])
+    sig = torch.empty(int(off[-1]), dtype=torch.float64, device=dev)
+    for g, (piv, r) in enumerate(zip(pivots, rows)):
+        n = lens[:, g]
+        tot = int(n.sum())
+        if not tot:
+            continue
+        first = torch.cumsum(n, 0) - n
+        within = torch.arange(tot, dtype=torch.int64, device=dev) - torch.repeat_interleave(first, n)
+        src = torch.repeat_interleave(piv['off'][:-1][r], n) + within
+        dst = torch.repeat_interleave(off[:-1].reshape(npos, G)[:, g], n) + within
+        sig[dst] = piv['sig'][src]
+    base = pivots[-1]['base'][rows[-1]] if npos else torch.zeros(0, dtype=torch.uint8, device=dev)
+    return dict(key=key, base=base, off=off, sig=sig, names=names, n_samples=G, n_control=int(n_control))

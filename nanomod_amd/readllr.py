@@ -266,6 +266,109 @@ def write_site_diff(path, sites):
         f.writelines(fmt % row for row in zip(*cols))
 
 
+_REP_KEYS = ('min_valid', 'ci_level', 'phi_floor', 'max_iter', 'tol')
+SITE_DIFF_REP_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond', 'p_cond', 'stat_het', 'p_het', 'phi', 'p_rep')
+
+
+def compare_reads_llr_rep(reads0_list, reads1_list, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None,
+                          min_coverage=1, diff={}, fdr=None, fdr_alpha=0.05, names=None, device=0, log=print):
+    """Compare the modified share of every site between two replicated conditions: reads0_list the read-level sets
+    (container.READ_FIELDS) of the control condition's replicates, reads1_list those of the other; three or more sets in all.
+    compare_reads_llr's chain per sample — the optional rescaling (K11), the window sums (K13), the pivot with one list of chromosome
+    names — then the sites every sample holds with at least min_coverage reads (engine.match_score_rows_multi) compared by
+    nmod_site_diff_rep (K24).  diff: a dict of engine.site_diff_rep_host's options (min_valid, ci_level, phi_floor, max_iter, tol).
+    fdr: None, 'bh' or 'by': p_rep goes through nmod_fdr_adjust on the device at fdr_alpha and `sites` gains q.
+    Returns `sites`, one entry per matched site: chrom, strand, pos, base, n_samples, n_control, n_valid and pi_s (npos x G), pi0, pi1,
+    pi_pool, delta, delta_lo, delta_hi, stat_cond, p_cond, stat_het, p_het, phi, p_rep, [q,] rep_status (uint8, L.REP_* bits).  One
+    summary line goes to `log`."""
+    import torch
+    reads = list(reads0_list) + list(reads1_list)
+    n_control, G = len(reads0_list), len(reads)
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    if rescale is not None:
+        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
+        if unknown:
+            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    unknown = sorted(set(diff) - set(_REP_KEYS))
+    if unknown:
+        raise ValueError('diff: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_REP_KEYS)))
+    engine._rep_opts(G, n_control, *(diff.get(key, default) for key, default in zip(_REP_KEYS, (3, 0.95, 0.0, 60, 1e-12))))
+    if fdr is not None:
+        engine._fdr_method(fdr)
+    if int(min_coverage) != min_coverage or int(min_coverage) < 1:
+        raise ValueError('min_coverage must be an integer >= 1, not %r' % (min_coverage,))
+    samples = [_checked_reads(r, 'reads%d[%d]' % (g >= n_control, g - n_control if g >= n_control else g)) for g, r in enumerate(reads)]
+    every = engine.chrom_names(*reads)
+    names = every if names is None else [str(n) for n in names]
+    lacking = sorted(set(every) - set(names))
+    if lacking or names != sorted(set(names)):
+        raise ValueError('names must be the sorted chromosome names of all samples; missing or out of order: %s' % (', '.join(lacking) or 'order'))
+    engine._join_warm_up(device)
+    det = engine.DeviceDetector(device)
+    dev = torch.device('cuda', device)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+    pivots = []
+    for rd, (val, off, base) in zip(reads, samples):
+        d_val, d_off, d_base = t(val), t(off), t(base)
+        if rescale is not None:
+            d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
+        calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
+                             prior_logit=prior_logit, want=('llr_win',))
+        pivots.append(engine.pivot_reads(rd, device, names=names, val=calls['llr_win']))
+    rows = engine.match_score_rows_multi(pivots, n_control, int(min_coverage), device)
+    res = det.site_diff_rep(rows['sig'], rows['off'], G, n_control, **diff)
+    q = None
+    if fdr is not None:
+        (q,), _ = det.fdr(res, tracks=('p_rep',), method=fdr, alpha=fdr_alpha)
+    key = rows['key'].cpu().numpy()
+    nm = np.array(names, dtype=str)
+    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
+                 pos=key & ((1 << 40) - 1), base=rows['base'].cpu().numpy().view('S1').astype('U1'), n_samples=G, n_control=n_control,
+                 n_valid=res['n_valid'].cpu().numpy().reshape(-1, G), pi_s=res['pi_s'].cpu().numpy().reshape(-1, G),
+                 **{f: res[f].cpu().numpy() for f in SITE_DIFF_REP_FIELDS})
+    if q is not None:
+        sites['q'] = q.cpu().numpy()
+    sites['rep_status'] = res['status'].cpu().numpy()
+    est = (sites['rep_status'] & L.REP_NO_ESTIMATE) == 0
+    log('readdiff: %d and %d sample(s) of %s read(s); %d site(s) in every sample with at least %d read(s), %d with an estimate, %d with an '
+        'interval of delta that excludes 0%s'
+        % (n_control, G - n_control, ', '.join(str(len(s[1]) - 1) for s in samples), len(key), int(min_coverage), int(est.sum()),
+           int((est & ((sites['delta_lo'] > 0.0) | (sites['delta_hi'] < 0.0))).sum()),
+           '' if q is None else '; %d with q <= %g (%s)' % (int((sites['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
+    return sites
+
+
+def write_site_diff_rep(path, sites):
+    """<FileID>_site_diff_rep.txt: per site 'chrom strand pos+1 base G', then n_valid and pi_s of every sample ('%d %.6f' each), then
+    'pi0 pi1 pi_pool delta delta_lo delta_hi stat_cond p_cond stat_het p_het phi p_rep [q] status' as six '%.6f' + '%.3f %.3E %.3f
+    %.3E %.3f %.3E [%.3E] %d' (write_site_diff's formats: the position 1-based; 'nan' as Python spells it where the site has no
+    estimate; `sites` of compare_reads_llr_rep)"""
+    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
+    G = int(sites['n_samples'])
+    nv, ps = np.asarray(sites['n_valid']).reshape(-1, G), np.asarray(sites['pi_s']).reshape(-1, G)
+    per = []
+    for g in range(G):
+        per += [nv[:, g].tolist(), ps[:, g].tolist()]
+    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
+            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist(), [G] * len(nv)] + per + \
+           [np.asarray(sites[f]).tolist() for f in ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond')] + \
+           [sci(sites['p_cond']), np.asarray(sites['stat_het']).tolist(), sci(sites['p_het']), np.asarray(sites['phi']).tolist(), sci(sites['p_rep'])] + \
+           ([sci(sites['q'])] if 'q' in sites else []) + [np.asarray(sites['rep_status']).tolist()]
+    fmt = '%s %s %d %s %d ' + '%d %.6f ' * G + '%.6f %.6f %.6f %.6f %.6f %.6f %.3f %s %.3f %s %.3f %s ' + ('%s ' if 'q' in sites else '') + '%d\n'
+    with open(path, 'w') as f:
+        f.writelines(fmt % row for row in zip(*cols))
+
+
 _PAIR_STAT_FIELDS = ('log_or', 'se', 'phi', 'p_fisher')
 LINK_MIN_READS = 20         # reads valid at both sites below which the soft linkage of a pair is not fitted (include/nanomod_hip.h, K18)
 
