@@ -305,6 +305,31 @@ def build_parser():
     return p
 
 
+def _read_inputs_checked(errs, a, files):
+    """the tail the checks of the read-level commands share: the input files exist and --wrkBase1 is a read-level container"""
+    for f in files:
+        if not os.path.isfile(f):
+            errs.append('Error: input %s does not exist' % f)
+    if not errs and not container.is_read_level(a.wrkBase1):
+        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
+    return errs
+
+
+def _quiet_log(a, log):
+    """the log of a read-level command: `log`, or nothing above --outLevel error"""
+    return (lambda *x: None) if a.outLevel > detect.OUTPUT_ERROR else log
+
+
+def _save(a, say, suffix, write, what, *tables):
+    """make --outFolder, write(<outFolder>/<FileID><suffix>, *tables), and with `what` say where it went; returns the path"""
+    os.makedirs(a.outFolder, exist_ok=True)
+    path = os.path.join(a.outFolder, a.FileID + suffix)
+    write(path, *tables)
+    if what:
+        say('%s saved in %s' % (what, path))
+    return path
+
+
 def parse_classes(text):
     """--classes: the list of counts of 'C' or 'C,C,...'; None for anything else"""
     parts = text.split(',')
@@ -338,31 +363,20 @@ def validate_readclasses(a):
         errs.append('Error: --tol should be finite and not negative')
     if not 0.0 < a.siteAlpha <= 1.0:
         errs.append('Error: --siteAlpha should be in (0, 1]')
-    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)))
 
 
 def run_readclasses(a, log=print):
     from . import kmermodel, readllr
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
     res = readllr.cluster_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                     sites=sites, classes=parse_classes(a.classes), n_init=a.nInit, seed=a.seed, max_iter=a.maxIter, tol=a.tol,
                                     window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None, site_alpha=a.siteAlpha,
-                                    thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
-                                    log=(lambda *x: None) if quiet else log)
-    os.makedirs(a.outFolder, exist_ok=True)
-    for suffix, write, what in (('_read_classes.txt', readllr.write_read_classes, 'Read classes are'),
-                                ('_class_sites.txt', readllr.write_class_sites, 'Class shares per site are'),
-                                ('_classes_fit.txt', readllr.write_classes_fit, 'The fits are')):
-        path = os.path.join(a.outFolder, a.FileID + suffix)
-        write(path, res)
-        if not quiet:
-            log('%s saved in %s' % (what, path))
+                                    thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device, log=say)
+    _save(a, say, '_read_classes.txt', readllr.write_read_classes, 'Read classes are', res)
+    _save(a, say, '_class_sites.txt', readllr.write_class_sites, 'Class shares per site are', res)
+    _save(a, say, '_classes_fit.txt', readllr.write_classes_fit, 'The fits are', res)
     return res
 
 
@@ -401,12 +415,7 @@ def validate_readllr(a):
         errs.append('Error: --minValid should be larger than 0')
     if not 0.0 < a.ciLevel < 1.0:
         errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
-    for f in (a.wrkBase1, a.kmerModel, a.altModel):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel))
 
 
 def readdiff_samples(a):
@@ -470,12 +479,7 @@ def validate_readpairs(a):
         errs.append('Error: --fdrAlpha should be in (0, 1]')
     if not 0.0 < a.ciLevel < 1.0:
         errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
-    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)))
 
 
 def validate_readhmm(a):
@@ -508,26 +512,20 @@ def validate_readhmm(a):
         errs.append('Error: --callPost should lie between 0.5 and 1, both excluded')
     if not 0.0 < a.siteAlpha <= 1.0:
         errs.append('Error: --siteAlpha should be in (0, 1]')
-    for f in (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel) + (() if a.sites == 'stoich' else (a.sites,)))
 
 
 def run_readhmm(a, log=print):
     from . import kmermodel, readllr
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
     res = readllr.smooth_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                    sites=sites, pi=a.hmmPi, length=a.hmmLength, fit_length=None if a.fitLength is None else parse_fit_length(a.fitLength),
                                    call_post=a.callPost, window=parse_llr_window(a.llrWindow), rescale={} if a.rescale else None,
                                    site_alpha=a.siteAlpha, thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions, device=a.device,
-                                   log=(lambda *x: None) if quiet else log, **({} if a.decode == 'posterior' else {'decode': a.decode}),
+                                   log=say, **({} if a.decode == 'posterior' else {'decode': a.decode}),
                                    **({'fit': 'mle', 'fix_pi': bool(a.fixPi or a.sitePrior)} if a.fitHmm else {}),
                                    **({'site_prior': True, 'prior_reads': a.priorReads} if a.sitePrior else {}))
-    os.makedirs(a.outFolder, exist_ok=True)
     files = []
     if a.fitHmm:
         files.append(('_hmm_fit.txt', readllr.write_hmm_fit, 'The fit of pi and length is', res['fit']))
@@ -541,91 +539,63 @@ def run_readhmm(a, log=print):
         files += [('_read_viterbi.txt', readllr.write_read_viterbi, 'Viterbi paths are', v),
                   ('_read_domains_viterbi.txt', readllr.write_read_domains, 'Viterbi domains are', v),
                   ('_site_viterbi.txt', readllr.write_site_viterbi, 'Viterbi site counts are', v)]
-    for suffix, write, what, arg in files:
-        path = os.path.join(a.outFolder, a.FileID + suffix)
-        write(path, arg)
-        if not quiet:
-            log('%s saved in %s' % (what, path))
-    if not quiet:
-        for v, ll in res['profile']:
-            log('length %g: log-likelihood %.6f%s' % (v, ll, ' *' if v == res['length'] else ''))
+    for suffix, write, what, table in files:
+        _save(a, say, suffix, write, what, table)
+    for v, ll in res['profile']:
+        say('length %g: log-likelihood %.6f%s' % (v, ll, ' *' if v == res['length'] else ''))
     return res
 
 
 def run_readpairs(a, log=print):
     from . import kmermodel, readllr
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     sites = 'stoich' if a.sites == 'stoich' else readllr.read_sites_file(a.sites)
     pairs = readllr.cooccur_reads_llr(container.load_reads(a.wrkBase1), kmermodel.load_kmer_model(a.kmerModel),
                                       kmermodel.load_kmer_model(a.altModel), sites=sites, max_dist=a.maxDist, thr=a.llrThreshold,
                                       min_reads=a.minReads, window=parse_llr_window(a.llrWindow), prior=a.prior,
                                       min_positions=a.minPositions, rescale={} if a.rescale else None,
                                       fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, site_alpha=a.siteAlpha, device=a.device,
-                                      log=(lambda *x: None) if quiet else log, **(dict(soft=True, ci_level=a.ciLevel) if a.soft else {}))
-    os.makedirs(a.outFolder, exist_ok=True)
-    path = os.path.join(a.outFolder, a.FileID + '_site_pairs.txt')
-    readllr.write_site_pairs(path, pairs)
-    if not quiet:
-        log('Site pairs are saved in %s' % path)
+                                      log=say, **(dict(soft=True, ci_level=a.ciLevel) if a.soft else {}))
+    _save(a, say, '_site_pairs.txt', readllr.write_site_pairs, 'Site pairs are', pairs)
     if a.soft:
-        path = os.path.join(a.outFolder, a.FileID + '_site_linkage.txt')
-        readllr.write_site_linkage(path, pairs)
-        if not quiet:
-            log('Site linkage is saved in %s' % path)
+        _save(a, say, '_site_linkage.txt', readllr.write_site_linkage, 'Site linkage is', pairs)
     return pairs
 
 
 def run_readdiff(a, log=print):
     from . import kmermodel, readllr
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     c0, c1 = readdiff_samples(a)
+    models = lambda: (kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel))
+    shared = dict(window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions, rescale={} if a.rescale else None,
+                  min_coverage=a.minCoverage, fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, device=a.device, log=say)
     if len(c0) + len(c1) > 2:
-        sites = readllr.compare_reads_llr_rep([container.load_reads(f) for f in c0], [container.load_reads(f) for f in c1],
-                                              kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
-                                              window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions,
-                                              rescale={} if a.rescale else None, min_coverage=a.minCoverage,
-                                              diff=dict(min_valid=a.minValid, ci_level=a.ciLevel, phi_floor=a.phiFloor),
-                                              fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, device=a.device,
-                                              log=(lambda *x: None) if quiet else log)
-        os.makedirs(a.outFolder, exist_ok=True)
-        path = os.path.join(a.outFolder, a.FileID + '_site_diff_rep.txt')
-        readllr.write_site_diff_rep(path, sites)
-        if not quiet:
-            log('Site comparisons are saved in %s' % path)
-        return sites
-    sites = readllr.compare_reads_llr(container.load_reads(a.wrkBase1), container.load_reads(a.wrkBase2),
-                                      kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
-                                      window=parse_llr_window(a.llrWindow), prior=a.prior, min_positions=a.minPositions,
-                                      rescale={} if a.rescale else None, min_coverage=a.minCoverage,
-                                      diff=dict(min_valid=a.minValid, ci_level=a.ciLevel), fdr=None if a.fdr == 'none' else a.fdr,
-                                      fdr_alpha=a.fdrAlpha, device=a.device, log=(lambda *x: None) if quiet else log)
-    os.makedirs(a.outFolder, exist_ok=True)
-    path = os.path.join(a.outFolder, a.FileID + '_site_diff.txt')
-    readllr.write_site_diff(path, sites)
-    if not quiet:
-        log('Site comparisons are saved in %s' % path)
+        sites = readllr.compare_reads_llr_rep([container.load_reads(f) for f in c0], [container.load_reads(f) for f in c1], *models(),
+                                              diff=dict(min_valid=a.minValid, ci_level=a.ciLevel, phi_floor=a.phiFloor), **shared)
+        _save(a, say, '_site_diff_rep.txt', readllr.write_site_diff_rep, 'Site comparisons are', sites)
+    else:
+        sites = readllr.compare_reads_llr(container.load_reads(a.wrkBase1), container.load_reads(a.wrkBase2), *models(),
+                                          diff=dict(min_valid=a.minValid, ci_level=a.ciLevel), **shared)
+        _save(a, say, '_site_diff.txt', readllr.write_site_diff, 'Site comparisons are', sites)
     return sites
 
 
 def run_readllr(a, log=print):
     from . import kmermodel, readllr
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     reads = container.load_reads(a.wrkBase1)
     res = readllr.call_reads_llr(reads, kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                  window=parse_llr_window(a.llrWindow), thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions,
-                                 rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device,
-                                 log=(lambda *x: None) if quiet else log,
+                                 rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device, log=say,
                                  **(dict(stoich=dict(min_valid=a.minValid, ci_level=a.ciLevel)) if a.siteFraction else {}))
     table, sites = res[0], res[1]
-    os.makedirs(a.outFolder, exist_ok=True)
-    readllr.write_read_llr(os.path.join(a.outFolder, a.FileID + '_read_llr.txt'), table)
-    readllr.write_site_llr(os.path.join(a.outFolder, a.FileID + '_site_llr.txt'), sites)
+    first = _save(a, say, '_read_llr.txt', readllr.write_read_llr, None, table)
+    _save(a, say, '_site_llr.txt', readllr.write_site_llr, None, sites)
     if a.siteFraction:
-        readllr.write_site_stoich(os.path.join(a.outFolder, a.FileID + '_site_stoich.txt'), sites)
+        _save(a, say, '_site_stoich.txt', readllr.write_site_stoich, None, sites)
     if a.outEvents:
         np.savez(a.outEvents, off=np.asarray(reads['off'], dtype=np.int64), **res[2])
-    if not quiet:
-        log('Read calls are saved in %s' % os.path.join(a.outFolder, a.FileID + '_read_llr.txt'))
+    say('Read calls are saved in %s' % first)                  # (the first file alone is announced)
     return res
 
 
@@ -638,29 +608,21 @@ def validate_readcalls(a):
         errs.append('Error: --callAlpha should be larger than 0 and not larger than 1')
     if a.minPositions < 1:
         errs.append('Error: --minPositions should be larger than 0')
-    for f in (a.wrkBase1, a.kmerModel):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel))
 
 
 def run_readcalls(a, log=print):
     from . import kmermodel, readcalls
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     reads = container.load_reads(a.wrkBase1)
     res = readcalls.call_reads(reads, kmermodel.load_kmer_model(a.kmerModel), nb=a.neighborPvalues, alpha=a.callAlpha,
-                               min_positions=a.minPositions, rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device,
-                               log=(lambda *x: None) if quiet else log)
+                               min_positions=a.minPositions, rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device, log=say)
     table, sites = res[0], res[1]
-    os.makedirs(a.outFolder, exist_ok=True)
-    readcalls.write_read_calls(os.path.join(a.outFolder, a.FileID + '_read_calls.txt'), table)
-    readcalls.write_site_calls(os.path.join(a.outFolder, a.FileID + '_site_calls.txt'), sites)
+    first = _save(a, say, '_read_calls.txt', readcalls.write_read_calls, None, table)
+    _save(a, say, '_site_calls.txt', readcalls.write_site_calls, None, sites)
     if a.outEvents:
         np.savez(a.outEvents, off=np.asarray(reads['off'], dtype=np.int64), **res[2])
-    if not quiet:
-        log('Read calls are saved in %s' % os.path.join(a.outFolder, a.FileID + '_read_calls.txt'))
+    say('Read calls are saved in %s' % first)                  # (the first file alone is announced)
     return res
 
 
@@ -677,27 +639,19 @@ def validate_rescale(a):
         errs.append('Error: --scaleLo should be positive, finite and not above --scaleHi')
     if a.minPositions < 1:
         errs.append('Error: --minPositions should be larger than 0')
-    for f in (a.wrkBase1, a.kmerModel):
-        if not os.path.isfile(f):
-            errs.append('Error: input %s does not exist' % f)
-    if not errs and not container.is_read_level(a.wrkBase1):
-        errs.append('Error: --wrkBase1 %s is not a read-level container (per-position containers have no reads)' % a.wrkBase1)
-    return errs
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel))
 
 
 def run_rescale(a, log=print):
     from . import kmermodel, rescale
-    quiet = a.outLevel > detect.OUTPUT_ERROR
+    say = _quiet_log(a, log)
     reads = container.load_reads(a.wrkBase1)
     out, table = rescale.rescale_reads(reads, kmermodel.load_kmer_model(a.kmerModel), weighted=not a.unweighted, clip_sigma=a.clipSigma,
                                        clip_rounds=a.clipRounds, min_events=a.minEvents, scale_range=(a.scaleLo, a.scaleHi),
-                                       min_positions=a.minPositions, drop_failed=a.dropFailed, device=a.device,
-                                       log=(lambda *x: None) if quiet else log)
+                                       min_positions=a.minPositions, drop_failed=a.dropFailed, device=a.device, log=say)
     container.save_reads(a.outReads, out['chrom'], out['strand'], out['start'], out['off'], out['norm_mean'], out['base'])
-    os.makedirs(a.outFolder, exist_ok=True)
-    rescale.write_read_scale(os.path.join(a.outFolder, a.FileID + '_read_scale.txt'), reads, table)
-    if not quiet:
-        log('Rescaled reads are saved in %s' % a.outReads)
+    _save(a, say, '_read_scale.txt', rescale.write_read_scale, None, reads, table)
+    say('Rescaled reads are saved in %s' % a.outReads)
     return out, table
 
 

@@ -2116,6 +2116,22 @@ def chrom_strand_ids(chrom, strand, names, what='reads'):
     return (2 * cid + (strand == '-')).astype(np.int32)
 
 
+def key_sites(key, names):
+    """chrom, strand and pos (a dict of numpy arrays, in that order) of a host vector of nmod_pivot_reads' keys cs << 40 | pos over the
+    chromosome list `names`; chrom of no key is a zero-length str array"""
+    key = np.asarray(key)
+    return dict(chrom=np.array(names, dtype=str)[key >> 41] if len(key) else np.zeros(0, dtype=str),
+                strand=np.where((key >> 40) & 1, '-', '+').astype('U1'), pos=key & ((1 << 40) - 1))
+
+
+def read_head(reads, nreads, off=None):
+    """the leading columns of a per-read table of a read-level set: index, chrom, strand and, with the reads' offsets, start and events"""
+    head = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str))
+    if off is not None:
+        head.update(start=np.asarray(reads['start'], dtype=np.int64), events=np.diff(off))
+    return head
+
+
 class _CallTimer:
     """HIP events around one library call on the current stream; adds its device time (s) to timer[name] when timer is a dict"""
 

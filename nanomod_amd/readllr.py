@@ -26,10 +26,44 @@ import numpy as np
 from . import _lib as L
 from . import engine
 from . import rescale as _rescale
-from .readcalls import _RESCALE_KEYS
+from . import tables as T
+from .readcalls import _RESCALE_KEYS, _checked_reads, _known_options, _open_device, _pivot_sites, _read_table, _upload_rescaled
 
 
 _STOICH_KEYS = ('min_valid', 'ci_level', 'max_iter', 'tol')
+
+
+def _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale):
+    """The two masked models and K13's options of the entries that score a read-level set, with their refusals, before any device
+    work: (m0, m1, k, center, prior_logit, opts)"""
+    m0 = _rescale.masked_model(model, min_positions)
+    m1 = _rescale.masked_model(alt_model, min_positions)
+    k, center = m0['k'], m0['center']
+    if (m1['k'], m1['center']) != (k, center):
+        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
+    prior = float(prior)
+    if not 0.0 < prior < 1.0:
+        raise ValueError('prior must lie inside (0, 1)')
+    prior_logit = math.log(prior / (1.0 - prior))
+    _known_options('rescale', rescale, _RESCALE_KEYS)
+    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    return m0, m1, k, center, prior_logit, opts
+
+
+def _scorer(setup, rescale, thr, device):
+    """Open the device and upload the two models once: (det, t, score).  score(sample, want) uploads one checked sample (val, off, base),
+    rescales it against the unmodified model when `rescale` is a dict (K11) and scores it with K13: (d_off, nmod_read_llr's results
+    with the event tracks `want`, the rescale fit or None)"""
+    m0, m1, k, center, prior_logit, opts = setup
+    det, t = _open_device(device)
+    d_models = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
+
+    def score(sample, want=('llr_win',)):
+        d_val, d_off, d_base, fit = _upload_rescaled(det, t, sample, d_models[0], d_models[1], k, center, rescale)
+        calls = det.read_llr(d_val, d_off, d_base, *d_models, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr, prior_logit=prior_logit,
+                             want=want)
+        return d_off, calls, fit
+    return det, t, score
 
 
 def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None, events=False, device=0,
@@ -48,64 +82,21 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
       modified share of every position by maximum likelihood over all its window sums (K14, nmod_site_stoich) on the same stream;
       `sites` gains pi, pi_lo, pi_hi, stat, p_null (float64), iters (int32) and stoich_status (uint8, L.STOICH_* bits).
     One summary line goes to `log`."""
-    import torch
-    m0 = _rescale.masked_model(model, min_positions)
-    m1 = _rescale.masked_model(alt_model, min_positions)
-    k, center = m0['k'], m0['center']
-    if (m1['k'], m1['center']) != (k, center):
-        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
-    prior = float(prior)
-    if not 0.0 < prior < 1.0:
-        raise ValueError('prior must lie inside (0, 1)')
-    prior_logit = math.log(prior / (1.0 - prior))
-    if rescale is not None:
-        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
-        if unknown:
-            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
-    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
+    setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
+    opts = setup[-1]
     if stoich is not None:
-        unknown = sorted(set(stoich) - set(_STOICH_KEYS))
-        if unknown:
-            raise ValueError('stoich: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_STOICH_KEYS)))
+        _known_options('stoich', stoich, _STOICH_KEYS)
         engine._stoich_opts(*(stoich.get(key, default) for key, default in zip(_STOICH_KEYS, (3, 0.95, 60, 1e-12))))
-    val = np.ascontiguousarray(reads['norm_mean'])
-    if val.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('reads: norm_mean must be float32, int16 (milli-units) or float64')
-    off = np.ascontiguousarray(reads['off'], dtype=np.int64)
+    val, off, base = _checked_reads(reads, 'reads')
     nreads = len(off) - 1
-    if nreads < 0 or len(reads['start']) != nreads:
-        raise ValueError('reads: off needs nreads + 1 entries')
-    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
-    if len(base) != len(val) or (nreads and (off[0] != 0 or off[-1] != len(val))):
-        raise ValueError('reads: norm_mean and base need one entry per event of off')
-    engine._join_warm_up(device)
-    det = engine.DeviceDetector(device)
-    dev = torch.device('cuda', device)
-    t = lambda x: torch.from_numpy(x).to(dev)
-    d_val, d_off, d_base = t(val), t(off), t(base)
-    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
-    fit = None
-    if rescale is not None:
-        fit = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)
-        d_val = fit['val']
-    want = L.LLR_EVENT_FIELDS if events else ('llr_win',)
-    calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
-                         prior_logit=prior_logit, want=want)
+    det, _, score = _scorer(setup, rescale, thr, device)
+    _, calls, fit = score((val, off, base), L.LLR_EVENT_FIELDS if events else ('llr_win',))
     piv = engine.pivot_reads(reads, device, val=calls['llr_win'])
     counts = det.site_llr(piv['sig'], off=piv['off'], thr=thr)
     share = det.site_stoich(piv['sig'], off=piv['off'], **stoich) if stoich is not None else None
 
-    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
-                 start=np.asarray(reads['start'], dtype=np.int64), events=np.diff(off),
-                 **{f: calls[f].cpu().numpy() for f in L.LLR_READ_FIELDS})
-    if fit is not None:
-        table.update(shift=fit['shift'].cpu().numpy(), scale=fit['scale'].cpu().numpy(), rescale_status=fit['status'].cpu().numpy())
-    key = piv['key'].cpu().numpy()
-    names = np.array(piv['names'], dtype=str)
-    row_off = piv['off'].cpu().numpy()
-    sites = dict(chrom=names[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                 pos=key & ((1 << 40) - 1), base=piv['base'].cpu().numpy().view('S1').astype('U1'), n_reads=np.diff(row_off).astype(np.int32),
-                 **{f: counts[f].cpu().numpy() for f in L.SITE_LLR_FIELDS})
+    table = _read_table(reads, off, calls, L.LLR_READ_FIELDS, fit)
+    sites = _pivot_sites(piv, counts, L.SITE_LLR_FIELDS)
     clause = ''
     if share is not None:
         sites.update({f: share[f].cpu().numpy() for f in L.STOICH_FIELDS + ('iters',)}, stoich_status=share['status'].cpu().numpy())
@@ -114,7 +105,7 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
     log('readllr: %d read(s), %d of %d event(s) scored, %d modified and %d canonical at threshold %g over %d + 1 + %d event(s); '
         '%d position(s), %d with a modified call%s%s'
         % (nreads, int(table['n_sites'].sum()), len(val), int(table['n_mod'].sum()), int(table['n_can'].sum()), float(thr), opts.nb_lo, opts.nb_hi,
-           len(key), int((sites['n_mod'] > 0).sum()),
+           len(sites['pos']), int((sites['n_mod'] > 0).sum()),
            '' if fit is None else '; %d read(s) not rescaled' % int(((table['rescale_status'] & L.RESCALE_FAILED) != 0).sum()), clause))
     if events:
         return table, sites, {f: calls[f].cpu().numpy() for f in L.LLR_EVENT_FIELDS}
@@ -123,54 +114,89 @@ def call_reads_llr(reads, model, alt_model, *, window='kmer', thr=2.5, prior=0.5
 
 def write_read_llr(path, table):
     """<FileID>_read_llr.txt: per read 'index chrom strand start events n_sites n_mod n_can status' as '%d %s %s %d %d %d %d %d %d'"""
-    cols = [np.asarray(table['index']).tolist(), np.asarray(table['chrom']).astype(str).tolist(), np.asarray(table['strand']).astype(str).tolist()] + \
-           [np.asarray(table[f]).tolist() for f in ('start', 'events', 'n_sites', 'n_mod', 'n_can', 'status')]
-    with open(path, 'w') as f:
-        f.writelines('%d %s %s %d %d %d %d %d %d\n' % row for row in zip(*cols))
+    T.write_rows(path, '%d %s %s %d %d %d %d %d %d\n', T.read_cols(table) + T.fields(table, 'start', 'events', 'n_sites', 'n_mod', 'n_can', 'status'))
 
 
 def write_site_llr(path, sites):
     """<FileID>_site_llr.txt: per position 'chrom strand pos+1 base n_reads n_valid n_mod n_can frac' as '%s %s %d %s %d %d %d %d %.6f'
     (the position 1-based like every text output; frac 'nan' where no read is confident)"""
-    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
-            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
-           [np.asarray(sites[f]).tolist() for f in ('n_reads', 'n_valid', 'n_mod', 'n_can', 'frac')]
-    with open(path, 'w') as f:
-        f.writelines('%s %s %d %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%s %s %d %s %d %d %d %d %.6f\n',
+                 T.site_cols(sites, base=True) + T.fields(sites, 'n_reads', 'n_valid', 'n_mod', 'n_can', 'frac'))
 
 
 def write_site_stoich(path, sites):
     """<FileID>_site_stoich.txt: per position 'chrom strand pos+1 base n_reads n_valid pi pi_lo pi_hi stat p_null status' as
     '%s %s %d %s %d %d %.6f %.6f %.6f %.3f %.3E %d' (the position 1-based; 'nan' as Python spells it where the position has no
     estimate; `sites` of call_reads_llr(..., stoich=...))"""
-    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
-            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
-           [np.asarray(sites[f]).tolist() for f in ('n_reads', 'n_valid', 'pi', 'pi_lo', 'pi_hi', 'stat')] + \
-           [['%.3E' % p if p == p else 'nan' for p in np.asarray(sites['p_null']).tolist()], np.asarray(sites['stoich_status']).tolist()]
-    with open(path, 'w') as f:
-        f.writelines('%s %s %d %s %d %d %.6f %.6f %.6f %.3f %s %d\n' % row for row in zip(*cols))
+    T.write_rows(path, '%s %s %d %s %d %d %.6f %.6f %.6f %.3f %s %d\n',
+                 T.site_cols(sites, base=True) + T.fields(sites, 'n_reads', 'n_valid', 'pi', 'pi_lo', 'pi_hi', 'stat') + [T.sci(sites['p_null'])] +
+                 T.fields(sites, 'stoich_status'))
 
 
 _DIFF_KEYS = ('min_valid', 'ci_level', 'max_iter', 'tol')
 SITE_DIFF_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat', 'p_diff')
+_REP_KEYS = ('min_valid', 'ci_level', 'phi_floor', 'max_iter', 'tol')
+SITE_DIFF_REP_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond', 'p_cond', 'stat_het', 'p_het', 'phi', 'p_rep')
+
+# What follows the per-sample chain in the two comparisons: the options of `diff` and their check, the matcher of the pivots' rows, the
+# entry, the columns between `base` and the entry's float fields, the p-value track that goes to fdr, the status key and its no-estimate
+# bit, and the words of the names refusal and of the summary line.
+_TWO_SAMPLES = dict(
+    keys=_DIFF_KEYS, defaults=(3, 0.95, 60, 1e-12), check=lambda G, n_control, *v: engine._diff_opts(*v),
+    match=lambda pivots, n_control, min_coverage, device: engine.match_score_rows(pivots[0], pivots[1], min_coverage, device),
+    entry=lambda det, rows, G, n_control, diff: det.site_diff(rows['sig0'], rows['sig1'], off0=rows['off0'], off1=rows['off1'], **diff),
+    columns=lambda rows, res, G, n_control: dict(
+        n_reads0=np.diff(rows['off0'].cpu().numpy()).astype(np.int32), n_reads1=np.diff(rows['off1'].cpu().numpy()).astype(np.int32),
+        n_valid0=res['n_valid0'].cpu().numpy(), n_valid1=res['n_valid1'].cpu().numpy()),
+    fields=SITE_DIFF_FIELDS, track='p_diff', status='diff_status', no_estimate=L.DIFF_NO_ESTIMATE, whose='both samples',
+    summary=lambda nreads, n_control: 'readdiff: %d and %d read(s); %%d site(s) in both samples' % tuple(nreads))
+_REPLICATED = dict(
+    keys=_REP_KEYS, defaults=(3, 0.95, 0.0, 60, 1e-12), check=lambda G, n_control, *v: engine._rep_opts(G, n_control, *v),
+    match=lambda pivots, n_control, min_coverage, device: engine.match_score_rows_multi(pivots, n_control, min_coverage, device),
+    entry=lambda det, rows, G, n_control, diff: det.site_diff_rep(rows['sig'], rows['off'], G, n_control, **diff),
+    columns=lambda rows, res, G, n_control: dict(n_samples=G, n_control=n_control, n_valid=res['n_valid'].cpu().numpy().reshape(-1, G),
+                                                 pi_s=res['pi_s'].cpu().numpy().reshape(-1, G)),
+    fields=SITE_DIFF_REP_FIELDS, track='p_rep', status='rep_status', no_estimate=L.REP_NO_ESTIMATE, whose='all samples',
+    summary=lambda nreads, n_control: 'readdiff: %d and %d sample(s) of %s read(s); %%d site(s) in every sample'
+                                      % (n_control, len(nreads) - n_control, ', '.join(str(n) for n in nreads)))
 
 
-def _checked_reads(reads, which):
-    """the arrays of a read-level set (container.READ_FIELDS) that K13 takes, checked: val, off, base"""
-    missing = [f for f in ('chrom', 'strand', 'start', 'off', 'norm_mean', 'base') if f not in reads]
-    if missing:
-        raise ValueError('%s is not a read-level set (no %s): per-position containers have no reads' % (which, ', '.join(missing)))
-    val = np.ascontiguousarray(reads['norm_mean'])
-    if val.dtype not in (np.float32, np.int16, np.float64):
-        raise ValueError('%s: norm_mean must be float32, int16 (milli-units) or float64' % which)
-    off = np.ascontiguousarray(reads['off'], dtype=np.int64)
-    nreads = len(off) - 1
-    if nreads < 0 or len(reads['start']) != nreads:
-        raise ValueError('%s: off needs nreads + 1 entries' % which)
-    base = np.ascontiguousarray(np.asarray(reads['base']).astype('S1')).view(np.uint8)
-    if len(base) != len(val) or (nreads and (off[0] != 0 or off[-1] != len(val))):
-        raise ValueError('%s: norm_mean and base need one entry per event of off' % which)
-    return val, off, base
+def _compare(tail, reads, labels, n_control, model, alt_model, window, thr, prior, min_positions, rescale, min_coverage, diff, fdr, fdr_alpha,
+             names, device, log):
+    """compare_reads_llr and compare_reads_llr_rep: the chain of every sample of `reads` (labelled `labels` in a refusal), the first
+    n_control of them the control condition's, then the `tail` (_TWO_SAMPLES or _REPLICATED)"""
+    G = len(reads)
+    setup = _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale)
+    _known_options('diff', diff, tail['keys'])
+    tail['check'](G, n_control, *(diff.get(key, default) for key, default in zip(tail['keys'], tail['defaults'])))
+    if fdr is not None:
+        engine._fdr_method(fdr)
+    if int(min_coverage) != min_coverage or int(min_coverage) < 1:
+        raise ValueError('min_coverage must be an integer >= 1, not %r' % (min_coverage,))
+    samples = [_checked_reads(r, label) for r, label in zip(reads, labels)]
+    every = engine.chrom_names(*reads)
+    names = every if names is None else [str(n) for n in names]
+    lacking = sorted(set(every) - set(names))
+    if lacking or names != sorted(set(names)):
+        raise ValueError('names must be the sorted chromosome names of %s; missing or out of order: %s' % (tail['whose'], ', '.join(lacking) or 'order'))
+    det, _, score = _scorer(setup, rescale, thr, device)
+    pivots = [engine.pivot_reads(r, device, names=names, val=score(sample)[1]['llr_win']) for r, sample in zip(reads, samples)]
+    rows = tail['match'](pivots, n_control, int(min_coverage), device)
+    res = tail['entry'](det, rows, G, n_control, diff)
+    q = None
+    if fdr is not None:
+        (q,), _ = det.fdr(res, tracks=(tail['track'],), method=fdr, alpha=fdr_alpha)
+    sites = dict(engine.key_sites(rows['key'].cpu().numpy(), names), base=rows['base'].cpu().numpy().view('S1').astype('U1'),
+                 **tail['columns'](rows, res, G, n_control), **{f: res[f].cpu().numpy() for f in tail['fields']})
+    if q is not None:
+        sites['q'] = q.cpu().numpy()
+    status = sites[tail['status']] = res['status'].cpu().numpy()
+    est = (status & tail['no_estimate']) == 0
+    log((tail['summary']([len(s[1]) - 1 for s in samples], n_control) +
+         ' with at least %d read(s), %d with an estimate, %d with an interval of delta that excludes 0%s')
+        % (len(sites['pos']), int(min_coverage), int(est.sum()), int((est & ((sites['delta_lo'] > 0.0) | (sites['delta_hi'] < 0.0))).sum()),
+           '' if q is None else '; %d with q <= %g (%s)' % (int((sites['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
+    return sites
 
 
 def compare_reads_llr(reads0, reads1, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None,
@@ -185,89 +211,19 @@ def compare_reads_llr(reads0, reads1, model, alt_model, *, window='kmer', thr=2.
     Returns `sites`, one entry per matched site in the reference's row order: chrom, strand, pos, base, n_reads0, n_reads1, n_valid0,
     n_valid1, pi0, pi1, pi_pool, delta, delta_lo, delta_hi, stat, p_diff, [q,] diff_status (uint8, L.DIFF_* bits).  One summary line
     goes to `log`."""
-    import torch
-    m0 = _rescale.masked_model(model, min_positions)
-    m1 = _rescale.masked_model(alt_model, min_positions)
-    k, center = m0['k'], m0['center']
-    if (m1['k'], m1['center']) != (k, center):
-        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
-    prior = float(prior)
-    if not 0.0 < prior < 1.0:
-        raise ValueError('prior must lie inside (0, 1)')
-    prior_logit = math.log(prior / (1.0 - prior))
-    if rescale is not None:
-        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
-        if unknown:
-            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
-    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
-    unknown = sorted(set(diff) - set(_DIFF_KEYS))
-    if unknown:
-        raise ValueError('diff: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_DIFF_KEYS)))
-    engine._diff_opts(*(diff.get(key, default) for key, default in zip(_DIFF_KEYS, (3, 0.95, 60, 1e-12))))
-    if fdr is not None:
-        engine._fdr_method(fdr)
-    if int(min_coverage) != min_coverage or int(min_coverage) < 1:
-        raise ValueError('min_coverage must be an integer >= 1, not %r' % (min_coverage,))
-    samples = [_checked_reads(reads0, 'reads0'), _checked_reads(reads1, 'reads1')]
-    both = engine.chrom_names(reads0, reads1)
-    names = both if names is None else [str(n) for n in names]
-    lacking = sorted(set(both) - set(names))
-    if lacking or names != sorted(set(names)):
-        raise ValueError('names must be the sorted chromosome names of both samples; missing or out of order: %s' % (', '.join(lacking) or 'order'))
-    engine._join_warm_up(device)
-    det = engine.DeviceDetector(device)
-    dev = torch.device('cuda', device)
-    t = lambda x: torch.from_numpy(x).to(dev)
-    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
-    pivots = []
-    for reads, (val, off, base) in zip((reads0, reads1), samples):
-        d_val, d_off, d_base = t(val), t(off), t(base)
-        if rescale is not None:
-            d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
-        calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
-                             prior_logit=prior_logit, want=('llr_win',))
-        pivots.append(engine.pivot_reads(reads, device, names=names, val=calls['llr_win']))
-    rows = engine.match_score_rows(pivots[0], pivots[1], int(min_coverage), device)
-    res = det.site_diff(rows['sig0'], rows['sig1'], off0=rows['off0'], off1=rows['off1'], **diff)
-    q = None
-    if fdr is not None:
-        (q,), _ = det.fdr(res, tracks=('p_diff',), method=fdr, alpha=fdr_alpha)
-    key = rows['key'].cpu().numpy()
-    nm = np.array(names, dtype=str)
-    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                 pos=key & ((1 << 40) - 1), base=rows['base'].cpu().numpy().view('S1').astype('U1'),
-                 n_reads0=np.diff(rows['off0'].cpu().numpy()).astype(np.int32), n_reads1=np.diff(rows['off1'].cpu().numpy()).astype(np.int32),
-                 n_valid0=res['n_valid0'].cpu().numpy(), n_valid1=res['n_valid1'].cpu().numpy(),
-                 **{f: res[f].cpu().numpy() for f in SITE_DIFF_FIELDS})
-    if q is not None:
-        sites['q'] = q.cpu().numpy()
-    sites['diff_status'] = res['status'].cpu().numpy()
-    est = (sites['diff_status'] & L.DIFF_NO_ESTIMATE) == 0
-    log('readdiff: %d and %d read(s); %d site(s) in both samples with at least %d read(s), %d with an estimate, %d with an interval of '
-        'delta that excludes 0%s'
-        % (len(samples[0][1]) - 1, len(samples[1][1]) - 1, len(key), int(min_coverage), int(est.sum()),
-           int((est & ((sites['delta_lo'] > 0.0) | (sites['delta_hi'] < 0.0))).sum()),
-           '' if q is None else '; %d with q <= %g (%s)' % (int((sites['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
-    return sites
+    return _compare(_TWO_SAMPLES, [reads0, reads1], ['reads0', 'reads1'], 1, model, alt_model, window, thr, prior, min_positions, rescale,
+                    min_coverage, diff, fdr, fdr_alpha, names, device, log)
 
 
 def write_site_diff(path, sites):
     """<FileID>_site_diff.txt: per site 'chrom strand pos+1 base n_reads0 n_reads1 n_valid0 n_valid1 pi0 pi1 pi_pool delta delta_lo
     delta_hi stat p_diff [q] status' as '%s %s %d %s %d %d %d %d' + six '%.6f' + '%.3f %.3E [%.3E] %d' (the position 1-based; 'nan' as
     Python spells it where the site has no estimate; `sites` of compare_reads_llr)"""
-    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
-    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
-            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist()] + \
-           [np.asarray(sites[f]).tolist() for f in ('n_reads0', 'n_reads1', 'n_valid0', 'n_valid1', 'pi0', 'pi1', 'pi_pool', 'delta',
-                                                    'delta_lo', 'delta_hi', 'stat')] + \
-           [sci(sites['p_diff'])] + ([sci(sites['q'])] if 'q' in sites else []) + [np.asarray(sites['diff_status']).tolist()]
-    fmt = '%s %s %d %s %d %d %d %d %.6f %.6f %.6f %.6f %.6f %.6f %.3f %s ' + ('%s ' if 'q' in sites else '') + '%d\n'
-    with open(path, 'w') as f:
-        f.writelines(fmt % row for row in zip(*cols))
-
-
-_REP_KEYS = ('min_valid', 'ci_level', 'phi_floor', 'max_iter', 'tol')
-SITE_DIFF_REP_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond', 'p_cond', 'stat_het', 'p_het', 'phi', 'p_rep')
+    q_cols, q_fmt = T.sci_if(sites, 'q')
+    T.write_rows(path, '%s %s %d %s %d %d %d %d %.6f %.6f %.6f %.6f %.6f %.6f %.3f %s ' + q_fmt + '%d\n',
+                 T.site_cols(sites, base=True) + T.fields(sites, 'n_reads0', 'n_reads1', 'n_valid0', 'n_valid1', 'pi0', 'pi1', 'pi_pool', 'delta',
+                                                          'delta_lo', 'delta_hi', 'stat') + [T.sci(sites['p_diff'])] + q_cols +
+                 T.fields(sites, 'diff_status'))
 
 
 def compare_reads_llr_rep(reads0_list, reads1_list, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None,
@@ -281,71 +237,9 @@ def compare_reads_llr_rep(reads0_list, reads1_list, model, alt_model, *, window=
     Returns `sites`, one entry per matched site: chrom, strand, pos, base, n_samples, n_control, n_valid and pi_s (npos x G), pi0, pi1,
     pi_pool, delta, delta_lo, delta_hi, stat_cond, p_cond, stat_het, p_het, phi, p_rep, [q,] rep_status (uint8, L.REP_* bits).  One
     summary line goes to `log`."""
-    import torch
-    reads = list(reads0_list) + list(reads1_list)
-    n_control, G = len(reads0_list), len(reads)
-    m0 = _rescale.masked_model(model, min_positions)
-    m1 = _rescale.masked_model(alt_model, min_positions)
-    k, center = m0['k'], m0['center']
-    if (m1['k'], m1['center']) != (k, center):
-        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
-    prior = float(prior)
-    if not 0.0 < prior < 1.0:
-        raise ValueError('prior must lie inside (0, 1)')
-    prior_logit = math.log(prior / (1.0 - prior))
-    if rescale is not None:
-        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
-        if unknown:
-            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
-    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
-    unknown = sorted(set(diff) - set(_REP_KEYS))
-    if unknown:
-        raise ValueError('diff: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_REP_KEYS)))
-    engine._rep_opts(G, n_control, *(diff.get(key, default) for key, default in zip(_REP_KEYS, (3, 0.95, 0.0, 60, 1e-12))))
-    if fdr is not None:
-        engine._fdr_method(fdr)
-    if int(min_coverage) != min_coverage or int(min_coverage) < 1:
-        raise ValueError('min_coverage must be an integer >= 1, not %r' % (min_coverage,))
-    samples = [_checked_reads(r, 'reads%d[%d]' % (g >= n_control, g - n_control if g >= n_control else g)) for g, r in enumerate(reads)]
-    every = engine.chrom_names(*reads)
-    names = every if names is None else [str(n) for n in names]
-    lacking = sorted(set(every) - set(names))
-    if lacking or names != sorted(set(names)):
-        raise ValueError('names must be the sorted chromosome names of all samples; missing or out of order: %s' % (', '.join(lacking) or 'order'))
-    engine._join_warm_up(device)
-    det = engine.DeviceDetector(device)
-    dev = torch.device('cuda', device)
-    t = lambda x: torch.from_numpy(x).to(dev)
-    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
-    pivots = []
-    for rd, (val, off, base) in zip(reads, samples):
-        d_val, d_off, d_base = t(val), t(off), t(base)
-        if rescale is not None:
-            d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
-        calls = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
-                             prior_logit=prior_logit, want=('llr_win',))
-        pivots.append(engine.pivot_reads(rd, device, names=names, val=calls['llr_win']))
-    rows = engine.match_score_rows_multi(pivots, n_control, int(min_coverage), device)
-    res = det.site_diff_rep(rows['sig'], rows['off'], G, n_control, **diff)
-    q = None
-    if fdr is not None:
-        (q,), _ = det.fdr(res, tracks=('p_rep',), method=fdr, alpha=fdr_alpha)
-    key = rows['key'].cpu().numpy()
-    nm = np.array(names, dtype=str)
-    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                 pos=key & ((1 << 40) - 1), base=rows['base'].cpu().numpy().view('S1').astype('U1'), n_samples=G, n_control=n_control,
-                 n_valid=res['n_valid'].cpu().numpy().reshape(-1, G), pi_s=res['pi_s'].cpu().numpy().reshape(-1, G),
-                 **{f: res[f].cpu().numpy() for f in SITE_DIFF_REP_FIELDS})
-    if q is not None:
-        sites['q'] = q.cpu().numpy()
-    sites['rep_status'] = res['status'].cpu().numpy()
-    est = (sites['rep_status'] & L.REP_NO_ESTIMATE) == 0
-    log('readdiff: %d and %d sample(s) of %s read(s); %d site(s) in every sample with at least %d read(s), %d with an estimate, %d with an '
-        'interval of delta that excludes 0%s'
-        % (n_control, G - n_control, ', '.join(str(len(s[1]) - 1) for s in samples), len(key), int(min_coverage), int(est.sum()),
-           int((est & ((sites['delta_lo'] > 0.0) | (sites['delta_hi'] < 0.0))).sum()),
-           '' if q is None else '; %d with q <= %g (%s)' % (int((sites['q'] <= fdr_alpha).sum()), fdr_alpha, fdr)))
-    return sites
+    n0, n1 = len(reads0_list), len(reads1_list)
+    return _compare(_REPLICATED, list(reads0_list) + list(reads1_list), ['reads0[%d]' % i for i in range(n0)] + ['reads1[%d]' % i for i in range(n1)],
+                    n0, model, alt_model, window, thr, prior, min_positions, rescale, min_coverage, diff, fdr, fdr_alpha, names, device, log)
 
 
 def write_site_diff_rep(path, sites):
@@ -353,20 +247,15 @@ def write_site_diff_rep(path, sites):
     'pi0 pi1 pi_pool delta delta_lo delta_hi stat_cond p_cond stat_het p_het phi p_rep [q] status' as six '%.6f' + '%.3f %.3E %.3f
     %.3E %.3f %.3E [%.3E] %d' (write_site_diff's formats: the position 1-based; 'nan' as Python spells it where the site has no
     estimate; `sites` of compare_reads_llr_rep)"""
-    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
     G = int(sites['n_samples'])
     nv, ps = np.asarray(sites['n_valid']).reshape(-1, G), np.asarray(sites['pi_s']).reshape(-1, G)
-    per = []
-    for g in range(G):
-        per += [nv[:, g].tolist(), ps[:, g].tolist()]
-    cols = [np.asarray(sites['chrom']).astype(str).tolist(), np.asarray(sites['strand']).astype(str).tolist(),
-            (np.asarray(sites['pos'], dtype=np.int64) + 1).tolist(), np.asarray(sites['base']).astype(str).tolist(), [G] * len(nv)] + per + \
-           [np.asarray(sites[f]).tolist() for f in ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond')] + \
-           [sci(sites['p_cond']), np.asarray(sites['stat_het']).tolist(), sci(sites['p_het']), np.asarray(sites['phi']).tolist(), sci(sites['p_rep'])] + \
-           ([sci(sites['q'])] if 'q' in sites else []) + [np.asarray(sites['rep_status']).tolist()]
-    fmt = '%s %s %d %s %d ' + '%d %.6f ' * G + '%.6f %.6f %.6f %.6f %.6f %.6f %.3f %s %.3f %s %.3f %s ' + ('%s ' if 'q' in sites else '') + '%d\n'
-    with open(path, 'w') as f:
-        f.writelines(fmt % row for row in zip(*cols))
+    per = [col.tolist() for g in range(G) for col in (nv[:, g], ps[:, g])]
+    q_cols, q_fmt = T.sci_if(sites, 'q')
+    T.write_rows(path, '%s %s %d %s %d ' + '%d %.6f ' * G + '%.6f %.6f %.6f %.6f %.6f %.6f %.3f %s %.3f %s %.3f %s ' + q_fmt + '%d\n',
+                 T.site_cols(sites, base=True) + [[G] * len(nv)] + per +
+                 T.fields(sites, 'pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond') +
+                 [T.sci(sites['p_cond'])] + T.fields(sites, 'stat_het') + [T.sci(sites['p_het'])] + T.fields(sites, 'phi') + [T.sci(sites['p_rep'])] +
+                 q_cols + T.fields(sites, 'rep_status'))
 
 
 _PAIR_STAT_FIELDS = ('log_or', 'se', 'phi', 'p_fisher')
@@ -403,26 +292,6 @@ def site_keys(sites, names):
     return np.unique((cs << 40) | pos[known])
 
 
-def _llr_setup(model, alt_model, window, thr, prior, min_positions, rescale):
-    """The two masked models and K13's options of the entries that score a read-level set and then keep the read (cooccur_reads_llr,
-    smooth_reads_llr), with their refusals, before any device work: (m0, m1, k, center, prior_logit, opts)"""
-    m0 = _rescale.masked_model(model, min_positions)
-    m1 = _rescale.masked_model(alt_model, min_positions)
-    k, center = m0['k'], m0['center']
-    if (m1['k'], m1['center']) != (k, center):
-        raise ValueError('the two models must share k and center: %d / %d and %d / %d' % (k, center, m1['k'], m1['center']))
-    prior = float(prior)
-    if not 0.0 < prior < 1.0:
-        raise ValueError('prior must lie inside (0, 1)')
-    prior_logit = math.log(prior / (1.0 - prior))
-    if rescale is not None:
-        unknown = sorted(set(rescale) - set(_RESCALE_KEYS))
-        if unknown:
-            raise ValueError('rescale: unknown option(s) %s; known: %s' % (', '.join(unknown), ', '.join(_RESCALE_KEYS)))
-    opts, _ = engine._llr_opts(window, thr, prior_logit, k, center, k, center, ())           # the refusals, before any device work
-    return m0, m1, k, center, prior_logit, opts
-
-
 def _sites_by_stoich(sites):
     by_stoich = isinstance(sites, str)
     if by_stoich and sites != 'stoich':
@@ -436,24 +305,17 @@ def _site_scores(reads, setup, sites, site_alpha, rescale, thr, device, want_sha
     Returns a dict: det, names, nreads, the CUDA vectors d_cs, d_start, d_off, llr_win and d_key, and with want_share site_pi: K14's
     estimates at the candidate sites that have one (a CUDA vector)."""
     import torch
-    m0, m1, k, center, prior_logit, opts = setup
     by_stoich = _sites_by_stoich(sites)
-    val, off, base = _checked_reads(reads, 'reads')
-    nreads = len(off) - 1
+    sample = _checked_reads(reads, 'reads')
+    nreads = len(sample[1]) - 1
     names = engine.chrom_names(reads)
     cs = engine.chrom_strand_ids(np.asarray(reads['chrom']).astype(str), np.asarray(reads['strand']).astype(str), names)
     start = np.ascontiguousarray(reads['start'], dtype=np.int64)
     host_key = None if by_stoich else site_keys(sites, names)
-    engine._join_warm_up(device)
-    det = engine.DeviceDetector(device)
-    dev = torch.device('cuda', device)
-    t = lambda x: torch.from_numpy(x).to(dev)
-    d_val, d_off, d_base = t(val), t(off), t(base)
-    d_mean0, d_sd0, d_mean1, d_sd1 = t(m0['mean']), t(m0['sd']), t(m1['mean']), t(m1['sd'])
-    if rescale is not None:
-        d_val = det.rescale_reads(d_val, d_off, d_base, d_mean0, d_sd0, k, center, mode='fit_apply', **rescale)['val']
-    llr_win = det.read_llr(d_val, d_off, d_base, d_mean0, d_sd0, d_mean1, d_sd1, k, center, window=(opts.nb_lo, opts.nb_hi), thr=thr,
-                           prior_logit=prior_logit, want=('llr_win',))['llr_win']
+    det, t, score = _scorer(setup, rescale, thr, device)
+    d_off, calls, _ = score(sample)
+    llr_win = calls['llr_win']
+    dev = llr_win.device
     site_pi = None
     if by_stoich or want_share:
         piv = engine.pivot_reads(reads, device, names=names, val=llr_win)
@@ -528,11 +390,9 @@ def cooccur_reads_llr(reads, model, alt_model, *, sites='stoich', max_dist=100, 
     key = d_key.cpu().numpy()
     first, second = res['first'].cpu().numpy().astype(np.int64), res['second'].cpu().numpy().astype(np.int64)
     counts = res['counts'].cpu().numpy().reshape(-1, 4)
-    nm = np.array(names, dtype=str)
-    ka, kb = key[first], key[second]
-    pos_a, pos_b = ka & ((1 << 40) - 1), kb & ((1 << 40) - 1)
-    pairs = dict(chrom=nm[ka >> 41] if len(ka) else np.zeros(0, dtype=str), strand=np.where((ka >> 40) & 1, '-', '+').astype('U1'),
-                 pos_a=pos_a, pos_b=pos_b, dist=pos_b - pos_a, n11=counts[:, 3].copy(), n10=counts[:, 2].copy(), n01=counts[:, 1].copy(),
+    a, b = engine.key_sites(key[first], names), engine.key_sites(key[second], names)
+    pairs = dict(chrom=a['chrom'], strand=a['strand'], pos_a=a['pos'], pos_b=b['pos'], dist=b['pos'] - a['pos'],
+                 n11=counts[:, 3].copy(), n10=counts[:, 2].copy(), n01=counts[:, 1].copy(),
                  n00=counts[:, 0].copy(), **{f: res[f].cpu().numpy() for f in _PAIR_STAT_FIELDS})
     if q is not None:
         pairs['q'] = q.cpu().numpy()
@@ -560,28 +420,21 @@ def write_site_pairs(path, pairs):
     """<FileID>_site_pairs.txt: per pair 'chrom strand pos_a+1 pos_b+1 dist n11 n10 n01 n00 log_or se phi p_fisher [q] status' as
     '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %.3E [%.3E] %d' (the positions 1-based; 'nan' as Python spells it where the pair has no
     value; `pairs` of cooccur_reads_llr)"""
-    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
-    cols = [np.asarray(pairs['chrom']).astype(str).tolist(), np.asarray(pairs['strand']).astype(str).tolist(),
-            (np.asarray(pairs['pos_a'], dtype=np.int64) + 1).tolist(), (np.asarray(pairs['pos_b'], dtype=np.int64) + 1).tolist()] + \
-           [np.asarray(pairs[f]).tolist() for f in ('dist', 'n11', 'n10', 'n01', 'n00', 'log_or', 'se', 'phi')] + \
-           [sci(pairs['p_fisher'])] + ([sci(pairs['q'])] if 'q' in pairs else []) + [np.asarray(pairs['status']).tolist()]
-    fmt = '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %s ' + ('%s ' if 'q' in pairs else '') + '%d\n'
-    with open(path, 'w') as f:
-        f.writelines(fmt % row for row in zip(*cols))
+    q_cols, q_fmt = T.sci_if(pairs, 'q')
+    T.write_rows(path, '%s %s %d %d %d %d %d %d %d %.6f %.6f %.6f %s ' + q_fmt + '%d\n',
+                 T.site_cols(pairs, pos=('pos_a', 'pos_b')) + T.fields(pairs, 'dist', 'n11', 'n10', 'n01', 'n00', 'log_or', 'se', 'phi') +
+                 [T.sci(pairs['p_fisher'])] + q_cols + T.fields(pairs, 'status'))
 
 
 def write_site_linkage(path, pairs):
     """<FileID>_site_linkage.txt: per pair 'chrom strand pos_a+1 pos_b+1 dist n_cov pa pb d d_lo d_hi r pi11 pi10 pi01 pi00 stat p_indep
     [q_indep] link_status' as '%s %s %d %d %d %d' + ten '%.6f' + '%.3f %.3E [%.3E] %d' (the positions 1-based; 'nan' as Python spells it
     where the pair has no estimate; `pairs` of cooccur_reads_llr(..., soft=True))"""
-    sci = lambda a: ['%.3E' % p if p == p else 'nan' for p in np.asarray(a).tolist()]
-    cols = [np.asarray(pairs['chrom']).astype(str).tolist(), np.asarray(pairs['strand']).astype(str).tolist(),
-            (np.asarray(pairs['pos_a'], dtype=np.int64) + 1).tolist(), (np.asarray(pairs['pos_b'], dtype=np.int64) + 1).tolist()] + \
-           [np.asarray(pairs[f]).tolist() for f in ('dist', 'n_cov', 'pa', 'pb', 'd', 'd_lo', 'd_hi', 'r', 'pi11', 'pi10', 'pi01', 'pi00', 'stat')] + \
-           [sci(pairs['p_indep'])] + ([sci(pairs['q_indep'])] if 'q_indep' in pairs else []) + [np.asarray(pairs['link_status']).tolist()]
-    fmt = '%s %s %d %d %d %d' + ' %.6f' * 10 + ' %.3f %s ' + ('%s ' if 'q_indep' in pairs else '') + '%d\n'
-    with open(path, 'w') as f:
-        f.writelines(fmt % row for row in zip(*cols))
+    q_cols, q_fmt = T.sci_if(pairs, 'q_indep')
+    T.write_rows(path, '%s %s %d %d %d %d' + ' %.6f' * 10 + ' %.3f %s ' + q_fmt + '%d\n',
+                 T.site_cols(pairs, pos=('pos_a', 'pos_b')) +
+                 T.fields(pairs, 'dist', 'n_cov', 'pa', 'pb', 'd', 'd_lo', 'd_hi', 'r', 'pi11', 'pi10', 'pi01', 'pi00', 'stat') +
+                 [T.sci(pairs['p_indep'])] + q_cols + T.fields(pairs, 'link_status'))
 
 
 def read_domains(hoff, site, state, post, site_pos, delta=None):
@@ -715,27 +568,23 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
             % (pi, fitted['pi_lo'], fitted['pi_hi'], length, fitted['length_lo'], fitted['length_hi'], fitted['ll'], fitted['n_eval'],
                'converged' if fitted['converged'] else 'not converged', fitted['status']))
     key = d_key.cpu().numpy()
-    nm = np.array(names, dtype=str)
     if prior_out is not None:
-        prior_out.update(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                         pos=key & ((1 << 40) - 1))
+        prior_out.update(engine.key_sites(key, names))
     vit = None
     if decode != 'posterior':
         vit = {f: v.cpu().numpy() for f, v in det.read_viterbi(*shared, hoff, nrows, pi=pi, length=length, **prior_kw).items()}
     if decode == 'viterbi':
         out = dict(pi=pi, length=length, profile=profile, **({} if fitted is None else {'fit': fitted}),
                    **({} if prior_out is None else {'site_prior': prior_out}))
-        out['viterbi'] = _viterbi_result(vit, hoff.cpu().numpy(), key, nm, reads, nreads, None, None, pi, length, log)
+        out['viterbi'] = _viterbi_result(vit, hoff.cpu().numpy(), key, names, reads, nreads, None, None, pi, length, log)
         return out
     res = det.read_hmm(*shared, hoff, nrows, pi=pi, length=length, call_post=call_post, **prior_kw)
     res = {f: v.cpu().numpy() for f, v in res.items()}
     called = (res['site_mod'] + res['site_can']).astype(np.float64)
     with np.errstate(invalid='ignore', divide='ignore'):
         share = np.where(called > 0, res['site_mod'] / called, np.nan)
-    out_sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                     pos=key & ((1 << 40) - 1), n=res['site_n'], n_mod=res['site_mod'], n_can=res['site_can'], share=share)
-    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
-                 **{f: res[f] for f in L.HMM_READ_FIELDS})
+    out_sites = dict(engine.key_sites(key, names), n=res['site_n'], n_mod=res['site_mod'], n_can=res['site_can'], share=share)
+    table = dict(engine.read_head(reads, nreads), **{f: res[f] for f in L.HMM_READ_FIELDS})
     entries = dict(hoff=hoff.cpu().numpy(), site=res['site'], post=res['post'], state=res['state'])
     domains = read_domains(entries['hoff'], entries['site'], entries['state'], entries['post'], out_sites['pos'])
     log('readhmm: %d read(s), %d candidate site(s), %d entr%s; pi %.6g, length %g%s; %d modified and %d canonical at posterior %g, %d domain(s) on %d read(s)'
@@ -747,7 +596,7 @@ def smooth_reads_llr(reads, model, alt_model, *, sites='stoich', pi=None, length
     if prior_out is not None:
         out['site_prior'] = prior_out
     if vit is not None:
-        out['viterbi'] = _viterbi_result(vit, entries['hoff'], key, nm, reads, nreads, res['ll'], res['post'], pi, length, log)
+        out['viterbi'] = _viterbi_result(vit, entries['hoff'], key, names, reads, nreads, res['ll'], res['post'], pi, length, log)
     return out
 
 
@@ -880,14 +729,12 @@ def write_hmm_fit(path, fit):
         f.write('status %s\n' % fit['status'])
 
 
-def _viterbi_result(vit, hoff, key, nm, reads, nreads, ll, post, pi, length, log):
+def _viterbi_result(vit, hoff, key, names, reads, nreads, ll, post, pi, length, log):
     """smooth_reads_llr's `viterbi` entry from nmod_read_viterbi's outputs (ll, post: nmod_read_hmm's, or None)"""
     with np.errstate(invalid='ignore', divide='ignore'):
         share = np.where(vit['site_n'] > 0, vit['site_mod'] / vit['site_n'].astype(np.float64), np.nan)
-    sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                 pos=key & ((1 << 40) - 1), n=vit['site_n'], n_mod=vit['site_mod'], share=share)
-    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
-                 **{f: vit[f] for f in L.VIT_READ_FIELDS})
+    sites = dict(engine.key_sites(key, names), n=vit['site_n'], n_mod=vit['site_mod'], share=share)
+    table = dict(engine.read_head(reads, nreads), **{f: vit[f] for f in L.VIT_READ_FIELDS})
     if ll is not None:
         table['path_logpost'] = vit['vit'] - ll
     entries = dict(hoff=hoff, site=vit['site'], path=vit['path'], delta=vit['delta'])
@@ -903,10 +750,8 @@ def write_read_hmm(path, res):
     '%d %s %s %d %d %d %d %.6f %.6f %.6f' (`res` of smooth_reads_llr)"""
     t = res['reads']
     ll, ind = np.asarray(t['ll'], np.float64), np.asarray(t['ll_indep'], np.float64)
-    cols = [np.asarray(t['index']).tolist(), np.asarray(t['chrom']).astype(str).tolist(), np.asarray(t['strand']).astype(str).tolist()] + \
-           [np.asarray(t[f]).tolist() for f in ('n_sites', 'n_mod', 'n_can', 'n_runs')] + [ll.tolist(), ind.tolist(), (2.0 * (ll - ind)).tolist()]
-    with open(path, 'w') as f:
-        f.writelines('%d %s %s %d %d %d %d %.6f %.6f %.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%d %s %s %d %d %d %d %.6f %.6f %.6f\n',
+                 T.read_cols(t) + T.fields(t, 'n_sites', 'n_mod', 'n_can', 'n_runs') + [ll.tolist(), ind.tolist(), (2.0 * (ll - ind)).tolist()])
 
 
 def write_read_domains(path, res):
@@ -916,24 +761,17 @@ def write_read_domains(path, res):
     posteriors)"""
     d, t = res['domains'], res['reads']
     read = np.asarray(d['read'], np.int64)
-    cols = [read.tolist(), np.asarray(t['chrom']).astype(str)[read].tolist(), np.asarray(t['strand']).astype(str)[read].tolist(),
-            (np.asarray(d['first'], np.int64) + 1).tolist(), (np.asarray(d['last'], np.int64) + 1).tolist(), np.asarray(d['n_sites']).tolist(),
-            np.asarray(d['mean_post']).tolist()]
-    if 'min_delta' in d:
-        cols.append(np.asarray(d['min_delta']).tolist())
-    fmt = '%d %s %s %d %d %d %.6f' + (' %.6f' if 'min_delta' in d else '') + '\n'
-    with open(path, 'w') as f:
-        f.writelines(fmt % row for row in zip(*cols))
+    more = ('min_delta',) if 'min_delta' in d else ()
+    T.write_rows(path, '%d %s %s %d %d %d %.6f' + ' %.6f' * len(more) + '\n',
+                 [read.tolist(), T.strs(np.asarray(t['chrom'])[read]), T.strs(np.asarray(t['strand'])[read]), T.pos1(d['first']), T.pos1(d['last'])] +
+                 T.fields(d, 'n_sites', 'mean_post', *more))
 
 
 def write_site_hmm(path, res):
     """<FileID>_site_hmm.txt: per candidate site 'chrom strand pos+1 n n_mod n_can share' as '%s %s %d %d %d %d %.6f' (the position
     1-based; share 'nan' where no entry is called; `res` of smooth_reads_llr)"""
     s = res['sites']
-    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()] + \
-           [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'n_can', 'share')]
-    with open(path, 'w') as f:
-        f.writelines('%s %s %d %d %d %d %.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%s %s %d %d %d %d %.6f\n', T.site_cols(s) + T.fields(s, 'n', 'n_mod', 'n_can', 'share'))
 
 
 def write_read_viterbi(path, res):
@@ -942,30 +780,23 @@ def write_read_viterbi(path, res):
     e, s = res['entries'], res['sites']
     hoff, site = np.asarray(e['hoff'], np.int64), np.asarray(e['site'], np.int64)
     read = np.searchsorted(hoff, np.arange(len(site)), 'right') - 1
-    cols = [read.tolist(), site.tolist(), np.asarray(s['chrom']).astype(str)[site].tolist(), np.asarray(s['strand']).astype(str)[site].tolist(),
-            (np.asarray(s['pos'], np.int64)[site] + 1).tolist(), np.asarray(e['path']).tolist(), np.asarray(e['delta'], np.float64).tolist()]
-    with open(path, 'w') as f:
-        f.writelines('%d %d %s %s %d %d %.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%d %d %s %s %d %d %.6f\n',
+                 [read.tolist(), site.tolist(), T.strs(np.asarray(s['chrom'])[site]), T.strs(np.asarray(s['strand'])[site]),
+                  T.pos1(np.asarray(s['pos'])[site])] + T.fields(e, 'path', 'delta'))
 
 
 def write_site_prior(path, res):
     """<FileID>_site_prior.txt: per candidate site 'chrom strand pos+1 n_valid pi_hat prior' as '%s %s %d %d %.9g %.9g' (the position
     1-based; 'nan' twice at a site without an estimate; `res`: smooth_reads_llr's result with site_prior)"""
     s = res['site_prior']
-    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist(),
-            np.asarray(s['n_valid'], np.int64).tolist(), np.asarray(s['pi_hat'], np.float64).tolist(), np.asarray(s['prior'], np.float64).tolist()]
-    with open(path, 'w') as f:
-        f.writelines('%s %s %d %d %.9g %.9g\n' % row for row in zip(*cols))
+    T.write_rows(path, '%s %s %d %d %.9g %.9g\n', T.site_cols(s) + T.fields(s, 'n_valid', 'pi_hat', 'prior'))
 
 
 def write_site_viterbi(path, res):
     """<FileID>_site_viterbi.txt: per candidate site 'chrom strand pos+1 n n_mod share' as '%s %s %d %d %d %.6f' (the position 1-based;
     share 'nan' where no read has an entry; `res`: the `viterbi` entry of smooth_reads_llr)"""
     s = res['sites']
-    cols = [np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()] + \
-           [np.asarray(s[f]).tolist() for f in ('n', 'n_mod', 'share')]
-    with open(path, 'w') as f:
-        f.writelines('%s %s %d %d %d %.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%s %s %d %d %d %.6f\n', T.site_cols(s) + T.fields(s, 'n', 'n_mod', 'share'))
 
 
 # ---------------------------------------------------------------------------------------------------------------- K22: classes of reads
@@ -1127,15 +958,11 @@ def cluster_reads_llr(reads, model, alt_model, *, sites='stoich', classes=2, n_i
     gamma = fin['gamma'].cpu().numpy().reshape(nreads, C_)[:, order]
     cls = fin['cls'].cpu().numpy()
     cls = np.where(cls >= 0, rank[np.maximum(cls, 0)], -1).astype(np.int32)
-    key = d_key.cpu().numpy()
-    nm = np.array(names, dtype=str)
     n_sites = np.diff(hoff.cpu().numpy()).astype(np.int32)
-    table = dict(index=np.arange(nreads, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
-                 n_sites=n_sites, cls=cls, gamma=np.where(cls >= 0, gamma[np.arange(nreads), np.maximum(cls, 0)], 0.0) if nreads else np.zeros(0),
-                 gamma_all=gamma, ll=fin['ll'].cpu().numpy(), status=fin['status'].cpu().numpy())
+    table = dict(engine.read_head(reads, nreads), n_sites=n_sites, cls=cls,
+                 gamma=np.where(cls >= 0, gamma[np.arange(nreads), np.maximum(cls, 0)], 0.0) if nreads else np.zeros(0), gamma_all=gamma, ll=fin['ll'].cpu().numpy(), status=fin['status'].cpu().numpy())
     theta = chosen['theta'].cpu().numpy().reshape(nsites, C_)[:, order]
-    out_sites = dict(chrom=nm[key >> 41] if len(key) else np.zeros(0, dtype=str), strand=np.where((key >> 40) & 1, '-', '+').astype('U1'),
-                     pos=key & ((1 << 40) - 1), theta=theta, n=fin['n_site'].cpu().numpy().reshape(nsites, C_)[:, order])
+    out_sites = dict(engine.key_sites(d_key.cpu().numpy(), names), theta=theta, n=fin['n_site'].cpu().numpy().reshape(nsites, C_)[:, order])
     w = chosen['w'].cpu().numpy()[order]
     log('readclasses: %d read(s), %d with an entry, %d candidate site(s), %d entr%s; %d class(es) kept%s, weights %s'
         % (nreads, int(chosen['sums'][1]), nsites, nrows, 'y' if nrows == 1 else 'ies', C_,
@@ -1147,12 +974,8 @@ def write_read_classes(path, res):
     """<FileID>_read_classes.txt: a header line, then per read 'read chrom strand n_sites class gamma ll', tab-separated, as
     '%d %s %s %d %d %.6f %.6f' (class -1 and gamma 0 for a read without an entry; `res` of cluster_reads_llr)"""
     t = res['reads']
-    cols = [np.asarray(t['index']).tolist(), np.asarray(t['chrom']).astype(str).tolist(), np.asarray(t['strand']).astype(str).tolist(),
-            np.asarray(t['n_sites']).tolist(), np.asarray(t['cls']).tolist(), np.asarray(t['gamma'], np.float64).tolist(),
-            np.asarray(t['ll'], np.float64).tolist()]
-    with open(path, 'w') as f:
-        f.write('read\tchrom\tstrand\tn_sites\tclass\tgamma\tll\n')
-        f.writelines('%d\t%s\t%s\t%d\t%d\t%.6f\t%.6f\n' % row for row in zip(*cols))
+    T.write_rows(path, '%d\t%s\t%s\t%d\t%d\t%.6f\t%.6f\n', T.read_cols(t) + T.fields(t, 'n_sites', 'cls', 'gamma', 'll'),
+                 header='read\tchrom\tstrand\tn_sites\tclass\tgamma\tll\n')
 
 
 def write_class_sites(path, res):
@@ -1161,11 +984,9 @@ def write_class_sites(path, res):
     s = res['sites']
     theta, n = np.asarray(s['theta'], np.float64), np.asarray(s['n'], np.float64)
     nc = theta.shape[1] if theta.ndim == 2 else int(res['C'])
-    chrom, strand, pos = np.asarray(s['chrom']).astype(str).tolist(), np.asarray(s['strand']).astype(str).tolist(), (np.asarray(s['pos'], np.int64) + 1).tolist()
-    with open(path, 'w') as f:
-        f.write('chrom\tstrand\tpos' + ''.join('\ttheta_%d\tN_%d' % (c, c) for c in range(nc)) + '\n')
-        for j in range(len(pos)):
-            f.write('%s\t%s\t%d' % (chrom[j], strand[j], pos[j]) + ''.join('\t%.6f\t%.3f' % (theta[j, c], n[j, c]) for c in range(nc)) + '\n')
+    per = [col.tolist() for c in range(nc) for col in (theta[:, c], n[:, c])] if len(theta) else []
+    T.write_rows(path, '%s\t%s\t%d' + '\t%.6f\t%.3f' * nc + '\n', T.site_cols(s) + per,
+                 header='chrom\tstrand\tpos' + ''.join('\ttheta_%d\tN_%d' % (c, c) for c in range(nc)) + '\n')
 
 
 def write_classes_fit(path, res):

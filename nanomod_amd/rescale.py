@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib as L
 from . import engine
+from . import tables as T
 
 _REASONS = ((L.RESCALE_TOO_FEW, 'too few events'), (L.RESCALE_DEGENERATE, 'degenerate'), (L.RESCALE_OUT_OF_RANGE, 'scale out of range'),
             (L.RESCALE_TOO_LARGE, 'beyond %d events' % L.MAX_DEEP))
@@ -59,9 +60,8 @@ def rescale_reads(reads, model, *, weighted=True, clip_sigma=3.0, clip_rounds=2,
                                     device=device)
     st = res['status']
     n = len(st)
-    table = dict(index=np.arange(n, dtype=np.int64), chrom=np.asarray(reads['chrom']).astype(str), strand=np.asarray(reads['strand']).astype(str),
-                 start=np.asarray(reads['start'], dtype=np.int64), events=np.diff(np.asarray(reads['off'], dtype=np.int64)),
-                 n_used=res['n_used'], shift=res['shift'], scale=res['scale'], status=st)
+    table = dict(engine.read_head(reads, n, np.asarray(reads['off'], dtype=np.int64)), n_used=res['n_used'], shift=res['shift'], scale=res['scale'],
+                 status=st)
     out = dict(reads)
     out['norm_mean'] = res['val']
     failed = (st & L.RESCALE_FAILED) != 0
@@ -79,7 +79,5 @@ def write_read_scale(path, reads, table):
     '%d %s %s %d %d %d %.6f %.6f %d'.  chrom / strand / start come from `reads` when it holds the table's reads (nothing was dropped),
     else from the table itself."""
     src = reads if reads is not None and len(reads['start']) == len(table['index']) else table
-    cols = [np.asarray(table['index']).tolist(), np.asarray(src['chrom']).astype(str).tolist(), np.asarray(src['strand']).astype(str).tolist(),
-            np.asarray(src['start']).tolist()] + [np.asarray(table[f]).tolist() for f in ('events', 'n_used', 'shift', 'scale', 'status')]
-    with open(path, 'w') as f:
-        f.writelines('%d %s %s %d %d %d %.6f %.6f %d\n' % row for row in zip(*cols))
+    T.write_rows(path, '%d %s %s %d %d %d %.6f %.6f %d\n', T.fields(table, 'index') + [T.strs(src['chrom']), T.strs(src['strand'])] +
+                 T.fields(src, 'start') + T.fields(table, 'events', 'n_used', 'shift', 'scale', 'status'))
