@@ -971,6 +971,77 @@ typedef struct nmod_rep_out { int32_t struct_size; int32_t reserved;
 int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score, const int64_t* off,
                        const nmod_rep_opts* opts, const nmod_rep_out* out);
 
+/* The dispersions of nmod_site_diff_rep shrunk across sites: an empirical-Bayes prior law of phi fitted over all sites of a call
+ * (nmod_rep_prior), and nmod_site_diff_rep with every site's phi replaced by its posterior value under that law and its test taken on
+ * the degrees of freedom the prior adds (nmod_site_diff_rep_mod) (K25; the reference project has no such step).  limma's, DSS's and
+ * edgeR's step: with 2 or 4 degrees of freedom per site the denominator of F is mostly noise, and all sites together say how much.
+ *
+ * nmod_rep_prior.  Inputs: df = G - 2 in 1 .. NMOD_REP_MAX_SAMPLES - 2; phi[npos] (double) and status[npos] (uint8) as
+ *   nmod_site_diff_rep wrote them; ci_level strictly inside (0, 1).  Output: the RECORD prior[NMOD_REP_PRIOR_WORDS], 8 doubles.  All
+ *   arrays in the memspace of prm.
+ *   A site ENTERS THE FIT iff its status has none of NMOD_REP_TOO_FEW, FLAT, TOO_LARGE and phi is finite and phi > 0; n of them.  A
+ *   site with none of these bits and phi <= 0 is a ZERO (nmod_site_diff_rep clamps stat_het at 0: such sites exist); a NaN phi is
+ *   neither.
+ *   The fit is limma's fitFDist at equal degrees of freedom (phi ~ s0^2 F(df, d0); psi, psi' the di- and trigamma functions):
+ *     e_i = ln phi_i - psi(df / 2) + ln(df / 2)          (in this order: two roundings after the logarithm)
+ *     emean = sum e_i / n
+ *     evar = sum (e_i - emean)^2 / (n - 1) - psi'(df / 2)        (the centred squares in a second pass over phi)
+ *     evar > 0:   d0 = 2 psi'^-1(evar),   s0^2 = exp(emean + psi(d0 / 2) - ln(d0 / 2))
+ *     evar <= 0:  d0 = +inf,              s0^2 = exp(emean)      (the sites differ no more than chi2_df alone makes them)
+ *     n < 2:      d0 = 0 ("no prior"),    s0^2 = NaN, evar = NaN (emean: the one e, or NaN)
+ *   psi'^-1 is a Newton iteration on 1 / psi' from 1/2 + 1/x; it stops after the first step of relative size below 1e-8 (what is
+ *   left is of the order of its square) or after 50 steps; x > 1e7: 1 / sqrt(x), x < 1e-6: 1 / x.
+ *   The record, in this order:  d0;  s0^2;  df_tot = df + d0;  ci_drop, the ci_level quantile of F(1, df_tot), found by bisecting the
+ *   two-sided Student t tail for real df_tot down to neighbouring doubles (df_tot = +inf: norm_isf((1 - ci_level) / 2)^2, the chi2_1
+ *   quantile; d0 = 0: the F(1, df) quantile);  n (n_used);  the number of zeros (n_zero);  emean;  evar.
+ *   Sums.  A CHUNK is NMOD_REP_PRIOR_CHUNK consecutive sites.  A workgroup of 256 threads sums a chunk: thread t its sites t, t + 256,
+ *   ... in ascending order, the threads joined by the wave and workgroup sums; one workgroup then adds the chunks' words in ascending
+ *   chunk order (thread t a contiguous run of chunks, the runs joined in ascending t), and does the scalar solve — psi, psi', psi'^-1,
+ *   s0^2 and the quantile — in one thread on the device.  No float atomics; nothing depends on the size of the grid: for given arrays
+ *   the record has the same bits in every run and in both memspaces.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host
+ *   read and no synchronisation.
+ *   NMOD_ERR_INVALID_ARG before any device work: prm as for nmod_site_diff_rep, a NULL prior, NULL phi or status with npos > 0, df out
+ *   of range, ci_level outside (0, 1) or NaN, npos < 0 or beyond INT32_MAX - 1.  npos == 0 is NMOD_OK and gives the n < 2 record.
+ *
+ * nmod_site_diff_rep_mod: nmod_site_diff_rep's arguments, then prior (the record, in the memspace of prm; read by the kernels, never
+ *   by the host) and phi_post (double[npos] or NULL, a trailing output: nmod_rep_out keeps its size).  What changes:
+ *     d0 == 0:     phi_post = phi
+ *     d0 == +inf:  phi_post = s0^2
+ *     otherwise:   phi_post = (d0 s0^2 + df phi) / (d0 + df)      (two products, two sums, one division; contraction is off)
+ *     phi_used = max(phi_post, opts->phi_floor);  F = stat_cond / phi_used;  p_rep = max(the two-sided Student t tail of sqrt(F) on
+ *     df_tot = prior[2] degrees of freedom, DBL_MIN); df_tot = +inf: erfc(sqrt(F / 2)).  stat_cond == 0: p_rep = 1; otherwise
+ *     phi_used == 0 (d0 == 0 or s0^2 == 0, and a floor of 0): p_rep = DBL_MIN with NMOD_REP_PHI_ZERO.
+ *     The interval of delta is taken at the drop phi_used * prior[3]; opts->ci_drop is checked as before and then IGNORED.
+ *   Everything else — pi_s, pi0, pi1, pi_pool, delta, stat_cond, p_cond, stat_het, p_het, phi, n_valid, iters — has the bytes
+ *   nmod_site_diff_rep gives for the same rows, and with a d0 == 0 record so have p_rep and, at ci_drop = prior[3], the interval.
+ *   The record's contents are not validated by the entry (they may exist on the device alone).  A NaN in d0 or df_tot, a NaN in s0^2
+ *   while d0 > 0, or a negative value among the record's first four words gives EVERY site, with or without an estimate, NaN p_rep,
+ *   phi_post, delta_lo and delta_hi and the status bit NMOD_REP_BAD_PRIOR; no interval root is run and NMOD_REP_PHI_ZERO is not set.
+ *   Refusals: nmod_site_diff_rep's, and a NULL prior.
+ * Limits: the prior has no trend in coverage or share; all sites carry the same df; zeros are left out of the fit
+ * (and moderated all the same); no robust (winsorised) fit: a few wild sites lower d0 for all; the F(1, df_tot) law of a moderated
+ * quasi-likelihood ratio is an approximation.  The three fits run twice (once for phi, once moderated).  Measured with the numpy
+ * restatement (tests/diff_mod_ref.py) on nmod_site_diff_rep's seeded cells, the prior fitted per cell, rejected at the 5 % level of
+ * 400 sites (tests/test_site_diff_mod.py, profiles/site_diff_mod.txt); `planted`: the same cell with a planted difference:
+ *     3 v 3, rho 0, null:    p_cond 0.045  p_rep 0.040  moderated 0.045
+ *     3 v 3, rho 0, planted: p_cond 0.368  p_rep 0.250  moderated 0.363
+ *     3 v 3, rho 0.05, null:    p_cond 0.203  p_rep 0.053  moderated 0.048
+ *     3 v 3, rho 0.05, planted: p_cond 0.695  p_rep 0.310  moderated 0.425
+ *     3 v 3, rho 0.15, null:    p_cond 0.403  p_rep 0.058  moderated 0.053
+ *     3 v 3, rho 0.15, planted: p_cond 0.903  p_rep 0.328  moderated 0.525
+ *     2 v 2, rho 0.1, null:    p_cond 0.278  p_rep 0.028  moderated 0.033
+ *     2 v 2, rho 0.1, planted: p_cond 0.985  p_rep 0.400  moderated 0.875
+ * (planted differences of the share: +0.12, +0.22, +0.36, +0.50, chosen so that p_rep rejects a quarter to two fifths of the sites.
+ * In six of the eight fits evar <= 0 and d0 = +inf: 400 sites of one cell do not tell their dispersions apart, and the test is then
+ * the normal one at the common dispersion s0^2.) */
+#define NMOD_REP_PRIOR_WORDS 8
+#define NMOD_REP_PRIOR_CHUNK 1024          /* sites per chunk of nmod_rep_prior's sums */
+enum { NMOD_REP_BAD_PRIOR = 64 };
+int nmod_rep_prior(const nmod_params* prm, int64_t npos, int32_t df, const double* phi, const uint8_t* status, double ci_level,
+                   double* prior);
+int nmod_site_diff_rep_mod(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score,
+                           const int64_t* off, const nmod_rep_opts* opts, const nmod_rep_out* out, const double* prior, double* phi_post);
+
 /* Same-read co-occurrence of modification calls at pairs of sites: per pair the 2 x 2 table of the reads that have a call at both
  * sites, its log odds ratio, phi and the two-sided exact test (K16; the reference project has no such step).  K11 .. K15 reduce over
  * the reads of one position; this entry keeps the read: it walks the reads and counts, per pair of candidate sites, the reads by

@@ -291,6 +291,10 @@ make_diff_out = functools.partial(make_out, NmodDiffOut)
 
 REP_TOO_FEW, REP_FLAT, REP_NOT_CONVERGED, REP_POOL_AT_END, REP_PHI_ZERO, REP_TOO_LARGE = 1, 2, 4, 8, 16, 32
 REP_NO_ESTIMATE = REP_TOO_FEW | REP_FLAT | REP_TOO_LARGE
+REP_BAD_PRIOR = 64          # nmod_site_diff_rep_mod: the record of the prior cannot be used
+REP_PRIOR_WORDS = 8         # nmod_rep_prior: the doubles of its record, REP_PRIOR_FIELDS in order
+REP_PRIOR_CHUNK = 1024      # nmod_rep_prior: consecutive sites per chunk of its sums
+REP_PRIOR_FIELDS = ('d0', 's0sq', 'df_tot', 'ci_drop', 'n_used', 'n_zero', 'emean', 'evar')
 REP_MAX_SAMPLES = 16        # nmod_site_diff_rep: the largest number of samples of a site (the smallest is 3)
 REP_SAMPLE_FIELDS = ('pi_s',)                               # npos * G doubles
 REP_FIELDS = ('pi0', 'pi1', 'pi_pool', 'delta', 'delta_lo', 'delta_hi', 'stat_cond', 'p_cond', 'stat_het', 'p_het', 'phi', 'p_rep')
@@ -542,6 +546,9 @@ _SIGNATURES = {
                                  C.POINTER(NmodDiffOut)]),
     'nmod_site_diff_rep': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NmodRepOpts),
                                      C.POINTER(NmodRepOut)]),
+    'nmod_rep_prior': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    'nmod_site_diff_rep_mod': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NmodRepOpts),
+                                         C.POINTER(NmodRepOut), C.c_void_p, C.c_void_p]),
     'nmod_pair_index': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
     'nmod_site_pairs': (C.c_int, [C.POINTER(NmodParams), C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.POINTER(NmodPairsOpts), C.POINTER(NmodPairsOut)]),

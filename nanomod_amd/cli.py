@@ -210,6 +210,9 @@ def build_parser():
     rd.add_argument('--ciLevel', type=float, default=0.95, help='the level of the interval of delta, inside (0, 1)')
     rd.add_argument('--phiFloor', type=float, default=0.0, help='replicates only: the dispersion between replicates never counts as less '
                     '(0: as estimated; 1: never below binomial), >= 0')
+    rd.add_argument('--moderate', type=int, default=0, choices=[0, 1], help='replicates only (three or more containers): 1: shrink the '
+                    'dispersion of every site towards a prior fitted over all sites; p_rep, the interval and --fdr are then the moderated '
+                    'ones, written to <FileID>_site_diff_mod.txt and <FileID>_rep_prior.txt')
     rd.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='bh / by: q-values of p_diff (with replicates: of p_rep) over '
                     'all compared sites')
     rd.add_argument('--fdrAlpha', type=float, default=0.05)
@@ -432,6 +435,8 @@ def validate_readdiff(a):
         errs.append('Error: --wrkBase1 and --wrkBase2 should name at most %d containers in all' % L.REP_MAX_SAMPLES)
     if not (math.isfinite(a.phiFloor) and a.phiFloor >= 0.0):
         errs.append('Error: --phiFloor should be finite and not negative')
+    if a.moderate and len(c0) + len(c1) < 3:
+        errs.append('Error: --moderate 1 needs replicates: three or more containers in all')
     win = parse_llr_window(a.llrWindow)
     if win is None or (win != 'kmer' and not all(0 <= v <= L.MAX_NB for v in win)):
         errs.append("Error: --llrWindow should be 'kmer' or LO,HI with both in 0 .. %d" % L.MAX_NB)
@@ -571,8 +576,13 @@ def run_readdiff(a, log=print):
                   min_coverage=a.minCoverage, fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, device=a.device, log=say)
     if len(c0) + len(c1) > 2:
         sites = readllr.compare_reads_llr_rep([container.load_reads(f) for f in c0], [container.load_reads(f) for f in c1], *models(),
-                                              diff=dict(min_valid=a.minValid, ci_level=a.ciLevel, phi_floor=a.phiFloor), **shared)
-        _save(a, say, '_site_diff_rep.txt', readllr.write_site_diff_rep, 'Site comparisons are', sites)
+                                              diff=dict(min_valid=a.minValid, ci_level=a.ciLevel, phi_floor=a.phiFloor), **shared,
+                                              **(dict(moderate=True) if a.moderate else {}))
+        if a.moderate:
+            path = _save(a, say, '_site_diff_mod.txt', readllr.write_site_diff_mod, 'Moderated site comparisons are', sites)
+            say('The prior of the dispersions is saved in %s' % (path[:-len('_site_diff_mod.txt')] + '_rep_prior.txt'))
+        else:
+            _save(a, say, '_site_diff_rep.txt', readllr.write_site_diff_rep, 'Site comparisons are', sites)
     else:
         sites = readllr.compare_reads_llr(container.load_reads(a.wrkBase1), container.load_reads(a.wrkBase2), *models(),
                                           diff=dict(min_valid=a.minValid, ci_level=a.ciLevel), **shared)

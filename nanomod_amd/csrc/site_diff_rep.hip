@@ -10,6 +10,9 @@
 //   dr_reg_kernel<64>    both super-rows <= 512: the whole wave x (8 + 8)
 //   dr_block_kernel      beyond: a workgroup per site, K15's stage
 //   dr_tail_kernel       a thread per site: p_cond, p_het and p_rep from the statistics the kernels above left in their places
+// nmod_site_diff_rep_mod (K25) is the same launches with the MOD instances of the three iterating kernels and dr_tail_mod_kernel: they
+// read the record of nmod_rep_prior (rep_prior.hip) from device memory, take the posterior dispersion for phi_used and the record's
+// quantile for the drop; the plain instances keep their code and their bytes.
 // The saturated fit: a sample is an index range of its super-row, and a sample view hands st_solve the super-row with every element
 // outside the range as w = 0, which adds exactly 0 to S, D and g (st_term).  The register forms mask the registers they hold; the
 // workgroup form walks the range alone, a thread over the words t + 512 j of the super-row it staged itself.  The lane (thread)
@@ -38,6 +41,7 @@ struct DrArgs {
   int max_iter, min_valid; double tol, ci_drop, phi_floor;
   nmod_rep_out out;
   PosLists<3> pl;
+  const double* prior; double* phi_post;          // nmod_site_diff_rep_mod alone (the MOD instances): K25's record, the moderated dispersion
 };
 
 // the outputs of a site without an estimate; n_valid is the caller's
@@ -57,6 +61,7 @@ __device__ __forceinline__ void dr_write_nan(const DrArgs& a, int64_t i, unsigne
   if (o.p_het) o.p_het[i] = nan;
   if (o.phi) o.phi[i] = nan;
   if (o.p_rep) o.p_rep[i] = nan;
+  if (a.phi_post) a.phi_post[i] = nan;
   if (o.iters) o.iters[i] = 0;
   if (o.status) o.status[i] = (uint8_t)status;
 }
@@ -144,10 +149,18 @@ struct DrBlockSample {
   }
 };
 
+// A record no site can be moderated with: a NaN in d0 or df_tot, a NaN in s0^2 where it is used (d0 > 0), a negative word among the
+// first four.  The one rule: the MOD instances below skip the interval under it, dr_tail_mod_kernel writes what follows from it.
+__device__ __forceinline__ bool dr_prior_bad(const double* prior) {
+  const double d0 = prior[0], s0 = prior[1], dft = prior[2], ci = prior[3];
+  return d0 != d0 || dft != dft || (d0 > 0.0 && s0 != s0) || d0 < 0.0 || s0 < 0.0 || dft < 0.0 || ci < 0.0;
+}
+
 // Everything between a site's counts and its outputs.  sample(g): the view of sample g; `lead`: the thread that writes.  The condition
 // level is df_estimate's (site_diff.hip), operation for operation, with the saturated fit between its test and its interval: the drop
 // of the interval needs the dispersion.
-template <class Pair, class SampleOf>
+// MOD (nmod_site_diff_rep_mod): the dispersion is the posterior one under the record a.prior and the drop is scaled by the record's quantile.
+template <bool MOD, class Pair, class SampleOf>
 __device__ __forceinline__ void dr_estimate(const DrArgs& a, const Pair& pair, const SampleOf& sample, bool have, bool lead, int64_t pos,
                                             bool too_few, bool flat) {
   const bool run = have && !too_few && !flat;
@@ -192,9 +205,19 @@ __device__ __forceinline__ void dr_estimate(const DrArgs& a, const Pair& pair, c
   const double df = (double)(a.G - 2);
   const double stat_het = fmax(2.0 * (gsat - ghat), 0.0);
   const double phi = stat_het / df;
-  const double phi_used = fmax(phi, a.phi_floor);
+  double phi_post = phi, ci_drop = a.ci_drop;
+  bool bad = false;
+  if constexpr (MOD) {
+    const double d0 = a.prior[0], s0 = a.prior[1];
+    bad = dr_prior_bad(a.prior);
+    ci_drop = bad ? 0.0 : a.prior[3];                         // (a drop of 0: no interval root runs; the tail kernel writes the NaN)
+    if (d0 == 0.0) phi_post = phi;
+    else if (d0 > kDblMax) phi_post = s0;
+    else phi_post = (d0 * s0 + df * phi) / (d0 + df);
+  }
+  const double phi_used = fmax(phi_post, a.phi_floor);
   const double F = stat == 0.0 ? 0.0 : stat / phi_used;       // (phi_used == 0: +inf, whose tail the clamp turns into DBL_MIN)
-  const double drop = phi_used * a.ci_drop;
+  const double drop = phi_used * ci_drop;
 
   double gm = g01 + g10, gp = g00 + g11;                      // h(-1) = g0(1) + g1(0), h(+1) = g0(0) + g1(1)
   if constexpr (Pair::kAgain) {                               // (the workgroup form evaluates them here again, the same bits, as K15 does)
@@ -227,16 +250,17 @@ __device__ __forceinline__ void dr_estimate(const DrArgs& a, const Pair& pair, c
       if (o.p_het) o.p_het[pos] = stat_het;
       if (o.phi) o.phi[pos] = phi;
       if (o.p_rep) o.p_rep[pos] = F;
+      if constexpr (MOD) { if (a.phi_post) a.phi_post[pos] = phi_post; }
       if (o.iters) o.iters[pos] = iters;
       if (o.status) o.status[pos] = (uint8_t)((nc0 || nc1 || ncp || ncs || nclo || nchi || prof_lo.nc || prof_hi.nc ? NMOD_REP_NOT_CONVERGED : 0) |
                                               (pip == 0.0 || pip == 1.0 ? NMOD_REP_POOL_AT_END : 0) |
-                                              (stat != 0.0 && phi_used == 0.0 ? NMOD_REP_PHI_ZERO : 0));
+                                              (stat != 0.0 && phi_used == 0.0 && !bad ? NMOD_REP_PHI_ZERO : 0));
     }
   }
 }
 
 // two waves per SIMD: the register budget of K15's forms
-template <int G>
+template <int G, bool MOD>
 __global__ __launch_bounds__(kDfThreads, 2) void dr_reg_kernel(DrArgs a) {
   const int gl = threadIdx.x & (G - 1);
   for (GroupWalk<G == 16 ? 0 : 1, G, kDfThreads> it(a.pl); it.more(); it.next()) {
@@ -287,10 +311,11 @@ __global__ __launch_bounds__(kDfThreads, 2) void dr_reg_kernel(DrArgs a) {
       if (have) dr_range(a, pos, g, second ? m1 : m0, lo, hi);
       return DrRegSample<G>{pair, second, (int)lo, (int)hi, gl};
     };
-    dr_estimate(a, pair, sample, have, gl == 0, pos, too_few, !too_few && any_flat);
+    dr_estimate<MOD>(a, pair, sample, have, gl == 0, pos, too_few, !too_few && any_flat);
   }
 }
 
+template <bool MOD>
 __global__ __launch_bounds__(kStBlockThreads) void dr_block_kernel(DrArgs a) {
   __shared__ double stage[kDfStage];
   __shared__ double sh[kStBlockWaves];
@@ -333,7 +358,7 @@ __global__ __launch_bounds__(kStBlockThreads) void dr_block_kernel(DrArgs a) {
       dr_range(a, pos, g, second ? m1 : m0, lo, hi);
       return DrBlockSample{second ? sc1 : sc0, stage + (second ? m0 : 0), lo, hi, sh, rot, staged};
     };
-    dr_estimate(a, pair, sample, true, tid == 0, pos, too_few, !too_few && any_flat);
+    dr_estimate<MOD>(a, pair, sample, true, tid == 0, pos, too_few, !too_few && any_flat);
   }
 }
 
@@ -357,12 +382,48 @@ __global__ __launch_bounds__(256) void dr_tail_kernel(double* p_cond, double* p_
   }
 }
 
+// nmod_site_diff_rep_mod's tail: p_cond and p_het as above; p_rep on the record's df_tot degrees of freedom (+inf: the normal tail of
+// sqrt(F), erfc(sqrt(F / 2))); and, decided here once for every site, with or without an estimate, what a record that cannot be used
+// does: NaN p_rep, phi_post and interval, and NMOD_REP_BAD_PRIOR.
+__global__ __launch_bounds__(256) void dr_tail_mod_kernel(DrArgs a) {
+  const nmod_rep_out& o = a.out;
+  const int df = a.G - 2;
+  const bool bad = dr_prior_bad(a.prior);
+  const double dft = a.prior[2];
+  const bool normal = dft > kDblMax;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.npos; i += (int64_t)gridDim.x * 256) {
+    if (o.p_cond) {
+      const double stat = o.p_cond[i];
+      if (stat == stat) o.p_cond[i] = fmax(erfc(sqrt(0.5 * stat)), kDblMin);
+    }
+    if (o.p_het) {
+      const double stat = o.p_het[i];
+      if (stat == stat) o.p_het[i] = fmax(df & 1 ? chi2_sf_odd(stat, df >> 1) : chi2_sf_even(stat, df >> 1), kDblMin);
+    }
+    if (o.p_rep) {
+      const double F = o.p_rep[i];
+      const double p = normal ? erfc(sqrt(0.5 * F)) : student_t_two_sided(sqrt(F), bad ? 1.0 : dft);   // (every lane of the trip votes)
+      if (F == F) o.p_rep[i] = fmax(p, kDblMin);
+    }
+    if (bad) {
+      const double nan = nan_f64();
+      if (o.p_rep) o.p_rep[i] = nan;
+      if (a.phi_post) a.phi_post[i] = nan;
+      if (o.delta_lo) o.delta_lo[i] = nan;
+      if (o.delta_hi) o.delta_hi[i] = nan;
+      if (o.status) o.status[i] = (uint8_t)(o.status[i] | NMOD_REP_BAD_PRIOR);
+    }
+  }
+}
+
 }  // namespace nmod
 
 using namespace nmod;
 
-extern "C" int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score,
-                                  const int64_t* off, const nmod_rep_opts* opts, const nmod_rep_out* out) {
+// both entries; MOD: nmod_site_diff_rep_mod, with the record `prior` and the output `phi_post` (or NULL)
+template <bool MOD>
+static int dr_entry(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score, const int64_t* off,
+                    const nmod_rep_opts* opts, const nmod_rep_out* out, const double* prior, double* phi_post) {
   if (check_prm_common(prm, kPrmAnyDtype) != NMOD_OK) return NMOD_ERR_INVALID_ARG;
   if (!opts || opts->struct_size != (int32_t)sizeof(nmod_rep_opts)) return NMOD_ERR_INVALID_ARG;
   if (!out || out->struct_size != (int32_t)sizeof(nmod_rep_out)) return NMOD_ERR_INVALID_ARG;
@@ -371,7 +432,7 @@ extern "C" int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t 
   if (!(opts->phi_floor >= 0.0) || !(opts->phi_floor <= kDblMax)) return NMOD_ERR_INVALID_ARG;
   if (nsamples < 3 || nsamples > NMOD_REP_MAX_SAMPLES || ncontrol < 1 || ncontrol > nsamples - 1) return NMOD_ERR_INVALID_ARG;
   if (npos < 0 || npos > ((int64_t)INT32_MAX - 1) / nsamples) return NMOD_ERR_INVALID_ARG;
-  if (!off || (npos > 0 && !score)) return NMOD_ERR_INVALID_ARG;
+  if (!off || (npos > 0 && !score) || (MOD && !prior)) return NMOD_ERR_INVALID_ARG;
   const bool host = prm->memspace == NMOD_MEM_HOST;
   const int64_t nrows = npos * nsamples;
   int num_cus = 0;
@@ -388,6 +449,7 @@ extern "C" int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t 
   a.G = nsamples; a.nc = ncontrol;
   a.max_iter = opts->max_iter; a.min_valid = opts->min_valid; a.tol = opts->tol; a.ci_drop = opts->ci_drop; a.phi_floor = opts->phi_floor;
   a.out = *out;
+  a.prior = prior; a.phi_post = phi_post;
 
   // one slab: the three work lists and their count words; for the host entry the inputs and outputs as well
   Slab slab(host);
@@ -398,13 +460,27 @@ extern "C" int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t 
   slab.out(a.out.stat_cond, np * 8); slab.out(a.out.p_cond, np * 8); slab.out(a.out.stat_het, np * 8); slab.out(a.out.p_het, np * 8);
   slab.out(a.out.phi, np * 8); slab.out(a.out.p_rep, np * 8);
   slab.out(a.out.n_valid, nr * 4); slab.out(a.out.iters, np * 4); slab.out(a.out.status, np);
+  if (MOD) { slab.in(a.prior, NMOD_REP_PRIOR_WORDS * 8); slab.out(a.phi_post, np * 8); }
   NMOD_HIP(slab.commit(stream, prm->device));
   NMOD_HIP(lists.fill<DrRule>(slab, a, num_cus, stream));
-  launch_groups<16, kDfThreads>(dr_reg_kernel<16>, a, num_cus, stream);
-  launch_groups<64, kDfThreads>(dr_reg_kernel<64>, a, num_cus, stream);
-  launch_blocks<kStBlockThreads>(dr_block_kernel, a, num_cus, stream);
-  if (a.out.p_cond || a.out.p_het || a.out.p_rep)
-    hipLaunchKernelGGL(dr_tail_kernel, dim3(persistent_grid(npos, 256, (int64_t)num_cus * 16)), dim3(256), 0, stream, a.out.p_cond, a.out.p_het,
-                       a.out.p_rep, nsamples - 2, npos);
+  launch_groups<16, kDfThreads>(dr_reg_kernel<16, MOD>, a, num_cus, stream);
+  launch_groups<64, kDfThreads>(dr_reg_kernel<64, MOD>, a, num_cus, stream);
+  launch_blocks<kStBlockThreads>(dr_block_kernel<MOD>, a, num_cus, stream);
+  const dim3 tail_grid(persistent_grid(npos, 256, (int64_t)num_cus * 16));
+  if (MOD)
+    hipLaunchKernelGGL(dr_tail_mod_kernel, tail_grid, dim3(256), 0, stream, a);
+  else if (a.out.p_cond || a.out.p_het || a.out.p_rep)
+    hipLaunchKernelGGL(dr_tail_kernel, tail_grid, dim3(256), 0, stream, a.out.p_cond, a.out.p_het, a.out.p_rep, nsamples - 2, npos);
   return launches_end(slab, stream);
+}
+
+extern "C" int nmod_site_diff_rep(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score,
+                                  const int64_t* off, const nmod_rep_opts* opts, const nmod_rep_out* out) {
+  return dr_entry<false>(prm, npos, nsamples, ncontrol, score, off, opts, out, nullptr, nullptr);
+}
+
+extern "C" int nmod_site_diff_rep_mod(const nmod_params* prm, int64_t npos, int32_t nsamples, int32_t ncontrol, const double* score,
+                                      const int64_t* off, const nmod_rep_opts* opts, const nmod_rep_out* out, const double* prior,
+                                      double* phi_post) {
+  return dr_entry<true>(prm, npos, nsamples, ncontrol, score, off, opts, out, prior, phi_post);
 }

@@ -276,4 +276,91 @@ __device__ inline double chi2_sf_odd(double X, int M) {
   return sum > 1.0 ? 1.0 : sum;
 }
 
+// ---- the polygamma functions of K25's prior fit (nmod_rep_prior: one thread; x > 0).  All three by the same method: the recurrence
+// f(x) = f(x + 1) -+ n! / x^(n+1) up to z >= 16, then the asymptotic (Bernoulli) series in 1 / z^2 through B14 (next term below 1e-19
+// at z = 16).  The recurrence terms are summed on their own and joined to the series once.  Measured against 50-digit mpmath on 4 000
+// log-uniform points of 1e-3 <= x <= 1e8 and the half-integers 1/2 .. 7 (tests/test_site_diff_mod.py, profiles/site_diff_mod.txt):
+//   digamma    1.4e-15 relative to max(1, |psi|) (it crosses 0 at 1.4616), 5.3e-16 relative from x = 4 on
+//   trigamma   6.7e-16 relative
+//   tetragamma 7.2e-16 relative
+// psi(x) = ln z - 1/(2z) - sum_n B_2n / (2n z^2n) - sum_{k < z - x} 1 / (x + k)
+__device__ inline double digamma(double x) {
+  double z = x, shift = 0.0;
+#pragma unroll 1
+  while (z < 16.0) { shift += 1.0 / z; z += 1.0; }
+  const double r = 1.0 / z, r2 = r * r;
+  const double tail = r2 * (1.0 / 12.0 - r2 * (1.0 / 120.0 - r2 * (1.0 / 252.0 - r2 * (1.0 / 240.0 - r2 * (1.0 / 132.0
+                      - r2 * (691.0 / 32760.0 - r2 * (1.0 / 12.0)))))));
+  return log(z) - 0.5 * r - tail - shift;
+}
+
+// psi'(x) = 1/z + 1/(2 z^2) + sum_n B_2n / z^(2n+1) + sum_{k < z - x} 1 / (x + k)^2
+__device__ inline double trigamma(double x) {
+  double z = x, shift = 0.0;
+#pragma unroll 1
+  while (z < 16.0) { shift += 1.0 / (z * z); z += 1.0; }
+  const double r = 1.0 / z, r2 = r * r;
+  const double tail = r * r2 * (1.0 / 6.0 - r2 * (1.0 / 30.0 - r2 * (1.0 / 42.0 - r2 * (1.0 / 30.0 - r2 * (5.0 / 66.0
+                      - r2 * (691.0 / 2730.0 - r2 * (7.0 / 6.0)))))));
+  return r + 0.5 * r2 + tail + shift;
+}
+
+// psi''(x) = -1/z^2 - 1/z^3 - sum_n (2n + 1) B_2n / z^(2n+2) - sum_{k < z - x} 2 / (x + k)^3   (the slope of the Newton step below)
+__device__ inline double tetragamma(double x) {
+  double z = x, shift = 0.0;
+#pragma unroll 1
+  while (z < 16.0) { shift += 2.0 / (z * z * z); z += 1.0; }
+  const double r = 1.0 / z, r2 = r * r;
+  const double tail = r2 * r2 * (0.5 - r2 * (1.0 / 6.0 - r2 * (1.0 / 6.0 - r2 * (0.3 - r2 * (5.0 / 6.0
+                      - r2 * (691.0 / 210.0 - r2 * (17.5)))))));
+  return -(r2 + r * r2 + tail + shift);
+}
+
+// The y > 0 with psi'(y) = x, x > 0: limma's trigammaInverse.  Newton on 1 / psi', which is convex and nearly linear in y, from
+// y = 1/2 + 1/x, which lies below the root: the iterates rise to it.  The step is dif = psi'(y) (1 - psi'(y) / x) / psi''(y), and
+// the iteration STOPS after the first step with -dif / y < 1e-8 (the step is applied; convergence is quadratic, so what is left
+// is of the order 1e-16), or after 50 steps.  x > 1e7: 1 / sqrt(x), x < 1e-6: 1 / x (the leading terms; the next is 1e-7 relative
+// at most, and the prior fit reaches neither: evar there means d0 below 1e-3 or above 1e6).  NaN for NaN; not for x <= 0.
+// Against mpmath's root on 1e-6 <= x <= 1e7: 4.3e-16 relative (tests/test_site_diff_mod.py).
+__device__ inline double trigamma_inverse(double x) {
+  if (x != x) return x;
+  if (x > 1e7) return 1.0 / sqrt(x);
+  if (x < 1e-6) return 1.0 / x;
+  double y = 0.5 + 1.0 / x;
+#pragma unroll 1
+  for (int it = 0; it < 50; ++it) {
+    const double tri = trigamma(y);
+    const double dif = tri * (1.0 - tri / x) / tetragamma(y);
+    y += dif;
+    if (-dif / y < 1e-8) break;
+  }
+  return y;
+}
+
+// The `level` quantile of F(1, nu) for real nu > 0, 0 < level < 1: the square of the t with student_t_two_sided(t, nu) = 1 - level,
+// by bisection of that tail (decreasing in t) until the bracket is two neighbouring doubles; nu = +inf: norm_isf((1 - level) / 2)^2,
+// the chi2_1 quantile.  One thread's work (the tail votes with __ballot: a lone thread's vote is its own).  Its error is the tail's:
+// against mpmath over nu in {1 .. 14, 2.37, 14.6, 1e6, inf} and levels 0.9, 0.95, 0.999, compiled for the host: 2.6e-13 relative, but
+// 1.9e-11 at nu = 1 and 0.999 (t = 637: the tail's log1p(-y) with y within 2.5e-6 of 1); on the device 4e-15 over the eleven fits
+// of tests/test_site_diff_mod_gpu.py (tests/test_site_diff_mod.py; profiles/site_diff_mod.txt §3).
+__device__ inline double f1_quantile(double level, double nu) {
+  const double alpha = 1.0 - level;
+  if (nu != nu || alpha != alpha) return __builtin_nan("");
+  if (isinf(nu)) { const double z = norm_isf(0.5 * alpha); return z * z; }
+  double lo = 0.0, hi = 1.0;
+#pragma unroll 1
+  while (student_t_two_sided(hi, nu) > alpha) {
+    lo = hi; hi *= 2.0;
+    if (hi > 1e150) return __builtin_inf();
+  }
+#pragma unroll 1
+  for (int it = 0; it < 1100; ++it) {
+    const double mid = lo + 0.5 * (hi - lo);
+    if (mid <= lo || mid >= hi) break;
+    if (student_t_two_sided(mid, nu) > alpha) lo = mid; else hi = mid;
+  }
+  const double t = lo + 0.5 * (hi - lo);
+  return t * t;
+}
+
 }  // namespace nmod

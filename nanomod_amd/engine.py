@@ -909,9 +909,11 @@ def _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, to
     return L.make_rep_opts(o.max_iter, o.min_valid, o.tol, ci_drop, phi_floor), int(n_samples), int(n_control)
 
 
-def _rep_shapes(npos, n_samples, interval=True):
+def _rep_shapes(npos, n_samples, interval=True, moderated=False):
     shapes = {k: ('float64', npos * n_samples) for k in L.REP_SAMPLE_FIELDS}
     shapes.update({k: ('float64', npos) for k in L.REP_FIELDS if interval or k not in ('delta_lo', 'delta_hi')})
+    if moderated:
+        shapes['phi_post'] = ('float64', npos)
     shapes.update({k: ('int32', npos * n_samples) for k in L.REP_SAMPLE_INT_FIELDS})
     shapes.update({k: ('int32', npos) for k in L.REP_INT_FIELDS})
     shapes['status'] = ('uint8', npos)
@@ -924,26 +926,68 @@ def _rep_npos(nrows, n_samples, what):
     return nrows // n_samples
 
 
+def _rep_prior_args(df, ci_level):
+    """(df, ci_level) as nmod_rep_prior takes them; ValueError for what it refuses"""
+    if int(df) != df or not 1 <= int(df) <= L.REP_MAX_SAMPLES - 2:
+        raise ValueError('df must be an integer in 1 .. %d (n_samples - 2), not %r' % (L.REP_MAX_SAMPLES - 2, df))
+    ci_level = float(ci_level)
+    if not 0.0 < ci_level < 1.0:
+        raise ValueError('ci_level must lie strictly between 0 and 1, not %r' % (ci_level,))
+    return int(df), ci_level
+
+
+def rep_prior_record(prior):
+    """the record of nmod_rep_prior as 8 float64: from rep_prior_host's dict, or any sequence of 8 numbers as it is"""
+    rec = np.array([prior[f] for f in L.REP_PRIOR_FIELDS] if isinstance(prior, dict) else prior, dtype=np.float64)
+    if rec.shape != (L.REP_PRIOR_WORDS,):
+        raise ValueError('prior must hold the %d doubles of nmod_rep_prior\'s record' % L.REP_PRIOR_WORDS)
+    return np.ascontiguousarray(rec)
+
+
+def rep_prior_host(phi, status, df, *, ci_level=0.95, device=0):
+    """The prior law of the per-site dispersions of site_diff_rep_host fitted over all sites (nmod_rep_prior, include/nanomod_hip.h):
+    phi float64 and status uint8 as site_diff_rep_host returned them, df = n_samples - 2.  Returns the record as a dict of floats: d0
+    (the prior's degrees of freedom; 0: no prior, inf: one dispersion for all), s0sq, df_tot = df + d0, ci_drop (the ci_level
+    quantile of F(1, df_tot)), n_used, n_zero, emean, evar.  site_diff_rep_host(..., prior=) takes it as it is."""
+    lib = L.load()
+    df, ci_level = _rep_prior_args(df, ci_level)
+    phi, status = np.ascontiguousarray(phi, dtype=np.float64), np.ascontiguousarray(status, dtype=np.uint8)
+    if phi.ndim != 1 or phi.shape != status.shape:
+        raise ValueError('rep_prior: phi and status must be vectors of one length')
+    rec = np.full(L.REP_PRIOR_WORDS, np.nan)
+    _join_warm_up(device)
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
+    _call(lib, 'nmod_rep_prior', prm, len(phi), df, _np_ptr(phi), _np_ptr(status), ci_level, _np_ptr(rec))
+    return dict(zip(L.REP_PRIOR_FIELDS, rec.tolist()))
+
+
 def site_diff_rep_host(score, off, n_samples, n_control, *, min_valid=3, ci_level=0.95, phi_floor=0.0, max_iter=60, tol=1e-12, interval=True,
-                       device=0):
+                       prior=None, device=0):
     """The modified shares of two replicated conditions compared per site (nmod_site_diff_rep, include/nanomod_hip.h): score float64,
     off int64[npos * n_samples + 1], row i * n_samples + g for site i and sample g; the first n_control samples of every site are
     condition 0.  Returns a dict of numpy arrays: pi_s and n_valid per sample (npos * n_samples); per site pi0, pi1, pi_pool, delta,
     with `interval` delta_lo and delta_hi at ci_level, stat_cond and p_cond (site_diff's test of the pooled reads), stat_het, p_het and
     phi (the heterogeneity of the replicates and the dispersion), p_rep (the F(1, n_samples - 2) test of delta that carries it),
-    float64; iters (int32); status (uint8, L.REP_* bits).  phi_floor: the dispersion never counts as less (1.0: never below binomial)."""
+    float64; iters (int32); status (uint8, L.REP_* bits).  phi_floor: the dispersion never counts as less (1.0: never below binomial).
+    prior: the record of rep_prior_host (its dict, or 8 doubles): nmod_site_diff_rep_mod — phi is moderated under it, p_rep is on the
+    record's df_tot, the interval is at the record's quantile (ci_level is then unused) and the result gains phi_post."""
     lib = L.load()
     opts, n_samples, n_control = _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, tol)
+    rec = None if prior is None else rep_prior_record(prior)
     if off is None:
         raise ValueError('site_diff_rep takes CSR rows: off is required')
     score, off, _, nrows = _host_score_rows(score, off, 0)
     npos = _rep_npos(nrows, n_samples, 'site_diff_rep')
-    shapes = _rep_shapes(npos, n_samples, interval)
+    shapes = _rep_shapes(npos, n_samples, interval, moderated=rec is not None)
     res = _host_outputs(shapes, fill=shapes)
     _join_warm_up(device)
-    out = L.make_out(L.NmodRepOut, **_np_ptrs(res))
+    out = L.make_out(L.NmodRepOut, **_np_ptrs({k: v for k, v in res.items() if k != 'phi_post'}))
     prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64)
-    _call(lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, _np_ptr(score), _np_ptr(off), C.byref(opts), C.byref(out))
+    if rec is None:
+        _call(lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, _np_ptr(score), _np_ptr(off), C.byref(opts), C.byref(out))
+    else:
+        _call(lib, 'nmod_site_diff_rep_mod', prm, npos, n_samples, n_control, _np_ptr(score), _np_ptr(off), C.byref(opts), C.byref(out),
+              _np_ptr(rec), _np_ptr(res['phi_post']))
     return res
 
 
@@ -1818,20 +1862,43 @@ class DeviceDetector:
         _call(self.lib, 'nmod_site_diff', prm, npos0, score0.data_ptr(), _ptr(off0), score1.data_ptr(), _ptr(off1), C.byref(opts), C.byref(o))
         return res
 
+    def rep_prior(self, phi, status, df, *, ci_level=0.95, out=None):
+        """The prior law of site_diff_rep's dispersions (nmod_rep_prior, NMOD_MEM_DEVICE) on the current stream, nothing read back: phi
+        a float64 and status a uint8 CUDA vector of one length, as site_diff_rep returned them.  Returns the record, a float64 CUDA
+        vector of L.REP_PRIOR_WORDS (`out` if given), which site_diff_rep(prior=) reads on the device."""
+        torch = self.torch
+        df, ci_level = _rep_prior_args(df, ci_level)
+        _cuda_vecs('rep_prior', (('phi', phi, torch.float64, None), ('status', status, torch.uint8, phi.numel())), one_dim=True)
+        if out is None:
+            out = torch.empty(L.REP_PRIOR_WORDS, dtype=torch.float64, device=self._dev)
+        else:
+            _cuda_vecs('rep_prior: out', (('out', out, torch.float64, L.REP_PRIOR_WORDS),), one_dim=True)
+        prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_rep_prior', prm, phi.numel(), df, phi.data_ptr(), status.data_ptr(), ci_level, out.data_ptr())
+        return out
+
     def site_diff_rep(self, score, off, n_samples, n_control, *, min_valid=3, ci_level=0.95, phi_floor=0.0, max_iter=60, tol=1e-12,
-                      interval=True, out=None):
+                      interval=True, prior=None, out=None):
         """The modified shares of two replicated conditions compared per site (nmod_site_diff_rep, NMOD_MEM_DEVICE) on the current
         stream, nothing read back: score a float64 CUDA vector, off an int64 CUDA vector of npos * n_samples + 1 offsets, row
         i * n_samples + g for site i and sample g, the first n_control samples condition 0 (engine.match_score_rows_multi makes them).
-        Returns a dict of CUDA tensors as site_diff_rep_host's arrays.  p_rep, p_cond and p_het are tracks fdr() takes as they are."""
+        Returns a dict of CUDA tensors as site_diff_rep_host's arrays.  p_rep, p_cond and p_het are tracks fdr() takes as they are.
+        prior: the record rep_prior() left on the device (nmod_site_diff_rep_mod: the result gains phi_post); the kernels read it, the
+        host never does."""
         opts, n_samples, n_control = _rep_opts(n_samples, n_control, min_valid, ci_level, phi_floor, max_iter, tol)
         _cuda_vecs('site_diff_rep', (('score', score, self.torch.float64, None),), one_dim=True)
+        if prior is not None:
+            _cuda_vecs('site_diff_rep', (('prior', prior, self.torch.float64, L.REP_PRIOR_WORDS),), one_dim=True)
         npos = _rep_npos(_device_offsets(self.torch, off, 'site_diff_rep', 'npos * n_samples'), n_samples, 'site_diff_rep')
-        shapes = _rep_shapes(npos, n_samples, interval)
+        shapes = _rep_shapes(npos, n_samples, interval, moderated=prior is not None)
         res = self._outputs(out, shapes, 'site_diff_rep')
-        o = L.make_out(L.NmodRepOut, **{name: res[name].data_ptr() for name in shapes})
+        o = L.make_out(L.NmodRepOut, **{name: res[name].data_ptr() for name in shapes if name != 'phi_post'})
         prm = self._params(L.DTYPE_F64, 0, 0, 0, 0)
-        _call(self.lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, score.data_ptr(), off.data_ptr(), C.byref(opts), C.byref(o))
+        if prior is None:
+            _call(self.lib, 'nmod_site_diff_rep', prm, npos, n_samples, n_control, score.data_ptr(), off.data_ptr(), C.byref(opts), C.byref(o))
+        else:
+            _call(self.lib, 'nmod_site_diff_rep_mod', prm, npos, n_samples, n_control, score.data_ptr(), off.data_ptr(), C.byref(opts), C.byref(o),
+                  prior.data_ptr(), res['phi_post'].data_ptr())
         return res
 
     def pair_index(self, key, max_dist=100):

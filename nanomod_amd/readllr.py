@@ -27,6 +27,7 @@ from . import _lib as L
 from . import engine
 from . import rescale as _rescale
 from . import tables as T
+from .sitemod import moderated_entry, write_site_diff_mod         # (K25: the moderated chain step and the writer of its two files)
 from .readcalls import _RESCALE_KEYS, _checked_reads, _known_options, _open_device, _pivot_sites, _read_table, _upload_rescaled
 
 
@@ -161,6 +162,9 @@ _REPLICATED = dict(
                                       % (n_control, len(nreads) - n_control, ', '.join(str(n) for n in nreads)))
 
 
+_MODERATED = dict(_REPLICATED, entry=moderated_entry, fields=SITE_DIFF_REP_FIELDS + ('phi_post', 'rep_prior'))
+
+
 def _compare(tail, reads, labels, n_control, model, alt_model, window, thr, prior, min_positions, rescale, min_coverage, diff, fdr, fdr_alpha,
              names, device, log):
     """compare_reads_llr and compare_reads_llr_rep: the chain of every sample of `reads` (labelled `labels` in a refusal), the first
@@ -227,7 +231,7 @@ def write_site_diff(path, sites):
 
 
 def compare_reads_llr_rep(reads0_list, reads1_list, model, alt_model, *, window='kmer', thr=2.5, prior=0.5, min_positions=1, rescale=None,
-                          min_coverage=1, diff={}, fdr=None, fdr_alpha=0.05, names=None, device=0, log=print):
+                          min_coverage=1, diff={}, fdr=None, fdr_alpha=0.05, names=None, device=0, log=print, moderate=False):
     """Compare the modified share of every site between two replicated conditions: reads0_list the read-level sets
     (container.READ_FIELDS) of the control condition's replicates, reads1_list those of the other; three or more sets in all.
     compare_reads_llr's chain per sample — the optional rescaling (K11), the window sums (K13), the pivot with one list of chromosome
@@ -236,10 +240,20 @@ def compare_reads_llr_rep(reads0_list, reads1_list, model, alt_model, *, window=
     fdr: None, 'bh' or 'by': p_rep goes through nmod_fdr_adjust on the device at fdr_alpha and `sites` gains q.
     Returns `sites`, one entry per matched site: chrom, strand, pos, base, n_samples, n_control, n_valid and pi_s (npos x G), pi0, pi1,
     pi_pool, delta, delta_lo, delta_hi, stat_cond, p_cond, stat_het, p_het, phi, p_rep, [q,] rep_status (uint8, L.REP_* bits).  One
-    summary line goes to `log`."""
+    summary line goes to `log`.
+    moderate: shrink the dispersions across sites (K25): K24 without its interval for phi, nmod_rep_prior over all matched sites, then
+    nmod_site_diff_rep_mod.  p_rep, the interval and q are then the moderated ones, and `sites` gains phi_post, df_tot and rep_prior (the
+    record as a dict of L.REP_PRIOR_FIELDS); a second line about the prior goes to `log`.  The three fits run twice."""
     n0, n1 = len(reads0_list), len(reads1_list)
-    return _compare(_REPLICATED, list(reads0_list) + list(reads1_list), ['reads0[%d]' % i for i in range(n0)] + ['reads1[%d]' % i for i in range(n1)],
-                    n0, model, alt_model, window, thr, prior, min_positions, rescale, min_coverage, diff, fdr, fdr_alpha, names, device, log)
+    sites = _compare(_MODERATED if moderate else _REPLICATED, list(reads0_list) + list(reads1_list),
+                     ['reads0[%d]' % i for i in range(n0)] + ['reads1[%d]' % i for i in range(n1)],
+                     n0, model, alt_model, window, thr, prior, min_positions, rescale, min_coverage, diff, fdr, fdr_alpha, names, device, log)
+    if moderate:
+        rec = sites['rep_prior'] = dict(zip(L.REP_PRIOR_FIELDS, sites['rep_prior'].tolist()))
+        sites['df_tot'] = rec['df_tot']
+        log('readdiff: the prior of the dispersions rests on %d site(s) (%d more at 0): d0 %g, s0^2 %g; p_rep on %g degrees of freedom'
+            % (int(rec['n_used']), int(rec['n_zero']), rec['d0'], rec['s0sq'], rec['df_tot']))
+    return sites
 
 
 def write_site_diff_rep(path, sites):
