@@ -786,6 +786,56 @@ typedef struct nmod_site_llr_out { int32_t struct_size; int32_t reserved; int32_
 int nmod_site_llr(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */, double thr,
                   const nmod_site_llr_out* out);
 
+/* Per-read log-likelihood ratios of one unmodified k-mer table against SEVERAL modified tables in one walk, with a joint call and a
+ * posterior over the states per event (K26; the reference project has no such step).  Where nmod_read_llr asks "modified or canonical"
+ * against one alternative, this asks "which of n_alt modifications, or none": state 0 is canonical, state m (1 .. n_alt) is alt[m-1].
+ *   Inputs: nmod_read_llr's, with n_alt (1 .. NMOD_MULTI_MAX) and alt, an array of n_alt pointers to nmod_rescale_model structs, in the
+ *     place of `alt`; every alt[m]->k and ->center must equal model's; all tables live in the call's memspace (the structs and the array
+ *     of pointers on the host).  total_events >= 0 is the length of one output plane: per-event outputs are PLANES of total_events
+ *     elements, plane p at out[p * total_events + j] with j the event's index in val's layout; a host call requires
+ *     off[nreads] <= total_events.  opts->prior_logit[m-1] is the log prior odds of state m against canonical, each finite with
+ *     |.| <= 700 (entries beyond n_alt are not read).  One thr and one window (nb_lo, nb_hi) for all states.
+ *   Tracks.  Track m is nmod_read_llr's llr and llr_win for the pair (model, alt[m-1]), word for word: the usable-code rule per pair,
+ *     the candidate and eligibility rule with NMOD_LLR_MAX, the formula with contraction off, the ascending window sum that skips
+ *     ineligible terms, reads as walls, NMOD_CALLS_TOO_LARGE.  Plane m-1 of llr and of llr_win therefore holds the BITS that
+ *     nmod_read_llr(model, alt[m-1]) writes with the same window.  A plane is contiguous and goes into nmod_pivot_reads as `val`.
+ *   Joint call per event, contraction off.  State m is OPEN at event j iff L_m (its llr_win) is not NaN; the event is eligible iff some
+ *     state is open.  b = the open m with the largest L_m, ties to the smaller m; second = the largest of 0 and the other open L_m'.
+ *       call = b                        iff L_b - second >= thr
+ *            = 0 (canonical)            iff every open L_m <= -thr
+ *            = NMOD_MULTI_AMBIGUOUS     otherwise
+ *            = NMOD_MULTI_NONE          for an ineligible event.
+ *     At n_alt = 1 this is nmod_read_llr's MOD / CAN rule exactly.
+ *   Posterior (post, n_alt + 1 planes, plane 0 canonical): u_0 = 0 and u_m = L_m + prior_logit[m-1] over the open m; mx = the largest of
+ *     0 and the u_m; e_0 = exp(-mx), e_m = exp(u_m - mx); Z = e_0 + e_m summed in ascending m; post_m = e_m / Z.  0 for a closed state,
+ *     NaN in every plane for an ineligible event.  Not clamped: a plane may hold 0 or 1.
+ *   Per read: n_sites = the eligible events, n_can = the events called 0, n_mod = n_alt planes of nreads (plane m-1 counts the events
+ *     called m), all int32, and status (uint8) 0 or NMOD_CALLS_TOO_LARGE (NaN tracks, NMOD_MULTI_NONE calls, zero counts).
+ *   Outputs: llr, llr_win (n_alt planes each), post (n_alt + 1 planes), call (uint8, total_events), n_sites, n_can (nreads), n_mod
+ *     (n_alt * nreads), status (nreads).  A NULL member is skipped, and asking for fewer outputs never changes the bits of the others.
+ *     Elements of a plane outside [off[0], off[nreads]) are left alone by a device call and are unspecified after a host call.
+ * nmod_read_llr's contract carries over: prm's fields read, the memspaces, everything on prm->stream with no host read and no
+ * synchronisation for NMOD_MEM_DEVICE (scratch: 8 bytes per read + 8 (2 + 3 n_alt) bytes per code, stream-ordered from the pool), a read's
+ * bits depend on the read alone, no float atomics.  NMOD_ERR_INVALID_ARG before any device work: nmod_read_llr's refusals, and n_alt
+ * outside 1 .. NMOD_MULTI_MAX, alt or an alt[m] NULL, a k or center that differs in any alt[m], a prior_logit[m] (m < n_alt) not finite
+ * or beyond 700 in magnitude, total_events < 0 or (host) < off[nreads].
+ * nmod_read_llr_multi_table_in_lds(n_alt, k): 1 if a call with these sizes keeps its table in LDS, 0 if it reads it through L2 (the two
+ * forms give the same bits; tests use this to cover both), -1 for sizes out of range.
+ * Stops here: one window and one threshold for all states; normal levels; reads independent; the states exclusive at a base (no
+ * "both m6A and m5C in this k-mer"); n_alt <= NMOD_MULTI_MAX. */
+#define NMOD_MULTI_MAX 4
+#define NMOD_MULTI_AMBIGUOUS 255           /* call: eligible, but neither one state nor canonical by thr */
+#define NMOD_MULTI_NONE 254                /* call: an ineligible event */
+typedef struct nmod_llr_multi_opts { int32_t struct_size, nb_lo, nb_hi, reserved; double thr; double prior_logit[NMOD_MULTI_MAX]; } nmod_llr_multi_opts;
+typedef struct nmod_llr_multi_out { int32_t struct_size; int32_t reserved;
+  double *llr, *llr_win, *post;     /* n_alt, n_alt, n_alt + 1 planes of total_events */
+  uint8_t* call;                    /* total_events */
+  int32_t *n_sites, *n_can, *n_mod; uint8_t* status; /* nreads each; n_mod: n_alt planes of nreads */ } nmod_llr_multi_out;
+int nmod_read_llr_multi(const nmod_params* prm, int64_t nreads, int64_t total_events, const int64_t* off, const void* val,
+                        const uint8_t* base, const nmod_rescale_model* model, int32_t n_alt, const nmod_rescale_model* const* alt,
+                        const nmod_llr_multi_opts* opts, const nmod_llr_multi_out* out);
+int nmod_read_llr_multi_table_in_lds(int32_t n_alt, int32_t k);
+
 /* Per-position modified fraction by maximum likelihood, with a likelihood interval, a test of "nothing is modified here" and a posterior
  * per read (K14; the reference project has no such step).  The rows are those of nmod_site_llr: per position the window sums L of the
  * reads that cover it.  If a share pi of the molecules is modified, the log-likelihood of the row relative to "all canonical" is
@@ -848,6 +898,66 @@ typedef struct nmod_stoich_out { int32_t struct_size; int32_t reserved;
   double* resp;                                                                            /* one per score, in its layout */ } nmod_stoich_out;
 int nmod_site_stoich(const nmod_params* prm, int64_t npos, const double* score, const int64_t* off /* or prm->stride0 */,
                      const nmod_stoich_opts* opts, const nmod_stoich_out* out);
+
+/* The shares of all states at a site by maximum likelihood, with a test per state and the responsibilities per read (K26; the reference
+ * project has no such step).  nmod_site_stoich's question with nmod_read_llr_multi's states: per position and state m = 1 .. n_alt one row
+ * of window sums, s_im for read i, all n_alt rows in ONE layout (the pivoted llr_win planes: nmod_pivot_reads orders its rows by the
+ * reads' layout alone, so pivoting each plane gives aligned rows).  With shares pi = (pi_0 canonical, pi_1 .. pi_n_alt) on the simplex, the
+ * log-likelihood of the row relative to "all canonical" is
+ *     l(pi) = sum_i log(pi_0 + sum_m pi_m e^{s_im}),
+ * concave in pi; the estimate is its maximiser by EM.
+ *   Inputs: n_alt (1 .. NMOD_MULTI_MAX), score: an array (on the host) of n_alt pointers to float64 scores in the call's memspace, all read
+ *     by the one `off` (int64[npos + 1]) or prm->stride0; total_scores: the length of a score plane (>= off[npos], or npos * stride0),
+ *     which is also the plane length of resp.  opts: min_valid >= 1, max_iter in 1 .. NMOD_COMPOSE_MAX_ITER, tol >= 0 finite.
+ *   Per row.  A score is finite iff fabs(s) <= DBL_MAX.  State m is OPEN iff some s_im of the row is finite.  A read is VALID iff at least
+ *     one state is open and its s_im is finite for every open m; n_valid counts them, n_partial counts the reads that are finite in some
+ *     but not all open states: they take no part.  Weights, once per valid read: mx_i = the largest of 0 and the s_im of the open m,
+ *     w_i0 = exp(-mx_i), w_im = exp(s_im - mx_i); 0 for a closed m.  No exp is evaluated inside an iteration.
+ *   The fit (contraction off).  Start: pi_m = 1 / (1 + the number of open states) on canonical and the open states, 0 elsewhere.  One
+ *     ITERATION, per valid read: t_0 = pi_0 w_i0, den_i = t_0, then in ascending m t_m = pi_m w_im, den_i += t_m; q = 1 / den_i;
+ *     R_m += t_m q.  Then pi'_m = R_m / n_valid, step = max_m |pi'_m - pi_m|, pi = pi'.  Stop iff tol > 0 and step <= tol; max_iter
+ *     bounds the iterations; iters = those made.  A fit whose loop ends without the stop test holding (always, at tol == 0) sets
+ *     NMOD_COMPOSE_NOT_CONVERGED; the values are written all the same.  One last evaluation at the final pi:
+ *     ll = sum_i (log(den_i) + mx_i);  stat = 2 max(ll, 0).  A closed state keeps pi_m = 0.
+ *   Per-state test (only when stat_m or p_m is asked for; asking never changes the bits of the other outputs, status's bits from the refits
+ *     excepted).  For every open m: the same fit with state m closed as well — the same weights and valid reads, the uniform start over
+ *     the rest, the same max_iter and tol — gives ll_without_m;  stat_m = 2 max(ll - ll_without_m, 0);  p_m = 1 at stat_m = 0, else
+ *     max(0.5 erfc(sqrt(stat_m / 2)), DBL_MIN): the 1/2 chi2_0 + 1/2 chi2_1 boundary law of the likelihood-ratio test of pi_m = 0.  It is
+ *     ASYMPTOTIC, and right only when the remaining shares are interior; it assumes that all tables are right and the reads independent.
+ *     A closed m gets NaN.  A refit that does not converge also sets NMOD_COMPOSE_NOT_CONVERGED.  At n_alt = 1, stat_1, p_1 and pi_1 are
+ *     nmod_site_stoich's stat, p_null and pi up to the convergence of EM.
+ *   resp (optional; n_alt + 1 planes of total_scores in the score layout, plane 0 canonical): t_m q of the last evaluation; NaN in every
+ *     plane for a read that is not valid and for every read of a row without an estimate.
+ *   Outputs (a NULL member is skipped): pi (n_alt + 1 planes of npos: pi[m * npos + row]), ll, stat (npos), stat_m, p_m (n_alt planes of
+ *     npos, plane m - 1 for state m), int32 n_valid, n_partial, iters, uint8 open_mask (bit m - 1: state m is open) and status (npos), resp.
+ *     Status bits:
+ *       NMOD_COMPOSE_NO_STATE        no state is open: NaN outputs, iters 0
+ *       NMOD_COMPOSE_TOO_FEW         a state is open and n_valid < min_valid: NaN outputs, iters 0 (the counts and open_mask are written)
+ *       NMOD_COMPOSE_NOT_CONVERGED   see above
+ *       NMOD_COMPOSE_DEGENERATE      a den_i of 0 after a share underflowed: NaN outputs, iters 0; in a refit: NaN stat_m and p_m of that state
+ *       NMOD_COMPOSE_TOO_LARGE       a row beyond NMOD_MAX_DEEP reads (or, NMOD_MEM_DEVICE, beyond total_scores): NaN outputs, zero counts
+ * Sums: a fixed-order chain per lane (the lane's reads in ascending index), then fixed-order lane, wave and LDS reductions; no float
+ * atomics.  A row of up to NMOD_STOICH_SMALL reads is computed by 16 lanes, up to NMOD_STOICH_WAVE by a wave, a longer one by a workgroup:
+ * a row's bits depend on the row alone, not on the batch, the order of the rows, CSR versus stride, the memspace or the outputs asked for.
+ * Reads struct_size, device, stream, memspace, stride0 of prm.  NMOD_MEM_DEVICE: everything is enqueued on prm->stream, no host read and no
+ * synchronisation; scratch comes stream-ordered from the library's pool: 12 bytes per row, and 8 (n_alt + 1) total_scores bytes when a row
+ * can be longer than nmod_site_compose_stage_reads(n_alt) (by the host offsets or the stride where known, else by total_scores).
+ * npos == 0 is NMOD_OK.  NMOD_ERR_INVALID_ARG before any device work: opts / out NULL or of another struct_size, max_iter outside
+ * 1 .. NMOD_COMPOSE_MAX_ITER, min_valid < 1, tol not finite or < 0, n_alt out of range, score or a score[m] NULL with npos > 0,
+ * total_scores < 0 or below the scores the rows hold, and nmod_site_llr's rules for prm, npos and off / stride0.
+ * Stops here: states exclusive at a base; reads independent; one window upstream; plain EM without acceleration (a share that goes to the
+ * boundary converges slowly: raise max_iter or accept NOT_CONVERGED); no interval on the shares; p_m's law as said above. */
+#define NMOD_COMPOSE_MAX_ITER 2000
+enum { NMOD_COMPOSE_TOO_FEW = 1, NMOD_COMPOSE_NO_STATE = 2, NMOD_COMPOSE_NOT_CONVERGED = 4, NMOD_COMPOSE_DEGENERATE = 8,
+       NMOD_COMPOSE_TOO_LARGE = 32 };
+typedef struct nmod_compose_opts { int32_t struct_size, max_iter, min_valid, reserved; double tol; } nmod_compose_opts;
+typedef struct nmod_compose_out { int32_t struct_size; int32_t reserved;
+  double *pi, *ll, *stat, *stat_m, *p_m;                       /* n_alt + 1, 1, 1, n_alt, n_alt planes of npos */
+  int32_t *n_valid, *n_partial, *iters; uint8_t *open_mask, *status; /* npos each */
+  double* resp;                                                /* n_alt + 1 planes of total_scores */ } nmod_compose_out;
+int nmod_site_compose(const nmod_params* prm, int64_t npos, int64_t total_scores, int32_t n_alt, const double* const* score,
+                      const int64_t* off /* or prm->stride0 */, const nmod_compose_opts* opts, const nmod_compose_out* out);
+int64_t nmod_site_compose_stage_reads(int32_t n_alt);         /* reads of a row up to which the workgroup form keeps its weights in LDS */
 
 /* The modified shares of two samples compared per site: each sample's estimate, the pooled one, the likelihood-ratio test of
  * pi0 = pi1 and the profile-likelihood interval of delta = pi1 - pi0 (K15; the reference project has no such step).  Per site two

@@ -12,6 +12,8 @@ from .kmermodel import (kmer_codes, build_kmer_model, save_kmer_model, load_kmer
 from .rescale import rescale_reads, write_read_scale  # noqa: F401
 from .readcalls import call_reads, write_read_calls, write_site_calls  # noqa: F401
 from .readllr import call_reads_llr, write_read_llr, write_site_llr, write_site_stoich, compare_reads_llr, write_site_diff, compare_reads_llr_rep, write_site_diff_rep, cooccur_reads_llr, write_site_pairs  # noqa: F401
+from .engine import read_llr_multi_host, site_compose_host  # noqa: F401
+from .readllr import call_reads_llr_multi, write_read_llr_multi, write_site_llr_multi, write_site_compose  # noqa: F401
 from . import simulate, sharding  # noqa: F401
 
 __all__ = ['mtest2', 'mfilter_coverage', 'getKStest', 'get_combin_pvalue', 'combin_pvalues', 'pos_check',
@@ -26,4 +28,5 @@ __all__ = ['mtest2', 'mfilter_coverage', 'getKStest', 'get_combin_pvalue', 'comb
            'site_stoich_host', 'write_site_stoich',
            'site_diff_host', 'match_score_rows', 'compare_reads_llr', 'write_site_diff',
            'site_diff_rep_host', 'match_score_rows_multi', 'compare_reads_llr_rep', 'write_site_diff_rep',
-           'pair_index_host', 'site_pairs_host', 'cooccur_reads_llr', 'write_site_pairs']
+           'pair_index_host', 'site_pairs_host', 'cooccur_reads_llr', 'write_site_pairs',
+           'read_llr_multi_host', 'site_compose_host', 'call_reads_llr_multi', 'write_read_llr_multi', 'write_site_llr_multi', 'write_site_compose']

@@ -264,6 +264,63 @@ def make_stoich_opts(max_iter=60, min_valid=3, tol=1e-12, ci_drop=STOICH_CI_DROP
 make_stoich_out = functools.partial(make_out, NmodStoichOut)
 
 
+MULTI_MAX = 4              # nmod_read_llr_multi / nmod_site_compose: alternative tables (states beside canonical) of one call
+MULTI_AMBIGUOUS, MULTI_NONE = 255, 254     # nmod_read_llr_multi: the call of an eligible event that is neither, of an ineligible event
+LLR_MULTI_EVENT_FIELDS = ('llr', 'llr_win', 'post', 'call')
+LLR_MULTI_READ_FIELDS = ('n_sites', 'n_can', 'n_mod', 'status')
+
+
+class NmodLlrMultiOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'nb_lo', 'nb_hi', 'reserved')] + [('thr', C.c_double), ('prior_logit', C.c_double * MULTI_MAX)]
+
+
+class NmodLlrMultiOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + [(n, C.c_void_p) for n in LLR_MULTI_EVENT_FIELDS + LLR_MULTI_READ_FIELDS]
+
+
+def make_llr_multi_opts(nb_lo=0, nb_hi=0, thr=2.5, prior_logit=()):
+    o = NmodLlrMultiOpts()
+    o.struct_size = C.sizeof(NmodLlrMultiOpts)
+    o.nb_lo, o.nb_hi, o.thr = int(nb_lo), int(nb_hi), float(thr)
+    for m, v in enumerate(prior_logit):
+        o.prior_logit[m] = float(v)
+    return o
+
+
+make_llr_multi_out = functools.partial(make_out, NmodLlrMultiOut)
+
+
+def model_ptr_array(models):
+    """an array of pointers to the given nmod_rescale_model structs (keep both alive for the call)"""
+    return (C.POINTER(NmodRescaleModel) * len(models))(*[C.pointer(m) for m in models])
+
+
+COMPOSE_TOO_FEW, COMPOSE_NO_STATE, COMPOSE_NOT_CONVERGED, COMPOSE_DEGENERATE, COMPOSE_TOO_LARGE = 1, 2, 4, 8, 32
+COMPOSE_NO_ESTIMATE = COMPOSE_TOO_FEW | COMPOSE_NO_STATE | COMPOSE_DEGENERATE | COMPOSE_TOO_LARGE
+COMPOSE_MAX_ITER = 2000
+COMPOSE_FIELDS = ('pi', 'll', 'stat', 'stat_m', 'p_m')
+COMPOSE_INT_FIELDS = ('n_valid', 'n_partial', 'iters')
+
+
+class NmodComposeOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('struct_size', 'max_iter', 'min_valid', 'reserved')] + [('tol', C.c_double)]
+
+
+class NmodComposeOut(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32)] + \
+               [(n, C.c_void_p) for n in COMPOSE_FIELDS + COMPOSE_INT_FIELDS + ('open_mask', 'status', 'resp')]
+
+
+def make_compose_opts(max_iter=500, min_valid=3, tol=1e-9):
+    o = NmodComposeOpts()
+    o.struct_size = C.sizeof(NmodComposeOpts)
+    o.max_iter, o.min_valid, o.tol = int(max_iter), int(min_valid), float(tol)
+    return o
+
+
+make_compose_out = functools.partial(make_out, NmodComposeOut)
+
+
 DIFF_TOO_FEW, DIFF_FLAT, DIFF_NOT_CONVERGED, DIFF_POOL_AT_END, DIFF_TOO_LARGE = 1, 2, 4, 8, 32
 DIFF_NO_ESTIMATE = DIFF_TOO_FEW | DIFF_FLAT | DIFF_TOO_LARGE
 DIFF_SMALL, DIFF_WAVE = 128, 512          # nmod_site_diff: scores of the longer row up to which 16 lanes / one wave compute a site
@@ -542,6 +599,12 @@ _SIGNATURES = {
                                 C.POINTER(NmodRescaleModel), C.POINTER(NmodLlrOpts), C.POINTER(NmodLlrOut)]),
     'nmod_site_llr': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(NmodSiteLlrOut)]),
     'nmod_site_stoich': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(NmodStoichOpts), C.POINTER(NmodStoichOut)]),
+    'nmod_read_llr_multi': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodRescaleModel),
+                                      C.c_int32, C.c_void_p, C.POINTER(NmodLlrMultiOpts), C.POINTER(NmodLlrMultiOut)]),
+    'nmod_read_llr_multi_table_in_lds': (C.c_int, [C.c_int32, C.c_int32]),
+    'nmod_site_compose': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NmodComposeOpts),
+                                    C.POINTER(NmodComposeOut)]),
+    'nmod_site_compose_stage_reads': (C.c_int64, [C.c_int32]),
     'nmod_site_diff': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NmodDiffOpts),
                                  C.POINTER(NmodDiffOut)]),
     'nmod_site_diff_rep': (C.c_int, [C.POINTER(NmodParams), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NmodRepOpts),

@@ -175,7 +175,19 @@ def build_parser():
     rl.add_argument('--outLevel', type=int, default=2, choices=[0, 1, 2, 3])
     rl.add_argument('--wrkBase1', required=True, help='the sample reads: a read-level .npz container')
     rl.add_argument('--kmerModel', required=True, help="the unmodified k-mer model, written by 'kmermodel'")
-    rl.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample")
+    rl.add_argument('--altModel', required=True, help="the modified k-mer model, written by 'kmermodel' from a fully modified control or learnt by 'kmermix' from a mixed sample"
+                    "; or two to four of them, comma-separated: every event is called between canonical and all of these modifications at once "
+                    "(<FileID>_read_llr_multi.txt and <FileID>_site_llr_multi.txt)")
+    rl.add_argument('--modNames', default='', help='several --altModel: a name per modified model, comma-separated (default mod1,mod2,...)')
+    rl.add_argument('--modPrior', default='', help='several --altModel: the prior probability of each modification behind the posterior '
+                    'track, comma-separated, their sum below 1 (default: canonical and the modifications alike)')
+    rl.add_argument('--siteCompose', type=int, default=0, choices=[0, 1], help='several --altModel, 1: also estimate the shares of all '
+                    'modifications at every position by maximum likelihood, with a test per modification (<FileID>_site_compose.txt)')
+    rl.add_argument('--composeMaxIter', type=int, default=500, help='--siteCompose: the most EM iterations of a fit, 1 .. %d' % L.COMPOSE_MAX_ITER)
+    rl.add_argument('--composeTol', type=float, default=1e-9, help='--siteCompose: a fit stops when no share moves by more than this, >= 0')
+    rl.add_argument('--fdr', default='none', choices=['none', 'bh', 'by'], help='--siteCompose: bh / by: q-values of the test of every '
+                    'modification over all positions, a column beside each p-value')
+    rl.add_argument('--fdrAlpha', type=float, default=0.05)
     rl.add_argument('--llrThreshold', type=float, default=2.5, help='an event is called when its window sum reaches +- this, > 0')
     rl.add_argument('--llrWindow', default='kmer', help="'kmer': the events whose k-mer holds the base; or LO,HI: events of the same read "
                     'before and after, 0 .. 64 each')
@@ -418,7 +430,37 @@ def validate_readllr(a):
         errs.append('Error: --minValid should be larger than 0')
     if not 0.0 < a.ciLevel < 1.0:
         errs.append('Error: --ciLevel should lie between 0 and 1, both excluded')
-    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel))
+    alts = a.altModel.split(',')
+    if len(alts) == 1:
+        if a.modNames or a.modPrior or a.siteCompose or a.fdr != 'none':
+            errs.append('Error: --modNames, --modPrior, --siteCompose and --fdr need several --altModel files, comma-separated')
+        return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel, a.altModel))
+    if len(alts) > L.MULTI_MAX:
+        errs.append('Error: --altModel takes at most %d files' % L.MULTI_MAX)
+    if a.siteFraction or a.outEvents:
+        errs.append('Error: --siteFraction and --outEvents are for a single --altModel (several: --siteCompose)')
+    if a.modNames and len(a.modNames.split(',')) != len(alts):
+        errs.append('Error: --modNames should name every --altModel file')
+    if a.modPrior and parse_mod_prior(a.modPrior, len(alts)) is None:
+        errs.append('Error: --modPrior should hold a probability inside (0, 1) per --altModel file, their sum below 1')
+    if not 1 <= a.composeMaxIter <= L.COMPOSE_MAX_ITER:
+        errs.append('Error: --composeMaxIter should be in 1 .. %d' % L.COMPOSE_MAX_ITER)
+    if not 0.0 <= a.composeTol < float('inf'):
+        errs.append('Error: --composeTol should be finite and not negative')
+    if a.fdr != 'none' and not a.siteCompose:
+        errs.append('Error: --fdr needs --siteCompose 1')
+    if not 0.0 < a.fdrAlpha <= 1.0:
+        errs.append('Error: --fdrAlpha should be in (0, 1]')
+    return _read_inputs_checked(errs, a, (a.wrkBase1, a.kmerModel) + tuple(alts))
+
+
+def parse_mod_prior(text, n):
+    """--modPrior: n probabilities inside (0, 1) whose sum is below 1; None for anything else"""
+    try:
+        vals = [float(q) for q in text.split(',')]
+    except ValueError:
+        return None
+    return vals if len(vals) == n and all(0.0 < v < 1.0 for v in vals) and sum(vals) < 1.0 else None
 
 
 def readdiff_samples(a):
@@ -594,6 +636,20 @@ def run_readllr(a, log=print):
     from . import kmermodel, readllr
     say = _quiet_log(a, log)
     reads = container.load_reads(a.wrkBase1)
+    alts = a.altModel.split(',')
+    if len(alts) > 1:                                          # several modifications at once (K26); a single path: what follows, as ever
+        res = readllr.call_reads_llr_multi(
+            reads, kmermodel.load_kmer_model(a.kmerModel), [kmermodel.load_kmer_model(f) for f in alts],
+            names=a.modNames.split(',') if a.modNames else None, priors=parse_mod_prior(a.modPrior, len(alts)) if a.modPrior else None,
+            compose=dict(min_valid=a.minValid, max_iter=a.composeMaxIter, tol=a.composeTol) if a.siteCompose else None,
+            window=parse_llr_window(a.llrWindow), thr=a.llrThreshold, min_positions=a.minPositions, rescale={} if a.rescale else None,
+            fdr=None if a.fdr == 'none' else a.fdr, fdr_alpha=a.fdrAlpha, device=a.device, log=say)
+        first = _save(a, say, '_read_llr_multi.txt', readllr.write_read_llr_multi, None, res[0])
+        _save(a, say, '_site_llr_multi.txt', readllr.write_site_llr_multi, None, res[1])
+        if a.siteCompose:
+            _save(a, say, '_site_compose.txt', readllr.write_site_compose, None, res[1])
+        say('Read calls are saved in %s' % first)
+        return res
     res = readllr.call_reads_llr(reads, kmermodel.load_kmer_model(a.kmerModel), kmermodel.load_kmer_model(a.altModel),
                                  window=parse_llr_window(a.llrWindow), thr=a.llrThreshold, prior=a.prior, min_positions=a.minPositions,
                                  rescale={} if a.rescale else None, events=bool(a.outEvents), device=a.device, log=say,

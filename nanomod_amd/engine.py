@@ -816,6 +816,145 @@ def site_stoich_host(score, off, *, stride=0, min_valid=3, ci_level=0.95, max_it
     return res
 
 
+def _llr_multi_opts(window, thr, prior_logit, k, center, alt_kc, want):
+    """nmod_llr_multi_opts from the Python arguments (the window, thr and each prior through _llr_opts, K13's rules); ValueError for what
+    the C entry refuses.  alt_kc: (k, center) of every alternative table; prior_logit: None (all 0), or one value per table"""
+    n_alt = len(alt_kc)
+    if not 1 <= n_alt <= L.MULTI_MAX:
+        raise ValueError('read_llr_multi takes 1 .. %d alternative models, not %d' % (L.MULTI_MAX, n_alt))
+    prior_logit = [0.0] * n_alt if prior_logit is None else [float(v) for v in np.atleast_1d(np.asarray(prior_logit, dtype=np.float64))]
+    if len(prior_logit) != n_alt:
+        raise ValueError('prior_logit needs one value per alternative model')
+    for (ak, ac), pl in zip(alt_kc, prior_logit):
+        one, _ = _llr_opts(window, thr, pl, k, center, ak, ac, ())
+    want = tuple(want)
+    if any(w not in L.LLR_MULTI_EVENT_FIELDS for w in want):
+        raise ValueError("want must name tracks of 'llr', 'llr_win', 'post', 'call'")
+    return L.make_llr_multi_opts(one.nb_lo, one.nb_hi, one.thr, prior_logit), want
+
+
+_LLR_MULTI_PLANES = dict(llr=0, llr_win=0, post=1)           # planes of an event track beyond n_alt
+
+
+def _llr_multi_shapes(want, nval, nreads, n_alt):
+    shapes = {w: ('uint8', nval) if w == 'call' else ('float64', (n_alt + _LLR_MULTI_PLANES[w]) * nval) for w in want}
+    shapes.update(n_sites=('int32', nreads), n_can=('int32', nreads), n_mod=('int32', n_alt * nreads), status=('uint8', nreads))
+    return shapes
+
+
+def _llr_multi_views(res, nval, nreads, n_alt):
+    """the flat outputs as (planes, events) / (n_alt, nreads) views"""
+    out = dict(res)
+    for w in ('llr', 'llr_win', 'post'):
+        if w in out:
+            out[w] = out[w].reshape(n_alt + _LLR_MULTI_PLANES[w], nval)
+    out['n_mod'] = out['n_mod'].reshape(n_alt, nreads)
+    return out
+
+
+def read_llr_multi_host(val, off, base, model, alts, *, window='kmer', thr=2.5, prior_logit=None, want=('llr', 'llr_win', 'post', 'call'), device=0):
+    """Per-read log-likelihood ratios of one unmodified k-mer model against several modified ones in one walk, with a joint call and a
+    posterior over the states per event (nmod_read_llr_multi, include/nanomod_hip.h), on host-resident reads: val, off, base and model
+    as for read_llr_host; alts: 1 .. L.MULTI_MAX mappings with k, center, mean, sd (k and center as model's); prior_logit: the log
+    prior odds of each state against canonical (None: 0).  Returns a dict of numpy arrays: the tracks named in `want` — llr, llr_win
+    (float64[n_alt, events]: row m - 1 holds the bits read_llr_host gives for (model, alts[m - 1])), post (float64[n_alt + 1, events], row 0
+    canonical), call (uint8: 0 canonical, m, L.MULTI_AMBIGUOUS, L.MULTI_NONE) — and per read n_sites, n_can (int32), n_mod
+    (int32[n_alt, nreads]) and status (uint8, L.CALLS_TOO_LARGE)."""
+    lib = L.load()
+    val, dtype = _signal(val, 'val')
+    off, nreads, nev = _read_layout(val, off, 'val')
+    if model is None or alts is None or any(a is None for a in alts):
+        raise ValueError('read_llr_multi needs a k-mer model and its alternatives')
+    alts = list(alts)
+    opts, want = _llr_multi_opts(window, thr, prior_logit, int(model['k']), int(model['center']), [(int(a['k']), int(a['center'])) for a in alts], want)
+    n_alt = len(alts)
+    m0, alive0 = _host_model(model)
+    ms = [_host_model(a) for a in alts]
+    arr = L.model_ptr_array([m for m, _ in ms])
+    base = _host_base(base, nev)
+    nval = val.shape[0]
+    shapes = _llr_multi_shapes(want, nval, nreads, n_alt)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodLlrMultiOut, **_np_ptrs(res))
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=dtype)
+    _call(lib, 'nmod_read_llr_multi', prm, nreads, nval, _np_ptr(off), _np_ptr(val), _np_ptr(base), C.byref(m0), n_alt, C.addressof(arr),
+          C.byref(opts), C.byref(out))
+    res = _llr_multi_views(res, nval, nreads, n_alt)
+    lo, hi = (int(off[0]), nev) if nreads else (nval, nval)     # events outside [off[0], off[-1]) belong to no read
+    for w in want:
+        res[w][..., :lo] = L.MULTI_NONE if w == 'call' else np.nan
+        res[w][..., hi:] = L.MULTI_NONE if w == 'call' else np.nan
+    return res
+
+
+def _compose_opts(n_alt, min_valid, max_iter, tol):
+    """nmod_compose_opts from the Python arguments; ValueError for what the C entry refuses"""
+    import math
+    if not 1 <= n_alt <= L.MULTI_MAX:
+        raise ValueError('site_compose takes the scores of 1 .. %d states, not %d' % (L.MULTI_MAX, n_alt))
+    if int(min_valid) != min_valid or int(min_valid) < 1:
+        raise ValueError('min_valid must be an integer >= 1, not %r' % (min_valid,))
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= L.COMPOSE_MAX_ITER:
+        raise ValueError('max_iter must be an integer in 1 .. %d, not %r' % (L.COMPOSE_MAX_ITER, max_iter))
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError('tol must be finite and >= 0, not %r' % (tol,))
+    return L.make_compose_opts(int(max_iter), int(min_valid), tol)
+
+
+def _compose_shapes(npos, n_alt, test=True, nresp=None):
+    shapes = dict(pi=('float64', (n_alt + 1) * npos), ll=('float64', npos), stat=('float64', npos))
+    if test:
+        shapes.update(stat_m=('float64', n_alt * npos), p_m=('float64', n_alt * npos))
+    shapes.update(n_valid=('int32', npos), n_partial=('int32', npos), iters=('int32', npos), open_mask=('uint8', npos), status=('uint8', npos))
+    if nresp is not None:
+        shapes['resp'] = ('float64', (n_alt + 1) * nresp)
+    return shapes
+
+
+def _compose_views(res, npos, n_alt):
+    out = dict(res)
+    out['pi'] = out['pi'].reshape(n_alt + 1, npos)
+    for w in ('stat_m', 'p_m'):
+        if w in out:
+            out[w] = out[w].reshape(n_alt, npos)
+    if 'resp' in out:
+        out['resp'] = out['resp'].reshape(n_alt + 1, -1)
+    return out
+
+
+def site_compose_host(scores, off, *, stride=0, min_valid=3, max_iter=500, tol=1e-9, test=True, resp=False, device=0):
+    """The shares of all states per position by maximum likelihood over pivoted window sums (nmod_site_compose, include/nanomod_hip.h):
+    scores: 1 .. L.MULTI_MAX float64 vectors of one length (or a 2-d array, a row per state), all read by the one `off`
+    (int64[npos + 1]) or, with off None, a fixed `stride`.  Returns a dict of numpy arrays: pi (float64[n_alt + 1, npos], row 0
+    canonical), ll, stat; with `test` stat_m and p_m (float64[n_alt, npos]: the likelihood-ratio test of each state's share being 0,
+    an asymptotic boundary p-value); n_valid, n_partial, iters (int32); open_mask and status (uint8, L.COMPOSE_* bits); and with `resp`
+    the responsibilities of every read (float64[n_alt + 1, scores])."""
+    lib = L.load()
+    scores = [s for s in scores]
+    opts = _compose_opts(len(scores), min_valid, max_iter, tol)
+    n_alt = len(scores)
+    rows = [_host_score_rows(s, off, stride) for s in scores]
+    score0, off, stride, npos = rows[0]
+    if any(r[0].shape != score0.shape for r in rows):
+        raise ValueError('the scores of all states must have one length')
+    total = score0.shape[0]
+    shapes = _compose_shapes(npos, n_alt, test, total if resp else None)
+    res = _host_outputs(shapes, fill=shapes)
+    _join_warm_up(device)
+    out = L.make_out(L.NmodComposeOut, **_np_ptrs(res))
+    ptrs = (C.c_void_p * n_alt)(*[_np_ptr(r[0]) for r in rows])
+    prm = L.make_params(device=device, memspace=L.MEM_HOST, dtype=L.DTYPE_F64, stride0=stride if off is None else 0)
+    _call(lib, 'nmod_site_compose', prm, npos, total, n_alt, C.addressof(ptrs), _np_ptr(off), C.byref(opts), C.byref(out))
+    res = _compose_views(res, npos, n_alt)
+    if resp and off is not None:                                     # scores outside every row belong to no row
+        lo, hi = (int(off[0]), int(off[-1])) if npos else (total, total)
+        res['resp'][:, :lo] = np.nan
+        res['resp'][:, hi:] = np.nan
+    return res
+
+
 def _diff_opts(min_valid, ci_level, max_iter, tol):
     """nmod_diff_opts from the Python arguments: the checks and the conversion of ci_level are those of _stoich_opts"""
     o = _stoich_opts(min_valid, ci_level, max_iter, tol)
@@ -1842,6 +1981,64 @@ class DeviceDetector:
         prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
         _call(self.lib, 'nmod_site_stoich', prm, npos, score.data_ptr(), _ptr(off), C.byref(opts), C.byref(o))
         return res
+
+    def read_llr_multi(self, val, off, base, mean, sd, alt_means, alt_sds, k, center, *, window='kmer', thr=2.5, prior_logit=None,
+                       want=('llr', 'llr_win', 'post', 'call'), out=None):
+        """Per-read log-likelihood ratios against several modified k-mer models in one walk (nmod_read_llr_multi, NMOD_MEM_DEVICE),
+        enqueued on the current stream without synchronising or reading anything back.  val, off, base, mean, sd as for read_llr;
+        alt_means / alt_sds: 1 .. L.MULTI_MAX float64 CUDA vectors of 4^k entries each.  Returns a dict of CUDA tensors: the tracks
+        named in `want` — llr, llr_win (float64[n_alt, events]; row m - 1 holds read_llr's bits for alt m - 1 and is what pivot_reads'
+        device form takes as `val`), post (float64[n_alt + 1, events]), call (uint8) — and per read n_sites, n_can (int32), n_mod
+        (int32[n_alt, nreads]) and status (uint8).  Events outside every read keep what the tensors held (NaN / L.MULTI_NONE when they
+        are allocated here).  out: such a dict from an earlier call of the same shape."""
+        torch = self.torch
+        dtype = self._dtype_of(val)
+        alt_means, alt_sds = list(alt_means), list(alt_sds)
+        if len(alt_means) != len(alt_sds):
+            raise ValueError('read_llr_multi: one alt_sd per alt_mean')
+        opts, want = _llr_multi_opts(window, thr, prior_logit, k, center, [(k, center)] * len(alt_means), want)
+        n_alt = len(alt_means)
+        nreads = _device_offsets(torch, off, 'read_llr_multi', 'nreads')
+        m0 = _device_model(torch, 'read_llr_multi', val, base, mean, sd, k, center, one_dim=True)
+        ms = [_device_model(torch, 'read_llr_multi', val, base, am, asd, k, center, one_dim=True) for am, asd in zip(alt_means, alt_sds)]
+        arr = L.model_ptr_array(ms)
+        nval = val.numel()
+        shapes = _llr_multi_shapes(want, nval, nreads, n_alt)
+        given = None
+        if out is None:
+            given = {w: torch.full((shapes[w][1],), L.MULTI_NONE if w == 'call' else float('nan'), dtype=self._kinds[shapes[w][0]], device=self._dev)
+                     for w in want}
+        res = self._outputs({name: t.reshape(-1) for name, t in out.items()} if out is not None else None, shapes, 'read_llr_multi', given=given)
+        o = L.make_out(L.NmodLlrMultiOut, **{name: res[name].data_ptr() for name in shapes})
+        prm = self._params(dtype, 0, 0, 0, 0)
+        _call(self.lib, 'nmod_read_llr_multi', prm, nreads, nval, off.data_ptr(), val.data_ptr(), base.data_ptr(), C.byref(m0), n_alt,
+              C.addressof(arr), C.byref(opts), C.byref(o))
+        return out if out is not None else _llr_multi_views(res, nval, nreads, n_alt)
+
+    def site_compose(self, scores, *, off=None, stride=0, npos=None, min_valid=3, max_iter=500, tol=1e-9, test=True, resp=False, out=None):
+        """The shares of all states per position by maximum likelihood (nmod_site_compose, NMOD_MEM_DEVICE) on the current stream,
+        nothing read back: scores: 1 .. L.MULTI_MAX float64 CUDA vectors of one length (the pivoted llr_win planes of read_llr_multi),
+        rows by the one `off` (int64 CUDA vector) or a fixed `stride`.  Returns a dict of CUDA tensors pi (float64[n_alt + 1, npos]),
+        ll, stat, with `test` stat_m and p_m (float64[n_alt, npos]), n_valid, n_partial, iters (int32), open_mask, status (uint8,
+        L.COMPOSE_* bits) and with `resp` the responsibilities (float64[n_alt + 1, scores]; a score outside every row keeps NaN).  A row
+        of p_m is a track fdr() takes."""
+        torch = self.torch
+        scores = list(scores)
+        opts = _compose_opts(len(scores), min_valid, max_iter, tol)
+        n_alt = len(scores)
+        for s in scores:
+            stride, n = self._score_rows('site_compose', s, off, stride, npos)
+            if s.numel() != scores[0].numel():
+                raise ValueError('site_compose: the scores of all states must have one length')
+        npos, total = n, scores[0].numel()
+        shapes = _compose_shapes(npos, n_alt, test, total if resp else None)
+        given = {'resp': torch.full((shapes['resp'][1],), float('nan'), dtype=torch.float64, device=self._dev)} if resp and out is None else None
+        res = self._outputs({name: t.reshape(-1) for name, t in out.items()} if out is not None else None, shapes, 'site_compose', given=given)
+        o = L.make_out(L.NmodComposeOut, **{name: res[name].data_ptr() for name in shapes})
+        ptrs = (C.c_void_p * n_alt)(*[s.data_ptr() for s in scores])
+        prm = self._params(L.DTYPE_F64, stride if off is None else 0, 0, 0, 0)
+        _call(self.lib, 'nmod_site_compose', prm, npos, total, n_alt, C.addressof(ptrs), _ptr(off), C.byref(opts), C.byref(o))
+        return out if out is not None else _compose_views(res, npos, n_alt)
 
     def site_diff(self, score0, score1, *, off0=None, off1=None, stride0=0, stride1=0, npos=None, min_valid=3, ci_level=0.95, max_iter=60,
                   tol=1e-12, interval=True, out=None):

@@ -28,6 +28,7 @@ from . import engine
 from . import rescale as _rescale
 from . import tables as T
 from .sitemod import moderated_entry, write_site_diff_mod         # (K25: the moderated chain step and the writer of its two files)
+from .multimod import call_reads_llr_multi, write_read_llr_multi, write_site_llr_multi, write_site_compose   # (K26: several modified tables at once)
 from .readcalls import _RESCALE_KEYS, _checked_reads, _known_options, _open_device, _pivot_sites, _read_table, _upload_rescaled
 
 
